@@ -8,10 +8,16 @@ n=4096 x 4 RNS primes (the four largest 60-bit primes = 1 mod 8192) x batch 4096
 independent, so N GPUs run N shards with no collective on the data path (weak scaling:
 fixed work per GPU); the only communication is the barrier / max-reduce of the timing.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1 is launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, clock ramp, W warm-up steps, the K timed steps, the
+outputs of the last step if --dump-outputs is given, the JSON line.  --full adds everything else: the round-trip
+guard before timing, power / clock samples (`power`, `roofline.bound_note`), the secondary lines (other
+operations, sizes and moduli, N = 1) and the CPU baseline (N = 1); --no-secondary / --no-cpu-baseline drop
+those two from a --full run.
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ PRIME_BITS = 60
 BATCH_PER_GPU = 4096
 NUM_SLABS = 4
 RAMP_SECONDS = 0.5                        # set-up work that brings the GPU clock out of idle (see main)
+DUMP_FRAMES = 512                         # --dump-outputs: frames sampled from the last step's slab (2 x 16 MiB of float64)
 HBM_PEAK_GBS = 8000.0                     # MI355X_MICROARCH.md: 8.0 TB/s spec
 ALGO_BYTES_PER_NTT = 16 * N_COEFF         # read 8n + write 8n
 
@@ -307,6 +314,22 @@ def bound_note(power, value_per_gpu):
                     "value_over_value_at_cap ~ 1 means the kernel is power-bound (DESIGN.md 3.5)"}
 
 
+def dump_outputs(torch, out_dir, slab, frames):
+    """--dump-outputs DIR: what the last timed step handed its caller -- the forward NTT of one slab, in place, uint64 residues
+    below q < 2^60 -- as a fixed sample of whole frames (frame f = prime f // batch, polynomial f % batch of this shard; all
+    frames when there are at most DUMP_FRAMES, else DUMP_FRAMES of them picked by a seeded generator, in ascending order).
+    float64 holds 53 bits, so each residue x is split exactly: forward_hi32.npy = x >> 32, forward_lo32.npy = x & 0xffffffff,
+    both [frames, n] float64."""
+    import numpy as np
+
+    pick = np.arange(frames) if frames <= DUMP_FRAMES else np.sort(np.random.default_rng(0).choice(frames, DUMP_FRAMES, replace=False))
+    idx = torch.from_numpy(pick).to(slab.device)
+    got = slab.view(frames, N_COEFF).index_select(0, idx).cpu().numpy().view(np.uint64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "forward_hi32.npy"), (got >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(out_dir, "forward_lo32.npy"), (got & np.uint64(0xFFFFFFFF)).astype(np.float64))
+
+
 def main_group(args, torch, agx):
     """--single-process: the same step on N devices through agx_ntt_group_* (include/agx_ntt.h section 5).  One process, no
     torch.distributed: the group's host threads launch every shard on its own stream; the timed region is bracketed by
@@ -325,36 +348,45 @@ def main_group(args, torch, agx):
         torch.cuda.set_device(d)
         _, plan_h, stream_h = grp.shard(i)
         ext.append(torch.cuda.ExternalStream(stream_h, device=torch.device("cuda", d)))
-        mine = [torch.empty(per_slab, dtype=torch.int64, device=f"cuda:{d}") for _ in range(NUM_SLABS)]
-        for k, sl in enumerate(mine):
-            rc = L.agx_ntt_fill_synthetic(plan_h, sl.data_ptr(), batch, (k * world + i) * batch, 42, stream_h)
-            if rc:
-                raise SystemExit(f"fill_synthetic failed on shard {i}: {rc}")
-        slabs.append(mine)
-    grp.synchronize()
-    # correctness guard before timing: INTT(NTT(x)) == x on slab 0 of every shard, through the group calls
-    checks = []
-    for i, d in enumerate(devices):
-        torch.cuda.set_device(d)
-        checks.append(slabs[i][0].clone())
-    torch.cuda.synchronize()
-    grp.forward([c.data_ptr() for c in checks], [c.data_ptr() for c in checks], [batch] * world)
-    grp.inverse([c.data_ptr() for c in checks], [c.data_ptr() for c in checks], [batch] * world)
-    grp.synchronize()
-    for i in range(world):
-        if not torch.equal(checks[i], slabs[i][0]):
-            raise SystemExit(f"round trip failed on shard {i}: refusing to report a number")
-    del checks
+        slabs.append([torch.empty(per_slab, dtype=torch.int64, device=f"cuda:{d}") for _ in range(NUM_SLABS)])
+
+    def fill():
+        for i in range(world):
+            torch.cuda.set_device(devices[i])
+            _, plan_h, stream_h = grp.shard(i)
+            for k, sl in enumerate(slabs[i]):
+                rc = L.agx_ntt_fill_synthetic(plan_h, sl.data_ptr(), batch, (k * world + i) * batch, 42, stream_h)
+                if rc:
+                    raise SystemExit(f"fill_synthetic failed on shard {i}: {rc}")
+        grp.synchronize()
+
+    fill()
+    if args.full:
+        # correctness guard before timing: INTT(NTT(x)) == x on slab 0 of every shard, through the group calls
+        checks = []
+        for i, d in enumerate(devices):
+            torch.cuda.set_device(d)
+            checks.append(slabs[i][0].clone())
+        torch.cuda.synchronize()
+        grp.forward([c.data_ptr() for c in checks], [c.data_ptr() for c in checks], [batch] * world)
+        grp.inverse([c.data_ptr() for c in checks], [c.data_ptr() for c in checks], [batch] * world)
+        grp.synchronize()
+        for i in range(world):
+            if not torch.equal(checks[i], slabs[i][0]):
+                raise SystemExit(f"round trip failed on shard {i}: refusing to report a number")
+        del checks
     batches = [batch] * world
 
     def step(it):
         ptrs = [slabs[i][it % NUM_SLABS].data_ptr() for i in range(world)]
         grp.forward(ptrs, ptrs, batches)
 
-    sampler = PowerSampler(torch, devices[0])
-    t_idle0 = time.perf_counter()
-    time.sleep(0.4)
-    idle_w = sampler.median_w(t_idle0, time.perf_counter())
+    sampler = PowerSampler(torch, devices[0]) if args.full else None
+    idle_w = None
+    if sampler:
+        t_idle0 = time.perf_counter()
+        time.sleep(0.4)
+        idle_w = sampler.median_w(t_idle0, time.perf_counter())
     t_busy0 = time.perf_counter() + 0.2
     ramp_steps = 0
     t_end = time.perf_counter() + args.ramp_seconds
@@ -363,6 +395,7 @@ def main_group(args, torch, agx):
             step(ramp_steps)
             ramp_steps += 1
         grp.synchronize()
+    fill()      # the ramp's step count follows the clock: the W + K steps start from the same data in every run
     for i in range(args.warmup):
         step(i)
     grp.synchronize()      # the barrier: every shard idle
@@ -380,7 +413,10 @@ def main_group(args, torch, agx):
     grp.synchronize()
     elapsed = time.perf_counter() - t0      # all shards: the slowest one defines it
     t_busy1 = time.perf_counter()
-    power = sampler.window(t_busy0, t_busy1)
+    power = sampler.window(t_busy0, t_busy1) if sampler else None
+    if args.dump_outputs:
+        torch.cuda.set_device(devices[0])
+        dump_outputs(torch, args.dump_outputs, slabs[0][(args.warmup + args.steps - 1) % NUM_SLABS], NUM_PRIMES * batch)
     kernel_ms = [ev[i][0].elapsed_time(ev[i][1]) / args.steps for i in range(world)]
     per_rank = [{"rank": i, "device": devices[i], "elapsed_s": kernel_ms[i] * args.steps * 1e-3, "kernel_ms": kernel_ms[i],
                  "socket_power_w_median": power["socket_power_w_median"] if (power and devices[i] == devices[0]) else None,
@@ -418,7 +454,8 @@ def main_group(args, torch, agx):
         out["roofline"]["bound_note"] = note
     if power:
         out["power"] = power
-    sampler.stop()
+    if sampler:
+        sampler.stop()
     print(json.dumps(out), flush=True)
     grp.close()
 
@@ -435,8 +472,12 @@ def main():
                     help="drive the N GPUs from ONE process through the library's own multi-GPU driver (agx_ntt_group_*: one shard, host thread and "
                          "stream per device, no torch.distributed); same JSON line, per_rank from per-device HIP events")
     ap.add_argument("--devices", type=str, default=None, help="with --single-process: explicit device list, e.g. 0,0 (two shards on one GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (inverse, poly-mul, n=16384, n=32768)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: round-trip guard, power / clock samples, secondary lines and CPU baseline (the last two at N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's output to DIR/*.npy (float64; rank / shard 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary lines (inverse, poly-mul, n=16384, n=32768)")
     args = ap.parse_args()
 
     import torch
@@ -467,17 +508,21 @@ def main():
     stream = torch.cuda.current_stream().cuda_stream
     # this rank's shard of the global batch: polynomials [rank*batch, (rank+1)*batch) of every slab
     slabs = [torch.empty(per_slab, dtype=torch.int64, device="cuda") for _ in range(NUM_SLABS)]
-    for i, s in enumerate(slabs):
-        plan.fill_synthetic(s.data_ptr(), batch, first_poly=(i * world + rank) * batch, seed=42, stream=stream)
 
-    # correctness guard on real data before timing: INTT(NTT(x)) == x on slab 0 (product path only)
-    check = slabs[0].clone()
-    plan.forward(check.data_ptr(), check.data_ptr(), batch, stream)
-    plan.inverse(check.data_ptr(), check.data_ptr(), batch, stream)
-    torch.cuda.synchronize()
-    if not torch.equal(check, slabs[0]):
-        raise SystemExit("round trip failed: refusing to report a number")
-    del check
+    def fill():
+        for i, s in enumerate(slabs):
+            plan.fill_synthetic(s.data_ptr(), batch, first_poly=(i * world + rank) * batch, seed=42, stream=stream)
+
+    fill()
+    if args.full:
+        # correctness guard on real data before timing: INTT(NTT(x)) == x on slab 0 (product path only)
+        check = slabs[0].clone()
+        plan.forward(check.data_ptr(), check.data_ptr(), batch, stream)
+        plan.inverse(check.data_ptr(), check.data_ptr(), batch, stream)
+        torch.cuda.synchronize()
+        if not torch.equal(check, slabs[0]):
+            raise SystemExit("round trip failed: refusing to report a number")
+        del check
 
     def step(i):
         s = slabs[i % NUM_SLABS]
@@ -490,11 +535,14 @@ def main():
     # follow unchanged.  The first barrier here also pays RCCL's communicator set-up outside the timing.
     grp.barrier()
     torch.cuda.synchronize()
-    sampler = PowerSampler(torch, dev_index)       # every rank samples its own GPU (per_rank below); rank 0's goes into `power`
-    # idle socket power: 0.4 s with nothing queued, before the ramp (the baseline of energy_uj_per_ntt)
-    t_idle0 = time.perf_counter()
-    time.sleep(0.4)
-    idle_w = sampler.median_w(t_idle0, time.perf_counter())
+    # --full: every rank samples its own GPU (per_rank below); rank 0's goes into `power`
+    sampler = PowerSampler(torch, dev_index) if args.full else None
+    idle_w = None
+    if sampler:
+        # idle socket power: 0.4 s with nothing queued, before the ramp (the baseline of energy_uj_per_ntt)
+        t_idle0 = time.perf_counter()
+        time.sleep(0.4)
+        idle_w = sampler.median_w(t_idle0, time.perf_counter())
     t_busy0 = time.perf_counter() + 0.2     # skip the first 200 ms (idle -> ramp)
     ramp_steps = 0
     t_end = time.perf_counter() + args.ramp_seconds
@@ -503,6 +551,7 @@ def main():
             step(ramp_steps)
             ramp_steps += 1
         torch.cuda.synchronize()
+    fill()      # the ramp's step count follows the clock: the W + K steps start from the same data in every run
 
     for i in range(args.warmup):
         step(i)
@@ -518,7 +567,9 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0     # this rank's K steps; the slowest rank defines the job (MAX below)
     t_busy1 = time.perf_counter()
-    power = sampler.window(t_busy0, t_busy1)
+    power = sampler.window(t_busy0, t_busy1) if sampler else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, slabs[(args.warmup + args.steps - 1) % NUM_SLABS], NUM_PRIMES * batch)
     grp.barrier()
     torch.cuda.synchronize()
     kernel_ms = ev0.elapsed_time(ev1) / args.steps   # average launch duration over the timed region
@@ -580,10 +631,11 @@ def main():
         out["roofline"]["bound_note"] = note      # the three numbers the "power-bound" argument rests on, measured in this run
     if power and rank == 0:
         out["power"] = power
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         out["secondary"] = secondary_lines(torch, agx, plan, slabs, batch, stream, sampler, idle_w)
-    sampler.stop()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if sampler:
+        sampler.stop()
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(out), flush=True)
