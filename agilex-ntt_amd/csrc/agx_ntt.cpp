@@ -276,20 +276,19 @@ int build_plan(agx_ntt_plan** out, uint32_t n, uint32_t num_primes, const uint64
     return instantiate_plan(out, img);
 }
 
-// Do two frame sets of the same shape -- frame (p, b) at base + p prime_stride + b poly_stride, n elements each -- overlap without being
-// the same set?  Identical bases are in place (legal: a workgroup reads its frame before it writes it); otherwise NO frame of one may
-// touch any frame of the other, because workgroups run in any order (include/agx_ntt.h: AGX_ERR_BAD_ARGUMENT "overlapping in/out").
-// Interleaved layouts whose frames do not touch (out = in + n with poly_stride = 2n) are legal and pass.
-bool partial_overlap(const void* a, const void* b, uint32_t n, uint32_t num_primes, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
-    if (a == b || batch == 0) return false;
-    const int64_t delta = (int64_t)((reinterpret_cast<intptr_t>(b) - reinterpret_cast<intptr_t>(a)) / (intptr_t)sizeof(uint64_t));     // elements (both 8-byte aligned)
-    const int64_t extent = (int64_t)(num_primes - 1) * prime_stride + (int64_t)(batch - 1) * poly_stride + (int64_t)n;
-    if (delta >= extent || -delta >= extent) return false;      // disjoint ranges
-    // frames i of A and j of B touch iff |delta + dp prime_stride + db poly_stride| < n for their index differences (dp, db)
+// Does any frame of set A touch a frame of set B = A shifted by delta elements?  Frame (p, b) lies at base + p prime_stride + b poly_stride,
+// n elements long; frames i of A and j of B touch iff |delta + dp prime_stride + db poly_stride| < n for their index differences
+// (dp, db).  skip_self excludes (dp, db) = (0, 0) when delta = 0: a frame does not collide with itself.
+bool frames_touch(int64_t delta, bool skip_self, uint32_t n, uint32_t num_primes, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
     const int64_t P = (int64_t)num_primes, B = (int64_t)batch;
     for (int64_t dp = -(P - 1); dp <= P - 1; ++dp) {
         const int64_t base = delta + dp * prime_stride;
+        const bool self_row = skip_self && dp == 0;
         if (poly_stride == 0 || B == 1) {
+            if (self_row) {
+                if (B > 1) return true;      // poly_stride 0: frames (p, 0) and (p, 1) are the same words
+                continue;
+            }
             if (base > -(int64_t)n && base < (int64_t)n) return true;
             continue;
         }
@@ -297,11 +296,37 @@ bool partial_overlap(const void* a, const void* b, uint32_t n, uint32_t num_prim
         int64_t d0 = -base / poly_stride;
         for (int64_t db = d0 - 1; db <= d0 + 1; ++db) {
             const int64_t dbc = std::max<int64_t>(-(B - 1), std::min<int64_t>(B - 1, db));
+            if (self_row && dbc == 0) continue;
             const int64_t v = base + dbc * poly_stride;
             if (v > -(int64_t)n && v < (int64_t)n) return true;
         }
     }
     return false;
+}
+
+// Do two frame sets of the same shape overlap without being the same set?  Identical bases are in place (legal: a workgroup reads its
+// frame before it writes it); otherwise NO frame of one may touch any frame of the other, because workgroups run in any order
+// (include/agx_ntt.h: AGX_ERR_BAD_ARGUMENT "overlapping in/out").  Interleaved layouts whose frames do not touch (out = in + n with
+// poly_stride = 2n) are legal and pass.
+bool partial_overlap(const void* a, const void* b, uint32_t n, uint32_t num_primes, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
+    if (a == b || batch == 0) return false;
+    const int64_t delta = (int64_t)((reinterpret_cast<intptr_t>(b) - reinterpret_cast<intptr_t>(a)) / (intptr_t)sizeof(uint64_t));     // elements (both 8-byte aligned)
+    const int64_t extent = (int64_t)(num_primes - 1) * prime_stride + (int64_t)(batch - 1) * poly_stride + (int64_t)n;
+    if (delta >= extent || -delta >= extent) return false;      // disjoint ranges
+    return frames_touch(delta, false, n, num_primes, batch, prime_stride, poly_stride);
+}
+
+// Does one frame set overlap itself (two distinct frames (p, b) != (p', b') touch)?  Two workgroups would then transform the same words
+// in place, under different moduli for dp != 0: garbage.  The dense [prime][batch][n] layout and the [poly][prime][n] layout answer in
+// O(1) (no loop on the latency path); anything else takes frames_touch's closest-db search with delta = 0.
+bool self_overlap(uint32_t n, uint32_t num_primes, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
+    if (batch == 0 || (num_primes == 1 && batch == 1)) return false;
+    const int64_t N = (int64_t)n, P = (int64_t)num_primes, B = (int64_t)batch;
+    // prime-major: batches of one prime are n apart, primes clear the whole batch
+    if ((B == 1 || poly_stride >= N) && (P == 1 || prime_stride >= (B - 1) * poly_stride + N)) return false;
+    // poly-major: primes of one polynomial are n apart, polynomials clear every prime
+    if ((P == 1 || prime_stride >= N) && (B == 1 || poly_stride >= (P - 1) * prime_stride + N)) return false;
+    return frames_touch(0, true, n, num_primes, batch, prime_stride, poly_stride);
 }
 
 int check_call(const agx_ntt_plan* plan, const void* a, const void* b, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
@@ -310,6 +335,7 @@ int check_call(const agx_ntt_plan* plan, const void* a, const void* b, uint64_t 
     if (hipGetDevice(&dev) != hipSuccess || dev != plan->device) return AGX_ERR_BAD_ARGUMENT;   // the plan's tables live on plan->device
     if (prime_stride < 0 || poly_stride < 0) return AGX_ERR_BAD_ARGUMENT;
     if (batch > 1 && poly_stride < (int64_t)plan->n) return AGX_ERR_BAD_ARGUMENT;   // frames would overlap
+    if (self_overlap(plan->n, plan->num_primes, batch, prime_stride, poly_stride)) return AGX_ERR_BAD_ARGUMENT;   // (p, b) and (p', b') share words
     if ((batch << (plan->log_n > 14 ? plan->log_n - 14 : 0)) > 0x7fffffffull) return AGX_ERR_BAD_ARGUMENT;  // grid.x limit (the radix-2 kernels split n = 32768 in two blocks)
     if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7u) != 0) return AGX_ERR_BAD_ARGUMENT;      // uint64_t data
     if (partial_overlap(a, b, plan->n, plan->num_primes, batch, prime_stride, poly_stride)) return AGX_ERR_BAD_ARGUMENT;

@@ -135,7 +135,11 @@ AGX_API int agx_ntt_plan_get_modulus(const agx_ntt_plan* plan, uint32_t prime_in
 /* poly_stride = n).  In place (d_out == d_in) is allowed; an output whose     */
 /* frames touch the input's frames without being the same frames (d_out =      */
 /* d_in + n/2, c = a + 8 ...) returns AGX_ERR_BAD_ARGUMENT: workgroups run in  */
-/* any order, so such a call would corrupt its own inputs.  Asynchronous on    */
+/* any order, so such a call would corrupt its own inputs.  A layout whose     */
+/* own frames touch one another (two distinct (p, b) less than n elements      */
+/* apart: prime_stride = 0 with two primes, prime_stride = poly_stride = n     */
+/* with two polynomials, ...) returns AGX_ERR_BAD_ARGUMENT too: two workgroups */
+/* would transform the same words under different moduli.  Asynchronous on    */
 /* `stream`; nothing is allocated or synchronised inside, so the calls can be  */
 /* captured into a hipGraph (kernels that hand out frames through a counter    */
 /* switch to a stateless form while the stream is capturing).                   */

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from gpu_util import oracle_polymul as _oracle_polymul
 from gpu_util import rand_coeffs, tables_for
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +72,51 @@ def test_forward_bit_exact(agx, orc, dev, n, variant):
     # in place
     plan.forward(d_in.data_ptr(), d_in.data_ptr(), batch, dev.stream)
     assert np.array_equal(dev.to_host(d_in), want)
+    plan.close()
+
+
+RADIX2_CASES = [(n, 60) for n in ALL_SIZES] + [(4, 30), (32, 30), (1024, 30), (32768, 30), (2, 62), (512, 62), (4096, 62), (16384, 62)]
+
+
+@pytest.mark.parametrize("n,bits", RADIX2_CASES)
+def test_radix2_inverse_and_product_bit_exact(agx, orc, dev, n, bits):
+    """the radix-2 LDS kernels other tests use as an independent twin: inverse (inv_radix2_lds) on arbitrary data in [0,4q) against the
+    oracle's inverse, and the three-launch product (forward, forward, pointwise, inverse through caller scratch) with c distinct,
+    c aliasing a and c aliasing b against the schoolbook product (n <= 1024) or the oracle's NTT pipeline; ragged batch, two primes"""
+    batch = 5 if n <= 4096 else 3
+    primes = 2
+    plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, primes)
+    plan.set_variant(agx.VARIANT_LDS_RADIX2)
+    rng = np.random.default_rng(n * 5 + bits)
+    x = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4) for t in tabs])
+    d_x, d_y = dev.to_device(x), dev.empty(x.size)
+    plan.inverse(d_x.data_ptr(), d_y.data_ptr(), batch, dev.stream)
+    want = np.empty_like(x)
+    for p, t in enumerate(tabs):
+        sl = slice(p * batch * n, (p + 1) * batch * n)
+        want[sl] = orc.inverse(x[sl] % np.uint64(t[0]), t[0], orc.make_inv_tables(t[0], t[1], n)[0], n)
+    assert np.array_equal(dev.to_host(d_y), want)
+    assert np.array_equal(dev.to_host(d_x), x), "input must not be modified"
+    plan.inverse(d_x.data_ptr(), d_x.data_ptr(), batch, dev.stream)           # in place
+    assert np.array_equal(dev.to_host(d_x), want)
+
+    a = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4) for t in tabs])
+    b = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4) for t in tabs])
+    prod = np.empty_like(a)
+    for p, t in enumerate(tabs):
+        for f in range(batch):
+            sl = slice((p * batch + f) * n, (p * batch + f + 1) * n)
+            prod[sl] = (orc.schoolbook(a[sl] % np.uint64(t[0]), b[sl] % np.uint64(t[0]), t[0], n) if n <= 1024
+                        else _oracle_polymul(orc, a[sl], b[sl], t[0], t[1], n))
+    d_a, d_b, d_c, d_s = dev.to_device(a), dev.to_device(b), dev.empty(a.size), dev.empty(a.size)
+    plan.polymul(d_a.data_ptr(), d_b.data_ptr(), d_c.data_ptr(), d_s.data_ptr(), batch, dev.stream)
+    assert np.array_equal(dev.to_host(d_c), prod)
+    assert np.array_equal(dev.to_host(d_a), a) and np.array_equal(dev.to_host(d_b), b)      # operands untouched
+    plan.polymul(d_a.data_ptr(), d_b.data_ptr(), d_a.data_ptr(), d_s.data_ptr(), batch, dev.stream)   # c aliasing a
+    assert np.array_equal(dev.to_host(d_a), prod)
+    d_a = dev.to_device(a)
+    plan.polymul(d_a.data_ptr(), d_b.data_ptr(), d_b.data_ptr(), d_s.data_ptr(), batch, dev.stream)   # c aliasing b
+    assert np.array_equal(dev.to_host(d_b), prod)
     plan.close()
 
 
@@ -675,15 +721,6 @@ def test_config5_polymul_32768(agx, orc, dev):
     want = orc.inverse(orc.pointwise(orc.forward(a2, q, tw, pre, n), orc.forward(b[:n], q, tw, pre, n), q), q, itw, n)
     assert np.array_equal(dev.to_host(d_c)[:n], want)
     plan.close()
-
-
-def _oracle_polymul(orc, a, b, q, psi, n):
-    """INTT(NTT(a) o NTT(b)) through the oracle's own transforms, frame by frame"""
-    tw, pre = orc.make_tables(q, psi, n)
-    itw, _ = orc.make_inv_tables(q, psi, n)
-    fa = orc.forward(a % np.uint64(q), q, tw, pre, n)
-    fb = orc.forward(b % np.uint64(q), q, tw, pre, n)
-    return orc.inverse(orc.pointwise(fa, fb, q), q, itw, n)
 
 
 @pytest.mark.parametrize("bits", [60, 61, 62])
