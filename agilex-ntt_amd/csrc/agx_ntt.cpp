@@ -514,7 +514,7 @@ static int plan_set_variant_impl(agx_ntt_plan* plan, int variant) {
         const regblock_layout rb = regblock_choose(plan->n, config_id, plan->arith_level, plan->narrow_level);
         if (!rb.valid()) {
             if (variant == AGX_VARIANT_REGBLOCK) return AGX_ERR_BAD_SIZE;
-        } else if (rb.config_id != plan->rb.config_id) {
+        } else if (rb.entry != plan->rb.entry) {
             std::vector<uint64_t> w(plan->n), wp(plan->n);
             ulonglong2* d_new[2] = {nullptr, nullptr};
             const ulonglong2* d_src[2] = {plan->d_tw, plan->d_itw};

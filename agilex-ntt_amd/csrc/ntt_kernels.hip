@@ -274,25 +274,19 @@ regblock_layout regblock_choose(uint32_t n, int config_id, int arith_level, int 
             if (c && c->log_n == log_n && legal(*c)) { e = c; break; }
         }
     }
-    if (!e) return rb;
-    rb.config_id = e->id;
-    rb.log_n = log_n;
-    rb.r = e->r;
-    rb.pairs_per_prime = e->table_pairs;
+    rb.entry = e;
     return rb;
 }
 
 regblock_layout regblock_forward_companion(const regblock_layout& main, uint32_t n, int arith_level, int narrow_level) {
-    const rb_entry* e = main.valid() ? rb_lookup(main.config_id) : nullptr;
-    if (!e || e->fwd_companion <= 0) return regblock_layout{};
-    regblock_layout rb = regblock_choose(n, e->fwd_companion, arith_level, narrow_level);
-    rb.min_frames = e->fwd_companion_min_frames;
+    if (!main.valid() || main.entry->fwd_companion <= 0) return regblock_layout{};
+    regblock_layout rb = regblock_choose(n, main.entry->fwd_companion, arith_level, narrow_level);
+    rb.min_frames = main.entry->fwd_companion_min_frames;
     return rb;
 }
 
 void regblock_build_table(const regblock_layout& rb, const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
-    const rb_entry* e = rb_lookup(rb.config_id);
-    if (e) e->build(rb, tw, pre, out);
+    if (rb.valid()) rb.entry->build(tw, pre, out);
 }
 
 hipError_t kernels_init() {
@@ -342,31 +336,22 @@ hipError_t launch_inverse_radix2(const plan_view& pv, const uint64_t* in, uint64
 }
 
 hipError_t launch_forward_regblock(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    const rb_entry* e = pv.rb.valid() ? rb_lookup(pv.rb.config_id) : nullptr;
-    if (!e) return hipErrorInvalidValue;
-    return e->launch(pv, in, out, fl, s);
+    if (!pv.rb.valid()) return hipErrorInvalidValue;
+    return pv.rb.entry->launch(pv, in, out, fl, s);
 }
 
-bool regblock_has_inverse(const regblock_layout& rb) {
-    const rb_entry* e = rb_lookup(rb.config_id);
-    return e && e->launch_inv;
-}
+bool regblock_has_inverse(const regblock_layout& rb) { return rb.valid() && rb.entry->launch_inv; }
 
-bool regblock_has_polymul(const regblock_layout& rb) {
-    const rb_entry* e = rb_lookup(rb.config_id);
-    return e && e->launch_mul;
-}
+bool regblock_has_polymul(const regblock_layout& rb) { return rb.valid() && rb.entry->launch_mul; }
 
 hipError_t launch_inverse_regblock(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    const rb_entry* e = rb_lookup(pv.rb.config_id);
-    if (!e || !e->launch_inv || !pv.itw_rb) return hipErrorInvalidValue;
-    return e->launch_inv(pv, in, in2, out, fl, s);
+    if (!regblock_has_inverse(pv.rb) || !pv.itw_rb) return hipErrorInvalidValue;
+    return pv.rb.entry->launch_inv(pv, in, in2, out, fl, s);
 }
 
 hipError_t launch_polymul_regblock(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
-    const rb_entry* e = rb_lookup(pv.rb.config_id);
-    if (!e || !e->launch_mul || !pv.itw_rb) return hipErrorInvalidValue;
-    return e->launch_mul(pv, a, b, c, fl, s);
+    if (!regblock_has_polymul(pv.rb) || !pv.itw_rb) return hipErrorInvalidValue;
+    return pv.rb.entry->launch_mul(pv, a, b, c, fl, s);
 }
 
 hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {

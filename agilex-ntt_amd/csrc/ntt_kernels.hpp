@@ -15,14 +15,14 @@ struct prime_consts {           // one per prime, device array
     uint64_t est;               // low word: float slightly below 2^32 / q for reduce_final_est, 0 when q < 2^58
 };
 
-// geometry of one register-blocked configuration (compile-time L, R mirrored at run time)
+struct rb_entry;   // one configuration of the kernel registry (rb_registry.hpp)
+
+// the register-blocked configuration a plan runs: its registry entry (static storage, valid for the life of the library), resolved once
+// by regblock_choose; everything about the configuration (id, log_n, r, table length per prime) is read from the entry
 struct regblock_layout {
-    int log_n = 0;       // whole transform = the frame one workgroup (or one wave's group of lanes) holds
-    int r = 0;           // log2 coefficients per thread
-    int config_id = -1;  // entry of the kernel registry in ntt_kernels.hip
-    uint32_t pairs_per_prime = 0;  // table length per prime, in {w,w'} pairs
-    uint32_t min_frames = 0;       // forward companions: only launches of at least this many frames take this layout
-    bool valid() const { return r > 0; }
+    const rb_entry* entry = nullptr;
+    uint32_t min_frames = 0;       // forward companions: only launches of at least this many frames take this layout (set by the main entry)
+    bool valid() const { return entry != nullptr; }
 };
 
 // device-side view of a plan
@@ -32,7 +32,7 @@ struct plan_view {
     const ulonglong2* tw = nullptr;        // [P][n] {w,w'} natural index   (forward)
     const ulonglong2* itw = nullptr;       // [P][n] {w,w'} natural index   (inverse) or null
     regblock_layout rb;                    // forward register-blocked layout
-    const ulonglong2* tw_rb = nullptr;     // [P][rb.pairs_per_prime]
+    const ulonglong2* tw_rb = nullptr;     // [P][rb.entry->table_pairs]
     const ulonglong2* itw_rb = nullptr;    // same layout from the inverse tables, or null
     // Kernels that hand out frames through a counter ask for a {next frame, retired workgroups} pair of the plan HERE, at launch time and
     // only if they need one: the pair is keyed by the stream (launches on one stream serialise, so they may share a pair; the last
@@ -51,7 +51,7 @@ struct frame_layout {
 };
 
 // host-side construction of the register-blocked forward table for one prime from its
-// natural-index tables; appends rb.pairs_per_prime pairs to `out`
+// natural-index tables; appends rb.entry->table_pairs pairs to `out`
 // config_id -1: tuned default for n; arith_level: 0 exact only, 1 every modulus <= 2^61 (fast form legal),
 // 2 every modulus <= 2^60 (16q-lazy form legal)
 // narrow_level: 0 some modulus >= 2^31; 1 every modulus < 2^31; 2 every modulus < 2^30 (the 32-bit kernels of rb32_kernels.hpp; they

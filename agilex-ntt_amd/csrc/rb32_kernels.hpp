@@ -353,87 +353,36 @@ polymul_q32(const uint64_t* __restrict__ pa, const uint64_t* __restrict__ pb, ui
     }
 }
 
-// ---- host side: table, launches, registry entry ------------------------------------------------------------------------------
-// same geometry as build_table_t<L, R, true> (wave-uniform passes keep one column's C entries contiguous, per-lane passes one
-// entry's columns), entries {w, precon >> 32}; appended to `out` as raw bytes (two entries per ulonglong2)
+// ---- host side: table and registry entry (the launch glue is rb_kernels.hpp's) ------------------------------------------------------------
+// build_table_t's geometry (for_each_table_slot), entries {w, precon >> 32}; appended to `out` as raw bytes (two entries per ulonglong2)
 template <int L, int R>
-void build_table32_t(const regblock_layout&, const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
+void build_table32_t(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
     using G = rb_geom<L, R>;
     static_assert(G::table_pairs % 2 == 0, "two 8-byte entries per 16-byte slot");
     std::vector<uint2> t((size_t)G::table_pairs, make_uint2(0, 0));
-    for (int p = 0; p < G::NP; ++p) {
-        const int rlo = G::rlo(p), hi = G::hi(p), H = G::H(p);
-        uint2* tp = t.data() + G::table_off(p);
-        for (int j = 1; j < G::C; ++j) {
-            int k = 0;
-            while ((2 << k) <= j) ++k;
-            const int o = j - (1 << k), rb_bit = R - 1 - k, b = rlo + rb_bit;
-            if (b > hi) continue;      // stage belongs to an earlier pass (short last pass)
-            const uint32_t m_local = 1u << (L - 1 - b);
-            for (int h = 0; h < H; ++h) {
-                const uint32_t idx = m_local + ((uint32_t)h << k) + (uint32_t)o;      // natural twiddle index m + i (ntt.cpp:298-300)
-                const size_t at = rb2_geom<L, R>::uniform_pass(p) ? (size_t)h * G::C + j : (size_t)j * H + h;
-                tp[at] = make_uint2((uint32_t)tw[idx], (uint32_t)(pre[idx] >> 32));
-            }
-        }
-    }
+    for_each_table_slot<L, R>([&](size_t at, uint32_t idx) { t[at] = make_uint2((uint32_t)tw[idx], (uint32_t)(pre[idx] >> 32)); });
     const size_t start = out.size();
     out.resize(start + (size_t)G::table_pairs / 2);
     std::memcpy(out.data() + start, t.data(), t.size() * sizeof(uint2));
 }
 
-template <int L, int R, int PPB>
-constexpr size_t q32_lds_bytes() { return (size_t)((1u << L) + (1u << (L - 5))) * 4 * PPB; }
-
-inline uint32_t q32_flags(const void* a, const void* b, const void* c, const frame_layout& fl) {
-    const bool aligned = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0 && ((fl.prime_stride | fl.poly_stride) & 1) == 0;
-    return (fl.lazy_out ? 1u : 0u) | (aligned ? 2u : 0u);
-}
-
-template <int L, int R, int PPB, int TIER, int MINW>
-hipError_t launch_q32_t(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
-    dim3 grid((unsigned)((fl.batch + PPB - 1) / PPB), pv.num_primes);
-    const size_t lds = q32_lds_bytes<L, R, PPB>();
-    hipLaunchKernelGGL((fwd_q32<L, R, PPB, TIER, MINW>), grid, dim3(G::T * PPB), lds, s, in, out, pv.consts, pv.tw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride, q32_flags(in, out, nullptr, fl));
-    return hipGetLastError();
-}
-template <int L, int R, int PPB, int TIER, int MINW>
-hipError_t launch_inv_q32_t(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
-    dim3 grid((unsigned)((fl.batch + PPB - 1) / PPB), pv.num_primes);
-    const size_t lds = q32_lds_bytes<L, R, PPB>();
-    hipLaunchKernelGGL((inv_q32<L, R, PPB, TIER, MINW>), grid, dim3(G::T * PPB), lds, s, in, in2, out, pv.consts, pv.itw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride, q32_flags(in, in2, out, fl));
-    return hipGetLastError();
-}
-template <int L, int R, int PPB, int TIER, int MINW>
-hipError_t launch_mul_q32_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
-    dim3 grid((unsigned)((fl.batch + PPB - 1) / PPB), pv.num_primes);
-    const size_t lds = q32_lds_bytes<L, R, PPB>();
-    hipLaunchKernelGGL((polymul_q32<L, R, PPB, TIER, MINW>), grid, dim3(G::T * PPB), lds, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride, 0u);
-    return hipGetLastError();
-}
-template <int L, int R, int PPB, int TIER, int MINW>
-hipError_t init_q32_t() {
-    const int bytes = (int)q32_lds_bytes<L, R, PPB>();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_q32<L, R, PPB, TIER, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_q32<L, R, PPB, TIER, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&polymul_q32<L, R, PPB, TIER, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return e;
-}
-
 // TIER 2 needs every modulus below 2^30, TIER 1 below 2^31 (rb_entry::narrow); the tables must honour the precon contract (arith >= 1)
 template <int L, int R, int PPB, int TIER, int MINW>
+struct q32_shape {
+    static constexpr int log_n = L, r = R, fpb = PPB, threads = rb_geom<L, R>::T * PPB, min_waves = MINW, arith = 1, narrow = TIER;
+    static constexpr uint32_t table_pairs = rb_geom<L, R>::table_pairs / 2;
+    static constexpr size_t lds = (size_t)((1u << L) + (1u << (L - 5))) * 4 * PPB;
+    static constexpr auto build = &build_table32_t<L, R>;
+    static constexpr bool flags_everywhere = true;      // the flag word described above fwd_q32
+    static uint32_t flags(const void* a, const void* b, const void* c, const frame_layout& fl) {
+        const bool aligned = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0 && ((fl.prime_stride | fl.poly_stride) & 1) == 0;
+        return (fl.lazy_out ? 1u : 0u) | (aligned ? 2u : 0u);
+    }
+};
+
+template <int L, int R, int PPB, int TIER, int MINW>
 constexpr rb_entry make_entry_q32(int id) {
-    rb_entry e{id, L, R, PPB, MINW, (uint32_t)rb_geom<L, R>::table_pairs / 2, q32_lds_bytes<L, R, PPB>(),
-               &build_table32_t<L, R>, &launch_q32_t<L, R, PPB, TIER, MINW>, &init_q32_t<L, R, PPB, TIER, MINW>, 1,
-               &launch_inv_q32_t<L, R, PPB, TIER, MINW>, &launch_mul_q32_t<L, R, PPB, TIER, MINW>};
-    e.narrow = TIER;
-    return e;
+    return make_entry3<q32_shape<L, R, PPB, TIER, MINW>, &fwd_q32<L, R, PPB, TIER, MINW>, &inv_q32<L, R, PPB, TIER, MINW>, &polymul_q32<L, R, PPB, TIER, MINW>>(id);
 }
 
 }  // namespace AGX_TU

@@ -18,7 +18,7 @@
 #define AGX_POLYMUL_MAXW 5
 #endif
 #ifndef AGX_TU
-#error "define AGX_TU (a per-translation-unit namespace name) before including rb_kernels.hpp"
+#error "define AGX_TU (a per-translation-unit namespace name) before including rb_frame.hpp / rb_kernels.hpp"
 #endif
 
 namespace agx {
@@ -160,9 +160,11 @@ constexpr int kOptStreamCh1 = 1 << 29;     // with kOptStreamTw: one table entry
 // the inverse's twiddle-first / priority policies, timing ablations, persistent streaming / loop forms of the forward, resident sub-blocks with
 // recomputed or separate leading stages (split / pair kernels), the first-generation portable-butterfly kernel.
 
+#ifdef AGX_DIAG
 // where the kOptTrace kernels write: [wave][16] words, set through agx_ntt_debug_set_trace_buffer
 __device__ uint64_t* g_trace_buf = nullptr;     // one copy per translation unit (namespace AGX_TU); only reg_diag.hip uses it
 __device__ uint64_t g_trace_waves = 0;
+#endif
 
 // per-frame state shared by the kernels
 template <int L, int R, bool FAST, int OPT = 0>
@@ -196,6 +198,9 @@ struct rb2_frame {
         }
     }
     __device__ __forceinline__ void trace_flush() const {
+#ifndef AGX_DIAG
+        static_assert(!TRACE, "kOptTrace kernels belong to the diagnostics library (AGX_DIAG): the product library has no trace buffer");
+#else
         if constexpr (TRACE) {
             const uint64_t wave = trace_wave != ~0ull ? trace_wave
                                                       : ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -207,6 +212,7 @@ struct rb2_frame {
                 dst[13] = __builtin_amdgcn_s_getreg((31 << 11) | 20);    // XCC_ID
             }
         }
+#endif
     }
     // a per-lane pass with all R stages: the shape the look-ahead twiddle fetch handles
     static constexpr bool lane_full_pass(int p) { return p >= 0 && p < NP && G::rlo(p) < 6 && G::hi(p) - G::rlo(p) + 1 == R; }

@@ -326,14 +326,16 @@ polysquare_rb2(const uint64_t* __restrict__ a, uint64_t* __restrict__ c,
     }
 }
 
-template <int L, int R>
-void build_table_t(const regblock_layout&, const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
+// ---- host side: pass tables, launch glue and registry entries, written once for every kernel family ---------------------------------
+// (the 32-bit kernels of rb32_kernels.hpp and the wave-packed kernels of wp_kernels.hpp bring their own shape struct and nothing else)
+
+// The geometry of one prime's pass table: f(at, idx) for every slot `at` in [0, rb_geom<L, R>::table_pairs) that holds a twiddle, idx = its
+// natural twiddle index.  What a slot stores is the builder's business ({w, w'} here, {(u32)w, w' >> 32} in build_table32_t).
+template <int L, int R, class F>
+void for_each_table_slot(F&& f) {
     using G = rb2_geom<L, R>;
-    const size_t start = out.size();
-    out.resize(start + (size_t)G::table_pairs, make_ulonglong2(0, 0));
     for (int p = 0; p < G::NP; ++p) {
         const int rlo = G::rlo(p), hi = G::hi(p), H = G::H(p);
-        ulonglong2* t = out.data() + start + (size_t)G::table_off(p);
         for (int j = 1; j < G::C; ++j) {
             int k = 0;
             while ((2 << k) <= j) ++k;
@@ -345,10 +347,17 @@ void build_table_t(const regblock_layout&, const uint64_t* tw, const uint64_t* p
                 // wave-uniform passes keep one column's C entries contiguous (wide scalar loads);
                 // per-lane passes keep one entry's columns contiguous (coalesced vector loads)
                 const size_t at = G::uniform_pass(p) ? (size_t)h * G::C + j : (size_t)j * H + h;
-                t[at] = make_ulonglong2(tw[idx], pre[idx]);
+                f((size_t)G::table_off(p) + at, idx);
             }
         }
     }
+}
+
+template <int L, int R>
+void build_table_t(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
+    const size_t start = out.size();
+    out.resize(start + (size_t)rb_geom<L, R>::table_pairs, make_ulonglong2(0, 0));
+    for_each_table_slot<L, R>([&](size_t at, uint32_t idx) { out[start + at] = make_ulonglong2(tw[idx], pre[idx]); });
 }
 
 template <int L, int R, int PPB, int ARITH>
@@ -360,117 +369,99 @@ constexpr size_t rb2_lds_bytes() {
 template <int ARITH>
 constexpr int rb2_arith_level() { return (ARITH & 1) ? ((((ARITH >> 1) & kOptLazy16) != 0) ? 2 : 1) : 0; }      // rb_entry::arith
 
+// A kernel shape S says what the launches of one family differ in besides the kernel symbol: the rb_entry fields (log_n, r, fpb = frames per
+// workgroup, min_waves, table_pairs, lds, build, arith, narrow), threads per workgroup, and the flag word.  Every forward kernel ends in one:
+// lazy_out here and in the wave-packed kernels (fwd_rb2 tests lazy_out != 0: it must never see another bit), q32_shape::flags in rb32_kernels.hpp,
+// whose inverse and product kernels take one too (flags_everywhere).
+struct lazy_flag {
+    static constexpr bool flags_everywhere = false;
+    static uint32_t flags(const void*, const void*, const void*, const frame_layout& fl) { return fl.lazy_out ? 1u : 0u; }
+};
+
 template <int L, int R, int PPB, int ARITH, int MINW>
-hipError_t launch_rb2_t(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
-    const size_t lds = rb2_lds_bytes<L, R, PPB, ARITH>();
-    dim3 grid((unsigned)((fl.batch + PPB - 1) / PPB), pv.num_primes);
-    hipLaunchKernelGGL((fwd_rb2<L, R, PPB, ARITH, MINW>), grid, dim3(G::T * PPB), lds, s, in, out, pv.consts, pv.tw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride, (uint32_t)(fl.lazy_out ? 1 : 0));
+struct rb2_shape : lazy_flag {
+    static constexpr int log_n = L, r = R, fpb = PPB, threads = rb_geom<L, R>::T * PPB, min_waves = MINW, arith = rb2_arith_level<ARITH>(), narrow = 0;
+    static constexpr uint32_t table_pairs = rb_geom<L, R>::table_pairs;
+    static constexpr size_t lds = rb2_lds_bytes<L, R, PPB, ARITH>();
+    static constexpr auto build = &build_table_t<L, R>;
+};
+
+// the one place the registry kernels' dynamic LDS is allowed: BYTES on each of K
+template <size_t BYTES, auto... K>
+hipError_t allow_lds() {
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BYTES)), ...);
+    return e;
+}
+
+// one workgroup per S::fpb frames and prime
+template <class S, class K, class... A>
+hipError_t launch_frames(K kernel, const plan_view& pv, const frame_layout& fl, hipStream_t s, A... args) {
+    const dim3 grid((unsigned)((fl.batch + S::fpb - 1) / S::fpb), pv.num_primes);
+    hipLaunchKernelGGL(kernel, grid, dim3(S::threads), S::lds, s, args...);
     return hipGetLastError();
 }
 
-template <int L, int R, int PPB, int ARITH, int MINW>
-hipError_t launch_inv_rb2_t(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
-    dim3 grid((unsigned)((fl.batch + PPB - 1) / PPB), pv.num_primes);
-    const size_t lds = rb2_lds_bytes<L, R, PPB, ARITH>();
-    hipLaunchKernelGGL((inv_rb2<L, R, PPB, ARITH, MINW>), grid, dim3(G::T * PPB), lds, s, in, in2, out, pv.consts,
-                       pv.itw_rb, pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride);
-    return hipGetLastError();
+template <class S, auto K>
+hipError_t launch_fwd_t(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
+    return launch_frames<S>(K, pv, fl, s, in, out, pv.consts, pv.tw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
+                            S::flags(in, out, nullptr, fl));
 }
 
-template <int L, int R, int PPB, int ARITH, int MINW>
-hipError_t launch_mul_rb2_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
-    dim3 grid((unsigned)((fl.batch + PPB - 1) / PPB), pv.num_primes);
-    const size_t lds = rb2_lds_bytes<L, R, PPB, ARITH>();
-    hipLaunchKernelGGL((polymul_rb2<L, R, PPB, ARITH, MINW>), grid, dim3(G::T * PPB), lds, s, a, b, c, pv.consts,
-                       pv.tw_rb, pv.itw_rb, pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride);
-    return hipGetLastError();
+template <class S, auto K>
+hipError_t launch_inv_t(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
+    if constexpr (S::flags_everywhere)
+        return launch_frames<S>(K, pv, fl, s, in, in2, out, pv.consts, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
+                                S::flags(in, in2, out, fl));
+    else
+        return launch_frames<S>(K, pv, fl, s, in, in2, out, pv.consts, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride);
+}
+
+template <class S, auto K>
+hipError_t launch_mul_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
+    if constexpr (S::flags_everywhere)      // the product kernels read no flag
+        return launch_frames<S>(K, pv, fl, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride, 0u);
+    else
+        return launch_frames<S>(K, pv, fl, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride);
 }
 
 template <int L, int R, int ARITH, int MINW>
 hipError_t launch_mul_park_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
-    dim3 grid((unsigned)fl.batch, pv.num_primes);
-    const size_t lds = rb2_lds_bytes<L, R, 1, ARITH>();
-    if (a == b) {      // squaring: NTT(a) times itself in registers (the parked form would read its own parked words back when c aliases too)
-        hipLaunchKernelGGL((polysquare_rb2<L, R, ARITH, MINW>), grid, dim3(G::T), lds, s, a, c, pv.consts,
-                           pv.tw_rb, pv.itw_rb, pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride);
-        return hipGetLastError();
-    }
+    using S = rb2_shape<L, R, 1, ARITH, MINW>;
+    if (a == b)      // squaring: NTT(a) times itself in registers (the parked form would read its own parked words back when c aliases too)
+        return launch_frames<S>(&polysquare_rb2<L, R, ARITH, MINW>, pv, fl, s, a, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch,
+                                fl.prime_stride, fl.poly_stride);
     // the operand c aliases (if any) must be the one that is read completely before c's frame is written
     const uint64_t* first = (c == b) ? b : a;
     const uint64_t* second = (c == b) ? a : b;
-    hipLaunchKernelGGL((polymul_rb2_park<L, R, ARITH, MINW>), grid, dim3(G::T), lds, s, first, second, c, pv.consts,
-                       pv.tw_rb, pv.itw_rb, pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride);
-    return hipGetLastError();
+    return launch_frames<S>(&polymul_rb2_park<L, R, ARITH, MINW>, pv, fl, s, first, second, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs,
+                            fl.batch, fl.prime_stride, fl.poly_stride);
 }
 
-template <int L, int R, int ARITH, int MINW>
-hipError_t init_mul_park_t() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&polymul_rb2_park<L, R, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)rb2_lds_bytes<L, R, 1, ARITH>());
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&polysquare_rb2<L, R, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)rb2_lds_bytes<L, R, 1, ARITH>());
-    return e;
-}
-
-template <int L, int R, int PPB, int ARITH, int MINW>
-hipError_t init_rb2_t() {
-    const int bytes = (int)rb2_lds_bytes<L, R, PPB, ARITH>();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_rb2<L, R, PPB, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_rb2<L, R, PPB, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&polymul_rb2<L, R, PPB, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return e;
-}
-
-// PPB frames per workgroup, every transform one workgroup per frame, the product with both forward results in registers
-// (the n = 4096 defaults: R = 3, 8 waves/SIMD)
-template <int L, int R, int PPB, int ARITH, int MINW>
-constexpr rb_entry make_entry2(int id) {
-    rb_entry e{id, L, R, PPB, MINW, (uint32_t)rb_geom<L, R>::table_pairs, rb2_lds_bytes<L, R, PPB, ARITH>(),
-               &build_table_t<L, R>, &launch_rb2_t<L, R, PPB, ARITH, MINW>, &init_rb2_t<L, R, PPB, ARITH, MINW>, rb2_arith_level<ARITH>(),
-               &launch_inv_rb2_t<L, R, PPB, ARITH, MINW>, &launch_mul_rb2_t<L, R, PPB, ARITH, MINW>};
-    return e;
-}
-
-// forward kernel only (a plan's forward companion: rb_entry::fwd_companion)
-template <int L, int R, int PPB, int ARITH, int MINW>
-hipError_t init_rb2_fwd_only_t() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_rb2<L, R, PPB, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)rb2_lds_bytes<L, R, PPB, ARITH>());
-}
-template <int L, int R, int ARITH, int MINW>
-constexpr rb_entry make_entry_single_fwd(int id) {
-    rb_entry e{id, L, R, 1, MINW, (uint32_t)rb_geom<L, R>::table_pairs, rb2_lds_bytes<L, R, 1, ARITH>(),
-               &build_table_t<L, R>, &launch_rb2_t<L, R, 1, ARITH, MINW>, &init_rb2_fwd_only_t<L, R, 1, ARITH, MINW>, rb2_arith_level<ARITH>(), nullptr, nullptr};
-    return e;
-}
-
-// workgroups the current device holds at once at MINW waves per SIMD (the loop kernels' grid)
-template <int L, int R, int MINW>
-hipError_t resident_workgroups(unsigned* out) {
+// The loop kernels' launch: a resident grid -- as many workgroups as the current device holds at once at S::min_waves waves per SIMD, at most
+// one per frame -- over `total` = batch x primes frames, which the kernels number in 32 bits
+template <class S>
+hipError_t resident_grid(const plan_view& pv, const frame_layout& fl, unsigned* grid, uint32_t* total) {
     int dev = 0, cus = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) *out = (unsigned)cus * (unsigned)(MINW * 256 / rb_geom<L, R>::T);
-    return e;
+    if (e != hipSuccess) return e;
+    const uint64_t frames = fl.batch * pv.num_primes, resident = (uint64_t)cus * (unsigned)(S::min_waves * 256 / S::threads);
+    if (frames >= (1ull << 31)) return hipErrorInvalidValue;
+    *total = (uint32_t)frames;
+    *grid = (unsigned)(frames < resident ? frames : resident);
+    return hipSuccess;
 }
 
 template <int L, int R, int ARITH, int MINW>
 hipError_t launch_inv_rb2_loop_t(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
-    unsigned resident = 0;
-    hipError_t e = resident_workgroups<L, R, MINW>(&resident);
+    using S = rb2_shape<L, R, 1, ARITH, MINW>;
+    unsigned grid = 0;
+    uint32_t total = 0;
+    const hipError_t e = resident_grid<S>(pv, fl, &grid, &total);
     if (e != hipSuccess) return e;
-    const uint64_t total = fl.batch * pv.num_primes;
-    if (total >= (1ull << 31)) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(total < resident ? total : resident);
-    const size_t lds = rb2_lds_bytes<L, R, 1, ARITH>();
-    hipLaunchKernelGGL((inv_rb2_loop<L, R, ARITH, MINW>), dim3(grid), dim3(G::T), lds, s, in, in2, out, pv.consts, pv.itw_rb,
-                       pv.rb.pairs_per_prime, (uint32_t)fl.batch, (uint32_t)total, fl.prime_stride, fl.poly_stride);
+    hipLaunchKernelGGL((inv_rb2_loop<L, R, ARITH, MINW>), dim3(grid), dim3(S::threads), S::lds, s, in, in2, out, pv.consts, pv.itw_rb,
+                       pv.rb.entry->table_pairs, (uint32_t)fl.batch, total, fl.prime_stride, fl.poly_stride);
     return hipGetLastError();
 }
 
@@ -481,42 +472,61 @@ inline bool stream_is_capturing(hipStream_t s) {
     return hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusActive;
 }
 
+constexpr size_t kDloopMailboxBytes = 16;      // inv_rb2_dloop's two-slot mailbox behind the frame's image
+
 template <int L, int R, int ARITH, int MINW>
 hipError_t launch_inv_rb2_dloop_t(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    using G = rb_geom<L, R>;
+    using S = rb2_shape<L, R, 1, ARITH, MINW>;
     if (stream_is_capturing(s)) return launch_inv_rb2_loop_t<L, R, ARITH, MINW>(pv, in, in2, out, fl, s);
-    unsigned resident = 0;
-    hipError_t e = resident_workgroups<L, R, MINW>(&resident);
+    unsigned grid = 0;
+    uint32_t total = 0;
+    hipError_t e = resident_grid<S>(pv, fl, &grid, &total);
     if (e != hipSuccess) return e;
-    const uint64_t total = fl.batch * pv.num_primes;
-    if (total >= (1ull << 31)) return hipErrorInvalidValue;
     uint32_t* ticket = pv.ticket(s);      // taken last: from here on the launch is issued and ticket_done() follows it
     if (!ticket) return launch_inv_rb2_loop_t<L, R, ARITH, MINW>(pv, in, in2, out, fl, s);      // no pair provably free: stateless form
-    const unsigned grid = (unsigned)(total < resident ? total : resident);
-    const size_t lds = rb2_lds_bytes<L, R, 1, ARITH>() + 16;
-    hipLaunchKernelGGL((inv_rb2_dloop<L, R, ARITH, MINW>), dim3(grid), dim3(G::T), lds, s, in, in2, out, pv.consts, pv.itw_rb,
-                       pv.rb.pairs_per_prime, (uint32_t)fl.batch, (uint32_t)total, fl.prime_stride, fl.poly_stride, ticket);
+    hipLaunchKernelGGL((inv_rb2_dloop<L, R, ARITH, MINW>), dim3(grid), dim3(S::threads), S::lds + kDloopMailboxBytes, s, in, in2, out, pv.consts, pv.itw_rb,
+                       pv.rb.entry->table_pairs, (uint32_t)fl.batch, total, fl.prime_stride, fl.poly_stride, ticket);
     e = hipGetLastError();
     pv.ticket_done(s, ticket);      // an event behind the launch: when it has fired the pair is idle (and zero) and the plan may hand it to another stream
     return e;
 }
 
+// ---- registry entries: each is built from exactly the kernels it launches, so nothing else is instantiated ----------------------------
+template <class S>
+constexpr rb_entry shape_entry(int id, decltype(rb_entry::launch) fwd, decltype(rb_entry::init) init, decltype(rb_entry::launch_inv) inv,
+                               decltype(rb_entry::launch_mul) mul) {
+    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow};
+}
+
+// forward, inverse and the product with both forward results in registers, one workgroup per S::fpb frames each (every family has this form)
+template <class S, auto FWD, auto INV, auto MUL>
+constexpr rb_entry make_entry3(int id) {
+    return shape_entry<S>(id, &launch_fwd_t<S, FWD>, &allow_lds<S::lds, FWD, INV, MUL>, &launch_inv_t<S, INV>, &launch_mul_t<S, MUL>);
+}
+
+// PPB frames per workgroup (the n = 4096 defaults: R = 3, 8 waves/SIMD); the product kernel at MULW waves per SIMD
+template <int L, int R, int PPB, int ARITH, int MINW, int MULW = MINW>
+constexpr rb_entry make_entry2(int id) {
+    return make_entry3<rb2_shape<L, R, PPB, ARITH, MINW>, &fwd_rb2<L, R, PPB, ARITH, MINW>, &inv_rb2<L, R, PPB, ARITH, MINW>, &polymul_rb2<L, R, PPB, ARITH, MULW>>(id);
+}
+
+// forward kernel only (a plan's forward companion: rb_entry::fwd_companion)
+template <int L, int R, int ARITH, int MINW>
+constexpr rb_entry make_entry_single_fwd(int id) {
+    using S = rb2_shape<L, R, 1, ARITH, MINW>;
+    constexpr auto fwd = &fwd_rb2<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd>, nullptr, nullptr);
+}
+
 // the streamed single-frame kernels (reg_s<n>.hip): one frame in registers per workgroup at any time (R = 5: a second frame cannot
 // be held): forward, inverse, and the fused product by polymul_rb2_park / polysquare_rb2
 template <int L, int R, int ARITH, int MINW>
-hipError_t init_rb2_single_t() {
-    const int bytes = (int)rb2_lds_bytes<L, R, 1, ARITH>();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_rb2<L, R, 1, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_rb2<L, R, 1, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = init_mul_park_t<L, R, ARITH, MINW>();
-    return e;
-}
-template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single(int id) {
-    rb_entry e{id, L, R, 1, MINW, (uint32_t)rb_geom<L, R>::table_pairs, rb2_lds_bytes<L, R, 1, ARITH>(),
-               &build_table_t<L, R>, &launch_rb2_t<L, R, 1, ARITH, MINW>, &init_rb2_single_t<L, R, ARITH, MINW>, rb2_arith_level<ARITH>(),
-               &launch_inv_rb2_t<L, R, 1, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>};
-    return e;
+    using S = rb2_shape<L, R, 1, ARITH, MINW>;
+    constexpr auto fwd = &fwd_rb2<L, R, 1, ARITH, MINW>;
+    constexpr auto inv = &inv_rb2<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>>,
+                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>);
 }
 
 // entry e with forward calls of its plans routed to the forward-only entry `id` (rb_entry::fwd_companion)
@@ -529,36 +539,21 @@ constexpr rb_entry with_fwd_companion(rb_entry e, int id, uint32_t min_frames = 
 // ... with the fused product by polymul_rb2 (both forward results in registers) at MULW waves per SIMD: small frames, where two
 // frames of 2^R coefficients still fit the register budget and the parked product's round trip through c's frame costs more
 template <int L, int R, int ARITH, int MINW, int MULW>
-hipError_t init_rb2_single_mul2_t() {
-    const int bytes = (int)rb2_lds_bytes<L, R, 1, ARITH>();
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_rb2<L, R, 1, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_rb2<L, R, 1, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&polymul_rb2<L, R, 1, ARITH, MULW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return e;
-}
-template <int L, int R, int ARITH, int MINW, int MULW>
-constexpr rb_entry make_entry_single_mul2(int id) {
-    rb_entry e = make_entry_single<L, R, ARITH, MINW>(id);
-    e.init = &init_rb2_single_mul2_t<L, R, ARITH, MINW, MULW>;
-    e.launch_mul = &launch_mul_rb2_t<L, R, 1, ARITH, MULW>;
-    return e;
-}
+constexpr rb_entry make_entry_single_mul2(int id) { return make_entry2<L, R, 1, ARITH, MINW, MULW>(id); }
 
 // ... with the inverse by the ticket-drawing loop kernel (captured launches and streams without a ticket pair take the fixed-stride form)
 template <int L, int R, int ARITH, int MINW>
 hipError_t init_rb2_single_invloop_t() {
-    hipError_t e = init_rb2_single_t<L, R, ARITH, MINW>();
-    const int bytes = (int)rb2_lds_bytes<L, R, 1, ARITH>();
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_rb2_loop<L, R, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_rb2_dloop<L, R, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes + 16);
-    return e;
+    using S = rb2_shape<L, R, 1, ARITH, MINW>;
+    const hipError_t e = allow_lds<S::lds, &fwd_rb2<L, R, 1, ARITH, MINW>, &inv_rb2_loop<L, R, ARITH, MINW>, &polymul_rb2_park<L, R, ARITH, MINW>,
+                                   &polysquare_rb2<L, R, ARITH, MINW>>();
+    return e != hipSuccess ? e : allow_lds<S::lds + kDloopMailboxBytes, &inv_rb2_dloop<L, R, ARITH, MINW>>();
 }
 template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single_invloop(int id) {
-    rb_entry e = make_entry_single<L, R, ARITH, MINW>(id);
-    e.init = &init_rb2_single_invloop_t<L, R, ARITH, MINW>;
-    e.launch_inv = &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>;
-    return e;
+    using S = rb2_shape<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, &fwd_rb2<L, R, 1, ARITH, MINW>>, &init_rb2_single_invloop_t<L, R, ARITH, MINW>,
+                          &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>);
 }
 
 }  // namespace AGX_TU

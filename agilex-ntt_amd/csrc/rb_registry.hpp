@@ -13,9 +13,9 @@ struct rb_entry {
     int min_waves;
     uint32_t table_pairs;   // pass-table length per prime, in {w,w'} pairs
     size_t lds_bytes;
-    void (*build)(const regblock_layout&, const uint64_t*, const uint64_t*, std::vector<ulonglong2>&);
+    void (*build)(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out);      // appends one prime's pass table
     hipError_t (*launch)(const plan_view&, const uint64_t*, uint64_t*, const frame_layout&, hipStream_t);
-    hipError_t (*init)();
+    hipError_t (*init)();    // allows every kernel the entry launches the dynamic LDS it is launched with
     int arith;   // 0: exact (reference op sequence, q < 2^62); 1: fast (q <= 2^61); 2: 16q-lazy (q <= 2^60)
     hipError_t (*launch_inv)(const plan_view&, const uint64_t*, const uint64_t*, uint64_t*, const frame_layout&, hipStream_t);      // in2 != null: in * in2 is transformed
     hipError_t (*launch_mul)(const plan_view&, const uint64_t*, const uint64_t*, uint64_t*, const frame_layout&, hipStream_t);      // c = INTT(NTT(a) o NTT(b)) in one launch

@@ -279,54 +279,24 @@ polymul_wp(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, uint6
     }
 }
 
-template <int L, int R, int WPB, int ARITH, int MINW>
-hipError_t launch_wp_t(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    constexpr int FPB = wp_geom<L, R>::FPW * WPB;
-    dim3 grid((unsigned)((fl.batch + FPB - 1) / FPB), pv.num_primes);
-    const size_t lds = wp_lds_bytes<L, R, ARITH>(WPB);
-    hipLaunchKernelGGL((fwd_wp<L, R, WPB, ARITH, MINW>), grid, dim3(64 * WPB), lds, s, in, out, pv.consts, pv.tw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride, (uint32_t)(fl.lazy_out ? 1 : 0));
-    return hipGetLastError();
-}
-template <int L, int R, int WPB, int ARITH, int MINW>
-hipError_t launch_inv_wp_t(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    constexpr int FPB = wp_geom<L, R>::FPW * WPB;
-    dim3 grid((unsigned)((fl.batch + FPB - 1) / FPB), pv.num_primes);
-    const size_t lds = wp_lds_bytes<L, R, ARITH>(WPB);
-    hipLaunchKernelGGL((inv_wp<L, R, WPB, ARITH, MINW>), grid, dim3(64 * WPB), lds, s, in, in2, out, pv.consts, pv.itw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride);
-    return hipGetLastError();
-}
 // the product keeps two frames in registers: 16 coefficients per lane and more get 4 waves per SIMD (128 VGPRs)
 template <int R, int MINW>
 constexpr int wp_mul_waves() { return R >= 4 ? 4 : (MINW > AGX_POLYMUL_MAXW ? AGX_POLYMUL_MAXW : MINW); }
 
+// WPB waves per workgroup (no barrier: the group only shares an LDS allocation), MINW waves per SIMD
 template <int L, int R, int WPB, int ARITH, int MINW>
-hipError_t launch_mul_wp_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
-    constexpr int FPB = wp_geom<L, R>::FPW * WPB;
-    dim3 grid((unsigned)((fl.batch + FPB - 1) / FPB), pv.num_primes);
-    const size_t lds = wp_lds_bytes<L, R, ARITH>(WPB);
-    hipLaunchKernelGGL((polymul_wp<L, R, WPB, ARITH, wp_mul_waves<R, MINW>()>), grid, dim3(64 * WPB), lds, s, a, b, c,
-                       pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride);
-    return hipGetLastError();
-}
-template <int L, int R, int WPB, int ARITH, int MINW>
-hipError_t init_wp_t() {
-    const int bytes = (int)wp_lds_bytes<L, R, ARITH>(WPB);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_wp<L, R, WPB, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_wp<L, R, WPB, ARITH, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&polymul_wp<L, R, WPB, ARITH, wp_mul_waves<R, MINW>()>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return e;
-}
+struct wp_shape : lazy_flag {
+    static constexpr int log_n = L, r = R, fpb = wp_geom<L, R>::FPW * WPB, threads = 64 * WPB, min_waves = MINW, arith = rb2_arith_level<ARITH>(), narrow = 0;
+    static constexpr uint32_t table_pairs = rb_geom<L, R>::table_pairs;
+    static constexpr size_t lds = wp_lds_bytes<L, R, ARITH>(WPB);
+    static constexpr auto build = &build_table_t<L, R>;
+};
 
-// registry entry: forward, inverse and the one-launch product of one (L, R) shape; WPB waves per workgroup (no barrier: the group
-// only shares an LDS allocation), MINW waves per SIMD
+// registry entry: forward, inverse and the one-launch product of one (L, R) shape
 template <int L, int R, int WPB, int ARITH, int MINW>
 constexpr rb_entry make_entry_wp(int id) {
-    rb_entry e{id, L, R, wp_geom<L, R>::FPW * WPB, MINW, (uint32_t)rb_geom<L, R>::table_pairs, wp_lds_bytes<L, R, ARITH>(WPB),
-               &build_table_t<L, R>, &launch_wp_t<L, R, WPB, ARITH, MINW>, &init_wp_t<L, R, WPB, ARITH, MINW>, rb2_arith_level<ARITH>(),
-               &launch_inv_wp_t<L, R, WPB, ARITH, MINW>, &launch_mul_wp_t<L, R, WPB, ARITH, MINW>};
-    return e;
+    return make_entry3<wp_shape<L, R, WPB, ARITH, MINW>, &fwd_wp<L, R, WPB, ARITH, MINW>, &inv_wp<L, R, WPB, ARITH, MINW>,
+                       &polymul_wp<L, R, WPB, ARITH, wp_mul_waves<R, MINW>()>>(id);
 }
 
 
@@ -455,47 +425,17 @@ template <int R, int MINW>
 constexpr int wp32_mul_waves() { return R >= 5 ? (MINW > 4 ? 4 : MINW) : R == 4 ? (MINW > 5 ? 5 : MINW) : MINW; }
 
 template <int L, int R, int WPB, int TIER, int MINW>
-hipError_t launch_wp32_t(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    constexpr int FPB = wp_geom<L, R>::FPW * WPB;
-    dim3 grid((unsigned)((fl.batch + FPB - 1) / FPB), pv.num_primes);
-    const size_t lds = wp32_lds_bytes<L, R>(WPB);
-    hipLaunchKernelGGL((fwd_wp32<L, R, WPB, TIER, MINW>), grid, dim3(64 * WPB), lds, s, in, out, pv.consts, pv.tw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride, (uint32_t)(fl.lazy_out ? 1 : 0));
-    return hipGetLastError();
-}
-template <int L, int R, int WPB, int TIER, int MINW>
-hipError_t launch_inv_wp32_t(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    constexpr int FPB = wp_geom<L, R>::FPW * WPB;
-    dim3 grid((unsigned)((fl.batch + FPB - 1) / FPB), pv.num_primes);
-    const size_t lds = wp32_lds_bytes<L, R>(WPB);
-    hipLaunchKernelGGL((inv_wp32<L, R, WPB, TIER, MINW>), grid, dim3(64 * WPB), lds, s, in, in2, out, pv.consts, pv.itw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride);
-    return hipGetLastError();
-}
-template <int L, int R, int WPB, int TIER, int MINW>
-hipError_t launch_mul_wp32_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
-    constexpr int FPB = wp_geom<L, R>::FPW * WPB;
-    dim3 grid((unsigned)((fl.batch + FPB - 1) / FPB), pv.num_primes);
-    const size_t lds = wp32_lds_bytes<L, R>(WPB);
-    hipLaunchKernelGGL((polymul_wp32<L, R, WPB, TIER, wp32_mul_waves<R, MINW>()>), grid, dim3(64 * WPB), lds, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb,
-                       pv.rb.pairs_per_prime, fl.batch, fl.prime_stride, fl.poly_stride);
-    return hipGetLastError();
-}
-template <int L, int R, int WPB, int TIER, int MINW>
-hipError_t init_wp32_t() {
-    const int bytes = (int)wp32_lds_bytes<L, R>(WPB);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&fwd_wp32<L, R, WPB, TIER, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&inv_wp32<L, R, WPB, TIER, MINW>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&polymul_wp32<L, R, WPB, TIER, wp32_mul_waves<R, MINW>()>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return e;
-}
+struct wp32_shape : lazy_flag {
+    static constexpr int log_n = L, r = R, fpb = wp_geom<L, R>::FPW * WPB, threads = 64 * WPB, min_waves = MINW, arith = 1, narrow = TIER;
+    static constexpr uint32_t table_pairs = rb_geom<L, R>::table_pairs / 2;
+    static constexpr size_t lds = wp32_lds_bytes<L, R>(WPB);
+    static constexpr auto build = &build_table32_t<L, R>;
+};
+
 template <int L, int R, int WPB, int TIER, int MINW>
 constexpr rb_entry make_entry_wp32(int id) {
-    rb_entry e{id, L, R, wp_geom<L, R>::FPW * WPB, MINW, (uint32_t)rb_geom<L, R>::table_pairs / 2, wp32_lds_bytes<L, R>(WPB),
-               &build_table32_t<L, R>, &launch_wp32_t<L, R, WPB, TIER, MINW>, &init_wp32_t<L, R, WPB, TIER, MINW>, 1,
-               &launch_inv_wp32_t<L, R, WPB, TIER, MINW>, &launch_mul_wp32_t<L, R, WPB, TIER, MINW>};
-    e.narrow = TIER;
-    return e;
+    return make_entry3<wp32_shape<L, R, WPB, TIER, MINW>, &fwd_wp32<L, R, WPB, TIER, MINW>, &inv_wp32<L, R, WPB, TIER, MINW>,
+                       &polymul_wp32<L, R, WPB, TIER, wp32_mul_waves<R, MINW>()>>(id);
 }
 #endif  // AGX_WP_Q32
 
