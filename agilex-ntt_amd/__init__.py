@@ -49,6 +49,7 @@ ABI = {
     "agx_ntt_inverse_strided": (_int, [_vp, _vp, _vp, _u64, _i64, _i64, _vp]),
     "agx_ntt_pointwise": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_polymul": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "agx_ntt_polymul_ntt": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
@@ -66,6 +67,7 @@ ABI = {
     "agx_ntt_group_forward": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64]),
     "agx_ntt_group_inverse": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64]),
     "agx_ntt_group_polymul": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64]),
+    "agx_ntt_group_polymul_ntt": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64, _p64]),
     "agx_ntt_group_synchronize": (_int, [_vp]),
 }
 
@@ -276,6 +278,11 @@ class Plan:
     def polymul(self, d_a, d_b, d_c, d_scratch, batch, stream=0):
         _check(lib().agx_ntt_polymul(self._h, d_a, d_b, d_c, d_scratch, batch, stream), "polymul")
 
+    def polymul_ntt(self, d_a, d_bhat, d_c, batch, bhat_batch=None, stream=0):
+        """c = a * b with b given by its transform d_bhat (what forward / forward_lazy of this plan wrote); bhat_batch: None = batch
+        (one bhat frame per frame) or 1 (one bhat frame per prime, shared by the whole batch)"""
+        _check(lib().agx_ntt_polymul_ntt(self._h, d_a, d_bhat, d_c, batch, batch if bhat_batch is None else bhat_batch, stream), "polymul_ntt")
+
     def fill_synthetic(self, d_out, batch, first_poly=0, seed=42, stream=0):
         _check(lib().agx_ntt_fill_synthetic(self._h, d_out, batch, first_poly, seed, stream), "fill_synthetic")
 
@@ -382,6 +389,11 @@ class DeviceGroup:
 
     def polymul(self, d_a, d_b, d_c, batch, d_scratch=None):
         _check(lib().agx_ntt_group_polymul(self._h, self._ptrs(d_a), self._ptrs(d_b), self._ptrs(d_c), self._ptrs(d_scratch), self._batches(batch)), "group_polymul")
+
+    def polymul_ntt(self, d_a, d_bhat, d_c, batch, bhat_batch=None):
+        """per shard as Plan.polymul_ntt; bhat_batch: None = batch, or one entry (batch[i] or 1) per shard"""
+        _check(lib().agx_ntt_group_polymul_ntt(self._h, self._ptrs(d_a), self._ptrs(d_bhat), self._ptrs(d_c), self._batches(batch),
+                                               self._batches(batch if bhat_batch is None else bhat_batch)), "group_polymul_ntt")
 
     def synchronize(self):
         _check(lib().agx_ntt_group_synchronize(self._h), "group_synchronize")

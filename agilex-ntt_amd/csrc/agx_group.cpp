@@ -259,11 +259,11 @@ int agx_ntt_group_inverse_host(const agx_ntt_group* group, const uint64_t* in, u
 }
 
 // ---- device pointers: one pointer and one batch per shard, every shard launched from its own thread on its own stream ---------
-enum group_op { OP_FORWARD, OP_INVERSE, OP_POLYMUL };
+enum group_op { OP_FORWARD, OP_INVERSE, OP_POLYMUL, OP_POLYMUL_NTT };
 
 static int group_device(const agx_ntt_group* group, group_op op, const uint64_t* const* a, const uint64_t* const* b, uint64_t* const* c,
-                        uint64_t* const* scratch, const uint64_t* batch) {
-    if (!group || !a || !c || !batch || (op == OP_POLYMUL && !b)) return AGX_ERR_NULL_POINTER;
+                        uint64_t* const* scratch, const uint64_t* batch, const uint64_t* bhat_batch = nullptr) {
+    if (!group || !a || !c || !batch || ((op == OP_POLYMUL || op == OP_POLYMUL_NTT) && !b) || (op == OP_POLYMUL_NTT && !bhat_batch)) return AGX_ERR_NULL_POINTER;
     return guarded([&] {
         return on_every_shard(group, [&](uint32_t i) -> int {
             shard* s = group->shards[i].get();
@@ -271,7 +271,8 @@ static int group_device(const agx_ntt_group* group, group_op op, const uint64_t*
             switch (op) {
                 case OP_FORWARD: return agx_ntt_forward(s->plan, a[i], c[i], batch[i], s->stream);
                 case OP_INVERSE: return agx_ntt_inverse(s->plan, a[i], c[i], batch[i], s->stream);
-                default: return agx_ntt_polymul(s->plan, a[i], b[i], c[i], scratch ? scratch[i] : nullptr, batch[i], s->stream);
+                case OP_POLYMUL: return agx_ntt_polymul(s->plan, a[i], b[i], c[i], scratch ? scratch[i] : nullptr, batch[i], s->stream);
+                default: return agx_ntt_polymul_ntt(s->plan, a[i], b[i], c[i], batch[i], bhat_batch[i], s->stream);
             }
         });
     });
@@ -288,6 +289,11 @@ int agx_ntt_group_inverse(const agx_ntt_group* group, const uint64_t* const* d_i
 int agx_ntt_group_polymul(const agx_ntt_group* group, const uint64_t* const* d_a, const uint64_t* const* d_b, uint64_t* const* d_c,
                           uint64_t* const* d_scratch, const uint64_t* batch) {
     return group_device(group, OP_POLYMUL, d_a, d_b, d_c, d_scratch, batch);
+}
+
+int agx_ntt_group_polymul_ntt(const agx_ntt_group* group, const uint64_t* const* d_a, const uint64_t* const* d_bhat, uint64_t* const* d_c,
+                              const uint64_t* batch, const uint64_t* bhat_batch) {
+    return group_device(group, OP_POLYMUL_NTT, d_a, d_bhat, d_c, nullptr, batch, bhat_batch);
 }
 
 int agx_ntt_group_synchronize(const agx_ntt_group* group) {

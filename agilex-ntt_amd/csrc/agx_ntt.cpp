@@ -661,6 +661,38 @@ int agx_ntt_polymul(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_
     return agx_ntt_inverse(plan, d_c, d_c, batch, stream);
 }
 
+int agx_ntt_polymul_ntt(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c,
+                        uint64_t batch, uint64_t bhat_batch, void* stream) {
+    if (!plan || !d_a || !d_bhat || !d_c) return AGX_ERR_NULL_POINTER;
+    const int64_t n = (int64_t)plan->n;
+    int rc = check_call(plan, d_a, d_c, batch, (int64_t)batch * n, n);      // c may BE a, never straddle it
+    if (rc) return rc;
+    if (bhat_batch != batch && bhat_batch != 1) return AGX_ERR_BAD_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_bhat) & 7u) != 0) return AGX_ERR_BAD_ARGUMENT;
+    {
+        // both sets are dense, so each is one range of words: c's [prime][batch][n] must not touch bhat's [prime][bhat_batch][n] anywhere
+        // (bhat is read by every workgroup of its prime while others already write c)
+        const uintptr_t c0 = reinterpret_cast<uintptr_t>(d_c), b0 = reinterpret_cast<uintptr_t>(d_bhat);
+        const uintptr_t c_bytes = (uintptr_t)plan->num_primes * batch * plan->n * sizeof(uint64_t);
+        const uintptr_t b_bytes = (uintptr_t)plan->num_primes * bhat_batch * plan->n * sizeof(uint64_t);
+        if (c0 < b0 + b_bytes && b0 < c0 + c_bytes) return AGX_ERR_BAD_ARGUMENT;
+    }
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    const int64_t bhat_prime_stride = (int64_t)bhat_batch * n, bhat_poly_stride = bhat_batch == 1 ? 0 : n;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (use_regblock(plan) && regblock_has_mulhat(plan->rb) && plan->d_itw_rb) {
+        // one kernel: the forward transform, the product with bhat as it streams in and the inverse stay on chip
+        const frame_layout fl{batch, (int64_t)batch * n, n};
+        AGX_HIP(launch_polymul_ntt_regblock(view_of(plan), d_a, d_bhat, d_c, fl, bhat_prime_stride, bhat_poly_stride, s));
+        return AGX_OK;
+    }
+    // generic path, no scratch: c <- NTT(a) (lazy: the product reduces its operands); c <- c o bhat in place; c <- INTT(c)
+    if ((rc = forward_common(plan, d_a, d_c, batch, (int64_t)batch * n, n, true, stream))) return rc;
+    AGX_HIP(launch_pointwise_bhat(view_of(plan), d_c, d_bhat, batch, bhat_prime_stride, bhat_poly_stride, s));
+    return agx_ntt_inverse(plan, d_c, d_c, batch, stream);
+}
+
 int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly, uint64_t seed, void* stream) {
     if (!plan || !d_out) return AGX_ERR_NULL_POINTER;
     int rc = check_call(plan, d_out, d_out, batch, (int64_t)(batch * plan->n), (int64_t)plan->n);

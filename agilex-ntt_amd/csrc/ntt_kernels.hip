@@ -190,6 +190,22 @@ __global__ void pointwise_kernel(const uint64_t* __restrict__ a, const uint64_t*
     }
 }
 
+// c <- c o bhat in place: element i of frame f of prime p meets bhat[p * bhat_prime_stride + f * bhat_poly_stride + i]
+// (bhat_poly_stride = 0: every frame of a prime meets the same bhat frame); both may be lazy ([0,4q))
+__global__ void pointwise_bhat_kernel(uint64_t* __restrict__ c, const uint64_t* __restrict__ bhat, const prime_consts* __restrict__ consts,
+                                      uint32_t log_n, uint64_t per_prime, int64_t bhat_prime_stride, int64_t bhat_poly_stride) {
+    const uint32_t prime = blockIdx.y;
+    const prime_consts k = consts[prime];
+    const barrett128 bk{k.q, k.mu_hi, k.mu_lo};
+    const uint64_t q2 = k.q << 1;
+    uint64_t* cp = c + (uint64_t)prime * per_prime;
+    const uint64_t* bp = bhat + (int64_t)prime * bhat_prime_stride;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t v = bp[(int64_t)(i >> log_n) * bhat_poly_stride + (int64_t)(i & ((1ull << log_n) - 1ull))];
+        cp[i] = mul_mod_barrett(reduce_4q(cp[i], k.q, q2), reduce_4q(v, k.q, q2), bk);
+    }
+}
+
 __device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -352,6 +368,22 @@ hipError_t launch_inverse_regblock(const plan_view& pv, const uint64_t* in, cons
 hipError_t launch_polymul_regblock(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
     if (!regblock_has_polymul(pv.rb) || !pv.itw_rb) return hipErrorInvalidValue;
     return pv.rb.entry->launch_mul(pv, a, b, c, fl, s);
+}
+
+bool regblock_has_mulhat(const regblock_layout& rb) { return rb.valid() && rb.entry->launch_mulhat; }
+
+hipError_t launch_polymul_ntt_regblock(const plan_view& pv, const uint64_t* a, const uint64_t* bhat, uint64_t* c, const frame_layout& fl,
+                                       int64_t bhat_prime_stride, int64_t bhat_poly_stride, hipStream_t s) {
+    if (!regblock_has_mulhat(pv.rb) || !pv.itw_rb) return hipErrorInvalidValue;
+    return pv.rb.entry->launch_mulhat(pv, a, bhat, c, fl, bhat_prime_stride, bhat_poly_stride, s);
+}
+
+hipError_t launch_pointwise_bhat(const plan_view& pv, uint64_t* c, const uint64_t* bhat, uint64_t batch, int64_t bhat_prime_stride,
+                                 int64_t bhat_poly_stride, hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
+    hipLaunchKernelGGL(pointwise_bhat_kernel, grid, dim3(256), 0, s, c, bhat, pv.consts, pv.log_n, per_prime, bhat_prime_stride, bhat_poly_stride);
+    return hipGetLastError();
 }
 
 hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {

@@ -72,7 +72,15 @@ bool regblock_has_polymul(const regblock_layout& rb);   // fused NTT -> pointwis
 // in2 != null: transforms the coefficient-wise product in * in2 (the pointwise step fused into the load)
 hipError_t launch_inverse_regblock(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s);
 hipError_t launch_polymul_regblock(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s);
+bool regblock_has_mulhat(const regblock_layout& rb);    // NTT -> product with a pre-transformed operand -> INTT in one kernel
+// c = INTT(NTT(a) o bhat): fl lays out a and c; frame (p, f) of bhat starts at p * bhat_prime_stride + f * bhat_poly_stride
+// (bhat_poly_stride 0: one bhat frame per prime for the whole batch)
+hipError_t launch_polymul_ntt_regblock(const plan_view& pv, const uint64_t* a, const uint64_t* bhat, uint64_t* c, const frame_layout& fl,
+                                       int64_t bhat_prime_stride, int64_t bhat_poly_stride, hipStream_t s);
 hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
+// c <- c o bhat in place on the dense [prime][batch][n] layout, bhat with strides of its own as above (the generic path of agx_ntt_polymul_ntt)
+hipError_t launch_pointwise_bhat(const plan_view& pv, uint64_t* c, const uint64_t* bhat, uint64_t batch, int64_t bhat_prime_stride,
+                                 int64_t bhat_poly_stride, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

@@ -4,6 +4,13 @@
 #pragma once
 #include "rb_frame.hpp"
 
+// mulhat_rb2 of a shape tuned for 8 waves/SIMD (n = 4096: 64 VGPRs) is compiled for 6 (80 VGPRs): with bhat's 16 words per thread
+// requested ahead of the last forward pass it needs 69-80 registers, 64 cost 12-92 bytes of scratch per lane, and 512-thread
+// workgroups occupy a SIMD two waves at a time anyway (7 = 6).  Measured equal to the 8-wave late-request form with a bhat frame
+// per frame and +1.5 % with a shared one (profiles/r05_mulntt.md).
+#ifndef AGX_MULHAT_MAXW
+#define AGX_MULHAT_MAXW 6
+#endif
 namespace agx {
 namespace AGX_TU {
 
@@ -326,6 +333,75 @@ polysquare_rb2(const uint64_t* __restrict__ a, uint64_t* __restrict__ c,
     }
 }
 
+// c = a * b in Z_q[X]/(X^n + 1) with b given by its transform bhat (what agx_ntt_forward / agx_ntt_forward_lazy of this plan wrote:
+// bit-reversed order, so thread tid's registers 0 .. C-1 of the last pass's layout meet bhat words tid C .. tid C + C-1): one forward
+// transform, the product where the coefficients sit in registers, the inverse.  One frame in registers at any time; nothing is
+// parked.  bhat has strides of its own: a poly stride of 0 multiplies every frame of a prime by the same bhat frame.  Each lane
+// reads its own C consecutive words of bhat with 16-byte loads (plain loads: a shared bhat should stay in L2 / MALL), GRP registers'
+// worth at a time and one group ahead of the one being multiplied; the kernels that run the forward transform pass by pass
+// (no streamed twiddles) request the first groups before the last forward pass.  24n bytes of traffic per product with a bhat frame per
+// frame, 16n + 8n / batch with a shared one.  A workgroup reads its whole frame of a before it writes c: c may alias a.
+typedef uint64_t bhat_pair __attribute__((ext_vector_type(2), aligned(8)));      // bhat is only known to be 8-byte aligned
+
+template <int L, int R, int PPB, int ARITH, int MINW>
+__global__ void __launch_bounds__((1 << (L - R)) * PPB, (MINW > AGX_MULHAT_MAXW ? AGX_MULHAT_MAXW : MINW))
+mulhat_rb2(const uint64_t* __restrict__ a, const uint64_t* __restrict__ bhat, uint64_t* __restrict__ c,
+           const prime_consts* __restrict__ consts, const twpair* __restrict__ tw_rb, const twpair* __restrict__ itw_rb,
+           uint32_t pairs_per_prime, uint64_t frames_x, int64_t prime_stride, int64_t poly_stride,
+           int64_t bhat_prime_stride, int64_t bhat_poly_stride) {
+    AGX_RB2_PROLOGUE;
+    const prime_consts pc = consts[prime];
+    const barrett128 bk{pc.q, pc.mu_hi, pc.mu_lo};
+    f.lazy_out = F::LAZY16;     // the Barrett product takes operands in [0,4q) when q <= 2^60
+    constexpr bool NTL = ((ARITH >> 1) & kOptNtLoad) != 0, NTS = ((ARITH >> 1) & kOptNtStore) != 0;
+    constexpr int GRP = 4, NG = C / GRP;      // registers per group of bhat loads (two 16-byte loads), groups per thread
+    static_assert(C % GRP == 0, "whole groups");
+    // pass by pass forward kernels (R = 3, 8 waves/SIMD, 16 words of bhat per thread): every group is requested before the last
+    // forward pass; streamed kernels (R = 4 / 5: the whole transform is one call) request group g + 1 before they multiply group g
+    constexpr bool EARLY = !F::STREAM_TW && !F::SPLIT && F::NP >= 2 && NG <= 2;
+    const bhat_pair* bp = reinterpret_cast<const bhat_pair*>(bhat + ((int64_t)prime * bhat_prime_stride + (int64_t)fx * bhat_poly_stride) + (uint32_t)f.tid * C);
+    uint64_t x[C];
+#pragma unroll
+    for (int r = 0; r < C; ++r) x[r] = NTL ? __builtin_nontemporal_load(&a[base + f.tid + (uint32_t)r * T]) : a[base + f.tid + (uint32_t)r * T];
+    bhat_pair z[EARLY ? NG : 2][GRP / 2];
+    auto request = [&](auto Gq) {
+        constexpr int g = Gq;
+        static_for<0, GRP / 2>([&](auto I) { z[EARLY ? g : (g & 1)][I] = bp[g * (GRP / 2) + (int)I]; });
+    };
+    if constexpr (EARLY) {
+        f.template forward_passes<0, F::NP - 1>(x, tw_rb + (size_t)prime * pairs_per_prime);
+        static_for<0, NG>(request);
+        f.template forward_passes<F::NP - 1, F::NP>(x, tw_rb + (size_t)prime * pairs_per_prime);
+    } else {
+        f.forward(x, tw_rb + (size_t)prime * pairs_per_prime);
+        request(std::integral_constant<int, 0>{});
+    }
+    static_for<0, NG>([&](auto Gq) {
+        constexpr int g = Gq;
+        if constexpr (!EARLY && g + 1 < NG) request(std::integral_constant<int, g + 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<0, GRP>([&](auto I) {
+            constexpr int i = I, r = g * GRP + i;
+            uint64_t u = z[EARLY ? g : (g & 1)][i / 2][i & 1];
+            // forward_lazy may have left bhat in [0,4q); beyond 2^60 the product wants it (and NTT(a), which is then fully reduced) below q
+            if constexpr (!F::LAZY16) u = reduce_4q(u, pc.q, pc.q << 1);
+            asm volatile("" : "+v"(x[r]));
+            x[r] = mul_mod_barrett(x[r], u, bk);
+            asm volatile("" : "+v"(x[r]));
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    __syncthreads();   // the image is reused: every wave is done reading the forward transform's exchanges
+    f.inverse(x, itw_rb + (size_t)prime * pairs_per_prime, pc);
+    if (live) {
+#pragma unroll
+        for (int r = 0; r < C; ++r) {
+            if constexpr (NTS) __builtin_nontemporal_store(x[r], &c[base + f.tid + (uint32_t)r * T]);
+            else c[base + f.tid + (uint32_t)r * T] = x[r];
+        }
+    }
+}
+
 // ---- host side: pass tables, launch glue and registry entries, written once for every kernel family ---------------------------------
 // (the 32-bit kernels of rb32_kernels.hpp and the wave-packed kernels of wp_kernels.hpp bring their own shape struct and nothing else)
 
@@ -425,6 +501,14 @@ hipError_t launch_mul_t(const plan_view& pv, const uint64_t* a, const uint64_t* 
         return launch_frames<S>(K, pv, fl, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride);
 }
 
+// the product by a pre-transformed operand: the frame layout describes a and c, bhat brings its own two strides
+template <class S, auto K>
+hipError_t launch_mulhat_t(const plan_view& pv, const uint64_t* a, const uint64_t* bhat, uint64_t* c, const frame_layout& fl, int64_t bhat_prime_stride,
+                           int64_t bhat_poly_stride, hipStream_t s) {
+    return launch_frames<S>(K, pv, fl, s, a, bhat, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
+                            bhat_prime_stride, bhat_poly_stride);
+}
+
 template <int L, int R, int ARITH, int MINW>
 hipError_t launch_mul_park_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
@@ -494,8 +578,8 @@ hipError_t launch_inv_rb2_dloop_t(const plan_view& pv, const uint64_t* in, const
 // ---- registry entries: each is built from exactly the kernels it launches, so nothing else is instantiated ----------------------------
 template <class S>
 constexpr rb_entry shape_entry(int id, decltype(rb_entry::launch) fwd, decltype(rb_entry::init) init, decltype(rb_entry::launch_inv) inv,
-                               decltype(rb_entry::launch_mul) mul) {
-    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow};
+                               decltype(rb_entry::launch_mul) mul, decltype(rb_entry::launch_mulhat) mulhat = nullptr) {
+    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow, mulhat};
 }
 
 // forward, inverse and the product with both forward results in registers, one workgroup per S::fpb frames each (every family has this form)
@@ -505,9 +589,15 @@ constexpr rb_entry make_entry3(int id) {
 }
 
 // PPB frames per workgroup (the n = 4096 defaults: R = 3, 8 waves/SIMD); the product kernel at MULW waves per SIMD
+// and the product by a pre-transformed operand (one frame in registers; at most AGX_MULHAT_MAXW waves per SIMD)
 template <int L, int R, int PPB, int ARITH, int MINW, int MULW = MINW>
 constexpr rb_entry make_entry2(int id) {
-    return make_entry3<rb2_shape<L, R, PPB, ARITH, MINW>, &fwd_rb2<L, R, PPB, ARITH, MINW>, &inv_rb2<L, R, PPB, ARITH, MINW>, &polymul_rb2<L, R, PPB, ARITH, MULW>>(id);
+    using S = rb2_shape<L, R, PPB, ARITH, MINW>;
+    constexpr auto fwd = &fwd_rb2<L, R, PPB, ARITH, MINW>;
+    constexpr auto inv = &inv_rb2<L, R, PPB, ARITH, MINW>;
+    constexpr auto mul = &polymul_rb2<L, R, PPB, ARITH, MULW>;
+    constexpr auto mulhat = &mulhat_rb2<L, R, PPB, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>);
 }
 
 // forward kernel only (a plan's forward companion: rb_entry::fwd_companion)
@@ -519,14 +609,15 @@ constexpr rb_entry make_entry_single_fwd(int id) {
 }
 
 // the streamed single-frame kernels (reg_s<n>.hip): one frame in registers per workgroup at any time (R = 5: a second frame cannot
-// be held): forward, inverse, and the fused product by polymul_rb2_park / polysquare_rb2
+// be held): forward, inverse, the fused product by polymul_rb2_park / polysquare_rb2, and the product by a pre-transformed operand
 template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     constexpr auto fwd = &fwd_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto inv = &inv_rb2<L, R, 1, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>>,
-                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>);
+    constexpr auto mulhat = &mulhat_rb2<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat>,
+                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, mulhat>);
 }
 
 // entry e with forward calls of its plans routed to the forward-only entry `id` (rb_entry::fwd_companion)
@@ -546,14 +637,14 @@ template <int L, int R, int ARITH, int MINW>
 hipError_t init_rb2_single_invloop_t() {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     const hipError_t e = allow_lds<S::lds, &fwd_rb2<L, R, 1, ARITH, MINW>, &inv_rb2_loop<L, R, ARITH, MINW>, &polymul_rb2_park<L, R, ARITH, MINW>,
-                                   &polysquare_rb2<L, R, ARITH, MINW>>();
+                                   &polysquare_rb2<L, R, ARITH, MINW>, &mulhat_rb2<L, R, 1, ARITH, MINW>>();
     return e != hipSuccess ? e : allow_lds<S::lds + kDloopMailboxBytes, &inv_rb2_dloop<L, R, ARITH, MINW>>();
 }
 template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single_invloop(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     return shape_entry<S>(id, &launch_fwd_t<S, &fwd_rb2<L, R, 1, ARITH, MINW>>, &init_rb2_single_invloop_t<L, R, ARITH, MINW>,
-                          &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>);
+                          &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, &mulhat_rb2<L, R, 1, ARITH, MINW>>);
 }
 
 }  // namespace AGX_TU

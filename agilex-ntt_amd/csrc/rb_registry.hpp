@@ -23,6 +23,10 @@ struct rb_entry {
     uint32_t fwd_companion_min_frames = 0;   // ... for launches of at least this many frames (batch x primes): a shape with fewer threads per frame wins
                                              // on throughput but loses on the latency of a launch that does not fill the chip
     int narrow = 0;            // 0: 64-bit arithmetic; 1: 32-bit arithmetic, every modulus < 2^31; 2: every modulus < 2^30 (rb32_kernels.hpp)
+    // c = INTT(NTT(a) o bhat) in one launch, bhat already transformed (frame (p, f) of bhat at p * bhat_prime_stride + f * bhat_poly_stride,
+    // a poly stride of 0 = one bhat frame per prime for the whole batch); null: the entry's plans take the generic three-launch path
+    hipError_t (*launch_mulhat)(const plan_view&, const uint64_t*, const uint64_t*, uint64_t*, const frame_layout&, int64_t bhat_prime_stride,
+                                int64_t bhat_poly_stride, hipStream_t) = nullptr;
 };
 
 struct rb_span {

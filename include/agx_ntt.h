@@ -165,6 +165,24 @@ AGX_API int agx_ntt_pointwise(const agx_ntt_plan* plan, const uint64_t* d_a, con
 AGX_API int agx_ntt_polymul(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c,
                     uint64_t* d_scratch, uint64_t batch, void* stream);
 
+/* c = a * b in Z_q[X]/(X^n + 1) with b given by its transform: d_bhat holds what agx_ntt_forward or agx_ntt_forward_lazy
+ * OF THIS PLAN wrote for b (bit-reversed order; values in [0,q), or lazy exactly as agx_ntt_forward_lazy leaves them): the
+ * product for a fixed operand (a key, a plaintext, a gadget row) that the caller keeps in NTT form -- two transforms
+ * instead of the three of agx_ntt_polymul.
+ * a, c: dense [prime][batch][n].  d_bhat: dense [prime][bhat_batch][n] with bhat_batch == batch (frame (p, f) is
+ * multiplied by bhat frame (p, f)) or bhat_batch == 1 (every frame of prime p is multiplied by the one bhat frame (p, 0):
+ * the shared operand is stored and fetched once, 16n + 8n/batch bytes of traffic per product instead of 24n).
+ * a may hold values in [0,4q) wherever agx_ntt_polymul accepts them; c is fully reduced.  c may alias a (in place);
+ * c must not touch d_bhat, and c / a must not partially overlap: AGX_ERR_BAD_ARGUMENT, nothing written.  bhat_batch other
+ * than batch or 1: AGX_ERR_BAD_ARGUMENT; a plan without inverse tables: AGX_ERR_NO_INVERSE.
+ * Asynchronous on `stream`, allocates and synchronises nothing (capturable into a hipGraph), needs no scratch.
+ * ONE launch (forward, product with bhat as it streams in, inverse, one frame on chip) for n = 1024 ... 32768 whenever some
+ * modulus is 2^31 or larger (the 16q-lazy, fast and exact 64-bit kernels alike).  Three launches (forward a -> c, c o bhat in
+ * place, inverse c -> c; 40n bytes) for n <= 512, for plans whose moduli are all below 2^31 (the 32-bit kernels) and for
+ * plans forced onto AGX_VARIANT_LDS_RADIX2. */
+AGX_API int agx_ntt_polymul_ntt(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c,
+                                uint64_t batch, uint64_t bhat_batch, void* stream);
+
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */
 AGX_API int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly,
@@ -224,6 +242,9 @@ AGX_API int agx_ntt_group_inverse(const agx_ntt_group* group, const uint64_t* co
 /* d_scratch may be NULL (or hold NULL entries) wherever agx_ntt_polymul accepts a NULL scratch */
 AGX_API int agx_ntt_group_polymul(const agx_ntt_group* group, const uint64_t* const* d_a, const uint64_t* const* d_b, uint64_t* const* d_c,
                                   uint64_t* const* d_scratch, const uint64_t* batch);
+/* agx_ntt_polymul_ntt per shard; bhat_batch[i] is batch[i] or 1 */
+AGX_API int agx_ntt_group_polymul_ntt(const agx_ntt_group* group, const uint64_t* const* d_a, const uint64_t* const* d_bhat,
+                                      uint64_t* const* d_c, const uint64_t* batch, const uint64_t* bhat_batch);
 AGX_API int agx_ntt_group_synchronize(const agx_ntt_group* group);
 
 #ifdef __cplusplus

@@ -1,6 +1,6 @@
 """tools/run_op.py -- launch ONE operation of the engine a fixed number of times (for rocprofv3 --pmc / --kernel-trace
 runs on paths bench.py's headline does not cover).
-Usage: python3 tools/run_op.py --op {fwd,inv,mul} [--n N --primes P --batch B --bits 60 --oop --launches K --variant ID]
+Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt} [--n N --primes P --batch B --bits 60 --oop --launches K --variant ID]
 Under the profiler: rocprofv3 ... -- python3 tools/run_op.py ...   (the interpreter itself after `--`, never this file: an
 `env` shebang hop after the profiler's preload has initialised the GPU is a forbidden exec on this pool)."""
 import argparse
@@ -15,7 +15,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -26,6 +26,7 @@ ap.add_argument("--oop", action="store_true", help="forward / inverse out of pla
 ap.add_argument("--variant", type=int, default=None, help="registry id (AGX_VARIANT_REGBLOCK_BASE + id)")
 ap.add_argument("--ramp-seconds", type=float, default=0.5, help="run the operation this long before the warm-up launches so the GPU clock has ramped, as bench.py does (0 = cold)")
 ap.add_argument("--mulsets", type=int, default=0, help="mul: K rotating (a, b) operand sets, c and scratch separate (bench.py's n = 32768 product line); 0 = c aliases a on the slabs")
+ap.add_argument("--bcast", action="store_true", help="mulntt: one bhat frame per prime shared by the whole batch (bhat_batch = 1)")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
@@ -38,17 +39,35 @@ for i, s in enumerate(slabs):
     plan.fill_synthetic(s.data_ptr(), args.batch, i * args.batch, 42, stream)
 scratch = torch.empty(per, dtype=torch.int64, device="cuda")
 sets, cbuf = [], None
-if args.op == "mul" and args.mulsets:
+if args.op in ("mul", "mulntt") and args.mulsets:
     sets = [[torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(2)] for _ in range(args.mulsets)]
     for k, (a, b) in enumerate(sets):
         plan.fill_synthetic(a.data_ptr(), args.batch, 2 * k * args.batch, 42, stream)
         plan.fill_synthetic(b.data_ptr(), args.batch, (2 * k + 1) * args.batch, 42, stream)
     cbuf = torch.empty(per, dtype=torch.int64, device="cuda")
+# mulntt: the second operand of every pair is transformed once, outside the timed region (agx_ntt_polymul_ntt's bhat); --bcast keeps
+# one frame per prime of it
+hats = {}
+if args.op == "mulntt":
+    for b in ([s[1] for s in sets] if sets else slabs):
+        if args.bcast:
+            b1 = b.view(args.primes, args.batch, args.n)[:, 0].contiguous().view(-1)
+            h = torch.empty_like(b1)
+            plan.forward(b1.data_ptr(), h.data_ptr(), 1, stream)
+        else:
+            h = torch.empty_like(b)
+            plan.forward(b.data_ptr(), h.data_ptr(), args.batch, stream)
+        hats[b.data_ptr()] = h
+    torch.cuda.synchronize()
+bhat_batch = 1 if args.bcast else args.batch
 
 
 def run(i):
     if sets:
         a, b = sets[i % len(sets)]
+        if args.op == "mulntt":
+            plan.polymul_ntt(a.data_ptr(), hats[b.data_ptr()].data_ptr(), cbuf.data_ptr(), args.batch, bhat_batch, stream)
+            return
         plan.polymul(a.data_ptr(), b.data_ptr(), cbuf.data_ptr(), scratch.data_ptr(), args.batch, stream)
         return
     a, b = slabs[i % args.slabs], slabs[(i + 1) % args.slabs]
@@ -57,8 +76,10 @@ def run(i):
         plan.forward(a.data_ptr(), dst.data_ptr(), args.batch, stream)
     elif args.op == "inv":
         plan.inverse(a.data_ptr(), dst.data_ptr(), args.batch, stream)
-    else:
+    elif args.op == "mul":
         plan.polymul(a.data_ptr(), b.data_ptr(), a.data_ptr(), scratch.data_ptr(), args.batch, stream)
+    else:
+        plan.polymul_ntt(a.data_ptr(), hats[b.data_ptr()].data_ptr(), a.data_ptr(), args.batch, bhat_batch, stream)
 
 
 import time  # noqa: E402

@@ -72,6 +72,15 @@ while time.time() - t0 < SECONDS:
             rows = slice(p * batch, (p + 1) * batch)
             want = np.concatenate([(np.uint64(q) - ar[rows, -1:]) % np.uint64(q), ar[rows, :-1]], axis=1)
             assert np.array_equal(c[rows], want), ("mul", n, bits, primes, batch)
+        # the same product with b given in NTT form, one frame per frame and (b is the same X in every frame) one shared frame per prime, in place
+        dbh, dc2 = dev.empty(a.size), dev.to_device(a)
+        plan.forward(db.data_ptr(), dbh.data_ptr(), batch, dev.stream)
+        plan.polymul_ntt(da.data_ptr(), dbh.data_ptr(), dc.data_ptr(), batch, batch, dev.stream)
+        dev.sync()
+        dbh1 = dbh.view(primes, batch, n)[:, 0].contiguous()
+        plan.polymul_ntt(dc2.data_ptr(), dbh1.data_ptr(), dc2.data_ptr(), batch, 1, dev.stream)
+        for got in (dev.to_host(dc), dev.to_host(dc2)):
+            assert np.array_equal(got, c.reshape(-1)), ("mulntt", n, bits, primes, batch)
         # squaring in place: (X^(n/2))^2 = X^n = -1
         h = np.zeros_like(a); h[n // 2::n] = 1
         dh = dev.to_device(h)
