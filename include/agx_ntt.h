@@ -132,7 +132,9 @@ AGX_API int agx_ntt_plan_get_modulus(const agx_ntt_plan* plan, uint32_t prime_in
 /* (3) Device-pointer batched transforms.  Frame (p, b) starts at              */
 /* base + p*prime_stride + b*poly_stride (strides in uint64_t elements);       */
 /* the dense forms use the [prime][batch][n] layout (prime_stride = batch*n,   */
-/* poly_stride = n).  In place (d_out == d_in) is allowed; an output whose     */
+/* poly_stride = n).  Base pointers need 8-byte alignment only (frames need    */
+/* not start on a 16-byte boundary), and strides may be odd.                   */
+/* In place (d_out == d_in) is allowed; an output whose                        */
 /* frames touch the input's frames without being the same frames (d_out =      */
 /* d_in + n/2, c = a + 8 ...) returns AGX_ERR_BAD_ARGUMENT: workgroups run in  */
 /* any order, so such a call would corrupt its own inputs.  A layout whose     */

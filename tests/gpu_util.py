@@ -44,6 +44,18 @@ def tables_for(orc, n, bits, count=1):
     return out
 
 
+def plan_from_oracle_tables(agx, orc, n, bits, count, inverse=True):
+    """(plan, tabs) for the `count` largest primes below 2^bits, the plan created from the oracle's own tables"""
+    tabs = tables_for(orc, n, bits, count)
+    tw = np.stack([t[2] for t in tabs])
+    pre = np.stack([t[3] for t in tabs])
+    tables = [tw, pre]
+    if inverse:
+        inv = [orc.make_inv_tables(t[0], t[1], n) for t in tabs]
+        tables += [np.stack([i[0] for i in inv]), np.stack([i[1] for i in inv])]
+    return agx.Plan(n, [t[0] for t in tabs], tables=tuple(tables)), tabs
+
+
 def oracle_polymul(orc, a, b, q, psi, n):
     """INTT(NTT(a) o NTT(b)) through the oracle's own transforms, frame by frame (operands may be lazy: reduced first)"""
     tw, pre = orc.make_tables(q, psi, n)
@@ -113,3 +125,165 @@ def boundary_frames(batch, extra=()):
         s |= {m - 1, m}
     s |= set(extra)
     return sorted(f for f in s if 0 <= f < batch)
+
+
+# ---------------------------------------------------------------------------------------
+# guarded arenas: where the words of a call live, and what a call must leave alone
+# ---------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(i):
+    """the splitmix64 output function of the uint64 indices i (numpy array), wrapping arithmetic"""
+    with np.errstate(over="ignore"):
+        z = (np.asarray(i, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)) & np.uint64(_M64)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def canary(first, count):
+    """canary[i] = splitmix64(i) | 2^63 for i = first .. first + count - 1.  Bit 63 keeps every word at or above 2^62, the bound of
+    the moduli, so no residue equals it; the words differ at every index, so canary data copied to another place is caught too"""
+    return splitmix64(np.arange(first, first + count, dtype=np.uint64)) | np.uint64(1 << 63)
+
+
+class Layout:
+    """where the frames of a [prime][batch][n] operand live: frame (p, b) starts at element offset + p * prime_stride + b * poly_stride of
+    the payload of an arena (the base pointer of the call is the payload's element `offset`)"""
+
+    def __init__(self, n, primes, batch, prime_stride=None, poly_stride=None, offset=0):
+        self.n, self.primes, self.batch = int(n), int(primes), int(batch)
+        self.poly_stride = self.n if poly_stride is None else int(poly_stride)
+        self.prime_stride = self.batch * self.n if prime_stride is None else int(prime_stride)
+        self.offset = int(offset)
+
+    def at(self, offset):
+        return Layout(self.n, self.primes, self.batch, self.prime_stride, self.poly_stride, offset)
+
+    def starts(self):
+        """payload index of the first word of every frame, [primes][batch]"""
+        p = np.arange(self.primes, dtype=np.int64)[:, None] * self.prime_stride
+        b = np.arange(self.batch, dtype=np.int64)[None, :] * self.poly_stride
+        return self.offset + p + b
+
+    def span(self):
+        """payload words from index 0 to the end of the last frame"""
+        return int(self.starts().max()) + self.n
+
+    def index(self):
+        """payload index of every frame word, [primes][batch][n]"""
+        return self.starts()[:, :, None] + np.arange(self.n, dtype=np.int64)[None, None, :]
+
+    def __repr__(self):
+        return (f"Layout(n={self.n}, primes={self.primes}, batch={self.batch}, prime_stride={self.prime_stride}, "
+                f"poly_stride={self.poly_stride}, offset={self.offset})")
+
+
+def scatter_frames(words, base, layout, frames):
+    """frames ([primes][batch][n], any shape of that size) -> words[base + layout.index()]"""
+    words[base + layout.index().reshape(-1)] = np.asarray(frames, dtype=np.uint64).reshape(-1)
+
+
+def gather_frames(words, base, layout):
+    """the frames of `layout` out of `words`, flat [primes][batch][n]"""
+    return words[base + layout.index().reshape(-1)].copy()
+
+
+def arena_faults(image, band, placed, limit=4):
+    """Compare an arena image (uint64 words: band | payload | band) with what it must hold: the canary at every word that belongs to no
+    frame, and, for every (layout, frames) of `placed` whose frames are not None, those frames.  Frames given as None are the call's
+    outputs: their words are not judged here.  Returns up to `limit` faults, lowest index first, each a dict with
+      index  -- payload index of the word (negative: leading band),   got / want -- the word found and the word expected,
+      prime, frame, rel -- the nearest frame and the word's position relative to its first word (rel < 0: before it, rel >= n: behind it)"""
+    image = np.asarray(image, dtype=np.uint64)
+    want = canary(0, image.size)
+    judged = np.ones(image.size, dtype=bool)
+    firsts, owners = [], []
+    n = None
+    for layout, frames in placed:
+        n = layout.n
+        idx = band + layout.index().reshape(-1)
+        if frames is None:
+            judged[idx] = False
+        else:
+            want[idx] = np.asarray(frames, dtype=np.uint64).reshape(-1)
+        st = layout.starts()
+        firsts.append(st.reshape(-1))
+        owners += [(p, b) for p in range(layout.primes) for b in range(layout.batch)]
+    bad = np.flatnonzero(judged & (image != want))[:limit]
+    if bad.size == 0:
+        return []
+    firsts = np.concatenate(firsts)
+    order = np.argsort(firsts, kind="stable")
+    out = []
+    for i in bad:
+        pay = int(i) - band
+        k = int(np.searchsorted(firsts[order], pay, side="right")) - 1        # last frame that starts at or before the word
+        cands = [c for c in (k, k + 1) if 0 <= c < order.size]
+
+        def distance(c):
+            s = int(firsts[order[c]])
+            return 0 if s <= pay < s + n else (s - pay if pay < s else pay - (s + n - 1))
+
+        c = min(cands, key=distance)
+        p, b = owners[int(order[c])]
+        out.append({"index": pay, "got": int(image[i]), "want": int(want[i]), "prime": p, "frame": b, "rel": pay - int(firsts[order[c]])})
+    return out
+
+
+class GuardedArena:
+    """One allocation = leading band | payload | trailing band, every word pre-filled with canary(index); the bands hold at least
+    max(4096, n) words each (an even count, so payload element 0 is as aligned as the allocation).  Frames are placed with place();
+    address(offset) is the base pointer of a call whose layout has that offset; faults() judges the words after the call.
+    On the host (dev=None) the words are a numpy array and address() points into it; with a DeviceHelper the words are uploaded by
+    commit() into one torch allocation (256-byte aligned) and faults() downloads them."""
+
+    def __init__(self, n, span, dev=None, band=None):
+        self.n = int(n)
+        self.band = max(4096, self.n) if band is None else int(band)
+        assert self.band >= max(4096, self.n) and self.band % 2 == 0
+        self.span = int(span)
+        self.words = canary(0, self.band + self.span + self.band)
+        self.dev = dev
+        self.tensor = None
+
+    def place(self, layout, frames):
+        assert layout.span() <= self.span and layout.offset >= 0
+        scatter_frames(self.words, self.band, layout, frames)
+        return self
+
+    def commit(self):
+        """upload the host image (device arenas only); the host copy stays as it was built"""
+        self.tensor = self.dev.to_device(self.words)
+        assert self.tensor.data_ptr() % 256 == 0
+        return self
+
+    def address(self, offset=0):
+        assert 0 <= offset <= self.span
+        if self.dev is None:
+            return self.words.ctypes.data + 8 * (self.band + offset)
+        return self.tensor.data_ptr() + 8 * (self.band + offset)
+
+    def view(self, offset, count):
+        """host arenas: the payload words offset .. offset + count - 1 as a numpy view (an `out=` argument)"""
+        assert self.dev is None and offset >= 0 and offset + count <= self.span
+        return self.words[self.band + offset:self.band + offset + count]
+
+    def image(self):
+        return self.words if self.dev is None else self.dev.to_host(self.tensor)
+
+    def frames(self, layout, image=None):
+        return gather_frames(self.image() if image is None else image, self.band, layout)
+
+    def faults(self, placed, image=None, limit=4):
+        return arena_faults(self.image() if image is None else image, self.band, placed, limit)
+
+
+def arena_for(dev, n, *placed):
+    """a committed arena that spans every layout of `placed` ((layout, frames or None), ...), the given frames placed"""
+    arena = GuardedArena(n, max(l.span() for l, _ in placed), dev)
+    for layout, frames in placed:
+        if frames is not None:
+            arena.place(layout, frames)
+    return arena.commit() if dev is not None else arena

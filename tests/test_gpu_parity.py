@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from gpu_util import oracle_polymul as _oracle_polymul
+from gpu_util import plan_from_oracle_tables as _plan_from_oracle_tables
 from gpu_util import rand_coeffs, tables_for
 
 pytestmark = pytest.mark.gpu
@@ -30,17 +31,6 @@ def _select(agx, plan, config):
         plan.close()
         pytest.skip(f"registry id {config} lives in lib/libagxntt_diag.so (covered by tests/test_gpu_diag.py)")
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + config)
-
-
-def _plan_from_oracle_tables(agx, orc, n, bits, count, inverse=True):
-    tabs = tables_for(orc, n, bits, count)
-    tw = np.stack([t[2] for t in tabs])
-    pre = np.stack([t[3] for t in tabs])
-    tables = [tw, pre]
-    if inverse:
-        inv = [orc.make_inv_tables(t[0], t[1], n) for t in tabs]
-        tables += [np.stack([i[0] for i in inv]), np.stack([i[1] for i in inv])]
-    return agx.Plan(n, [t[0] for t in tabs], tables=tuple(tables)), tabs
 
 
 def _oracle_forward_rns(orc, x, tabs, n, batch):
