@@ -1,14 +1,10 @@
 // ntt_kernels.hip -- gfx950 (CDNA4, wave64) kernels for the batched negacyclic NTT.
 //
-// Two families:
-//  * radix-2 / LDS-resident kernels: one workgroup per frame, one butterfly stage per barrier.
-//    They perform exactly the reference's operation sequence (src/kernel/ntt.cpp:147-180,
-//    298-300, 331-369, 377-394), so they are bit-identical to it even on out-of-contract
-//    tables.  Any power-of-two n; used for small n, as the always-available fallback and
-//    for the inverse transform.
-//  * register-blocked kernels: every thread keeps 2^R coefficients in VGPRs and runs R
-//    butterfly stages per pass with no memory traffic; passes exchange through one padded
-//    LDS slab.  This is the throughput path (n >= 32; their registry is rb_registry.hpp).
+// The radix-2 / LDS-resident kernels: one workgroup per frame, one butterfly stage per barrier.
+// They perform exactly the reference's operation sequence (src/kernel/ntt.cpp:147-180,
+// 298-300, 331-369, 377-394), so they are bit-identical to it even on out-of-contract
+// tables.  Any power-of-two n; the always-available fallback.  The register-blocked kernels
+// (the throughput path) live in rb_frame.hpp / rb_kernels.hpp and the reg_*.hip registry groups.
 //
 // No MFMA: this is 64-bit integer modular arithmetic (v_mad_u64_u32 / v_mul_hi_u32), bounded
 // by VALU integer multiply issue and HBM bandwidth.

@@ -153,11 +153,9 @@ struct rb32_frame {
                 constexpr int kk = R - 1 - rb;
                 constexpr bool last_stage = (rlo + rb) == 0;
                 static_for<0, C / 2>([&](auto B) {
-                    constexpr int b = B;
-                    constexpr int r0 = ((b >> rb) << (rb + 1)) | (b & ((1 << rb) - 1));
-                    constexpr int r1 = r0 | (1 << rb);
-                    constexpr int j = (1 << kk) + (r0 >> (rb + 1));
-                    a.ct(x[r0], x[r1], entry<p>(tbl, j));
+                    constexpr bf_regs bf = bf_pair<rb>(B);
+                    constexpr int r0 = bf.r0, r1 = bf.r1;
+                    a.ct(x[r0], x[r1], entry<p>(tbl, (1 << kk) + bf.o));
                     if constexpr (last_stage) {
                         x[r0] = a.final_fwd(x[r0], lazy_out);
                         x[r1] = a.final_fwd(x[r1], lazy_out);
@@ -181,11 +179,9 @@ struct rb32_frame {
                 constexpr int kk = R - 1 - rb;
                 constexpr bool top_stage = (rlo + rb) == L - 1;
                 static_for<0, C / 2>([&](auto B) {
-                    constexpr int b = B;
-                    constexpr int r0 = ((b >> rb) << (rb + 1)) | (b & ((1 << rb) - 1));
-                    constexpr int r1 = r0 | (1 << rb);
-                    if constexpr (top_stage) a.gs_last(x[r0], x[r1], ninv, w1n);
-                    else a.gs(x[r0], x[r1], entry<p>(itbl, (1 << kk) + (r0 >> (rb + 1))));
+                    constexpr bf_regs bf = bf_pair<rb>(B);
+                    if constexpr (top_stage) a.gs_last(x[bf.r0], x[bf.r1], ninv, w1n);
+                    else a.gs(x[bf.r0], x[bf.r1], entry<p>(itbl, (1 << kk) + bf.o));
                 });
             });
             if constexpr (p > 0) {

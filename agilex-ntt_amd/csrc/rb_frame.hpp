@@ -83,7 +83,7 @@ struct rb_geom {
 //    workgroup barrier (one wave's LDS operations execute in program order); which exchanges
 //    those are is decided at compile time by exchange_is_wave_local(): one s_barrier per frame;
 //  * LDS image padded by one word per 16 (default) so every exchange access is thread base +
-//    immediate offset; the XOR-swizzled image (conflict-free, exactly 8n bytes) is kept as an option;
+//    immediate offset (the XOR-swizzled image, conflict-free in exactly 8n bytes, was measured and removed in round 4);
 //  * results leave through the LDS image as coalesced stores (each wave owns a contiguous
 //    chunk of the frame after the first exchange); direct 16-byte strided stores measured 5 % slower.
 // ---------------------------------------------------------------------------------------
@@ -133,6 +133,35 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// B-th butterfly of a stage whose gap is register bit rb: registers (r0, r1) = B with a 0 / 1 inserted at bit rb, twiddle o of the stage's 2^kk
+// (table entry 2^kk + o, kk = R - 1 - rb)
+struct bf_regs {
+    int r0, r1, o;
+};
+template <int rb>
+constexpr bf_regs bf_pair(int b) {
+    const int r0 = ((b >> rb) << (rb + 1)) | (b & ((1 << rb) - 1));
+    return {r0, r0 | (1 << rb), b >> rb};
+}
+
+// 64-bit values through a 32-bit image of half the size, all but the last step: low words out at wr(r), `mid`, sync, low words in from rd(r) into lo,
+// sync, high words out, sync -- the caller then takes (uint64_t)lo[r] | (uint64_t)w[rd(r)] << 32.  Every lane is active in every step and no register
+// is needed beyond x and lo.  Three synchronisations instead of one: the middle one keeps anyone from overwriting low words that another thread has
+// not read yet (between full-word exchanges the "a thread overwrites only what it read" rule makes that unnecessary).
+struct no_op {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <int C, class WR, class RD, class SYNC, class MID = no_op>
+__device__ __forceinline__ void split_words_out(const uint64_t (&x)[C], uint32_t* w, uint32_t (&lo)[C], WR&& wr, RD&& rd, SYNC&& sync, MID&& mid = MID{}) {
+    static_for<0, C>([&](auto r) { w[wr(r)] = (uint32_t)x[r]; });
+    mid();
+    sync();
+    static_for<0, C>([&](auto r) { lo[r] = w[rd(r)]; });
+    sync();
+    static_for<0, C>([&](auto r) { w[wr(r)] = (uint32_t)(x[r] >> 32); });
+    sync();
+}
+
 // option bits of the kernels (the tuned sets are in the registry groups; values are stable: rocprof kernel names carry them)
 constexpr int kOptPad = 1;       // padded LDS image, exchanges addressed base + immediate offset
 constexpr int kOptSelect = 2;    // conditional subtract by compare + select instead of sign mask
@@ -171,23 +200,23 @@ template <int L, int R, bool FAST, int OPT = 0>
 struct rb2_frame {
     using G = rb2_geom<L, R>;
     static constexpr int C = G::C, T = G::T, NP = G::NP;
-    static constexpr bool SEL = (OPT & kOptSelect) != 0, LAZY16 = FAST && (OPT & kOptLazy16) != 0;
+    static constexpr bool FAST_ARITH = FAST, SEL = (OPT & kOptSelect) != 0, LAZY16 = FAST && (OPT & kOptLazy16) != 0;
     static_assert((OPT & kOptPad) != 0, "every kernel uses the padded image");
     static constexpr bool TWA = (OPT & kOptTwAhead) != 0 && R >= 3;
     static constexpr bool TRACE = (OPT & kOptTrace) != 0;
     static constexpr bool PRIO = (OPT & kOptPrio) != 0;
     static constexpr bool PRIO_BARRIER = PRIO && (OPT & kOptPrioBarrier) != 0, SCALAR_BASE = (OPT & kOptScalarBase) != 0;
     static constexpr bool LAZY_INV = LAZY16 && (OPT & kOptLazyInv) != 0;
-    static constexpr bool NT_LOAD = (OPT & kOptNtLoad) != 0;
+    static constexpr bool NT_LOAD = (OPT & kOptNtLoad) != 0, NT_STORE = (OPT & kOptNtStore) != 0;
     static constexpr bool TWA_INV = (OPT & kOptTwAheadInv) != 0 && R == 3;
     static constexpr bool EST = LAZY16 && SEL && (OPT & kOptEstReduce) != 0;
     static constexpr bool SPLIT = (OPT & kOptSplitWord) != 0;
-    static constexpr bool STREAM_TW = (OPT & kOptStreamTw) != 0;
-    static constexpr bool SADDR_TW = STREAM_TW, FINAL_MODE = STREAM_TW;
+    static constexpr bool STREAM_TW = (OPT & kOptStreamTw) != 0, PIN_BF = (OPT & kOptPinBf) != 0, STREAM_CH1 = (OPT & kOptStreamCh1) != 0;
     static_assert(!EST || lazy16_tailfree::valid(L), "tail-free schedule must keep every stage within 16q");
     mutable uint64_t ts[12];
-    uint64_t trace_wave = ~0ull;   // row of the trace buffer (default: launch-wide wave number)
-    bool trace_wait_stores = true; // stamp 11 after the stores have retired (not in the streaming kernel: that would drain its prefetch)
+    // kept old form: polymul_wp<1, 1, 1, kWpExact, 5> -- without these two members (dead since round 4) b's frame load moves ahead of NTT(a)'s address arithmetic
+    uint64_t trace_wave = ~0ull;
+    bool trace_wait_stores = true;
     // phase stamp I, ordered after `anchor` is available and before anything that uses it afterwards
     template <int I>
     __device__ __forceinline__ void stamp(uint64_t& anchor) const {
@@ -202,8 +231,7 @@ struct rb2_frame {
         static_assert(!TRACE, "kOptTrace kernels belong to the diagnostics library (AGX_DIAG): the product library has no trace buffer");
 #else
         if constexpr (TRACE) {
-            const uint64_t wave = trace_wave != ~0ull ? trace_wave
-                                                      : ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+            const uint64_t wave = ((uint64_t)blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);      // row of the trace buffer
             if ((threadIdx.x & 63u) == 0 && g_trace_buf != nullptr && wave < g_trace_waves) {
                 uint64_t* dst = g_trace_buf + wave * 16;
 #pragma unroll
@@ -219,13 +247,12 @@ struct rb2_frame {
     // pad: one image word per 16 coefficients for the 64-bit image (ds_read_b64: 64 banks), one per 32 for the split-word image, whose
     // 32-bit accesses see 32 banks per group of 32 lanes: with it every exchange pattern of the R = 5 kernels is conflict-free, with one
     // per 16 every one of them was two-way conflicted (SQ_LDS_BANK_CONFLICT 45 % of the LDS cycles, profiles/r03c_fwd4096_summary.md)
-    static constexpr int PADS = (OPT & kOptSplitWord) != 0 ? 5 : 4;
+    static constexpr int PADS = SPLIT ? 5 : 4;
     static constexpr uint32_t slab_elems = (1u << L) + (L >= PADS ? (1u << (L >= PADS ? L - PADS : 0)) : 0u);      // frames below 2^PADS coefficients (wave-packed kernels, one lane per frame) never exchange: no pad of their own
-    static constexpr uint32_t image_bytes = slab_elems * (((OPT & kOptSplitWord) != 0) ? 4u : 8u);   // one frame's LDS image
+    static constexpr uint32_t image_bytes = slab_elems * (SPLIT ? 4u : 8u);   // one frame's LDS image
     // image word of coefficient e: additive over disjoint bit fields, which is what lets an exchange address
     // register r as (thread base) + compile-time constant
     static __device__ __forceinline__ constexpr uint32_t img(uint32_t e) { return e + (e >> PADS); }
-    static __device__ __forceinline__ constexpr uint32_t join(uint32_t base, uint32_t delta) { return base + delta; }
     uint32_t tid;
     bool lazy_out = false;   // forward only: leave results in [0,4q) (wave-uniform)
     uint64_t* slab;
@@ -257,6 +284,43 @@ struct rb2_frame {
         else ct_butterfly_exact(a, b, w.x, w.y, k);
     }
 
+    // ... followed, in the transform's last stage, by the final reduction in mode MODE (final_reduce below)
+    template <int stage, int MODE>
+    __device__ __forceinline__ void forward_step(uint64_t& a, uint64_t& b, const twpair& w) const {
+        butterfly<stage>(a, b, w);
+        if constexpr (stage == L - 1) {
+            a = final_reduce<MODE>(a);
+            b = final_reduce<MODE>(b);
+        }
+    }
+    // inverse butterfly of the stage with gap bit `gap` on registers that enter below BND q (16q-lazy form); tw() yields the twiddle, which the top
+    // stage does not read: it multiplies by n^-1 / n^-1 w instead and reduces fully
+    template <int gap, int BND, class TW>
+    __device__ __forceinline__ void inverse_step(uint64_t& a, uint64_t& b, const prime_consts& pc, TW&& tw) const {
+        if constexpr (gap == L - 1) {
+            if constexpr (LAZY_INV) gs_last_lazy16<BND, SEL>(a, b, pc.n_inv, pc.n_inv_p, pc.w1n, pc.w1n_p, k, fc);
+            else gs_last_form<FAST>(a, b, pc.n_inv, pc.n_inv_p, pc.w1n, pc.w1n_p, k);
+            a = reduce_final_inv<FAST, SEL>(a, k, fc);
+            b = reduce_final_inv<FAST, SEL>(b, k, fc);
+        } else {
+            const twpair w = tw();
+            if constexpr (LAZY_INV) gs_butterfly_lazy16<BND, SEL>(a, b, w.x, w.y, k, fc);
+            else gs_butterfly_form<FAST, SEL>(a, b, w.x, w.y, k);
+        }
+    }
+    // 16q-lazy inverse: every register of the first pass (p = NP - 1) starts below 4q, of the later ones below 8q ...
+    static constexpr int inv_b0(int p) { return p == NP - 1 ? 4 : 8; }
+    // ... so after pass p the registers that ended at 16q come back below 8q for the next one
+    template <int p>
+    __device__ __forceinline__ void inverse_pass_cleanup(uint64_t (&x)[C]) const {
+        if constexpr (LAZY_INV && p > 0) {
+            static_for<0, C>([&](auto Rr) {
+                constexpr int r = Rr;
+                if constexpr (gs_bound(inv_b0(p), G::hi(p) - G::rlo(p) + 1, r) == 16) x[r] = csub_8q<SEL>(x[r], fc);
+            });
+        }
+    }
+
     // final reduction of one coefficient.  MODE bit 0: lazy outputs; bit 1: quotient estimate (EST kernels, q >= 2^58).  The caller branches ONCE per group of butterflies on the wave-uniform conditions (lazy_out, est_inv) and
     // passes the outcome here as a constant, so the last stage is straight-line code (a branch per coefficient splits it into dozens of
     // basic blocks, which costs registers: R = 5 kernels went from 204 to the VGPRs of the arithmetic proper).
@@ -274,7 +338,7 @@ struct rb2_frame {
     // run body(integral_constant<int, MODE>) under the wave-uniform choice of the final-reduction mode
     template <class Body>
     __device__ __forceinline__ void with_final_mode(Body&& body) const {
-        if constexpr (!FINAL_MODE) {
+        if constexpr (!STREAM_TW) {
             body(std::integral_constant<int, 4>{});      // the kernels tuned at the 64-VGPR edge keep the per-coefficient form
             return;
         }
@@ -331,7 +395,7 @@ struct rb2_frame {
     template <int p>
     __device__ __forceinline__ twpair lane_entry(const twpair* tbl, int j) const {
         constexpr int rlo = G::rlo(p), H = G::H(p);
-        if constexpr (!SADDR_TW) {
+        if constexpr (!STREAM_TW) {
             const twpair* col = tbl + G::table_off(p) + (tid >> rlo);
             return col[(size_t)j * (uint32_t)H];
         }
@@ -347,12 +411,12 @@ struct rb2_frame {
     template <int p>
     __device__ __forceinline__ void image_read(uint64_t (&x)[C]) const {
         const uint32_t sb = sbase<p>();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = slab[join(sb, img((uint32_t)r << G::rlo(p)))]; });
+        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = slab[sb + img((uint32_t)r << G::rlo(p))]; });
     }
     template <int p>
     __device__ __forceinline__ void image_write(const uint64_t (&x)[C]) const {
         const uint32_t sb = sbase<p>();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; slab[join(sb, img((uint32_t)r << G::rlo(p)))] = x[r]; });
+        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; slab[sb + img((uint32_t)r << G::rlo(p))] = x[r]; });
     }
     // order the read side of the exchange between passes p and p+1 (either direction)
     template <int p>
@@ -361,23 +425,16 @@ struct rb2_frame {
         else wave_lds_sync();
     }
 
-    // SPLIT: the whole exchange between passes p and p+1 through a 32-bit image -- low words out, low words in, high words
-    // out, high words in.  The image holds n words of 4 bytes; every lane is active in every step and no register is
-    // needed beyond x.  Three synchronisations instead of one: the middle one keeps anyone from overwriting low words
-    // that another thread has not read yet (between full exchanges the "a thread overwrites only what it read" rule
-    // makes that unnecessary).
-    template <int p>
+    // SPLIT: the whole exchange from pass `from` to its neighbour `to` (forward: from + 1, inverse: from - 1) through the 32-bit image of n words
+    template <int from, int to>
     __device__ __forceinline__ void split_exchange(uint64_t (&x)[C]) const {
+        static_assert(to == from + 1 || to == from - 1, "neighbouring passes");
         uint32_t* w = reinterpret_cast<uint32_t*>(slab);
-        const uint32_t sb = sbase<p>(), nb = sbase<p + 1>();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[join(sb, img((uint32_t)r << G::rlo(p)))] = (uint32_t)x[r]; });
-        exchange_sync<p>();
+        const uint32_t sb = sbase<from>(), nb = sbase<to>();
+        auto rd = [&](auto r) { return nb + img((uint32_t)r << G::rlo(to)); };
         uint32_t lo[C];
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; lo[r] = w[join(nb, img((uint32_t)r << G::rlo(p + 1)))]; });
-        exchange_sync<p>();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[join(sb, img((uint32_t)r << G::rlo(p)))] = (uint32_t)(x[r] >> 32); });
-        exchange_sync<p>();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = (uint64_t)lo[r] | ((uint64_t)w[join(nb, img((uint32_t)r << G::rlo(p + 1)))] << 32); });
+        split_words_out(x, w, lo, [&](auto r) { return sb + img((uint32_t)r << G::rlo(from)); }, rd, [&] { exchange_sync<(from < to ? from : to)>(); });
+        static_for<0, C>([&](auto r) { x[r] = (uint64_t)lo[r] | ((uint64_t)w[rd(r)] << 32); });
     }
 
     // forward passes [P0, P1): pass P0 reads the image unless it is pass 0 (x already holds the
@@ -386,7 +443,7 @@ struct rb2_frame {
     // ---- streamed twiddles (STREAM_TW) -------------------------------------------------------------------------------
     // A pass of ns stages reads, at its stage S, the 2^kk table entries j = 2^kk + o (kk = R - ns + S, o = b >> rb for butterfly b):
     // they are taken in chunks of up to CH entries, in stage order; chunk q+1 is requested before chunk q's butterflies run.
-    static constexpr int CH = (OPT & kOptStreamCh1) != 0 ? 1 : R >= 5 ? 2 : 4;      // R = 5: two entries (8 VGPRs per buffer) keep the pass inside 128 VGPRs
+    static constexpr int CH = STREAM_CH1 ? 1 : R >= 5 ? 2 : 4;      // R = 5: two entries (8 VGPRs per buffer) keep the pass inside 128 VGPRs
     // forward: stage S of a pass has kk = R - ns + S (1, 2, 4 ... entries); inverse (INV): stages run the other way, kk = R - 1 - S
     static constexpr int st_kk(int ns, int S, bool inv = false) { return inv ? R - 1 - S : R - ns + S; }
     static constexpr int st_chunks_in_stage(int ns, int S, bool inv = false) { return (1 << st_kk(ns, S, inv)) > CH ? (1 << st_kk(ns, S, inv)) / CH : 1; }
@@ -426,17 +483,11 @@ struct rb2_frame {
                 __builtin_amdgcn_sched_barrier(0);
                 auto chunk_body = [&](auto M) {
                     static_for<(cc * CH) << rb, (cc * CH + cnt) << rb>([&](auto B) {
-                        constexpr int b = B;
-                        constexpr int r0 = ((b >> rb) << (rb + 1)) | (b & ((1 << rb) - 1));
-                        constexpr int r1 = r0 | (1 << rb);
-                        constexpr int stage = L - 1 - (rlo + rb);
-                        if constexpr ((OPT & kOptPinBf) != 0) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
-                        butterfly<stage>(x[r0], x[r1], buf[q & 1].e[(b >> rb) - cc * CH]);
-                        if constexpr (last_stage) {
-                            x[r0] = final_reduce<decltype(M)::value>(x[r0]);
-                            x[r1] = final_reduce<decltype(M)::value>(x[r1]);
-                        }
-                        if constexpr ((OPT & kOptPinBf) != 0) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
+                        constexpr bf_regs bf = bf_pair<rb>(B);
+                        constexpr int r0 = bf.r0, r1 = bf.r1;
+                        if constexpr (PIN_BF) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
+                        forward_step<L - 1 - (rlo + rb), decltype(M)::value>(x[r0], x[r1], buf[q & 1].e[bf.o - cc * CH]);
+                        if constexpr (PIN_BF) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
                     });
                 };
                 if constexpr (last_stage) with_final_mode(chunk_body);
@@ -444,7 +495,7 @@ struct rb2_frame {
                 __builtin_amdgcn_sched_barrier(0);
             });
             if constexpr (p < NP - 1) {
-                if constexpr (SPLIT) split_exchange<p>(x);
+                if constexpr (SPLIT) split_exchange<p, p + 1>(x);
                 else {
                     image_write<p>(x);
                     exchange_sync<p>();
@@ -496,21 +547,13 @@ struct rb2_frame {
                 // the transform's last stage: one wave-uniform branch around the whole stage picks the final-reduction mode
                 auto stage_body = [&](auto M) {
                     static_for<0, C / 2>([&](auto B) {
-                        // B-th butterfly of the stage: insert a 0 at register bit rb
-                        constexpr int b = B;
-                        constexpr int r0 = ((b >> rb) << (rb + 1)) | (b & ((1 << rb) - 1));
-                        constexpr int r1 = r0 | (1 << rb);
-                        constexpr int j = (1 << kk) + (r0 >> (rb + 1));
+                        constexpr bf_regs bf = bf_pair<rb>(B);
+                        constexpr int j = (1 << kk) + bf.o;
                         twpair w;
                         if constexpr (twa_here && j < C / 2) w = ahead[j];
                         else if constexpr (twa_here) w = late[j - C / 2];
                         else w = twiddle<p>(t, j);
-                        constexpr int stage = L - 1 - (rlo + rb);   // position in the whole transform
-                        butterfly<stage>(x[r0], x[r1], w);
-                        if constexpr (last_stage) {
-                            x[r0] = final_reduce<decltype(M)::value>(x[r0]);
-                            x[r1] = final_reduce<decltype(M)::value>(x[r1]);
-                        }
+                        forward_step<L - 1 - (rlo + rb), decltype(M)::value>(x[bf.r0], x[bf.r1], w);   // stage = position in the whole transform
                     });
                 };
                 if constexpr (last_stage) with_final_mode(stage_body);
@@ -522,7 +565,7 @@ struct rb2_frame {
                 // thread can still need them: only the read side of an exchange has to be ordered.
                 if constexpr (SPLIT) {
                     static_assert(!SPLIT || (P0 == 0 && P1 == NP), "split-word exchanges run the whole transform in one call");
-                    split_exchange<p>(x);
+                    split_exchange<p, p + 1>(x);
                     if constexpr (PRIO_BARRIER && !G::exchange_is_wave_local(p)) __builtin_amdgcn_s_setprio(0);
                 } else {
                 image_write<p>(x);
@@ -540,29 +583,12 @@ struct rb2_frame {
         forward_passes<0, NP>(x, tbl);
     }
 
-    static constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v >> 1); }
-    // SPLIT: the exchange between inverse passes p and p-1 through the 32-bit image (the mirror of split_exchange)
-    template <int p>
-    __device__ __forceinline__ void split_exchange_inv(uint64_t (&x)[C]) const {
-        uint32_t* w = reinterpret_cast<uint32_t*>(slab);
-        const uint32_t sb = sbase<p>(), nb = sbase<p - 1>();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[join(sb, img((uint32_t)r << G::rlo(p)))] = (uint32_t)x[r]; });
-        exchange_sync<p - 1>();
-        uint32_t lo[C];
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; lo[r] = w[join(nb, img((uint32_t)r << G::rlo(p - 1)))]; });
-        exchange_sync<p - 1>();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[join(sb, img((uint32_t)r << G::rlo(p)))] = (uint32_t)(x[r] >> 32); });
-        exchange_sync<p - 1>();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = (uint64_t)lo[r] | ((uint64_t)w[join(nb, img((uint32_t)r << G::rlo(p - 1)))] << 32); });
-    }
-
     // STREAM_TW form of the inverse (whole frames only: split_log = 0, so the top stage folds n^-1 in): twiddles in chunks, one chunk
     // ahead, butterflies pinned in program order (kOptPinBf) -- see forward_passes_streamed
     __device__ __forceinline__ void inverse_streamed(uint64_t (&x)[C], const twpair* itbl, const prime_consts& pc) const {
         static_for<0, NP>([&](auto Qp) {
             constexpr int p = NP - 1 - Qp;
             constexpr int rlo = G::rlo(p), hi = G::hi(p), ns = hi - rlo + 1, NQ = st_total(ns, true);
-            constexpr int B0 = (p == NP - 1) ? 4 : 8;
             tw_src<p> t;
             fetch<p>(t, itbl);
             tw_chunk buf[2];
@@ -572,37 +598,20 @@ struct rb2_frame {
                 constexpr int q = Qc;
                 constexpr int S = st_stage(ns, q, true), cc = st_chunk(ns, q, true), cnt = st_count(ns, S, true);
                 constexpr int rb = S;                         // gap bits ascend
-                constexpr bool top_stage = (rlo + rb) == L - 1;
                 if constexpr (q + 1 < NQ) stream_load<p, q + 1, true>(buf[(q + 1) & 1], t);
                 __builtin_amdgcn_sched_barrier(0);
                 static_for<(cc * CH) << rb, (cc * CH + cnt) << rb>([&](auto Bf) {
-                    constexpr int b = Bf;
-                    constexpr int r0 = ((b >> rb) << (rb + 1)) | (b & ((1 << rb) - 1));
-                    constexpr int r1 = r0 | (1 << rb);
-                    constexpr int BND = gs_bound(B0, rb, r0);
-                    if constexpr ((OPT & kOptPinBf) != 0) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
-                    if constexpr (top_stage) {
-                        if constexpr (LAZY_INV) gs_last_lazy16<BND, SEL>(x[r0], x[r1], pc.n_inv, pc.n_inv_p, pc.w1n, pc.w1n_p, k, fc);
-                        else gs_last_form<FAST>(x[r0], x[r1], pc.n_inv, pc.n_inv_p, pc.w1n, pc.w1n_p, k);
-                        x[r0] = reduce_final_inv<FAST, SEL>(x[r0], k, fc);
-                        x[r1] = reduce_final_inv<FAST, SEL>(x[r1], k, fc);
-                    } else {
-                        const twpair w = buf[q & 1].e[(b >> rb) - cc * CH];
-                        if constexpr (LAZY_INV) gs_butterfly_lazy16<BND, SEL>(x[r0], x[r1], w.x, w.y, k, fc);
-                        else gs_butterfly_form<FAST, SEL>(x[r0], x[r1], w.x, w.y, k);
-                    }
-                    if constexpr ((OPT & kOptPinBf) != 0) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
+                    constexpr bf_regs bf = bf_pair<rb>(Bf);
+                    constexpr int r0 = bf.r0, r1 = bf.r1;
+                    if constexpr (PIN_BF) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
+                    inverse_step<rlo + rb, gs_bound(inv_b0(p), rb, r0)>(x[r0], x[r1], pc, [&] { return buf[q & 1].e[bf.o - cc * CH]; });
+                    if constexpr (PIN_BF) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
                 });
                 __builtin_amdgcn_sched_barrier(0);
             });
-            if constexpr (LAZY_INV && p > 0) {
-                static_for<0, C>([&](auto Rr) {
-                    constexpr int r = Rr;
-                    if constexpr (gs_bound(B0, ns, r) == 16) x[r] = csub_8q<SEL>(x[r], fc);
-                });
-            }
+            inverse_pass_cleanup<p>(x);
             if constexpr (p > 0) {
-                if constexpr (SPLIT) split_exchange_inv<p>(x);
+                if constexpr (SPLIT) split_exchange<p, p - 1>(x);
                 else {
                     image_write<p>(x);
                     exchange_sync<p - 1>();
@@ -630,52 +639,45 @@ struct rb2_frame {
                 image_read<p>(x);
                 if constexpr (2 + 2 * Q < 12) stamp<2 + 2 * Q>(x[C - 1]);     // trace: exchange done (Q = passes completed)
             }
-            // 16q-lazy form: every register of the first pass starts below 4q, of the later ones below 8q
-            constexpr int B0 = (p == NP - 1) ? 4 : 8;
             static_for<0, hi - rlo + 1>([&](auto S) {
                 constexpr int rb = S;                     // gap bits ascend
                 constexpr int kk = R - 1 - rb;
-                constexpr bool top_stage = (rlo + rb) == L - 1;
                 if constexpr (twa_next && S == hi - rlo) {
                     // `first` is free: this pass's first stage is long done
                     constexpr int pn = p - 1;
                     static_for<0, 4>([&](auto J) { constexpr int jj = J; first[jj] = lane_entry<pn>(itbl, jj + 4); });
                 }
                 static_for<0, C / 2>([&](auto Bf) {
-                    constexpr int b = Bf;
-                    constexpr int r0 = ((b >> rb) << (rb + 1)) | (b & ((1 << rb) - 1));
-                    constexpr int r1 = r0 | (1 << rb);
-                    constexpr int BND = gs_bound(B0, rb, r0);
-                    if constexpr (top_stage) {
-                        if constexpr (LAZY_INV) gs_last_lazy16<BND, SEL>(x[r0], x[r1], pc.n_inv, pc.n_inv_p, pc.w1n, pc.w1n_p, k, fc);
-                        else gs_last_form<FAST>(x[r0], x[r1], pc.n_inv, pc.n_inv_p, pc.w1n, pc.w1n_p, k);
-                    } else {
-                        constexpr int j = (1 << kk) + (r0 >> (rb + 1));
-                        twpair w;
-                        if constexpr (twa_have && j >= 4) w = first[j - 4];
-                        else w = twiddle<p>(t, j);
-                        if constexpr (LAZY_INV) gs_butterfly_lazy16<BND, SEL>(x[r0], x[r1], w.x, w.y, k, fc);
-                        else gs_butterfly_form<FAST, SEL>(x[r0], x[r1], w.x, w.y, k);
-                    }
-                    if constexpr (top_stage) {
-                        x[r0] = reduce_final_inv<FAST, SEL>(x[r0], k, fc);
-                        x[r1] = reduce_final_inv<FAST, SEL>(x[r1], k, fc);
-                    }
+                    constexpr bf_regs bf = bf_pair<rb>(Bf);
+                    constexpr int j = (1 << kk) + bf.o;
+                    inverse_step<rlo + rb, gs_bound(inv_b0(p), rb, bf.r0)>(x[bf.r0], x[bf.r1], pc, [&] {
+                        if constexpr (twa_have && j >= 4) return first[j - 4];
+                        else return twiddle<p>(t, j);
+                    });
                 });
             });
             if constexpr (3 + 2 * Q < 12) stamp<3 + 2 * Q>(x[C - 1]);       // trace: this pass's butterflies done
-            if constexpr (LAZY_INV && p > 0) {
-                // the next pass assumes 8q: bring the registers that ended at 16q back
-                static_for<0, C>([&](auto Rr) {
-                    constexpr int r = Rr;
-                    if constexpr (gs_bound(B0, hi - rlo + 1, r) == 16) x[r] = csub_8q<SEL>(x[r], fc);
-                });
-            }
+            inverse_pass_cleanup<p>(x);
             if constexpr (p > 0) {
                 image_write<p>(x);
                 exchange_sync<p - 1>();
             }
         });
+    }
+
+    // pass-0 layout (register r = element tid + r T) <-> global memory
+    __device__ __forceinline__ void load_pass0(uint64_t (&x)[C], const uint64_t* p, int64_t base) const {
+#pragma unroll
+        for (int r = 0; r < C; ++r) x[r] = NT_LOAD ? __builtin_nontemporal_load(&p[base + tid + (uint32_t)r * T]) : p[base + tid + (uint32_t)r * T];
+    }
+    __device__ __forceinline__ void store_pass0(const uint64_t (&x)[C], uint64_t* p, int64_t base, bool live = true) const {
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < C; ++r) {
+                if constexpr (NT_STORE) __builtin_nontemporal_store(x[r], &p[base + tid + (uint32_t)r * T]);
+                else p[base + tid + (uint32_t)r * T] = x[r];
+            }
+        }
     }
 
     // last-pass layout <-> lane-contiguous global accesses, through the image (wave-local: after
@@ -686,34 +688,31 @@ struct rb2_frame {
             uint32_t* w = reinterpret_cast<uint32_t*>(slab);
             const uint32_t own32 = img(tid << R);
             const uint32_t e0 = ((tid >> 6) << (6 + R)) + (tid & 63u), s0 = img(e0);
-            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[join(own32, img((uint32_t)r))] = (uint32_t)x[r]; });
-            wave_lds_sync();
             uint32_t lo[C];
-            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; lo[r] = w[join(s0, img(64u * (uint32_t)r))]; });
-            wave_lds_sync();
-            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[join(own32, img((uint32_t)r))] = (uint32_t)(x[r] >> 32); });
-            wave_lds_sync();
+            split_words_out(x, w, lo, [&](auto r) { return own32 + img((uint32_t)r); }, [&](auto r) { return s0 + img(64u * (uint32_t)r); }, [] { wave_lds_sync(); });
             if (live) {
                 static_for<0, C>([&](auto Rr) {
                     constexpr int r = Rr;
-                    const uint64_t v = (uint64_t)lo[r] | ((uint64_t)w[join(s0, img(64u * (uint32_t)r))] << 32);
-                    if constexpr ((OPT & kOptNtStore) != 0) __builtin_nontemporal_store(v, &out[base + e0 + 64u * (uint32_t)r]);
+                    const uint64_t v = (uint64_t)lo[r] | ((uint64_t)w[s0 + img(64u * (uint32_t)r)] << 32);
+                    if constexpr (NT_STORE) __builtin_nontemporal_store(v, &out[base + e0 + 64u * (uint32_t)r]);
                     else out[base + e0 + 64u * (uint32_t)r] = v;
                 });
             }
             return;
         }
+        // kept old form (here and in load_last_stage's full-word branch): as one write / sync / read primitive with the image bases computed up front,
+        // fwd_rb2 and inv_rb2 are rescheduled (the bases belong behind the wave barrier)
         const uint32_t own = img(tid << R);
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; slab[join(own, img((uint32_t)r))] = x[r]; });
+        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; slab[own + img((uint32_t)r)] = x[r]; });
         wave_lds_sync();
         if constexpr (TRACE) {
             const uint32_t e0 = ((tid >> 6) << (6 + R)) + (tid & 63u), s0 = img(e0);
             uint64_t y[C];
-            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; y[r] = slab[join(s0, img(64u * (uint32_t)r))]; });
+            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; y[r] = slab[s0 + img(64u * (uint32_t)r)]; });
             stamp<9>(y[C - 1]);
             if (live) static_for<0, C>([&](auto Rr) { constexpr int r = Rr; out[base + e0 + 64u * (uint32_t)r] = y[r]; });
             stamp<10>(y[0]);
-            if (trace_wait_stores) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // stamp 11 after the stores have retired
             stamp<11>(y[0]);
             trace_flush();
             return;
@@ -722,17 +721,10 @@ struct rb2_frame {
             const uint32_t e0 = ((tid >> 6) << (6 + R)) + (tid & 63u), s0 = img(e0);
             static_for<0, C>([&](auto Rr) {
                 constexpr int r = Rr;
-                if constexpr ((OPT & kOptNtStore) != 0) __builtin_nontemporal_store(slab[join(s0, img(64u * (uint32_t)r))], &out[base + e0 + 64u * (uint32_t)r]);
-                else out[base + e0 + 64u * (uint32_t)r] = slab[join(s0, img(64u * (uint32_t)r))];
+                if constexpr (NT_STORE) __builtin_nontemporal_store(slab[s0 + img(64u * (uint32_t)r)], &out[base + e0 + 64u * (uint32_t)r]);
+                else out[base + e0 + 64u * (uint32_t)r] = slab[s0 + img(64u * (uint32_t)r)];
             });
         }
-    }
-    // `in2` (may be null): the coefficient-wise product in * in2 mod q is taken while loading, so a
-    // polynomial product needs no separate pointwise pass before its inverse transform
-    __device__ __forceinline__ void load_last_layout(uint64_t (&x)[C], const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2,
-                                                     const barrett128& bk, int64_t base) const {
-        load_last_issue(x, in, base);
-        load_last_stage(x, in2, bk, base);
     }
     // first half: the frame's lane-contiguous global loads (no LDS traffic yet, so a loop kernel can put its
     // image hand-over barrier between the two halves, behind the load latency)
@@ -740,9 +732,10 @@ struct rb2_frame {
         const uint32_t e0 = ((tid >> 6) << (6 + R)) + (tid & 63u);
 #pragma unroll
         for (int r = 0; r < C; ++r)
-            x[r] = (OPT & kOptNtLoad) ? __builtin_nontemporal_load(&in[base + e0 + 64u * (uint32_t)r]) : in[base + e0 + 64u * (uint32_t)r];
+            x[r] = NT_LOAD ? __builtin_nontemporal_load(&in[base + e0 + 64u * (uint32_t)r]) : in[base + e0 + 64u * (uint32_t)r];
     }
-    // second half: optional coefficient-wise product with in2, staging through the wave's own part of the image
+    // second half: optional coefficient-wise product with in2 (may be null: in * in2 mod q is taken while loading, so a polynomial product needs
+    // no separate pointwise pass before its inverse transform), staging through the wave's own part of the image
     __device__ __forceinline__ void load_last_stage(uint64_t (&x)[C], const uint64_t* __restrict__ in2, const barrett128& bk, int64_t base) const {
         const uint32_t e0 = ((tid >> 6) << (6 + R)) + (tid & 63u), s0 = img(e0);
         if constexpr (SPLIT) {
@@ -753,38 +746,34 @@ struct rb2_frame {
             for (int r = 0; r < C; ++r) {
                 uint64_t v = x[r];
                 if (in2) {   // wave-uniform
-                    const uint64_t u = (OPT & kOptNtLoad) ? __builtin_nontemporal_load(&in2[base + e0 + 64u * (uint32_t)r]) : in2[base + e0 + 64u * (uint32_t)r];
+                    const uint64_t u = NT_LOAD ? __builtin_nontemporal_load(&in2[base + e0 + 64u * (uint32_t)r]) : in2[base + e0 + 64u * (uint32_t)r];
                     v = mul_mod_barrett(reduce_4q(v, k.q, k.q << 1), reduce_4q(u, k.q, k.q << 1), bk);
                 }
                 if constexpr (!FAST) v = csub(v, k.m);
                 x[r] = v;
             }
-            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[join(s0, img(64u * (uint32_t)r))] = (uint32_t)x[r]; });
-            if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
-            wave_lds_sync();
             uint32_t lo[C];
-            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; lo[r] = w[join(own32, img((uint32_t)r))]; });
-            wave_lds_sync();
-            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[join(s0, img(64u * (uint32_t)r))] = (uint32_t)(x[r] >> 32); });
-            wave_lds_sync();
-            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = (uint64_t)lo[r] | ((uint64_t)w[join(own32, img((uint32_t)r))] << 32); });
+            split_words_out(
+                x, w, lo, [&](auto r) { return s0 + img(64u * (uint32_t)r); }, [&](auto r) { return own32 + img((uint32_t)r); }, [] { wave_lds_sync(); },
+                [] { if constexpr (PRIO) __builtin_amdgcn_s_setprio(0); });
+            static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = (uint64_t)lo[r] | ((uint64_t)w[own32 + img((uint32_t)r)] << 32); });
             return;
         }
 #pragma unroll
         for (int r = 0; r < C; ++r) {
             uint64_t v = x[r];
             if (in2) {   // wave-uniform
-                const uint64_t u = (OPT & kOptNtLoad) ? __builtin_nontemporal_load(&in2[base + e0 + 64u * (uint32_t)r]) : in2[base + e0 + 64u * (uint32_t)r];
+                const uint64_t u = NT_LOAD ? __builtin_nontemporal_load(&in2[base + e0 + 64u * (uint32_t)r]) : in2[base + e0 + 64u * (uint32_t)r];
                 v = mul_mod_barrett(reduce_4q(v, k.q, k.q << 1), reduce_4q(u, k.q, k.q << 1), bk);
             }
             if constexpr (!FAST) v = csub(v, k.m);    // exact form wants [0,2q); inputs may be < 4q
-            slab[join(s0, img(64u * (uint32_t)r))] = v;
+            slab[s0 + img(64u * (uint32_t)r)] = v;
         }
         if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
         wave_lds_sync();
         const uint32_t own = img(tid << R);
 #pragma unroll
-        for (int r = 0; r < C; ++r) x[r] = slab[join(own, img((uint32_t)r))];
+        for (int r = 0; r < C; ++r) x[r] = slab[own + img((uint32_t)r)];
     }
 };
 

@@ -14,8 +14,12 @@
 namespace agx {
 namespace AGX_TU {
 
+// the frame type of a kernel's packed ARITH parameter: bit 0 = fast (1) / exact (0) arithmetic, the option bits (rb_frame.hpp) above it
+template <int L, int R, int ARITH>
+using frame_of = rb2_frame<L, R, (ARITH & 1) == 1, (ARITH >> 1)>;
+
 #define AGX_RB2_PROLOGUE                                                                          \
-    using F = rb2_frame<L, R, (ARITH & 1) == 1, (ARITH >> 1)>;                                    \
+    using F = frame_of<L, R, ARITH>;                                                              \
     constexpr int C = F::C, T = F::T;                                                             \
     static_assert(T >= 64, "one frame must span whole waves");                                    \
     F f;                                                                                          \
@@ -36,12 +40,13 @@ fwd_rb2(const uint64_t* __restrict__ in, uint64_t* __restrict__ out,
         uint32_t pairs_per_prime, uint64_t frames_x,
         int64_t prime_stride, int64_t poly_stride, uint32_t lazy_out) {
     uint64_t t_entry = 0;
-    if constexpr (((ARITH >> 1) & kOptTrace) != 0) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry) : : "memory");
-    if constexpr (((ARITH >> 1) & kOptPrio) != 0) __builtin_amdgcn_s_setprio(3);
+    if constexpr (frame_of<L, R, ARITH>::TRACE) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry) : : "memory");
+    if constexpr (frame_of<L, R, ARITH>::PRIO) __builtin_amdgcn_s_setprio(3);
     AGX_RB2_PROLOGUE;
     f.lazy_out = lazy_out != 0;
     uint64_t x[C];
-    if constexpr (((ARITH >> 1) & kOptNtLoad) != 0) {
+    // kept old form: fwd_rb2 (every instance) -- through a load_pass0 member the slab address and the lazy_out test move ahead of the frame loads
+    if constexpr (F::NT_LOAD) {
         const uint64_t* src = in + base;     // wave-uniform
 #pragma unroll
         for (int r = 0; r < C; ++r) x[r] = __builtin_nontemporal_load(src + (uint32_t)r * T + f.tid);
@@ -86,13 +91,14 @@ __device__ __forceinline__ void dloop_retire(uint32_t* ticket) {
     }
 }
 
+// kept old form: the per-frame body of inv_rb2, inv_rb2_loop and inv_rb2_dloop is spelled out in each -- as one shared function every instance is rescheduled
 template <int L, int R, int ARITH, int MINW>
 __global__ void __launch_bounds__((1 << (L - R)), MINW)
 inv_rb2_dloop(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2, uint64_t* __restrict__ out,
               const prime_consts* __restrict__ consts, const twpair* __restrict__ itw_rb,
               uint32_t pairs_per_prime, uint32_t batch, uint32_t total, int64_t prime_stride, int64_t poly_stride,
               uint32_t* __restrict__ ticket) {
-    using F = rb2_frame<L, R, (ARITH & 1) == 1, (ARITH >> 1)>;
+    using F = frame_of<L, R, ARITH>;
     static_assert(!F::G::exchange_is_wave_local(0), "the mailbox is read behind the last exchange's workgroup barrier");
     constexpr int C = F::C, T = F::T;
     F f;
@@ -113,9 +119,10 @@ inv_rb2_dloop(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2,
         f.load_last_stage(x, in2, bk, base);
         f.inverse(x, itw_rb + (size_t)prime * pairs_per_prime, pc);      // its last exchange is a workgroup barrier: the mailbox is visible behind it
         const uint32_t next = (uint32_t)__builtin_amdgcn_readfirstlane((int)mailbox[it & 1u]);
+        // kept old form: inv_rb2_dloop<14, 5, kLazy, 4> -- through store_pass0 the stores are scheduled differently around the mailbox read
 #pragma unroll
         for (int r = 0; r < C; ++r) {
-            if constexpr (((ARITH >> 1) & kOptNtStore) != 0) __builtin_nontemporal_store(x[r], &out[base + f.tid + (uint32_t)r * T]);
+            if constexpr (F::NT_STORE) __builtin_nontemporal_store(x[r], &out[base + f.tid + (uint32_t)r * T]);
             else out[base + f.tid + (uint32_t)r * T] = x[r];
         }
         fr = next;
@@ -129,8 +136,8 @@ __global__ void __launch_bounds__((1 << (L - R)), MINW)
 inv_rb2_loop(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2, uint64_t* __restrict__ out,
              const prime_consts* __restrict__ consts, const twpair* __restrict__ itw_rb,
              uint32_t pairs_per_prime, uint32_t batch, uint32_t total, int64_t prime_stride, int64_t poly_stride) {
-    using F = rb2_frame<L, R, (ARITH & 1) == 1, (ARITH >> 1)>;
-    constexpr int C = F::C, T = F::T;
+    using F = frame_of<L, R, ARITH>;
+    constexpr int C = F::C;
     F f;
     f.tid = threadIdx.x;
     f.slab = reinterpret_cast<uint64_t*>(agx_dyn_lds);
@@ -147,11 +154,7 @@ inv_rb2_loop(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2, 
         if (!first) __builtin_amdgcn_s_barrier();
         f.load_last_stage(x, in2, bk, base);
         f.inverse(x, itw_rb + (size_t)prime * pairs_per_prime, pc);
-#pragma unroll
-        for (int r = 0; r < C; ++r) {
-            if constexpr (((ARITH >> 1) & kOptNtStore) != 0) __builtin_nontemporal_store(x[r], &out[base + f.tid + (uint32_t)r * T]);
-            else out[base + f.tid + (uint32_t)r * T] = x[r];
-        }
+        f.store_pass0(x, out, base);
         first = false;
     }
 }
@@ -163,8 +166,8 @@ inv_rb2(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2, uint6
         uint32_t pairs_per_prime, uint64_t frames_x,
         int64_t prime_stride, int64_t poly_stride) {
     uint64_t t_entry = 0;
-    if constexpr (((ARITH >> 1) & kOptTrace) != 0) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry) : : "memory");
-    if constexpr (((ARITH >> 1) & kOptPrio) != 0) __builtin_amdgcn_s_setprio(3);   // until the frame loads are out
+    if constexpr (frame_of<L, R, ARITH>::TRACE) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry) : : "memory");
+    if constexpr (frame_of<L, R, ARITH>::PRIO) __builtin_amdgcn_s_setprio(3);   // until the frame loads are out
     AGX_RB2_PROLOGUE;
     const prime_consts pc = consts[prime];
     const barrett128 bk{pc.q, pc.mu_hi, pc.mu_lo};
@@ -177,13 +180,7 @@ inv_rb2(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2, uint6
     f.load_last_stage(x, in2, bk, base);
     if constexpr (F::TRACE) f.template stamp<2>(x[C - 1]);      // staged through the image into the last pass's layout
     f.inverse(x, itw_rb + (size_t)prime * pairs_per_prime, pc);
-    if (live) {
-#pragma unroll
-        for (int r = 0; r < C; ++r) {
-            if constexpr (((ARITH >> 1) & kOptNtStore) != 0) __builtin_nontemporal_store(x[r], &out[base + f.tid + (uint32_t)r * T]);
-            else out[base + f.tid + (uint32_t)r * T] = x[r];
-        }
-    }
+    f.store_pass0(x, out, base, live);
     if constexpr (F::TRACE) {
         f.template stamp<10>(x[0]);         // stores issued
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -207,7 +204,8 @@ polymul_rb2(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, uint
     // both forward transforms may skip their last two conditional subtracts
     f.lazy_out = F::LAZY16;
     uint64_t xa[C], xb[C];
-    constexpr bool NTL = ((ARITH >> 1) & kOptNtLoad) != 0, NTS = ((ARITH >> 1) & kOptNtStore) != 0;
+    // kept old form (both loads): polymul_rb2<12, 3, 1, ...> -- through load_pass0 the slab address moves ahead of the frame loads
+    constexpr bool NTL = F::NT_LOAD;
 #pragma unroll
     for (int r = 0; r < C; ++r) xa[r] = NTL ? __builtin_nontemporal_load(&a[base + f.tid + (uint32_t)r * T]) : a[base + f.tid + (uint32_t)r * T];
     f.forward(xa, tw_rb + (size_t)prime * pairs_per_prime);
@@ -219,13 +217,7 @@ polymul_rb2(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, uint
 #pragma unroll
     for (int r = 0; r < C; ++r) xa[r] = mul_mod_barrett(xa[r], xb[r], bk);
     f.inverse(xa, itw_rb + (size_t)prime * pairs_per_prime, pc);
-    if (live) {
-#pragma unroll
-        for (int r = 0; r < C; ++r) {
-            if constexpr (NTS) __builtin_nontemporal_store(xa[r], &c[base + f.tid + (uint32_t)r * T]);
-            else c[base + f.tid + (uint32_t)r * T] = xa[r];
-        }
-    }
+    f.store_pass0(xa, c, base, live);
 }
 
 // The same product with only ONE frame in registers at a time: NTT(first) is parked in c's own frame (plain global
@@ -247,10 +239,8 @@ polymul_rb2_park(const uint64_t* __restrict__ first, const uint64_t* __restrict_
     const prime_consts pc = consts[prime];
     const barrett128 bk{pc.q, pc.mu_hi, pc.mu_lo};
     f.lazy_out = F::LAZY16;     // the Barrett product takes operands in [0,4q) when q <= 2^60
-    constexpr bool NTL = ((ARITH >> 1) & kOptNtLoad) != 0, NTS = ((ARITH >> 1) & kOptNtStore) != 0;
     uint64_t x[C];
-#pragma unroll
-    for (int r = 0; r < C; ++r) x[r] = NTL ? __builtin_nontemporal_load(&first[base + f.tid + (uint32_t)r * T]) : first[base + f.tid + (uint32_t)r * T];
+    f.load_pass0(x, first, base);
     f.forward(x, tw_rb + (size_t)prime * pairs_per_prime);
     static_assert(F::STREAM_TW, "the parked product is a streamed single-frame kernel");
     {
@@ -263,8 +253,7 @@ polymul_rb2_park(const uint64_t* __restrict__ first, const uint64_t* __restrict_
         }
         asm volatile("" ::: "memory");      // the second operand's loads stay behind the parking stores (or two frames would be live)
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < C; ++r) x[r] = NTL ? __builtin_nontemporal_load(&second[base + f.tid + (uint32_t)r * T]) : second[base + f.tid + (uint32_t)r * T];
+        f.load_pass0(x, second, base);
         __syncthreads();   // the image is reused
         {
             const twpair* tbl2 = tw_rb + (size_t)prime * pairs_per_prime;
@@ -288,13 +277,7 @@ polymul_rb2_park(const uint64_t* __restrict__ first, const uint64_t* __restrict_
             __builtin_amdgcn_sched_barrier(0);
         });
         f.inverse(x, itw_rb + (size_t)prime * pairs_per_prime, pc);
-        if (live) {
-#pragma unroll
-            for (int r = 0; r < C; ++r) {
-                if constexpr (NTS) __builtin_nontemporal_store(x[r], &c[base + f.tid + (uint32_t)r * T]);
-                else c[base + f.tid + (uint32_t)r * T] = x[r];
-            }
-        }
+        f.store_pass0(x, c, base, live);
     }
 }
 
@@ -311,10 +294,10 @@ polysquare_rb2(const uint64_t* __restrict__ a, uint64_t* __restrict__ c,
     const prime_consts pc = consts[prime];
     const barrett128 bk{pc.q, pc.mu_hi, pc.mu_lo};
     f.lazy_out = F::LAZY16;     // the Barrett product takes operands in [0,4q) when q <= 2^60
-    constexpr bool NTL = ((ARITH >> 1) & kOptNtLoad) != 0, NTS = ((ARITH >> 1) & kOptNtStore) != 0;
     uint64_t x[C];
+    // kept old form: polysquare_rb2<12, 5, kLazy | kOptPrio, 4> (diagnostics twin) -- through load_pass0 its loads are scheduled differently
 #pragma unroll
-    for (int r = 0; r < C; ++r) x[r] = NTL ? __builtin_nontemporal_load(&a[base + f.tid + (uint32_t)r * T]) : a[base + f.tid + (uint32_t)r * T];
+    for (int r = 0; r < C; ++r) x[r] = F::NT_LOAD ? __builtin_nontemporal_load(&a[base + f.tid + (uint32_t)r * T]) : a[base + f.tid + (uint32_t)r * T];
     f.forward(x, tw_rb + (size_t)prime * pairs_per_prime);
 #pragma unroll
     for (int r = 0; r < C; ++r) {
@@ -324,13 +307,7 @@ polysquare_rb2(const uint64_t* __restrict__ a, uint64_t* __restrict__ c,
     }
     __syncthreads();   // the image is reused: every wave is done reading the forward transform's exchanges
     f.inverse(x, itw_rb + (size_t)prime * pairs_per_prime, pc);
-    if (live) {
-#pragma unroll
-        for (int r = 0; r < C; ++r) {
-            if constexpr (NTS) __builtin_nontemporal_store(x[r], &c[base + f.tid + (uint32_t)r * T]);
-            else c[base + f.tid + (uint32_t)r * T] = x[r];
-        }
-    }
+    f.store_pass0(x, c, base, live);
 }
 
 // c = a * b in Z_q[X]/(X^n + 1) with b given by its transform bhat (what agx_ntt_forward / agx_ntt_forward_lazy of this plan wrote:
@@ -353,7 +330,7 @@ mulhat_rb2(const uint64_t* __restrict__ a, const uint64_t* __restrict__ bhat, ui
     const prime_consts pc = consts[prime];
     const barrett128 bk{pc.q, pc.mu_hi, pc.mu_lo};
     f.lazy_out = F::LAZY16;     // the Barrett product takes operands in [0,4q) when q <= 2^60
-    constexpr bool NTL = ((ARITH >> 1) & kOptNtLoad) != 0, NTS = ((ARITH >> 1) & kOptNtStore) != 0;
+    constexpr bool NTL = F::NT_LOAD;
     constexpr int GRP = 4, NG = C / GRP;      // registers per group of bhat loads (two 16-byte loads), groups per thread
     static_assert(C % GRP == 0, "whole groups");
     // pass by pass forward kernels (R = 3, 8 waves/SIMD, 16 words of bhat per thread): every group is requested before the last
@@ -361,6 +338,7 @@ mulhat_rb2(const uint64_t* __restrict__ a, const uint64_t* __restrict__ bhat, ui
     constexpr bool EARLY = !F::STREAM_TW && !F::SPLIT && F::NP >= 2 && NG <= 2;
     const bhat_pair* bp = reinterpret_cast<const bhat_pair*>(bhat + ((int64_t)prime * bhat_prime_stride + (int64_t)fx * bhat_poly_stride) + (uint32_t)f.tid * C);
     uint64_t x[C];
+    // kept old form: mulhat_rb2 (every instance) -- through load_pass0 the slab address moves ahead of the frame loads
 #pragma unroll
     for (int r = 0; r < C; ++r) x[r] = NTL ? __builtin_nontemporal_load(&a[base + f.tid + (uint32_t)r * T]) : a[base + f.tid + (uint32_t)r * T];
     bhat_pair z[EARLY ? NG : 2][GRP / 2];
@@ -393,13 +371,7 @@ mulhat_rb2(const uint64_t* __restrict__ a, const uint64_t* __restrict__ bhat, ui
     });
     __syncthreads();   // the image is reused: every wave is done reading the forward transform's exchanges
     f.inverse(x, itw_rb + (size_t)prime * pairs_per_prime, pc);
-    if (live) {
-#pragma unroll
-        for (int r = 0; r < C; ++r) {
-            if constexpr (NTS) __builtin_nontemporal_store(x[r], &c[base + f.tid + (uint32_t)r * T]);
-            else c[base + f.tid + (uint32_t)r * T] = x[r];
-        }
-    }
+    f.store_pass0(x, c, base, live);
 }
 
 // ---- host side: pass tables, launch glue and registry entries, written once for every kernel family ---------------------------------
@@ -436,14 +408,8 @@ void build_table_t(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglon
     for_each_table_slot<L, R>([&](size_t at, uint32_t idx) { out[start + at] = make_ulonglong2(tw[idx], pre[idx]); });
 }
 
-template <int L, int R, int PPB, int ARITH>
-constexpr size_t rb2_lds_bytes() {
-    using F = rb2_frame<L, R, (ARITH & 1) == 1, (ARITH >> 1)>;
-    return (size_t)F::image_bytes * PPB;
-}
-
-template <int ARITH>
-constexpr int rb2_arith_level() { return (ARITH & 1) ? ((((ARITH >> 1) & kOptLazy16) != 0) ? 2 : 1) : 0; }      // rb_entry::arith
+template <class F>
+constexpr int rb2_arith_level() { return F::LAZY16 ? 2 : F::FAST_ARITH ? 1 : 0; }      // rb_entry::arith
 
 // A kernel shape S says what the launches of one family differ in besides the kernel symbol: the rb_entry fields (log_n, r, fpb = frames per
 // workgroup, min_waves, table_pairs, lds, build, arith, narrow), threads per workgroup, and the flag word.  Every forward kernel ends in one:
@@ -456,9 +422,9 @@ struct lazy_flag {
 
 template <int L, int R, int PPB, int ARITH, int MINW>
 struct rb2_shape : lazy_flag {
-    static constexpr int log_n = L, r = R, fpb = PPB, threads = rb_geom<L, R>::T * PPB, min_waves = MINW, arith = rb2_arith_level<ARITH>(), narrow = 0;
+    static constexpr int log_n = L, r = R, fpb = PPB, threads = rb_geom<L, R>::T * PPB, min_waves = MINW, arith = rb2_arith_level<frame_of<L, R, ARITH>>(), narrow = 0;
     static constexpr uint32_t table_pairs = rb_geom<L, R>::table_pairs;
-    static constexpr size_t lds = rb2_lds_bytes<L, R, PPB, ARITH>();
+    static constexpr size_t lds = (size_t)frame_of<L, R, ARITH>::image_bytes * PPB;
     static constexpr auto build = &build_table_t<L, R>;
 };
 
@@ -588,7 +554,8 @@ constexpr rb_entry make_entry3(int id) {
     return shape_entry<S>(id, &launch_fwd_t<S, FWD>, &allow_lds<S::lds, FWD, INV, MUL>, &launch_inv_t<S, INV>, &launch_mul_t<S, MUL>);
 }
 
-// PPB frames per workgroup (the n = 4096 defaults: R = 3, 8 waves/SIMD); the product kernel at MULW waves per SIMD
+// PPB frames per workgroup (the n = 4096 defaults: R = 3, 8 waves/SIMD; n = 1024 with streamed twiddles, where two frames of 2^R coefficients still fit
+// the register budget and the parked product's round trip through c's frame would cost more); the product kernel at MULW waves per SIMD
 // and the product by a pre-transformed operand (one frame in registers; at most AGX_MULHAT_MAXW waves per SIMD)
 template <int L, int R, int PPB, int ARITH, int MINW, int MULW = MINW>
 constexpr rb_entry make_entry2(int id) {
@@ -626,11 +593,6 @@ constexpr rb_entry with_fwd_companion(rb_entry e, int id, uint32_t min_frames = 
     e.fwd_companion_min_frames = min_frames;
     return e;
 }
-
-// ... with the fused product by polymul_rb2 (both forward results in registers) at MULW waves per SIMD: small frames, where two
-// frames of 2^R coefficients still fit the register budget and the parked product's round trip through c's frame costs more
-template <int L, int R, int ARITH, int MINW, int MULW>
-constexpr rb_entry make_entry_single_mul2(int id) { return make_entry2<L, R, 1, ARITH, MINW, MULW>(id); }
 
 // ... with the inverse by the ticket-drawing loop kernel (captured launches and streams without a ticket pair take the fixed-stride form)
 template <int L, int R, int ARITH, int MINW>

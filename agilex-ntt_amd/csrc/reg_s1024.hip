@@ -22,9 +22,9 @@ namespace agx {
 namespace AGX_TU {
 const rb_entry kEntries[] = {
     // n = 1024: one wave per frame, R = 4, five waves per SIMD; product with both frames in registers
-    make_entry_single_mul2<10, 4, kLazy, 5, 4>(150),
-    make_entry_single_mul2<10, 4, kFast, 5, 4>(151),
-    make_entry_single_mul2<10, 4, kExact, 5, 4>(152),
+    make_entry2<10, 4, 1, kLazy, 5, 4>(150),
+    make_entry2<10, 4, 1, kFast, 5, 4>(151),
+    make_entry2<10, 4, 1, kExact, 5, 4>(152),
 };
 }  // namespace AGX_TU
 

@@ -8,9 +8,7 @@
 namespace agx {
 namespace AGX_TU {
 // streamed twiddles + pinned butterflies as in the single-frame kernels of the large sizes (rb_stream_opts.hpp), full 64-bit image
-constexpr int kWpLazy = 1 | ((kOptPad | kOptSelect | kOptLazy16 | kOptLazyInv | kOptNtLoad | kOptNtStore | kOptEstReduce | kOptStreamTw | kOptPinBf) << 1);   // q <= 2^60
-constexpr int kWpFast = 1 | ((kOptPad | kOptSelect | kOptNtLoad | kOptNtStore | kOptStreamTw | kOptPinBf) << 1);                                            // q <= 2^61
-constexpr int kWpExact = 0 | ((kOptPad | kOptNtLoad | kOptNtStore | kOptStreamTw | kOptPinBf) << 1);                                                        // q < 2^62, reference op sequence
+constexpr int kWpLazy = kLazy & ~(kOptSplitWord << 1), kWpFast = kFast & ~(kOptSplitWord << 1), kWpExact = kExact & ~(kOptSplitWord << 1);
 // One wave per workgroup everywhere: nothing is shared between the waves of a group but the LDS allocation, and a wave that retires alone frees
 // its slot at once (four waves per workgroup: -1 ... -5 %, profiles/r04_small_sizes_sweeps.txt).
 const rb_entry kEntries[] = {
@@ -34,7 +32,7 @@ const rb_entry kEntries[] = {
     // A/B shapes kept in lib/libagxntt_diag.so (measured in profiles/r04_small_sizes_sweeps.txt; 216-219, 223, 225, 226 measured there and deleted)
     make_entry_wp<5, 5, 4, kWpLazy | (kOptSplitWord << 1), 4>(215),      // n = 32: ONE LANE per frame, every twiddle a scalar, split-word image: -5 % forward
     make_entry_wp<9, 5, 1, kWpLazy | (kOptSplitWord << 1), 4>(220),      // n = 512: 32 x 16 (two passes): +1 ... +2 % forward / inverse, -5 % product
-    make_entry_single_mul2<9, 3, kLazy, 8, 5>(221),                      // n = 512: one wave per frame, 8 x 64 (the large sizes' kernel shape): equal
+    make_entry2<9, 3, 1, kLazy, 8, 5>(221),                           // n = 512: one wave per frame, 8 x 64 (the large sizes' kernel shape): equal
     make_entry_wp<8, 4, 4, kWpLazy, 5>(222),                             // n = 256: four waves per workgroup
     make_entry_wp<5, 3, 4, kWpLazy, 8>(224),                             // n = 32: four waves per workgroup: -5 % forward, -7 % inverse and product
 #endif

@@ -46,11 +46,11 @@ struct wp_geom {
     }
 };
 
-// one wave's coefficients from layout FROM to layout TO through its part of the LDS image (64-bit words; with SPLIT the low and the
-// high 32-bit words in turn through an image of half the size; wp_relayout32 below: the 32-bit kernels' image).
+// one wave's coefficients from layout FROM to layout TO through its part of the LDS image, word index E + (E >> PADS): words of type W (64-bit, or
+// 32-bit in the 32-bit kernels), or with SPLIT the low and the high halves of 64-bit words in turn through an image of half the size (rb_frame.hpp).
 // The leading fence orders this wave's earlier LDS reads of the same words (an exchange, the previous operand's staging).
-template <int L, int R, int FROM, int TO, int PADS, bool SPLIT>
-__device__ __forceinline__ void wp_relayout(uint64_t (&x)[1 << R], void* wimg, uint32_t lane) {
+template <int L, int R, int FROM, int TO, int PADS, bool SPLIT, typename W>
+__device__ __forceinline__ void wp_relayout(W (&x)[1 << R], void* wimg, uint32_t lane) {
     using G = wp_geom<L, R>;
     constexpr int C = G::C;
     auto img = [](uint32_t e) constexpr { return e + (e >> PADS); };
@@ -58,31 +58,15 @@ __device__ __forceinline__ void wp_relayout(uint64_t (&x)[1 << R], void* wimg, u
     wave_lds_sync();
     if constexpr (SPLIT) {
         uint32_t* w = static_cast<uint32_t*>(wimg);
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[a + img(G::template reg_part<FROM>(r))] = (uint32_t)x[r]; });
-        wave_lds_sync();
         uint32_t lo[C];
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; lo[r] = w[b + img(G::template reg_part<TO>(r))]; });
-        wave_lds_sync();
-        static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[a + img(G::template reg_part<FROM>(r))] = (uint32_t)(x[r] >> 32); });
-        wave_lds_sync();
+        split_words_out(x, w, lo, [&](auto r) { return a + img(G::template reg_part<FROM>(r)); }, [&](auto r) { return b + img(G::template reg_part<TO>(r)); }, [] { wave_lds_sync(); });
         static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = (uint64_t)lo[r] | ((uint64_t)w[b + img(G::template reg_part<TO>(r))] << 32); });
     } else {
-        uint64_t* w = static_cast<uint64_t*>(wimg);
+        W* w = static_cast<W*>(wimg);
         static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[a + img(G::template reg_part<FROM>(r))] = x[r]; });
         wave_lds_sync();
         static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = w[b + img(G::template reg_part<TO>(r))]; });
     }
-}
-template <int L, int R, int FROM, int TO>
-__device__ __forceinline__ void wp_relayout32(uint32_t (&x)[1 << R], uint32_t* w, uint32_t lane) {
-    using G = wp_geom<L, R>;
-    constexpr int C = G::C;
-    auto img = [](uint32_t e) constexpr { return e + (e >> 5); };
-    const uint32_t a = img(G::template lane_part<FROM>(lane)), b = img(G::template lane_part<TO>(lane));
-    wave_lds_sync();
-    static_for<0, C>([&](auto Rr) { constexpr int r = Rr; w[a + img(G::template reg_part<FROM>(r))] = x[r]; });
-    wave_lds_sync();
-    static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = w[b + img(G::template reg_part<TO>(r))]; });
 }
 
 // where a wave's frames live in global memory
@@ -165,9 +149,8 @@ __device__ __forceinline__ void wp_store(const uint64_t (&v)[1 << R], uint64_t* 
 
 // ---- 64-bit arithmetic ------------------------------------------------------------------------------------------------------------
 #define AGX_WP_FRAME                                                                               \
-    using F = rb2_frame<L, R, (ARITH & 1) == 1, (ARITH >> 1)>;                                     \
-    constexpr bool NTL = ((ARITH >> 1) & kOptNtLoad) != 0, NTS = ((ARITH >> 1) & kOptNtStore) != 0;  \
-    [[maybe_unused]] constexpr bool FASTA = (ARITH & 1) == 1;                                                       \
+    using F = frame_of<L, R, ARITH>;                                                               \
+    constexpr bool NTL = F::NT_LOAD, NTS = F::NT_STORE;                                            \
     constexpr int PADS = F::PADS;                                                                  \
     unsigned char* wimg = agx_dyn_lds + (size_t)wave * wp_wave_image_bytes<L, R, ARITH>();         \
     F f;                                                                                           \
@@ -180,13 +163,15 @@ __device__ __forceinline__ void wp_store(const uint64_t (&v)[1 << R], uint64_t* 
 // frame has at least 2^PADS coefficients)
 template <int L, int R, int ARITH>
 constexpr size_t wp_wave_image_bytes() {
-    using F = rb2_frame<L, R, (ARITH & 1) == 1, (ARITH >> 1)>;
+    using F = frame_of<L, R, ARITH>;
     constexpr size_t words = ((size_t)64 << R) + (((size_t)64 << R) >> F::PADS);
     return words * (F::SPLIT ? 4 : 8);
 }
 template <int L, int R, int ARITH>
 constexpr size_t wp_lds_bytes(int wpb) { return (size_t)wpb * wp_wave_image_bytes<L, R, ARITH>(); }
 
+// kept old form: fwd_wp / inv_wp / polymul_wp and their 32-bit twins -- with the direct_pass0 load / store choice in shared functions, or the
+// bodies shared over a word-type struct, most instances are scheduled differently (fwd_wp<5, 3, ...>, polymul_wp32<9, 4, ...> among them)
 template <int L, int R, int WPB, int ARITH, int MINW>
 __global__ void __launch_bounds__(64 * WPB, MINW)
 fwd_wp(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, const prime_consts* __restrict__ consts,
@@ -222,7 +207,7 @@ inv_wp(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2, uint64
 #pragma unroll
         for (int r = 0; r < C; ++r) x[r] = mul_mod_barrett(reduce_4q(x[r], pc.q, pc.q << 1), reduce_4q(y[r], pc.q, pc.q << 1), bk);
     }
-    if constexpr (!FASTA) {
+    if constexpr (!F::FAST_ARITH) {
 #pragma unroll
         for (int r = 0; r < C; ++r) x[r] = csub(x[r], f.k.m);      // the exact form wants [0,2q); inputs may be below 4q
     }
@@ -286,7 +271,7 @@ constexpr int wp_mul_waves() { return R >= 4 ? 4 : (MINW > AGX_POLYMUL_MAXW ? AG
 // WPB waves per workgroup (no barrier: the group only shares an LDS allocation), MINW waves per SIMD
 template <int L, int R, int WPB, int ARITH, int MINW>
 struct wp_shape : lazy_flag {
-    static constexpr int log_n = L, r = R, fpb = wp_geom<L, R>::FPW * WPB, threads = 64 * WPB, min_waves = MINW, arith = rb2_arith_level<ARITH>(), narrow = 0;
+    static constexpr int log_n = L, r = R, fpb = wp_geom<L, R>::FPW * WPB, threads = 64 * WPB, min_waves = MINW, arith = rb2_arith_level<frame_of<L, R, ARITH>>(), narrow = 0;
     static constexpr uint32_t table_pairs = rb_geom<L, R>::table_pairs;
     static constexpr size_t lds = wp_lds_bytes<L, R, ARITH>(WPB);
     static constexpr auto build = &build_table_t<L, R>;
@@ -348,10 +333,10 @@ fwd_wp32(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, const prim
         wp_load32<L, R, WP_PASS0, TIER, false>(x, in, sp, lane, f.a);
     } else {
         wp_load32<L, R, WP_LANE, TIER, false>(x, in, sp, lane, f.a);
-        wp_relayout32<L, R, WP_LANE, WP_PASS0>(x, wimg, lane);
+        wp_relayout<L, R, WP_LANE, WP_PASS0, 5, false>(x, wimg, lane);
     }
     f.forward(x, tbl, lazy_out != 0);
-    wp_relayout32<L, R, WP_LAST, WP_LANE>(x, wimg, lane);
+    wp_relayout<L, R, WP_LAST, WP_LANE, 5, false>(x, wimg, lane);
     wp_store32<L, R, WP_LANE>(x, out, sp, lane);
 }
 
@@ -370,13 +355,13 @@ inv_wp32(const uint64_t* __restrict__ in, const uint64_t* __restrict__ in2, uint
     } else {
         wp_load32<L, R, WP_LANE, TIER, true>(x, in, sp, lane, f.a);
     }
-    wp_relayout32<L, R, WP_LANE, WP_LAST>(x, wimg, lane);
+    wp_relayout<L, R, WP_LANE, WP_LAST, 5, false>(x, wimg, lane);
     const tw32 ninv = make_uint2((uint32_t)pc.n_inv, (uint32_t)(pc.n_inv_p >> 32)), w1n = make_uint2((uint32_t)pc.w1n, (uint32_t)(pc.w1n_p >> 32));
     f.inverse(x, tbl, ninv, w1n);
     if constexpr (G::direct_pass0) {
         wp_store32<L, R, WP_PASS0>(x, out, sp, lane);
     } else {
-        wp_relayout32<L, R, WP_PASS0, WP_LANE>(x, wimg, lane);
+        wp_relayout<L, R, WP_PASS0, WP_LANE, 5, false>(x, wimg, lane);
         wp_store32<L, R, WP_LANE>(x, out, sp, lane);
     }
 }
@@ -395,7 +380,7 @@ polymul_wp32(const uint64_t* __restrict__ pa, const uint64_t* __restrict__ pb, u
             wp_load32<L, R, WP_PASS0, TIER, false>(x, src, sp, lane, f.a);
         } else {
             wp_load32<L, R, WP_LANE, TIER, false>(x, src, sp, lane, f.a);
-            wp_relayout32<L, R, WP_LANE, WP_PASS0>(x, wimg, lane);
+            wp_relayout<L, R, WP_LANE, WP_PASS0, 5, false>(x, wimg, lane);
         }
     };
     load_pass0(xa, pa);
@@ -415,7 +400,7 @@ polymul_wp32(const uint64_t* __restrict__ pa, const uint64_t* __restrict__ pb, u
     if constexpr (G::direct_pass0) {
         wp_store32<L, R, WP_PASS0>(xa, pcout, sp, lane);
     } else {
-        wp_relayout32<L, R, WP_PASS0, WP_LANE>(xa, wimg, lane);
+        wp_relayout<L, R, WP_PASS0, WP_LANE, 5, false>(xa, wimg, lane);
         wp_store32<L, R, WP_LANE>(xa, pcout, sp, lane);
     }
 }

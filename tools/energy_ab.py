@@ -3,8 +3,8 @@
 At the board's power cap throughput follows the energy of one transform, so an A/B of two kernel shapes has to
 report micro-joules per NTT beside milliseconds.  Each configuration runs back-to-back launches for --seconds while amdgpu's sysfs
 files are sampled every 20 ms (bench.py's PowerSampler); idle power is sampled first.  Ids follow tools/sweep.py
-(AGX_VARIANT_REGBLOCK_BASE + id, -2 = the plan's tuned default); the timing-only ablation twins (67-72) need
-`make -C agilex-ntt_amd diag EXTRA=-DAGX_TIMING_ABLATIONS` and AGX_NTT_LIB=agilex-ntt_amd/lib/libagxntt_diag.so.
+(AGX_VARIANT_REGBLOCK_BASE + id, -2 = the plan's tuned default); diag-only ids need `make -C agilex-ntt_amd diag` and
+AGX_NTT_LIB=agilex-ntt_amd/lib/libagxntt_diag.so (the timing-only ablation twins 67-72 this tool once measured were removed in round 4).
 
 Usage: python3 tools/energy_ab.py [--n N --primes P --batch B --bits 60 --op fwd|inv|mul --seconds 1.5 --rounds 2] ids..."""
 import argparse
