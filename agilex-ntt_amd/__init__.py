@@ -41,6 +41,7 @@ ABI = {
     "agx_ntt_plan_destroy": (_int, [_vp]),
     "agx_ntt_plan_set_variant": (_int, [_vp, _int]),
     "agx_ntt_plan_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "agx_ntt_plan_forward_kernel": (_int, [_vp, _u64, ctypes.POINTER(_int)]),
     "agx_ntt_plan_get_modulus": (_int, [_vp, _u32, _p64, _p64]),
     "agx_ntt_forward": (_int, [_vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_forward_lazy": (_int, [_vp, _vp, _vp, _u64, _vp]),
@@ -256,6 +257,12 @@ class Plan:
 
     def set_variant(self, variant):
         _check(lib().agx_ntt_plan_set_variant(self._h, variant), "plan_set_variant")
+
+    def forward_kernel(self, batch):
+        """registry id of the kernel a forward call of `batch` frames per prime runs (-1: the LDS radix-2 kernels)"""
+        k = _int(0)
+        _check(lib().agx_ntt_plan_forward_kernel(self._h, batch, ctypes.byref(k)), "plan_forward_kernel")
+        return k.value
 
     def forward(self, d_in, d_out, batch, stream=0):
         _check(lib().agx_ntt_forward(self._h, d_in, d_out, batch, stream), "forward")

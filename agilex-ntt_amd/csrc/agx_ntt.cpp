@@ -152,6 +152,12 @@ void free_plan(agx_ntt_plan* p) {
     delete p;
 }
 
+// c of a modulus q = 2^60 - c with 0 < c < 2^28, or 0 for any other modulus
+static uint32_t q60c_of(uint64_t q) {
+    const uint64_t top = 1ull << 60;
+    return q < top && top - q < (1ull << 28) ? (uint32_t)(top - q) : 0u;
+}
+
 void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
                         const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre) {
     img.n = n;
@@ -168,9 +174,11 @@ void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const 
     // and the tables honour the contract precon[j] = floor(twiddle[j] * 2^64 / q), twiddle[j] < q.
     // Tables that do not (e.g. the placeholders of the reference's main.cpp:49-55) get the exact
     // kernels, which repeat the reference's operations mod 2^64 whatever they are fed.
-    img.arith_level = 2;
+    // level 3 (on top of level 2): every modulus is 2^60 - c with 0 < c < 2^28 (the forward kernels specialised for this class, modarith.hpp)
+    img.arith_level = 3;
     for (uint32_t k = 0; k < num_primes && img.arith_level > 0; ++k) {
         const uint64_t q = moduli[k];
+        if (!q60c_of(q)) img.arith_level = std::min(img.arith_level, 2);
         if (q > (1ull << 60)) img.arith_level = std::min(img.arith_level, 1);
         if (q > (1ull << 61)) img.arith_level = 0;
         for (uint32_t j = 1; j < n && img.arith_level > 0; ++j) {
@@ -208,6 +216,8 @@ void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const 
             std::memcpy(&bits, &f, sizeof(bits));
             c.est = bits;
         }
+        c.est |= (uint64_t)q60c_of(q) << 32;
+
         c.n_inv = inv_pow2_mod(img.log_n, q);
         c.n_inv_p = shoup_quotient(c.n_inv, q);
         const uint64_t* twk = tw + (size_t)k * n;
@@ -553,6 +563,15 @@ int agx_ntt_plan_info(const agx_ntt_plan* plan, uint32_t* n, uint32_t* num_prime
     if (num_primes) *num_primes = plan->num_primes;
     if (device) *device = plan->device;
     if (has_inverse) *has_inverse = plan->has_inverse ? 1 : 0;
+    return AGX_OK;
+}
+
+int agx_ntt_plan_forward_kernel(const agx_ntt_plan* plan, uint64_t batch, int* registry_id) {
+    if (!plan || !registry_id) return AGX_ERR_NULL_POINTER;
+    // the choice forward_common makes
+    if (!use_regblock(plan)) *registry_id = -1;
+    else if (plan->rb_fwd.valid() && batch * plan->num_primes >= plan->rb_fwd.min_frames) *registry_id = regblock_id(plan->rb_fwd);
+    else *registry_id = regblock_id(plan->rb);
     return AGX_OK;
 }
 

@@ -111,6 +111,7 @@ struct bf_consts {
     uint64_t nm;     // 2^64 - m
     uint32_t one_a, one_b;  // two separate opaque_one() values (see add64_32)
     float est_inv;          // slightly below 2^32 / q, or 0 when q < 2^58 (reduce_final_est)
+    uint32_t c, c8;         // q = 2^60 - c kernels only (below): c and 8c
 };
 
 // x in [0,2m) -> x - (x >= m ? m : 0) through the sign of x - m; needs 2m <= 2^63... see callers
@@ -337,6 +338,77 @@ __device__ __forceinline__ uint64_t reduce_final_est(uint64_t v, const bf_consts
     if (lazy_out) return v;
     v = csub_select_c(v, f.nq2);
     return csub_select_c(v, f.nq1);
+}
+
+// ---------------------------------------------------------------------------------------
+// q = 2^60 - c with 0 < c < 2^28 (the primes just below 2^60 that RNS users pick; every modulus of the plan must be
+// of this form: arithmetic level 3).  The 16q-lazy forward transform with the tail-free schedule, and 2^60 = c (mod q)
+// in place of the two operations that treat q as an opaque number:
+//  * the mid-transform conditional subtract tests the SIGN BIT instead of comparing with 8q = 2^63 - 8c:
+//    x >= 2^63 -> x - 8q = (x - 2^63) + 8c, else x stays.  A kept x lies below 2^63 = 8q + 8c rather than below 8q, so
+//    the bounds carry a slack of 8c (q60c_tailfree: b q + e 8c); nothing passes 16q + 8c = 2^64 - 8c.
+//  * the final reduction folds the top four bits: v = k 2^60 + r = r + k c (mod q).
+// Same residues as the other forms at every stage, so the fully reduced outputs are identical.
+// ---------------------------------------------------------------------------------------
+struct q60c_tailfree {
+    struct bound {
+        int b, e;      // coefficients below b q + e 8c
+    };
+    // bound on the coefficients entering stage s (s = total: on the transform's outputs); inputs are < 4q
+    static constexpr bound bound_in(int s, int total) {
+        bound v{4, 0};
+        for (int i = 0; i < s; ++i) {
+            if (lazy16_tailfree::subtracts(i, total)) {
+                // sign bit set: x - 8q < (b - 8) q + e 8c; clear: x < 2^63 = 8q + 8c
+                v.b = v.b - 8 > 8 ? v.b - 8 : 8;
+                v.e = v.e > 1 ? v.e : 1;
+            }
+            v.b += 4;      // x' = tx + Q~, y' = tx + 4q - Q~, Q~ < 4q
+        }
+        return v;
+    }
+    // every stage's inputs and the outputs stay within 16q + 8c = 2^64 - 8c, so no sum wraps and a set sign bit means x >= 2^63 > 8q
+    static constexpr bool valid(int total) {
+        for (int s = 0; s <= total; ++s) {
+            const bound v = bound_in(s, total);
+            if (v.b > 16 || v.e > 1) return false;
+        }
+        return lazy16_tailfree::valid(total);
+    }
+};
+
+// x < 2^64 -> x - [x >= 2^63] 8q, below max(2^63, x - 8q): shift, mask and one multiply-add (8c < 2^31) instead of a 64-bit add,
+// a 64-bit compare and two selects
+__device__ __forceinline__ uint64_t csub_8q_q60c(uint64_t x, const bf_consts& k) {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 v = __builtin_bit_cast(u32x2, x);
+    uint32_t s = v.y >> 31;
+    asm("" : "+v"(s));      // opaque: a known 0 / 1 factor turns the multiply-add back into a compare and selects
+    v.y &= 0x7fffffffu;
+    return mad64(s, k.c8, __builtin_bit_cast(uint64_t, v));
+}
+
+template <bool DO_CSUB>
+__device__ __forceinline__ void ct_butterfly_q60c(uint64_t& x, uint64_t& y, uint64_t w, uint64_t wp, const bf_consts& k) {
+    const uint32_t y0 = (uint32_t)y, y1 = (uint32_t)(y >> 32), p0 = (uint32_t)wp, p1 = (uint32_t)(wp >> 32);
+    const uint64_t tx = DO_CSUB ? csub_8q_q60c(x, k) : x;
+    uint64_t c = mad64(p1, y1, (uint64_t)__umulhi(y0, p1));                  // one v_mov builds the {h,0} pair
+    c = add64_32(c, __umulhi(y1, p0), k.one_b);
+    const uint64_t xn = fold_product(tx, y, w, c, k);
+    y = (tx << 1) + k.m - xn;                                               // tx + 4q - Q~
+    x = xn;
+}
+
+// any v < 2^64 (the transform's outputs are below 16q + 8c) -> [0,q), or only below 2q for lazy outputs.  v = k 2^60 + r with
+// k = v >> 60 <= 15 and r < 2^60; 2^60 = c (mod q), so v = r + k c (mod q), and with c < 2^28: k c < 15 2^28 < 2^32,
+// r + k c < 2^60 + 2^32 < 2^61 - 2^29 < 2q.  One conditional subtract of q finishes (r + k c < 2^63: the sign test is exact).
+__device__ __forceinline__ uint64_t reduce_final_q60c(uint64_t v, const bf_consts& k, const final_consts& f, bool lazy_out) {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 r = __builtin_bit_cast(u32x2, v);
+    const uint32_t kq = r.y >> 28;
+    r.y &= 0x0fffffffu;
+    const uint64_t t = mad64(kq, k.c, __builtin_bit_cast(uint64_t, r));
+    return lazy_out ? t : csub_select_c(t, f.nq1);
 }
 
 // w*d - c*q (mod 2^64) with the quotient estimate of the chosen arithmetic:

@@ -292,10 +292,18 @@ regblock_layout regblock_choose(uint32_t n, int config_id, int arith_level, int 
 
 regblock_layout regblock_forward_companion(const regblock_layout& main, uint32_t n, int arith_level, int narrow_level) {
     if (!main.valid() || main.entry->fwd_companion <= 0) return regblock_layout{};
-    regblock_layout rb = regblock_choose(n, main.entry->fwd_companion, arith_level, narrow_level);
+    // tuned defaults among the forward companions: {companion, its twin for a narrower class of moduli}; the twin serves the plans whose moduli
+    // allow it (same shape, same pass table)
+    static const int kCompanionDefaults[][2] = {{159, 165}};      // n = 4096: moduli 2^60 - c, 0 < c < 2^28 (arithmetic level 3)
+    int id = main.entry->fwd_companion;
+    for (const auto& d : kCompanionDefaults)
+        if (d[0] == id && regblock_choose(n, d[1], arith_level, narrow_level).valid()) id = d[1];
+    regblock_layout rb = regblock_choose(n, id, arith_level, narrow_level);
     rb.min_frames = main.entry->fwd_companion_min_frames;
     return rb;
 }
+
+int regblock_id(const regblock_layout& rb) { return rb.valid() ? rb.entry->id : -1; }
 
 void regblock_build_table(const regblock_layout& rb, const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
     if (rb.valid()) rb.entry->build(tw, pre, out);

@@ -12,7 +12,8 @@ struct prime_consts {           // one per prime, device array
     uint64_t mu_hi, mu_lo;      // floor(2^128 / q)           (pointwise multiply)
     uint64_t n_inv, n_inv_p;    // n^-1 mod q and its precomputed quotient      (inverse, last stage)
     uint64_t w1n, w1n_p;        // inv_twiddle[1] * n^-1 mod q and its quotient  (inverse, last stage)
-    uint64_t est;               // low word: float slightly below 2^32 / q for reduce_final_est, 0 when q < 2^58
+    uint64_t est;               // low word: float slightly below 2^32 / q for reduce_final_est, 0 when q < 2^58;
+                                // high word: c when q = 2^60 - c with 0 < c < 2^28, else 0 (reduce_final_q60c, csub_8q_q60c)
 };
 
 struct rb_entry;   // one configuration of the kernel registry (rb_registry.hpp)
@@ -53,13 +54,14 @@ struct frame_layout {
 // host-side construction of the register-blocked forward table for one prime from its
 // natural-index tables; appends rb.entry->table_pairs pairs to `out`
 // config_id -1: tuned default for n; arith_level: 0 exact only, 1 every modulus <= 2^61 (fast form legal),
-// 2 every modulus <= 2^60 (16q-lazy form legal)
+// 2 every modulus <= 2^60 (16q-lazy form legal), 3 every modulus 2^60 - c with 0 < c < 2^28 (the forward kernels specialised for that class)
 // narrow_level: 0 some modulus >= 2^31; 1 every modulus < 2^31; 2 every modulus < 2^30 (the 32-bit kernels of rb32_kernels.hpp; they
 // also need arith_level >= 1, i.e. tables that honour the precon contract)
 regblock_layout regblock_choose(uint32_t n, int config_id, int arith_level, int narrow_level = 0);
 // forward-only layout that serves the forward calls of a plan whose tuned default is `main` (a second kernel shape that is faster for
 // the forward transform only), or an invalid layout
 regblock_layout regblock_forward_companion(const regblock_layout& main, uint32_t n, int arith_level, int narrow_level);
+int regblock_id(const regblock_layout& rb);      // registry id of the layout's entry, -1 for an invalid layout
 void regblock_build_table(const regblock_layout& rb, const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out);
 
 hipError_t kernels_init();  // one-time function attributes (large dynamic LDS)

@@ -20,7 +20,7 @@ struct agx_ntt_plan {
     int device = -1;
     int variant = AGX_VARIANT_AUTO;
     bool has_inverse = false;
-    int arith_level = 0;     // 0 exact only; 1: every modulus <= 2^61 (8q-lazy legal); 2: <= 2^60 (16q-lazy legal)
+    int arith_level = 0;     // 0 exact only; 1: every modulus <= 2^61 (8q-lazy legal); 2: <= 2^60 (16q-lazy legal); 3: every modulus 2^60 - c, 0 < c < 2^28
     int narrow_level = 0;    // 1: every modulus < 2^31, 2: < 2^30 -- the 32-bit kernels are legal (with arith_level >= 1: tables honour the contract)
     std::vector<uint64_t> moduli, psi;  // psi = 0 when the tables came from the caller
     agx::prime_consts* d_consts = nullptr;

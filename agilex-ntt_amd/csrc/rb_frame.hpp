@@ -184,6 +184,8 @@ constexpr int kOptStreamTw = 1 << 25;      // twiddles streamed in chunks of a f
 constexpr int kOptPinBf = 1 << 26;         // with kOptStreamTw: butterflies are pinned in program order (their operands pass through ordered empty asm statements), so the
                                            // instruction selector cannot start the partial products of the whole stage at once -- what takes an R = 5 pass from ~205 VGPRs to
                                            // the 128 a 1024-thread workgroup may use; one wave cannot issue faster than one VALU per ~8 clocks anyway (ILP buys nothing there)
+constexpr int kOptQ60c = 1 << 27;          // with kOptEstReduce, forward only: every modulus is 2^60 - c, 0 < c < 2^28 (arithmetic level 3): sign-bit conditional subtracts and the
+                                           // final reduction by the top four bits (modarith.hpp: q60c_tailfree)
 constexpr int kOptStreamCh1 = 1 << 29;     // with kOptStreamTw: one table entry per chunk instead of two or four (R = 4 passes then fit 64 VGPRs: 8 waves/SIMD)
 // Measured and removed in round 4 (the records stay in profiles/ and DESIGN.md 3.4-3.6): the XOR-swizzled image, cross products as 32-bit multiplies,
 // the inverse's twiddle-first / priority policies, timing ablations, persistent streaming / loop forms of the forward, resident sub-blocks with
@@ -210,9 +212,11 @@ struct rb2_frame {
     static constexpr bool NT_LOAD = (OPT & kOptNtLoad) != 0, NT_STORE = (OPT & kOptNtStore) != 0;
     static constexpr bool TWA_INV = (OPT & kOptTwAheadInv) != 0 && R == 3;
     static constexpr bool EST = LAZY16 && SEL && (OPT & kOptEstReduce) != 0;
+    static constexpr bool Q60C = EST && (OPT & kOptQ60c) != 0;
     static constexpr bool SPLIT = (OPT & kOptSplitWord) != 0;
     static constexpr bool STREAM_TW = (OPT & kOptStreamTw) != 0, PIN_BF = (OPT & kOptPinBf) != 0, STREAM_CH1 = (OPT & kOptStreamCh1) != 0;
     static_assert(!EST || lazy16_tailfree::valid(L), "tail-free schedule must keep every stage within 16q");
+    static_assert(!Q60C || q60c_tailfree::valid(L), "sign-bit subtracts must keep every stage within 16q + 8c");
     mutable uint64_t ts[12];
     // kept old form: polymul_wp<1, 1, 1, kWpExact, 5> -- without these two members (dead since round 4) b's frame load moves ahead of NTT(a)'s address arithmetic
     uint64_t trace_wave = ~0ull;
@@ -273,12 +277,17 @@ struct rb2_frame {
         fc.nq1 = opaque_sgpr64(0 - fc.q1);
         fc.q8 = q << 3;
         fc.nq8 = opaque_sgpr64(0 - fc.q8);
+        if constexpr (Q60C) {
+            k.c = (uint32_t)(est >> 32);      // the host sets it for the plans this kernel may serve (prime_consts::est)
+            k.c8 = k.c << 3;
+        }
     }
 
     // forward butterfly number `stage` of the whole transform in this frame's arithmetic
     template <int stage>
     __device__ __forceinline__ void butterfly(uint64_t& a, uint64_t& b, const twpair& w) const {
-        if constexpr (EST) ct_butterfly_lazy16<SEL, lazy16_tailfree::subtracts(stage, L), false>(a, b, w.x, w.y, k, fc);
+        if constexpr (Q60C) ct_butterfly_q60c<lazy16_tailfree::subtracts(stage, L)>(a, b, w.x, w.y, k);
+        else if constexpr (EST) ct_butterfly_lazy16<SEL, lazy16_tailfree::subtracts(stage, L), false>(a, b, w.x, w.y, k, fc);
         else if constexpr (LAZY16) ct_butterfly_lazy16<SEL, lazy16_schedule::subtracts(stage), stage == L - 1>(a, b, w.x, w.y, k, fc);
         else if constexpr (FAST) ct_butterfly_fast<SEL>(a, b, w.x, w.y, k);
         else ct_butterfly_exact(a, b, w.x, w.y, k);
@@ -326,6 +335,7 @@ struct rb2_frame {
     // basic blocks, which costs registers: R = 5 kernels went from 204 to the VGPRs of the arithmetic proper).
     template <int MODE>
     __device__ __forceinline__ uint64_t final_reduce(uint64_t v) const {
+        if constexpr (Q60C) return reduce_final_q60c(v, k, fc, MODE == 4 ? lazy_out : (MODE & 1) != 0);      // no quotient estimate: MODE bit 1 is never set
         if constexpr (MODE == 4) {      // undecided: branch per coefficient (the old form)
             if constexpr (EST) return reduce_final_est<SEL>(v, k, fc, lazy_out);
             else if constexpr (LAZY16) return reduce_final_lazy16<SEL>(v, k, fc, lazy_out);
@@ -344,12 +354,12 @@ struct rb2_frame {
         }
         if (lazy_out) {
             // EST kernels: lazy outputs of q >= 2^58 still take the estimate (MODE 1 inside reduce_final_est keys on est_inv itself)
-            if constexpr (EST) {
+            if constexpr (EST && !Q60C) {
                 if (k.est_inv != 0.0f) body(std::integral_constant<int, 3>{});
                 else body(std::integral_constant<int, 1>{});
             } else body(std::integral_constant<int, 1>{});
         } else {
-            if constexpr (EST) {
+            if constexpr (EST && !Q60C) {
                 if (k.est_inv != 0.0f) body(std::integral_constant<int, 2>{});
                 else body(std::integral_constant<int, 0>{});
             } else body(std::integral_constant<int, 0>{});

@@ -409,7 +409,7 @@ void build_table_t(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglon
 }
 
 template <class F>
-constexpr int rb2_arith_level() { return F::LAZY16 ? 2 : F::FAST_ARITH ? 1 : 0; }      // rb_entry::arith
+constexpr int rb2_arith_level() { return F::Q60C ? 3 : F::LAZY16 ? 2 : F::FAST_ARITH ? 1 : 0; }      // rb_entry::arith
 
 // A kernel shape S says what the launches of one family differ in besides the kernel symbol: the rb_entry fields (log_n, r, fpb = frames per
 // workgroup, min_waves, table_pairs, lds, build, arith, narrow), threads per workgroup, and the flag word.  Every forward kernel ends in one:
@@ -567,7 +567,7 @@ constexpr rb_entry make_entry2(int id) {
     return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>);
 }
 
-// forward kernel only (a plan's forward companion: rb_entry::fwd_companion)
+// forward kernel only (a plan's forward companion: rb_entry::fwd_companion), one frame per workgroup
 template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single_fwd(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;

@@ -16,7 +16,7 @@ struct rb_entry {
     void (*build)(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out);      // appends one prime's pass table
     hipError_t (*launch)(const plan_view&, const uint64_t*, uint64_t*, const frame_layout&, hipStream_t);
     hipError_t (*init)();    // allows every kernel the entry launches the dynamic LDS it is launched with
-    int arith;   // 0: exact (reference op sequence, q < 2^62); 1: fast (q <= 2^61); 2: 16q-lazy (q <= 2^60)
+    int arith;   // 0: exact (reference op sequence, q < 2^62); 1: fast (q <= 2^61); 2: 16q-lazy (q <= 2^60); 3: 16q-lazy for q = 2^60 - c, 0 < c < 2^28
     hipError_t (*launch_inv)(const plan_view&, const uint64_t*, const uint64_t*, uint64_t*, const frame_layout&, hipStream_t);      // in2 != null: in * in2 is transformed
     hipError_t (*launch_mul)(const plan_view&, const uint64_t*, const uint64_t*, uint64_t*, const frame_layout&, hipStream_t);      // c = INTT(NTT(a) o NTT(b)) in one launch
     int fwd_companion = 0;     // registry id of a forward-only entry that serves forward calls of a plan whose main entry is this one (0: none)

@@ -14,6 +14,10 @@ const rb_entry kEntries[] = {
     with_fwd_companion(make_entry2<12, 3, 1, 1 | ((kOptPad | kOptSelect | kOptLazy16 | kOptTwAhead | kOptPrio | kOptPrioBarrier | kOptScalarBase | kOptLazyInv | kOptTwAheadInv | kOptNtLoad | kOptNtStore | kOptEstReduce) << 1), 8>(93), 159, 4096),
     make_entry2<12, 3, 1, 0 | ((kOptPad | kOptPrio | kOptPrioBarrier | kOptScalarBase) << 1), 8>(91),
     make_entry2<12, 3, 1, 1 | ((kOptPad | kOptSelect | kOptTwAhead | kOptPrio | kOptPrioBarrier | kOptScalarBase) << 1), 8>(92),
+#ifdef AGX_DIAG
+    // A/B twin kept in lib/libagxntt_diag.so: id 93's forward kernel with the arithmetic of id 165 (moduli 2^60 - c, 0 < c < 2^28)
+    make_entry_single_fwd<12, 3, 1 | ((kOptPad | kOptSelect | kOptLazy16 | kOptTwAhead | kOptPrio | kOptPrioBarrier | kOptScalarBase | kOptNtLoad | kOptNtStore | kOptEstReduce | kOptQ60c) << 1), 8>(166),
+#endif
 };
 }  // namespace AGX_TU
 

@@ -126,6 +126,9 @@ AGX_API int agx_ntt_plan_destroy(agx_ntt_plan* plan);
 /* or be issued from another thread while it runs (it synchronises the device before it frees the old tables)                         */
 AGX_API int agx_ntt_plan_set_variant(agx_ntt_plan* plan, int variant);
 AGX_API int agx_ntt_plan_info(const agx_ntt_plan* plan, uint32_t* n, uint32_t* num_primes, int* device, int* has_inverse);
+/* which kernel a forward call of `batch` frames per prime runs: its id in the kernel registry (the k of AGX_VARIANT_REGBLOCK_BASE + k), -1 for */
+/* the LDS radix-2 kernels.  Read-only; for tests and A/B measurements                                                                       */
+AGX_API int agx_ntt_plan_forward_kernel(const agx_ntt_plan* plan, uint64_t batch, int* registry_id);
 AGX_API int agx_ntt_plan_get_modulus(const agx_ntt_plan* plan, uint32_t prime_index, uint64_t* q, uint64_t* psi);
 
 /* ------------------------------------------------------------------------- */
