@@ -261,17 +261,19 @@ hipError_t set_lds_attr(F* fn, size_t bytes) {
 
 }  // namespace
 
-regblock_layout regblock_choose(uint32_t n, int config_id, int arith_level, int narrow_level) {
-    regblock_layout rb;
+rb_selection regblock_select(uint32_t n, int config_id, int arith_level, int narrow_level) {
+    rb_selection sel;
     int log_n = 0;
     while ((1u << log_n) < n) ++log_n;
-    if (log_n < 1) return rb;
+    if (log_n < 1) return sel;
     // a 32-bit entry is legal when every modulus fits its tier and the tables honour the precon contract
     auto legal = [&](const rb_entry& c) { return c.arith <= arith_level && (c.narrow == 0 || (arith_level >= 1 && narrow_level >= (c.narrow == 2 ? 2 : 1))); };
-    const rb_entry* e = nullptr;
+    auto find = [&](int id) -> const rb_entry* {
+        const rb_entry* c = rb_lookup(id);
+        return c && c->log_n == log_n && legal(*c) ? c : nullptr;
+    };
     if (config_id >= 0) {
-        e = rb_lookup(config_id);
-        if (e && (e->log_n != log_n || !legal(*e))) e = nullptr;
+        sel.main = find(config_id);
     } else {
         // tuned defaults, best first; the lazier arithmetic forms only when every modulus allows them
         static const int kDefaults[] = {260, 261, 262, 263, 264, 265, 266, 267, 230, 231, 232, 233, 234, 240, 241, 242, 243, 244,      // n = 2 ... 512, narrow moduli: wave-packed 32-bit kernels (tier 2, then tier 1)
@@ -281,32 +283,19 @@ regblock_layout regblock_choose(uint32_t n, int config_id, int arith_level, int 
                                         93, 92, 91,                                                      // n = 4096: R = 3, 8 waves/SIMD (16q-lazy, fast, exact)
                                         150, 151, 152, 153, 154, 155, 156, 157, 158,                     // n = 1024 / 2048 / 8192: streamed single-frame kernels
                                         119, 117, 121, 120, 123, 122};                                  // n = 32768 / 16384
-        for (int id : kDefaults) {
-            const rb_entry* c = rb_lookup(id);
-            if (c && c->log_n == log_n && legal(*c)) { e = c; break; }
-        }
+        for (int id : kDefaults)
+            if ((sel.main = find(id))) break;
     }
-    rb.entry = e;
-    return rb;
-}
-
-regblock_layout regblock_forward_companion(const regblock_layout& main, uint32_t n, int arith_level, int narrow_level) {
-    if (!main.valid() || main.entry->fwd_companion <= 0) return regblock_layout{};
+    if (!sel.main || sel.main->fwd_companion <= 0) return sel;
     // tuned defaults among the forward companions: {companion, its twin for a narrower class of moduli}; the twin serves the plans whose moduli
     // allow it (same shape, same pass table)
     static const int kCompanionDefaults[][2] = {{159, 165}};      // n = 4096: moduli 2^60 - c, 0 < c < 2^28 (arithmetic level 3)
-    int id = main.entry->fwd_companion;
+    int id = sel.main->fwd_companion;
     for (const auto& d : kCompanionDefaults)
-        if (d[0] == id && regblock_choose(n, d[1], arith_level, narrow_level).valid()) id = d[1];
-    regblock_layout rb = regblock_choose(n, id, arith_level, narrow_level);
-    rb.min_frames = main.entry->fwd_companion_min_frames;
-    return rb;
-}
-
-int regblock_id(const regblock_layout& rb) { return rb.valid() ? rb.entry->id : -1; }
-
-void regblock_build_table(const regblock_layout& rb, const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
-    if (rb.valid()) rb.entry->build(tw, pre, out);
+        if (d[0] == id && find(d[1])) id = d[1];
+    sel.forward_large = find(id);
+    sel.min_frames = sel.main->fwd_companion_min_frames;
+    return sel;
 }
 
 hipError_t kernels_init() {
@@ -353,33 +342,6 @@ hipError_t launch_inverse_radix2(const plan_view& pv, const uint64_t* in, uint64
                            fl.prime_stride, fl.poly_stride);
     }
     return hipGetLastError();
-}
-
-hipError_t launch_forward_regblock(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    if (!pv.rb.valid()) return hipErrorInvalidValue;
-    return pv.rb.entry->launch(pv, in, out, fl, s);
-}
-
-bool regblock_has_inverse(const regblock_layout& rb) { return rb.valid() && rb.entry->launch_inv; }
-
-bool regblock_has_polymul(const regblock_layout& rb) { return rb.valid() && rb.entry->launch_mul; }
-
-hipError_t launch_inverse_regblock(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    if (!regblock_has_inverse(pv.rb) || !pv.itw_rb) return hipErrorInvalidValue;
-    return pv.rb.entry->launch_inv(pv, in, in2, out, fl, s);
-}
-
-hipError_t launch_polymul_regblock(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
-    if (!regblock_has_polymul(pv.rb) || !pv.itw_rb) return hipErrorInvalidValue;
-    return pv.rb.entry->launch_mul(pv, a, b, c, fl, s);
-}
-
-bool regblock_has_mulhat(const regblock_layout& rb) { return rb.valid() && rb.entry->launch_mulhat; }
-
-hipError_t launch_polymul_ntt_regblock(const plan_view& pv, const uint64_t* a, const uint64_t* bhat, uint64_t* c, const frame_layout& fl,
-                                       int64_t bhat_prime_stride, int64_t bhat_poly_stride, hipStream_t s) {
-    if (!regblock_has_mulhat(pv.rb) || !pv.itw_rb) return hipErrorInvalidValue;
-    return pv.rb.entry->launch_mulhat(pv, a, bhat, c, fl, bhat_prime_stride, bhat_poly_stride, s);
 }
 
 hipError_t launch_pointwise_bhat(const plan_view& pv, uint64_t* c, const uint64_t* bhat, uint64_t batch, int64_t bhat_prime_stride,

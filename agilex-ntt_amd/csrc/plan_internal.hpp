@@ -9,43 +9,12 @@
 #include <new>
 #include <system_error>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "ntt_kernels.hpp"
 
 constexpr uint32_t kTicketSlots = 64;    // distinct streams of one plan that may run ticket-drawing kernels; further streams get the stateless kernels
-
-struct agx_ntt_plan {
-    uint32_t n = 0, log_n = 0, num_primes = 0;
-    int device = -1;
-    int variant = AGX_VARIANT_AUTO;
-    bool has_inverse = false;
-    int arith_level = 0;     // 0 exact only; 1: every modulus <= 2^61 (8q-lazy legal); 2: <= 2^60 (16q-lazy legal); 3: every modulus 2^60 - c, 0 < c < 2^28
-    int narrow_level = 0;    // 1: every modulus < 2^31, 2: < 2^30 -- the 32-bit kernels are legal (with arith_level >= 1: tables honour the contract)
-    std::vector<uint64_t> moduli, psi;  // psi = 0 when the tables came from the caller
-    agx::prime_consts* d_consts = nullptr;
-    ulonglong2* d_tw = nullptr;
-    ulonglong2* d_itw = nullptr;
-    ulonglong2* d_tw_rb = nullptr;
-    ulonglong2* d_itw_rb = nullptr;
-    agx::regblock_layout rb;
-    agx::regblock_layout rb_fwd;            // forward-only layout (another kernel shape that is faster for the forward transform), or invalid
-    ulonglong2* d_tw_rb_fwd = nullptr;
-    // {next frame, retired workgroups} pairs for the kernels that hand out frames dynamically (the inverse loop kernels of n >= 16384),
-    // one pair per STREAM: launches on one stream run one after the other, and the last workgroup of a launch zeroes the
-    // pair, so a stream's launches can share one; launches on different streams get different pairs.  Only a launcher that needs a
-    // pair asks for one (plan_view::ticket).  When all kTicketSlots are taken, a new stream gets the slot of a stream whose latest ticket
-    // launch has provably completed (its event has fired: the pair is idle and zero); if there is none, no pair: the stateless fixed-stride
-    // kernels (ADVICE r03: slots used to be claimed for good, so a long-lived plan used with short-lived streams ended up on the slower form).
-    uint32_t* d_ticket = nullptr;
-    mutable std::mutex ticket_mu;
-    mutable std::vector<hipStream_t> ticket_streams;
-    // slot i: an event recorded behind the stream's latest ticket launch (once it has completed the pair reads {0, 0} again: the last
-    // workgroup out zeroes it), and whether a launch that took the slot has not recorded its event yet
-    mutable std::vector<hipEvent_t> ticket_events;
-    mutable std::vector<char> ticket_pending;
-};
-
 
 namespace agx {
 
@@ -57,6 +26,79 @@ int& last_hip_error_slot();      // this thread's agx_ntt_last_hip_error() value
         hipError_t e_ = (expr);                          \
         if (e_ != hipSuccess) return agx::hip_fail(e_);  \
     } while (0)
+
+// device memory of a plan: move-only, freed with its owner
+template <class T>
+struct device_buf {
+    T* p = nullptr;
+    device_buf() = default;
+    device_buf(device_buf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    device_buf& operator=(device_buf&& o) noexcept { return std::swap(p, o.p), *this; }      // the old memory goes with `o`
+    ~device_buf() { if (p) (void)hipFree(p); }
+    operator T*() const { return p; }
+    int upload(const std::vector<T>& src) {      // into an empty owner
+        AGX_HIP(hipMalloc(reinterpret_cast<void**>(&p), src.size() * sizeof(T)));
+        AGX_HIP(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+        return AGX_OK;
+    }
+};
+
+// the pass tables of one registry entry for every prime of a plan ([P][entry->table_pairs] each), on the host and on the device
+template <class Table>
+struct pass_tables_of {
+    const rb_entry* entry = nullptr;
+    Table fwd, inv;      // from the forward tables; from the inverse tables (empty / null: the plan has none, or the entry is forward-only here)
+};
+using host_pass_tables = pass_tables_of<std::vector<ulonglong2>>;
+using pass_tables = pass_tables_of<device_buf<ulonglong2>>;
+
+// How a call finds its kernel: a route is a ready-made plan_view, its `rb` the registry entry that serves the call (null: the radix-2 /
+// generic kernels).  One route per operation, filled by resolve_routes (agx_ntt.cpp) whenever the plan's state changes.
+using route = plan_view;
+struct plan_routes {
+    route forward;
+    route forward_large;      // forward launches of >= min_frames frames (batch x primes); rb null: none, `forward` serves every launch
+    uint32_t min_frames = 0;
+    route inverse;            // rb set: rb->launch_inv; else the radix-2 inverse
+    route polymul;            // rb set: rb->launch_mul; else two forwards + `inverse` (product fused into its load when that has an entry)
+    route polymul_ntt;        // rb set: rb->launch_mulhat; else forward + product in place + inverse
+};
+
+}  // namespace agx
+
+struct agx_ntt_plan {
+    uint32_t n = 0, log_n = 0, num_primes = 0;
+    int device = -1;
+    int variant = AGX_VARIANT_AUTO;
+    bool explicit_id = false;     // the variant named a registry id: that entry serves every call (no large-launch companion)
+    bool has_inverse = false;
+    int arith_level = 0;     // 0 exact only; 1: every modulus <= 2^61 (8q-lazy legal); 2: <= 2^60 (16q-lazy legal); 3: every modulus 2^60 - c, 0 < c < 2^28
+    int narrow_level = 0;    // 1: every modulus < 2^31, 2: < 2^30 -- the 32-bit kernels are legal (with arith_level >= 1: tables honour the contract)
+    std::vector<uint64_t> moduli, psi;  // psi = 0 when the tables came from the caller
+    agx::device_buf<agx::prime_consts> d_consts;
+    agx::device_buf<ulonglong2> d_tw, d_itw;      // [P][n] {w,w'} natural index; d_itw null without inverse tables
+    agx::rb_selection chosen;      // the registry's answer for the current variant (LDS_RADIX2 leaves it as it was)
+    agx::pass_tables main;         // of chosen.main; replaced when set_variant changes the entry
+    // Of the tuned default's large-launch forward entry (forward table only): built at creation and kept for the plan's life, also
+    // across an explicit choice, so that AUTO / REGBLOCK find it again.  It serves calls only while chosen.forward_large names it.
+    agx::pass_tables companion;
+    agx::plan_routes routes;
+    // {next frame, retired workgroups} pairs for the kernels that hand out frames dynamically (the inverse loop kernels of n >= 16384),
+    // one pair per STREAM: launches on one stream run one after the other, and the last workgroup of a launch zeroes the
+    // pair, so a stream's launches can share one; launches on different streams get different pairs.  Only a launcher that needs a
+    // pair asks for one (plan_view::ticket).  When all kTicketSlots are taken, a new stream gets the slot of a stream whose latest ticket
+    // launch has provably completed (its event has fired: the pair is idle and zero); if there is none, no pair: the stateless fixed-stride
+    // kernels (ADVICE r03: slots used to be claimed for good, so a long-lived plan used with short-lived streams ended up on the slower form).
+    agx::device_buf<uint32_t> d_ticket;
+    mutable std::mutex ticket_mu;
+    mutable std::vector<hipStream_t> ticket_streams;
+    // slot i: an event recorded behind the stream's latest ticket launch (once it has completed the pair reads {0, 0} again: the last
+    // workgroup out zeroes it), and whether a launch that took the slot has not recorded its event yet
+    mutable std::vector<hipEvent_t> ticket_events;
+    mutable std::vector<char> ticket_pending;
+};
+
+namespace agx {
 
 // nothing may propagate across the C boundary: std::vector / std::thread can throw inside the entry points
 template <class F>
@@ -97,9 +139,10 @@ struct plan_image {
     bool has_inverse = false;
     int arith_level = 0, narrow_level = 0;
     std::vector<uint64_t> moduli, psi;
-    regblock_layout rb, rb_fwd;
+    rb_selection chosen;
     std::vector<prime_consts> consts;
-    std::vector<ulonglong2> tw_pairs, itw_pairs, rb_pairs, irb_pairs, fwd_pairs;
+    std::vector<ulonglong2> tw_pairs, itw_pairs;
+    std::vector<host_pass_tables> tables;      // one per distinct entry `chosen` names, the main entry first
 };
 // arguments as validated by agx_ntt_plan_create*: moduli legal for n, tables [num_primes][n]; psi / itw / ipre may be null
 void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
@@ -107,8 +150,13 @@ void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const 
 // a plan on the CURRENT device from a prepared image
 int instantiate_plan(agx_ntt_plan** out, const plan_image& img);
 void free_plan(agx_ntt_plan* p);
+// argument checks and the plan construction the one-shot calls of agx_host.cpp share with agx_ntt_plan_create
+int check_size(uint32_t n);
+int check_modulus(uint64_t q, uint32_t n);
+int build_plan(agx_ntt_plan** out, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
+               const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre);
 
-// staging resources of the host-pointer pipeline: three slots of {pinned in, pinned out, device} on three streams
+// staging resources of the host-pointer pipeline (agx_host.cpp): three slots of {pinned in, pinned out, device} on three streams
 constexpr size_t kStageChunkBytes = (size_t)32 << 20;
 struct staging_set {
     static constexpr int kSlots = 3;

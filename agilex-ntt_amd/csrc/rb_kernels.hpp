@@ -446,32 +446,32 @@ hipError_t launch_frames(K kernel, const plan_view& pv, const frame_layout& fl, 
 
 template <class S, auto K>
 hipError_t launch_fwd_t(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    return launch_frames<S>(K, pv, fl, s, in, out, pv.consts, pv.tw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
+    return launch_frames<S>(K, pv, fl, s, in, out, pv.consts, pv.tw_rb, pv.rb->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
                             S::flags(in, out, nullptr, fl));
 }
 
 template <class S, auto K>
 hipError_t launch_inv_t(const plan_view& pv, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
     if constexpr (S::flags_everywhere)
-        return launch_frames<S>(K, pv, fl, s, in, in2, out, pv.consts, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
+        return launch_frames<S>(K, pv, fl, s, in, in2, out, pv.consts, pv.itw_rb, pv.rb->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
                                 S::flags(in, in2, out, fl));
     else
-        return launch_frames<S>(K, pv, fl, s, in, in2, out, pv.consts, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride);
+        return launch_frames<S>(K, pv, fl, s, in, in2, out, pv.consts, pv.itw_rb, pv.rb->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride);
 }
 
 template <class S, auto K>
 hipError_t launch_mul_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
     if constexpr (S::flags_everywhere)      // the product kernels read no flag
-        return launch_frames<S>(K, pv, fl, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride, 0u);
+        return launch_frames<S>(K, pv, fl, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride, 0u);
     else
-        return launch_frames<S>(K, pv, fl, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride);
+        return launch_frames<S>(K, pv, fl, s, a, b, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride);
 }
 
 // the product by a pre-transformed operand: the frame layout describes a and c, bhat brings its own two strides
 template <class S, auto K>
 hipError_t launch_mulhat_t(const plan_view& pv, const uint64_t* a, const uint64_t* bhat, uint64_t* c, const frame_layout& fl, int64_t bhat_prime_stride,
                            int64_t bhat_poly_stride, hipStream_t s) {
-    return launch_frames<S>(K, pv, fl, s, a, bhat, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
+    return launch_frames<S>(K, pv, fl, s, a, bhat, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
                             bhat_prime_stride, bhat_poly_stride);
 }
 
@@ -479,12 +479,12 @@ template <int L, int R, int ARITH, int MINW>
 hipError_t launch_mul_park_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     if (a == b)      // squaring: NTT(a) times itself in registers (the parked form would read its own parked words back when c aliases too)
-        return launch_frames<S>(&polysquare_rb2<L, R, ARITH, MINW>, pv, fl, s, a, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs, fl.batch,
+        return launch_frames<S>(&polysquare_rb2<L, R, ARITH, MINW>, pv, fl, s, a, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb->table_pairs, fl.batch,
                                 fl.prime_stride, fl.poly_stride);
     // the operand c aliases (if any) must be the one that is read completely before c's frame is written
     const uint64_t* first = (c == b) ? b : a;
     const uint64_t* second = (c == b) ? a : b;
-    return launch_frames<S>(&polymul_rb2_park<L, R, ARITH, MINW>, pv, fl, s, first, second, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb.entry->table_pairs,
+    return launch_frames<S>(&polymul_rb2_park<L, R, ARITH, MINW>, pv, fl, s, first, second, c, pv.consts, pv.tw_rb, pv.itw_rb, pv.rb->table_pairs,
                             fl.batch, fl.prime_stride, fl.poly_stride);
 }
 
@@ -511,7 +511,7 @@ hipError_t launch_inv_rb2_loop_t(const plan_view& pv, const uint64_t* in, const 
     const hipError_t e = resident_grid<S>(pv, fl, &grid, &total);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((inv_rb2_loop<L, R, ARITH, MINW>), dim3(grid), dim3(S::threads), S::lds, s, in, in2, out, pv.consts, pv.itw_rb,
-                       pv.rb.entry->table_pairs, (uint32_t)fl.batch, total, fl.prime_stride, fl.poly_stride);
+                       pv.rb->table_pairs, (uint32_t)fl.batch, total, fl.prime_stride, fl.poly_stride);
     return hipGetLastError();
 }
 
@@ -535,7 +535,7 @@ hipError_t launch_inv_rb2_dloop_t(const plan_view& pv, const uint64_t* in, const
     uint32_t* ticket = pv.ticket(s);      // taken last: from here on the launch is issued and ticket_done() follows it
     if (!ticket) return launch_inv_rb2_loop_t<L, R, ARITH, MINW>(pv, in, in2, out, fl, s);      // no pair provably free: stateless form
     hipLaunchKernelGGL((inv_rb2_dloop<L, R, ARITH, MINW>), dim3(grid), dim3(S::threads), S::lds + kDloopMailboxBytes, s, in, in2, out, pv.consts, pv.itw_rb,
-                       pv.rb.entry->table_pairs, (uint32_t)fl.batch, total, fl.prime_stride, fl.poly_stride, ticket);
+                       pv.rb->table_pairs, (uint32_t)fl.batch, total, fl.prime_stride, fl.poly_stride, ticket);
     e = hipGetLastError();
     pv.ticket_done(s, ticket);      // an event behind the launch: when it has fired the pair is idle (and zero) and the plan may hand it to another stream
     return e;
