@@ -19,6 +19,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 AGX_OK = 0
 VARIANT_AUTO, VARIANT_LDS_RADIX2, VARIANT_REGBLOCK = 0, 1, 2
 VARIANT_REGBLOCK_BASE = 256  # + registry index: A/B measurements only
+RESCALE_FLOOR, RESCALE_ROUND = 0, 1
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -51,6 +52,7 @@ ABI = {
     "agx_ntt_pointwise": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_polymul": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_polymul_ntt": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    "agx_ntt_rescale": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
@@ -69,6 +71,7 @@ ABI = {
     "agx_ntt_group_inverse": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64]),
     "agx_ntt_group_polymul": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64]),
     "agx_ntt_group_polymul_ntt": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64, _p64]),
+    "agx_ntt_group_rescale": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64, _int]),
     "agx_ntt_group_synchronize": (_int, [_vp]),
 }
 
@@ -290,6 +293,11 @@ class Plan:
         (one bhat frame per frame) or 1 (one bhat frame per prime, shared by the whole batch)"""
         _check(lib().agx_ntt_polymul_ntt(self._h, d_a, d_bhat, d_c, batch, batch if bhat_batch is None else bhat_batch, stream), "polymul_ntt")
 
+    def rescale(self, d_x, d_out, d_scratch, batch, mode=RESCALE_ROUND, stream=0):
+        """exact division by the last modulus on NTT-form frames: d_x [P][batch][n] -> d_out [P-1][batch][n] (may be d_x); d_scratch:
+        batch*n words, or d_x's last slab (which is then overwritten); mode: RESCALE_FLOOR or RESCALE_ROUND"""
+        _check(lib().agx_ntt_rescale(self._h, d_x, d_out, d_scratch, batch, mode, stream), "rescale")
+
     def fill_synthetic(self, d_out, batch, first_poly=0, seed=42, stream=0):
         _check(lib().agx_ntt_fill_synthetic(self._h, d_out, batch, first_poly, seed, stream), "fill_synthetic")
 
@@ -401,6 +409,10 @@ class DeviceGroup:
         """per shard as Plan.polymul_ntt; bhat_batch: None = batch, or one entry (batch[i] or 1) per shard"""
         _check(lib().agx_ntt_group_polymul_ntt(self._h, self._ptrs(d_a), self._ptrs(d_bhat), self._ptrs(d_c), self._batches(batch),
                                                self._batches(batch if bhat_batch is None else bhat_batch)), "group_polymul_ntt")
+
+    def rescale(self, d_x, d_out, d_scratch, batch, mode=RESCALE_ROUND):
+        """per shard as Plan.rescale"""
+        _check(lib().agx_ntt_group_rescale(self._h, self._ptrs(d_x), self._ptrs(d_out), self._ptrs(d_scratch), self._batches(batch), mode), "group_rescale")
 
     def synchronize(self):
         _check(lib().agx_ntt_group_synchronize(self._h), "group_synchronize")

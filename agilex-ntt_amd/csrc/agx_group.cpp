@@ -259,11 +259,12 @@ int agx_ntt_group_inverse_host(const agx_ntt_group* group, const uint64_t* in, u
 }
 
 // ---- device pointers: one pointer and one batch per shard, every shard launched from its own thread on its own stream ---------
-enum group_op { OP_FORWARD, OP_INVERSE, OP_POLYMUL, OP_POLYMUL_NTT };
+enum group_op { OP_FORWARD, OP_INVERSE, OP_POLYMUL, OP_POLYMUL_NTT, OP_RESCALE };
 
 static int group_device(const agx_ntt_group* group, group_op op, const uint64_t* const* a, const uint64_t* const* b, uint64_t* const* c,
-                        uint64_t* const* scratch, const uint64_t* batch, const uint64_t* bhat_batch = nullptr) {
-    if (!group || !a || !c || !batch || ((op == OP_POLYMUL || op == OP_POLYMUL_NTT) && !b) || (op == OP_POLYMUL_NTT && !bhat_batch)) return AGX_ERR_NULL_POINTER;
+                        uint64_t* const* scratch, const uint64_t* batch, const uint64_t* bhat_batch = nullptr, int mode = 0) {
+    if (!group || !a || !c || !batch || ((op == OP_POLYMUL || op == OP_POLYMUL_NTT) && !b) || (op == OP_POLYMUL_NTT && !bhat_batch) || (op == OP_RESCALE && !scratch))
+        return AGX_ERR_NULL_POINTER;
     return guarded([&] {
         return on_every_shard(group, [&](uint32_t i) -> int {
             shard* s = group->shards[i].get();
@@ -272,6 +273,7 @@ static int group_device(const agx_ntt_group* group, group_op op, const uint64_t*
                 case OP_FORWARD: return agx_ntt_forward(s->plan, a[i], c[i], batch[i], s->stream);
                 case OP_INVERSE: return agx_ntt_inverse(s->plan, a[i], c[i], batch[i], s->stream);
                 case OP_POLYMUL: return agx_ntt_polymul(s->plan, a[i], b[i], c[i], scratch ? scratch[i] : nullptr, batch[i], s->stream);
+                case OP_RESCALE: return agx_ntt_rescale(s->plan, a[i], c[i], scratch[i], batch[i], mode, s->stream);
                 default: return agx_ntt_polymul_ntt(s->plan, a[i], b[i], c[i], batch[i], bhat_batch[i], s->stream);
             }
         });
@@ -294,6 +296,11 @@ int agx_ntt_group_polymul(const agx_ntt_group* group, const uint64_t* const* d_a
 int agx_ntt_group_polymul_ntt(const agx_ntt_group* group, const uint64_t* const* d_a, const uint64_t* const* d_bhat, uint64_t* const* d_c,
                               const uint64_t* batch, const uint64_t* bhat_batch) {
     return group_device(group, OP_POLYMUL_NTT, d_a, d_bhat, d_c, nullptr, batch, bhat_batch);
+}
+
+int agx_ntt_group_rescale(const agx_ntt_group* group, const uint64_t* const* d_x, uint64_t* const* d_out, uint64_t* const* d_scratch,
+                          const uint64_t* batch, int mode) {
+    return group_device(group, OP_RESCALE, d_x, nullptr, d_out, d_scratch, batch, nullptr, mode);
 }
 
 int agx_ntt_group_synchronize(const agx_ntt_group* group) {

@@ -136,7 +136,7 @@ static std::vector<ulonglong2> build_pass_table(const rb_entry* e, const std::ve
 static void resolve_routes(agx_ntt_plan* p) {
     route generic;
     generic.n = p->n, generic.log_n = p->log_n, generic.num_primes = p->num_primes;
-    generic.consts = p->d_consts, generic.tw = p->d_tw, generic.itw = p->d_itw;
+    generic.consts = p->d_consts, generic.tw = p->d_tw, generic.itw = p->d_itw, generic.rescale = p->d_rescale;
     generic.ticket_for = &plan_ticket_for, generic.ticket_launched = &plan_ticket_launched;
     generic.ticket_ctx = p;      // the plan is heap-allocated and never moves
     auto through = [&](const pass_tables& t) {
@@ -155,6 +155,9 @@ static void resolve_routes(agx_ntt_plan* p) {
     r.inverse = inv && e->launch_inv ? main : generic;
     r.polymul = inv && e->launch_mul ? main : generic;
     r.polymul_ntt = inv && e->launch_mulhat ? main : generic;
+    // the fused second launch pairs with whatever `inverse` is; everything else (n <= 512, the 32-bit families, radix-2) is generic: the
+    // call then runs `inverse`, the coefficient-domain step and `forward` on views of these routes
+    r.rescale = inv && e->launch_rescale ? main : generic;
 }
 
 static const route& forward_route(const agx_ntt_plan* p, uint64_t batch) {
@@ -240,6 +243,16 @@ void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const 
             c.w1n_p = shoup_quotient(c.w1n, q);
         }
     }
+    // agx_ntt_rescale: q_L^-1 mod q_i with its quotient, h mod q_i and h = (q_L - 1) / 2, for i < P-1
+    img.rescale_legal = num_primes >= 2;
+    img.rescale.assign(num_primes >= 2 ? num_primes - 1 : 0, rescale_consts{});
+    for (uint32_t k = 0; k + 1 < num_primes; ++k) {
+        const uint64_t q = moduli[k], q_last = moduli[num_primes - 1], h = (q_last - 1) >> 1;
+        rescale_consts& rc = img.rescale[k];
+        rc.q_last = q_last, rc.h = h, rc.h_mod_q = h % q;
+        if (inv_mod_euclid(q_last, q, &rc.qlinv)) rc.qlinv_p = shoup_quotient(rc.qlinv, q);
+        else img.rescale_legal = false;
+    }
     const rb_selection& c = img.chosen;
     if (c.main) img.tables.push_back({c.main, build_pass_table(c.main, img.tw_pairs, num_primes, n), itw ? build_pass_table(c.main, img.itw_pairs, num_primes, n) : std::vector<ulonglong2>{}});
     if (c.forward_large && c.forward_large != c.main) img.tables.push_back({c.forward_large, build_pass_table(c.forward_large, img.tw_pairs, num_primes, n), {}});
@@ -259,6 +272,7 @@ int instantiate_plan(agx_ntt_plan** out, const plan_image& img) {
     p->n = img.n, p->log_n = img.log_n, p->num_primes = img.num_primes;
     p->has_inverse = img.has_inverse, p->arith_level = img.arith_level, p->narrow_level = img.narrow_level;
     p->chosen = img.chosen;
+    p->rescale_legal = img.rescale_legal;
     p->ticket_streams.reserve(kTicketSlots);      // plan_ticket_for() runs inside unguarded launch calls: it must never allocate
     p->ticket_events.assign(kTicketSlots, nullptr);
     p->ticket_pending.assign(kTicketSlots, 0);
@@ -268,6 +282,7 @@ int instantiate_plan(agx_ntt_plan** out, const plan_image& img) {
     AGX_HIP(hipGetDevice(&p->device));
     AGX_HIP(kernels_init_once(p->device));
     if ((rc = p->d_consts.upload(img.consts))) return rc;
+    if (!img.rescale.empty() && (rc = p->d_rescale.upload(img.rescale))) return rc;
     if ((rc = p->d_ticket.upload(std::vector<uint32_t>(2 * kTicketSlots, 0)))) return rc;
     if ((rc = p->d_tw.upload(img.tw_pairs))) return rc;
     if (img.has_inverse && (rc = p->d_itw.upload(img.itw_pairs))) return rc;
@@ -623,6 +638,54 @@ int agx_ntt_polymul_ntt(const agx_ntt_plan* plan, const uint64_t* d_a, const uin
     if ((rc = forward_common(plan, d_a, d_c, batch, (int64_t)batch * n, n, true, stream))) return rc;
     AGX_HIP(launch_pointwise_bhat(plan->routes.forward, d_c, d_bhat, batch, bhat_prime_stride, bhat_poly_stride, s));
     return agx_ntt_inverse(plan, d_c, d_c, batch, stream);
+}
+
+int agx_ntt_rescale(const agx_ntt_plan* plan, const uint64_t* d_x, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, int mode, void* stream) {
+    if (!plan || !d_x || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes;
+    if (P < 2 || (mode != AGX_RESCALE_FLOOR && mode != AGX_RESCALE_ROUND)) return AGX_ERR_BAD_ARGUMENT;
+    const int64_t n = (int64_t)plan->n, slab = (int64_t)batch * n;
+    // x as the whole plan's frame set against itself (device, grid limit, alignment), then out against slabs 0 .. P-2 of x: the same frames or disjoint ones
+    int rc = check_call(plan, d_x, d_x, batch, slab, n);
+    if (rc) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_scratch)) & 7u) return AGX_ERR_BAD_ARGUMENT;
+    if (partial_overlap(d_x, d_out, plan->n, P - 1, batch, slab, n)) return AGX_ERR_BAD_ARGUMENT;
+    {
+        // every set is dense, so each is one range of words.  The scratch may BE x's last slab (the caller gives that slab up); otherwise it
+        // touches nothing of x, and never out or slabs 0 .. P-2 of x, which P-1 workgroups per frame read while others already write
+        const uintptr_t bytes = (uintptr_t)slab * sizeof(uint64_t), head = (uintptr_t)(P - 1) * bytes;
+        const uintptr_t x0 = reinterpret_cast<uintptr_t>(d_x), o0 = reinterpret_cast<uintptr_t>(d_out), s0 = reinterpret_cast<uintptr_t>(d_scratch);
+        auto touch = [](uintptr_t a, uintptr_t a_bytes, uintptr_t b, uintptr_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; };
+        if (touch(s0, bytes, o0, head) || touch(s0, bytes, x0, head)) return AGX_ERR_BAD_ARGUMENT;
+        if (s0 != x0 + head && touch(s0, bytes, x0 + head, bytes)) return AGX_ERR_BAD_ARGUMENT;
+        if (d_out != d_x && touch(o0, head, x0 + head, bytes)) return AGX_ERR_BAD_ARGUMENT;      // out over the last slab, which the first launch reads
+    }
+    if (!plan->rescale_legal) return AGX_ERR_BAD_MODULUS;      // some q_i shares a factor with (distinct primes: equals) the last modulus
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    const bool round = mode == AGX_RESCALE_ROUND;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const frame_layout fl{batch, slab, n};
+    const uint64_t* x_last = d_x + (size_t)(P - 1) * (size_t)slab;
+    // scratch <- INTT_L(x_L), coefficients in [0, q_L): the plan's inverse on the view of prime P-1
+    const route last = prime_range(plan->routes.inverse, P - 1, P);
+    auto inverse_on = [&](const route& r, const uint64_t* in, uint64_t* out) {
+        return r.rb ? r.rb->launch_inv(r, in, nullptr, out, fl, s) : launch_inverse_radix2(r, in, out, fl, s);
+    };
+    if (const route& r = plan->routes.rescale; r.rb) {
+        // two launches: the lift, the forward transform and (x_i - .) q_L^-1 stay on chip; a wave reads its words of x_i before it writes them
+        AGX_HIP(inverse_on(last, x_last, d_scratch));
+        AGX_HIP(r.rb->launch_rescale(prime_range(r, 0, P - 1), d_x, d_scratch, d_out, fl, round, s));
+        return AGX_OK;
+    }
+    // generic route, no more scratch: out <- INTT(x_0 .. x_{P-2}); scratch <- INTT_L(x_L); out <- (out - lift(scratch)) q_L^-1 in the
+    // coefficient domain; out <- NTT(out)
+    AGX_HIP(inverse_on(prime_range(plan->routes.inverse, 0, P - 1), d_x, d_out));
+    AGX_HIP(inverse_on(last, x_last, d_scratch));
+    const route head = prime_range(forward_route(plan, batch), 0, P - 1);
+    AGX_HIP(launch_rescale_coeff(head, d_out, d_scratch, batch, round, s));
+    AGX_HIP(head.rb ? head.rb->launch(head, d_out, d_out, fl, s) : launch_forward_radix2(head, d_out, d_out, fl, s));
+    return AGX_OK;
 }
 
 int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly, uint64_t seed, void* stream) {

@@ -78,6 +78,18 @@ uint64_t min_primitive_root_2n(uint64_t q, uint32_t n) {
     return least;
 }
 
+bool inv_mod_euclid(uint64_t a, uint64_t q, uint64_t* inv) {
+    // extended Euclid on (a mod q, q) with the coefficient of a kept mod q; gcd 1 <=> invertible
+    __int128 r0 = q, r1 = a % q, t0 = 0, t1 = 1;
+    while (r1 != 0) {
+        const __int128 k = r0 / r1, r2 = r0 - k * r1, t2 = t0 - k * t1;
+        r0 = r1, r1 = r2, t0 = t1, t1 = t2;
+    }
+    if (r0 != 1) return false;
+    *inv = (uint64_t)(t0 < 0 ? t0 + (__int128)q : t0);
+    return true;
+}
+
 uint64_t shoup_quotient(uint64_t w, uint64_t q) { return (uint64_t)(((u128)w << 64) / q); }
 
 void power_tables_bitrev(uint64_t q, uint64_t base, uint32_t n, uint64_t* tw, uint64_t* pre) {

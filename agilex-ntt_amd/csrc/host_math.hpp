@@ -10,6 +10,7 @@ namespace agx {
 uint64_t mul_mod(uint64_t a, uint64_t b, uint64_t q);
 uint64_t pow_mod(uint64_t a, uint64_t e, uint64_t q);
 uint64_t inv_mod(uint64_t a, uint64_t q);  // q prime
+bool inv_mod_euclid(uint64_t a, uint64_t q, uint64_t* inv);  // any q > 1: false when gcd(a, q) != 1
 bool is_prime_u64(uint64_t q);
 inline bool is_pow2(uint32_t n) { return n && !(n & (n - 1)); }
 inline int log2u(uint32_t n) { int l = 0; while ((1u << l) < n) ++l; return l; }

@@ -60,6 +60,28 @@ __device__ __forceinline__ uint64_t mul_mod_barrett(uint64_t a, uint64_t b, cons
 }
 
 
+// v mod q in [0,q) for ANY 64-bit v and any q < 2^62 (whatever the ratio v / q): mu_hi = floor(2^64 / q), so the estimate
+// e = floor(v mu_hi / 2^64) lies in (v/q - v/2^64 - 1, v/q]: e is floor(v/q) or one less, v - e q in [0,2q) < 2^63.
+__device__ __forceinline__ uint64_t reduce_u64(uint64_t v, const barrett128& k) {
+    return csub(v - __umul64hi(v, k.mu_hi) * k.q, k.q);
+}
+
+// Exact division by the last RNS modulus q_L (agx_ntt_rescale), per coefficient.
+// lift: t in [0,q_L) (a coefficient of the last slab) -> u = ((t + h) mod q_L) mod q - (h mod q)  mod q, in [0,q); floor mode passes
+// h = hq = 0.  t + h < 2 q_L < 2^63; one conditional subtract brings it under q_L, reduce_u64 under q for any ratio q_L / q.
+__device__ __forceinline__ uint64_t rescale_lift(uint64_t t, uint64_t h, uint64_t hq, uint64_t q_last, const barrett128& k) {
+    const uint64_t a = reduce_u64(csub(t + h, q_last), k);      // [0,q)
+    return a - hq + (a < hq ? k.q : 0);                           // hq < q: [0,q)
+}
+// finish: (x - z) q_L^-1 mod q in [0,q), {w, wp} = q_L^-1 mod q and its quotient.  LAZY (q <= 2^60 only): x, z in [0,4q), d = x + 4q - z
+// in (0,8q) <= 2^63.  Otherwise x, z in [0,q) and d = x + q - z in (0,2q) < 2^63: 4q is never formed, so q may be anything below 2^62.
+// mul_shoup_lazy takes any 64-bit d to [0,2q).
+template <bool LAZY>
+__device__ __forceinline__ uint64_t rescale_finish(uint64_t x, uint64_t z, uint64_t w, uint64_t wp, uint64_t q) {
+    const uint64_t d = x + (LAZY ? q << 2 : q) - z;
+    return csub(mul_shoup_lazy(d, w, wp, q), q);
+}
+
 // ---------------------------------------------------------------------------------------
 // Hand-selected instruction forms for the throughput kernels.
 //

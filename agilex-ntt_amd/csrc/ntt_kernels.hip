@@ -202,6 +202,21 @@ __global__ void pointwise_bhat_kernel(uint64_t* __restrict__ c, const uint64_t* 
     }
 }
 
+// agx_ntt_rescale, generic route, in the coefficient domain: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i with u_i the lift of t[k] to q_i
+// (rescale_lift).  out: dense [prime][batch][n] over the view's primes 0 .. P-2, values in [0,q_i) as the inverse leaves them; t: [batch][n]
+// in [0,q_L), shared by the primes.
+__global__ void rescale_coeff_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ t, const prime_consts* __restrict__ consts,
+                                     const rescale_consts* __restrict__ rcs, uint64_t per_prime, uint32_t round) {
+    const uint32_t prime = blockIdx.y;
+    const prime_consts k = consts[prime];
+    const rescale_consts rc = rcs[prime];
+    const barrett128 bk{k.q, k.mu_hi, k.mu_lo};
+    const uint64_t h = round ? rc.h : 0, hq = round ? rc.h_mod_q : 0;
+    uint64_t* op = out + (uint64_t)prime * per_prime;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_prime; i += (uint64_t)gridDim.x * blockDim.x)
+        op[i] = rescale_finish<false>(op[i], rescale_lift(t[i], h, hq, rc.q_last, bk), rc.qlinv, rc.qlinv_p, k.q);
+}
+
 __device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -356,6 +371,13 @@ hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64
     const uint64_t per_prime = batch << pv.log_n;
     dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
     hipLaunchKernelGGL(pointwise_kernel, grid, dim3(256), 0, s, a, b, c, pv.consts, per_prime);
+    return hipGetLastError();
+}
+
+hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
+    hipLaunchKernelGGL(rescale_coeff_kernel, grid, dim3(256), 0, s, out, t, pv.consts, pv.rescale, per_prime, round ? 1u : 0u);
     return hipGetLastError();
 }
 

@@ -16,6 +16,14 @@ struct prime_consts {           // one per prime, device array
                                 // high word: c when q = 2^60 - c with 0 < c < 2^28, else 0 (reduce_final_q60c, csub_8q_q60c)
 };
 
+// agx_ntt_rescale: what prime i < P-1 needs to divide by the last modulus q_L = q_{P-1}; a device array of its own ([P-1]) beside the
+// prime_consts, which every kernel loads and which therefore stay as narrow as they are.  q_last and h are the same in every entry.
+struct rescale_consts {
+    uint64_t qlinv, qlinv_p;    // q_L^-1 mod q_i and its precomputed quotient floor(qlinv * 2^64 / q_i)
+    uint64_t h_mod_q;           // h mod q_i, h = (q_L - 1) / 2                  (AGX_RESCALE_ROUND)
+    uint64_t q_last, h;
+};
+
 struct rb_entry;   // one configuration of the kernel registry (rb_registry.hpp): static storage, valid for the life of the library
 
 // device-side view of a plan
@@ -27,6 +35,7 @@ struct plan_view {
     const rb_entry* rb = nullptr;          // the registry entry this view serves, or null (the radix-2 / generic kernels only)
     const ulonglong2* tw_rb = nullptr;     // [P][rb->table_pairs]: the entry's pass tables from the forward tables
     const ulonglong2* itw_rb = nullptr;    // same layout from the inverse tables, or null
+    const rescale_consts* rescale = nullptr;   // [P-1], or null (one prime)
     // Kernels that hand out frames through a counter ask for a {next frame, retired workgroups} pair of the plan HERE, at launch time and
     // only if they need one: the pair is keyed by the stream (launches on one stream serialise, so they may share a pair; the last
     // workgroup out zeroes it).  nullptr = no pair can be proven free (too many distinct streams): take the stateless fixed-stride form.
@@ -64,6 +73,9 @@ hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64
 // c <- c o bhat in place on the dense [prime][batch][n] layout, bhat with strides of its own as above (the generic path of agx_ntt_polymul_ntt)
 hipError_t launch_pointwise_bhat(const plan_view& pv, uint64_t* c, const uint64_t* bhat, uint64_t batch, int64_t bhat_prime_stride,
                                  int64_t bhat_poly_stride, hipStream_t s);
+// the coefficient-domain step of agx_ntt_rescale's generic route: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i on the dense [prime][batch][n]
+// layout of pv's primes (a view of primes 0 .. P-2), u_i the lift of t[k] ([batch][n], coefficients of the last slab in [0, q_L)) to q_i
+hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

@@ -62,6 +62,7 @@ struct plan_routes {
     route inverse;            // rb set: rb->launch_inv; else the radix-2 inverse
     route polymul;            // rb set: rb->launch_mul; else two forwards + `inverse` (product fused into its load when that has an entry)
     route polymul_ntt;        // rb set: rb->launch_mulhat; else forward + product in place + inverse
+    route rescale;            // rb set: `inverse` on prime P-1, then rb->launch_rescale on primes 0 .. P-2; else inverse, coefficient-domain step, forward
 };
 
 }  // namespace agx
@@ -76,6 +77,8 @@ struct agx_ntt_plan {
     int narrow_level = 0;    // 1: every modulus < 2^31, 2: < 2^30 -- the 32-bit kernels are legal (with arith_level >= 1: tables honour the contract)
     std::vector<uint64_t> moduli, psi;  // psi = 0 when the tables came from the caller
     agx::device_buf<agx::prime_consts> d_consts;
+    agx::device_buf<agx::rescale_consts> d_rescale;      // [P-1]; null for one prime
+    bool rescale_legal = false;      // P >= 2 and q_{P-1} invertible modulo every other modulus (distinct primes are); judged at the call
     agx::device_buf<ulonglong2> d_tw, d_itw;      // [P][n] {w,w'} natural index; d_itw null without inverse tables
     agx::rb_selection chosen;      // the registry's answer for the current variant (LDS_RADIX2 leaves it as it was)
     agx::pass_tables main;         // of chosen.main; replaced when set_variant changes the entry
@@ -141,6 +144,8 @@ struct plan_image {
     std::vector<uint64_t> moduli, psi;
     rb_selection chosen;
     std::vector<prime_consts> consts;
+    std::vector<rescale_consts> rescale;      // [P-1] (agx_ntt_rescale); entries of moduli that share a factor with the last stay zero
+    bool rescale_legal = false;
     std::vector<ulonglong2> tw_pairs, itw_pairs;
     std::vector<host_pass_tables> tables;      // one per distinct entry `chosen` names, the main entry first
 };

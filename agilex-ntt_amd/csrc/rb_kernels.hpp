@@ -374,6 +374,71 @@ mulhat_rb2(const uint64_t* __restrict__ a, const uint64_t* __restrict__ bhat, ui
     f.store_pass0(x, c, base, live);
 }
 
+// The second launch of agx_ntt_rescale (exact division by the last RNS modulus q_L on NTT-form frames) for primes i < P-1:
+// out_i = (x_i - NTT_i(u_i)) q_L^-1 mod q_i, u_i = the lift of t to q_i (rescale_lift, modarith.hpp), t = INTT_L(x_L) in [0,q_L) as the
+// first launch (the plan's inverse on the view of prime P-1) left it in the scratch: dense [batch][n], read by the P-1 workgroups of
+// a frame (plain loads: it should stay in L2).  The frame of t is loaded in the pass-0 layout and lifted where it sits in registers,
+// then transformed; in the last pass's layout every lane streams in its own C consecutive words of x_i (16-byte loads, requested
+// ahead exactly as mulhat_rb2 requests bhat), which may be lazy ([0,4q), as agx_ntt_forward_lazy leaves them), and the result leaves
+// through the forward kernels' store.  One frame in registers; 16n bytes per (prime, frame) plus 8n per frame for t.
+// out may BE x (in place): a wave stores exactly the 64 C contiguous words its own lanes loaded from x (the last pass is
+// wave-contiguous), and store_last_layout relays them through the image behind a wavefront-scope release / acquire pair, which keeps
+// every load of x ahead of every store of the wave.  x and out are therefore not __restrict__.  Slots of a partly filled workgroup
+// read the last frame again and store nothing.
+template <int L, int R, int PPB, int ARITH, int MINW>
+__global__ void __launch_bounds__((1 << (L - R)) * PPB, (MINW > AGX_MULHAT_MAXW ? AGX_MULHAT_MAXW : MINW))
+rescale_rb2(const uint64_t* x, const uint64_t* __restrict__ t, uint64_t* out,
+            const prime_consts* __restrict__ consts, const rescale_consts* __restrict__ rcs, const twpair* __restrict__ tw_rb,
+            uint32_t pairs_per_prime, uint64_t frames_x, int64_t prime_stride, int64_t poly_stride, uint32_t round) {
+    AGX_RB2_PROLOGUE;
+    const prime_consts pc = consts[prime];
+    const rescale_consts rc = rcs[prime];
+    const barrett128 bk{pc.q, pc.mu_hi, pc.mu_lo};
+    const uint64_t h = round ? rc.h : 0, hq = round ? rc.h_mod_q : 0;      // wave-uniform
+    // q <= 2^60: rescale_finish takes both operands in [0,4q), so the transform may skip its last conditional subtracts and x_i needs no reduction
+    f.lazy_out = F::LAZY16;
+    constexpr int GRP = 4, NG = C / GRP;      // registers per group of x loads (two 16-byte loads), groups per thread
+    static_assert(C % GRP == 0, "whole groups");
+    constexpr bool EARLY = !F::STREAM_TW && !F::SPLIT && F::NP >= 2 && NG <= 2;      // as mulhat_rb2
+    const bhat_pair* xp = reinterpret_cast<const bhat_pair*>(x + base + (uint32_t)f.tid * C);
+    uint64_t u[C];
+    const uint64_t* tf = t + (int64_t)fx * poly_stride;      // input prime stride 0: every prime of the frame reads the same words
+#pragma unroll
+    for (int r = 0; r < C; ++r) u[r] = tf[f.tid + (uint32_t)r * T];
+#pragma unroll
+    for (int r = 0; r < C; ++r) u[r] = rescale_lift(u[r], h, hq, rc.q_last, bk);      // [0,q_L) -> [0,q)
+    bhat_pair z[EARLY ? NG : 2][GRP / 2];
+    auto request = [&](auto Gq) {
+        constexpr int g = Gq;
+        static_for<0, GRP / 2>([&](auto I) { z[EARLY ? g : (g & 1)][I] = xp[g * (GRP / 2) + (int)I]; });
+    };
+    if constexpr (EARLY) {
+        f.template forward_passes<0, F::NP - 1>(u, tw_rb + (size_t)prime * pairs_per_prime);
+        static_for<0, NG>(request);
+        f.template forward_passes<F::NP - 1, F::NP>(u, tw_rb + (size_t)prime * pairs_per_prime);
+    } else {
+        f.forward(u, tw_rb + (size_t)prime * pairs_per_prime);
+        request(std::integral_constant<int, 0>{});
+    }
+    static_for<0, NG>([&](auto Gq) {
+        constexpr int g = Gq;
+        if constexpr (!EARLY && g + 1 < NG) request(std::integral_constant<int, g + 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<0, GRP>([&](auto I) {
+            constexpr int i = I, r = g * GRP + i;
+            uint64_t v = z[EARLY ? g : (g & 1)][i / 2][i & 1];
+            // beyond 2^60 the difference wants x_i (lazy: below 4q, which may not fit 64 bits -- reduce_4q never forms it) and NTT(u), which is then
+            // fully reduced, below q
+            if constexpr (!F::LAZY16) v = reduce_4q(v, pc.q, pc.q << 1);
+            asm volatile("" : "+v"(u[r]));
+            u[r] = rescale_finish<F::LAZY16>(v, u[r], rc.qlinv, rc.qlinv_p, pc.q);
+            asm volatile("" : "+v"(u[r]));
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    f.store_last_layout(u, out, base, live);
+}
+
 // ---- host side: pass tables, launch glue and registry entries, written once for every kernel family ---------------------------------
 // (the 32-bit kernels of rb32_kernels.hpp and the wave-packed kernels of wp_kernels.hpp bring their own shape struct and nothing else)
 
@@ -475,6 +540,13 @@ hipError_t launch_mulhat_t(const plan_view& pv, const uint64_t* a, const uint64_
                             bhat_prime_stride, bhat_poly_stride);
 }
 
+// agx_ntt_rescale's second launch: pv is the view of primes 0 .. P-2, the frame layout describes x and out, t is dense [batch][n]
+template <class S, auto K>
+hipError_t launch_rescale_t(const plan_view& pv, const uint64_t* x, const uint64_t* t, uint64_t* out, const frame_layout& fl, bool round, hipStream_t s) {
+    return launch_frames<S>(K, pv, fl, s, x, t, out, pv.consts, pv.rescale, pv.tw_rb, pv.rb->table_pairs, fl.batch, fl.prime_stride, fl.poly_stride,
+                            round ? 1u : 0u);
+}
+
 template <int L, int R, int ARITH, int MINW>
 hipError_t launch_mul_park_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
@@ -544,8 +616,9 @@ hipError_t launch_inv_rb2_dloop_t(const plan_view& pv, const uint64_t* in, const
 // ---- registry entries: each is built from exactly the kernels it launches, so nothing else is instantiated ----------------------------
 template <class S>
 constexpr rb_entry shape_entry(int id, decltype(rb_entry::launch) fwd, decltype(rb_entry::init) init, decltype(rb_entry::launch_inv) inv,
-                               decltype(rb_entry::launch_mul) mul, decltype(rb_entry::launch_mulhat) mulhat = nullptr) {
-    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow, mulhat};
+                               decltype(rb_entry::launch_mul) mul, decltype(rb_entry::launch_mulhat) mulhat = nullptr,
+                               decltype(rb_entry::launch_rescale) rescale = nullptr) {
+    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow, mulhat, rescale};
 }
 
 // forward, inverse and the product with both forward results in registers, one workgroup per S::fpb frames each (every family has this form)
@@ -556,7 +629,7 @@ constexpr rb_entry make_entry3(int id) {
 
 // PPB frames per workgroup (the n = 4096 defaults: R = 3, 8 waves/SIMD; n = 1024 with streamed twiddles, where two frames of 2^R coefficients still fit
 // the register budget and the parked product's round trip through c's frame would cost more); the product kernel at MULW waves per SIMD
-// and the product by a pre-transformed operand (one frame in registers; at most AGX_MULHAT_MAXW waves per SIMD)
+// and the product by a pre-transformed operand and the rescale kernel (one frame in registers; at most AGX_MULHAT_MAXW waves per SIMD)
 template <int L, int R, int PPB, int ARITH, int MINW, int MULW = MINW>
 constexpr rb_entry make_entry2(int id) {
     using S = rb2_shape<L, R, PPB, ARITH, MINW>;
@@ -564,7 +637,9 @@ constexpr rb_entry make_entry2(int id) {
     constexpr auto inv = &inv_rb2<L, R, PPB, ARITH, MINW>;
     constexpr auto mul = &polymul_rb2<L, R, PPB, ARITH, MULW>;
     constexpr auto mulhat = &mulhat_rb2<L, R, PPB, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>);
+    constexpr auto rescale = &rescale_rb2<L, R, PPB, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat, rescale>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>,
+                          &launch_rescale_t<S, rescale>);
 }
 
 // forward kernel only (a plan's forward companion: rb_entry::fwd_companion), one frame per workgroup
@@ -576,15 +651,16 @@ constexpr rb_entry make_entry_single_fwd(int id) {
 }
 
 // the streamed single-frame kernels (reg_s<n>.hip): one frame in registers per workgroup at any time (R = 5: a second frame cannot
-// be held): forward, inverse, the fused product by polymul_rb2_park / polysquare_rb2, and the product by a pre-transformed operand
+// be held): forward, inverse, the fused product by polymul_rb2_park / polysquare_rb2, the product by a pre-transformed operand and the rescale kernel
 template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     constexpr auto fwd = &fwd_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto inv = &inv_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto mulhat = &mulhat_rb2<L, R, 1, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat>,
-                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, mulhat>);
+    constexpr auto rescale = &rescale_rb2<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat, rescale>,
+                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, mulhat>, &launch_rescale_t<S, rescale>);
 }
 
 // entry e with forward calls of its plans routed to the forward-only entry `id` (rb_entry::fwd_companion)
@@ -599,14 +675,15 @@ template <int L, int R, int ARITH, int MINW>
 hipError_t init_rb2_single_invloop_t() {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     const hipError_t e = allow_lds<S::lds, &fwd_rb2<L, R, 1, ARITH, MINW>, &inv_rb2_loop<L, R, ARITH, MINW>, &polymul_rb2_park<L, R, ARITH, MINW>,
-                                   &polysquare_rb2<L, R, ARITH, MINW>, &mulhat_rb2<L, R, 1, ARITH, MINW>>();
+                                   &polysquare_rb2<L, R, ARITH, MINW>, &mulhat_rb2<L, R, 1, ARITH, MINW>, &rescale_rb2<L, R, 1, ARITH, MINW>>();
     return e != hipSuccess ? e : allow_lds<S::lds + kDloopMailboxBytes, &inv_rb2_dloop<L, R, ARITH, MINW>>();
 }
 template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single_invloop(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     return shape_entry<S>(id, &launch_fwd_t<S, &fwd_rb2<L, R, 1, ARITH, MINW>>, &init_rb2_single_invloop_t<L, R, ARITH, MINW>,
-                          &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, &mulhat_rb2<L, R, 1, ARITH, MINW>>);
+                          &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, &mulhat_rb2<L, R, 1, ARITH, MINW>>,
+                          &launch_rescale_t<S, &rescale_rb2<L, R, 1, ARITH, MINW>>);
 }
 
 }  // namespace AGX_TU

@@ -27,7 +27,23 @@ struct rb_entry {
     // a poly stride of 0 = one bhat frame per prime for the whole batch); null: the entry's plans take the generic three-launch path
     hipError_t (*launch_mulhat)(const plan_view&, const uint64_t*, const uint64_t*, uint64_t*, const frame_layout&, int64_t bhat_prime_stride,
                                 int64_t bhat_poly_stride, hipStream_t) = nullptr;
+    // agx_ntt_rescale's second launch on a view of primes 0 .. P-2: out_i = (x_i - NTT_i(lift of t to q_i)) q_L^-1, t ([batch][n], poly stride as
+    // the frame layout's) the coefficients of the last slab; out may be x.  null: the entry's plans take the generic route
+    hipError_t (*launch_rescale)(const plan_view&, const uint64_t* x, const uint64_t* t, uint64_t* out, const frame_layout&, bool round, hipStream_t) = nullptr;
 };
+
+// The view of primes [lo, hi) of a route: every per-prime array starts at prime lo, so the launchers run on one slab or on the first
+// slabs of a call unchanged (the ticket plumbing stays the plan's).
+inline plan_view prime_range(plan_view v, uint32_t lo, uint32_t hi) {
+    v.consts += lo;
+    v.tw += (size_t)lo * v.n;
+    if (v.itw) v.itw += (size_t)lo * v.n;
+    if (v.tw_rb) v.tw_rb += (size_t)lo * v.rb->table_pairs;
+    if (v.itw_rb) v.itw_rb += (size_t)lo * v.rb->table_pairs;
+    if (v.rescale) v.rescale += lo;
+    v.num_primes = hi - lo;
+    return v;
+}
 
 struct rb_span {
     const rb_entry* first;

@@ -5,7 +5,8 @@
 // Checks, for n = 32 (30- and 60-bit q), n = 512 (60-bit), n = 1024 (30-bit q), n = 4096 / 16384 / 32768 (60-bit q) and n = 16384 under the reference's own 17-bit modulus 65537:
 //   NTT(delta_0) = (1,...,1);  NTT(X)[bitrev(k)] = psi^(2k+1);  INTT(NTT(x)) = x on random x;
 // the reference's operand pairing with inData2 != inData (src/kernel/ntt.cpp:584-590); and the convolution theorem against the
-// schoolbook product mod X^n + 1 (n = 64 and 1024).
+// schoolbook product mod X^n + 1 (n = 64 and 1024); and agx_ntt_rescale (n = 4096, two 60-bit primes, both modes) against the division of the
+// 120-bit integers themselves.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -128,6 +129,55 @@ static int run_schoolbook_case(uint32_t n, uint32_t bits) {
     int bad = 0;
     for (uint32_t i = 0; i < n; ++i) bad += fa[i] != want[i];
     std::printf("n=%5u q=%llu INTT(NTT(a) o NTT(b)) vs schoolbook product mod X^n+1  mismatches=%d  %s\n", n, (unsigned long long)q, bad, bad ? "FAIL" : "PASS");
+    return bad != 0;
+}
+
+// agx_ntt_rescale from the definition: X < q_0 q_1 drawn per coefficient (it fits unsigned __int128), its residues transformed on the device,
+// rescaled in place (the last slab as the scratch), and compared with the transform of floor(X / q_1) resp. floor((X + h) / q_1) mod q_0
+static int run_rescale_case(uint32_t n, uint32_t bits) {
+    typedef unsigned __int128 u128;
+    const uint64_t batch = 3;
+    uint64_t qs[2] = {0, 0};
+    if (agx_ntt_find_primes(bits, n, 2, qs)) return 1;
+    const uint64_t qL = qs[1], h = (qL - 1) / 2;
+    agx_ntt_plan *both = nullptr, *first = nullptr;
+    int rc = agx_ntt_plan_create_auto(&both, n, 2, qs, nullptr);
+    if (!rc) rc = agx_ntt_plan_create_auto(&first, n, 1, qs, nullptr);
+    const size_t slab = (size_t)batch * n;
+    std::vector<uint64_t> x(2 * slab), want(slab), got(slab);
+    std::vector<u128> X(slab);
+    uint64_t s = 0x7e5ca1eu + n;
+    auto next = [&] { s = s * 6364136223846793005ull + 1442695040888963407ull; return s >> 3; };
+    for (size_t i = 0; i < slab; ++i) {
+        X[i] = (((u128)next() << 61) | next()) % ((u128)qs[0] * qL);
+        if (i < 4) X[i] = (X[i] / qL) * qL + (i == 0 ? 0 : i == 1 ? h : i == 2 ? h + 1 : qL - 1);      // the boundaries of both modes
+        x[i] = (uint64_t)(X[i] % qs[0]);
+        x[slab + i] = (uint64_t)(X[i] % qL);
+    }
+    uint64_t *d_x = nullptr, *d_w = nullptr;
+    hipError_t he = hipMalloc(reinterpret_cast<void**>(&d_x), 2 * slab * sizeof(uint64_t));
+    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&d_w), slab * sizeof(uint64_t));
+    size_t bad = 0;
+    for (int mode = AGX_RESCALE_FLOOR; mode <= AGX_RESCALE_ROUND && !rc && he == hipSuccess; ++mode) {
+        for (size_t i = 0; i < slab; ++i) want[i] = (uint64_t)(((X[i] + (mode == AGX_RESCALE_ROUND ? h : 0)) / qL) % qs[0]);
+        he = hipMemcpy(d_x, x.data(), 2 * slab * sizeof(uint64_t), hipMemcpyHostToDevice);
+        if (he == hipSuccess) he = hipMemcpy(d_w, want.data(), slab * sizeof(uint64_t), hipMemcpyHostToDevice);
+        if (he != hipSuccess) break;
+        rc = agx_ntt_forward(both, d_x, d_x, batch, nullptr);
+        if (!rc) rc = agx_ntt_rescale(both, d_x, d_x, d_x + slab, batch, mode, nullptr);
+        if (!rc) rc = agx_ntt_forward(first, d_w, d_w, batch, nullptr);
+        if (rc) break;
+        he = hipMemcpy(got.data(), d_x, slab * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        if (he == hipSuccess) he = hipMemcpy(want.data(), d_w, slab * sizeof(uint64_t), hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < slab; ++i) bad += got[i] != want[i];
+    }
+    if (d_x) (void)hipFree(d_x);
+    if (d_w) (void)hipFree(d_w);
+    agx_ntt_plan_destroy(both);
+    agx_ntt_plan_destroy(first);
+    if (rc || he != hipSuccess) { std::printf("n=%u rescale: failed: %s / %s\n", n, agx_ntt_strerror(rc), hipGetErrorString(he)); return 1; }
+    std::printf("n=%5u q=%llu,%llu rescale (floor and round, in place) vs the division of X itself  mismatches=%zu  %s\n", n, (unsigned long long)qs[0],
+                (unsigned long long)qL, bad, bad ? "FAIL" : "PASS");
     return bad != 0;
 }
 
@@ -256,6 +306,7 @@ int main(int argc, char** argv) {
     int fail = run_case(32, 30) | run_case(32, 60) | run_case(512, 60) | run_case(1024, 30) | run_case(4096, 60) | run_case(16384, 60) | run_case(32768, 60) | run_case(16384, 17);
     fail |= run_pairing_case(1024, 30) | run_pairing_case(16384, 60);
     fail |= run_schoolbook_case(64, 30) | run_schoolbook_case(64, 60) | run_schoolbook_case(1024, 30);
+    fail |= run_rescale_case(4096, 60);
     std::printf(fail ? "HARNESS FAILED\n" : "HARNESS PASSED\n");
     return fail;
 }

@@ -39,7 +39,7 @@ typedef enum agx_status {
     AGX_OK = 0,
     AGX_ERR_NULL_POINTER = 1,   /* a required pointer argument is NULL                      */
     AGX_ERR_BAD_SIZE = 2,       /* n is not a power of two in [AGX_NTT_MIN_N, AGX_NTT_MAX_N] */
-    AGX_ERR_BAD_MODULUS = 3,    /* q >= 2^62, q even, q != 1 (mod 2n) or (plan_create_auto) q composite */
+    AGX_ERR_BAD_MODULUS = 3,    /* q >= 2^62, q even, q != 1 (mod 2n) or (plan_create_auto) q composite; rescale: q_i == q_last */
     AGX_ERR_BAD_ROOT = 4,       /* psi is not a primitive 2n-th root of unity mod q           */
     AGX_ERR_BAD_ARGUMENT = 5,   /* zero primes, negative stride, overlapping in/out, ...      */
     AGX_ERR_NO_DEVICE = 6,      /* no usable HIP device                                       */
@@ -188,6 +188,29 @@ AGX_API int agx_ntt_polymul(const agx_ntt_plan* plan, const uint64_t* d_a, const
 AGX_API int agx_ntt_polymul_ntt(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c,
                                 uint64_t batch, uint64_t bhat_batch, void* stream);
 
+/* Exact division by the plan's LAST modulus q_L = q_{P-1} on NTT-form frames (CKKS "rescale", BGV / BFV modulus switching), P >= 2.
+ * Per coefficient, with X in [0, q_0 ... q_{P-1}) the integer the P residues represent and h = (q_L - 1) / 2:
+ *   AGX_RESCALE_FLOOR: Y = floor(X / q_L)         AGX_RESCALE_ROUND: Y = floor((X + h) / q_L)
+ * and out holds Y mod q_i for i < P-1, fully reduced.  Input and output are in NTT form (bit-reversed order, as agx_ntt_forward of this
+ * plan writes it); no approximation anywhere: t = INTT_L(x_L) (+ h mod q_L), out_i = (x_i - NTT_i(t mod q_i - h mod q_i)) q_L^-1 mod q_i.
+ * d_x: dense [P][batch][n], values in [0,q) or lazy exactly as agx_ntt_forward_lazy leaves them.  d_out: dense [P-1][batch][n].
+ * d_scratch: batch*n elements of device memory; it receives the coefficient form of the last slab.
+ * Aliasing: d_out == d_x is allowed (in place: slabs 0 .. P-2 of both coincide).  d_scratch may be exactly d_x's last slab,
+ * d_x + (P-1)*batch*n: the caller thereby GIVES THAT SLAB UP (it is overwritten) -- with d_out == d_x this is the in-place use, which
+ * needs no memory beyond x.  Otherwise d_scratch must be disjoint from d_x and d_out, and x is left unchanged.  d_out partially overlapping
+ * d_x, d_out touching the scratch, or the scratch touching slabs 0 .. P-2 of d_x: AGX_ERR_BAD_ARGUMENT, nothing written.
+ * One prime, or a mode other than the two above: AGX_ERR_BAD_ARGUMENT; a modulus q_i, i < P-1, equal to q_L (decided at the call: plan
+ * creation accepts such plans): AGX_ERR_BAD_MODULUS; a plan without inverse tables: AGX_ERR_NO_INVERSE.
+ * Asynchronous on `stream`, allocates and synchronises nothing (capturable into a hipGraph).
+ * TWO launches (the inverse of the last slab into the scratch; then, one frame on chip, the lift to q_i, the forward transform and the
+ * difference with x_i as it streams in) for n = 1024 ... 32768 whenever some modulus is 2^31 or larger.  Four (inverse of slabs 0 .. P-2
+ * into out, inverse of the last slab, one coefficient-domain pass over out, forward of out in place) for n <= 512, for plans whose moduli
+ * are all below 2^31 and for plans forced onto AGX_VARIANT_LDS_RADIX2. */
+#define AGX_RESCALE_FLOOR 0
+#define AGX_RESCALE_ROUND 1
+AGX_API int agx_ntt_rescale(const agx_ntt_plan* plan, const uint64_t* d_x, uint64_t* d_out, uint64_t* d_scratch,
+                            uint64_t batch, int mode, void* stream);
+
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */
 AGX_API int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly,
@@ -250,6 +273,9 @@ AGX_API int agx_ntt_group_polymul(const agx_ntt_group* group, const uint64_t* co
 /* agx_ntt_polymul_ntt per shard; bhat_batch[i] is batch[i] or 1 */
 AGX_API int agx_ntt_group_polymul_ntt(const agx_ntt_group* group, const uint64_t* const* d_a, const uint64_t* const* d_bhat,
                                       uint64_t* const* d_c, const uint64_t* batch, const uint64_t* bhat_batch);
+/* agx_ntt_rescale per shard; every shard needs its own scratch (which may be its d_x's last slab) */
+AGX_API int agx_ntt_group_rescale(const agx_ntt_group* group, const uint64_t* const* d_x, uint64_t* const* d_out,
+                                  uint64_t* const* d_scratch, const uint64_t* batch, int mode);
 AGX_API int agx_ntt_group_synchronize(const agx_ntt_group* group);
 
 #ifdef __cplusplus

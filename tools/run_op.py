@@ -1,6 +1,6 @@
 """tools/run_op.py -- launch ONE operation of the engine a fixed number of times (for rocprofv3 --pmc / --kernel-trace
 runs on paths bench.py's headline does not cover).
-Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt} [--n N --primes P --batch B --bits 60 --oop --launches K --variant ID]
+Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes P --batch B --bits 60 --oop --launches K --variant ID]
 Under the profiler: rocprofv3 ... -- python3 tools/run_op.py ...   (the interpreter itself after `--`, never this file: an
 `env` shebang hop after the profiler's preload has initialised the GPU is a forbidden exec on this pool)."""
 import argparse
@@ -15,7 +15,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -27,6 +27,8 @@ ap.add_argument("--variant", type=int, default=None, help="registry id (AGX_VARI
 ap.add_argument("--ramp-seconds", type=float, default=0.5, help="run the operation this long before the warm-up launches so the GPU clock has ramped, as bench.py does (0 = cold)")
 ap.add_argument("--mulsets", type=int, default=0, help="mul: K rotating (a, b) operand sets, c and scratch separate (bench.py's n = 32768 product line); 0 = c aliases a on the slabs")
 ap.add_argument("--bcast", action="store_true", help="mulntt: one bhat frame per prime shared by the whole batch (bhat_batch = 1)")
+ap.add_argument("--mode", choices=["floor", "round"], default="round", help="rescale: AGX_RESCALE_FLOOR / AGX_RESCALE_ROUND")
+ap.add_argument("--inplace", action="store_true", help="rescale: out == x with x's last slab as the scratch (default: out and scratch of their own)")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
@@ -60,6 +62,9 @@ if args.op == "mulntt":
         hats[b.data_ptr()] = h
     torch.cuda.synchronize()
 bhat_batch = 1 if args.bcast else args.batch
+# rescale: x = a slab ([P][batch][n], the synthetic residues taken as NTT-form words), out [P-1][batch][n] and batch*n words of scratch
+rs_mode = agx.RESCALE_FLOOR if args.mode == "floor" else agx.RESCALE_ROUND
+rs_out = torch.empty((args.primes - 1) * args.batch * args.n, dtype=torch.int64, device="cuda") if args.op == "rescale" else None
 
 
 def run(i):
@@ -71,6 +76,12 @@ def run(i):
         plan.polymul(a.data_ptr(), b.data_ptr(), cbuf.data_ptr(), scratch.data_ptr(), args.batch, stream)
         return
     a, b = slabs[i % args.slabs], slabs[(i + 1) % args.slabs]
+    if args.op == "rescale":
+        if args.inplace:
+            plan.rescale(a.data_ptr(), a.data_ptr(), a.data_ptr() + 8 * (args.primes - 1) * args.batch * args.n, args.batch, rs_mode, stream)
+        else:
+            plan.rescale(a.data_ptr(), rs_out.data_ptr(), scratch.data_ptr(), args.batch, rs_mode, stream)
+        return
     dst = b if args.oop else a
     if args.op == "fwd":
         plan.forward(a.data_ptr(), dst.data_ptr(), args.batch, stream)
@@ -107,5 +118,9 @@ if args.report:
     import json
 
     json.dump({"calls": calls, "timed": args.launches, "ms_per_launch": ms}, open(args.report, "w"))
-print(f"{args.op} n={args.n} primes={args.primes} batch={args.batch}: {ms:.4f} ms per launch, {args.primes * args.batch / ms / 1e3:.2f} M units/s")
+if args.op == "rescale":
+    print(f"rescale ({args.mode}{', in place' if args.inplace else ''}) n={args.n} primes={args.primes} batch={args.batch} bits={args.bits}: {ms * 1e3:.1f} us per call, "
+          f"{args.batch / ms / 1e3:.3f} M RNS frames/s")
+else:
+    print(f"{args.op} n={args.n} primes={args.primes} batch={args.batch}: {ms:.4f} ms per launch, {args.primes * args.batch / ms / 1e3:.2f} M units/s")
 plan.close()
