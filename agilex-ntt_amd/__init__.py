@@ -20,6 +20,7 @@ AGX_OK = 0
 VARIANT_AUTO, VARIANT_LDS_RADIX2, VARIANT_REGBLOCK = 0, 1, 2
 VARIANT_REGBLOCK_BASE = 256  # + registry index: A/B measurements only
 RESCALE_FLOOR, RESCALE_ROUND = 0, 1
+FORM_COEFF, FORM_NTT = 0, 1
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -53,11 +54,13 @@ ABI = {
     "agx_ntt_polymul": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_polymul_ntt": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp]),
     "agx_ntt_rescale": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp]),
+    "agx_ntt_automorphism": (_int, [_vp, _vp, _vp, _u64, _u32, _int, _vp]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
     "agx_ntt_make_tables": (_int, [_u64, _u64, _u32, _p64, _p64]),
     "agx_ntt_make_inverse_tables": (_int, [_u64, _u64, _u32, _p64, _p64]),
+    "agx_ntt_galois_element": (_int, [_u32, _i64, ctypes.POINTER(_u32)]),
     # groups: the same calls over several GPUs (one shard, one host thread, one stream per listed device)
     "agx_ntt_shard_range": (_int, [_u64, _u32, _u32, _p64, _p64]),
     "agx_ntt_group_create": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_int), _u32, _u32, _u32, _p64, _p64, _p64, _p64, _p64]),
@@ -72,6 +75,7 @@ ABI = {
     "agx_ntt_group_polymul": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64]),
     "agx_ntt_group_polymul_ntt": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64, _p64]),
     "agx_ntt_group_rescale": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64, _int]),
+    "agx_ntt_group_automorphism": (_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _p64, _u32, _int]),
     "agx_ntt_group_synchronize": (_int, [_vp]),
 }
 
@@ -209,6 +213,13 @@ def make_tables(q, psi, n, inverse=False):
     return tw, pre
 
 
+def galois_element(n, step):
+    """the Galois element of a slot rotation by `step`: 5^step mod 2n (negative step: powers of 5^-1); conjugation is 2n - 1"""
+    g = _u32(0)
+    _check(lib().agx_ntt_galois_element(n, step, ctypes.byref(g)), "galois_element")
+    return g.value
+
+
 # ---------------------------------------------------------------------------------------
 # one-shot host path: the reference's ntt_input_kernel + fwd_ntt_kernel + ntt_output_kernel
 # ---------------------------------------------------------------------------------------
@@ -297,6 +308,11 @@ class Plan:
         """exact division by the last modulus on NTT-form frames: d_x [P][batch][n] -> d_out [P-1][batch][n] (may be d_x); d_scratch:
         batch*n words, or d_x's last slab (which is then overwritten); mode: RESCALE_FLOOR or RESCALE_ROUND"""
         _check(lib().agx_ntt_rescale(self._h, d_x, d_out, d_scratch, batch, mode, stream), "rescale")
+
+    def automorphism(self, d_in, d_out, batch, galois_elt, form=FORM_NTT, stream=0):
+        """a(X) -> a(X^galois_elt) on every frame, out of place (d_out may not touch d_in): FORM_NTT permutes the words of NTT-form frames,
+        FORM_COEFF moves and negates coefficients (inputs in [0,4q), outputs in [0,q)); galois_elt odd, below 2n"""
+        _check(lib().agx_ntt_automorphism(self._h, d_in, d_out, batch, galois_elt, form, stream), "automorphism")
 
     def fill_synthetic(self, d_out, batch, first_poly=0, seed=42, stream=0):
         _check(lib().agx_ntt_fill_synthetic(self._h, d_out, batch, first_poly, seed, stream), "fill_synthetic")
@@ -413,6 +429,10 @@ class DeviceGroup:
     def rescale(self, d_x, d_out, d_scratch, batch, mode=RESCALE_ROUND):
         """per shard as Plan.rescale"""
         _check(lib().agx_ntt_group_rescale(self._h, self._ptrs(d_x), self._ptrs(d_out), self._ptrs(d_scratch), self._batches(batch), mode), "group_rescale")
+
+    def automorphism(self, d_in, d_out, batch, galois_elt, form=FORM_NTT):
+        """per shard as Plan.automorphism"""
+        _check(lib().agx_ntt_group_automorphism(self._h, self._ptrs(d_in), self._ptrs(d_out), self._batches(batch), galois_elt, form), "group_automorphism")
 
     def synchronize(self):
         _check(lib().agx_ntt_group_synchronize(self._h), "group_synchronize")

@@ -259,10 +259,10 @@ int agx_ntt_group_inverse_host(const agx_ntt_group* group, const uint64_t* in, u
 }
 
 // ---- device pointers: one pointer and one batch per shard, every shard launched from its own thread on its own stream ---------
-enum group_op { OP_FORWARD, OP_INVERSE, OP_POLYMUL, OP_POLYMUL_NTT, OP_RESCALE };
+enum group_op { OP_FORWARD, OP_INVERSE, OP_POLYMUL, OP_POLYMUL_NTT, OP_RESCALE, OP_AUTOMORPHISM };
 
 static int group_device(const agx_ntt_group* group, group_op op, const uint64_t* const* a, const uint64_t* const* b, uint64_t* const* c,
-                        uint64_t* const* scratch, const uint64_t* batch, const uint64_t* bhat_batch = nullptr, int mode = 0) {
+                        uint64_t* const* scratch, const uint64_t* batch, const uint64_t* bhat_batch = nullptr, int mode = 0, uint32_t galois_elt = 0) {
     if (!group || !a || !c || !batch || ((op == OP_POLYMUL || op == OP_POLYMUL_NTT) && !b) || (op == OP_POLYMUL_NTT && !bhat_batch) || (op == OP_RESCALE && !scratch))
         return AGX_ERR_NULL_POINTER;
     return guarded([&] {
@@ -274,6 +274,7 @@ static int group_device(const agx_ntt_group* group, group_op op, const uint64_t*
                 case OP_INVERSE: return agx_ntt_inverse(s->plan, a[i], c[i], batch[i], s->stream);
                 case OP_POLYMUL: return agx_ntt_polymul(s->plan, a[i], b[i], c[i], scratch ? scratch[i] : nullptr, batch[i], s->stream);
                 case OP_RESCALE: return agx_ntt_rescale(s->plan, a[i], c[i], scratch[i], batch[i], mode, s->stream);
+                case OP_AUTOMORPHISM: return agx_ntt_automorphism(s->plan, a[i], c[i], batch[i], galois_elt, mode, s->stream);
                 default: return agx_ntt_polymul_ntt(s->plan, a[i], b[i], c[i], batch[i], bhat_batch[i], s->stream);
             }
         });
@@ -301,6 +302,11 @@ int agx_ntt_group_polymul_ntt(const agx_ntt_group* group, const uint64_t* const*
 int agx_ntt_group_rescale(const agx_ntt_group* group, const uint64_t* const* d_x, uint64_t* const* d_out, uint64_t* const* d_scratch,
                           const uint64_t* batch, int mode) {
     return group_device(group, OP_RESCALE, d_x, nullptr, d_out, d_scratch, batch, nullptr, mode);
+}
+
+int agx_ntt_group_automorphism(const agx_ntt_group* group, const uint64_t* const* d_in, uint64_t* const* d_out, const uint64_t* batch,
+                               uint32_t galois_elt, int form) {
+    return group_device(group, OP_AUTOMORPHISM, d_in, nullptr, d_out, nullptr, batch, nullptr, form, galois_elt);
 }
 
 int agx_ntt_group_synchronize(const agx_ntt_group* group) {

@@ -377,6 +377,23 @@ int agx_ntt_min_root(uint64_t q, uint32_t n, uint64_t* psi_out) {
     return AGX_OK;
 }
 
+int agx_ntt_galois_element(uint32_t n, int64_t step, uint32_t* galois_elt) {
+    if (!galois_elt) return AGX_ERR_NULL_POINTER;
+    int rc = check_size(n);
+    if (rc) return rc;
+    const uint32_t mask = 2u * n - 1u;
+    uint32_t base = 5u;
+    if (step < 0) {      // 5^-1 mod 2n: Newton's iteration on the odd 5 doubles the correct low bits (3 -> 6 -> 12 -> 24 >= 16)
+        for (int it = 0; it < 3; ++it) base *= 2u - 5u * base;
+    }
+    base &= mask;
+    uint32_t g = 1u;
+    for (uint64_t e = step < 0 ? 0 - (uint64_t)step : (uint64_t)step; e; e >>= 1, base = (base * base) & mask)      // factors below 2^16
+        if (e & 1u) g = (g * base) & mask;
+    *galois_elt = g;
+    return AGX_OK;
+}
+
 static int make_tables_common(uint64_t q, uint64_t psi, uint32_t n, uint64_t* tw, uint64_t* pre, bool inverse) {
     if (!tw || !pre) return AGX_ERR_NULL_POINTER;
     int rc = check_size(n);

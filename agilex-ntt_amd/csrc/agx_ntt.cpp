@@ -688,6 +688,28 @@ int agx_ntt_rescale(const agx_ntt_plan* plan, const uint64_t* d_x, uint64_t* d_o
     return AGX_OK;
 }
 
+int agx_ntt_automorphism(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t galois_elt, int form, void* stream) {
+    if (!plan || !d_in || !d_out) return AGX_ERR_NULL_POINTER;
+    const int64_t n = (int64_t)plan->n;
+    // in as a frame set against itself (device, grid limit, alignment); out is judged below: it may not even BE in
+    int rc = check_call(plan, d_in, d_in, batch, (int64_t)batch * n, n);
+    if (rc) return rc;
+    if ((reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return AGX_ERR_BAD_ARGUMENT;
+    if (!(galois_elt & 1u) || galois_elt >= 2u * plan->n || (form != AGX_FORM_COEFF && form != AGX_FORM_NTT)) return AGX_ERR_BAD_ARGUMENT;
+    {
+        // both sets are dense, so each is one range of words; a frame is permuted across its whole length and workgroups run in any
+        // order, so the ranges may not touch anywhere
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), o0 = reinterpret_cast<uintptr_t>(d_out);
+        const uintptr_t bytes = (uintptr_t)plan->num_primes * batch * plan->n * sizeof(uint64_t);
+        if (d_in == d_out || (o0 < i0 + bytes && i0 < o0 + bytes)) return AGX_ERR_BAD_ARGUMENT;
+    }
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const route& r = plan->routes.forward;      // the per-prime constants only: no table, no plan state
+    AGX_HIP(form == AGX_FORM_NTT ? launch_automorphism_ntt(r, d_in, d_out, batch, galois_elt, s) : launch_automorphism_coeff(r, d_in, d_out, batch, galois_elt, s));
+    return AGX_OK;
+}
+
 int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly, uint64_t seed, void* stream) {
     if (!plan || !d_out) return AGX_ERR_NULL_POINTER;
     int rc = check_call(plan, d_out, d_out, batch, (int64_t)(batch * plan->n), (int64_t)plan->n);

@@ -76,6 +76,11 @@ hipError_t launch_pointwise_bhat(const plan_view& pv, uint64_t* c, const uint64_
 // the coefficient-domain step of agx_ntt_rescale's generic route: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i on the dense [prime][batch][n]
 // layout of pv's primes (a view of primes 0 .. P-2), u_i the lift of t[k] ([batch][n], coefficients of the last slab in [0, q_L)) to q_i
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s);
+// agx_ntt_automorphism on the dense [prime][batch][n] layout of pv's primes, out of place (the ranges must not touch), g odd in [1, 2n).
+// NTT form: a permutation of words, the modulus is not read; 16-byte accesses when both bases allow them.  Coefficient form: inputs in
+// [0,4q), outputs in [0,q); gathered from global memory (the stride-g^-1 repeats hit L2).  One launch each.
+hipError_t launch_automorphism_ntt(const plan_view& pv, const uint64_t* in, uint64_t* out, uint64_t batch, uint32_t g, hipStream_t s);
+hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, uint64_t* out, uint64_t batch, uint32_t g, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

@@ -6,7 +6,8 @@
 //   NTT(delta_0) = (1,...,1);  NTT(X)[bitrev(k)] = psi^(2k+1);  INTT(NTT(x)) = x on random x;
 // the reference's operand pairing with inData2 != inData (src/kernel/ntt.cpp:584-590); and the convolution theorem against the
 // schoolbook product mod X^n + 1 (n = 64 and 1024); and agx_ntt_rescale (n = 4096, two 60-bit primes, both modes) against the division of the
-// 120-bit integers themselves.
+// 120-bit integers themselves; and agx_ntt_automorphism (both forms, g = 5 and g = 2n - 1, n = 64 / 4096 / 32768)
+// against the definition X^j -> X^(g j) applied on the host.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -181,6 +182,55 @@ static int run_rescale_case(uint32_t n, uint32_t bits) {
     return bad != 0;
 }
 
+// agx_ntt_automorphism from the definition: coefficient j of every frame goes to g j mod 2n (negated past n) on the host; the device's
+// coefficient form must give that, and its NTT form, applied to the transform of the input, the transform of that
+static int run_automorphism_case(uint32_t n, uint32_t bits) {
+    const uint64_t batch = 3;
+    uint64_t q = 0;
+    if (agx_ntt_find_primes(bits, n, 1, &q)) return 1;
+    agx_ntt_plan* plan = nullptr;
+    int rc = agx_ntt_plan_create_auto(&plan, n, 1, &q, nullptr);
+    const size_t words = (size_t)batch * n, bytes = words * sizeof(uint64_t);
+    std::vector<uint64_t> a(words), want(words), got(words), want_hat(words), got_hat(words);
+    uint64_t s = 0xa070u + n;
+    auto next = [&] { s = s * 6364136223846793005ull + 1442695040888963407ull; return s >> 3; };
+    for (auto& v : a) v = next() % q;
+    uint64_t *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;
+    hipError_t he = hipMalloc(reinterpret_cast<void**>(&d_a), bytes);
+    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&d_b), bytes);
+    if (he == hipSuccess) he = hipMalloc(reinterpret_cast<void**>(&d_c), bytes);
+    size_t bad = 0;
+    const uint32_t gs[2] = {5u % (2 * n), 2 * n - 1};
+    for (int k = 0; k < 2 && !rc && he == hipSuccess; ++k) {
+        const uint32_t g = gs[k];
+        for (size_t f = 0; f < batch; ++f)
+            for (uint32_t j = 0; j < n; ++j) {
+                const uint32_t e = (uint32_t)(((uint64_t)g * j) % (2 * n));
+                const uint64_t v = a[f * n + j];
+                want[f * n + (e < n ? e : e - n)] = e < n ? v : (v ? q - v : 0);
+            }
+        he = hipMemcpy(d_a, a.data(), bytes, hipMemcpyHostToDevice);
+        if (he != hipSuccess) break;
+        rc = agx_ntt_automorphism(plan, d_a, d_b, batch, g, AGX_FORM_COEFF, nullptr);
+        if (!rc) he = hipMemcpy(got.data(), d_b, bytes, hipMemcpyDeviceToHost);
+        if (!rc) rc = agx_ntt_forward(plan, d_b, d_b, batch, nullptr);      // d_b <- NTT(sigma_g(a))
+        if (!rc) rc = agx_ntt_forward(plan, d_a, d_a, batch, nullptr);
+        if (!rc) rc = agx_ntt_automorphism(plan, d_a, d_c, batch, g, AGX_FORM_NTT, nullptr);
+        if (rc || he != hipSuccess) break;
+        he = hipMemcpy(want_hat.data(), d_b, bytes, hipMemcpyDeviceToHost);
+        if (he == hipSuccess) he = hipMemcpy(got_hat.data(), d_c, bytes, hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < words; ++i) bad += (got[i] != want[i]) + (got_hat[i] != want_hat[i]);
+    }
+    if (d_a) (void)hipFree(d_a);
+    if (d_b) (void)hipFree(d_b);
+    if (d_c) (void)hipFree(d_c);
+    agx_ntt_plan_destroy(plan);
+    if (rc || he != hipSuccess) { std::printf("n=%u automorphism: failed: %s / %s\n", n, agx_ntt_strerror(rc), hipGetErrorString(he)); return 1; }
+    std::printf("n=%5u q=%llu automorphism (both forms, g = 5 and 2n-1) vs X^j -> X^(g j) on the host  mismatches=%zu  %s\n", n, (unsigned long long)q, bad,
+                bad ? "FAIL" : "PASS");
+    return bad != 0;
+}
+
 // ---- scaling mode (--gpus N / --devices a,b,...): the library-level multi-GPU driver (agx_ntt_group_*, include/agx_ntt.h section 5) ----
 // Host frames dealt to the listed devices (agx::ntt with a device list) against the single-device result, then the device-pointer
 // form timed: every shard transforms its own resident batch from its own host thread on its own stream, HIP events per shard.
@@ -307,6 +357,7 @@ int main(int argc, char** argv) {
     fail |= run_pairing_case(1024, 30) | run_pairing_case(16384, 60);
     fail |= run_schoolbook_case(64, 30) | run_schoolbook_case(64, 60) | run_schoolbook_case(1024, 30);
     fail |= run_rescale_case(4096, 60);
+    fail |= run_automorphism_case(64, 60) | run_automorphism_case(4096, 60) | run_automorphism_case(32768, 60);
     std::printf(fail ? "HARNESS FAILED\n" : "HARNESS PASSED\n");
     return fail;
 }

@@ -41,7 +41,7 @@ typedef enum agx_status {
     AGX_ERR_BAD_SIZE = 2,       /* n is not a power of two in [AGX_NTT_MIN_N, AGX_NTT_MAX_N] */
     AGX_ERR_BAD_MODULUS = 3,    /* q >= 2^62, q even, q != 1 (mod 2n) or (plan_create_auto) q composite; rescale: q_i == q_last */
     AGX_ERR_BAD_ROOT = 4,       /* psi is not a primitive 2n-th root of unity mod q           */
-    AGX_ERR_BAD_ARGUMENT = 5,   /* zero primes, negative stride, overlapping in/out, ...      */
+    AGX_ERR_BAD_ARGUMENT = 5,   /* zero primes, negative stride, overlapping in/out, an even or too large Galois element, an unknown form or mode, ... */
     AGX_ERR_NO_DEVICE = 6,      /* no usable HIP device                                       */
     AGX_ERR_HIP = 7,            /* a HIP runtime call failed (agx_ntt_last_hip_error)         */
     AGX_ERR_ALLOC = 8,          /* host or device allocation failed                           */
@@ -211,6 +211,26 @@ AGX_API int agx_ntt_polymul_ntt(const agx_ntt_plan* plan, const uint64_t* d_a, c
 AGX_API int agx_ntt_rescale(const agx_ntt_plan* plan, const uint64_t* d_x, uint64_t* d_out, uint64_t* d_scratch,
                             uint64_t batch, int mode, void* stream);
 
+/* The Galois automorphism sigma_g: a(X) -> a(X^g) mod (X^n + 1), g = galois_elt odd, 1 <= g < 2n, on every frame of the dense [prime][batch][n]
+ * layout: the ring operation of every CKKS / BGV slot rotation (g = 5^step mod 2n, agx_ntt_galois_element) and of conjugation (g = 2n - 1).
+ *   AGX_FORM_COEFF (natural order): coefficient j goes to position e = g j mod 2n if e < n, and negated to position e - n otherwise; inputs may lie
+ *     in [0,4q) as agx_ntt_forward accepts them, outputs are fully reduced (so -0 = 0).  g = 1 is a reduce-to-[0,q) copy.
+ *   AGX_FORM_NTT (bit-reversed order, as agx_ntt_forward / agx_ntt_forward_lazy of this plan write it): out[p] = in[brev((g brev(p) + (g-1)/2) mod n)],
+ *     brev the log2(n)-bit reversal: a pure permutation of 64-bit words.  No arithmetic and no modulus: lazy values stay exactly as they were.
+ *     g = 1 is a copy.  agx_ntt_inverse of the result is the AGX_FORM_COEFF result of the coefficients.
+ * Every plan serves both forms, whatever its variant or moduli; no inverse tables are needed.  No tables of its own either: plan creation is unchanged.
+ * OUT OF PLACE ONLY: d_out's [prime][batch][n] range may not touch d_in's anywhere, equal pointers included (AGX_ERR_BAD_ARGUMENT, nothing written):
+ * workgroups run in any order and a frame is permuted across its whole length, so no workgroup could read all it needs before another has
+ * written there.  galois_elt even or >= 2n, or a form other than the two below: AGX_ERR_BAD_ARGUMENT.  Pointers need 8-byte alignment only.
+ * Asynchronous on `stream`, allocates and synchronises nothing, touches no plan state (capturable into a hipGraph).  ONE launch in either form:
+ * NTT form one thread per word (per pair of words with 16-byte accesses when both bases are 16-byte aligned), no LDS, no barrier -- a wave
+ * that writes 64 consecutive words reads one 512-byte segment; coefficient form one thread per word, gathered from global memory (the repeats hit L2).
+ * Either form runs at the rate of a device copy of the same words or above it (profiles/r07_automorphism.md). */
+#define AGX_FORM_COEFF 0
+#define AGX_FORM_NTT 1
+AGX_API int agx_ntt_automorphism(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t galois_elt, int form,
+                                 void* stream);
+
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */
 AGX_API int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly,
@@ -225,6 +245,9 @@ AGX_API int agx_ntt_find_primes(uint32_t bits, uint32_t n, uint32_t count, uint6
 AGX_API int agx_ntt_min_root(uint64_t q, uint32_t n, uint64_t* psi_out);
 AGX_API int agx_ntt_make_tables(uint64_t q, uint64_t psi, uint32_t n, uint64_t* twiddles, uint64_t* precons);
 AGX_API int agx_ntt_make_inverse_tables(uint64_t q, uint64_t psi, uint32_t n, uint64_t* inv_twiddles, uint64_t* inv_precons);
+/* the Galois element of a slot rotation by `step`: g = 5^step mod 2n, a negative step taking powers of 5^-1 mod 2n; always odd and below 2n.
+ * (Conjugation is not a power of 5: its element is g = 2n - 1.)  Pure arithmetic, no device needed */
+AGX_API int agx_ntt_galois_element(uint32_t n, int64_t step, uint32_t* galois_elt);
 
 /* ------------------------------------------------------------------------- */
 /* (5) Groups: the same calls over several GPUs of one node.                    */
@@ -276,6 +299,9 @@ AGX_API int agx_ntt_group_polymul_ntt(const agx_ntt_group* group, const uint64_t
 /* agx_ntt_rescale per shard; every shard needs its own scratch (which may be its d_x's last slab) */
 AGX_API int agx_ntt_group_rescale(const agx_ntt_group* group, const uint64_t* const* d_x, uint64_t* const* d_out,
                                   uint64_t* const* d_scratch, const uint64_t* batch, int mode);
+/* agx_ntt_automorphism per shard, the same Galois element and form on every shard */
+AGX_API int agx_ntt_group_automorphism(const agx_ntt_group* group, const uint64_t* const* d_in, uint64_t* const* d_out, const uint64_t* batch,
+                                       uint32_t galois_elt, int form);
 AGX_API int agx_ntt_group_synchronize(const agx_ntt_group* group);
 
 #ifdef __cplusplus

@@ -1,6 +1,7 @@
 """tools/run_op.py -- launch ONE operation of the engine a fixed number of times (for rocprofv3 --pmc / --kernel-trace
 runs on paths bench.py's headline does not cover).
 Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes P --batch B --bits 60 --oop --launches K --variant ID]
+       python3 tools/run_op.py --op auto --form {coeff,ntt} --galois G [--odd --reps 5 ...]   (agx_ntt_automorphism beside a device copy of the same words)
 Under the profiler: rocprofv3 ... -- python3 tools/run_op.py ...   (the interpreter itself after `--`, never this file: an
 `env` shebang hop after the profiler's preload has initialised the GPU is a forbidden exec on this pool)."""
 import argparse
@@ -15,7 +16,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -29,6 +30,10 @@ ap.add_argument("--mulsets", type=int, default=0, help="mul: K rotating (a, b) o
 ap.add_argument("--bcast", action="store_true", help="mulntt: one bhat frame per prime shared by the whole batch (bhat_batch = 1)")
 ap.add_argument("--mode", choices=["floor", "round"], default="round", help="rescale: AGX_RESCALE_FLOOR / AGX_RESCALE_ROUND")
 ap.add_argument("--inplace", action="store_true", help="rescale: out == x with x's last slab as the scratch (default: out and scratch of their own)")
+ap.add_argument("--form", choices=["coeff", "ntt"], default="ntt", help="auto: AGX_FORM_COEFF / AGX_FORM_NTT")
+ap.add_argument("--galois", type=int, default=5, help="auto: the Galois element g (odd, below 2n; -1 = 2n - 1, conjugation)")
+ap.add_argument("--odd", action="store_true", help="auto: both bases one word past a 16-byte boundary (the NTT form then takes its 8-byte accesses)")
+ap.add_argument("--reps", type=int, default=5, help="auto: timed repetitions of --launches calls each, alternating with the copy; medians are reported")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
@@ -36,6 +41,63 @@ if args.variant is not None:
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + args.variant)
 stream = torch.cuda.current_stream().cuda_stream
 per = args.primes * args.batch * args.n
+
+
+def run_auto():
+    """agx_ntt_automorphism and a device-to-device copy of the same [prime][batch][n] words, alternating in one process: both read and
+    write 16n bytes per frame, so the copy is the yardstick.  Prints us per call, GB/s and the ratio, each the median of --reps
+    repetitions, with the copy's own spread beside it."""
+    import statistics
+    import time
+
+    g = 2 * args.n - 1 if args.galois < 0 else args.galois
+    form = agx.FORM_COEFF if args.form == "coeff" else agx.FORM_NTT
+    pad = 2      # words: keeps the shifted views inside their allocations
+    src, dst = (torch.empty(per + pad, dtype=torch.int64, device="cuda") for _ in range(2))
+    off = 1 if args.odd else 0
+    plan.fill_synthetic(src.data_ptr() + 8 * off, args.batch, 0, 42, stream)
+    s_view, d_view = src[off:off + per], dst[off:off + per]
+
+    def auto():
+        plan.automorphism(s_view.data_ptr(), d_view.data_ptr(), args.batch, g, form, stream)
+
+    def copy():
+        d_view.copy_(s_view)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / args.launches      # us per call
+
+    t_end = time.perf_counter() + args.ramp_seconds
+    while time.perf_counter() < t_end:      # clock ramp, as below
+        for _ in range(8):
+            auto()
+            copy()
+        torch.cuda.synchronize()
+    t_auto, t_copy = [], []
+    for _ in range(args.reps):
+        t_auto.append(timed(auto))
+        t_copy.append(timed(copy))
+    gbs = lambda us: 16.0 * per / us / 1e3      # noqa: E731  (8 bytes read + 8 written per word)
+    ma, mc = statistics.median(t_auto), statistics.median(t_copy)
+    print(f"auto form={args.form} g={g} n={args.n} primes={args.primes} batch={args.batch} bits={args.bits}{' odd bases' if args.odd else ''}: "
+          f"{ma:.1f} us per call, {gbs(ma):.0f} GB/s (min {min(t_auto):.1f} max {max(t_auto):.1f} us); "
+          f"copy {mc:.1f} us, {gbs(mc):.0f} GB/s (min {min(t_copy):.1f} max {max(t_copy):.1f} us); ratio auto/copy {ma / mc:.3f}")
+    if args.report:
+        import json
+
+        json.dump({"us_auto": t_auto, "us_copy": t_copy, "launches": args.launches, "bytes": 16 * per}, open(args.report, "w"))
+    plan.close()
+
+
+if args.op == "auto":
+    run_auto()
+    sys.exit(0)
 slabs = [torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(args.slabs)]
 for i, s in enumerate(slabs):
     plan.fill_synthetic(s.data_ptr(), args.batch, i * args.batch, 42, stream)
