@@ -287,3 +287,223 @@ def arena_for(dev, n, *placed):
         if frames is not None:
             arena.place(layout, frames)
     return arena.commit() if dev is not None else arena
+
+
+# ---------------------------------------------------------------------------------------
+# launches at scale: the oracle per plan, sampled frames, whole-buffer checkers on the device
+# ---------------------------------------------------------------------------------------
+class OracleRef:
+    """the CPU oracle for one plan's moduli and roots"""
+
+    def __init__(self, orc, plan):
+        self.orc, self.n = orc, plan.n
+        self.q = plan.moduli
+        self.psi = [plan.psi(p) for p in range(plan.num_primes)]
+        self.tab = [orc.make_tables(q, r, self.n) for q, r in zip(self.q, self.psi)]
+        self.itw = [orc.make_inv_tables(q, r, self.n)[0] for q, r in zip(self.q, self.psi)]
+
+    def forward(self, p, x):
+        return self.orc.forward(x % np.uint64(self.q[p]), self.q[p], self.tab[p][0], self.tab[p][1], self.n)
+
+    def inverse(self, p, y):
+        return self.orc.inverse(y % np.uint64(self.q[p]), self.q[p], self.itw[p], self.n)
+
+    def polymul(self, p, a, b):
+        return oracle_polymul(self.orc, a, b, self.q[p], self.psi[p], self.n)
+
+
+def sample_frames(primes, batch, n, elements=()):
+    """global frame indices ([prime][batch] order) to check with the oracle: every prime's boundary frames, and the frames on both
+    sides of each of the given element offsets"""
+    g = {p * batch + f for p in range(primes) for f in boundary_frames(batch)}
+    for e in elements:
+        g |= {(e - 1) // n, e // n}
+    return sorted(f for f in g if f < primes * batch)
+
+
+def frames_to_host(t, frames, n):
+    """only the listed frames of a device tensor, copied to the host"""
+    return {g: t[g * n:(g + 1) * n].cpu().numpy().view(np.uint64) for g in frames}
+
+
+def thin_frames(frames, keep, limit=16):
+    """at most `limit` of the frame numbers `frames`: every one that is in `keep`, the room left filled evenly from the rest"""
+    frames = sorted(set(frames))
+    kept = [f for f in frames if f in set(keep)]
+    rest = [f for f in frames if f not in set(keep)]
+    room = min(max(0, limit - len(kept)), len(rest))
+    return sorted(kept + [rest[(k * len(rest)) // room] for k in range(room)])
+
+
+def spread_lazy_(torch, x, moduli, seed):
+    """x ([primes][...] on any device, residues in [0, q_p)) += q_p * k in place, k uniform in 0..3 per element: the same residues spread
+    over the lazy input range [0, 4q); in chunks, so the temporaries stay small"""
+    g = torch.Generator(device=x.device)
+    g.manual_seed(seed)
+    v = x.view(len(moduli), -1)
+    step = 1 << 26
+    for p, q in enumerate(moduli):
+        for lo in range(0, v.shape[1], step):
+            part = v[p, lo:lo + step]
+            part += int(q) * torch.randint(0, 4, part.shape, generator=g, device=x.device, dtype=torch.int64)
+    return x
+
+
+def _first_bad(got, want, prime, f0, limit=4):
+    """(prime, frame, element) of the first differing words of two [frames][n] chunks, frame numbers from f0"""
+    return [(prime, f0 + int(r), int(c)) for r, c in (got != want).nonzero()[:limit].tolist()]
+
+
+# ---- agx_ntt_automorphism ---------------------------------------------------------------------------------------------------------
+def sigma(a, g, n, q):
+    """sigma_g of the frames a ([frames][n] or flat, any values: reduced mod q first) under one modulus, from the definition"""
+    a = np.asarray(a, dtype=np.uint64).reshape(-1, n) % np.uint64(q)
+    e = (np.arange(n, dtype=np.int64) * g) % (2 * n)
+    out = np.empty_like(a)
+    low = e < n
+    out[:, e[low]] = a[:, low]
+    out[:, e[~low] - n] = (np.uint64(q) - a[:, ~low]) % np.uint64(q)
+    return out.reshape(-1)
+
+
+def brev(n):
+    bits = n.bit_length() - 1
+    r = np.zeros(n, dtype=np.int64)
+    for b in range(bits):
+        r |= ((np.arange(n) >> b) & 1) << (bits - 1 - b)
+    return r
+
+
+def ntt_pi(n, g):
+    """out[p] = in[pi(p)] in NTT form: pi(p) = brev((g brev(p) + (g-1)/2) mod n)"""
+    r = brev(n)
+    return r[(g * r + (g - 1) // 2) % n]
+
+
+def check_automorphism_ntt(torch, got, src, batch, n, g, device=None):
+    """NTT form on the whole buffer: got.view(-1, n) must equal src.view(-1, n)[:, pi], pi built on the host, compared in chunks of
+    frames on `device` (default: where got lives); returns up to 4 (prime, frame, element) of differing words (empty = pass)"""
+    device = got.device if device is None else device
+    pi = torch.from_numpy(ntt_pi(n, g)).to(device)
+    gv, sv = got.view(-1, n), src.view(-1, n)
+    step = max(1, (1 << 26) // n)
+    bad = []
+    for f0 in range(0, gv.shape[0], step):
+        want = sv[f0:f0 + step][:, pi]
+        if not torch.equal(gv[f0:f0 + step], want):
+            bad += [(f // batch, f % batch, e) for _, f, e in _first_bad(gv[f0:f0 + step], want, 0, f0)]
+            if len(bad) >= 4:
+                break
+    return bad[:4]
+
+
+def check_automorphism_coeff(torch, got, src, moduli, batch, n, g, device=None):
+    """coefficient form on the whole buffer, as the gather out[i] = +-src[j mod n], j = g^-1 i mod 2n, minus iff j >= n, with (q - v) % q
+    in int64 (q < 2^62; src in [0, 4q) below 2^63 is reduced first); returns up to 4 (prime, frame, element) (empty = pass)"""
+    device = got.device if device is None else device
+    j = (pow(int(g), -1, 2 * n) * np.arange(n, dtype=np.int64)) % (2 * n)
+    idx, neg = torch.from_numpy(j % n).to(device), torch.from_numpy(j >= n).to(device)[None, :]
+    gv, sv = got.view(len(moduli), batch, n), src.view(len(moduli), batch, n)
+    step = max(1, (1 << 26) // n)
+    bad = []
+    for p, q in enumerate(moduli):
+        for f0 in range(0, batch, step):
+            v = sv[p, f0:f0 + step][:, idx] % int(q)
+            want = torch.where(neg, (int(q) - v) % int(q), v)
+            if not torch.equal(gv[p, f0:f0 + step], want):
+                bad += _first_bad(gv[p, f0:f0 + step], want, p, f0)
+                if len(bad) >= 4:
+                    return bad[:4]
+    return bad
+
+
+# ---- agx_ntt_rescale: the constructed-quotient identity ---------------------------------------------------------------------------
+# Slabs 0 .. P-2 of one random [P][batch][n] buffer y are the residues y_i of an integer Y in [0, Q / q_L) (any residues are: CRT), the
+# last slab is r in [0, q_L).  X = Y q_L + r < Q has the residues x_i = (y_i (q_L mod q_i) + r mod q_i) mod q_i and x_L = r, so
+# floor(X / q_L) = Y, and floor((X + h) / q_L) = Y + [r + h >= q_L] = Y + [r > h], h = (q_L - 1) / 2 (q_L = 2h + 1).
+def rescale_identity_constants(moduli):
+    """C_i = q_L mod q_i for i < P-1, C_L = 0: the second operand of the product y o C"""
+    return [int(moduli[-1]) % int(q) for q in moduli[:-1]] + [0]
+
+
+def fill_rescale_constants(torch, c, moduli):
+    """c ([P][...]): slab i <- C_i"""
+    v = c.view(len(moduli), -1)
+    for p, k in enumerate(rescale_identity_constants(moduli)):
+        v[p].fill_(k)
+    return c
+
+
+def rescale_identity_sum_(torch, x, y, moduli):
+    """x ([P][...], holding y o C mod q_i) <- the residues of X in place: x_i = (x_i + r mod q_i) mod q_i (both terms below 2^62: int64
+    holds the sum), x_L = r, r the last slab of y"""
+    P = len(moduli)
+    xv, yv = x.view(P, -1), y.view(P, -1)
+    step = 1 << 26
+    for lo in range(0, xv.shape[1], step):
+        r = yv[P - 1, lo:lo + step]
+        for p in range(P - 1):
+            part = xv[p, lo:lo + step]
+            part += r % int(moduli[p])
+            part %= int(moduli[p])
+        xv[P - 1, lo:lo + step] = r
+    return x
+
+
+def check_rescale_identity(torch, got, y, moduli, batch, n, mode, device=None):
+    """got ([P-1 or more][batch][n], COEFFICIENT form: the call's output taken back by the inverse) on every word: slab i must be y_i
+    (mode 0, floor) or (y_i + [r > h]) mod q_i (mode 1, round); returns up to 4 (prime, frame, element) (empty = pass).  `device` is
+    accepted like the other checkers'; everything here is computed where the tensors live"""
+    P = len(moduli)
+    h = (int(moduli[-1]) - 1) // 2
+    gv, yv = got.view(-1, batch, n), y.view(P, batch, n)
+    step = max(1, (1 << 26) // n)
+    bad = []
+    for p in range(P - 1):
+        for f0 in range(0, batch, step):
+            want = yv[p, f0:f0 + step]
+            if mode:
+                want = (want + (yv[P - 1, f0:f0 + step] > h).to(want.dtype)) % int(moduli[p])
+            if not torch.equal(gv[p, f0:f0 + step], want):
+                bad += _first_bad(gv[p, f0:f0 + step], want, p, f0)
+                if len(bad) >= 4:
+                    return bad[:4]
+    return bad
+
+
+def rescale_reference(residues, moduli, mode):
+    """Python integers: residues ([P][count] uint64) -> X per coefficient by CRT -> Y = floor((X + {0, h}) / q_L) -> Y mod q_i, [P-1][count]"""
+    moduli = [int(q) for q in moduli]
+    Q = 1
+    for q in moduli:
+        Q *= q
+    qL = moduli[-1]
+    h = (qL - 1) // 2 if mode else 0
+    res = np.asarray(residues, dtype=np.uint64).reshape(len(moduli), -1)
+    X = np.zeros(res.shape[1], dtype=object)
+    for p, q in enumerate(moduli):
+        X = X + res[p].astype(object) * ((Q // q) * pow(Q // q, -1, q))
+    Y = (X % Q + h) // qL
+    return np.stack([(Y % q).astype(np.uint64) for q in moduli[:-1]])
+
+
+# ---- products by one fixed monomial per prime -------------------------------------------------------------------------------------
+def check_fixed_shifts(torch, c, a, moduli, batch, n, shifts, device=None):
+    """every frame of prime p of c ([primes][batch][n]) must be X^shifts[p] * a_f mod (X^n + 1, q_p), a in [0, 4q): built with gather /
+    where in chunks of frames; returns up to 4 (prime, frame, element) (empty = pass)"""
+    device = c.device if device is None else device
+    cv, av = c.view(len(moduli), batch, n), a.view(len(moduli), batch, n)
+    i = torch.arange(n, dtype=torch.int64, device=device)
+    step = max(1, (1 << 26) // n)
+    bad = []
+    for p, q in enumerate(moduli):
+        j = int(shifts[p])
+        idx, neg = (i - j) % n, (i < j)[None, :]
+        for f0 in range(0, batch, step):
+            v = av[p, f0:f0 + step][:, idx] % int(q)
+            want = torch.where(neg, (int(q) - v) % int(q), v)
+            if not torch.equal(cv[p, f0:f0 + step], want):
+                bad += _first_bad(cv[p, f0:f0 + step], want, p, f0)
+                if len(bad) >= 4:
+                    return bad[:4]
+    return bad

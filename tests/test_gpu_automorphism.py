@@ -8,7 +8,7 @@ import functools
 import numpy as np
 import pytest
 
-from gpu_util import Layout, arena_for, canary
+from gpu_util import Layout, arena_for, canary, ntt_pi as _pi, sigma as _sigma
 
 pytestmark = pytest.mark.gpu
 
@@ -43,35 +43,10 @@ def _plan(agx, orc, n, moduli, inverse=True):
 
 
 # ---- the reference: the definition as a scatter ---------------------------------------------------------------------------------
-def _sigma(a, g, n, q):
-    """sigma_g of the frames a ([frames][n] or flat, any values: reduced mod q first) under one modulus, from the definition"""
-    a = np.asarray(a, dtype=np.uint64).reshape(-1, n) % np.uint64(q)
-    e = (np.arange(n, dtype=np.int64) * g) % (2 * n)
-    out = np.empty_like(a)
-    low = e < n
-    out[:, e[low]] = a[:, low]
-    out[:, e[~low] - n] = (np.uint64(q) - a[:, ~low]) % np.uint64(q)
-    return out.reshape(-1)
-
-
 def _sigma_all(a, g, n, moduli, batch):
     """the same on a dense [prime][batch][n] set"""
     a = np.asarray(a).reshape(len(moduli), batch * n)
     return np.concatenate([_sigma(a[p], g, n, q) for p, q in enumerate(moduli)])
-
-
-def _brev(n):
-    bits = n.bit_length() - 1
-    r = np.zeros(n, dtype=np.int64)
-    for b in range(bits):
-        r |= ((np.arange(n) >> b) & 1) << (bits - 1 - b)
-    return r
-
-
-def _pi(n, g):
-    """out[p] = in[pi(p)] in NTT form: pi(p) = brev((g brev(p) + (g-1)/2) mod n)"""
-    r = _brev(n)
-    return r[(g * r + (g - 1) // 2) % n]
 
 
 def _forward_all(orc, a, n, moduli):

@@ -8,29 +8,9 @@ np.array_equal on the host."""
 import numpy as np
 import pytest
 
-from gpu_util import boundary_frames, check_negacyclic_shifts, fill_monomials, oracle_polymul, radix2_twin, shift_exponents
+from gpu_util import OracleRef as _Ref, check_negacyclic_shifts, fill_monomials, frames_to_host as _frames, radix2_twin, sample_frames as _sample, shift_exponents
 
 pytestmark = pytest.mark.gpu
-
-
-class _Ref:
-    """the CPU oracle for one plan's moduli and roots"""
-
-    def __init__(self, orc, plan):
-        self.orc, self.n = orc, plan.n
-        self.q = plan.moduli
-        self.psi = [plan.psi(p) for p in range(plan.num_primes)]
-        self.tab = [orc.make_tables(q, r, self.n) for q, r in zip(self.q, self.psi)]
-        self.itw = [orc.make_inv_tables(q, r, self.n)[0] for q, r in zip(self.q, self.psi)]
-
-    def forward(self, p, x):
-        return self.orc.forward(x % np.uint64(self.q[p]), self.q[p], self.tab[p][0], self.tab[p][1], self.n)
-
-    def inverse(self, p, y):
-        return self.orc.inverse(y % np.uint64(self.q[p]), self.q[p], self.itw[p], self.n)
-
-    def polymul(self, p, a, b):
-        return oracle_polymul(self.orc, a, b, self.q[p], self.psi[p], self.n)
 
 
 def _lazy(torch, x, moduli, seed):
@@ -40,20 +20,6 @@ def _lazy(torch, x, moduli, seed):
     k = torch.randint(0, 4, x.shape, generator=g, device=x.device, dtype=torch.int64)
     q = torch.tensor([int(v) for v in moduli], dtype=torch.int64, device=x.device)[:, None]
     return (x.view(len(moduli), -1) + q * k.view(len(moduli), -1)).view(-1)
-
-
-def _sample(primes, batch, n, elements=()):
-    """global frame indices ([prime][batch] order) to check with the oracle: every prime's boundary frames, and the frames on both
-    sides of each of the given element offsets"""
-    g = {p * batch + f for p in range(primes) for f in boundary_frames(batch)}
-    for e in elements:
-        g |= {(e - 1) // n, e // n}
-    return sorted(f for f in g if f < primes * batch)
-
-
-def _frames(t, frames, n):
-    """only the listed frames of a device tensor, copied to the host"""
-    return {g: t[g * n:(g + 1) * n].cpu().numpy().view(np.uint64) for g in frames}
 
 
 def _check_oracle(kind, ref, frames, batch, got, *ins):
