@@ -144,6 +144,25 @@ def _np_ptr(a):
     return a.ctypes.data_as(_p64)
 
 
+def _table_args(moduli, psi, tables):
+    """what follows (n, num_primes) in agx_ntt_{plan,group}_create_auto (tables is None: moduli, psi or NULL) and in
+    agx_ntt_{plan,group}_create (moduli, tw, pre, itw or NULL, ipre or NULL; the inverse pair only where four tables are given)"""
+    import numpy as np
+
+    if tables is None:
+        arrays = [moduli, None if psi is None else [int(p) for p in psi]]
+    else:
+        arrays = [moduli] + list(tables[:2]) + (list(tables[2:]) if len(tables) == 4 else [None, None])
+    return [None if a is None else _np_ptr(np.ascontiguousarray(a, dtype=np.uint64)) for a in arrays]      # a pointer keeps its array alive
+
+
+def _out_array(out, count):
+    """the caller's `out`, or a fresh array of `count` words"""
+    import numpy as np
+
+    return np.zeros(count, dtype=np.uint64) if out is None else out
+
+
 def kernel_source_sha16():
     """sha256[:16] over the DEVICE sources the kernels are built from (csrc/*.hip and the headers they include, sorted by
     name; not the host-side agx_ntt.cpp / host_math.*): ties a committed PMC figure (profiles/hbm_traffic.json) to the
@@ -241,24 +260,11 @@ class Plan:
     unless `tables=(tw, pre[, itw, ipre])` (each [num_primes, n] uint64) is given."""
 
     def __init__(self, n, moduli, psi=None, tables=None):
-        import numpy as np
-
         self.n = int(n)
         self.moduli = [int(q) for q in moduli]
-        mods = np.array(self.moduli, dtype=np.uint64)
         self._h = _vp(None)
-        if tables is None:
-            psi_arr = None if psi is None else np.array([int(p) for p in psi], dtype=np.uint64)
-            _check(lib().agx_ntt_plan_create_auto(ctypes.byref(self._h), self.n, len(self.moduli), _np_ptr(mods),
-                                                  None if psi_arr is None else _np_ptr(psi_arr)), "plan_create_auto")
-        else:
-            tw, pre = (np.ascontiguousarray(t, dtype=np.uint64) for t in tables[:2])
-            itw = ipre = None
-            if len(tables) == 4:
-                itw, ipre = (np.ascontiguousarray(t, dtype=np.uint64) for t in tables[2:])
-            _check(lib().agx_ntt_plan_create(ctypes.byref(self._h), self.n, len(self.moduli), _np_ptr(mods), _np_ptr(tw),
-                                             _np_ptr(pre), None if itw is None else _np_ptr(itw),
-                                             None if ipre is None else _np_ptr(ipre)), "plan_create")
+        create, where = (lib().agx_ntt_plan_create_auto, "plan_create_auto") if tables is None else (lib().agx_ntt_plan_create, "plan_create")
+        _check(create(ctypes.byref(self._h), self.n, len(self.moduli), *_table_args(self.moduli, psi, tables)), where)
 
     @property
     def num_primes(self):
@@ -320,18 +326,12 @@ class Plan:
     def forward_host_stream(self, in1, in2, num_frames, out=None):
         """host frames through this (single-modulus) plan with overlapped transfers; `out` (optional) is a caller-owned
         uint64 array of num_frames*n elements (a fresh np.zeros array costs a page fault per 4 KiB when it is first written)"""
-        import numpy as np
-
-        if out is None:
-            out = np.zeros(num_frames * self.n, dtype=np.uint64)
+        out = _out_array(out, num_frames * self.n)
         _check(lib().agx_ntt_forward_host_stream(self._h, _np_ptr(in1), _np_ptr(in2), _np_ptr(out), num_frames), "forward_host_stream")
         return out
 
     def inverse_host_stream(self, in1, num_frames, out=None):
-        import numpy as np
-
-        if out is None:
-            out = np.zeros(num_frames * self.n, dtype=np.uint64)
+        out = _out_array(out, num_frames * self.n)
         _check(lib().agx_ntt_inverse_host_stream(self._h, _np_ptr(in1), _np_ptr(out), num_frames), "inverse_host_stream")
         return out
 
@@ -360,25 +360,13 @@ class DeviceGroup:
     blocks, device-pointer calls take one pointer per shard.  No collective anywhere."""
 
     def __init__(self, devices, n, moduli, psi=None, tables=None):
-        import numpy as np
-
         self.n = int(n)
         self.devices = [int(d) for d in devices]
         self.moduli = [int(q) for q in moduli]
-        mods = np.array(self.moduli, dtype=np.uint64)
         devs = (_int * len(self.devices))(*self.devices)
         self._h = _vp(None)
-        if tables is None:
-            psi_arr = None if psi is None else np.array([int(p) for p in psi], dtype=np.uint64)
-            _check(lib().agx_ntt_group_create_auto(ctypes.byref(self._h), devs, len(self.devices), self.n, len(self.moduli), _np_ptr(mods),
-                                                   None if psi_arr is None else _np_ptr(psi_arr)), "group_create_auto")
-        else:
-            tw, pre = (np.ascontiguousarray(t, dtype=np.uint64) for t in tables[:2])
-            itw = ipre = None
-            if len(tables) == 4:
-                itw, ipre = (np.ascontiguousarray(t, dtype=np.uint64) for t in tables[2:])
-            _check(lib().agx_ntt_group_create(ctypes.byref(self._h), devs, len(self.devices), self.n, len(self.moduli), _np_ptr(mods), _np_ptr(tw),
-                                              _np_ptr(pre), None if itw is None else _np_ptr(itw), None if ipre is None else _np_ptr(ipre)), "group_create")
+        create, where = (lib().agx_ntt_group_create_auto, "group_create_auto") if tables is None else (lib().agx_ntt_group_create, "group_create")
+        _check(create(ctypes.byref(self._h), devs, len(self.devices), self.n, len(self.moduli), *_table_args(self.moduli, psi, tables)), where)
 
     @property
     def num_shards(self):
@@ -391,18 +379,12 @@ class DeviceGroup:
         return dev.value, plan.value, stream.value
 
     def forward_host(self, in1, in2, num_frames, out=None):
-        import numpy as np
-
-        if out is None:
-            out = np.zeros(num_frames * self.n, dtype=np.uint64)
+        out = _out_array(out, num_frames * self.n)
         _check(lib().agx_ntt_group_forward_host(self._h, _np_ptr(in1), _np_ptr(in2), _np_ptr(out), num_frames), "group_forward_host")
         return out
 
     def inverse_host(self, in1, num_frames, out=None):
-        import numpy as np
-
-        if out is None:
-            out = np.zeros(num_frames * self.n, dtype=np.uint64)
+        out = _out_array(out, num_frames * self.n)
         _check(lib().agx_ntt_group_inverse_host(self._h, _np_ptr(in1), _np_ptr(out), num_frames), "group_inverse_host")
         return out
 

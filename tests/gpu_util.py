@@ -1,5 +1,10 @@
-"""Helpers for the GPU parity tests: torch is only the device-memory allocator here."""
+"""Shared support of the tests, written once: device memory (torch is only the allocator here), moduli / oracle tables / plans, the
+oracle over dense frame sets, status_of, the one stream-capture helper, the group-of-two scaffolding, guarded arenas, whole-buffer
+checkers, and the kernel registry as the tests know it.  No test module imports another test module; they import from here."""
+import functools
+
 import numpy as np
+import pytest
 
 
 class DeviceHelper:
@@ -33,27 +38,99 @@ def rand_coeffs(rng, count, q, hi_mult=1):
     return rng.integers(0, hi, size=count, dtype=np.uint64)
 
 
+# ---------------------------------------------------------------------------------------
+# moduli, the oracle's tables, plans made from them
+# ---------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def oracle_tables(orc, n, q):
+    """(q, psi, tw, pre) for the least root of q, computed once per (n, q) and shared by every test: the arrays are read-only"""
+    psi = orc.min_root(q, n)
+    tw, pre = orc.make_tables(q, psi, n)
+    tw.setflags(write=False)
+    pre.setflags(write=False)
+    return q, psi, tw, pre
+
+
+def moduli_for(find_prime, n, spec):
+    """spec: modulus widths in bits; the k-th use of a width takes find_prime(bits, n, k), the k-th largest prime below 2^bits.
+    find_prime is the oracle's (orc.find_prime) or the library's (library_find_prime(agx))"""
+    seen, out = {}, []
+    for bits in spec:
+        out.append(find_prime(bits, n, seen.get(bits, 0)))
+        seen[bits] = seen.get(bits, 0) + 1
+    return tuple(out)
+
+
+def library_find_prime(agx):
+    """the library's prime finder with the oracle's signature"""
+    return lambda bits, n, k=0: agx.find_primes(bits, n, k + 1)[k]
+
+
+def plan_for_moduli(agx, orc, n, moduli, inverse=True):
+    """(plan, tabs): a plan created from the oracle's own tables for `moduli`, tabs = [(q, psi, tw, pre)]"""
+    tabs = [oracle_tables(orc, n, q) for q in moduli]
+    tables = [np.stack([t[2] for t in tabs]), np.stack([t[3] for t in tabs])]
+    if inverse:
+        inv = [orc.make_inv_tables(t[0], t[1], n) for t in tabs]
+        tables += [np.stack([i[0] for i in inv]), np.stack([i[1] for i in inv])]
+    return agx.Plan(n, list(moduli), tables=tuple(tables)), tabs
+
+
 def tables_for(orc, n, bits, count=1):
     """[(q, psi, tw, pre)] for the `count` largest primes below 2^bits"""
-    out = []
-    for k in range(count):
-        q = orc.find_prime(bits, n, k)
-        psi = orc.min_root(q, n)
-        tw, pre = orc.make_tables(q, psi, n)
-        out.append((q, psi, tw, pre))
-    return out
+    return [oracle_tables(orc, n, q) for q in moduli_for(orc.find_prime, n, [bits] * count)]
 
 
 def plan_from_oracle_tables(agx, orc, n, bits, count, inverse=True):
     """(plan, tabs) for the `count` largest primes below 2^bits, the plan created from the oracle's own tables"""
-    tabs = tables_for(orc, n, bits, count)
-    tw = np.stack([t[2] for t in tabs])
-    pre = np.stack([t[3] for t in tabs])
-    tables = [tw, pre]
-    if inverse:
-        inv = [orc.make_inv_tables(t[0], t[1], n) for t in tabs]
-        tables += [np.stack([i[0] for i in inv]), np.stack([i[1] for i in inv])]
-    return agx.Plan(n, [t[0] for t in tabs], tables=tuple(tables)), tabs
+    return plan_for_moduli(agx, orc, n, moduli_for(orc.find_prime, n, [bits] * count), inverse)
+
+
+def oracle_forward_rns(orc, x, tabs, n):
+    """the oracle's forward of a dense [prime][...][n] set x (any shape of that size) under tabs = [(q, psi, tw, pre)], flat"""
+    x = np.asarray(x).reshape(len(tabs), -1)
+    return np.concatenate([orc.forward(np.ascontiguousarray(x[p]), q, tw, pre, n) for p, (q, _, tw, pre) in enumerate(tabs)])
+
+
+def status_of(agx, fn, *args):
+    """0 when fn(*args) returns, the status of the AgxError it raises otherwise"""
+    try:
+        fn(*args)
+        return 0
+    except agx.AgxError as e:
+        return e.status
+
+
+def capture(dev, warm_up, body):
+    """A HIP graph of the launches body(stream) makes.  warm_up(stream) runs first, on the same side stream and OUTSIDE the capture
+    (first launches may load code objects or allocate, which a capture cannot record), and is synchronised; both take the raw stream
+    handle.  Everything is recorded on exactly one stream: captured graphs here must have no parallel branches, because the runtime
+    replays the branches of a graph on separate hardware queues and has crashed doing so where a process owns few of them.  The device
+    is synchronised in front, the side stream waits for the current one before and the current one for the side stream after, so the
+    caller's buffers are ready when the warm-up reads them and the graph is ready to replay when this returns."""
+    torch = dev.torch
+    side = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    dev.sync()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        warm_up(side.cuda_stream)
+        side.synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            body(torch.cuda.current_stream().cuda_stream)
+    torch.cuda.current_stream().wait_stream(side)
+    return graph
+
+
+def group_of_two(agx, orc, n, moduli, frames):
+    """(group, plan, batches): a DeviceGroup on devices [0, 0] and the single Plan with the same moduli and (least) roots, and the
+    frames each of the two shards gets when `frames` (odd) are dealt to them"""
+    psi = [oracle_tables(orc, n, q)[1] for q in moduli]
+    grp = agx.DeviceGroup([0, 0], n, list(moduli), psi=psi)
+    plan = agx.Plan(n, list(moduli), psi=psi)
+    batches = [agx.shard_block(frames, 2, i)[1] for i in range(2)]
+    assert sum(batches) == frames and batches[0] != batches[1]
+    return grp, plan, batches
 
 
 def oracle_polymul(orc, a, b, q, psi, n):
@@ -507,3 +584,79 @@ def check_fixed_shifts(torch, c, a, moduli, batch, n, shifts, device=None):
                 if len(bad) >= 4:
                     return bad[:4]
     return bad
+
+
+# ---------------------------------------------------------------------------------------
+# the kernel registry as the tests know it
+# ---------------------------------------------------------------------------------------
+# registry ids of the product library (what a default or a call-shape selector can reach); every other id is an A/B entry that
+# only lib/libagxntt_diag.so carries: tests/test_gpu_diag.py re-runs the id-parametrised tests of test_gpu_parity.py in a child
+# process bound to that library
+PRODUCT_IDS = ({93, 92, 91, 159, 164, 117, 119, 120, 121, 122, 123} | set(range(150, 159)) | set(range(130, 142))
+               | set(range(200, 215)) | set(range(230, 235)) | set(range(240, 245)) | set(range(250, 258)) | set(range(260, 268)))
+
+# every entry of the kernel registry, (id, n, max_bits): the size it serves and the largest modulus its arithmetic admits
+# (exact: 62 bits, fast: 61, 16q-lazy: 60)
+REGISTRY = [
+    (91, 4096, 62), (92, 4096, 61), (93, 4096, 60), (159, 4096, 60), (147, 4096, 60), (161, 4096, 60), (70, 4096, 60),
+    # streamed single-frame kernels (lazy, fast, exact): n = 1024 / 2048 / 8192, 16384 (117 + forward companion 164), 32768; A/B twins 115 / 160 / 114
+    (150, 1024, 60), (151, 1024, 61), (152, 1024, 62), (153, 2048, 60), (154, 2048, 61), (155, 2048, 62), (156, 8192, 60), (157, 8192, 61), (158, 8192, 62),
+    (117, 16384, 60), (164, 16384, 60), (120, 16384, 61), (122, 16384, 62), (115, 16384, 60), (160, 16384, 60),
+    (119, 32768, 60), (121, 32768, 61), (123, 32768, 62), (114, 32768, 60),
+    # 32-bit arithmetic: tier 2 (every q < 2^30), tier 1 (every q < 2^31)
+    (130, 1024, 30), (131, 2048, 30), (132, 4096, 30), (133, 8192, 30), (134, 16384, 30), (135, 32768, 30),
+    (136, 1024, 31), (137, 2048, 31), (138, 4096, 31), (139, 8192, 31), (140, 16384, 31), (141, 32768, 31),
+    # wave-packed kernels of n = 32 ... 512 (csrc/wp_kernels.hpp): 16q-lazy / fast / exact per size, then the 32-bit tiers
+    (200, 32, 60), (201, 32, 61), (202, 32, 62), (203, 64, 60), (204, 64, 61), (205, 64, 62), (206, 128, 60), (207, 128, 61), (208, 128, 62),
+    (209, 256, 60), (210, 256, 61), (211, 256, 62), (212, 512, 60), (213, 512, 61), (214, 512, 62),
+    (230, 32, 30), (231, 64, 30), (232, 128, 30), (233, 256, 30), (234, 512, 30), (240, 32, 31), (241, 64, 31), (242, 128, 31), (243, 256, 31), (244, 512, 31),
+    # n = 2 ... 16: one lane per frame (fast / exact; 32-bit tiers)
+    (250, 2, 61), (251, 2, 62), (252, 4, 61), (253, 4, 62), (254, 8, 61), (255, 8, 62), (256, 16, 61), (257, 16, 62),
+    (260, 2, 30), (261, 4, 30), (262, 8, 30), (263, 16, 30), (264, 2, 31), (265, 4, 31), (266, 8, 31), (267, 16, 31),
+    # A/B shapes of the wave-packed kernels (lib/libagxntt_diag.so)
+    (215, 32, 60), (220, 512, 60), (221, 512, 60), (222, 256, 60), (224, 32, 60), (235, 32, 30), (236, 512, 30),
+]
+
+# the product library's registry entries that carry launch_rescale (the A/B twins 70, 114, 115, 147, 160, 161, 221 carry it too; they
+# live in the diagnostics library only)
+RESCALE_IDS = [91, 92, 93, 150, 151, 152, 153, 154, 155, 156, 157, 158, 117, 120, 122, 119, 121, 123]
+
+
+def registry_entries(ids):
+    """the (id, n, max_bits) entries of REGISTRY for `ids`, in the order of `ids`"""
+    by_id = {e[0]: e for e in REGISTRY}
+    return [by_id[i] for i in ids]
+
+
+def select_entry(agx, plan, config):
+    """explicit registry entry (AGX_VARIANT_REGBLOCK_BASE + id); A/B ids are skipped unless the diag library is loaded"""
+    if config is None or config == "default":
+        return
+    if config not in PRODUCT_IDS and not agx.LIB_PATH.endswith("libagxntt_diag.so"):
+        plan.close()
+        pytest.skip(f"registry id {config} lives in lib/libagxntt_diag.so (covered by tests/test_gpu_diag.py)")
+    plan.set_variant(agx.VARIANT_REGBLOCK_BASE + config)
+
+
+# ---------------------------------------------------------------------------------------
+# launches of more than 2^32 elements (34 GB and more per buffer: an MI355X holds 288 GB)
+# ---------------------------------------------------------------------------------------
+EDGES = (1 << 28, 1 << 31, 1 << 32)      # 2^31 bytes, 2^31 and 2^32 elements
+
+
+@pytest.fixture
+def big_memory(dev):
+    """frees torch's cached blocks before and after, so that the test (and the plans of later tests) can have the memory;
+    need(buffers, elements) skips unless 1.1x that much device memory is free"""
+    torch = dev.torch
+    torch.cuda.empty_cache()
+
+    def need(buffers, elements):
+        want = buffers * elements * 8 + (4 << 30)      # + chunked temporaries of the device-side checks
+        free, _ = torch.cuda.mem_get_info()
+        if free < 1.1 * want:
+            pytest.skip(f"needs {1.1 * want / 2**30:.0f} GiB of free device memory, {free / 2**30:.0f} GiB free")
+
+    yield need
+    dev.sync()
+    torch.cuda.empty_cache()

@@ -11,7 +11,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import agilex_ntt_amd as agx  # noqa: E402
-from gpu_util import DeviceHelper, rand_coeffs, tables_for  # noqa: E402
+from gpu_util import DeviceHelper, oracle_forward_rns, plan_from_oracle_tables, rand_coeffs  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
 assert agx.LIB_PATH.endswith("libagxntt_diag.so"), agx.LIB_PATH
@@ -20,8 +20,7 @@ orc.build()
 dev = DeviceHelper(torch)
 n, batch = 4096, 3
 
-tabs = tables_for(orc, n, 60, 2)
-plan = agx.Plan(n, [t[0] for t in tabs], tables=(np.stack([t[2] for t in tabs]), np.stack([t[3] for t in tabs])))
+plan, tabs = plan_from_oracle_tables(agx, orc, n, 60, 2, inverse=False)
 plan.set_variant(agx.VARIANT_REGBLOCK_BASE + config)
 assert plan.forward_kernel(batch) == config
 rng = np.random.default_rng(config)
@@ -29,7 +28,7 @@ for hi_mult, lazy in ((1, False), (4, False), (4, True)):
     x = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=hi_mult) for t in tabs])
     if hi_mult == 4:
         x[:n] = np.uint64(4 * tabs[0][0] - 1)      # one frame at the very top of the input range
-    want = np.concatenate([orc.forward(x[p * batch * n:(p + 1) * batch * n], t[0], t[2], t[3], n) for p, t in enumerate(tabs)])
+    want = oracle_forward_rns(orc, x, tabs, n)
     d = dev.to_device(x)
     (plan.forward_lazy if lazy else plan.forward)(d.data_ptr(), d.data_ptr(), batch, dev.stream)
     got = dev.to_host(d)
@@ -42,8 +41,7 @@ for hi_mult, lazy in ((1, False), (4, False), (4, True)):
 plan.close()
 
 # a modulus outside the class must be refused
-tabs = tables_for(orc, n, 59, 1)
-plan = agx.Plan(n, [t[0] for t in tabs], tables=(np.stack([t[2] for t in tabs]), np.stack([t[3] for t in tabs])))
+plan, tabs = plan_from_oracle_tables(agx, orc, n, 59, 1, inverse=False)
 try:
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + config)
     raise SystemExit(f"config {config} accepted a 59-bit modulus")

@@ -11,16 +11,124 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared_symbols():
+def _header():
+    """include/agx_ntt.h without its comments"""
     text = open(os.path.join(ROOT, "include", "agx_ntt.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(agx_ntt_\w+)\s*\(", text)))
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _prototypes():
+    """{name: (return type, number of arguments)} of every function the header declares"""
+    out = {}
+    for ret, name, args in re.findall(r"AGX_API\s+([\w\s\*]+?)\s*\b(agx_ntt_\w+)\s*\(([^)]*)\)\s*;", _header()):
+        out[name] = (ret.replace(" ", ""), 0 if args.strip() == "void" else len(args.split(",")))
+    return out
+
+
+def _declared_symbols():
+    return sorted(set(re.findall(r"\b(agx_ntt_\w+)\s*\(", _header())))
 
 
 def test_header_and_binding_agree(agx):
     declared = _declared_symbols()
     assert len(declared) >= 20
     assert sorted(agx.ABI) == declared
+
+
+def test_binding_matches_the_header(agx):
+    """argument count and return type of every prototype, as the binding has them: int everywhere but agx_ntt_strerror's char*"""
+    protos = _prototypes()
+    assert sorted(protos) == _declared_symbols()
+    for name, (ret, nargs) in protos.items():
+        assert nargs == len(agx.ABI[name][1]), name
+        if name == "agx_ntt_strerror":
+            assert ret == "constchar*" and agx.ABI[name][0] is ctypes.c_char_p
+        else:
+            assert ret == "int" and agx.ABI[name][0] is ctypes.c_int, name
+
+
+# the operations added to the boundary one at a time: their symbols, the Plan / DeviceGroup wrapper, the header's constants with the
+# values the binding repeats, and calls with a NULL plan or group with the status each must return before it touches a device
+OPERATIONS = {
+    "polymul_ntt": {
+        "names": ("agx_ntt_polymul_ntt", "agx_ntt_group_polymul_ntt"),
+        "constants": {},
+        "null_calls": [("agx_ntt_polymul_ntt", (None, None, None, None, 1, 1, None), 1),
+                       ("agx_ntt_group_polymul_ntt", (None, None, None, None, None, None), 1)],
+    },
+    "rescale": {
+        "names": ("agx_ntt_rescale", "agx_ntt_group_rescale"),
+        "constants": {"RESCALE_FLOOR": 0, "RESCALE_ROUND": 1},
+        "null_calls": [("agx_ntt_rescale", (None, None, None, None, 1, 0, None), 1), ("agx_ntt_rescale", (None, None, None, None, 1, 7, None), 1),
+                       ("agx_ntt_group_rescale", (None, None, None, None, None, 0), 1), ("agx_ntt_group_rescale", (None, None, None, None, None, 1), 1)],
+    },
+    "automorphism": {
+        "names": ("agx_ntt_automorphism", "agx_ntt_group_automorphism", "agx_ntt_galois_element"),
+        "constants": {"FORM_COEFF": 0, "FORM_NTT": 1},
+        "null_calls": [(name, args, 1) for form in (0, 1, 7) for name, args in (("agx_ntt_automorphism", (None, None, None, 1, 5, form, None)),
+                                                                               ("agx_ntt_group_automorphism", (None, None, None, None, 5, form)))],
+    },
+}
+
+
+@pytest.mark.parametrize("op", OPERATIONS)
+def test_operation_is_bound_exported_and_declared(agx, op):
+    text = _header()
+    raw = ctypes.CDLL(agx.LIB_PATH)
+    for name in OPERATIONS[op]["names"]:
+        assert name in agx.ABI, name
+        assert hasattr(raw, name), name
+        assert re.search(r"\b" + name + r"\s*\(", text), name
+    assert hasattr(agx.Plan, op) and hasattr(agx.DeviceGroup, op)
+    if op == "automorphism":
+        assert callable(agx.galois_element)
+
+
+@pytest.mark.parametrize("op", [op for op in OPERATIONS if OPERATIONS[op]["constants"]])
+def test_operation_constants_match_the_header(agx, op):
+    """every AGX_<OP>_* constant of the header, and the same values under the binding's names"""
+    want = OPERATIONS[op]["constants"]
+    prefix = os.path.commonprefix(["AGX_" + k for k in want])      # AGX_RESCALE_, AGX_FORM_
+    assert prefix.endswith("_") and len(prefix) > len("AGX_")
+    consts = dict(re.findall(r"#define\s+(" + prefix + r"\w+)\s+(\d+)", _header()))
+    assert consts == {"AGX_" + k: str(v) for k, v in want.items()}
+    assert all(getattr(agx, k) == v for k, v in want.items())
+
+
+@pytest.mark.parametrize("op", OPERATIONS)
+def test_operation_fails_loudly_without_a_plan_or_a_group(agx, op):
+    L = agx.lib()
+    for name, args, status in OPERATIONS[op]["null_calls"]:
+        assert getattr(L, name)(*args) == status, (name, args)
+
+
+def test_a_plan_cannot_be_made_without_a_device(agx):
+    """where no GPU is visible there is no plan to call with: creation reports it instead of handing out something a rescale could run on"""
+    if agx.device_count() != 0:
+        return
+    h = ctypes.c_void_p(None)
+    q = (ctypes.c_uint64 * 2)(*agx.find_primes(60, 64, 2))
+    assert agx.lib().agx_ntt_plan_create_auto(ctypes.byref(h), 64, 2, q, None) == 6      # AGX_ERR_NO_DEVICE
+    assert not h.value
+
+
+@pytest.mark.parametrize("n", [2, 4, 8, 4096, 32768])
+def test_galois_elements_are_powers_of_five(agx, n):
+    for step in (0, 1, -1, 7, n // 2, -(n // 2) - 3):
+        g = agx.galois_element(n, step)
+        assert g == pow(5, step, 2 * n), (n, step)
+        assert agx.galois_element(n, -step) == pow(5, -step, 2 * n), (n, -step)
+        assert g % 2 == 1 and g < 2 * n
+        assert g * agx.galois_element(n, -step) % (2 * n) == 1
+
+
+def test_galois_element_validates_its_arguments(agx):
+    L = agx.lib()
+    g = ctypes.c_uint32(0)
+    for n in (0, 1, 3, 1000, 65536):
+        assert L.agx_ntt_galois_element(n, 1, ctypes.byref(g)) == 2, n
+    assert L.agx_ntt_galois_element(4096, 1, None) == 1
+    assert L.agx_ntt_galois_element(4096, -(1 << 63), ctypes.byref(g)) == 0 and g.value == pow(5, -(1 << 63), 8192)
 
 
 def test_library_exports_every_declared_symbol(agx):

@@ -8,38 +8,13 @@ import functools
 import numpy as np
 import pytest
 
-from gpu_util import Layout, arena_for, canary, ntt_pi as _pi, sigma as _sigma
+from gpu_util import (Layout, arena_for, canary, capture, group_of_two, moduli_for, ntt_pi as _pi, oracle_forward_rns, oracle_tables, plan_for_moduli,
+                      sigma as _sigma, status_of)
 
 pytestmark = pytest.mark.gpu
 
 COEFF, NTT = 0, 1
 FORMS = (COEFF, NTT)
-
-
-# ---- plans from the oracle's tables ----------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _tables(orc, n, q):
-    psi = orc.min_root(q, n)
-    tw, pre = orc.make_tables(q, psi, n)
-    return q, psi, tw, pre
-
-
-def _moduli(orc, n, spec):
-    """spec: modulus widths in bits; the k-th use of a width takes the k-th largest prime below 2^bits"""
-    seen, out = {}, []
-    for bits in spec:
-        out.append(orc.find_prime(bits, n, seen.get(bits, 0)))
-        seen[bits] = seen.get(bits, 0) + 1
-    return tuple(out)
-
-
-def _plan(agx, orc, n, moduli, inverse=True):
-    tabs = [_tables(orc, n, q) for q in moduli]
-    tables = [np.stack([t[2] for t in tabs]), np.stack([t[3] for t in tabs])]
-    if inverse:
-        inv = [orc.make_inv_tables(t[0], t[1], n) for t in tabs]
-        tables += [np.stack([i[0] for i in inv]), np.stack([i[1] for i in inv])]
-    return agx.Plan(n, list(moduli), tables=tuple(tables))
 
 
 # ---- the reference: the definition as a scatter ---------------------------------------------------------------------------------
@@ -49,21 +24,12 @@ def _sigma_all(a, g, n, moduli, batch):
     return np.concatenate([_sigma(a[p], g, n, q) for p, q in enumerate(moduli)])
 
 
-def _forward_all(orc, a, n, moduli):
-    a = np.asarray(a).reshape(len(moduli), -1)
-    out = []
-    for p, q in enumerate(moduli):
-        _, _, tw, pre = _tables(orc, n, q)
-        out.append(orc.forward(np.ascontiguousarray(a[p]), q, tw, pre, n))
-    return np.concatenate(out)
-
-
 @functools.lru_cache(maxsize=None)
 def _case(orc, n, moduli, batch, seed):
     """(coefficients a [P][batch][n] in [0,q), their transform); computed once per case and shared (read-only)"""
     rng = np.random.default_rng(seed)
     a = np.concatenate([rng.integers(0, q, size=batch * n, dtype=np.uint64) for q in moduli])
-    ahat = _forward_all(orc, a, n, moduli)
+    ahat = oracle_forward_rns(orc, a, [oracle_tables(orc, n, q) for q in moduli], n)
     a.setflags(write=False)
     ahat.setflags(write=False)
     return a, ahat
@@ -92,14 +58,14 @@ PARITY = [(n, spec, b) for n in SIZES for spec in SPECS for b in ((1, 5, 259) if
 def test_parity_both_forms(agx, orc, dev, n, spec, batch):
     """every size at which a kernel shape or its tiling changes, one 60-bit prime and three primes of mixed classes; batch 259 at n = 8
     and 64 puts several frames into one wave and leaves the last wave partly filled"""
-    moduli = _moduli(orc, n, spec)
-    plan = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, spec)
+    plan, tabs = plan_for_moduli(agx, orc, n, moduli)
     a, ahat = _case(orc, n, moduli, batch, 31 * n + len(spec) + batch)
     d_a, d_ahat = dev.to_device(a), dev.to_device(ahat)
     for g in _galois(n):
         want = _sigma_all(a, g, n, moduli, batch)
         assert np.array_equal(_run(dev, plan, None, batch, g, COEFF, d_in=d_a), want), ("coefficient form", n, spec, batch, g)
-        assert np.array_equal(_run(dev, plan, None, batch, g, NTT, d_in=d_ahat), _forward_all(orc, want, n, moduli)), ("NTT form", n, spec, batch, g)
+        assert np.array_equal(_run(dev, plan, None, batch, g, NTT, d_in=d_ahat), oracle_forward_rns(orc, want, tabs, n)), ("NTT form", n, spec, batch, g)
     plan.close()
 
 
@@ -107,8 +73,8 @@ def test_parity_both_forms(agx, orc, dev, n, spec, batch):
 def test_ntt_form_moves_words_unchanged(agx, orc, dev, n):
     """arbitrary 64-bit words (none of them a residue) come out as the numpy permutation of them: nothing is reduced, nothing is lost"""
     batch = 3
-    moduli = _moduli(orc, n, (60, 30, 61))
-    plan = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, (60, 30, 61))
+    plan, tabs = plan_for_moduli(agx, orc, n, moduli)
     words = canary(7, len(moduli) * batch * n)
     for g in (5, 2 * n - 1, n + 1):
         got = _run(dev, plan, words, batch, g, NTT).reshape(-1, n)
@@ -122,9 +88,9 @@ def test_ntt_form_moves_words_unchanged(agx, orc, dev, n):
 def test_coefficient_form_takes_the_lazy_range(agx, orc, dev, n, bits):
     """inputs in [0,4q) with 0, q, 2q, 3q, q-1 and 4q-1 planted where the image keeps its sign and where it is negated; outputs in [0,q)"""
     batch = 2
-    moduli = _moduli(orc, n, (bits,))
+    moduli = moduli_for(orc.find_prime, n, (bits,))
     q = moduli[0]
-    plan = _plan(agx, orc, n, moduli)
+    plan, tabs = plan_for_moduli(agx, orc, n, moduli)
     rng = np.random.default_rng(n + bits)
     planted = [0, q, 2 * q, 3 * q, q - 1, 4 * q - 1]
     for g in (5, 2 * n - 1):
@@ -146,8 +112,8 @@ def test_coefficient_form_takes_the_lazy_range(agx, orc, dev, n, bits):
 @pytest.mark.parametrize("n", [4096, 512])
 def test_algebra_on_the_device(agx, orc, dev, n):
     batch = 3
-    moduli = _moduli(orc, n, (60, 30, 61))
-    plan = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, (60, 30, 61))
+    plan, tabs = plan_for_moduli(agx, orc, n, moduli)
     a, ahat = _case(orc, n, moduli, batch, 5 * n + 1)
     total = a.size
     d = {COEFF: dev.to_device(a), NTT: dev.to_device(ahat)}
@@ -176,8 +142,8 @@ def test_guarded_arenas_at_odd_offsets(agx, orc, dev, n, form, out_odd):
     """d_in (and d_out, or d_in alone) 8-byte but not 16-byte aligned inside one arena: the canaries and the input frames are intact, the
     output frames are as expected"""
     batch = 3
-    moduli = _moduli(orc, n, (60, 30, 61))
-    plan = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, (60, 30, 61))
+    plan, tabs = plan_for_moduli(agx, orc, n, moduli)
     a, ahat = _case(orc, n, moduli, batch, 3 * n + 2)
     src = a if form == COEFF else ahat
     li = Layout(n, len(moduli), batch, offset=1)
@@ -189,23 +155,15 @@ def test_guarded_arenas_at_odd_offsets(agx, orc, dev, n, form, out_odd):
         img = arena.image()
         assert not arena.faults([(li, src), (lo, None)], img), "a word outside the output changed"
         want = _sigma_all(a, g, n, moduli, batch)
-        assert np.array_equal(arena.frames(lo, img), want if form == COEFF else _forward_all(orc, want, n, moduli)), (n, form, g)
+        assert np.array_equal(arena.frames(lo, img), want if form == COEFF else oracle_forward_rns(orc, want, tabs, n)), (n, form, g)
     plan.close()
-
-
-def _status(agx, fn, *args):
-    try:
-        fn(*args)
-        return 0
-    except agx.AgxError as e:
-        return e.status
 
 
 @pytest.mark.parametrize("n", [64, 4096])
 def test_rejections_write_nothing(agx, orc, dev, n):
     primes, batch = 3, 2
-    moduli = _moduli(orc, n, (60,) * primes)
-    plan = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, (60,) * primes)
+    plan, tabs = plan_for_moduli(agx, orc, n, moduli)
     a, _ = _case(orc, n, moduli, batch, 7 * n)
     total = primes * batch * n
     li = Layout(n, primes, batch, offset=0)
@@ -216,18 +174,18 @@ def test_rejections_write_nothing(agx, orc, dev, n):
     A, st, w = plan.automorphism, dev.stream, 8
     for form in FORMS:
         for g in (0, 2, 2 * n, 2 * n + 1):
-            assert _status(agx, A, x, out, batch, g, form, st) == 5, g
-        assert _status(agx, A, x, x, batch, 5, form, st) == 5                                   # in place
-        assert _status(agx, A, x, x + w * (n // 2), batch, 5, form, st) == 5
-        assert _status(agx, A, x, x + w * (total - n // 2), batch, 5, form, st) == 5            # out starts inside in's last frame
-        assert _status(agx, A, x, x + w * (total - 1), batch, 5, form, st) == 5
-        assert _status(agx, A, out + w * (total - n // 2), out, batch, 5, form, st) == 5        # in starts inside out's last frame
-        assert _status(agx, A, out + w * (total - 1), out, batch, 5, form, st) == 5
-        assert _status(agx, A, x + 4, out, batch, 5, form, st) == 5 and _status(agx, A, x, out + 4, batch, 5, form, st) == 5      # uint64_t data
-        assert _status(agx, A, 0, out, batch, 5, form, st) == 1 and _status(agx, A, x, 0, batch, 5, form, st) == 1
+            assert status_of(agx, A, x, out, batch, g, form, st) == 5, g
+        assert status_of(agx, A, x, x, batch, 5, form, st) == 5                                   # in place
+        assert status_of(agx, A, x, x + w * (n // 2), batch, 5, form, st) == 5
+        assert status_of(agx, A, x, x + w * (total - n // 2), batch, 5, form, st) == 5            # out starts inside in's last frame
+        assert status_of(agx, A, x, x + w * (total - 1), batch, 5, form, st) == 5
+        assert status_of(agx, A, out + w * (total - n // 2), out, batch, 5, form, st) == 5        # in starts inside out's last frame
+        assert status_of(agx, A, out + w * (total - 1), out, batch, 5, form, st) == 5
+        assert status_of(agx, A, x + 4, out, batch, 5, form, st) == 5 and status_of(agx, A, x, out + 4, batch, 5, form, st) == 5      # uint64_t data
+        assert status_of(agx, A, 0, out, batch, 5, form, st) == 1 and status_of(agx, A, x, 0, batch, 5, form, st) == 1
         A(x, out, 0, 5, form, st)      # empty batch: nothing happens
     for form in (2, -1):
-        assert _status(agx, A, x, out, batch, 5, form, st) == 5
+        assert status_of(agx, A, x, out, batch, 5, form, st) == 5
     dev.sync()
     assert np.array_equal(arena.image(), before), "a rejected call wrote memory"
     A(x, x + w * total, batch, 5, NTT, st)      # out right behind in: the ranges do not touch
@@ -241,23 +199,17 @@ def test_calls_are_graph_capturable(agx, orc, dev, n, form):
     """two calls captured one after the other on a side stream (no parallel branches), replayed twice on new data"""
     torch = dev.torch
     batch, gs = 5, (5, 2 * n - 1)
-    moduli = _moduli(orc, n, (60, 30, 61))
-    plan = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, (60, 30, 61))
+    plan, tabs = plan_for_moduli(agx, orc, n, moduli)
     cases = [_case(orc, n, moduli, batch, n + k) for k in (1, 2)]
     d_in = dev.to_device(cases[0][form])
     d_out = [dev.empty(d_in.numel()) for _ in gs]
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    dev.sync()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        plan.automorphism(d_in.data_ptr(), d_out[0].data_ptr(), batch, gs[0], form, side.cuda_stream)      # warm-up outside capture
-        side.synchronize()
-        with torch.cuda.graph(graph, stream=side):
-            s = torch.cuda.current_stream().cuda_stream
-            for g, d in zip(gs, d_out):
-                plan.automorphism(d_in.data_ptr(), d.data_ptr(), batch, g, form, s)
-    torch.cuda.current_stream().wait_stream(side)
+
+    def both_elements(s):
+        for g, d in zip(gs, d_out):
+            plan.automorphism(d_in.data_ptr(), d.data_ptr(), batch, g, form, s)
+
+    graph = capture(dev, lambda s: plan.automorphism(d_in.data_ptr(), d_out[0].data_ptr(), batch, gs[0], form, s), both_elements)
     for a, ahat in cases:
         d_in.copy_(torch.from_numpy((a, ahat)[form].view(np.int64).copy()))
         for d in d_out:
@@ -266,17 +218,17 @@ def test_calls_are_graph_capturable(agx, orc, dev, n, form):
         dev.sync()
         for g, d in zip(gs, d_out):
             want = _sigma_all(a, g, n, moduli, batch)
-            assert np.array_equal(dev.to_host(d), want if form == COEFF else _forward_all(orc, want, n, moduli)), ("replay", g)
+            assert np.array_equal(dev.to_host(d), want if form == COEFF else oracle_forward_rns(orc, want, tabs, n)), ("replay", g)
     plan.close()
 
 
 def test_group_equals_the_single_plan(agx, orc, dev):
     """DeviceGroup.automorphism on devices [0, 0] with unequal batches, against Plan.automorphism on the same words"""
-    n, batches = 4096, [3, 2]
-    moduli = _moduli(orc, n, (60, 30, 61))
-    psi = [_tables(orc, n, q)[1] for q in moduli]
-    grp = agx.DeviceGroup([0, 0], n, list(moduli), psi=psi)
-    plan = agx.Plan(n, list(moduli), psi=psi)
+    n = 4096
+    moduli = moduli_for(orc.find_prime, n, (60, 30, 61))
+    tabs = [oracle_tables(orc, n, q) for q in moduli]
+    grp, plan, batches = group_of_two(agx, orc, n, moduli, 5)
+    assert batches == [3, 2]
     cases = [_case(orc, n, moduli, bt, 900 + i) for i, bt in enumerate(batches)]
     for form in FORMS:
         d_in = [dev.to_device(c[form]) for c in cases]
@@ -289,7 +241,7 @@ def test_group_equals_the_single_plan(agx, orc, dev):
                 got = dev.to_host(d_out[i])
                 want = _sigma_all(cases[i][0], g, n, moduli, bt)
                 assert np.array_equal(got, single[i]), f"shard {i} differs from the single plan"
-                assert np.array_equal(got, want if form == COEFF else _forward_all(orc, want, n, moduli)), f"shard {i} differs from the reference"
+                assert np.array_equal(got, want if form == COEFF else oracle_forward_rns(orc, want, tabs, n)), f"shard {i} differs from the reference"
     grp.close()
     plan.close()
 
@@ -297,11 +249,11 @@ def test_group_equals_the_single_plan(agx, orc, dev):
 @pytest.mark.parametrize("n", [64, 4096])
 def test_forward_only_plans_run_both_forms(agx, orc, dev, n):
     batch = 2
-    moduli = _moduli(orc, n, (60, 30, 61))
-    plan = _plan(agx, orc, n, moduli, inverse=False)
+    moduli = moduli_for(orc.find_prime, n, (60, 30, 61))
+    plan, tabs = plan_for_moduli(agx, orc, n, moduli, inverse=False)
     a, ahat = _case(orc, n, moduli, batch, 11 * n)
     g = pow(5, 7, 2 * n)
     want = _sigma_all(a, g, n, moduli, batch)
     assert np.array_equal(_run(dev, plan, a, batch, g, COEFF), want)
-    assert np.array_equal(_run(dev, plan, ahat, batch, g, NTT), _forward_all(orc, want, n, moduli))
+    assert np.array_equal(_run(dev, plan, ahat, batch, g, NTT), oracle_forward_rns(orc, want, tabs, n))
     plan.close()

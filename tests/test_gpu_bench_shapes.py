@@ -8,7 +8,8 @@ np.array_equal on the host."""
 import numpy as np
 import pytest
 
-from gpu_util import OracleRef as _Ref, check_negacyclic_shifts, fill_monomials, frames_to_host as _frames, radix2_twin, sample_frames as _sample, shift_exponents
+from gpu_util import EDGES, OracleRef as _Ref, big_memory, check_negacyclic_shifts, fill_monomials, frames_to_host as _frames      # noqa: F401  (big_memory: the fixture is used by name)
+from gpu_util import radix2_twin, sample_frames as _sample, shift_exponents
 
 pytestmark = pytest.mark.gpu
 
@@ -138,27 +139,6 @@ def test_bench_config5_slice_shape(agx, orc, dev):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # launches of more than 2^32 elements (34 GB and more per buffer: an MI355X holds 288 GB)
 # ---------------------------------------------------------------------------------------------------------------------------------
-EDGES = (1 << 28, 1 << 31, 1 << 32)      # 2^31 bytes, 2^31 and 2^32 elements
-
-
-@pytest.fixture
-def big_memory(dev):
-    """frees torch's cached blocks before and after, so that the test (and the plans of later tests) can have the memory;
-    need(buffers, elements) skips unless 1.1x that much device memory is free"""
-    torch = dev.torch
-    torch.cuda.empty_cache()
-
-    def need(buffers, elements):
-        want = buffers * elements * 8 + (4 << 30)      # + chunked temporaries of the device-side checks
-        free, _ = torch.cuda.mem_get_info()
-        if free < 1.1 * want:
-            pytest.skip(f"needs {1.1 * want / 2**30:.0f} GiB of free device memory, {free / 2**30:.0f} GiB free")
-
-    yield need
-    dev.sync()
-    torch.cuda.empty_cache()
-
-
 @pytest.mark.parametrize("n,primes,batch", [(4096, 4, 262400), (16384, 8, 33000), (32, 4, (1 << 25) + (1 << 20))])
 def test_transforms_past_2_32_elements(agx, orc, dev, big_memory, n, primes, batch):
     """the default forward out of place against the radix-2 twin on the whole buffer and the oracle on both sides of element offsets

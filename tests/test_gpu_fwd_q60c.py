@@ -10,26 +10,13 @@ import sys
 import numpy as np
 import pytest
 
-from gpu_util import rand_coeffs
+from gpu_util import oracle_tables, plan_for_moduli, rand_coeffs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 4096
 Q60C_ID, GENERAL_COMPANION_ID, MAIN_ID, TWIN_ID = 165, 159, 93, 166
 BIG = 4096 + 1      # frames per prime: with any number of primes past the companion's 4,096-frame threshold, and an odd tail
 PERIOD = 7          # the big batch repeats PERIOD distinct frames (odd: every frame meets workgroups of every parity)
-
-
-def _tables(orc, moduli):
-    tabs = []
-    for q in moduli:
-        psi = orc.min_root(q, N)
-        tw, pre = orc.make_tables(q, psi, N)
-        tabs.append((q, psi, tw, pre))
-    return tabs
-
-
-def _plan(agx, tabs):
-    return agx.Plan(N, [t[0] for t in tabs], tables=(np.stack([t[2] for t in tabs]), np.stack([t[3] for t in tabs])))
 
 
 def _input_kinds(rng, q, frames):
@@ -46,7 +33,7 @@ def _input_kinds(rng, q, frames):
 def bench_case(agx, orc):
     """the four benchmark primes, the frames every test of this module transforms, and the oracle's transform of them, computed once:
     per prime 3 frames of each input kind (batches 1 and 3), and PERIOD base frames for the big batch (3 below q, q - 1, zero, 2 in [3q,4q))"""
-    tabs = _tables(orc, agx.find_primes(60, N, 4))
+    tabs = [oracle_tables(orc, N, q) for q in agx.find_primes(60, N, 4)]
     rng = np.random.default_rng(165)
     small = [_input_kinds(rng, t[0], 3) for t in tabs]
     base = []
@@ -83,11 +70,11 @@ def _check_lazy(got, want, tabs, batch, where):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("lazy", [False, True], ids=["reduced", "lazy"])
-def test_specialised_path_small_batches(agx, dev, bench_case, lazy):
+def test_specialised_path_small_batches(agx, orc, dev, bench_case, lazy):
     """cases A and B at 1 and 3 frames per prime: the plan's own choice for launches this small is the 512-thread kernel (id 93), so the specialised
     kernel is selected explicitly -- it must be legal for these moduli"""
     tabs = bench_case["tabs"]
-    plan = _plan(agx, tabs)
+    plan, _ = plan_for_moduli(agx, orc, N, [t[0] for t in tabs], inverse=False)
     assert plan.forward_kernel(1) == MAIN_ID and plan.forward_kernel(3) == MAIN_ID
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + Q60C_ID)
     for batch in (1, 3):
@@ -105,11 +92,11 @@ def test_specialised_path_small_batches(agx, dev, bench_case, lazy):
 
 
 @pytest.mark.gpu
-def test_specialised_path_is_the_default_past_the_companion_threshold(agx, dev, bench_case):
+def test_specialised_path_is_the_default_past_the_companion_threshold(agx, orc, dev, bench_case):
     """cases A and B at 4,096 + 1 frames per prime: the plan itself sends the launch to id 165; every frame, reduced and lazy, on the device"""
     torch = dev.torch
     tabs = bench_case["tabs"]
-    plan = _plan(agx, tabs)
+    plan, _ = plan_for_moduli(agx, orc, N, [t[0] for t in tabs], inverse=False)
     assert plan.forward_kernel(BIG) == Q60C_ID
     d_x, d_want = _tiled(dev, bench_case["base"]), _tiled(dev, bench_case["base_want"])
     d_y = dev.empty(d_x.numel())
@@ -142,8 +129,7 @@ def test_one_modulus_outside_the_class_falls_back(agx, orc, dev, outsider):
     general kernels -- id 159 past the threshold, id 93 below it -- and id 165 refuses the plan"""
     q_out = orc.find_prime(59, N, 0) if outsider == "59-bit" else _upward_60bit_prime(orc)
     assert q_out < (1 << 60) - (1 << 28)
-    tabs = _tables(orc, [agx.find_primes(60, N, 1)[0], q_out])
-    plan = _plan(agx, tabs)
+    plan, tabs = plan_for_moduli(agx, orc, N, [agx.find_primes(60, N, 1)[0], q_out], inverse=False)
     batch = 2048      # x 2 primes: exactly on the companion's threshold
     assert plan.forward_kernel(batch) == GENERAL_COMPANION_ID and plan.forward_kernel(3) == MAIN_ID
     rng = np.random.default_rng(59)
@@ -188,9 +174,8 @@ def test_golden_boundary_primes_are_the_boundary(orc):
 def test_boundary_values_of_c(agx, orc, dev):
     """case D: one plan over the smallest and the largest c; one frame each against the committed oracle outputs, then 3 frames of every input kind"""
     cases = _golden()
-    tabs = _tables(orc, [c["q"] for c in cases])
+    plan, tabs = plan_for_moduli(agx, orc, N, [c["q"] for c in cases], inverse=False)
     assert [t[1] for t in tabs] == [c["psi"] for c in cases]
-    plan = _plan(agx, tabs)
     assert plan.forward_kernel(BIG) == Q60C_ID
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + Q60C_ID)
     x = np.concatenate([orc.fill_splitmix(N, c["seed"], c["q"]) for c in cases])

@@ -8,13 +8,9 @@ import threading
 import numpy as np
 import pytest
 
-from gpu_util import rand_coeffs, tables_for
+from gpu_util import oracle_forward_rns, rand_coeffs, tables_for
 
 pytestmark = pytest.mark.gpu
-
-
-def _oracle_forward(orc, x, t, n):
-    return orc.forward(x, t[0], t[2], t[3], n)
 
 
 @pytest.mark.parametrize("n,frames", [(4096, 1101), (16384, 301)])
@@ -34,7 +30,7 @@ def test_group_host_frames_on_two_shards_of_one_gpu(agx, orc, n, frames):
     b[:, :n // 2] = np.uint64(0xFFFFFFFFFFFFFFFF)
     out = np.full(frames * n, 7, dtype=np.uint64)
     got = grp.forward_host(a.reshape(-1), b.reshape(-1), frames, out=out)
-    want = _oracle_forward(orc, x, t, n)
+    want = oracle_forward_rns(orc, x, [t], n)
     assert np.array_equal(got, want)
     back = grp.inverse_host(got, frames)
     assert np.array_equal(back, x % np.uint64(q))
@@ -52,7 +48,7 @@ def test_group_more_shards_than_frames_and_zero_frames(agx, orc):
         x = rand_coeffs(rng, max(frames, 1) * n, t[0])[: frames * n]
         got = grp.forward_host(x, x, frames) if frames else grp.forward_host(np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64), 0, out=np.zeros(1, dtype=np.uint64))
         if frames:
-            assert np.array_equal(got, _oracle_forward(orc, x, t, n)), frames
+            assert np.array_equal(got, oracle_forward_rns(orc, x, [t], n)), frames
     grp.close()
 
 
@@ -73,7 +69,7 @@ def test_group_device_pointer_calls(agx, orc, dev):
     grp.forward([d.data_ptr() for d in d_in], [d.data_ptr() for d in d_out], batches)
     grp.synchronize()
     for x, d, b in zip(xs, d_out, batches):
-        want = np.concatenate([_oracle_forward(orc, x[p * b * n:(p + 1) * b * n], t, n) for p, t in enumerate(tabs)])
+        want = oracle_forward_rns(orc, x, tabs, n)
         assert np.array_equal(dev.to_host(d), want)
     grp.inverse([d.data_ptr() for d in d_out], [d.data_ptr() for d in d_out], batches)      # in place
     grp.synchronize()
@@ -155,13 +151,13 @@ def test_partial_overlap_of_in_and_out_is_rejected(agx, orc, dev):
     assert np.array_equal(dev.to_host(d), x), "a rejected call must not touch memory"
     # legal: disjoint (out = in + batch n), in place, and interleaved frames (poly_stride = 2n, out = in + n: frames never touch)
     plan.forward(base, base + 8 * batch * n, batch, dev.stream)
-    want = _oracle_forward(orc, x[: batch * n], t, n)
+    want = oracle_forward_rns(orc, x[: batch * n], [t], n)
     assert np.array_equal(dev.to_host(d)[batch * n:2 * batch * n], want)
     d2 = dev.to_device(x)
     plan.forward_strided(d2.data_ptr(), d2.data_ptr() + 8 * n, batch, 0, 2 * n, dev.stream)
     got = dev.to_host(d2).reshape(-1, n)
     evens = x.reshape(-1, n)[0:2 * batch:2]
-    assert np.array_equal(got[1:2 * batch:2].reshape(-1), _oracle_forward(orc, evens.reshape(-1), t, n))
+    assert np.array_equal(got[1:2 * batch:2].reshape(-1), oracle_forward_rns(orc, evens.reshape(-1), [t], n))
     assert np.array_equal(got[0:2 * batch:2], evens)
     with pytest.raises(agx.AgxError) as ei:      # ... but shifted by half a frame they do touch
         plan.forward_strided(d2.data_ptr(), d2.data_ptr() + 8 * (n + n // 2), batch, 0, 2 * n, dev.stream)
@@ -232,7 +228,7 @@ def test_group_calls_from_two_host_threads(agx, orc):
     g2 = agx.DeviceGroup([0], n, [t[0]], psi=[t[1]])
     rng = np.random.default_rng(21)
     xs = [rand_coeffs(rng, frames * n, t[0]) for _ in range(3)]
-    wants = [_oracle_forward(orc, x, t, n) for x in xs]
+    wants = [oracle_forward_rns(orc, x, [t], n) for x in xs]
     outs = [None] * 3
     errs = []
 
@@ -268,7 +264,7 @@ def test_one_shot_call_over_a_device_list_from_the_environment(agx, orc):
     a, b = x.copy().reshape(frames, n), x.copy().reshape(frames, n)
     a[:, n // 2:] = np.uint64(1)
     b[:, :n // 2] = np.uint64(2)
-    want = _oracle_forward(orc, x, t, n)
+    want = oracle_forward_rns(orc, x, [t], n)
     old = os.environ.get("AGX_NTT_DEVICES")
     try:
         os.environ["AGX_NTT_DEVICES"] = "0,0"
@@ -276,7 +272,7 @@ def test_one_shot_call_over_a_device_list_from_the_environment(agx, orc):
         assert np.array_equal(agx.forward_host(x, x, t[0], t[2], t[3], n, frames), want)      # cached group
         t2 = tables_for(orc, n, 59)[0]                                                         # other tables: the group is rebuilt
         x2 = x % np.uint64(t2[0])
-        assert np.array_equal(agx.forward_host(x2, x2, t2[0], t2[2], t2[3], n, frames), _oracle_forward(orc, x2, t2, n))
+        assert np.array_equal(agx.forward_host(x2, x2, t2[0], t2[2], t2[3], n, frames), oracle_forward_rns(orc, x2, [t2], n))
         os.environ["AGX_NTT_DEVICES"] = "0,77"
         with pytest.raises(agx.AgxError) as ei:
             agx.forward_host(x, x, t[0], t[2], t[3], n, frames)

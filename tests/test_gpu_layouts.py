@@ -8,7 +8,7 @@ call -- must come back as it went in.  tests/test_layout_helpers.py shows on the
 import numpy as np
 import pytest
 
-from gpu_util import GuardedArena, Layout, arena_for, oracle_polymul, plan_from_oracle_tables, rand_coeffs
+from gpu_util import GuardedArena, Layout, arena_for, capture, oracle_polymul, plan_from_oracle_tables, rand_coeffs
 
 pytestmark = pytest.mark.gpu
 
@@ -312,15 +312,8 @@ def test_counter_driven_inverse_under_a_stride(agx, orc, dev):
     # captured: out of place, so that a replay is repeatable
     src, dst = arena_for(dev, n, (lay, x)), arena_for(dev, n, (lay, None))
     warm = arena_for(dev, n, (lay, x))
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        case.plan.inverse_strided(warm.address(0), warm.address(0), batch, lay.prime_stride, lay.poly_stride, side.cuda_stream)   # warm-up outside capture
-        side.synchronize()
-        with torch.cuda.graph(graph, stream=side):
-            case.plan.inverse_strided(src.address(0), dst.address(0), batch, lay.prime_stride, lay.poly_stride, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.current_stream().wait_stream(side)
+    graph = capture(dev, lambda s: case.plan.inverse_strided(warm.address(0), warm.address(0), batch, lay.prime_stride, lay.poly_stride, s),   # warm-up on an arena of its own
+                    lambda s: case.plan.inverse_strided(src.address(0), dst.address(0), batch, lay.prime_stride, lay.poly_stride, s))
     rep.check("capture must not run the launch", dst, [(lay, None)])
     rep.require("capture must not run the launch: an output frame holds results", not np.array_equal(dst.frames(lay), want_i))
     graph.replay()

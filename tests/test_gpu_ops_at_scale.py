@@ -8,26 +8,15 @@ oracle and by Python integers.  All comparisons are exact: torch.equal on the de
 import numpy as np
 import pytest
 
-from gpu_util import (OracleRef, boundary_frames, check_automorphism_coeff, check_automorphism_ntt, check_fixed_shifts,
-                      check_rescale_identity, fill_rescale_constants, frames_to_host, radix2_twin, rescale_identity_sum_, rescale_reference,
-                      sample_frames, sigma, spread_lazy_, thin_frames)
-from test_gpu_bench_shapes import EDGES, big_memory      # noqa: F401  (the fixture is used by name)
+from gpu_util import (EDGES, OracleRef, big_memory, boundary_frames, capture, check_automorphism_coeff, check_automorphism_ntt,      # noqa: F401  (big_memory: the fixture is used by name)
+                      check_fixed_shifts, check_rescale_identity, fill_rescale_constants, frames_to_host, library_find_prime, moduli_for,
+                      radix2_twin, rescale_identity_sum_, rescale_reference, sample_frames, sigma, spread_lazy_, thin_frames)
 
 pytestmark = pytest.mark.gpu
 
 COEFF, NTT = 0, 1
 FLOOR, ROUND = 0, 1
 TRIP = 2048 * 8 * 256      # work items of one trip round a grid-stride loop (grid_1d, csrc/ntt_kernels.hip)
-
-
-def _moduli(agx, n, spec):
-    """spec: modulus widths in bits; the k-th use of a width takes the k-th largest prime below 2^bits"""
-    pool = {bits: agx.find_primes(bits, n, spec.count(bits)) for bits in set(spec)}
-    seen, out = {}, []
-    for bits in spec:
-        out.append(pool[bits][seen.get(bits, 0)])
-        seen[bits] = seen.get(bits, 0) + 1
-    return out
 
 
 def _where(bad):
@@ -95,7 +84,7 @@ AUTOMORPHISM = [
 def test_automorphism_past_one_grid_stride_trip(agx, orc, dev, n, spec, batch, odd, second_trip):
     """g in {5, 2n-1, n+1}, inputs in [0, 4q) for the coefficient form; both buffers at an even or at an odd word of a larger allocation"""
     torch = dev.torch
-    moduli = _moduli(agx, n, spec)
+    moduli = list(moduli_for(library_find_prime(agx), n, spec))
     primes, total = len(moduli), len(moduli) * batch * n
     items = {"per_prime": batch * n, "words": total, "pairs": total // 2}
     for k in second_trip:
@@ -144,7 +133,7 @@ def test_polymul_ntt_generic_path_past_one_grid_stride_trip(agx, orc, dev, n, sp
     against agx_ntt_polymul of a default plan (one fused kernel, no pointwise pass) with c distinct: dense, then broadcast against the
     product with the one b frame tiled; the oracle on the boundary frames"""
     torch = dev.torch
-    moduli = _moduli(agx, n, spec)
+    moduli = list(moduli_for(library_find_prime(agx), n, spec))
     primes, total = len(moduli), len(moduli) * batch * n
     assert batch * n > TRIP
     fused = agx.Plan(n, moduli)
@@ -294,7 +283,7 @@ def test_rescale_past_one_grid_stride_trip_and_one_resident_grid(agx, orc, dev, 
     Where the two-launch route serves the plan (n >= 1024 and some modulus of 2^31 or more) the radix-2 twin's four launches must give
     the same words."""
     torch = dev.torch
-    moduli = _moduli(agx, n, spec)
+    moduli = list(moduli_for(library_find_prime(agx), n, spec))
     P = len(moduli)
     resident = _resident_grid(torch, n)
     if kind == "loop":
@@ -343,7 +332,7 @@ def test_rescale_stateless_loop_inverse_in_a_graph(agx, orc, dev):
     on every word and equal the eager call's"""
     torch = dev.torch
     n, spec = 16384, (60, 60)
-    moduli = _moduli(agx, n, spec)
+    moduli = list(moduli_for(library_find_prime(agx), n, spec))
     P = len(moduli)
     batch, resident = _loop_batch(torch, n), _resident_grid(torch, n)
     assert batch > resident and batch % resident != 0, (batch, resident)
@@ -354,18 +343,12 @@ def test_rescale_stateless_loop_inverse_in_a_graph(agx, orc, dev):
     plan.forward(x.data_ptr(), xhat.data_ptr(), batch, dev.stream)
     outs = [dev.empty(P * slab) for _ in (FLOOR, ROUND)]
     eager, scratch = dev.empty(P * slab), dev.empty(slab)
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    dev.sync()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        plan.rescale(xhat.data_ptr(), eager.data_ptr(), scratch.data_ptr(), batch, FLOOR, side.cuda_stream)      # warm-up outside capture
-        side.synchronize()
-        with torch.cuda.graph(graph, stream=side):
-            s = torch.cuda.current_stream().cuda_stream
-            for mode in (FLOOR, ROUND):
-                plan.rescale(xhat.data_ptr(), outs[mode].data_ptr(), scratch.data_ptr(), batch, mode, s)
-    torch.cuda.current_stream().wait_stream(side)
+
+    def both_modes(s):
+        for mode in (FLOOR, ROUND):
+            plan.rescale(xhat.data_ptr(), outs[mode].data_ptr(), scratch.data_ptr(), batch, mode, s)
+
+    graph = capture(dev, lambda s: plan.rescale(xhat.data_ptr(), eager.data_ptr(), scratch.data_ptr(), batch, FLOOR, s), both_modes)      # warm-up into a buffer of its own
     for o in outs:
         o.fill_(-1)
     graph.replay()

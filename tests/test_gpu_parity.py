@@ -6,40 +6,14 @@ import os
 import numpy as np
 import pytest
 
+from gpu_util import PRODUCT_IDS, REGISTRY, capture, oracle_forward_rns, rand_coeffs, select_entry, tables_for
 from gpu_util import oracle_polymul as _oracle_polymul
 from gpu_util import plan_from_oracle_tables as _plan_from_oracle_tables
-from gpu_util import rand_coeffs, tables_for
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ALL_SIZES = [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384, 32768]
-
-
-# registry ids of the product library (what a default or a call-shape selector can reach); every other id is an A/B entry that
-# only lib/libagxntt_diag.so carries: tests/test_gpu_diag.py re-runs the id-parametrised tests of this file in a child process
-# bound to that library
-PRODUCT_IDS = ({93, 92, 91, 159, 164, 117, 119, 120, 121, 122, 123} | set(range(150, 159)) | set(range(130, 142))
-               | set(range(200, 215)) | set(range(230, 235)) | set(range(240, 245)) | set(range(250, 258)) | set(range(260, 268)))
-
-
-def _select(agx, plan, config):
-    """explicit registry entry (AGX_VARIANT_REGBLOCK_BASE + id); A/B ids are skipped unless the diag library is loaded"""
-    if config is None or config == "default":
-        return
-    if config not in PRODUCT_IDS and not agx.LIB_PATH.endswith("libagxntt_diag.so"):
-        plan.close()
-        pytest.skip(f"registry id {config} lives in lib/libagxntt_diag.so (covered by tests/test_gpu_diag.py)")
-    plan.set_variant(agx.VARIANT_REGBLOCK_BASE + config)
-
-
-def _oracle_forward_rns(orc, x, tabs, n, batch):
-    """x: [P][batch][n] flat"""
-    out = np.empty_like(x)
-    for p, (q, _, tw, pre) in enumerate(tabs):
-        sl = slice(p * batch * n, (p + 1) * batch * n)
-        out[sl] = orc.forward(x[sl], q, tw, pre, n)
-    return out
 
 
 @pytest.mark.parametrize("variant", ["radix2", "regblock"])
@@ -56,7 +30,7 @@ def test_forward_bit_exact(agx, orc, dev, n, variant):
     d_out = dev.empty(x.size)
     plan.forward(d_in.data_ptr(), d_out.data_ptr(), batch, dev.stream)
     got = dev.to_host(d_out)
-    want = _oracle_forward_rns(orc, x, tabs, n, batch)
+    want = oracle_forward_rns(orc, x, tabs, n)
     assert np.array_equal(got, want)
     assert np.array_equal(dev.to_host(d_in), x), "input must not be modified"
     # in place
@@ -237,12 +211,12 @@ def test_n4096_kernel_registry_variants(agx, orc, dev, bits, config):
             assert ei.value.status == 2
             plan.close()
             return
-        _select(agx, plan, config)
+        select_entry(agx, plan, config)
     rng = np.random.default_rng(bits * 100 + (config if config != "default" else 7))
     x = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4 if bits < 62 else 3) for t in tabs])
     d = dev.to_device(x)
     plan.forward(d.data_ptr(), d.data_ptr(), batch, dev.stream)
-    assert np.array_equal(dev.to_host(d), _oracle_forward_rns(orc, x, tabs, n, batch))
+    assert np.array_equal(dev.to_host(d), oracle_forward_rns(orc, x, tabs, n))
     plan.close()
 
 
@@ -333,7 +307,7 @@ def test_inverse_round_trip_and_oracle(agx, orc, dev, n):
     want = np.concatenate([orc.inverse(r[p * batch * n:(p + 1) * batch * n], tabs[p][0],
                                        orc.make_inv_tables(tabs[p][0], tabs[p][1], n)[0], n) for p in range(primes)])
     assert np.array_equal(dev.to_host(d_r), want)
-    assert np.array_equal(y, _oracle_forward_rns(orc, x, tabs, n, batch))
+    assert np.array_equal(y, oracle_forward_rns(orc, x, tabs, n))
     plan.close()
 
 
@@ -436,7 +410,7 @@ def test_large_frames_fast_and_exact_forms(agx, orc, dev, n, bits):
     plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, primes, inverse=False)
     rng = np.random.default_rng(n + bits)
     x = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4 if bits < 62 else 3) for t in tabs])
-    want = _oracle_forward_rns(orc, x, tabs, n, batch)
+    want = oracle_forward_rns(orc, x, tabs, n)
     d_in = dev.to_device(x)
     d_out = dev.empty(x.size)
     plan.forward(d_in.data_ptr(), d_out.data_ptr(), batch, dev.stream)     # out of place
@@ -459,17 +433,12 @@ def test_calls_are_graph_capturable(agx, orc, dev, n, batch):
     buf = dev.empty(batch * n)
     mid = dev.empty(batch * n)
     out = dev.empty(batch * n)
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        plan.forward(buf.data_ptr(), mid.data_ptr(), batch, side.cuda_stream)      # warm-up outside capture
-        side.synchronize()
-        with torch.cuda.graph(graph, stream=side):
-            s = torch.cuda.current_stream().cuda_stream
-            plan.forward(buf.data_ptr(), mid.data_ptr(), batch, s)
-            plan.inverse(mid.data_ptr(), out.data_ptr(), batch, s)
-    torch.cuda.current_stream().wait_stream(side)
+
+    def both(s):
+        plan.forward(buf.data_ptr(), mid.data_ptr(), batch, s)
+        plan.inverse(mid.data_ptr(), out.data_ptr(), batch, s)
+
+    graph = capture(dev, lambda s: plan.forward(buf.data_ptr(), mid.data_ptr(), batch, s), both)
     rng = np.random.default_rng(4)
     for _ in range(2):
         x = rand_coeffs(rng, batch * n, q)
@@ -749,7 +718,7 @@ def test_one_launch_product_with_aliasing_and_no_scratch(agx, orc, dev, n, confi
     exact forms under a 60-bit modulus: no caller scratch, c distinct / aliasing a / aliasing b, operands in [0,4q), two primes"""
     batch, primes = 5, 2
     plan, tabs = _plan_from_oracle_tables(agx, orc, n, 60, primes)
-    _select(agx, plan, config)
+    select_entry(agx, plan, config)
     rng = np.random.default_rng(3700)
     a = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4) for t in tabs])
     b = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4) for t in tabs])
@@ -786,29 +755,6 @@ def test_polymul_lazy_operands(agx, orc, dev):
     plan.close()
 
 
-# every entry of the kernel registry with the size it serves and the largest modulus its arithmetic admits
-# (exact: 62 bits, fast: 61, 16q-lazy: 60); defaults are reached by the other tests, this one reaches the rest
-REGISTRY = [
-    (91, 4096, 62), (92, 4096, 61), (93, 4096, 60), (159, 4096, 60), (147, 4096, 60), (161, 4096, 60), (70, 4096, 60),
-    # streamed single-frame kernels (lazy, fast, exact): n = 1024 / 2048 / 8192, 16384 (117 + forward companion 164), 32768; A/B twins 115 / 160 / 114
-    (150, 1024, 60), (151, 1024, 61), (152, 1024, 62), (153, 2048, 60), (154, 2048, 61), (155, 2048, 62), (156, 8192, 60), (157, 8192, 61), (158, 8192, 62),
-    (117, 16384, 60), (164, 16384, 60), (120, 16384, 61), (122, 16384, 62), (115, 16384, 60), (160, 16384, 60),
-    (119, 32768, 60), (121, 32768, 61), (123, 32768, 62), (114, 32768, 60),
-    # 32-bit arithmetic: tier 2 (every q < 2^30), tier 1 (every q < 2^31)
-    (130, 1024, 30), (131, 2048, 30), (132, 4096, 30), (133, 8192, 30), (134, 16384, 30), (135, 32768, 30),
-    (136, 1024, 31), (137, 2048, 31), (138, 4096, 31), (139, 8192, 31), (140, 16384, 31), (141, 32768, 31),
-    # wave-packed kernels of n = 32 ... 512 (csrc/wp_kernels.hpp): 16q-lazy / fast / exact per size, then the 32-bit tiers
-    (200, 32, 60), (201, 32, 61), (202, 32, 62), (203, 64, 60), (204, 64, 61), (205, 64, 62), (206, 128, 60), (207, 128, 61), (208, 128, 62),
-    (209, 256, 60), (210, 256, 61), (211, 256, 62), (212, 512, 60), (213, 512, 61), (214, 512, 62),
-    (230, 32, 30), (231, 64, 30), (232, 128, 30), (233, 256, 30), (234, 512, 30), (240, 32, 31), (241, 64, 31), (242, 128, 31), (243, 256, 31), (244, 512, 31),
-    # n = 2 ... 16: one lane per frame (fast / exact; 32-bit tiers)
-    (250, 2, 61), (251, 2, 62), (252, 4, 61), (253, 4, 62), (254, 8, 61), (255, 8, 62), (256, 16, 61), (257, 16, 62),
-    (260, 2, 30), (261, 4, 30), (262, 8, 30), (263, 16, 30), (264, 2, 31), (265, 4, 31), (266, 8, 31), (267, 16, 31),
-    # A/B shapes of the wave-packed kernels (lib/libagxntt_diag.so)
-    (215, 32, 60), (220, 512, 60), (221, 512, 60), (222, 256, 60), (224, 32, 60), (235, 32, 30), (236, 512, 30),
-]
-
-
 @pytest.mark.parametrize("config,n,max_bits", REGISTRY)
 def test_every_registry_entry_at_its_own_size(agx, orc, dev, config, n, max_bits):
     """each registered kernel configuration selected explicitly (AGX_VARIANT_REGBLOCK_BASE + id) at the size it
@@ -817,7 +763,7 @@ def test_every_registry_entry_at_its_own_size(agx, orc, dev, config, n, max_bits
     batch = 3
     for bits in (max_bits, 30):
         plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, 1)
-        _select(agx, plan, config)
+        select_entry(agx, plan, config)
         q, psi, tw, pre = tabs[0]
         rng = np.random.default_rng(config * 131 + bits)
         x = rand_coeffs(rng, batch * n, q, hi_mult=4 if bits < 62 else 3)
@@ -860,7 +806,7 @@ def test_wave_packed_small_sizes(agx, orc, dev, n, bits):
             x[p * batch * n:p * batch * n + n:3] = np.uint64(t[0] - 1)
             if batch > 1:
                 x[(p * batch + 1) * n:(p * batch + 2) * n:2] = np.uint64(hi * t[0] - 1)
-        want = _oracle_forward_rns(orc, x, tabs, n, batch)
+        want = oracle_forward_rns(orc, x, tabs, n)
         d_x, d_y = dev.to_device(x), dev.empty(x.size)
         plan.forward(d_x.data_ptr(), d_y.data_ptr(), batch, dev.stream)
         assert np.array_equal(dev.to_host(d_y), want), (n, bits, batch, "forward out of place")
@@ -971,12 +917,12 @@ def test_loop_kernels_more_frames_than_workgroups(agx, orc, dev, config, n, batc
     two primes, in place: forward and inverse against the oracle"""
     primes = 2
     plan, tabs = _plan_from_oracle_tables(agx, orc, n, 60, primes)
-    _select(agx, plan, config)
+    select_entry(agx, plan, config)
     rng = np.random.default_rng(config + 1000)
     x = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4) for t in tabs])
     d = dev.to_device(x)
     plan.forward(d.data_ptr(), d.data_ptr(), batch, dev.stream)
-    assert np.array_equal(dev.to_host(d), _oracle_forward_rns(orc, x, tabs, n, batch))
+    assert np.array_equal(dev.to_host(d), oracle_forward_rns(orc, x, tabs, n))
     r = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=4) for t in tabs])
     want = np.concatenate([orc.inverse(r[p * batch * n:(p + 1) * batch * n] % np.uint64(tabs[p][0]), tabs[p][0],
                                        orc.make_inv_tables(tabs[p][0], tabs[p][1], n)[0], n) for p in range(primes)])
@@ -994,7 +940,7 @@ def test_dynamic_loop_kernels_on_two_streams_of_one_plan(agx, orc, dev, config):
 
     n, batch = (16384, 700) if config == 117 else (32768, 400)
     plan, tabs = _plan_from_oracle_tables(agx, orc, n, 60, 1)
-    _select(agx, plan, config)
+    select_entry(agx, plan, config)
     q, psi, tw, pre = tabs[0]
     rng = np.random.default_rng(3737)
     xa, xb = rand_coeffs(rng, batch * n, q), rand_coeffs(rng, batch * n, q)
@@ -1019,7 +965,7 @@ def test_large_frames_on_many_rounds_of_workgroups(agx, orc, dev, n, config, bat
     """n = 32768 / 16384 on several rounds of workgroups per CU: the whole-frame R = 5 defaults and the two-halves-in-turn kernels
     they replaced (registry ids 54 / 53, A/B): forward in place and inverse against the oracle"""
     plan, tabs = _plan_from_oracle_tables(agx, orc, n, 60, 1)
-    _select(agx, plan, config)
+    select_entry(agx, plan, config)
     q, psi, tw, pre = tabs[0]
     rng = np.random.default_rng(n + batch)
     x = rand_coeffs(rng, batch * n, q, hi_mult=4)
@@ -1270,7 +1216,7 @@ def test_randomised_shapes_against_oracle(agx, orc, dev):
         lazy = bool(rng.integers(0, 2))
         (plan.forward_lazy if lazy else plan.forward)(d_x.data_ptr(), d_y.data_ptr(), batch, dev.stream)
         y = dev.to_host(d_y)
-        want = _oracle_forward_rns(orc, x, tabs, n, batch)
+        want = oracle_forward_rns(orc, x, tabs, n)
         for p, t in enumerate(tabs):
             sl = slice(p * batch * n, (p + 1) * batch * n)
             if lazy:

@@ -6,8 +6,8 @@ NTT pipeline (gpu_util.oracle_polymul) and, on whole batches, from agx_ntt_polym
 import numpy as np
 import pytest
 
-from gpu_util import boundary_frames, check_negacyclic_shifts, fill_monomials, oracle_polymul, rand_coeffs
-from test_gpu_parity import REGISTRY, _plan_from_oracle_tables, _select
+from gpu_util import (REGISTRY, boundary_frames, capture, check_negacyclic_shifts, fill_monomials, group_of_two, moduli_for, oracle_polymul,
+                      oracle_tables, plan_from_oracle_tables, rand_coeffs, select_entry, status_of)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,7 +49,7 @@ def test_parity_against_the_oracle(agx, orc, dev, n, bits):
     are also what agx_ntt_polymul writes for (a, b)"""
     primes = 2
     batch = 259 if n <= 512 else 5
-    plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, primes)
+    plan, tabs = plan_from_oracle_tables(agx, orc, n, bits, primes)
     rng = np.random.default_rng(n * 101 + bits)
     a, b = _operands(rng, tabs, batch, n, bits)
     want = _oracle(orc, a, b, tabs, batch, n, frames=boundary_frames(batch) if n <= 512 else None)
@@ -76,7 +76,7 @@ def test_broadcast(agx, orc, dev, n, bits, batch):
     """bhat_batch = 1: the whole batch equals the dense call on bhat tiled `batch` times, and the oracle on the boundary frames"""
     torch = dev.torch
     primes = 2
-    plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, primes)
+    plan, tabs = plan_from_oracle_tables(agx, orc, n, bits, primes)
     rng = np.random.default_rng(n * 7 + bits + batch)
     a, b = _operands(rng, tabs, batch, n, bits, b_batch=1)
     d_a, d_b = dev.to_device(a), dev.to_device(b)
@@ -116,33 +116,25 @@ def test_every_registry_entry_at_its_own_size(agx, orc, dev, config, n, max_bits
     primes: dense and broadcast against the oracle.  Entries without a kernel of their own for this product (forward-only ids, the
     32-bit and wave-packed families) are served by the generic path, without scratch."""
     for bits in (max_bits, 30):
-        plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, 2)
-        _select(agx, plan, config)
+        plan, tabs = plan_from_oracle_tables(agx, orc, n, bits, 2)
+        select_entry(agx, plan, config)
         _dense_and_broadcast(agx, orc, dev, plan, tabs, n, bits, config * 131 + bits, (config, bits))
         plan.close()
 
 
 @pytest.mark.parametrize("n,bits", [(32, 60), (4096, 60), (4096, 62), (16384, 30), (32768, 60)])
 def test_radix2_plans_take_the_generic_path(agx, orc, dev, n, bits):
-    plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, 2)
+    plan, tabs = plan_from_oracle_tables(agx, orc, n, bits, 2)
     plan.set_variant(agx.VARIANT_LDS_RADIX2)
     _dense_and_broadcast(agx, orc, dev, plan, tabs, n, bits, n + bits, ("radix-2", n, bits))
     plan.close()
-
-
-def _status(agx, fn, *args):
-    try:
-        fn(*args)
-        return 0
-    except agx.AgxError as e:
-        return e.status
 
 
 @pytest.mark.parametrize("n,bits", [(64, 60), (4096, 60), (4096, 30), (16384, 61)])
 def test_aliasing_and_rejection(agx, orc, dev, n, bits):
     torch = dev.torch
     primes, batch = 2, 5
-    plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, primes)
+    plan, tabs = plan_from_oracle_tables(agx, orc, n, bits, primes)
     rng = np.random.default_rng(n + bits)
     a, b = _operands(rng, tabs, batch, n, bits)
     d_a, d_b = dev.to_device(a), dev.to_device(b)
@@ -161,17 +153,17 @@ def test_aliasing_and_rejection(agx, orc, dev, n, bits):
     keep_room, keep_c = d_room.clone(), d_c.clone()
     P = plan.polymul_ntt
     st = dev.stream
-    assert _status(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_bhat.data_ptr(), batch, batch, st) == 5           # c == bhat
-    assert _status(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_bhat.data_ptr() + 8 * (n // 2), batch, batch, st) == 5      # c over bhat, n/2 later
-    assert _status(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_bhat.data_ptr() - 8 * (n // 2), batch, batch, st) == 5      # ... n/2 earlier
-    assert _status(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_bhat.data_ptr() + 8 * (primes * n - n // 2), batch, 1, st) == 5   # broadcast: bhat is primes * n words
-    assert _status(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_c.data_ptr(), batch, 2, st) == 5                  # bhat_batch not in {1, batch}
-    assert _status(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_a.data_ptr() + 8 * (n // 2), batch, batch, st) == 5   # c straddles a
-    assert _status(agx, P, 0, d_bhat.data_ptr(), d_c.data_ptr(), batch, batch, st) == 1
-    assert _status(agx, P, d_a.data_ptr(), 0, d_c.data_ptr(), batch, batch, st) == 1
-    assert _status(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), 0, batch, batch, st) == 1
-    fwd_only, _ = _plan_from_oracle_tables(agx, orc, n, bits, primes, inverse=False)
-    assert _status(agx, fwd_only.polymul_ntt, d_a.data_ptr(), d_bhat.data_ptr(), d_c.data_ptr(), batch, batch, st) == 9
+    assert status_of(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_bhat.data_ptr(), batch, batch, st) == 5           # c == bhat
+    assert status_of(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_bhat.data_ptr() + 8 * (n // 2), batch, batch, st) == 5      # c over bhat, n/2 later
+    assert status_of(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_bhat.data_ptr() - 8 * (n // 2), batch, batch, st) == 5      # ... n/2 earlier
+    assert status_of(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_bhat.data_ptr() + 8 * (primes * n - n // 2), batch, 1, st) == 5   # broadcast: bhat is primes * n words
+    assert status_of(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_c.data_ptr(), batch, 2, st) == 5                  # bhat_batch not in {1, batch}
+    assert status_of(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), d_a.data_ptr() + 8 * (n // 2), batch, batch, st) == 5   # c straddles a
+    assert status_of(agx, P, 0, d_bhat.data_ptr(), d_c.data_ptr(), batch, batch, st) == 1
+    assert status_of(agx, P, d_a.data_ptr(), 0, d_c.data_ptr(), batch, batch, st) == 1
+    assert status_of(agx, P, d_a.data_ptr(), d_bhat.data_ptr(), 0, batch, batch, st) == 1
+    fwd_only, _ = plan_from_oracle_tables(agx, orc, n, bits, primes, inverse=False)
+    assert status_of(agx, fwd_only.polymul_ntt, d_a.data_ptr(), d_bhat.data_ptr(), d_c.data_ptr(), batch, batch, st) == 9
     fwd_only.close()
     P(d_a.data_ptr(), d_bhat.data_ptr(), d_c.data_ptr(), 0, 0, st)      # empty batch: nothing happens, as agx_ntt_polymul
     P(d_a.data_ptr(), d_bhat.data_ptr(), d_c.data_ptr(), 0, 1, st)
@@ -218,7 +210,7 @@ def test_calls_are_graph_capturable(agx, orc, dev, n, bits, batch):
     data: the same words as the eager calls"""
     torch = dev.torch
     primes = 2
-    plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, primes)
+    plan, tabs = plan_from_oracle_tables(agx, orc, n, bits, primes)
     rng = np.random.default_rng(n + batch)
     a, b = _operands(rng, tabs, batch, n, bits)
     d_a, d_b = dev.to_device(a), dev.to_device(b)
@@ -228,18 +220,12 @@ def test_calls_are_graph_capturable(agx, orc, dev, n, bits, batch):
     d_b1 = dev.to_device(b1)
     plan.forward(d_b1.data_ptr(), d_bhat1.data_ptr(), 1, dev.stream)
     c_dense, c_bcast = dev.empty(a.size), dev.empty(a.size)
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    dev.sync()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        plan.polymul_ntt(d_a.data_ptr(), d_bhat.data_ptr(), c_dense.data_ptr(), batch, batch, side.cuda_stream)      # warm-up outside capture
-        side.synchronize()
-        with torch.cuda.graph(graph, stream=side):
-            s = torch.cuda.current_stream().cuda_stream
-            plan.polymul_ntt(d_a.data_ptr(), d_bhat.data_ptr(), c_dense.data_ptr(), batch, batch, s)
-            plan.polymul_ntt(d_a.data_ptr(), d_bhat1.data_ptr(), c_bcast.data_ptr(), batch, 1, s)
-    torch.cuda.current_stream().wait_stream(side)
+
+    def dense_then_broadcast(s):
+        plan.polymul_ntt(d_a.data_ptr(), d_bhat.data_ptr(), c_dense.data_ptr(), batch, batch, s)
+        plan.polymul_ntt(d_a.data_ptr(), d_bhat1.data_ptr(), c_bcast.data_ptr(), batch, 1, s)
+
+    graph = capture(dev, lambda s: plan.polymul_ntt(d_a.data_ptr(), d_bhat.data_ptr(), c_dense.data_ptr(), batch, batch, s), dense_then_broadcast)
     e_dense, e_bcast = dev.empty(a.size), dev.empty(a.size)
     for _ in range(2):
         a, _unused = _operands(rng, tabs, batch, n, bits)
@@ -260,11 +246,9 @@ def test_group_equals_the_single_plan(agx, orc, dev):
     Plan.polymul_ntt on the same words"""
     torch = dev.torch
     n, primes, frames = 4096, 2, 41
-    tabs = [(q, orc.min_root(q, n)) for q in (orc.find_prime(60, n, k) for k in range(primes))]
-    grp = agx.DeviceGroup([0, 0], n, [t[0] for t in tabs], psi=[t[1] for t in tabs])
-    plan = agx.Plan(n, [t[0] for t in tabs], psi=[t[1] for t in tabs])
-    batches = [agx.shard_block(frames, 2, i)[1] for i in range(2)]
-    assert sum(batches) == frames and batches[0] != batches[1]
+    moduli = moduli_for(orc.find_prime, n, [60] * primes)
+    tabs = [oracle_tables(orc, n, q) for q in moduli]
+    grp, plan, batches = group_of_two(agx, orc, n, moduli, frames)
     rng = np.random.default_rng(17)
     d_a, d_bhat, d_c, d_w, bb = [], [], [], [], []
     for i, bt in enumerate(batches):

@@ -8,38 +8,13 @@ import functools
 import numpy as np
 import pytest
 
-from gpu_util import Layout, arena_for
+from gpu_util import (RESCALE_IDS, Layout, arena_for, capture, group_of_two, moduli_for, oracle_tables, plan_for_moduli, registry_entries,
+                      status_of)
 
 pytestmark = pytest.mark.gpu
 
 FLOOR, ROUND = 0, 1
 MODES = (FLOOR, ROUND)
-
-
-# ---- plans from the oracle's tables, for any list of moduli -----------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def _tables(orc, n, q):
-    psi = orc.min_root(q, n)
-    tw, pre = orc.make_tables(q, psi, n)
-    return q, psi, tw, pre
-
-
-def _moduli(orc, n, spec):
-    """spec: modulus widths in bits; the k-th use of a width takes the k-th largest prime below 2^bits"""
-    seen, out = {}, []
-    for bits in spec:
-        out.append(orc.find_prime(bits, n, seen.get(bits, 0)))
-        seen[bits] = seen.get(bits, 0) + 1
-    return tuple(out)
-
-
-def _plan(agx, orc, n, moduli, inverse=True):
-    tabs = [_tables(orc, n, q) for q in moduli]
-    tables = [np.stack([t[2] for t in tabs]), np.stack([t[3] for t in tabs])]
-    if inverse:
-        inv = [orc.make_inv_tables(t[0], t[1], n) for t in tabs]
-        tables += [np.stack([i[0] for i in inv]), np.stack([i[1] for i in inv])]
-    return agx.Plan(n, list(moduli), tables=tuple(tables)), tabs
 
 
 # ---- the reference: Python integers ---------------------------------------------------------------------------------------------
@@ -86,7 +61,7 @@ def _case(orc, n, moduli, batch, seed, boundary_only=False):
     X = _draw(rng, moduli, batch * n, boundary_only)
     qL = moduli[-1]
     h = (qL - 1) // 2
-    tabs = [_tables(orc, n, q) for q in moduli]
+    tabs = [oracle_tables(orc, n, q) for q in moduli]
     res = [np.array([x % q for x in X], dtype=np.uint64) for q in moduli]
     xhat = np.concatenate([orc.forward(r, q, tw, pre, n) for r, (q, _, tw, pre) in zip(res, tabs)])
     want = {}
@@ -128,15 +103,15 @@ def test_parity_both_modes(agx, orc, dev, n, bits, primes, batch):
     """every kernel family and both inverse forms of the large sizes (60-bit primes: the fused route from n = 1024 on, the generic route
     below; 30-bit plans: the generic route through the 32-bit kernels); batch 5 leaves the last workgroup partly filled wherever a
     workgroup holds more than one frame"""
-    moduli = _moduli(orc, n, [bits] * primes)
-    plan, _ = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, [bits] * primes)
+    plan, _ = plan_for_moduli(agx, orc, n, moduli)
     _check_plan(agx, orc, dev, plan, n, moduli, batch, n * 13 + bits + primes + batch, (n, bits, primes, batch))
     plan.close()
 
 
 def _mixed_plans(agx, orc, n):
     """[60, 30, 61]: q_L > 4 q_1; [61, 60, 30]: q_L far below the others; the three largest 62-bit-class primes: the exact-arithmetic entries"""
-    return [_moduli(orc, n, [60, 30, 61]), _moduli(orc, n, [61, 60, 30]), tuple(agx.find_primes(62, n, 3))]
+    return [moduli_for(orc.find_prime, n, [60, 30, 61]), moduli_for(orc.find_prime, n, [61, 60, 30]), tuple(agx.find_primes(62, n, 3))]
 
 
 @pytest.mark.parametrize("which", [0, 1, 2])
@@ -147,7 +122,7 @@ def test_mixed_widths(agx, orc, dev, which):
         assert moduli[2] > 4 * moduli[1]
     if which == 2:
         assert all(q > 1 << 61 for q in moduli)
-    plan, _ = _plan(agx, orc, n, moduli)
+    plan, _ = plan_for_moduli(agx, orc, n, moduli)
     _check_plan(agx, orc, dev, plan, n, moduli, batch, 77 + which, ("mixed", moduli))
     plan.close()
 
@@ -156,25 +131,18 @@ def test_mixed_widths(agx, orc, dev, which):
                                     (4096, [60, 60]), (4096, [30, 30, 30]), (16384, [61, 61]), (32768, [60, 60])])
 def test_boundary_coefficients(agx, orc, dev, n, spec):
     """frames made of nothing but boundary values: X mod q_L in {0, 1, h-1, h, h+1, q_L-1}, X in {0, Q-1}, residues q_i - 1"""
-    moduli = _moduli(orc, n, spec)
-    plan, _ = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, spec)
+    plan, _ = plan_for_moduli(agx, orc, n, moduli)
     _check_plan(agx, orc, dev, plan, n, moduli, 2, n + len(spec), ("boundary", n, spec), boundary_only=True)
     plan.close()
 
 
-# the product library's registry entries that carry launch_rescale, each with its size and the widest modulus its arithmetic admits
-# (the A/B twins 70, 114, 115, 147, 160, 161, 221 carry it too; they live in the diagnostics library only)
-RESCALE_ENTRIES = [(91, 4096, 62), (92, 4096, 61), (93, 4096, 60),
-                   (150, 1024, 60), (151, 1024, 61), (152, 1024, 62), (153, 2048, 60), (154, 2048, 61), (155, 2048, 62), (156, 8192, 60), (157, 8192, 61), (158, 8192, 62),
-                   (117, 16384, 60), (120, 16384, 61), (122, 16384, 62), (119, 32768, 60), (121, 32768, 61), (123, 32768, 62)]
-
-
-@pytest.mark.parametrize("config,n,max_bits", RESCALE_ENTRIES)
+@pytest.mark.parametrize("config,n,max_bits", registry_entries(RESCALE_IDS))
 def test_every_registry_entry_at_its_own_size(agx, orc, dev, config, n, max_bits):
     """each entry selected explicitly (AGX_VARIANT_REGBLOCK_BASE + id) under the widest modulus it admits, three primes, a ragged batch"""
     batch = 3
-    moduli = _moduli(orc, n, [max_bits] * 3)
-    plan, _ = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, [max_bits] * 3)
+    plan, _ = plan_for_moduli(agx, orc, n, moduli)
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + config)
     _check_plan(agx, orc, dev, plan, n, moduli, batch, config, ("registry id", config))
     plan.close()
@@ -183,10 +151,10 @@ def test_every_registry_entry_at_its_own_size(agx, orc, dev, config, n, max_bits
 @pytest.mark.parametrize("bits", [60, 62])
 def test_radix2_plans_take_the_generic_route_and_match_the_fused_one(agx, orc, dev, bits):
     n, batch, primes = 4096, 5, 3
-    moduli = _moduli(orc, n, [bits] * primes)
+    moduli = moduli_for(orc.find_prime, n, [bits] * primes)
     res, xhat, want = _case(orc, n, moduli, batch, 4096 + bits)
-    fused, _ = _plan(agx, orc, n, moduli)
-    generic, _ = _plan(agx, orc, n, moduli)
+    fused, _ = plan_for_moduli(agx, orc, n, moduli)
+    generic, _ = plan_for_moduli(agx, orc, n, moduli)
     generic.set_variant(agx.VARIANT_LDS_RADIX2)
     for mode in MODES:
         a, b = _run(dev, fused, xhat, batch, n, mode), _run(dev, generic, xhat, batch, n, mode)
@@ -202,8 +170,8 @@ def test_aliasing_and_guard_bands(agx, orc, dev, n, bits, primes, batch):
     """in place (out == x, scratch = x's last slab), out distinct with its own scratch, out distinct with x's last slab as the scratch:
     the same words every time; every word outside out and the scratch keeps its value (x included when the scratch is separate).
     The operands sit at odd element offsets, so no frame starts on a 16-byte boundary."""
-    moduli = _moduli(orc, n, [bits] * primes)
-    plan, _ = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, [bits] * primes)
+    plan, _ = plan_for_moduli(agx, orc, n, moduli)
     _, xhat, want = _case(orc, n, moduli, batch, n + bits + primes)
     slab = batch * n
     lx = Layout(n, primes, batch, offset=1)
@@ -240,19 +208,11 @@ def test_aliasing_and_guard_bands(agx, orc, dev, n, bits, primes, batch):
 
 
 # ---- rejections -----------------------------------------------------------------------------------------------------------------
-def _status(agx, fn, *args):
-    try:
-        fn(*args)
-        return 0
-    except agx.AgxError as e:
-        return e.status
-
-
 @pytest.mark.parametrize("n,bits", [(64, 60), (4096, 60), (4096, 30)])
 def test_rejections_write_nothing(agx, orc, dev, n, bits):
     primes, batch = 3, 2
-    moduli = _moduli(orc, n, [bits] * primes)
-    plan, _ = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, [bits] * primes)
+    plan, _ = plan_for_moduli(agx, orc, n, moduli)
     _, xhat, _ = _case(orc, n, moduli, batch, 5 * n + bits)
     slab = batch * n
     lx = Layout(n, primes, batch, offset=0)
@@ -262,32 +222,32 @@ def test_rejections_write_nothing(agx, orc, dev, n, bits):
     before = arena.image()
     x, out, scr, last = arena.address(0), arena.address(lo.offset), arena.address(ls.offset), arena.address((primes - 1) * slab)
     R, st, w = plan.rescale, dev.stream, 8
-    assert _status(agx, R, x, out, scr, batch, 2, st) == 5 and _status(agx, R, x, out, scr, batch, -1, st) == 5      # mode
-    assert _status(agx, R, x, x + w * (n // 2), scr, batch, ROUND, st) == 5                  # out partially over x
-    assert _status(agx, R, x, x + w * slab, scr, batch, ROUND, st) == 5                      # out = x one slab later: its slab 0 is x's slab 1
-    assert _status(agx, R, x, last, scr, batch, ROUND, st) == 5                              # out starts on x's last slab
-    assert _status(agx, R, x, out, out, batch, ROUND, st) == 5                               # out touching the scratch
-    assert _status(agx, R, x, out, out + w * ((primes - 1) * slab - n // 2), batch, ROUND, st) == 5
-    assert _status(agx, R, x, out, out - w * (slab - 1), batch, ROUND, st) == 5              # the scratch's last word is out's first
-    assert _status(agx, R, x, last, last, batch, ROUND, st) == 5
-    assert _status(agx, R, x, out, x, batch, ROUND, st) == 5                                 # the scratch on slabs 0 .. P-2 of x
-    assert _status(agx, R, x, out, last - w * (n // 2), batch, ROUND, st) == 5
-    assert _status(agx, R, x, x, x + w * slab, batch, ROUND, st) == 5
-    assert _status(agx, R, x, out, last + w * (n // 2), batch, ROUND, st) == 5               # the scratch over the last slab without being it
-    assert _status(agx, R, x, out, last - w, batch, ROUND, st) == 5
-    assert _status(agx, R, 0, out, scr, batch, ROUND, st) == 1 and _status(agx, R, x, 0, scr, batch, ROUND, st) == 1
-    assert _status(agx, R, x, out, 0, batch, ROUND, st) == 1
-    assert _status(agx, R, x + 4, out, scr, batch, ROUND, st) == 5 and _status(agx, R, x, out + 4, scr, batch, ROUND, st) == 5      # uint64_t data
-    assert _status(agx, R, x, out, scr + 4, batch, ROUND, st) == 5
-    one, _ = _plan(agx, orc, n, moduli[:1])
-    assert _status(agx, one.rescale, x, out, scr, batch, ROUND, st) == 5                     # P == 1
+    assert status_of(agx, R, x, out, scr, batch, 2, st) == 5 and status_of(agx, R, x, out, scr, batch, -1, st) == 5      # mode
+    assert status_of(agx, R, x, x + w * (n // 2), scr, batch, ROUND, st) == 5                  # out partially over x
+    assert status_of(agx, R, x, x + w * slab, scr, batch, ROUND, st) == 5                      # out = x one slab later: its slab 0 is x's slab 1
+    assert status_of(agx, R, x, last, scr, batch, ROUND, st) == 5                              # out starts on x's last slab
+    assert status_of(agx, R, x, out, out, batch, ROUND, st) == 5                               # out touching the scratch
+    assert status_of(agx, R, x, out, out + w * ((primes - 1) * slab - n // 2), batch, ROUND, st) == 5
+    assert status_of(agx, R, x, out, out - w * (slab - 1), batch, ROUND, st) == 5              # the scratch's last word is out's first
+    assert status_of(agx, R, x, last, last, batch, ROUND, st) == 5
+    assert status_of(agx, R, x, out, x, batch, ROUND, st) == 5                                 # the scratch on slabs 0 .. P-2 of x
+    assert status_of(agx, R, x, out, last - w * (n // 2), batch, ROUND, st) == 5
+    assert status_of(agx, R, x, x, x + w * slab, batch, ROUND, st) == 5
+    assert status_of(agx, R, x, out, last + w * (n // 2), batch, ROUND, st) == 5               # the scratch over the last slab without being it
+    assert status_of(agx, R, x, out, last - w, batch, ROUND, st) == 5
+    assert status_of(agx, R, 0, out, scr, batch, ROUND, st) == 1 and status_of(agx, R, x, 0, scr, batch, ROUND, st) == 1
+    assert status_of(agx, R, x, out, 0, batch, ROUND, st) == 1
+    assert status_of(agx, R, x + 4, out, scr, batch, ROUND, st) == 5 and status_of(agx, R, x, out + 4, scr, batch, ROUND, st) == 5      # uint64_t data
+    assert status_of(agx, R, x, out, scr + 4, batch, ROUND, st) == 5
+    one, _ = plan_for_moduli(agx, orc, n, moduli[:1])
+    assert status_of(agx, one.rescale, x, out, scr, batch, ROUND, st) == 5                     # P == 1
     one.close()
-    twice, _ = _plan(agx, orc, n, (moduli[0], moduli[1], moduli[0]))                         # q_0 == q_L: the plan exists, the call refuses
-    assert _status(agx, twice.rescale, x, out, scr, batch, ROUND, st) == 3
-    assert _status(agx, twice.rescale, x, out, scr, batch, FLOOR, st) == 3
+    twice, _ = plan_for_moduli(agx, orc, n, (moduli[0], moduli[1], moduli[0]))                         # q_0 == q_L: the plan exists, the call refuses
+    assert status_of(agx, twice.rescale, x, out, scr, batch, ROUND, st) == 3
+    assert status_of(agx, twice.rescale, x, out, scr, batch, FLOOR, st) == 3
     twice.close()
-    fwd_only, _ = _plan(agx, orc, n, moduli, inverse=False)
-    assert _status(agx, fwd_only.rescale, x, out, scr, batch, ROUND, st) == 9
+    fwd_only, _ = plan_for_moduli(agx, orc, n, moduli, inverse=False)
+    assert status_of(agx, fwd_only.rescale, x, out, scr, batch, ROUND, st) == 9
     fwd_only.close()
     R(x, out, scr, 0, ROUND, st)      # empty batch: nothing happens
     dev.sync()
@@ -301,24 +261,18 @@ def test_calls_are_graph_capturable(agx, orc, dev, n):
     """a floor and a round call captured one after the other on a side stream (no parallel branches), replayed twice on new data"""
     torch = dev.torch
     primes, batch = 3, 5
-    moduli = _moduli(orc, n, [60] * primes)
-    plan, _ = _plan(agx, orc, n, moduli)
+    moduli = moduli_for(orc.find_prime, n, [60] * primes)
+    plan, _ = plan_for_moduli(agx, orc, n, moduli)
     cases = [_case(orc, n, moduli, batch, n + k) for k in (1, 2)]
     d_x = dev.to_device(cases[0][1])
     d_out = [dev.empty((primes - 1) * batch * n) for _ in MODES]
     d_s = dev.empty(batch * n)
-    side = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    dev.sync()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        plan.rescale(d_x.data_ptr(), d_out[0].data_ptr(), d_s.data_ptr(), batch, FLOOR, side.cuda_stream)      # warm-up outside capture
-        side.synchronize()
-        with torch.cuda.graph(graph, stream=side):
-            s = torch.cuda.current_stream().cuda_stream
-            for mode in MODES:
-                plan.rescale(d_x.data_ptr(), d_out[mode].data_ptr(), d_s.data_ptr(), batch, mode, s)
-    torch.cuda.current_stream().wait_stream(side)
+
+    def both_modes(s):
+        for mode in MODES:
+            plan.rescale(d_x.data_ptr(), d_out[mode].data_ptr(), d_s.data_ptr(), batch, mode, s)
+
+    graph = capture(dev, lambda s: plan.rescale(d_x.data_ptr(), d_out[0].data_ptr(), d_s.data_ptr(), batch, FLOOR, s), both_modes)
     for _, xhat, want in cases:
         d_x.copy_(torch.from_numpy(xhat.view(np.int64).copy()))
         for d in d_out:
@@ -335,12 +289,8 @@ def test_group_equals_the_single_plan(agx, orc, dev):
     """DeviceGroup.rescale on devices [0, 0]: an odd frame count dealt to two shards, against Plan.rescale on the same words"""
     torch = dev.torch
     n, primes, frames = 4096, 3, 7
-    moduli = _moduli(orc, n, [60] * primes)
-    tabs = [_tables(orc, n, q) for q in moduli]
-    grp = agx.DeviceGroup([0, 0], n, list(moduli), psi=[t[1] for t in tabs])
-    plan = agx.Plan(n, list(moduli), psi=[t[1] for t in tabs])
-    batches = [agx.shard_block(frames, 2, i)[1] for i in range(2)]
-    assert sum(batches) == frames and batches[0] != batches[1]
+    moduli = moduli_for(orc.find_prime, n, [60] * primes)
+    grp, plan, batches = group_of_two(agx, orc, n, moduli, frames)
     d_x, d_out, d_s, wants = [], [], [], []
     for i, bt in enumerate(batches):
         _, xhat, want = _case(orc, n, moduli, bt, 900 + i)

@@ -7,7 +7,7 @@ Expected ids at n = 4096: main 93, general forward compa
 import numpy as np
 import pytest
 
-from gpu_util import oracle_polymul, radix2_twin, rand_coeffs
+from gpu_util import oracle_polymul, oracle_tables, plan_for_moduli, radix2_twin, rand_coeffs
 
 pytestmark = pytest.mark.gpu
 
@@ -19,15 +19,13 @@ ERR_BAD_SIZE, ERR_NO_INVERSE = 2, 9
 def _case(orc, n, moduli, seed):
     """operands a in [0,4q), b in [0,q) ([prime][BATCH][n] flat) under `moduli` with their minimal roots, and the oracle's results"""
     rng = np.random.default_rng(seed)
-    c = {"n": n, "moduli": [int(q) for q in moduli], "psi": [], "tables": [], "a": [], "b": [], "fwd": [], "inv": [], "mul": [], "mul0": []}
+    c = {"n": n, "moduli": [int(q) for q in moduli], "psi": [], "a": [], "b": [], "fwd": [], "inv": [], "mul": [], "mul0": []}
     for q in c["moduli"]:
-        psi = orc.min_root(q, n)
-        tw, pre = orc.make_tables(q, psi, n)
-        itw, ipre = orc.make_inv_tables(q, psi, n)
+        _, psi, tw, pre = oracle_tables(orc, n, q)
+        itw, _ = orc.make_inv_tables(q, psi, n)
         a, b = rand_coeffs(rng, BATCH * n, q, hi_mult=4), rand_coeffs(rng, BATCH * n, q)
         fwd = orc.forward(a, q, tw, pre, n)
         c["psi"].append(psi)
-        c["tables"].append((tw, pre, itw, ipre))
         c["a"].append(a)
         c["b"].append(b)
         c["fwd"].append(fwd)
@@ -49,12 +47,6 @@ def cases(agx, orc):
         "n64q60": _case(orc, 64, [orc.find_prime(60, 64, 0)], 4),
         "q61": _case(orc, 4096, [orc.find_prime(61, 4096, 0)], 5),
     }
-
-
-def _plan(agx, c, inverse=True):
-    if inverse:
-        return agx.Plan(c["n"], c["moduli"], psi=c["psi"])      # the library's own tables from the same roots, inverse included
-    return agx.Plan(c["n"], c["moduli"], tables=(np.stack([t[0] for t in c["tables"]]), np.stack([t[1] for t in c["tables"]])))
 
 
 def _check_forward(dev, plan, c, where):
@@ -108,7 +100,7 @@ def _ids(plan, batches):
 def test_n4096_q60c_walk_through_every_variant(agx, dev, cases):
     """(a) the four benchmark primes (all 2^60 - c): 1024 frames per prime are exactly the companion's 4,096-frame threshold"""
     c = cases["q60c"]
-    plan = _plan(agx, c)
+    plan = agx.Plan(c["n"], c["moduli"], psi=c["psi"])      # the library's own tables from the same roots, inverse included
     base = agx.VARIANT_REGBLOCK_BASE
     walk = [("AUTO (fresh)", None, MAIN_ID, TWIN_ID), ("BASE+165", base + 165, 165, 165), ("AUTO", agx.VARIANT_AUTO, MAIN_ID, TWIN_ID),
             ("LDS_RADIX2", agx.VARIANT_LDS_RADIX2, -1, -1), ("REGBLOCK", agx.VARIANT_REGBLOCK, MAIN_ID, TWIN_ID),
@@ -134,7 +126,7 @@ def test_n4096_q60c_walk_through_every_variant(agx, dev, cases):
 
 
 def _there_and_back(agx, dev, c, explicit_id, batches, check):
-    plan = _plan(agx, c)
+    plan = agx.Plan(c["n"], c["moduli"], psi=c["psi"])      # the library's own tables from the same roots, inverse included
     fresh = _ids(plan, batches)
     check(dev, plan, c, "fresh")
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + explicit_id)
@@ -164,10 +156,10 @@ def test_n64_explicit_id_and_back(agx, dev, cases):
     _there_and_back(agx, dev, cases["n64"], 203, (1, 3, 10**6), _check_all)
 
 
-def test_plan_without_inverse_tables(agx, dev, cases):
+def test_plan_without_inverse_tables(agx, orc, dev, cases):
     """(d) n = 64 from forward tables only: forward is right in every state; inverse and both products answer AGX_ERR_NO_INVERSE"""
     c = cases["n64q60"]
-    plan = _plan(agx, c, inverse=False)
+    plan, _ = plan_for_moduli(agx, orc, c["n"], c["moduli"], inverse=False)
     n = c["n"]
     d_a, d_b, d_c, d_s = dev.to_device(c["a"]), dev.to_device(c["b"]), dev.empty(BATCH * n), dev.empty(BATCH * n)
     for name, variant in (("AUTO", None), ("BASE+203", agx.VARIANT_REGBLOCK_BASE + 203), ("LDS_RADIX2", agx.VARIANT_LDS_RADIX2)):
@@ -188,7 +180,7 @@ def test_plan_without_inverse_tables(agx, dev, cases):
 def test_refused_choice_changes_nothing(agx, dev, cases, case, refused):
     """(e) an id that is not legal for the plan is refused with AGX_ERR_BAD_SIZE on the host, and the plan goes on as before"""
     c = cases[case]
-    plan = _plan(agx, c)
+    plan = agx.Plan(c["n"], c["moduli"], psi=c["psi"])      # the library's own tables from the same roots, inverse included
     before = _ids(plan, (1, 3, 10**6))
     with pytest.raises(agx.AgxError) as ei:
         plan.set_variant(agx.VARIANT_REGBLOCK_BASE + refused)

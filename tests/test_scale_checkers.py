@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from gpu_util import (check_automorphism_coeff, check_automorphism_ntt, check_fixed_shifts, check_rescale_identity, fill_rescale_constants,
-                      ntt_pi, oracle_polymul, rand_coeffs, rescale_identity_constants, rescale_identity_sum_, rescale_reference, sigma,
+                      moduli_for, ntt_pi, oracle_polymul, rand_coeffs, rescale_identity_constants, rescale_identity_sum_, rescale_reference, sigma,
                       spread_lazy_, thin_frames)
 
 CPU = torch.device("cpu")
@@ -19,14 +19,6 @@ N, BATCH, TRIP = 64, 9, 256      # a "grid-stride trip" of 256 words: frames 0 .
 
 def _t(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).copy())
-
-
-def _moduli(orc, n, spec):
-    seen, out = {}, []
-    for bits in spec:
-        out.append(orc.find_prime(bits, n, seen.get(bits, 0)))
-        seen[bits] = seen.get(bits, 0) + 1
-    return out
 
 
 # ---- the rescale identity against Python integers -------------------------------------------------------------------------------
@@ -48,7 +40,7 @@ def _identity_inputs(orc, rng, moduli, count):
 @pytest.mark.parametrize("n", [8, 64])
 @pytest.mark.parametrize("spec", [(60, 60, 60), (60, 30, 61), (30, 30, 30), (62, 62), (30, 30), (61, 60, 30), (62, 62, 62)], ids=str)
 def test_identity_words_equal_the_python_integer_reference(orc, n, spec):
-    moduli = _moduli(orc, n, spec)
+    moduli = list(moduli_for(orc.find_prime, n, spec))
     batch = 5
     rng = np.random.default_rng(n + sum(spec))
     y, x = _identity_inputs(orc, rng, moduli, batch * n)
@@ -78,7 +70,7 @@ def test_rescale_reference_on_drawn_integers(orc):
     """X drawn as Python integers, its residues handed over: the CRT inside rescale_reference must find the same X"""
     n = 64
     for spec in [(60, 60, 60), (60, 30, 61), (62, 62)]:
-        moduli = _moduli(orc, n, spec)
+        moduli = list(moduli_for(orc.find_prime, n, spec))
         Q = int(np.prod([int(q) for q in moduli], dtype=object))
         qL = moduli[-1]
         h = (qL - 1) // 2
@@ -96,7 +88,7 @@ def test_rescale_reference_on_drawn_integers(orc):
 def _case(orc, kind):
     """(the oracle's output [primes][BATCH][N] for `kind`, a function judging such an output with the checker of that kind)"""
     spec = (60, 30, 61) if kind != "rescale_round" and kind != "rescale_floor" else (60, 60, 61)
-    moduli = _moduli(orc, N, spec)
+    moduli = list(moduli_for(orc.find_prime, N, spec))
     P = len(moduli)
     rng = np.random.default_rng(len(kind))
     tabs = [(q, orc.min_root(q, N)) for q in moduli]
