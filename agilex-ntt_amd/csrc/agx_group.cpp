@@ -117,6 +117,7 @@ void shard_range(uint64_t num_frames, uint32_t num_shards, uint32_t index, uint6
 }
 
 int check_devices(const int* devices, uint32_t num_devices) {
+    if (num_devices == 0 || num_devices > 1024) return AGX_ERR_BAD_ARGUMENT;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return AGX_ERR_NO_DEVICE;
     for (uint32_t i = 0; i < num_devices; ++i)
@@ -147,10 +148,10 @@ int create_group(agx_ntt_group** out, const int* devices, uint32_t num_devices, 
     return AGX_OK;
 }
 
-int check_group_size(uint32_t n, uint32_t num_primes, uint32_t num_devices) {
-    if (n < AGX_NTT_MIN_N || n > AGX_NTT_MAX_N || (n & (n - 1))) return AGX_ERR_BAD_SIZE;
-    if (num_primes == 0 || num_primes > 65535 || num_devices == 0 || num_devices > 1024) return AGX_ERR_BAD_ARGUMENT;
-    return AGX_OK;
+// fn(shard, index) on the thread of every shard whose batch is not empty
+template <class F>
+int on_busy_shards(const agx_ntt_group* group, const uint64_t* batch, F&& fn) {
+    return guarded([&] { return on_every_shard(group, [&](uint32_t i) -> int { return batch[i] ? fn(*group->shards[i], i) : AGX_OK; }); });
 }
 
 }  // namespace
@@ -167,17 +168,12 @@ int agx_ntt_shard_range(uint64_t num_frames, uint32_t num_shards, uint32_t index
 int agx_ntt_group_create(agx_ntt_group** group, const int* devices, uint32_t num_devices, uint32_t n, uint32_t num_primes,
                          const uint64_t* moduli, const uint64_t* twiddles, const uint64_t* precons,
                          const uint64_t* inv_twiddles, const uint64_t* inv_precons) {
-    if (!group || !devices || !moduli || !twiddles || !precons) return AGX_ERR_NULL_POINTER;
+    if (!group || !devices) return AGX_ERR_NULL_POINTER;
     *group = nullptr;
-    if ((inv_twiddles == nullptr) != (inv_precons == nullptr)) return AGX_ERR_NULL_POINTER;
-    int rc = check_group_size(n, num_primes, num_devices);
+    const int rc = check_create_args(n, num_primes, moduli, twiddles, precons, inv_twiddles, inv_precons);      // the rules of agx_ntt_plan_create
+    if (rc && rc != AGX_ERR_BAD_MODULUS) return rc;
+    if (int drc = check_devices(devices, num_devices)) return drc;      // a device list that cannot serve is reported before an illegal modulus
     if (rc) return rc;
-    if ((rc = check_devices(devices, num_devices))) return rc;
-    // the modulus rules of agx_ntt_plan_create (src/kernel/ntt.cpp:302-369: 4q < 2^64, 2n | q - 1)
-    for (uint32_t k = 0; k < num_primes; ++k) {
-        const uint64_t q = moduli[k];
-        if (q < 3 || (q & 1) == 0 || q >= (1ull << 62) || (q - 1) % (2ull * n)) return AGX_ERR_BAD_MODULUS;
-    }
     return guarded([&]() -> int {
         plan_image img;
         prepare_plan_image(img, n, num_primes, moduli, nullptr, twiddles, precons, inv_twiddles, inv_precons);      // once, on the host
@@ -189,21 +185,11 @@ int agx_ntt_group_create_auto(agx_ntt_group** group, const int* devices, uint32_
                               const uint64_t* moduli, const uint64_t* psi) {
     if (!group || !devices || !moduli) return AGX_ERR_NULL_POINTER;
     *group = nullptr;
-    int rc = check_group_size(n, num_primes, num_devices);
-    if (rc) return rc;
-    if ((rc = check_devices(devices, num_devices))) return rc;
+    if (int rc = check_shape(n, num_primes)) return rc;
+    if (int rc = check_devices(devices, num_devices)) return rc;
     return guarded([&]() -> int {
-        // tables generated once: through the public host-math entry points, which validate (q, psi) exactly as agx_ntt_plan_create_auto does
-        std::vector<uint64_t> roots(num_primes), tw((size_t)num_primes * n), pre(tw.size()), itw(tw.size()), ipre(tw.size());
-        for (uint32_t k = 0; k < num_primes; ++k) {
-            roots[k] = psi ? psi[k] : 0;
-            int mrc = AGX_OK;
-            if (!psi && (mrc = agx_ntt_min_root(moduli[k], n, &roots[k]))) return mrc;
-            if ((mrc = agx_ntt_make_tables(moduli[k], roots[k], n, &tw[(size_t)k * n], &pre[(size_t)k * n]))) return mrc;
-            if ((mrc = agx_ntt_make_inverse_tables(moduli[k], roots[k], n, &itw[(size_t)k * n], &ipre[(size_t)k * n]))) return mrc;
-        }
-        plan_image img;
-        prepare_plan_image(img, n, num_primes, moduli, roots.data(), tw.data(), pre.data(), itw.data(), ipre.data());
+        plan_image img;      // roots judged and tables generated once, as agx_ntt_plan_create_auto does
+        if (int rc = prepare_auto_image(img, n, num_primes, moduli, psi)) return rc;
         return create_group(group, devices, num_devices, img);
     });
 }
@@ -259,54 +245,38 @@ int agx_ntt_group_inverse_host(const agx_ntt_group* group, const uint64_t* in, u
 }
 
 // ---- device pointers: one pointer and one batch per shard, every shard launched from its own thread on its own stream ---------
-enum group_op { OP_FORWARD, OP_INVERSE, OP_POLYMUL, OP_POLYMUL_NTT, OP_RESCALE, OP_AUTOMORPHISM };
-
-static int group_device(const agx_ntt_group* group, group_op op, const uint64_t* const* a, const uint64_t* const* b, uint64_t* const* c,
-                        uint64_t* const* scratch, const uint64_t* batch, const uint64_t* bhat_batch = nullptr, int mode = 0, uint32_t galois_elt = 0) {
-    if (!group || !a || !c || !batch || ((op == OP_POLYMUL || op == OP_POLYMUL_NTT) && !b) || (op == OP_POLYMUL_NTT && !bhat_batch) || (op == OP_RESCALE && !scratch))
-        return AGX_ERR_NULL_POINTER;
-    return guarded([&] {
-        return on_every_shard(group, [&](uint32_t i) -> int {
-            shard* s = group->shards[i].get();
-            if (batch[i] == 0) return AGX_OK;
-            switch (op) {
-                case OP_FORWARD: return agx_ntt_forward(s->plan, a[i], c[i], batch[i], s->stream);
-                case OP_INVERSE: return agx_ntt_inverse(s->plan, a[i], c[i], batch[i], s->stream);
-                case OP_POLYMUL: return agx_ntt_polymul(s->plan, a[i], b[i], c[i], scratch ? scratch[i] : nullptr, batch[i], s->stream);
-                case OP_RESCALE: return agx_ntt_rescale(s->plan, a[i], c[i], scratch[i], batch[i], mode, s->stream);
-                case OP_AUTOMORPHISM: return agx_ntt_automorphism(s->plan, a[i], c[i], batch[i], galois_elt, mode, s->stream);
-                default: return agx_ntt_polymul_ntt(s->plan, a[i], b[i], c[i], batch[i], bhat_batch[i], s->stream);
-            }
-        });
-    });
-}
-
 int agx_ntt_group_forward(const agx_ntt_group* group, const uint64_t* const* d_in, uint64_t* const* d_out, const uint64_t* batch) {
-    return group_device(group, OP_FORWARD, d_in, nullptr, d_out, nullptr, batch);
+    if (!group || !d_in || !d_out || !batch) return AGX_ERR_NULL_POINTER;
+    return on_busy_shards(group, batch, [&](const shard& s, uint32_t i) { return agx_ntt_forward(s.plan, d_in[i], d_out[i], batch[i], s.stream); });
 }
 
 int agx_ntt_group_inverse(const agx_ntt_group* group, const uint64_t* const* d_in, uint64_t* const* d_out, const uint64_t* batch) {
-    return group_device(group, OP_INVERSE, d_in, nullptr, d_out, nullptr, batch);
+    if (!group || !d_in || !d_out || !batch) return AGX_ERR_NULL_POINTER;
+    return on_busy_shards(group, batch, [&](const shard& s, uint32_t i) { return agx_ntt_inverse(s.plan, d_in[i], d_out[i], batch[i], s.stream); });
 }
 
 int agx_ntt_group_polymul(const agx_ntt_group* group, const uint64_t* const* d_a, const uint64_t* const* d_b, uint64_t* const* d_c,
                           uint64_t* const* d_scratch, const uint64_t* batch) {
-    return group_device(group, OP_POLYMUL, d_a, d_b, d_c, d_scratch, batch);
+    if (!group || !d_a || !d_b || !d_c || !batch) return AGX_ERR_NULL_POINTER;      // no scratch list: no shard has scratch
+    return on_busy_shards(group, batch, [&](const shard& s, uint32_t i) { return agx_ntt_polymul(s.plan, d_a[i], d_b[i], d_c[i], d_scratch ? d_scratch[i] : nullptr, batch[i], s.stream); });
 }
 
 int agx_ntt_group_polymul_ntt(const agx_ntt_group* group, const uint64_t* const* d_a, const uint64_t* const* d_bhat, uint64_t* const* d_c,
                               const uint64_t* batch, const uint64_t* bhat_batch) {
-    return group_device(group, OP_POLYMUL_NTT, d_a, d_bhat, d_c, nullptr, batch, bhat_batch);
+    if (!group || !d_a || !d_bhat || !d_c || !batch || !bhat_batch) return AGX_ERR_NULL_POINTER;
+    return on_busy_shards(group, batch, [&](const shard& s, uint32_t i) { return agx_ntt_polymul_ntt(s.plan, d_a[i], d_bhat[i], d_c[i], batch[i], bhat_batch[i], s.stream); });
 }
 
 int agx_ntt_group_rescale(const agx_ntt_group* group, const uint64_t* const* d_x, uint64_t* const* d_out, uint64_t* const* d_scratch,
                           const uint64_t* batch, int mode) {
-    return group_device(group, OP_RESCALE, d_x, nullptr, d_out, d_scratch, batch, nullptr, mode);
+    if (!group || !d_x || !d_out || !d_scratch || !batch) return AGX_ERR_NULL_POINTER;
+    return on_busy_shards(group, batch, [&](const shard& s, uint32_t i) { return agx_ntt_rescale(s.plan, d_x[i], d_out[i], d_scratch[i], batch[i], mode, s.stream); });
 }
 
 int agx_ntt_group_automorphism(const agx_ntt_group* group, const uint64_t* const* d_in, uint64_t* const* d_out, const uint64_t* batch,
                                uint32_t galois_elt, int form) {
-    return group_device(group, OP_AUTOMORPHISM, d_in, nullptr, d_out, nullptr, batch, nullptr, form, galois_elt);
+    if (!group || !d_in || !d_out || !batch) return AGX_ERR_NULL_POINTER;
+    return on_busy_shards(group, batch, [&](const shard& s, uint32_t i) { return agx_ntt_automorphism(s.plan, d_in[i], d_out[i], batch[i], galois_elt, form, s.stream); });
 }
 
 int agx_ntt_group_synchronize(const agx_ntt_group* group) {

@@ -49,12 +49,11 @@ void staging_set::destroy() {
 namespace {
 
 // one cached set per device, handed to one call at a time; a second concurrent call gets nullptr and builds its own
-constexpr int kPoolDevices = 64;
-std::mutex g_stage_mu[kPoolDevices];
-staging_set g_stage_pool[kPoolDevices];
+std::mutex g_stage_mu[kMaxDevices];
+staging_set g_stage_pool[kMaxDevices];
 
 staging_set* acquire_staging(int device) {
-    if (device < 0 || device >= kPoolDevices) return nullptr;
+    if (device < 0 || device >= kMaxDevices) return nullptr;
     return g_stage_mu[device].try_lock() ? &g_stage_pool[device] : nullptr;
 }
 void release_staging(int device) { g_stage_mu[device].unlock(); }
@@ -104,10 +103,7 @@ int host_stream_pipeline(const agx_ntt_plan* plan, const uint64_t* in, const uin
     if (!plan || !in || !in2 || !out) return AGX_ERR_NULL_POINTER;
     if (plan->num_primes != 1) return AGX_ERR_BAD_ARGUMENT;   // one modulus per stream, as the reference (ntt.cpp:143-144)
     if (inverse && !plan->has_inverse) return AGX_ERR_NO_INVERSE;
-    {
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev != plan->device) return AGX_ERR_BAD_ARGUMENT;   // staging memory is allocated on the current device
-    }
+    if (int rc = check_plan(plan)) return rc;   // staging memory is allocated on the current device
     if (num_frames == 0) return AGX_OK;
     auto transform = [&](uint64_t* d, uint64_t frames, hipStream_t s) {
         return inverse ? agx_ntt_inverse(plan, d, d, frames, s) : agx_ntt_forward(plan, d, d, frames, s);
@@ -247,7 +243,7 @@ struct oneshot_cache {
     agx_ntt_plan* plan = nullptr;
     oneshot_key key;
 };
-oneshot_cache g_oneshot[kPoolDevices];
+oneshot_cache g_oneshot[kMaxDevices];
 
 // AGX_NTT_DEVICES=0,1,2,3 in the environment: the one-shot call deals its frames to those devices (a group, include/agx_ntt.h section 5)
 // instead of running on the current one -- the reference's NUM_NTT_COMPUTE_UNITS replication (src/kernel/ntt.cpp:8-12, 526-536) for a
@@ -281,14 +277,13 @@ void env_device_list(std::vector<int>& out) {
 int agx_ntt_forward_host(const uint64_t* in, const uint64_t* in2, const uint64_t* modulus,
                          const uint64_t* twiddles, const uint64_t* precons, uint64_t* out,
                          uint32_t n, uint32_t num_frames) {
-    if (!in || !in2 || !modulus || !twiddles || !precons || !out) return AGX_ERR_NULL_POINTER;
-    int rc = check_size(n);
+    if (!in || !in2 || !out) return AGX_ERR_NULL_POINTER;
+    int rc = check_create_args(n, 1, modulus, twiddles, precons, nullptr, nullptr);      // the rules of the plan this call builds
     if (rc) return rc;
-    if ((rc = check_modulus(modulus[0], n))) return rc;
     if (num_frames == 0) return AGX_OK;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return AGX_ERR_NO_DEVICE;
-    try {
+    return guarded([&]() -> int {
         std::vector<int> devices;
         env_device_list(devices);
         if (!devices.empty()) {
@@ -304,7 +299,7 @@ int agx_ntt_forward_host(const uint64_t* in, const uint64_t* in2, const uint64_t
             }
             return agx_ntt_group_forward_host(c.group, in, in2, out, num_frames);
         }
-        if (dev < 0 || dev >= kPoolDevices) {      // no cache slot: build, use, destroy
+        if (dev < 0 || dev >= kMaxDevices) {      // no cache slot: build, use, destroy
             agx_ntt_plan* plan = nullptr;
             if ((rc = build_plan(&plan, n, 1, modulus, nullptr, twiddles, precons, nullptr, nullptr))) return rc;
             rc = agx_ntt_forward_host_stream(plan, in, in2, out, num_frames);
@@ -321,11 +316,7 @@ int agx_ntt_forward_host(const uint64_t* in, const uint64_t* in2, const uint64_t
             c.key.assign(n, modulus[0], twiddles, precons);
         }
         return agx_ntt_forward_host_stream(c.plan, in, in2, out, num_frames);
-    } catch (const std::bad_alloc&) {
-        return AGX_ERR_ALLOC;
-    } catch (...) {
-        return AGX_ERR_BAD_ARGUMENT;
-    }
+    });
 }
 
 // Frees what the library keeps between calls: the one-shot plans and the pinned / device staging buffers of every device
@@ -338,7 +329,7 @@ int agx_ntt_release_caches(void) {
         g_oneshot_group.group = nullptr;
         g_oneshot_group.key = oneshot_key{};
     }
-    for (int d = 0; d < kPoolDevices; ++d) {
+    for (int d = 0; d < kMaxDevices; ++d) {
         {
             std::lock_guard<std::mutex> lock(g_oneshot[d].mu);
             free_plan(g_oneshot[d].plan);
@@ -354,8 +345,7 @@ int agx_ntt_release_caches(void) {
 
 int agx_ntt_find_primes(uint32_t bits, uint32_t n, uint32_t count, uint64_t* primes_out) {
     if (!primes_out) return AGX_ERR_NULL_POINTER;
-    int rc = check_size(n);
-    if (rc) return rc;
+    if (int rc = check_size(n)) return rc;
     if (bits < 2 || bits > 62) return AGX_ERR_BAD_ARGUMENT;
     return guarded([&]() -> int {
         std::vector<uint64_t> v = find_ntt_primes(bits, n, count);
@@ -367,9 +357,8 @@ int agx_ntt_find_primes(uint32_t bits, uint32_t n, uint32_t count, uint64_t* pri
 
 int agx_ntt_min_root(uint64_t q, uint32_t n, uint64_t* psi_out) {
     if (!psi_out) return AGX_ERR_NULL_POINTER;
-    int rc = check_size(n);
-    if (rc) return rc;
-    if ((rc = check_modulus(q, n))) return rc;
+    if (int rc = check_size(n)) return rc;
+    if (int rc = check_modulus(q, n)) return rc;
     if (!is_prime_u64(q)) return AGX_ERR_BAD_MODULUS;
     const uint64_t r = min_primitive_root_2n(q, n);
     if (!r) return AGX_ERR_BAD_ROOT;
@@ -379,8 +368,7 @@ int agx_ntt_min_root(uint64_t q, uint32_t n, uint64_t* psi_out) {
 
 int agx_ntt_galois_element(uint32_t n, int64_t step, uint32_t* galois_elt) {
     if (!galois_elt) return AGX_ERR_NULL_POINTER;
-    int rc = check_size(n);
-    if (rc) return rc;
+    if (int rc = check_size(n)) return rc;
     const uint32_t mask = 2u * n - 1u;
     uint32_t base = 5u;
     if (step < 0) {      // 5^-1 mod 2n: Newton's iteration on the odd 5 doubles the correct low bits (3 -> 6 -> 12 -> 24 >= 16)
@@ -396,9 +384,8 @@ int agx_ntt_galois_element(uint32_t n, int64_t step, uint32_t* galois_elt) {
 
 static int make_tables_common(uint64_t q, uint64_t psi, uint32_t n, uint64_t* tw, uint64_t* pre, bool inverse) {
     if (!tw || !pre) return AGX_ERR_NULL_POINTER;
-    int rc = check_size(n);
-    if (rc) return rc;
-    if ((rc = check_modulus(q, n))) return rc;
+    if (int rc = check_size(n)) return rc;
+    if (int rc = check_modulus(q, n)) return rc;
     if (!is_prime_u64(q)) return AGX_ERR_BAD_MODULUS;
     if (!is_primitive_root_2n(psi, q, n)) return AGX_ERR_BAD_ROOT;
     power_tables_bitrev(q, inverse ? inv_mod(psi, q) : psi, n, tw, pre);

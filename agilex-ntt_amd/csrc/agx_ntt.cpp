@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "host_math.hpp"
+#include "operands.hpp"
 #include "plan_internal.hpp"
 #include "rb_registry.hpp"
 #ifdef AGX_DIAG
@@ -37,7 +38,6 @@ namespace {
 // function attributes (large dynamic LDS) are per device and never change: set them once per device,
 // not on every plan creation
 hipError_t kernels_init_once(int device) {
-    constexpr int kMaxDevices = 64;
     static std::once_flag once[kMaxDevices];
     static hipError_t result[kMaxDevices];
     if (device < 0 || device >= kMaxDevices) return kernels_init();
@@ -109,6 +109,26 @@ int check_modulus(uint64_t q, uint32_t n) {
     if (q < 3 || (q & 1) == 0 || q >= (1ull << 62)) return AGX_ERR_BAD_MODULUS;
     if ((q - 1) % (2ull * n)) return AGX_ERR_BAD_MODULUS;
     return AGX_OK;
+}
+
+int check_shape(uint32_t n, uint32_t num_primes) {
+    if (int rc = check_size(n)) return rc;
+    return num_primes == 0 || num_primes > 65535 ? AGX_ERR_BAD_ARGUMENT : AGX_OK;
+}
+
+int check_create_args(uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre) {
+    if (!moduli || !tw || !pre || (itw == nullptr) != (ipre == nullptr)) return AGX_ERR_NULL_POINTER;
+    if (int rc = check_shape(n, num_primes)) return rc;
+    for (uint32_t k = 0; k < num_primes; ++k)
+        if (int rc = check_modulus(moduli[k], n)) return rc;
+    return AGX_OK;
+}
+
+// Plan rule: there is a plan, and its tables (and any staging memory of the call) live on the current device.
+int check_plan(const agx_ntt_plan* plan) {
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    int dev = -1;
+    return hipGetDevice(&dev) == hipSuccess && dev == plan->device ? AGX_OK : AGX_ERR_BAD_ARGUMENT;
 }
 
 void free_plan(agx_ntt_plan* p) {
@@ -264,6 +284,21 @@ static int upload_pass_tables(pass_tables& dst, const host_pass_tables& src) {
     return src.inv.empty() ? AGX_OK : dst.inv.upload(src.inv);
 }
 
+int prepare_auto_image(plan_image& img, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi) {
+    std::vector<uint64_t> roots(num_primes), tw((size_t)num_primes * n), pre(tw.size()), itw(tw.size()), ipre(tw.size());
+    for (uint32_t k = 0; k < num_primes; ++k) {
+        const uint64_t q = moduli[k];
+        if (int rc = check_modulus(q, n)) return rc;
+        if (!is_prime_u64(q)) return AGX_ERR_BAD_MODULUS;
+        roots[k] = psi ? psi[k] : min_primitive_root_2n(q, n);
+        if (!is_primitive_root_2n(roots[k], q, n)) return AGX_ERR_BAD_ROOT;
+        power_tables_bitrev(q, roots[k], n, &tw[(size_t)k * n], &pre[(size_t)k * n]);
+        power_tables_bitrev(q, inv_mod(roots[k], q), n, &itw[(size_t)k * n], &ipre[(size_t)k * n]);
+    }
+    prepare_plan_image(img, n, num_primes, moduli, roots.data(), tw.data(), pre.data(), itw.data(), ipre.data());
+    return AGX_OK;
+}
+
 int instantiate_plan(agx_ntt_plan** out, const plan_image& img) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return AGX_ERR_NO_DEVICE;
@@ -295,8 +330,6 @@ int instantiate_plan(agx_ntt_plan** out, const plan_image& img) {
 
 int build_plan(agx_ntt_plan** out, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
                const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return AGX_ERR_NO_DEVICE;
     plan_image img;
     prepare_plan_image(img, n, num_primes, moduli, psi, tw, pre, itw, ipre);
     return instantiate_plan(out, img);
@@ -306,70 +339,30 @@ int build_plan(agx_ntt_plan** out, uint32_t n, uint32_t num_primes, const uint64
 
 namespace {
 
-// Does any frame of set A touch a frame of set B = A shifted by delta elements?  Frame (p, b) lies at base + p prime_stride + b poly_stride,
-// n elements long; frames i of A and j of B touch iff |delta + dp prime_stride + db poly_stride| < n for their index differences
-// (dp, db).  skip_self excludes (dp, db) = (0, 0) when delta = 0: a frame does not collide with itself.
-bool frames_touch(int64_t delta, bool skip_self, uint32_t n, uint32_t num_primes, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
-    const int64_t P = (int64_t)num_primes, B = (int64_t)batch;
-    for (int64_t dp = -(P - 1); dp <= P - 1; ++dp) {
-        const int64_t base = delta + dp * prime_stride;
-        const bool self_row = skip_self && dp == 0;
-        if (poly_stride == 0 || B == 1) {
-            if (self_row) {
-                if (B > 1) return true;      // poly_stride 0: frames (p, 0) and (p, 1) are the same words
-                continue;
-            }
-            if (base > -(int64_t)n && base < (int64_t)n) return true;
-            continue;
-        }
-        // db closest to -base / poly_stride, within [-(B-1), B-1]: try the two neighbours of the quotient
-        int64_t d0 = -base / poly_stride;
-        for (int64_t db = d0 - 1; db <= d0 + 1; ++db) {
-            const int64_t dbc = std::max<int64_t>(-(B - 1), std::min<int64_t>(B - 1, db));
-            if (self_row && dbc == 0) continue;
-            const int64_t v = base + dbc * poly_stride;
-            if (v > -(int64_t)n && v < (int64_t)n) return true;
-        }
-    }
-    return false;
-}
+uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }      // what operands.hpp takes
+bool aligned8(const void* p) { return (addr(p) & 7u) == 0; }      // uint64_t data
+bool batch_fits_grid(const agx_ntt_plan* plan, uint64_t batch) { return batch <= (0x7fffffffull >> (plan->log_n > 14 ? plan->log_n - 14 : 0)); }      // grid.x limit (the radix-2 kernels split n = 32768 in two blocks)
 
-// Do two frame sets of the same shape overlap without being the same set?  Identical bases are in place (legal: a workgroup reads its
-// frame before it writes it); otherwise NO frame of one may touch any frame of the other, because workgroups run in any order
-// (include/agx_ntt.h: AGX_ERR_BAD_ARGUMENT "overlapping in/out").  Interleaved layouts whose frames do not touch (out = in + n with
-// poly_stride = 2n) are legal and pass.
-bool partial_overlap(const void* a, const void* b, uint32_t n, uint32_t num_primes, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
-    if (a == b || batch == 0) return false;
-    const int64_t delta = (int64_t)((reinterpret_cast<intptr_t>(b) - reinterpret_cast<intptr_t>(a)) / (intptr_t)sizeof(uint64_t));     // elements (both 8-byte aligned)
-    const int64_t extent = (int64_t)(num_primes - 1) * prime_stride + (int64_t)(batch - 1) * poly_stride + (int64_t)n;
-    if (delta >= extent || -delta >= extent) return false;      // disjoint ranges
-    return frames_touch(delta, false, n, num_primes, batch, prime_stride, poly_stride);
-}
+// The dense [prime][batch][n] layout of a plan, for the checks and the launches alike.  Nothing is multiplied for a batch past the grid
+// limit, which check_frames refuses before it looks at a stride: batch * n stays below 2^46.
+frame_layout dense(const agx_ntt_plan* plan, uint64_t batch) { return frame_layout{batch, batch_fits_grid(plan, batch) ? (int64_t)(batch * plan->n) : 0, (int64_t)plan->n}; }
+uint64_t dense_words(const agx_ntt_plan* plan, uint64_t batch) { return plan->num_primes * batch * plan->n; }      // of a bounded batch: < 2^62
 
-// Does one frame set overlap itself (two distinct frames (p, b) != (p', b') touch)?  Two workgroups would then transform the same words
-// in place, under different moduli for dp != 0: garbage.  The dense [prime][batch][n] layout and the [poly][prime][n] layout answer in
-// O(1) (no loop on the latency path); anything else takes frames_touch's closest-db search with delta = 0.
-bool self_overlap(uint32_t n, uint32_t num_primes, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
-    if (batch == 0 || (num_primes == 1 && batch == 1)) return false;
-    const int64_t N = (int64_t)n, P = (int64_t)num_primes, B = (int64_t)batch;
-    // prime-major: batches of one prime are n apart, primes clear the whole batch
-    if ((B == 1 || poly_stride >= N) && (P == 1 || prime_stride >= (B - 1) * poly_stride + N)) return false;
-    // poly-major: primes of one polynomial are n apart, polynomials clear every prime
-    if ((P == 1 || prime_stride >= N) && (B == 1 || poly_stride >= (P - 1) * prime_stride + N)) return false;
-    return frames_touch(0, true, n, num_primes, batch, prime_stride, poly_stride);
-}
-
-int check_call(const agx_ntt_plan* plan, const void* a, const void* b, uint64_t batch, int64_t prime_stride, int64_t poly_stride) {
-    if (!plan || !a || !b) return AGX_ERR_NULL_POINTER;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != plan->device) return AGX_ERR_BAD_ARGUMENT;   // the plan's tables live on plan->device
-    if (prime_stride < 0 || poly_stride < 0) return AGX_ERR_BAD_ARGUMENT;
-    if (batch > 1 && poly_stride < (int64_t)plan->n) return AGX_ERR_BAD_ARGUMENT;   // frames would overlap
-    if (self_overlap(plan->n, plan->num_primes, batch, prime_stride, poly_stride)) return AGX_ERR_BAD_ARGUMENT;   // (p, b) and (p', b') share words
-    if ((batch << (plan->log_n > 14 ? plan->log_n - 14 : 0)) > 0x7fffffffull) return AGX_ERR_BAD_ARGUMENT;  // grid.x limit (the radix-2 kernels split n = 32768 in two blocks)
-    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7u) != 0) return AGX_ERR_BAD_ARGUMENT;      // uint64_t data
-    if (partial_overlap(a, b, plan->n, plan->num_primes, batch, prime_stride, poly_stride)) return AGX_ERR_BAD_ARGUMENT;
+// Frame-set rule: the plan's frames in layout fl at `base`.  Batch first, then layout_fits: nothing after them can overflow (operands.hpp).
+int check_frames(const agx_ntt_plan* plan, const void* base, const frame_layout& fl) {
+    if (!base) return AGX_ERR_NULL_POINTER;
+    if (!aligned8(base) || !batch_fits_grid(plan, fl.batch)) return AGX_ERR_BAD_ARGUMENT;
+    if (fl.batch > 1 && fl.poly_stride < (int64_t)plan->n) return AGX_ERR_BAD_ARGUMENT;   // frames would overlap
+    if (!layout_fits(plan->n, plan->num_primes, fl.batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;   // a negative stride, or an extent past 2^60 words
+    if (self_overlap(plan->n, plan->num_primes, fl.batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;   // (p, b) and (p', b') share words
     return AGX_OK;
+}
+
+// Pair rule: a second set in the layout of the checked set at `base` is that set itself (in place) or touches none of its frames.
+int check_pair(const agx_ntt_plan* plan, const void* base, const void* other, const frame_layout& fl) {
+    if (!other) return AGX_ERR_NULL_POINTER;
+    if (!aligned8(other)) return AGX_ERR_BAD_ARGUMENT;
+    return partial_overlap(addr(base), addr(other), plan->n, plan->num_primes, fl.batch, fl.prime_stride, fl.poly_stride) ? AGX_ERR_BAD_ARGUMENT : AGX_OK;
 }
 
 static int plan_set_variant_impl(agx_ntt_plan* plan, int variant) {
@@ -452,35 +445,20 @@ int agx_ntt_debug_set_trace_buffer(void* d_buf, uint64_t bytes) {
 int agx_ntt_plan_create(agx_ntt_plan** plan, uint32_t n, uint32_t num_primes, const uint64_t* moduli,
                         const uint64_t* twiddles, const uint64_t* precons,
                         const uint64_t* inv_twiddles, const uint64_t* inv_precons) {
-    if (!plan || !moduli || !twiddles || !precons) return AGX_ERR_NULL_POINTER;
+    if (!plan) return AGX_ERR_NULL_POINTER;
     *plan = nullptr;
-    if ((inv_twiddles == nullptr) != (inv_precons == nullptr)) return AGX_ERR_NULL_POINTER;
-    int rc = check_size(n);
-    if (rc) return rc;
-    if (num_primes == 0 || num_primes > 65535) return AGX_ERR_BAD_ARGUMENT;
-    for (uint32_t k = 0; k < num_primes; ++k)
-        if ((rc = check_modulus(moduli[k], n))) return rc;
+    if (int rc = check_create_args(n, num_primes, moduli, twiddles, precons, inv_twiddles, inv_precons)) return rc;
     return guarded([&] { return build_plan(plan, n, num_primes, moduli, nullptr, twiddles, precons, inv_twiddles, inv_precons); });
 }
 
 int agx_ntt_plan_create_auto(agx_ntt_plan** plan, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi) {
     if (!plan || !moduli) return AGX_ERR_NULL_POINTER;
     *plan = nullptr;
-    int rc = check_size(n);
-    if (rc) return rc;
-    if (num_primes == 0 || num_primes > 65535) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_shape(n, num_primes)) return rc;
     return guarded([&]() -> int {
-        std::vector<uint64_t> roots(num_primes), tw((size_t)num_primes * n), pre(tw.size()), itw(tw.size()), ipre(tw.size());
-        for (uint32_t k = 0; k < num_primes; ++k) {
-            const uint64_t q = moduli[k];
-            if (int mrc = check_modulus(q, n)) return mrc;
-            if (!is_prime_u64(q)) return AGX_ERR_BAD_MODULUS;
-            roots[k] = psi ? psi[k] : min_primitive_root_2n(q, n);
-            if (!is_primitive_root_2n(roots[k], q, n)) return AGX_ERR_BAD_ROOT;
-            power_tables_bitrev(q, roots[k], n, &tw[(size_t)k * n], &pre[(size_t)k * n]);
-            power_tables_bitrev(q, inv_mod(roots[k], q), n, &itw[(size_t)k * n], &ipre[(size_t)k * n]);
-        }
-        return build_plan(plan, n, num_primes, moduli, roots.data(), tw.data(), pre.data(), itw.data(), ipre.data());
+        plan_image img;
+        if (int rc = prepare_auto_image(img, n, num_primes, moduli, psi)) return rc;
+        return instantiate_plan(plan, img);
     });
 }
 
@@ -517,36 +495,28 @@ int agx_ntt_plan_get_modulus(const agx_ntt_plan* plan, uint32_t prime_index, uin
     return AGX_OK;
 }
 
-static int forward_common(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch,
-                          int64_t prime_stride, int64_t poly_stride, bool lazy_out, void* stream) {
-    int rc = check_call(plan, d_in, d_out, batch, prime_stride, poly_stride);
-    if (rc) return rc;
-    if (batch == 0) return AGX_OK;
-    frame_layout fl{batch, prime_stride, poly_stride};
-    fl.lazy_out = lazy_out;
-    const route& r = forward_route(plan, batch);
+static int forward_common(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, const frame_layout& fl, void* stream) {
+    if (!plan || !d_in || !d_out) return AGX_ERR_NULL_POINTER;
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_in, fl)) || (rc = check_pair(plan, d_in, d_out, fl))) return rc;      // out may BE in, never straddle it
+    if (fl.batch == 0) return AGX_OK;
+    const route& r = forward_route(plan, fl.batch);
     hipStream_t s = static_cast<hipStream_t>(stream);
     AGX_HIP(r.rb ? r.rb->launch(r, d_in, d_out, fl, s) : launch_forward_radix2(r, d_in, d_out, fl, s));
     return AGX_OK;
 }
 
-int agx_ntt_forward_strided(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch,
-                            int64_t prime_stride, int64_t poly_stride, void* stream) {
-    return forward_common(plan, d_in, d_out, batch, prime_stride, poly_stride, false, stream);
+int agx_ntt_forward_strided(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, int64_t prime_stride, int64_t poly_stride, void* stream) {
+    return forward_common(plan, d_in, d_out, frame_layout{batch, prime_stride, poly_stride}, stream);
 }
 
-int agx_ntt_forward_lazy(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, void* stream) {
-    if (!plan) return AGX_ERR_NULL_POINTER;
-    return forward_common(plan, d_in, d_out, batch, (int64_t)(batch * plan->n), (int64_t)plan->n, true, stream);
-}
-
-int agx_ntt_inverse_strided(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch,
-                            int64_t prime_stride, int64_t poly_stride, void* stream) {
-    int rc = check_call(plan, d_in, d_out, batch, prime_stride, poly_stride);
-    if (rc) return rc;
+int agx_ntt_inverse_strided(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, int64_t prime_stride, int64_t poly_stride, void* stream) {
+    if (!plan || !d_in || !d_out) return AGX_ERR_NULL_POINTER;
+    const frame_layout fl{batch, prime_stride, poly_stride};
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_in, fl)) || (rc = check_pair(plan, d_in, d_out, fl))) return rc;
     if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
     if (batch == 0) return AGX_OK;
-    const frame_layout fl{batch, prime_stride, poly_stride};
     const route& r = plan->routes.inverse;
     hipStream_t s = static_cast<hipStream_t>(stream);
     AGX_HIP(r.rb ? r.rb->launch_inv(r, d_in, nullptr, d_out, fl, s) : launch_inverse_radix2(r, d_in, d_out, fl, s));
@@ -555,19 +525,27 @@ int agx_ntt_inverse_strided(const agx_ntt_plan* plan, const uint64_t* d_in, uint
 
 int agx_ntt_forward(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, void* stream) {
     if (!plan) return AGX_ERR_NULL_POINTER;
-    return agx_ntt_forward_strided(plan, d_in, d_out, batch, (int64_t)(batch * plan->n), (int64_t)plan->n, stream);
+    return forward_common(plan, d_in, d_out, dense(plan, batch), stream);
+}
+
+int agx_ntt_forward_lazy(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, void* stream) {
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    frame_layout fl = dense(plan, batch);
+    fl.lazy_out = true;
+    return forward_common(plan, d_in, d_out, fl, stream);
 }
 
 int agx_ntt_inverse(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, void* stream) {
     if (!plan) return AGX_ERR_NULL_POINTER;
-    return agx_ntt_inverse_strided(plan, d_in, d_out, batch, (int64_t)(batch * plan->n), (int64_t)plan->n, stream);
+    const frame_layout fl = dense(plan, batch);
+    return agx_ntt_inverse_strided(plan, d_in, d_out, batch, fl.prime_stride, fl.poly_stride, stream);
 }
 
 int agx_ntt_pointwise(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, void* stream) {
     if (!plan || !d_a || !d_b || !d_c) return AGX_ERR_NULL_POINTER;
-    int rc = check_call(plan, d_a, d_c, batch, (int64_t)(batch * plan->n), (int64_t)plan->n);
-    if (rc) return rc;
-    if ((rc = check_call(plan, d_b, d_c, batch, (int64_t)(batch * plan->n), (int64_t)plan->n))) return rc;
+    const frame_layout fl = dense(plan, batch);
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_c, fl)) || (rc = check_pair(plan, d_c, d_a, fl)) || (rc = check_pair(plan, d_c, d_b, fl))) return rc;
     if (batch == 0) return AGX_OK;
     AGX_HIP(launch_pointwise(plan->routes.forward, d_a, d_b, d_c, batch, static_cast<hipStream_t>(stream)));
     return AGX_OK;
@@ -576,12 +554,11 @@ int agx_ntt_pointwise(const agx_ntt_plan* plan, const uint64_t* d_a, const uint6
 int agx_ntt_polymul(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c,
                     uint64_t* d_scratch, uint64_t batch, void* stream) {
     if (!plan || !d_a || !d_b || !d_c) return AGX_ERR_NULL_POINTER;
-    int rc = check_call(plan, d_a, d_c, batch, (int64_t)(batch * plan->n), (int64_t)plan->n);
-    if (rc) return rc;
-    if ((rc = check_call(plan, d_b, d_c, batch, (int64_t)(batch * plan->n), (int64_t)plan->n))) return rc;      // c may BE a or b, never straddle them
+    const frame_layout fl = dense(plan, batch);
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_c, fl)) || (rc = check_pair(plan, d_c, d_a, fl)) || (rc = check_pair(plan, d_c, d_b, fl))) return rc;      // c may BE a or b, never straddle them
     if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
     if (batch == 0) return AGX_OK;
-    const frame_layout fl{batch, (int64_t)(batch * plan->n), (int64_t)plan->n};
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (const route& r = plan->routes.polymul; r.rb) {
         // one kernel: both forward transforms, the product and the inverse stay on chip (24n bytes of HBM traffic);
@@ -590,9 +567,9 @@ int agx_ntt_polymul(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_
         return AGX_OK;
     }
     if (!d_scratch) return AGX_ERR_NULL_POINTER;
-    for (const uint64_t* other : {d_a, d_b, (const uint64_t*)d_c})      // the scratch frames must not touch a, b or c anywhere
-        if (d_scratch == other || partial_overlap(other, d_scratch, plan->n, plan->num_primes, batch, (int64_t)(batch * plan->n), (int64_t)plan->n))
-            return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t words = dense_words(plan, batch);
+    auto scratch_touches = [&](const uint64_t* p) { return ranges_touch(addr(d_scratch), words, addr(p), words); };
+    if (scratch_touches(d_a) || scratch_touches(d_b) || scratch_touches(d_c)) return AGX_ERR_BAD_ARGUMENT;      // not anywhere
     // scratch <- NTT(a); c <- NTT(b) (a is dead by now, so c may alias it); c <- INTT(c o scratch).
     // With the register-blocked inverse the product is taken while it loads (no pointwise pass) and
     // the forward results may stay lazily reduced.
@@ -611,31 +588,24 @@ int agx_ntt_polymul(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_
 int agx_ntt_polymul_ntt(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c,
                         uint64_t batch, uint64_t bhat_batch, void* stream) {
     if (!plan || !d_a || !d_bhat || !d_c) return AGX_ERR_NULL_POINTER;
-    const int64_t n = (int64_t)plan->n;
-    int rc = check_call(plan, d_a, d_c, batch, (int64_t)batch * n, n);      // c may BE a, never straddle it
-    if (rc) return rc;
+    const frame_layout fl = dense(plan, batch);
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_a, fl)) || (rc = check_pair(plan, d_a, d_c, fl))) return rc;      // c may BE a, never straddle it
     if (bhat_batch != batch && bhat_batch != 1) return AGX_ERR_BAD_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_bhat) & 7u) != 0) return AGX_ERR_BAD_ARGUMENT;
-    {
-        // both sets are dense, so each is one range of words: c's [prime][batch][n] must not touch bhat's [prime][bhat_batch][n] anywhere
-        // (bhat is read by every workgroup of its prime while others already write c)
-        const uintptr_t c0 = reinterpret_cast<uintptr_t>(d_c), b0 = reinterpret_cast<uintptr_t>(d_bhat);
-        const uintptr_t c_bytes = (uintptr_t)plan->num_primes * batch * plan->n * sizeof(uint64_t);
-        const uintptr_t b_bytes = (uintptr_t)plan->num_primes * bhat_batch * plan->n * sizeof(uint64_t);
-        if (c0 < b0 + b_bytes && b0 < c0 + c_bytes) return AGX_ERR_BAD_ARGUMENT;
-    }
+    if (!aligned8(d_bhat)) return AGX_ERR_BAD_ARGUMENT;
+    // c's [prime][batch][n] must not touch bhat's [prime][bhat_batch][n] anywhere: every workgroup of a prime reads bhat while others already write c
+    if (ranges_touch(addr(d_c), dense_words(plan, batch), addr(d_bhat), dense_words(plan, bhat_batch))) return AGX_ERR_BAD_ARGUMENT;
     if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
     if (batch == 0) return AGX_OK;
-    const int64_t bhat_prime_stride = (int64_t)bhat_batch * n, bhat_poly_stride = bhat_batch == 1 ? 0 : n;
+    const int64_t n = fl.poly_stride, bhat_prime_stride = (int64_t)bhat_batch * n, bhat_poly_stride = bhat_batch == 1 ? 0 : n;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (const route& r = plan->routes.polymul_ntt; r.rb) {
         // one kernel: the forward transform, the product with bhat as it streams in and the inverse stay on chip
-        const frame_layout fl{batch, (int64_t)batch * n, n};
         AGX_HIP(r.rb->launch_mulhat(r, d_a, d_bhat, d_c, fl, bhat_prime_stride, bhat_poly_stride, s));
         return AGX_OK;
     }
     // generic path, no scratch: c <- NTT(a) (lazy: the product reduces its operands); c <- c o bhat in place; c <- INTT(c)
-    if ((rc = forward_common(plan, d_a, d_c, batch, (int64_t)batch * n, n, true, stream))) return rc;
+    if ((rc = agx_ntt_forward_lazy(plan, d_a, d_c, batch, stream))) return rc;
     AGX_HIP(launch_pointwise_bhat(plan->routes.forward, d_c, d_bhat, batch, bhat_prime_stride, bhat_poly_stride, s));
     return agx_ntt_inverse(plan, d_c, d_c, batch, stream);
 }
@@ -644,65 +614,49 @@ int agx_ntt_rescale(const agx_ntt_plan* plan, const uint64_t* d_x, uint64_t* d_o
     if (!plan || !d_x || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
     const uint32_t P = plan->num_primes;
     if (P < 2 || (mode != AGX_RESCALE_FLOOR && mode != AGX_RESCALE_ROUND)) return AGX_ERR_BAD_ARGUMENT;
-    const int64_t n = (int64_t)plan->n, slab = (int64_t)batch * n;
-    // x as the whole plan's frame set against itself (device, grid limit, alignment), then out against slabs 0 .. P-2 of x: the same frames or disjoint ones
-    int rc = check_call(plan, d_x, d_x, batch, slab, n);
-    if (rc) return rc;
-    if ((reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(d_scratch)) & 7u) return AGX_ERR_BAD_ARGUMENT;
-    if (partial_overlap(d_x, d_out, plan->n, P - 1, batch, slab, n)) return AGX_ERR_BAD_ARGUMENT;
-    {
-        // every set is dense, so each is one range of words.  The scratch may BE x's last slab (the caller gives that slab up); otherwise it
-        // touches nothing of x, and never out or slabs 0 .. P-2 of x, which P-1 workgroups per frame read while others already write
-        const uintptr_t bytes = (uintptr_t)slab * sizeof(uint64_t), head = (uintptr_t)(P - 1) * bytes;
-        const uintptr_t x0 = reinterpret_cast<uintptr_t>(d_x), o0 = reinterpret_cast<uintptr_t>(d_out), s0 = reinterpret_cast<uintptr_t>(d_scratch);
-        auto touch = [](uintptr_t a, uintptr_t a_bytes, uintptr_t b, uintptr_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; };
-        if (touch(s0, bytes, o0, head) || touch(s0, bytes, x0, head)) return AGX_ERR_BAD_ARGUMENT;
-        if (s0 != x0 + head && touch(s0, bytes, x0 + head, bytes)) return AGX_ERR_BAD_ARGUMENT;
-        if (d_out != d_x && touch(o0, head, x0 + head, bytes)) return AGX_ERR_BAD_ARGUMENT;      // out over the last slab, which the first launch reads
-    }
+    const frame_layout fl = dense(plan, batch);
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_x, fl))) return rc;      // x: all P slabs
+    if (!aligned8(d_out) || !aligned8(d_scratch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t slab = (uint64_t)fl.prime_stride, head = (P - 1) * slab;
+    const uintptr_t x = addr(d_x), x_last = x + 8 * head, out = addr(d_out), scratch = addr(d_scratch);      // dense sets, one range each: x is P slabs, out P-1, the scratch one
+    if (out != x && ranges_touch(out, head, x, head + slab)) return AGX_ERR_BAD_ARGUMENT;      // out IS slabs 0 .. P-2 of x (in place) or touches nothing of x, the last slab included: the first launch reads it
+    if (ranges_touch(scratch, slab, out, head) || ranges_touch(scratch, slab, x, head)) return AGX_ERR_BAD_ARGUMENT;      // the scratch never touches out or slabs 0 .. P-2 of x: P-1 workgroups per frame read it while others already write
+    if (scratch != x_last && ranges_touch(scratch, slab, x_last, slab)) return AGX_ERR_BAD_ARGUMENT;      // the scratch IS the last slab of x (the caller gives that slab up) or does not touch it
     if (!plan->rescale_legal) return AGX_ERR_BAD_MODULUS;      // some q_i shares a factor with (distinct primes: equals) the last modulus
     if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
     if (batch == 0) return AGX_OK;
     const bool round = mode == AGX_RESCALE_ROUND;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const frame_layout fl{batch, slab, n};
-    const uint64_t* x_last = d_x + (size_t)(P - 1) * (size_t)slab;
     // scratch <- INTT_L(x_L), coefficients in [0, q_L): the plan's inverse on the view of prime P-1
     const route last = prime_range(plan->routes.inverse, P - 1, P);
-    auto inverse_on = [&](const route& r, const uint64_t* in, uint64_t* out) {
-        return r.rb ? r.rb->launch_inv(r, in, nullptr, out, fl, s) : launch_inverse_radix2(r, in, out, fl, s);
+    auto inverse_on = [&](const route& r, const uint64_t* in, uint64_t* out_) {
+        return r.rb ? r.rb->launch_inv(r, in, nullptr, out_, fl, s) : launch_inverse_radix2(r, in, out_, fl, s);
     };
     if (const route& r = plan->routes.rescale; r.rb) {
         // two launches: the lift, the forward transform and (x_i - .) q_L^-1 stay on chip; a wave reads its words of x_i before it writes them
-        AGX_HIP(inverse_on(last, x_last, d_scratch));
+        AGX_HIP(inverse_on(last, d_x + head, d_scratch));
         AGX_HIP(r.rb->launch_rescale(prime_range(r, 0, P - 1), d_x, d_scratch, d_out, fl, round, s));
         return AGX_OK;
     }
     // generic route, no more scratch: out <- INTT(x_0 .. x_{P-2}); scratch <- INTT_L(x_L); out <- (out - lift(scratch)) q_L^-1 in the
     // coefficient domain; out <- NTT(out)
     AGX_HIP(inverse_on(prime_range(plan->routes.inverse, 0, P - 1), d_x, d_out));
-    AGX_HIP(inverse_on(last, x_last, d_scratch));
-    const route head = prime_range(forward_route(plan, batch), 0, P - 1);
-    AGX_HIP(launch_rescale_coeff(head, d_out, d_scratch, batch, round, s));
-    AGX_HIP(head.rb ? head.rb->launch(head, d_out, d_out, fl, s) : launch_forward_radix2(head, d_out, d_out, fl, s));
+    AGX_HIP(inverse_on(last, d_x + head, d_scratch));
+    const route head_route = prime_range(forward_route(plan, batch), 0, P - 1);
+    AGX_HIP(launch_rescale_coeff(head_route, d_out, d_scratch, batch, round, s));
+    AGX_HIP(head_route.rb ? head_route.rb->launch(head_route, d_out, d_out, fl, s) : launch_forward_radix2(head_route, d_out, d_out, fl, s));
     return AGX_OK;
 }
 
 int agx_ntt_automorphism(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t galois_elt, int form, void* stream) {
     if (!plan || !d_in || !d_out) return AGX_ERR_NULL_POINTER;
-    const int64_t n = (int64_t)plan->n;
-    // in as a frame set against itself (device, grid limit, alignment); out is judged below: it may not even BE in
-    int rc = check_call(plan, d_in, d_in, batch, (int64_t)batch * n, n);
-    if (rc) return rc;
-    if ((reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return AGX_ERR_BAD_ARGUMENT;
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_in, dense(plan, batch)))) return rc;
+    if (!aligned8(d_out)) return AGX_ERR_BAD_ARGUMENT;
     if (!(galois_elt & 1u) || galois_elt >= 2u * plan->n || (form != AGX_FORM_COEFF && form != AGX_FORM_NTT)) return AGX_ERR_BAD_ARGUMENT;
-    {
-        // both sets are dense, so each is one range of words; a frame is permuted across its whole length and workgroups run in any
-        // order, so the ranges may not touch anywhere
-        const uintptr_t i0 = reinterpret_cast<uintptr_t>(d_in), o0 = reinterpret_cast<uintptr_t>(d_out);
-        const uintptr_t bytes = (uintptr_t)plan->num_primes * batch * plan->n * sizeof(uint64_t);
-        if (d_in == d_out || (o0 < i0 + bytes && i0 < o0 + bytes)) return AGX_ERR_BAD_ARGUMENT;
-    }
+    // out of place only, equal pointers included: a frame is permuted across its whole length and workgroups run in any order
+    if (d_out == d_in || ranges_touch(addr(d_in), dense_words(plan, batch), addr(d_out), dense_words(plan, batch))) return AGX_ERR_BAD_ARGUMENT;
     if (batch == 0) return AGX_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const route& r = plan->routes.forward;      // the per-prime constants only: no table, no plan state
@@ -712,8 +666,8 @@ int agx_ntt_automorphism(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_
 
 int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly, uint64_t seed, void* stream) {
     if (!plan || !d_out) return AGX_ERR_NULL_POINTER;
-    int rc = check_call(plan, d_out, d_out, batch, (int64_t)(batch * plan->n), (int64_t)plan->n);
-    if (rc) return rc;
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_out, dense(plan, batch)))) return rc;
     if (batch == 0) return AGX_OK;
     AGX_HIP(launch_fill(plan->routes.forward, d_out, batch, first_poly, seed, static_cast<hipStream_t>(stream)));
     return AGX_OK;

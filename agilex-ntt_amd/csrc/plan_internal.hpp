@@ -14,6 +14,7 @@
 
 #include "ntt_kernels.hpp"
 
+constexpr int kMaxDevices = 64;          // size of every per-device table (kernel attributes set once, staging pool, one-shot plans); devices past it work uncached
 constexpr uint32_t kTicketSlots = 64;    // distinct streams of one plan that may run ticket-drawing kernels; further streams get the stateless kernels
 
 namespace agx {
@@ -152,12 +153,18 @@ struct plan_image {
 // arguments as validated by agx_ntt_plan_create*: moduli legal for n, tables [num_primes][n]; psi / itw / ipre may be null
 void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
                         const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre);
+// the same for agx_ntt_{plan,group}_create_auto, from (moduli, psi or null: the least roots): judges primes and roots, generates the tables
+int prepare_auto_image(plan_image& img, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi);
 // a plan on the CURRENT device from a prepared image
 int instantiate_plan(agx_ntt_plan** out, const plan_image& img);
 void free_plan(agx_ntt_plan* p);
-// argument checks and the plan construction the one-shot calls of agx_host.cpp share with agx_ntt_plan_create
+// argument checks and the plan construction that agx_ntt_plan_create shares with the groups and the one-shot calls of agx_host.cpp
 int check_size(uint32_t n);
 int check_modulus(uint64_t q, uint32_t n);
+int check_shape(uint32_t n, uint32_t num_primes);      // check_size, then 1 .. 65535 primes
+int check_plan(const agx_ntt_plan* plan);               // the plan exists and the current device is its device
+// of agx_ntt_{plan,group}_create (one-shot: one modulus, no inverse tables): the pointer rules, check_shape, check_modulus of every modulus
+int check_create_args(uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre);
 int build_plan(agx_ntt_plan** out, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
                const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre);
 

@@ -41,7 +41,7 @@ typedef enum agx_status {
     AGX_ERR_BAD_SIZE = 2,       /* n is not a power of two in [AGX_NTT_MIN_N, AGX_NTT_MAX_N] */
     AGX_ERR_BAD_MODULUS = 3,    /* q >= 2^62, q even, q != 1 (mod 2n) or (plan_create_auto) q composite; rescale: q_i == q_last */
     AGX_ERR_BAD_ROOT = 4,       /* psi is not a primitive 2n-th root of unity mod q           */
-    AGX_ERR_BAD_ARGUMENT = 5,   /* zero primes, negative stride, overlapping in/out, an even or too large Galois element, an unknown form or mode, ... */
+    AGX_ERR_BAD_ARGUMENT = 5,   /* zero primes, negative stride, a layout extent past 2^60 words, overlapping in/out, an even or too large Galois element, an unknown form or mode, ... */
     AGX_ERR_NO_DEVICE = 6,      /* no usable HIP device                                       */
     AGX_ERR_HIP = 7,            /* a HIP runtime call failed (agx_ntt_last_hip_error)         */
     AGX_ERR_ALLOC = 8,          /* host or device allocation failed                           */
@@ -144,7 +144,9 @@ AGX_API int agx_ntt_plan_get_modulus(const agx_ntt_plan* plan, uint32_t prime_in
 /* own frames touch one another (two distinct (p, b) less than n elements      */
 /* apart: prime_stride = 0 with two primes, prime_stride = poly_stride = n     */
 /* with two polynomials, ...) returns AGX_ERR_BAD_ARGUMENT too: two workgroups */
-/* would transform the same words under different moduli.  Asynchronous on    */
+/* would transform the same words under different moduli.  So does a layout    */
+/* whose extent (P-1)*prime_stride + (B-1)*poly_stride + n is more than 2^60   */
+/* words: its byte offsets would not fit 64 bits.  Asynchronous on             */
 /* `stream`; nothing is allocated or synchronised inside, so the calls can be  */
 /* captured into a hipGraph (kernels that hand out frames through a counter    */
 /* switch to a stateless form while the stream is capturing).                   */

@@ -289,3 +289,34 @@ def test_overlapping_layouts_are_rejected(agx, orc, dev, n):
         plan.close()
     wrong = {k: v for k, v in wrong.items() if v}
     assert not wrong, f"{len(wrong)} layouts handled wrongly:\n" + "\n".join(f"{k}: {'; '.join(v[:4])}" for k, v in list(wrong.items())[:60])
+
+
+@pytest.mark.parametrize("n", [32, 4096])
+def test_layouts_that_do_not_fit_are_refused(agx, orc, dev, n):
+    """forward_strided / inverse_strided with a stride of 2^61 or 2^61 + n words between two polynomials (one prime, batch 2) or between two
+    primes (two primes, batch 1): the extent is past 2^60 words, byte offsets no longer fit 64 bits, so the call is refused with status 5
+    before anything is launched and every word stays as it was.  2^61 words are 2^64 bytes: the second frame of a build that wrongly
+    accepted such a call would wrap onto word 0 or n of the 2n-word payload, inside the buffer (n guard words on both sides)."""
+    torch = dev.torch
+    wrong = []
+    for primes in (1, 2):
+        plan = agx.Plan(n, [orc.find_prime(60, n, k) for k in range(primes)])
+        x = np.random.default_rng(n + primes).integers(0, min(plan.moduli), size=4 * n, dtype=np.uint64)
+        keep, d = dev.to_device(x), dev.to_device(x)
+        base = d.data_ptr() + 8 * n
+        for stride in ((1 << 61), (1 << 61) + n):
+            batch, ps, qs = (2, 2 * n, stride) if primes == 1 else (1, stride, n)
+            for op in ("forward", "inverse"):
+                try:
+                    getattr(plan, op + "_strided")(base, base, batch, ps, qs, dev.stream)
+                    status = 0
+                except agx.AgxError as e:
+                    status = e.status
+                dev.sync()
+                if status != 5:
+                    wrong.append(f"{op} P={primes} B={batch} prime_stride={ps} poly_stride={qs}: status {status}, want 5")
+                if not torch.equal(d, keep):
+                    wrong.append(f"{op} P={primes} B={batch} prime_stride={ps} poly_stride={qs}: memory changed")
+                    d.copy_(keep)
+        plan.close()
+    assert not wrong, "\n".join(wrong)
