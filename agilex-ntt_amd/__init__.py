@@ -21,6 +21,7 @@ VARIANT_AUTO, VARIANT_LDS_RADIX2, VARIANT_REGBLOCK = 0, 1, 2
 VARIANT_REGBLOCK_BASE = 256  # + registry index: A/B measurements only
 RESCALE_FLOOR, RESCALE_ROUND = 0, 1
 FORM_COEFF, FORM_NTT = 0, 1
+BASIS_MAX_SRC = 16
 
 _u64 = ctypes.c_uint64
 _u32 = ctypes.c_uint32
@@ -55,6 +56,10 @@ ABI = {
     "agx_ntt_polymul_ntt": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp]),
     "agx_ntt_rescale": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_automorphism": (_int, [_vp, _vp, _vp, _u64, _u32, _int, _vp]),
+    "agx_ntt_basis_create": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32]),
+    "agx_ntt_basis_destroy": (_int, [_vp]),
+    "agx_ntt_basis_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_int)]),
+    "agx_ntt_basis_extend": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
@@ -320,6 +325,10 @@ class Plan:
         FORM_COEFF moves and negates coefficients (inputs in [0,4q), outputs in [0,q)); galois_elt odd, below 2n"""
         _check(lib().agx_ntt_automorphism(self._h, d_in, d_out, batch, galois_elt, form, stream), "automorphism")
 
+    def basis(self, src_first, src_count, dst_first, dst_count):
+        """Basis(self, ...): the fast base conversion from primes [src_first, src_first + src_count) to [dst_first, dst_first + dst_count)"""
+        return Basis(self, src_first, src_count, dst_first, dst_count)
+
     def fill_synthetic(self, d_out, batch, first_poly=0, seed=42, stream=0):
         _check(lib().agx_ntt_fill_synthetic(self._h, d_out, batch, first_poly, seed, stream), "fill_synthetic")
 
@@ -338,6 +347,42 @@ class Plan:
     def close(self):
         if self._h:
             lib().agx_ntt_plan_destroy(self._h)
+            self._h = _vp(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Basis:
+    """The constants of a fast RNS base conversion (agx_ntt_basis_*) from the plan's primes [src_first, src_first + src_count) to
+    [dst_first, dst_first + dst_count).  `plan` is a Plan, or a raw plan handle (a DeviceGroup shard's: one basis per shard); it must
+    outlive the basis, and its device must be current here and at every call."""
+
+    def __init__(self, plan, src_first, src_count, dst_first, dst_count):
+        self.plan = plan      # keeps a Plan alive
+        self._h = _vp(None)
+        handle = plan._h if isinstance(plan, Plan) else plan
+        _check(lib().agx_ntt_basis_create(ctypes.byref(self._h), handle, src_first, src_count, dst_first, dst_count), "basis_create")
+
+    def info(self):
+        """(src_first, src_count, dst_first, dst_count, launches_ntt_form): the ranges, and the kernel launches a FORM_NTT call takes
+        under the plan's current variant"""
+        v = [_u32(0) for _ in range(4)]
+        launches = _int(0)
+        _check(lib().agx_ntt_basis_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(launches)), "basis_info")
+        return tuple(x.value for x in v) + (launches.value,)
+
+    def extend(self, d_x, d_out, batch, form=FORM_NTT, stream=0):
+        """d_x [src_count][batch][n], coefficient form, values in [0,4q) -> d_out [dst_count][batch][n]: sum_i y_i D_i mod q_j (y_i = x_i D_i^-1
+        mod q_i; no correction term), as coefficients (FORM_COEFF) or transformed as Plan.forward writes it (FORM_NTT); out of place"""
+        _check(lib().agx_ntt_basis_extend(self._h, d_x, d_out, batch, form, stream), "basis_extend")
+
+    def close(self):
+        if self._h:
+            lib().agx_ntt_basis_destroy(self._h)
             self._h = _vp(None)
 
     def __del__(self):

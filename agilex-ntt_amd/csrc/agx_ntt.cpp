@@ -178,6 +178,7 @@ static void resolve_routes(agx_ntt_plan* p) {
     // the fused second launch pairs with whatever `inverse` is; everything else (n <= 512, the 32-bit families, radix-2) is generic: the
     // call then runs `inverse`, the coefficient-domain step and `forward` on views of these routes
     r.rescale = inv && e->launch_rescale ? main : generic;
+    r.extend = e && e->launch_extend ? main : generic;      // forward tables only
 }
 
 static const route& forward_route(const agx_ntt_plan* p, uint64_t batch) {
@@ -661,6 +662,93 @@ int agx_ntt_automorphism(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_
     hipStream_t s = static_cast<hipStream_t>(stream);
     const route& r = plan->routes.forward;      // the per-prime constants only: no table, no plan state
     AGX_HIP(form == AGX_FORM_NTT ? launch_automorphism_ntt(r, d_in, d_out, batch, galois_elt, s) : launch_automorphism_coeff(r, d_in, d_out, batch, galois_elt, s));
+    return AGX_OK;
+}
+
+int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    *basis = nullptr;
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes;
+    auto in_plan = [&](uint32_t first, uint32_t count) { return count >= 1 && count <= P && first <= P - count; };
+    if (!in_plan(src_first, src_count) || !in_plan(dst_first, dst_count) || src_count > AGX_BASIS_MAX_SRC) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    return guarded([&]() -> int {
+        const uint32_t S = src_count, T = dst_count;
+        std::vector<uint64_t> dinv(S), dinv_p(S), mat((size_t)T * S), mat_p((size_t)T * S);
+        // D_i must be invertible modulo q_i: two equal source moduli have no conversion
+        if (!basis_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, dinv.data(), dinv_p.data(), mat.data(), mat_p.data())) return AGX_ERR_BAD_MODULUS;
+        std::vector<ulonglong2> dinv_pairs(S), mat_pairs((size_t)T * S);
+        for (size_t k = 0; k < dinv_pairs.size(); ++k) dinv_pairs[k] = make_ulonglong2(dinv[k], dinv_p[k]);
+        for (size_t k = 0; k < mat_pairs.size(); ++k) mat_pairs[k] = make_ulonglong2(mat[k], mat_p[k]);
+        std::unique_ptr<agx_ntt_basis> b(new (std::nothrow) agx_ntt_basis);
+        if (!b) return AGX_ERR_ALLOC;
+        b->plan = plan;
+        b->src_first = src_first, b->src_count = S, b->dst_first = dst_first, b->dst_count = T;
+        if (int rc = b->d_dinv.upload(dinv_pairs)) return rc;
+        if (int rc = b->d_mat.upload(mat_pairs)) return rc;
+        *basis = b.release();
+        return AGX_OK;
+    });
+}
+
+int agx_ntt_basis_destroy(agx_ntt_basis* basis) {
+    delete basis;      // the device memory goes with its owners
+    return AGX_OK;
+}
+
+// Does an AGX_FORM_NTT call of this basis take the fused kernel?  The plan's entry must carry it, and the shape must be one at which it was measured
+// ahead of the unfused pair (profiles/r08_basis_extend.md).  Every workgroup of a frame forms the y_i again -- 2 S Shoup products per output word
+// beside the transform's log2(n) / 2 -- so the fused kernel's arithmetic grows with S while the pair's conversion stays bound by its traffic:
+//   S = 1: fused at every size (0.83 ... 0.92 of the pair's time);
+//   S = 2: fused (0.96 ... 0.99) except at n = 4096 and 16384, where it measured 1.02 and 1.01 of the pair;
+//   S >= 3: the pair (S = 4, 8, 16 measured: the fused kernel takes 1.21 ... 1.49 of its time; S = 3 not measured, taken with them).
+static bool extend_is_fused(const agx_ntt_basis* b) {
+    const agx_ntt_plan* p = b->plan;
+    if (!p->routes.extend.rb) return false;
+    return b->src_count == 1 || (b->src_count == 2 && p->log_n != 12 && p->log_n != 14);
+}
+
+// kernel launches of one forward call of the plan: a registry entry is one launch whatever the batch (forward and forward_large alike: the second
+// exists only beside a first with an entry), the radix-2 kernels say themselves how many they take
+static int forward_launches(const agx_ntt_plan* p) { return forward_route(p, 1).rb ? 1 : forward_radix2_launches(p->log_n); }
+
+int agx_ntt_basis_info(const agx_ntt_basis* basis, uint32_t* src_first, uint32_t* src_count, uint32_t* dst_first, uint32_t* dst_count, int* launches_ntt_form) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    if (src_first) *src_first = basis->src_first;
+    if (src_count) *src_count = basis->src_count;
+    if (dst_first) *dst_first = basis->dst_first;
+    if (dst_count) *dst_count = basis->dst_count;
+    if (launches_ntt_form) *launches_ntt_form = extend_is_fused(basis) ? 1 : 1 + forward_launches(basis->plan);
+    return AGX_OK;
+}
+
+int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    if (!basis || !d_x || !d_out) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = basis->plan;
+    if (out_form != AGX_FORM_COEFF && out_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    const uint32_t S = basis->src_count, T = basis->dst_count;
+    if (!aligned8(d_x) || !aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of x ([S][batch][n]) and of out ([T][batch][n]) alike
+    if (!layout_fits(plan->n, S, batch, fl.prime_stride, fl.poly_stride) || !layout_fits(plan->n, T, batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;
+    // out of place only: every workgroup of a frame reads all S source frames while others already write their targets
+    if (ranges_touch(addr(d_x), S * batch * plan->n, addr(d_out), T * batch * plan->n)) return AGX_ERR_BAD_ARGUMENT;
+    const basis_view bv{basis->d_dinv, basis->d_mat, basis->src_first, S, basis->dst_first, T};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const route& r = plan->routes.extend; out_form == AGX_FORM_NTT && extend_is_fused(basis)) {
+        // one kernel: the conversion and the target prime's forward transform stay on chip; T workgroups per group of rb->ppb frames
+        if ((uint64_t)T * ((batch + r.rb->ppb - 1) / r.rb->ppb) > 0x7fffffffull) return AGX_ERR_BAD_ARGUMENT;      // grid limit
+        if (batch == 0) return AGX_OK;
+        AGX_HIP(r.rb->launch_extend(r, bv, d_x, d_out, fl, s));
+        return AGX_OK;
+    }
+    if (batch == 0) return AGX_OK;
+    AGX_HIP(launch_basis_coeff(plan->routes.forward, bv, d_x, d_out, batch, s));
+    if (out_form == AGX_FORM_NTT) {      // the plan's forward on the view of the target primes, in place
+        const route fr = prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T);
+        AGX_HIP(fr.rb ? fr.rb->launch(fr, d_out, d_out, fl, s) : launch_forward_radix2(fr, d_out, d_out, fl, s));
+    }
     return AGX_OK;
 }
 

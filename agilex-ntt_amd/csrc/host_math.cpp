@@ -103,4 +103,24 @@ void power_tables_bitrev(uint64_t q, uint64_t base, uint32_t n, uint64_t* tw, ui
     }
 }
 
+bool basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t* dinv, uint64_t* dinv_p, uint64_t* mat, uint64_t* mat_p) {
+    // D_i mod m, one factor at a time: S (S - 1) products per modulus, S <= 16
+    auto d_mod = [&](uint32_t i, uint64_t m) {
+        uint64_t r = 1 % m;
+        for (uint32_t k = 0; k < S; ++k)
+            if (k != i) r = mul_mod(r, src[k] % m, m);
+        return r;
+    };
+    for (uint32_t i = 0; i < S; ++i) {
+        if (!inv_mod_euclid(d_mod(i, src[i]), src[i], &dinv[i])) return false;
+        dinv_p[i] = shoup_quotient(dinv[i], src[i]);
+    }
+    for (uint32_t j = 0; j < T; ++j)
+        for (uint32_t i = 0; i < S; ++i) {
+            mat[(std::size_t)j * S + i] = d_mod(i, dst[j]);
+            mat_p[(std::size_t)j * S + i] = shoup_quotient(mat[(std::size_t)j * S + i], dst[j]);
+        }
+    return true;
+}
+
 }  // namespace agx

@@ -2,6 +2,7 @@
 // primitive roots and the twiddle / precomputed-quotient tables the reference expects its
 // caller to provide (include/kernel/ntt.h:35-41; src/main.cpp:49-55 ships placeholders only).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -30,5 +31,12 @@ bool is_primitive_root_2n(uint64_t psi, uint64_t q, uint32_t n);
 uint64_t shoup_quotient(uint64_t w, uint64_t q);
 // tw[j] = base^bitrev(j) mod q, pre[j] = shoup_quotient(tw[j])
 void power_tables_bitrev(uint64_t q, uint64_t base, uint32_t n, uint64_t* tw, uint64_t* pre);
+
+// The constants of a fast RNS base conversion (agx_ntt_basis_extend) from the moduli src[0 .. S) to the moduli dst[0 .. T), every modulus
+// odd, > 1 and < 2^62.  With D = prod src[i] and D_i = D / src[i]:
+//   dinv[i] = D_i^-1 mod src[i],   mat[j * S + i] = D_i mod dst[j],   dinv_p / mat_p their precomputed quotients (shoup_quotient).
+// false, nothing promised about the outputs, when some D_i is not invertible modulo src[i]: two source moduli share a factor (for primes:
+// are equal).  A target that is itself source k gets D_i mod dst[j] = 0 for i != k, so the conversion hands that residue through.
+bool basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t* dinv, uint64_t* dinv_p, uint64_t* mat, uint64_t* mat_p);
 
 }  // namespace agx

@@ -82,6 +82,19 @@ __device__ __forceinline__ uint64_t rescale_finish(uint64_t x, uint64_t z, uint6
     return csub(mul_shoup_lazy(d, w, wp, q), q);
 }
 
+// Fast RNS base conversion (agx_ntt_basis_extend), per coefficient: out_j = sum_i y_i (D_i mod q_j) mod q_j with y_i = x_i D_i^-1 mod q_i.
+// scale: a source word x (any 64-bit value: [0,4q_i) as the transforms accept it) -> y_i in [0,q_i), fully reduced -- the sum is an integer
+// formula in the y_i, so their representative matters.  {w, wp} = D_i^-1 mod q_i and its quotient.
+__device__ __forceinline__ uint64_t basis_scale(uint64_t x, uint64_t w, uint64_t wp, uint64_t qi) {
+    return csub(mul_shoup_lazy(x, w, wp, qi), qi);
+}
+// accumulate: acc in [0,2q) -> acc + y (D_i mod q_j) mod q_j in [0,2q).  y is a residue of ANOTHER modulus (any value below 2^62), which
+// mul_shoup_lazy takes to [0,2q); the sum stays below 4q < 2^64.  {c, cp} = D_i mod q_j and its quotient.  One conditional subtract per
+// term instead of a 128-bit sum and one reduction per word: half the accumulator registers, which the fused kernel needs (rb_kernels.hpp).
+__device__ __forceinline__ uint64_t basis_accumulate(uint64_t acc, uint64_t y, uint64_t c, uint64_t cp, uint64_t q, uint64_t q2) {
+    return csub(acc + mul_shoup_lazy(y, c, cp, q), q2);
+}
+
 // ---------------------------------------------------------------------------------------
 // Hand-selected instruction forms for the throughput kernels.
 //

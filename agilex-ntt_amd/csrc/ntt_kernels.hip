@@ -271,6 +271,39 @@ __global__ void automorphism_coeff_gather_kernel(const uint64_t* __restrict__ in
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// agx_ntt_basis_extend, coefficient form: fast RNS base conversion from S source primes to T target primes, dense layouts, out of place
+// ---------------------------------------------------------------------------------------
+// One thread per (frame, coefficient): it reads its S source words (slab i at x + i per_prime), forms every y_i = x_i D_i^-1 mod q_i once,
+// then walks the T targets and writes one word each: 8 (S + T) bytes per coefficient, no source word read twice.  The constants are
+// wave-uniform (scalar loads).  SMAX >= S bounds the y_i kept in registers (the loops over i are unrolled and guarded, never indexed).
+template <int SMAX>
+__global__ void basis_coeff_kernel(const uint64_t* __restrict__ x, uint64_t* __restrict__ out, const prime_consts* __restrict__ src_consts,
+                                   const prime_consts* __restrict__ dst_consts, const ulonglong2* __restrict__ dinv, const ulonglong2* __restrict__ mat,
+                                   uint32_t S, uint32_t T, uint64_t per_prime) {
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t y[SMAX];
+#pragma unroll
+        for (int i = 0; i < SMAX; ++i)
+            if ((uint32_t)i < S) {
+                const ulonglong2 d = dinv[i];
+                y[i] = basis_scale(x[(uint64_t)i * per_prime + e], d.x, d.y, src_consts[i].q);
+            }
+        for (uint32_t j = 0; j < T; ++j) {
+            const uint64_t q = dst_consts[j].q, q2 = q << 1;
+            const ulonglong2* row = mat + (size_t)j * S;
+            uint64_t acc = 0;
+#pragma unroll
+            for (int i = 0; i < SMAX; ++i)
+                if ((uint32_t)i < S) {
+                    const ulonglong2 c = row[i];
+                    acc = basis_accumulate(acc, y[i], c.x, c.y, q, q2);
+                }
+            out[(uint64_t)j * per_prime + e] = csub(acc, q);
+        }
+    }
+}
+
 __device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -383,8 +416,12 @@ static unsigned radix2_threads(uint32_t nb) {
     return t;
 }
 
+static uint32_t radix2_split(uint32_t log_n) { return log_n > (uint32_t)kMaxLdsLog ? log_n - kMaxLdsLog : 0; }      // stages run from global memory
+
+int forward_radix2_launches(uint32_t log_n) { return (int)radix2_split(log_n) + 1; }
+
 hipError_t launch_forward_radix2(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    const uint32_t split = pv.log_n > (uint32_t)kMaxLdsLog ? pv.log_n - kMaxLdsLog : 0;
+    const uint32_t split = radix2_split(pv.log_n);
     const uint32_t nb_log = pv.log_n - split;
     const uint64_t* src = in;
     for (uint32_t st = 0; st < split; ++st) {
@@ -400,7 +437,7 @@ hipError_t launch_forward_radix2(const plan_view& pv, const uint64_t* in, uint64
 }
 
 hipError_t launch_inverse_radix2(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
-    const uint32_t split = pv.log_n > (uint32_t)kMaxLdsLog ? pv.log_n - kMaxLdsLog : 0;
+    const uint32_t split = radix2_split(pv.log_n);
     const uint32_t nb_log = pv.log_n - split;
     dim3 grid((unsigned)(fl.batch << split), pv.num_primes);
     hipLaunchKernelGGL(inv_radix2_lds, grid, dim3(radix2_threads(1u << nb_log)), (size_t)8 << nb_log, s, in, out, pv.consts,
@@ -453,6 +490,22 @@ hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, ui
     const uint64_t per_prime = batch << pv.log_n;
     dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
     hipLaunchKernelGGL(automorphism_coeff_gather_kernel, grid, dim3(256), 0, s, in, out, pv.consts, pv.log_n, per_prime, h);
+    return hipGetLastError();
+}
+
+hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const uint64_t* x, uint64_t* out, uint64_t batch, hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    const dim3 grid(grid_1d(per_prime, 256));
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, x, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, bv.dinv, bv.mat, bv.src_count,
+                           bv.dst_count, per_prime);
+    };
+    const uint32_t S = bv.src_count;      // at most AGX_BASIS_MAX_SRC = 16
+    if (S <= 1) go(basis_coeff_kernel<1>);
+    else if (S <= 2) go(basis_coeff_kernel<2>);
+    else if (S <= 4) go(basis_coeff_kernel<4>);
+    else if (S <= 8) go(basis_coeff_kernel<8>);
+    else go(basis_coeff_kernel<16>);
     return hipGetLastError();
 }
 

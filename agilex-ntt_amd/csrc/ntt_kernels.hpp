@@ -24,6 +24,13 @@ struct rescale_consts {
     uint64_t q_last, h;
 };
 
+// agx_ntt_basis_extend: what a basis (plan, source range, target range) keeps on the device, and its ranges.  S = src_count, T = dst_count.
+struct basis_view {
+    const ulonglong2* dinv = nullptr;   // [S] {D_i^-1 mod q_i, its precomputed quotient}, q_i the modulus of plan prime src_first + i, D_i = prod_{k != i} q_k
+    const ulonglong2* mat = nullptr;    // [T][S] {D_i mod q_j, its precomputed quotient}, q_j the modulus of plan prime dst_first + j
+    uint32_t src_first = 0, src_count = 0, dst_first = 0, dst_count = 0;
+};
+
 struct rb_entry;   // one configuration of the kernel registry (rb_registry.hpp): static storage, valid for the life of the library
 
 // device-side view of a plan
@@ -68,6 +75,7 @@ rb_selection regblock_select(uint32_t n, int config_id, int arith_level, int nar
 hipError_t kernels_init();  // one-time function attributes (large dynamic LDS)
 
 hipError_t launch_forward_radix2(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s);
+int forward_radix2_launches(uint32_t log_n);      // kernel launches of one launch_forward_radix2 call: the global stages of a frame past the LDS limit, then the LDS kernel
 hipError_t launch_inverse_radix2(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s);
 hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
 // c <- c o bhat in place on the dense [prime][batch][n] layout, bhat with strides of its own as above (the generic path of agx_ntt_polymul_ntt)
@@ -81,6 +89,10 @@ hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64
 // [0,4q), outputs in [0,q); gathered from global memory (the stride-g^-1 repeats hit L2).  One launch each.
 hipError_t launch_automorphism_ntt(const plan_view& pv, const uint64_t* in, uint64_t* out, uint64_t batch, uint32_t g, hipStream_t s);
 hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, uint64_t* out, uint64_t batch, uint32_t g, hipStream_t s);
+// agx_ntt_basis_extend in coefficient form: x dense [S][batch][n] (slab i under plan prime src_first + i, values in [0,4q_i)) -> out dense
+// [T][batch][n] (slab j under plan prime dst_first + j), out_j = sum_i y_i (D_i mod q_j) mod q_j in [0,q_j), y_i = x_i D_i^-1 mod q_i in [0,q_i).
+// pv: a view of the WHOLE plan (only its constants are read); out of place (the ranges must not touch).  One launch.
+hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const uint64_t* x, uint64_t* out, uint64_t batch, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

@@ -63,6 +63,7 @@ struct plan_routes {
     route inverse;            // rb set: rb->launch_inv; else the radix-2 inverse
     route polymul;            // rb set: rb->launch_mul; else two forwards + `inverse` (product fused into its load when that has an entry)
     route polymul_ntt;        // rb set: rb->launch_mulhat; else forward + product in place + inverse
+    route extend;             // rb set: rb->launch_extend (agx_ntt_basis_extend to NTT form in one launch); else launch_basis_coeff, then `forward` in place on the target primes
     route rescale;            // rb set: `inverse` on prime P-1, then rb->launch_rescale on primes 0 .. P-2; else inverse, coefficient-domain step, forward
 };
 
@@ -100,6 +101,15 @@ struct agx_ntt_plan {
     // workgroup out zeroes it), and whether a launch that took the slot has not recorded its event yet
     mutable std::vector<hipEvent_t> ticket_events;
     mutable std::vector<char> ticket_pending;
+};
+
+// agx_ntt_basis_extend: the constants of one (plan, source range, target range) on the plan's device, and nothing of the plan but a pointer --
+// the kernels come from the plan's routes at every call, so agx_ntt_plan_set_variant between calls stays legal.  The plan outlives the basis.
+struct agx_ntt_basis {
+    const agx_ntt_plan* plan = nullptr;
+    uint32_t src_first = 0, src_count = 0, dst_first = 0, dst_count = 0;
+    agx::device_buf<ulonglong2> d_dinv;      // [S]    {D_i^-1 mod q_i, quotient}
+    agx::device_buf<ulonglong2> d_mat;       // [T][S] {D_i mod q_j, quotient}
 };
 
 namespace agx {

@@ -439,6 +439,78 @@ rescale_rb2(const uint64_t* x, const uint64_t* __restrict__ t, uint64_t* out,
     f.store_last_layout(u, out, base, live);
 }
 
+// agx_ntt_basis_extend to NTT form in one launch: fast RNS base conversion from the S source primes of a basis to ONE target prime, then that
+// prime's forward transform, one frame on chip.  x: dense [S][batch][n] in coefficient form (slab i under plan prime src_first + i, values in
+// [0,4q_i)); out: dense [T][batch][n], slab j under plan prime dst_first + j, written exactly as fwd_rb2 writes it.  For each source the
+// frame's words arrive in the pass-0 layout, GRP registers at a time and one group ahead of the one being folded in (plain loads: the T
+// workgroups of a frame all read them); y_i = x_i D_i^-1 mod q_i is formed in [0,q_i) and y_i (D_i mod q_j) is
+// added to the frame's accumulators, which stay in [0,2q_j) (basis_accumulate, modarith.hpp): one 64-bit accumulator per coefficient, so
+// the frame, one group in flight and one being folded are all that is live.  The forward passes take [0,2q_j) as it is.  Each workgroup
+// forms the y_i of its frame again, so a workgroup does 2 S Shoup products per output word (S to form the y_i, S to fold them in) beside the
+// log2(n) / 2 butterflies per word of the transform: at S = 16 that is 32 against 5 ... 7.5, and the host routes by S (extend_is_fused, agx_ntt.cpp).
+// BLOCK ORDER: the linear block index has the TARGET PRIME FASTEST, so the T workgroups of a group of frames are dispatched together (with the
+// prime on blockIdx.y, AGX_RB2_PROLOGUE, every frame of target 0 would run before any of target 1).  Measured, this does not make them share
+// the sources in L2: the L2s request about T times the source bytes (profiles/r08_basis_extend.md).
+template <int L, int R, int PPB, int ARITH, int MINW>
+__global__ void __launch_bounds__((1 << (L - R)) * PPB, (MINW > AGX_MULHAT_MAXW ? AGX_MULHAT_MAXW : MINW))
+extend_rb2(const uint64_t* __restrict__ x, uint64_t* __restrict__ out, const prime_consts* __restrict__ consts, const ulonglong2* __restrict__ dinv,
+           const ulonglong2* __restrict__ mat, const twpair* __restrict__ tw_rb, uint32_t pairs_per_prime, uint64_t frames_x,
+           int64_t prime_stride, int64_t poly_stride, uint32_t src_first, uint32_t num_src, uint32_t dst_first, uint32_t num_dst) {
+    using F = frame_of<L, R, ARITH>;
+    constexpr int C = F::C, T = F::T;
+    static_assert(T >= 64, "one frame must span whole waves");
+    F f;
+    f.tid = threadIdx.x & (T - 1);
+    const uint32_t slot = PPB == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / T));      // a frame spans whole waves: wave-uniform
+    // the quotient comes out of the vector unit (there is no scalar divide): pin it to a scalar register, or every address derived from it is
+    // held in vector registers for the whole kernel (R = 5: 12 ... 20 bytes of scratch per lane)
+    uint32_t group = blockIdx.x / num_dst;
+    asm volatile("" : "+s"(group));
+    const uint32_t j = blockIdx.x - group * num_dst;
+    uint64_t fx = (uint64_t)group * PPB + slot;
+    const bool live = fx < frames_x;
+    if (!live) fx = frames_x - 1;                         // keep every thread on the barriers
+    const uint32_t prime = dst_first + j;
+    const uint64_t q = consts[prime].q, q2 = q << 1;
+    f.init_consts(q, consts[prime].est);
+    f.slab = reinterpret_cast<uint64_t*>(agx_dyn_lds) + (size_t)slot * F::slab_elems;
+    int64_t base = (int64_t)j * prime_stride + (int64_t)fx * poly_stride;
+    constexpr int GRP = 4, NG = C / GRP;      // registers per group of source loads, groups per thread
+    static_assert(C % GRP == 0 && NG % 2 == 0, "whole groups, and group 0 of every source in buffer 0");
+    const uint64_t* xf = x + (int64_t)fx * poly_stride;      // the frame under source 0 (wave-uniform: lanes add tid)
+    // both wave-uniform and pinned to scalar registers of their own: sharing fx poly_stride, they were kept as one vector pair to the last store
+    asm volatile("" : "+s"(base), "+s"(xf));
+    const ulonglong2* row = mat + (size_t)j * num_src;
+    uint64_t acc[C], z[2][GRP];
+#pragma unroll
+    for (int r = 0; r < C; ++r) acc[r] = 0;
+    static_for<0, GRP>([&](auto I) { z[0][I] = xf[f.tid + (uint32_t)(int)I * T]; });
+    for (uint32_t i = 0; i < num_src; ++i) {      // wave-uniform
+        const uint64_t qi = consts[src_first + i].q;
+        const ulonglong2 d = dinv[i], c = row[i];
+        const uint64_t* cur = xf + (int64_t)i * prime_stride;
+        const uint64_t* nxt = xf + (int64_t)(i + 1 < num_src ? i + 1 : i) * prime_stride;      // behind the last source: its own first group again (a cache hit, dropped)
+        static_for<0, NG>([&](auto Gq) {
+            constexpr int g = Gq;
+            // the group's first word, opaque and scalar: every group then shares the GRP lane offsets tid + I T.  Seen through, the C distinct
+            // offsets r T (beyond the instruction's immediate from T = 512 on) are hoisted out of this loop into C register pairs, which spill
+            const uint64_t* pg = g + 1 < NG ? cur + (uint32_t)((g + 1) * GRP) * T : nxt;
+            asm volatile("" : "+s"(pg));
+            static_for<0, GRP>([&](auto I) { z[(g + 1) & 1][I] = pg[f.tid + (uint32_t)(int)I * T]; });
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<0, GRP>([&](auto I) {
+                constexpr int r = g * GRP + (int)I;
+                asm volatile("" : "+v"(acc[r]));
+                acc[r] = basis_accumulate(acc[r], basis_scale(z[g & 1][I], d.x, d.y, qi), c.x, c.y, q, q2);
+                asm volatile("" : "+v"(acc[r]));
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        });
+    }
+    f.forward(acc, tw_rb + (size_t)prime * pairs_per_prime);
+    f.store_last_layout(acc, out, base, live);
+}
+
 // ---- host side: pass tables, launch glue and registry entries, written once for every kernel family ---------------------------------
 // (the 32-bit kernels of rb32_kernels.hpp and the wave-packed kernels of wp_kernels.hpp bring their own shape struct and nothing else)
 
@@ -547,6 +619,17 @@ hipError_t launch_rescale_t(const plan_view& pv, const uint64_t* x, const uint64
                             round ? 1u : 0u);
 }
 
+// agx_ntt_basis_extend's fused launch: pv is the view of the whole plan, the frame layout describes x and out alike (dense); a linear grid, the
+// target prime fastest (extend_rb2)
+template <class S, auto K>
+hipError_t launch_extend_t(const plan_view& pv, const basis_view& bv, const uint64_t* x, uint64_t* out, const frame_layout& fl, hipStream_t s) {
+    const uint64_t blocks = (uint64_t)bv.dst_count * ((fl.batch + S::fpb - 1) / S::fpb);
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(K, dim3((unsigned)blocks), dim3(S::threads), S::lds, s, x, out, pv.consts, bv.dinv, bv.mat, pv.tw_rb, pv.rb->table_pairs, fl.batch,
+                       fl.prime_stride, fl.poly_stride, bv.src_first, bv.src_count, bv.dst_first, bv.dst_count);
+    return hipGetLastError();
+}
+
 template <int L, int R, int ARITH, int MINW>
 hipError_t launch_mul_park_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
@@ -617,8 +700,8 @@ hipError_t launch_inv_rb2_dloop_t(const plan_view& pv, const uint64_t* in, const
 template <class S>
 constexpr rb_entry shape_entry(int id, decltype(rb_entry::launch) fwd, decltype(rb_entry::init) init, decltype(rb_entry::launch_inv) inv,
                                decltype(rb_entry::launch_mul) mul, decltype(rb_entry::launch_mulhat) mulhat = nullptr,
-                               decltype(rb_entry::launch_rescale) rescale = nullptr) {
-    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow, mulhat, rescale};
+                               decltype(rb_entry::launch_rescale) rescale = nullptr, decltype(rb_entry::launch_extend) extend = nullptr) {
+    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow, mulhat, rescale, extend};
 }
 
 // forward, inverse and the product with both forward results in registers, one workgroup per S::fpb frames each (every family has this form)
@@ -629,7 +712,7 @@ constexpr rb_entry make_entry3(int id) {
 
 // PPB frames per workgroup (the n = 4096 defaults: R = 3, 8 waves/SIMD; n = 1024 with streamed twiddles, where two frames of 2^R coefficients still fit
 // the register budget and the parked product's round trip through c's frame would cost more); the product kernel at MULW waves per SIMD
-// and the product by a pre-transformed operand and the rescale kernel (one frame in registers; at most AGX_MULHAT_MAXW waves per SIMD)
+// and the product by a pre-transformed operand, the rescale kernel and the base-extension kernel (one frame in registers; at most AGX_MULHAT_MAXW waves per SIMD)
 template <int L, int R, int PPB, int ARITH, int MINW, int MULW = MINW>
 constexpr rb_entry make_entry2(int id) {
     using S = rb2_shape<L, R, PPB, ARITH, MINW>;
@@ -638,8 +721,9 @@ constexpr rb_entry make_entry2(int id) {
     constexpr auto mul = &polymul_rb2<L, R, PPB, ARITH, MULW>;
     constexpr auto mulhat = &mulhat_rb2<L, R, PPB, ARITH, MINW>;
     constexpr auto rescale = &rescale_rb2<L, R, PPB, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat, rescale>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>,
-                          &launch_rescale_t<S, rescale>);
+    constexpr auto extend = &extend_rb2<L, R, PPB, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat, rescale, extend>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>,
+                          &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>);
 }
 
 // forward kernel only (a plan's forward companion: rb_entry::fwd_companion), one frame per workgroup
@@ -651,7 +735,7 @@ constexpr rb_entry make_entry_single_fwd(int id) {
 }
 
 // the streamed single-frame kernels (reg_s<n>.hip): one frame in registers per workgroup at any time (R = 5: a second frame cannot
-// be held): forward, inverse, the fused product by polymul_rb2_park / polysquare_rb2, the product by a pre-transformed operand and the rescale kernel
+// be held): forward, inverse, the fused product by polymul_rb2_park / polysquare_rb2, the product by a pre-transformed operand, the rescale kernel and the base-extension kernel
 template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
@@ -659,8 +743,9 @@ constexpr rb_entry make_entry_single(int id) {
     constexpr auto inv = &inv_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto mulhat = &mulhat_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto rescale = &rescale_rb2<L, R, 1, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat, rescale>,
-                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, mulhat>, &launch_rescale_t<S, rescale>);
+    constexpr auto extend = &extend_rb2<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat, rescale, extend>,
+                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, mulhat>, &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>);
 }
 
 // entry e with forward calls of its plans routed to the forward-only entry `id` (rb_entry::fwd_companion)
@@ -675,7 +760,7 @@ template <int L, int R, int ARITH, int MINW>
 hipError_t init_rb2_single_invloop_t() {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     const hipError_t e = allow_lds<S::lds, &fwd_rb2<L, R, 1, ARITH, MINW>, &inv_rb2_loop<L, R, ARITH, MINW>, &polymul_rb2_park<L, R, ARITH, MINW>,
-                                   &polysquare_rb2<L, R, ARITH, MINW>, &mulhat_rb2<L, R, 1, ARITH, MINW>, &rescale_rb2<L, R, 1, ARITH, MINW>>();
+                                   &polysquare_rb2<L, R, ARITH, MINW>, &mulhat_rb2<L, R, 1, ARITH, MINW>, &rescale_rb2<L, R, 1, ARITH, MINW>, &extend_rb2<L, R, 1, ARITH, MINW>>();
     return e != hipSuccess ? e : allow_lds<S::lds + kDloopMailboxBytes, &inv_rb2_dloop<L, R, ARITH, MINW>>();
 }
 template <int L, int R, int ARITH, int MINW>
@@ -683,7 +768,7 @@ constexpr rb_entry make_entry_single_invloop(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     return shape_entry<S>(id, &launch_fwd_t<S, &fwd_rb2<L, R, 1, ARITH, MINW>>, &init_rb2_single_invloop_t<L, R, ARITH, MINW>,
                           &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, &mulhat_rb2<L, R, 1, ARITH, MINW>>,
-                          &launch_rescale_t<S, &rescale_rb2<L, R, 1, ARITH, MINW>>);
+                          &launch_rescale_t<S, &rescale_rb2<L, R, 1, ARITH, MINW>>, &launch_extend_t<S, &extend_rb2<L, R, 1, ARITH, MINW>>);
 }
 
 }  // namespace AGX_TU

@@ -30,6 +30,10 @@ struct rb_entry {
     // agx_ntt_rescale's second launch on a view of primes 0 .. P-2: out_i = (x_i - NTT_i(lift of t to q_i)) q_L^-1, t ([batch][n], poly stride as
     // the frame layout's) the coefficients of the last slab; out may be x.  null: the entry's plans take the generic route
     hipError_t (*launch_rescale)(const plan_view&, const uint64_t* x, const uint64_t* t, uint64_t* out, const frame_layout&, bool round, hipStream_t) = nullptr;
+    // agx_ntt_basis_extend to NTT form in one launch, on a view of the WHOLE plan: out_j = NTT_j(sum_i y_i (D_i mod q_j)) for the basis' targets, x
+    // dense [S][batch][n] in coefficient form, out dense [T][batch][n] (the frame layout's strides serve both), out of place.  The caller keeps
+    // T ceil(batch / ppb) workgroups within the grid limit.  null: the entry's plans run launch_basis_coeff, then the forward in place
+    hipError_t (*launch_extend)(const plan_view&, const basis_view&, const uint64_t* x, uint64_t* out, const frame_layout&, hipStream_t) = nullptr;
 };
 
 // The view of primes [lo, hi) of a route: every per-prime array starts at prime lo, so the launchers run on one slab or on the first

@@ -233,6 +233,42 @@ AGX_API int agx_ntt_rescale(const agx_ntt_plan* plan, const uint64_t* d_x, uint6
 AGX_API int agx_ntt_automorphism(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t galois_elt, int form,
                                  void* stream);
 
+/* Fast RNS base conversion ("fast basis extension", HPS / BEHZ): a polynomial known by its residues modulo the SOURCE primes [src_first, src_first + S)
+ * of a plan gets its residues modulo the TARGET primes [dst_first, dst_first + T): both halves of a hybrid key switch -- ModUp extends one digit to the
+ * whole basis Q u P, ModDown brings the special primes back to Q.  Both ranges lie inside the plan's primes [0, P); they may overlap,
+ * or one may contain the other.  Per coefficient, with D = prod_{i in source} q_i and D_i = D / q_i:
+ *   y_i = (x_i mod q_i) (D_i^-1 mod q_i) mod q_i in [0, q_i),    V = sum_i y_i D_i (an integer, 0 <= V < S D),    out_j = V mod q_j, fully reduced.
+ * This is the APPROXIMATE conversion: V = X + u D with X in [0, D) the CRT value of the residues and 0 <= u < S; no correction term is applied, callers
+ * absorb u D in their noise, as every hybrid key switch does.  It is a deterministic integer formula (exact against big-integer arithmetic); for a
+ * target j that is itself a source prime it gives out_j = x_j mod q_j.
+ * A BASIS holds the constants of one (plan, ranges) on the plan's device -- D_i^-1 mod q_i (S entries) and D_i mod q_j (T x S), computed once on the
+ * host -- and a pointer to the plan, nothing else of it: agx_ntt_plan_set_variant between calls stays legal, the plan must outlive the basis, and the
+ * plan's device must be current at creation and at every call.  Any plan serves (no inverse tables needed); plan creation is unchanged.
+ * S <= AGX_BASIS_MAX_SRC = 16 is part of the contract: it is what lets sum_i y_i (D_i mod q_j) < 16 2^62 2^62 = 2^128 be kept unreduced in 128 bits.
+ * (The kernels here reduce every term lazily instead and keep one 64-bit accumulator per coefficient.)
+ *   create : NULL basis or plan: AGX_ERR_NULL_POINTER; src_count == 0, dst_count == 0, a range past P, src_count > 16: AGX_ERR_BAD_ARGUMENT; two equal
+ *            source moduli (D_i is not invertible modulo q_i): AGX_ERR_BAD_MODULUS.        destroy: NULL is fine.
+ *   info   : the ranges, and launches_ntt_form = the kernel launches an AGX_FORM_NTT call takes under the plan's CURRENT variant.  Any out-pointer may be NULL.
+ *   extend : d_x dense [S][batch][n], COEFFICIENT form (natural order), slab i under prime src_first + i, values in [0, 4 q_i) as agx_ntt_forward accepts them;
+ *            d_out dense [T][batch][n], slab j under prime dst_first + j.  out_form AGX_FORM_COEFF writes out_j as defined above; AGX_FORM_NTT writes
+ *            NTT_j(out_j) exactly as agx_ntt_forward of this plan would write it (bit-reversed order, fully reduced).  Pointers need 8-byte alignment only.
+ *            OUT OF PLACE ONLY: d_out's range may not touch d_x's anywhere (AGX_ERR_BAD_ARGUMENT, nothing written).  An unknown form: AGX_ERR_BAD_ARGUMENT;
+ *            batch == 0: AGX_OK, nothing launched.  Asynchronous on `stream`, allocates and synchronises nothing (capturable into a hipGraph).
+ * AGX_FORM_COEFF is ONE launch on every plan (one thread per coefficient: S words read, T written, 8n(S + T) bytes per frame).  AGX_FORM_NTT is ONE launch
+ * (the conversion into one target prime's frame on chip, its forward transform, the store; T workgroups per frame) for n = 1024 ... 32768 whenever some modulus is
+ * 2^31 or larger AND the source count is one at which that kernel measured ahead of the two-launch form (profiles/r08_basis_extend.md): S = 1, and S = 2 except at
+ * n = 4096 and 16384; there T ceil(batch / frames per workgroup) workgroups past 2^31 - 1 return AGX_ERR_BAD_ARGUMENT.  Everywhere else -- S >= 3, S = 2 at n = 4096
+ * and 16384, n <= 512, plans whose moduli are all below 2^31, plans forced onto AGX_VARIANT_LDS_RADIX2 -- it is the coefficient-form launch followed by the plan's
+ * forward on the target slabs in place (two launches; three at n = 32768 under AGX_VARIANT_LDS_RADIX2, whose forward is two).
+ * Groups: there is no group form.  A basis is tied to one plan; agx_ntt_group_shard hands out each shard's plan and stream, so a caller makes one
+ * basis per shard and calls agx_ntt_basis_extend on that shard's device and stream. */
+#define AGX_BASIS_MAX_SRC 16
+typedef struct agx_ntt_basis agx_ntt_basis;
+AGX_API int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count);
+AGX_API int agx_ntt_basis_destroy(agx_ntt_basis* basis);
+AGX_API int agx_ntt_basis_info(const agx_ntt_basis* basis, uint32_t* src_first, uint32_t* src_count, uint32_t* dst_first, uint32_t* dst_count, int* launches_ntt_form);
+AGX_API int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream);
+
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */
 AGX_API int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly,

@@ -2,6 +2,7 @@
 runs on paths bench.py's headline does not cover).
 Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes P --batch B --bits 60 --oop --launches K --variant ID]
        python3 tools/run_op.py --op auto --form {coeff,ntt} --galois G [--odd --reps 5 ...]   (agx_ntt_automorphism beside a device copy of the same words)
+       python3 tools/run_op.py --op extend --src S [--dst T --only {both,fused,pair} --reps 5 ...]   (agx_ntt_basis_extend to NTT form beside the unfused pair)
 Under the profiler: rocprofv3 ... -- python3 tools/run_op.py ...   (the interpreter itself after `--`, never this file: an
 `env` shebang hop after the profiler's preload has initialised the GPU is a forbidden exec on this pool)."""
 import argparse
@@ -16,7 +17,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -34,6 +35,9 @@ ap.add_argument("--form", choices=["coeff", "ntt"], default="ntt", help="auto: A
 ap.add_argument("--galois", type=int, default=5, help="auto: the Galois element g (odd, below 2n; -1 = 2n - 1, conjugation)")
 ap.add_argument("--odd", action="store_true", help="auto: both bases one word past a 16-byte boundary (the NTT form then takes its 8-byte accesses)")
 ap.add_argument("--reps", type=int, default=5, help="auto: timed repetitions of --launches calls each, alternating with the copy; medians are reported")
+ap.add_argument("--src", type=int, default=2, help="extend: source primes [0, S)")
+ap.add_argument("--dst", type=int, default=0, help="extend: target primes [0, T); 0 = every prime of the plan")
+ap.add_argument("--only", choices=["both", "fused", "pair"], default="both", help="extend: time the AGX_FORM_NTT call, the unfused pair, or both alternating (a counter run wants one)")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
@@ -95,8 +99,73 @@ def run_auto():
     plan.close()
 
 
+def run_extend():
+    """agx_ntt_basis_extend from primes [0, S) to [0, T) in AGX_FORM_NTT (one launch where the fused kernel serves) and the unfused pair
+    -- the AGX_FORM_COEFF call, then agx_ntt_forward in place on a plan of the target primes -- alternating in one process.  Prints us per
+    call (median of --reps repetitions, min and max beside it), the model traffic 8n(S + T) bytes per frame as GB/s, and the ratio."""
+    import statistics
+    import time
+
+    S, T = args.src, args.dst or args.primes
+    basis = plan.basis(0, S, 0, T)
+    targets = agx.Plan(args.n, plan.moduli[:T], psi=[plan.psi(p) for p in range(T)])      # the same tables: what the pair's forward runs on
+    if args.variant is not None:
+        targets.set_variant(agx.VARIANT_REGBLOCK_BASE + args.variant)
+    words = args.batch * args.n
+    # fill_synthetic writes a slab for EVERY prime of the plan: the buffer holds them all, the call reads the first S (slab i: residues below q_i)
+    x = torch.empty(args.primes * words, dtype=torch.int64, device="cuda")
+    out = torch.empty(T * words, dtype=torch.int64, device="cuda")
+    plan.fill_synthetic(x.data_ptr(), args.batch, 0, 42, stream)
+
+    def fused():
+        basis.extend(x.data_ptr(), out.data_ptr(), args.batch, agx.FORM_NTT, stream)
+
+    def pair():
+        basis.extend(x.data_ptr(), out.data_ptr(), args.batch, agx.FORM_COEFF, stream)
+        targets.forward(out.data_ptr(), out.data_ptr(), args.batch, stream)
+
+    todo = [f for name, f in (("fused", fused), ("pair", pair)) if args.only in ("both", name)]
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / args.launches      # us per call
+
+    t_end = time.perf_counter() + args.ramp_seconds
+    while time.perf_counter() < t_end:      # clock ramp, as below
+        for _ in range(8):
+            for fn in todo:
+                fn()
+        torch.cuda.synchronize()
+    times = {fn.__name__: [] for fn in todo}
+    for _ in range(args.reps):
+        for fn in todo:
+            times[fn.__name__].append(timed(fn))
+    model = 8.0 * words * (S + T)      # bytes: every source word read once, every target word written once
+    head = f"extend n={args.n} S={S} T={T} batch={args.batch} bits={args.bits} launches_ntt_form={basis.info()[4]}:"
+    parts = [f"{name} {statistics.median(t):.1f} us per call (min {min(t):.1f} max {max(t):.1f}), {model / statistics.median(t) / 1e3:.0f} GB/s of model traffic"
+             for name, t in times.items()]
+    if len(times) == 2:
+        parts.append(f"ratio fused/pair {statistics.median(times['fused']) / statistics.median(times['pair']):.3f}")
+    print(head, "; ".join(parts))
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "model_bytes": model}, open(args.report, "w"))
+    basis.close()
+    targets.close()
+    plan.close()
+
+
 if args.op == "auto":
     run_auto()
+    sys.exit(0)
+if args.op == "extend":
+    run_extend()
     sys.exit(0)
 slabs = [torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(args.slabs)]
 for i, s in enumerate(slabs):
