@@ -60,6 +60,8 @@ ABI = {
     "agx_ntt_basis_destroy": (_int, [_vp]),
     "agx_ntt_basis_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_int)]),
     "agx_ntt_basis_extend": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
+    "agx_ntt_basis_mod_down": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "agx_ntt_basis_mod_down_info": (_int, [_vp, ctypes.POINTER(_int)]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
@@ -379,6 +381,18 @@ class Basis:
         """d_x [src_count][batch][n], coefficient form, values in [0,4q) -> d_out [dst_count][batch][n]: sum_i y_i D_i mod q_j (y_i = x_i D_i^-1
         mod q_i; no correction term), as coefficients (FORM_COEFF) or transformed as Plan.forward writes it (FORM_NTT); out of place"""
         _check(lib().agx_ntt_basis_extend(self._h, d_x, d_out, batch, form, stream), "basis_extend")
+
+    def mod_down(self, d_xq, d_xp, d_out, d_scratch, batch, stream=0):
+        """ModDown on NTT-form frames: d_xq [dst_count][batch][n] and d_xp [src_count][batch][n] as Plan.forward / forward_lazy write them ->
+        d_out [dst_count][batch][n] = (xq_j - NTT_j(sum_i y_i D_i)) D^-1 mod q_j, y_i = INTT_i(xp_i) D_i^-1 mod q_i; d_out may be d_xq;
+        d_scratch: src_count*batch*n words, or d_xp itself (which is then overwritten)"""
+        _check(lib().agx_ntt_basis_mod_down(self._h, d_xq, d_xp, d_out, d_scratch, batch, stream), "basis_mod_down")
+
+    def mod_down_launches(self):
+        """the kernel launches a mod_down call takes under the plan's current variant"""
+        launches = _int(0)
+        _check(lib().agx_ntt_basis_mod_down_info(self._h, ctypes.byref(launches)), "basis_mod_down_info")
+        return launches.value
 
     def close(self):
         if self._h:

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -179,6 +180,7 @@ static void resolve_routes(agx_ntt_plan* p) {
     // call then runs `inverse`, the coefficient-domain step and `forward` on views of these routes
     r.rescale = inv && e->launch_rescale ? main : generic;
     r.extend = e && e->launch_extend ? main : generic;      // forward tables only
+    r.moddown = inv && e->launch_moddown ? main : generic;      // pairs with `inverse` on the source primes, as rescale does on the last
 }
 
 static const route& forward_route(const agx_ntt_plan* p, uint64_t batch) {
@@ -687,6 +689,19 @@ int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32
         b->src_first = src_first, b->src_count = S, b->dst_first = dst_first, b->dst_count = T;
         if (int rc = b->d_dinv.upload(dinv_pairs)) return rc;
         if (int rc = b->d_mat.upload(mat_pairs)) return rc;
+        // agx_ntt_basis_mod_down: D^-1 mod q_j, and the source primes' constants with the inverse's last-stage factors scaled by D_i^-1 (the plan
+        // keeps no host copy of its constants: the S entries are read back).  A target that is a source modulus leaves the basis good for extend.
+        std::vector<prime_consts> sc(S);
+        AGX_HIP(hipMemcpy(sc.data(), plan->d_consts.p + src_first, S * sizeof(prime_consts), hipMemcpyDeviceToHost));
+        std::vector<uint64_t> n_inv(S), w1n(S), dall(T), dall_p(T), sn(S), sn_p(S), sw(S), sw_p(S);
+        for (uint32_t i = 0; i < S; ++i) n_inv[i] = sc[i].n_inv, w1n[i] = sc[i].w1n;
+        b->moddown_legal = moddown_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, dinv.data(), n_inv.data(), w1n.data(), dall.data(),
+                                             dall_p.data(), sn.data(), sn_p.data(), sw.data(), sw_p.data());
+        for (uint32_t i = 0; i < S; ++i) sc[i].n_inv = sn[i], sc[i].n_inv_p = sn_p[i], sc[i].w1n = sw[i], sc[i].w1n_p = sw_p[i];
+        std::vector<ulonglong2> dall_pairs(T);
+        for (uint32_t j = 0; j < T; ++j) dall_pairs[j] = make_ulonglong2(dall[j], dall_p[j]);
+        if (int rc = b->d_dall.upload(dall_pairs)) return rc;
+        if (int rc = b->d_src_consts.upload(sc)) return rc;
         *basis = b.release();
         return AGX_OK;
     });
@@ -734,7 +749,7 @@ int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64
     if (!layout_fits(plan->n, S, batch, fl.prime_stride, fl.poly_stride) || !layout_fits(plan->n, T, batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;
     // out of place only: every workgroup of a frame reads all S source frames while others already write their targets
     if (ranges_touch(addr(d_x), S * batch * plan->n, addr(d_out), T * batch * plan->n)) return AGX_ERR_BAD_ARGUMENT;
-    const basis_view bv{basis->d_dinv, basis->d_mat, basis->src_first, S, basis->dst_first, T};
+    const basis_view bv{basis->d_dinv, basis->d_mat, basis->d_dall, basis->src_first, S, basis->dst_first, T};
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (const route& r = plan->routes.extend; out_form == AGX_FORM_NTT && extend_is_fused(basis)) {
         // one kernel: the conversion and the target prime's forward transform stay on chip; T workgroups per group of rb->ppb frames
@@ -749,6 +764,71 @@ int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64
         const route fr = prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T);
         AGX_HIP(fr.rb ? fr.rb->launch(fr, d_out, d_out, fl, s) : launch_forward_radix2(fr, d_out, d_out, fl, s));
     }
+    return AGX_OK;
+}
+
+// Does a mod_down call of this basis take the two-launch route?  The plan's entry must carry the fused kernel (n = 1024 ... 32768, some modulus
+// >= 2^31, not AGX_VARIANT_LDS_RADIX2); resolved at the call, so agx_ntt_plan_set_variant between calls stays legal.
+// It serves every source count: measured at S = 1, 2, 4, 8, 16 against the four-launch route on the same plan (profiles/r09_mod_down.md).
+static bool moddown_is_fused(const agx_ntt_basis* b) {
+#ifdef AGX_DIAG
+    // lib/libagxntt_diag.so only: AGX_NTT_MOD_DOWN_GENERIC=1 in the environment, read at every call, sends the call down the four-launch route on the
+    // same plan (tools/run_op.py --op moddown times the two routes side by side)
+    if (const char* e = std::getenv("AGX_NTT_MOD_DOWN_GENERIC"); e && e[0] == '1') return false;
+#endif
+    return b->plan->routes.moddown.rb != nullptr;
+}
+
+static int inverse_launches(const agx_ntt_plan* p) { return p->routes.inverse.rb ? 1 : inverse_radix2_launches(p->log_n); }
+
+int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launches) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    // fused: the scaled inverse of the source slabs, then moddown_rb2; generic: both inverses, the coefficient-domain step, the forward
+    if (launches) *launches = moddown_is_fused(basis) ? inverse_launches(basis->plan) + 1 : 2 * inverse_launches(basis->plan) + 1 + forward_launches(basis->plan);
+    return AGX_OK;
+}
+
+int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!basis || !d_xq || !d_xp || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = basis->plan;
+    if (int rc = check_plan(plan)) return rc;
+    const uint32_t S = basis->src_count, T = basis->dst_count;
+    if (!aligned8(d_xq) || !aligned8(d_xp) || !aligned8(d_out) || !aligned8(d_scratch) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of xq and out ([T][batch][n]) and of xp and the scratch ([S][batch][n]) alike
+    if (!layout_fits(plan->n, S, batch, fl.prime_stride, fl.poly_stride) || !layout_fits(plan->n, T, batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;
+    const bool fused = moddown_is_fused(basis);
+    const route& r = plan->routes.moddown;
+    if (fused && (uint64_t)T * ((batch + r.rb->ppb - 1) / r.rb->ppb) > 0x7fffffffull) return AGX_ERR_BAD_ARGUMENT;      // grid limit: T workgroups per group of rb->ppb frames
+    const uint64_t slab = (uint64_t)fl.prime_stride, qwords = T * slab, pwords = S * slab;      // dense sets, one range each
+    const uintptr_t xq = addr(d_xq), xp = addr(d_xp), out = addr(d_out), scratch = addr(d_scratch);
+    if (out != xq && ranges_touch(out, qwords, xq, qwords)) return AGX_ERR_BAD_ARGUMENT;      // out IS xq (in place) or touches nothing of it
+    // out never touches xp or the scratch, the scratch never xq: T workgroups per frame read the scratch while others already write out
+    if (ranges_touch(out, qwords, xp, pwords) || ranges_touch(out, qwords, scratch, pwords) || ranges_touch(scratch, pwords, xq, qwords)) return AGX_ERR_BAD_ARGUMENT;
+    if (scratch != xp && ranges_touch(scratch, pwords, xp, pwords)) return AGX_ERR_BAD_ARGUMENT;      // the scratch IS xp (the caller gives those slabs up) or does not touch it
+    if (!basis->moddown_legal) return AGX_ERR_BAD_MODULUS;      // some target modulus is a source modulus: D has no inverse there
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    const basis_view bv{basis->d_dinv, basis->d_mat, basis->d_dall, basis->src_first, S, basis->dst_first, T};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto inverse_on = [&](const route& v, const uint64_t* in, uint64_t* out_) {
+        return v.rb ? v.rb->launch_inv(v, in, nullptr, out_, fl, s) : launch_inverse_radix2(v, in, out_, fl, s);
+    };
+    // scratch <- y_i = INTT_i(xp_i) D_i^-1 mod q_i in [0, q_i): the plan's inverse on the view of the source primes, its last-stage constants the basis'
+    route scaled = prime_range(plan->routes.inverse, basis->src_first, basis->src_first + S);
+    scaled.consts = basis->d_src_consts;
+    if (fused) {
+        // two launches: the accumulation, the forward transform and (xq_j - .) D^-1 stay on chip; a wave reads its words of xq_j before it writes them
+        AGX_HIP(inverse_on(scaled, d_xp, d_scratch));
+        AGX_HIP(r.rb->launch_moddown(r, bv, d_xq, d_scratch, d_out, fl, s));
+        return AGX_OK;
+    }
+    // generic route, no more scratch: out <- INTT(xq) on the target primes; scratch <- the y_i; out <- (out - sum_i y_i D_i) D^-1 in the coefficient
+    // domain; out <- NTT(out) in place
+    AGX_HIP(inverse_on(prime_range(plan->routes.inverse, basis->dst_first, basis->dst_first + T), d_xq, d_out));
+    AGX_HIP(inverse_on(scaled, d_xp, d_scratch));
+    AGX_HIP(launch_moddown_coeff(plan->routes.forward, bv, d_out, d_scratch, batch, s));
+    const route fr = prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T);
+    AGX_HIP(fr.rb ? fr.rb->launch(fr, d_out, d_out, fl, s) : launch_forward_radix2(fr, d_out, d_out, fl, s));
     return AGX_OK;
 }
 

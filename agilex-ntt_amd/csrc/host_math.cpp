@@ -123,4 +123,23 @@ bool basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint3
     return true;
 }
 
+bool moddown_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, const uint64_t* dinv, const uint64_t* n_inv, const uint64_t* w1n,
+                       uint64_t* dall, uint64_t* dall_p, uint64_t* sn, uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p) {
+    for (uint32_t i = 0; i < S; ++i) {
+        sn[i] = mul_mod(n_inv[i], dinv[i], src[i]);
+        sn_p[i] = shoup_quotient(sn[i], src[i]);
+        sw[i] = mul_mod(w1n[i], dinv[i], src[i]);
+        sw_p[i] = shoup_quotient(sw[i], src[i]);
+    }
+    bool all = true;
+    for (uint32_t j = 0; j < T; ++j) {
+        uint64_t d = 1 % dst[j];      // D mod dst[j], one factor at a time
+        for (uint32_t k = 0; k < S; ++k) d = mul_mod(d, src[k] % dst[j], dst[j]);
+        dall[j] = dall_p[j] = 0;
+        if (inv_mod_euclid(d, dst[j], &dall[j])) dall_p[j] = shoup_quotient(dall[j], dst[j]);
+        else all = false;
+    }
+    return all;
+}
+
 }  // namespace agx

@@ -39,4 +39,13 @@ void power_tables_bitrev(uint64_t q, uint64_t base, uint32_t n, uint64_t* tw, ui
 // are equal).  A target that is itself source k gets D_i mod dst[j] = 0 for i != k, so the conversion hands that residue through.
 bool basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t* dinv, uint64_t* dinv_p, uint64_t* mat, uint64_t* mat_p);
 
+// What agx_ntt_basis_mod_down needs beyond basis_constants, for the same moduli (dinv as basis_constants wrote it):
+//   dall[j] = D^-1 mod dst[j] with its quotient dall_p[j] -- {0, 0} where D is not invertible modulo dst[j] (dst[j] shares a factor with a source;
+//     for primes: equals one); the return value says whether every one exists;
+//   sn[i] = n_inv[i] dinv[i] mod src[i] and sw[i] = w1n[i] dinv[i] mod src[i] with their quotients sn_p / sw_p: the two constants of an inverse
+//     transform's last stage (n^-1 mod src[i] and inv_twiddle[1] n^-1 mod src[i], both below src[i]) scaled by D_i^-1, so that the inverse of
+//     the source slabs writes y_i = p_i D_i^-1 mod src[i] itself.
+bool moddown_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, const uint64_t* dinv, const uint64_t* n_inv, const uint64_t* w1n,
+                       uint64_t* dall, uint64_t* dall_p, uint64_t* sn, uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p);
+
 }  // namespace agx

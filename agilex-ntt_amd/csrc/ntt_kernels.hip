@@ -304,6 +304,36 @@ __global__ void basis_coeff_kernel(const uint64_t* __restrict__ x, uint64_t* __r
     }
 }
 
+// agx_ntt_basis_mod_down, generic route, in the coefficient domain: out_j[e] <- (out_j[e] - sum_i y_i[e] (D_i mod q_j)) D^-1 mod q_j.  One thread
+// per (frame, coefficient): it reads its S words of y (y_i in [0,q_i), as the scaled inverse of the source slabs wrote them: no basis_scale here),
+// then reads, finishes and writes back one word of each of the T target slabs, which the inverse left in [0,q_j): 8 (S + 2T) bytes per
+// coefficient.  The sum stays in [0,2q_j) term by term (basis_accumulate) and is brought below q_j for rescale_finish's reduced form, which
+// never forms 4q: any modulus below 2^62.  Constants are wave-uniform.  SMAX >= S as in basis_coeff_kernel.
+template <int SMAX>
+__global__ void moddown_coeff_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ y, const prime_consts* __restrict__ dst_consts,
+                                     const ulonglong2* __restrict__ mat, const ulonglong2* __restrict__ dall, uint32_t S, uint32_t T, uint64_t per_prime) {
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t yi[SMAX];
+#pragma unroll
+        for (int i = 0; i < SMAX; ++i)
+            if ((uint32_t)i < S) yi[i] = y[(uint64_t)i * per_prime + e];
+        for (uint32_t j = 0; j < T; ++j) {
+            const uint64_t q = dst_consts[j].q, q2 = q << 1;
+            const ulonglong2* row = mat + (size_t)j * S;
+            const ulonglong2 d = dall[j];
+            uint64_t acc = 0;
+#pragma unroll
+            for (int i = 0; i < SMAX; ++i)
+                if ((uint32_t)i < S) {
+                    const ulonglong2 c = row[i];
+                    acc = basis_accumulate(acc, yi[i], c.x, c.y, q, q2);
+                }
+            uint64_t* o = out + (uint64_t)j * per_prime + e;
+            *o = rescale_finish<false>(*o, csub(acc, q), d.x, d.y, q);
+        }
+    }
+}
+
 __device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -419,6 +449,7 @@ static unsigned radix2_threads(uint32_t nb) {
 static uint32_t radix2_split(uint32_t log_n) { return log_n > (uint32_t)kMaxLdsLog ? log_n - kMaxLdsLog : 0; }      // stages run from global memory
 
 int forward_radix2_launches(uint32_t log_n) { return (int)radix2_split(log_n) + 1; }
+int inverse_radix2_launches(uint32_t log_n) { return (int)radix2_split(log_n) + 1; }
 
 hipError_t launch_forward_radix2(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
     const uint32_t split = radix2_split(pv.log_n);
@@ -506,6 +537,21 @@ hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const u
     else if (S <= 4) go(basis_coeff_kernel<4>);
     else if (S <= 8) go(basis_coeff_kernel<8>);
     else go(basis_coeff_kernel<16>);
+    return hipGetLastError();
+}
+
+hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    const dim3 grid(grid_1d(per_prime, 256));
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, out, y, pv.consts + bv.dst_first, bv.mat, bv.dall, bv.src_count, bv.dst_count, per_prime);
+    };
+    const uint32_t S = bv.src_count;      // at most AGX_BASIS_MAX_SRC = 16
+    if (S <= 1) go(moddown_coeff_kernel<1>);
+    else if (S <= 2) go(moddown_coeff_kernel<2>);
+    else if (S <= 4) go(moddown_coeff_kernel<4>);
+    else if (S <= 8) go(moddown_coeff_kernel<8>);
+    else go(moddown_coeff_kernel<16>);
     return hipGetLastError();
 }
 

@@ -28,6 +28,7 @@ struct rescale_consts {
 struct basis_view {
     const ulonglong2* dinv = nullptr;   // [S] {D_i^-1 mod q_i, its precomputed quotient}, q_i the modulus of plan prime src_first + i, D_i = prod_{k != i} q_k
     const ulonglong2* mat = nullptr;    // [T][S] {D_i mod q_j, its precomputed quotient}, q_j the modulus of plan prime dst_first + j
+    const ulonglong2* dall = nullptr;   // [T] {D^-1 mod q_j, its precomputed quotient}, D = prod_i q_i (agx_ntt_basis_mod_down; {0, 0} where it does not exist)
     uint32_t src_first = 0, src_count = 0, dst_first = 0, dst_count = 0;
 };
 
@@ -77,6 +78,7 @@ hipError_t kernels_init();  // one-time function attributes (large dynamic LDS)
 hipError_t launch_forward_radix2(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s);
 int forward_radix2_launches(uint32_t log_n);      // kernel launches of one launch_forward_radix2 call: the global stages of a frame past the LDS limit, then the LDS kernel
 hipError_t launch_inverse_radix2(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s);
+int inverse_radix2_launches(uint32_t log_n);      // of one launch_inverse_radix2 call: the LDS kernel, then the global stages of a frame past the LDS limit
 hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
 // c <- c o bhat in place on the dense [prime][batch][n] layout, bhat with strides of its own as above (the generic path of agx_ntt_polymul_ntt)
 hipError_t launch_pointwise_bhat(const plan_view& pv, uint64_t* c, const uint64_t* bhat, uint64_t batch, int64_t bhat_prime_stride,
@@ -93,6 +95,10 @@ hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, ui
 // [T][batch][n] (slab j under plan prime dst_first + j), out_j = sum_i y_i (D_i mod q_j) mod q_j in [0,q_j), y_i = x_i D_i^-1 mod q_i in [0,q_i).
 // pv: a view of the WHOLE plan (only its constants are read); out of place (the ranges must not touch).  One launch.
 hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const uint64_t* x, uint64_t* out, uint64_t batch, hipStream_t s);
+// the coefficient-domain step of agx_ntt_basis_mod_down's generic route: out_j[k] <- (out_j[k] - sum_i y_i[k] (D_i mod q_j)) D^-1 mod q_j in place on
+// out, dense [T][batch][n] in coefficient form with values in [0,q_j) (slab j under plan prime dst_first + j); y: dense [S][batch][n], y_i in
+// [0,q_i) as the scaled inverse of the source slabs left them.  pv: a view of the WHOLE plan (only its constants are read).  One launch.
+hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

@@ -65,6 +65,7 @@ struct plan_routes {
     route polymul_ntt;        // rb set: rb->launch_mulhat; else forward + product in place + inverse
     route extend;             // rb set: rb->launch_extend (agx_ntt_basis_extend to NTT form in one launch); else launch_basis_coeff, then `forward` in place on the target primes
     route rescale;            // rb set: `inverse` on prime P-1, then rb->launch_rescale on primes 0 .. P-2; else inverse, coefficient-domain step, forward
+    route moddown;            // rb set: `inverse` (scaled constants) on the source primes, then rb->launch_moddown; else two inverses, launch_moddown_coeff, forward
 };
 
 }  // namespace agx
@@ -110,6 +111,13 @@ struct agx_ntt_basis {
     uint32_t src_first = 0, src_count = 0, dst_first = 0, dst_count = 0;
     agx::device_buf<ulonglong2> d_dinv;      // [S]    {D_i^-1 mod q_i, quotient}
     agx::device_buf<ulonglong2> d_mat;       // [T][S] {D_i mod q_j, quotient}
+    // agx_ntt_basis_mod_down
+    agx::device_buf<ulonglong2> d_dall;      // [T]    {D^-1 mod q_j, quotient}; {0, 0} where D is not invertible modulo q_j
+    bool moddown_legal = false;              // every D^-1 mod q_j exists (no target modulus is a source modulus); judged at the call
+    // [S]: the plan's prime_consts of the source primes with n_inv, w1n and their quotients multiplied by D_i^-1 mod q_i.  The plan's inverse on the
+    // view of the source primes with `consts` pointing here writes y_i = INTT_i(x_i) D_i^-1 mod q_i in [0,q_i): every inverse family reads its
+    // last-stage constants from its view's consts, and the transform is linear.
+    agx::device_buf<agx::prime_consts> d_src_consts;
 };
 
 namespace agx {

@@ -511,6 +511,108 @@ extend_rb2(const uint64_t* __restrict__ x, uint64_t* __restrict__ out, const pri
     f.store_last_layout(acc, out, base, live);
 }
 
+// The second launch of agx_ntt_basis_mod_down (ModDown of a hybrid key switch on NTT-form frames) for ONE target prime j of a basis:
+// out_j = (xq_j - NTT_j(sum_i y_i (D_i mod q_j))) D^-1 mod q_j, one frame on chip.  y: dense [S][batch][n], y_i = p_i D_i^-1 mod q_i in [0,q_i) as
+// the first launch left it in the scratch -- the plan's inverse on the source slabs with n^-1 D_i^-1 for n^-1 -- so there is no basis_scale here:
+// S Shoup products per output word, where extend_rb2 does 2 S.  The accumulation is extend_rb2's: the frame's words of every source arrive in the
+// pass-0 layout, GRP registers at a time and one group ahead of the one being folded in (plain loads: the T workgroups of a frame all read them),
+// one 64-bit accumulator per coefficient in [0,2q_j), which the forward passes take as it is.  The finish is rescale_rb2's: in the last pass's
+// layout every lane streams in its own C consecutive words of xq_j (16-byte loads requested ahead; lazy values allowed) and forms
+// (xq_j - acc) D^-1 mod q_j (rescale_finish: the lazy form for q <= 2^60, reduce_4q first otherwise), and the result leaves through the forward
+// kernels' store.  8n(S + 2) bytes per (target, frame) as requested by the workgroup.
+// out may BE xq (in place), by rescale_rb2's argument: a wave stores exactly the 64 C contiguous words its own lanes loaded from xq, and
+// store_last_layout relays them through the image behind a wavefront-scope release / acquire pair.  xq and out are therefore not __restrict__.
+// Block order and the three pinned scalars (group, base, yf) as in extend_rb2.
+template <int L, int R, int PPB, int ARITH, int MINW>
+__global__ void __launch_bounds__((1 << (L - R)) * PPB, (MINW > AGX_MULHAT_MAXW ? AGX_MULHAT_MAXW : MINW))
+moddown_rb2(const uint64_t* xq, const uint64_t* __restrict__ y, uint64_t* out, const prime_consts* __restrict__ consts, const ulonglong2* __restrict__ mat,
+            const ulonglong2* __restrict__ dall, const twpair* __restrict__ tw_rb, uint32_t pairs_per_prime, uint64_t frames_x, int64_t prime_stride,
+            int64_t poly_stride, uint32_t num_src, uint32_t dst_first, uint32_t num_dst) {
+    using F = frame_of<L, R, ARITH>;
+    constexpr int C = F::C, T = F::T;
+    static_assert(T >= 64, "one frame must span whole waves");
+    F f;
+    f.tid = threadIdx.x & (T - 1);
+    const uint32_t slot = PPB == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / T));      // a frame spans whole waves: wave-uniform
+    uint32_t group = blockIdx.x / num_dst;      // out of the vector unit: pinned to a scalar register (extend_rb2)
+    asm volatile("" : "+s"(group));
+    const uint32_t j = blockIdx.x - group * num_dst;
+    uint64_t fx = (uint64_t)group * PPB + slot;
+    const bool live = fx < frames_x;
+    if (!live) fx = frames_x - 1;                         // keep every thread on the barriers
+    const uint32_t prime = dst_first + j;
+    const uint64_t q = consts[prime].q, q2 = q << 1;
+    f.init_consts(q, consts[prime].est);
+    // q <= 2^60: rescale_finish takes both operands in [0,4q), so the transform may skip its last conditional subtracts and xq_j needs no reduction
+    f.lazy_out = F::LAZY16;
+    f.slab = reinterpret_cast<uint64_t*>(agx_dyn_lds) + (size_t)slot * F::slab_elems;
+    int64_t base = (int64_t)j * prime_stride + (int64_t)fx * poly_stride;
+    constexpr int GRP = 4, NG = C / GRP;      // registers per group of loads (y: GRP words; xq: two 16-byte loads), groups per thread
+    static_assert(C % GRP == 0 && NG % 2 == 0, "whole groups, and group 0 of every source in buffer 0");
+    const uint64_t* yf = y + (int64_t)fx * poly_stride;      // the frame under source 0 (wave-uniform: lanes add tid)
+    asm volatile("" : "+s"(base), "+s"(yf));      // wave-uniform, scalar registers of their own (extend_rb2)
+    const ulonglong2* row = mat + (size_t)j * num_src;
+    uint64_t acc[C];
+    {
+        uint64_t z[2][GRP];
+#pragma unroll
+        for (int r = 0; r < C; ++r) acc[r] = 0;
+        static_for<0, GRP>([&](auto I) { z[0][I] = yf[f.tid + (uint32_t)(int)I * T]; });
+        for (uint32_t i = 0; i < num_src; ++i) {      // wave-uniform
+            const ulonglong2 c = row[i];
+            const uint64_t* cur = yf + (int64_t)i * prime_stride;
+            const uint64_t* nxt = yf + (int64_t)(i + 1 < num_src ? i + 1 : i) * prime_stride;      // behind the last source: its own first group again (a cache hit, dropped)
+            static_for<0, NG>([&](auto Gq) {
+                constexpr int g = Gq;
+                const uint64_t* pg = g + 1 < NG ? cur + (uint32_t)((g + 1) * GRP) * T : nxt;      // opaque and scalar: every group shares the GRP lane offsets (extend_rb2)
+                asm volatile("" : "+s"(pg));
+                static_for<0, GRP>([&](auto I) { z[(g + 1) & 1][I] = pg[f.tid + (uint32_t)(int)I * T]; });
+                __builtin_amdgcn_sched_barrier(0);
+                static_for<0, GRP>([&](auto I) {
+                    constexpr int r = g * GRP + (int)I;
+                    asm volatile("" : "+v"(acc[r]));
+                    acc[r] = basis_accumulate(acc[r], z[g & 1][I], c.x, c.y, q, q2);
+                    asm volatile("" : "+v"(acc[r]));
+                });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        }
+    }
+    const ulonglong2 d = dall[j];      // {D^-1 mod q_j, quotient}: wave-uniform
+    constexpr bool EARLY = !F::STREAM_TW && !F::SPLIT && F::NP >= 2 && NG <= 2;      // as mulhat_rb2 / rescale_rb2
+    const bhat_pair* xp = reinterpret_cast<const bhat_pair*>(xq + base + (uint32_t)f.tid * C);
+    bhat_pair w[EARLY ? NG : 2][GRP / 2];
+    auto request = [&](auto Gq) {
+        constexpr int g = Gq;
+        static_for<0, GRP / 2>([&](auto I) { w[EARLY ? g : (g & 1)][I] = xp[g * (GRP / 2) + (int)I]; });
+    };
+    if constexpr (EARLY) {
+        f.template forward_passes<0, F::NP - 1>(acc, tw_rb + (size_t)prime * pairs_per_prime);
+        static_for<0, NG>(request);
+        f.template forward_passes<F::NP - 1, F::NP>(acc, tw_rb + (size_t)prime * pairs_per_prime);
+    } else {
+        f.forward(acc, tw_rb + (size_t)prime * pairs_per_prime);
+        request(std::integral_constant<int, 0>{});
+    }
+    static_for<0, NG>([&](auto Gq) {
+        constexpr int g = Gq;
+        if constexpr (!EARLY && g + 1 < NG) request(std::integral_constant<int, g + 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<0, GRP>([&](auto I) {
+            constexpr int i = I, r = g * GRP + i;
+            uint64_t v = w[EARLY ? g : (g & 1)][i / 2][i & 1];
+            // beyond 2^60 the difference wants xq_j (lazy: below 4q, which may not fit 64 bits -- reduce_4q never forms it) and the transform's
+            // result, which is then fully reduced, below q
+            if constexpr (!F::LAZY16) v = reduce_4q(v, q, q2);
+            asm volatile("" : "+v"(acc[r]));
+            acc[r] = rescale_finish<F::LAZY16>(v, acc[r], d.x, d.y, q);
+            asm volatile("" : "+v"(acc[r]));
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    });
+    f.store_last_layout(acc, out, base, live);
+}
+
 // ---- host side: pass tables, launch glue and registry entries, written once for every kernel family ---------------------------------
 // (the 32-bit kernels of rb32_kernels.hpp and the wave-packed kernels of wp_kernels.hpp bring their own shape struct and nothing else)
 
@@ -630,6 +732,17 @@ hipError_t launch_extend_t(const plan_view& pv, const basis_view& bv, const uint
     return hipGetLastError();
 }
 
+// agx_ntt_basis_mod_down's second launch: pv is the view of the whole plan, the frame layout describes xq, y and out alike (dense); a linear grid, the
+// target prime fastest (moddown_rb2)
+template <class S, auto K>
+hipError_t launch_moddown_t(const plan_view& pv, const basis_view& bv, const uint64_t* xq, const uint64_t* y, uint64_t* out, const frame_layout& fl, hipStream_t s) {
+    const uint64_t blocks = (uint64_t)bv.dst_count * ((fl.batch + S::fpb - 1) / S::fpb);
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(K, dim3((unsigned)blocks), dim3(S::threads), S::lds, s, xq, y, out, pv.consts, bv.mat, bv.dall, pv.tw_rb, pv.rb->table_pairs, fl.batch,
+                       fl.prime_stride, fl.poly_stride, bv.src_count, bv.dst_first, bv.dst_count);
+    return hipGetLastError();
+}
+
 template <int L, int R, int ARITH, int MINW>
 hipError_t launch_mul_park_t(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, const frame_layout& fl, hipStream_t s) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
@@ -700,8 +813,9 @@ hipError_t launch_inv_rb2_dloop_t(const plan_view& pv, const uint64_t* in, const
 template <class S>
 constexpr rb_entry shape_entry(int id, decltype(rb_entry::launch) fwd, decltype(rb_entry::init) init, decltype(rb_entry::launch_inv) inv,
                                decltype(rb_entry::launch_mul) mul, decltype(rb_entry::launch_mulhat) mulhat = nullptr,
-                               decltype(rb_entry::launch_rescale) rescale = nullptr, decltype(rb_entry::launch_extend) extend = nullptr) {
-    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow, mulhat, rescale, extend};
+                               decltype(rb_entry::launch_rescale) rescale = nullptr, decltype(rb_entry::launch_extend) extend = nullptr,
+                               decltype(rb_entry::launch_moddown) moddown = nullptr) {
+    return rb_entry{id, S::log_n, S::r, S::fpb, S::min_waves, S::table_pairs, S::lds, S::build, fwd, init, S::arith, inv, mul, 0, 0, S::narrow, mulhat, rescale, extend, moddown};
 }
 
 // forward, inverse and the product with both forward results in registers, one workgroup per S::fpb frames each (every family has this form)
@@ -712,7 +826,7 @@ constexpr rb_entry make_entry3(int id) {
 
 // PPB frames per workgroup (the n = 4096 defaults: R = 3, 8 waves/SIMD; n = 1024 with streamed twiddles, where two frames of 2^R coefficients still fit
 // the register budget and the parked product's round trip through c's frame would cost more); the product kernel at MULW waves per SIMD
-// and the product by a pre-transformed operand, the rescale kernel and the base-extension kernel (one frame in registers; at most AGX_MULHAT_MAXW waves per SIMD)
+// and the product by a pre-transformed operand, the rescale kernel and the base-extension and ModDown kernels (one frame in registers; at most AGX_MULHAT_MAXW waves per SIMD)
 template <int L, int R, int PPB, int ARITH, int MINW, int MULW = MINW>
 constexpr rb_entry make_entry2(int id) {
     using S = rb2_shape<L, R, PPB, ARITH, MINW>;
@@ -722,8 +836,9 @@ constexpr rb_entry make_entry2(int id) {
     constexpr auto mulhat = &mulhat_rb2<L, R, PPB, ARITH, MINW>;
     constexpr auto rescale = &rescale_rb2<L, R, PPB, ARITH, MINW>;
     constexpr auto extend = &extend_rb2<L, R, PPB, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat, rescale, extend>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>,
-                          &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>);
+    constexpr auto moddown = &moddown_rb2<L, R, PPB, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat, rescale, extend, moddown>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>,
+                          &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>, &launch_moddown_t<S, moddown>);
 }
 
 // forward kernel only (a plan's forward companion: rb_entry::fwd_companion), one frame per workgroup
@@ -735,7 +850,7 @@ constexpr rb_entry make_entry_single_fwd(int id) {
 }
 
 // the streamed single-frame kernels (reg_s<n>.hip): one frame in registers per workgroup at any time (R = 5: a second frame cannot
-// be held): forward, inverse, the fused product by polymul_rb2_park / polysquare_rb2, the product by a pre-transformed operand, the rescale kernel and the base-extension kernel
+// be held): forward, inverse, the fused product by polymul_rb2_park / polysquare_rb2, the product by a pre-transformed operand, the rescale kernel, the base-extension and ModDown kernels
 template <int L, int R, int ARITH, int MINW>
 constexpr rb_entry make_entry_single(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
@@ -744,8 +859,10 @@ constexpr rb_entry make_entry_single(int id) {
     constexpr auto mulhat = &mulhat_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto rescale = &rescale_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto extend = &extend_rb2<L, R, 1, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat, rescale, extend>,
-                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, mulhat>, &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>);
+    constexpr auto moddown = &moddown_rb2<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat, rescale, extend, moddown>,
+                          &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, mulhat>, &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>,
+                          &launch_moddown_t<S, moddown>);
 }
 
 // entry e with forward calls of its plans routed to the forward-only entry `id` (rb_entry::fwd_companion)
@@ -760,7 +877,8 @@ template <int L, int R, int ARITH, int MINW>
 hipError_t init_rb2_single_invloop_t() {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     const hipError_t e = allow_lds<S::lds, &fwd_rb2<L, R, 1, ARITH, MINW>, &inv_rb2_loop<L, R, ARITH, MINW>, &polymul_rb2_park<L, R, ARITH, MINW>,
-                                   &polysquare_rb2<L, R, ARITH, MINW>, &mulhat_rb2<L, R, 1, ARITH, MINW>, &rescale_rb2<L, R, 1, ARITH, MINW>, &extend_rb2<L, R, 1, ARITH, MINW>>();
+                                   &polysquare_rb2<L, R, ARITH, MINW>, &mulhat_rb2<L, R, 1, ARITH, MINW>, &rescale_rb2<L, R, 1, ARITH, MINW>, &extend_rb2<L, R, 1, ARITH, MINW>,
+                                   &moddown_rb2<L, R, 1, ARITH, MINW>>();
     return e != hipSuccess ? e : allow_lds<S::lds + kDloopMailboxBytes, &inv_rb2_dloop<L, R, ARITH, MINW>>();
 }
 template <int L, int R, int ARITH, int MINW>
@@ -768,7 +886,8 @@ constexpr rb_entry make_entry_single_invloop(int id) {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     return shape_entry<S>(id, &launch_fwd_t<S, &fwd_rb2<L, R, 1, ARITH, MINW>>, &init_rb2_single_invloop_t<L, R, ARITH, MINW>,
                           &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, &mulhat_rb2<L, R, 1, ARITH, MINW>>,
-                          &launch_rescale_t<S, &rescale_rb2<L, R, 1, ARITH, MINW>>, &launch_extend_t<S, &extend_rb2<L, R, 1, ARITH, MINW>>);
+                          &launch_rescale_t<S, &rescale_rb2<L, R, 1, ARITH, MINW>>, &launch_extend_t<S, &extend_rb2<L, R, 1, ARITH, MINW>>,
+                          &launch_moddown_t<S, &moddown_rb2<L, R, 1, ARITH, MINW>>);
 }
 
 }  // namespace AGX_TU

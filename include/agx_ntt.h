@@ -39,7 +39,7 @@ typedef enum agx_status {
     AGX_OK = 0,
     AGX_ERR_NULL_POINTER = 1,   /* a required pointer argument is NULL                      */
     AGX_ERR_BAD_SIZE = 2,       /* n is not a power of two in [AGX_NTT_MIN_N, AGX_NTT_MAX_N] */
-    AGX_ERR_BAD_MODULUS = 3,    /* q >= 2^62, q even, q != 1 (mod 2n) or (plan_create_auto) q composite; rescale: q_i == q_last */
+    AGX_ERR_BAD_MODULUS = 3,    /* q >= 2^62, q even, q != 1 (mod 2n) or (plan_create_auto) q composite; rescale: q_i == q_last; mod_down: a target modulus equal to a source modulus */
     AGX_ERR_BAD_ROOT = 4,       /* psi is not a primitive 2n-th root of unity mod q           */
     AGX_ERR_BAD_ARGUMENT = 5,   /* zero primes, negative stride, a layout extent past 2^60 words, overlapping in/out, an even or too large Galois element, an unknown form or mode, ... */
     AGX_ERR_NO_DEVICE = 6,      /* no usable HIP device                                       */
@@ -268,6 +268,38 @@ AGX_API int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan
 AGX_API int agx_ntt_basis_destroy(agx_ntt_basis* basis);
 AGX_API int agx_ntt_basis_info(const agx_ntt_basis* basis, uint32_t* src_first, uint32_t* src_count, uint32_t* dst_first, uint32_t* dst_count, int* launches_ntt_form);
 AGX_API int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream);
+
+/* ModDown of a hybrid key switch on NTT-form frames: the division of a polynomial known modulo the targets AND the sources of a basis by D = prod q_i
+ * over the sources (the special primes), in one call.  Inputs, both in NTT form exactly as agx_ntt_forward / agx_ntt_forward_lazy of the plan write
+ * them (bit-reversed order, values in [0,q) or lazy): d_xq dense [T][batch][n], slab j under plan prime dst_first + j; d_xp dense [S][batch][n], slab i
+ * under plan prime src_first + i.  Per coefficient of the underlying polynomials (a_j, p_i the coefficient forms of the slabs), with D_i = D / q_i:
+ *   y_i = p_i (D_i^-1 mod q_i) mod q_i in [0, q_i),    V = sum_i y_i D_i (an integer, V = X_P + u D, 0 <= u < S),    out_j = (a_j - V) (D^-1 mod q_j) mod q_j,
+ * and d_out, dense [T][batch][n], holds NTT_j(out_j), fully reduced: d_out_j = (xq_j - NTT_j(V mod q_j)) D^-1 mod q_j word for word.  This is the
+ * APPROXIMATE ModDown of every hybrid key switch, floor(X / D) - u with the u of agx_ntt_basis_extend: a deterministic integer formula, exact against
+ * big-integer arithmetic.  With S = 1 it is agx_ntt_rescale(..., AGX_RESCALE_FLOOR) word for word.  There is NO ROUNDING MODE here (adding
+ * floor(D / 2) first is a follow-up).
+ * d_scratch: S*batch*n words of device memory; it receives the scaled coefficient form y_i of the source slabs, its contents afterwards are
+ * unspecified.  It may be exactly d_xp: the caller thereby GIVES THOSE SLABS UP, as agx_ntt_rescale allows for its last slab; otherwise it is disjoint
+ * from d_xp and d_xp is left unchanged.  Aliasing: d_out == d_xq is allowed (in place); any other contact between d_out and d_xq, d_out touching d_xp or
+ * the scratch, the scratch touching d_xq, or the scratch partially overlapping d_xp: AGX_ERR_BAD_ARGUMENT, nothing written.  Pointers need 8-byte
+ * alignment only.  Ranges that meet end to end do not touch.
+ * Status order: a NULL pointer: AGX_ERR_NULL_POINTER; alignment, a layout extent past 2^60 words, on the two-launch route T ceil(batch / frames per
+ * workgroup) workgroups past 2^31 - 1, overlap: AGX_ERR_BAD_ARGUMENT; a target modulus equal to a source modulus -- D is not invertible there; any basis
+ * whose ranges overlap -- AGX_ERR_BAD_MODULUS (decided at the call: agx_ntt_basis_create accepts such bases for agx_ntt_basis_extend); a plan without
+ * inverse tables: AGX_ERR_NO_INVERSE; batch == 0: AGX_OK, nothing launched.  Asynchronous on `stream`, allocates and synchronises nothing
+ * (capturable into a hipGraph); agx_ntt_plan_set_variant between calls stays legal.
+ * TWO launches for n = 1024 ... 32768 whenever some modulus is 2^31 or larger: the plan's inverse of the S source slabs into the scratch with
+ * n^-1 D_i^-1 in the place of n^-1 (the inverse is linear, so it writes y_i itself, at no cost: the constants live in the basis, plan creation is
+ * unchanged and no second plan is needed); then, one target prime's frame on chip, the sum over the sources, the forward transform and the difference
+ * with xq_j as it streams in (T workgroups per frame; S Shoup products per output word) -- at every S up to 16 (profiles/r09_mod_down.md).
+ * Otherwise -- n <= 512, plans whose moduli are all below 2^31, plans forced onto AGX_VARIANT_LDS_RADIX2 -- the inverse of xq into out, the scaled
+ * inverse of xp into the scratch, one coefficient-domain pass over out and the plan's forward of out in place: four launches (seven at n = 32768 under
+ * AGX_VARIANT_LDS_RADIX2, whose transforms take two each); no memory beyond the scratch, and in place works as in agx_ntt_rescale.
+ * agx_ntt_basis_mod_down_info: the kernel launches a call takes under the plan's CURRENT variant; `launches` may be NULL.
+ * Groups: no group form, as for agx_ntt_basis_extend: one basis per shard, called on that shard's device and stream. */
+AGX_API int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch,
+                                   uint64_t batch, void* stream);
+AGX_API int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launches);
 
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */

@@ -3,6 +3,7 @@ runs on paths bench.py's headline does not cover).
 Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes P --batch B --bits 60 --oop --launches K --variant ID]
        python3 tools/run_op.py --op auto --form {coeff,ntt} --galois G [--odd --reps 5 ...]   (agx_ntt_automorphism beside a device copy of the same words)
        python3 tools/run_op.py --op extend --src S [--dst T --only {both,fused,pair} --reps 5 ...]   (agx_ntt_basis_extend to NTT form beside the unfused pair)
+       python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent} --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
 Under the profiler: rocprofv3 ... -- python3 tools/run_op.py ...   (the interpreter itself after `--`, never this file: an
 `env` shebang hop after the profiler's preload has initialised the GPU is a forbidden exec on this pool)."""
 import argparse
@@ -17,7 +18,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -37,9 +38,16 @@ ap.add_argument("--odd", action="store_true", help="auto: both bases one word pa
 ap.add_argument("--reps", type=int, default=5, help="auto: timed repetitions of --launches calls each, alternating with the copy; medians are reported")
 ap.add_argument("--src", type=int, default=2, help="extend: source primes [0, S)")
 ap.add_argument("--dst", type=int, default=0, help="extend: target primes [0, T); 0 = every prime of the plan")
-ap.add_argument("--only", choices=["both", "fused", "pair"], default="both", help="extend: time the AGX_FORM_NTT call, the unfused pair, or both alternating (a counter run wants one)")
+ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent"], default=None,
+                help="extend: time the AGX_FORM_NTT call (fused), the unfused pair, or both alternating (default); moddown: the two-launch route (fused), the "
+                     "four-launch route on the same plan (generic: needs lib/libagxntt_diag.so through AGX_NTT_LIB), inverse + extend as before mod_down existed "
+                     "(parent), or all alternating (default).  A counter run wants one")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
+if args.op == "moddown":
+    args.dst = args.dst or 4
+    args.primes = args.src + args.dst      # targets [0, T), sources [T, T + S)
+args.only = args.only or ("all" if args.op == "moddown" else "both")
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
 if args.variant is not None:
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + args.variant)
@@ -161,8 +169,89 @@ def run_extend():
     plan.close()
 
 
+def run_moddown():
+    """agx_ntt_basis_mod_down from the sources [T, T + S) to the targets [0, T), three ways alternating in one process:
+      fused   -- the call as the library routes it (two launches where the fused kernel serves);
+      generic -- the same call sent down the four-launch route on the same plan (AGX_NTT_MOD_DOWN_GENERIC=1, honoured by lib/libagxntt_diag.so only);
+      parent  -- what the library offered before mod_down: agx_ntt_inverse of the S source slabs on a plan over those primes, then
+                 agx_ntt_basis_extend(..., AGX_FORM_NTT); strictly less work (no subtraction from xq, no product by D^-1).
+    Prints us per call (median of --reps repetitions of --launches calls, min and max beside it) and the ratios."""
+    import statistics
+    import time
+
+    S, T = args.src, args.dst
+    basis = plan.basis(T, S, 0, T)
+    sources = agx.Plan(args.n, plan.moduli[T:], psi=[plan.psi(p) for p in range(T, T + S)])      # the parent's second plan, the same tables
+    if args.variant is not None:
+        sources.set_variant(agx.VARIANT_REGBLOCK_BASE + args.variant)
+    words = args.batch * args.n
+    x = torch.empty((T + S) * words, dtype=torch.int64, device="cuda")      # synthetic residues taken as NTT-form words: xq = slabs [0, T), xp = the rest
+    out, scratch = torch.empty(T * words, dtype=torch.int64, device="cuda"), torch.empty(S * words, dtype=torch.int64, device="cuda")
+    plan.fill_synthetic(x.data_ptr(), args.batch, 0, 42, stream)
+    xq, xp = x.data_ptr(), x.data_ptr() + 8 * T * words
+    diag = agx.LIB_PATH.endswith("libagxntt_diag.so")
+    if args.only in ("all", "generic") and not diag:
+        sys.exit("--only generic / all need lib/libagxntt_diag.so: AGX_NTT_LIB=agilex-ntt_amd/lib/libagxntt_diag.so (after `make -C agilex-ntt_amd diag`)")
+
+    def fused():
+        basis.mod_down(xq, xp, out.data_ptr(), scratch.data_ptr(), args.batch, stream)
+
+    def generic():
+        os.environ["AGX_NTT_MOD_DOWN_GENERIC"] = "1"
+        try:
+            basis.mod_down(xq, xp, out.data_ptr(), scratch.data_ptr(), args.batch, stream)
+        finally:
+            os.environ["AGX_NTT_MOD_DOWN_GENERIC"] = "0"
+
+    def parent():
+        sources.inverse(xp, scratch.data_ptr(), args.batch, stream)
+        basis.extend(scratch.data_ptr(), out.data_ptr(), args.batch, agx.FORM_NTT, stream)
+
+    launches = {"fused": basis.mod_down_launches(), "parent": 1 + basis.info()[4]}
+    if diag:
+        os.environ["AGX_NTT_MOD_DOWN_GENERIC"] = "1"
+        launches["generic"] = basis.mod_down_launches()
+        os.environ["AGX_NTT_MOD_DOWN_GENERIC"] = "0"
+    todo = [f for f in (fused, generic, parent) if args.only in ("all", f.__name__)]
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / args.launches      # us per call
+
+    t_end = time.perf_counter() + args.ramp_seconds
+    while time.perf_counter() < t_end:      # clock ramp
+        for _ in range(8):
+            for fn in todo:
+                fn()
+        torch.cuda.synchronize()
+    times = {fn.__name__: [] for fn in todo}
+    for _ in range(args.reps):
+        for fn in todo:
+            times[fn.__name__].append(timed(fn))
+    med = {k: statistics.median(t) for k, t in times.items()}
+    head = f"moddown n={args.n} S={S} T={T} batch={args.batch} bits={args.bits}:"
+    parts = [f"{name} ({launches[name]} launches) {med[name]:.1f} us per call (min {min(t):.1f} max {max(t):.1f})" for name, t in times.items()]
+    parts += [f"ratio fused/{other} {med['fused'] / med[other]:.3f}" for other in ("generic", "parent") if "fused" in med and other in med]
+    print(head, "; ".join(parts))
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "kernel_launches": launches}, open(args.report, "w"))
+    basis.close()
+    sources.close()
+    plan.close()
+
+
 if args.op == "auto":
     run_auto()
+    sys.exit(0)
+if args.op == "moddown":
+    run_moddown()
     sys.exit(0)
 if args.op == "extend":
     run_extend()
