@@ -62,6 +62,12 @@ ABI = {
     "agx_ntt_basis_extend": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_basis_mod_down": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_basis_mod_down_info": (_int, [_vp, ctypes.POINTER(_int)]),
+    "agx_ntt_inner_product": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _vp]),
+    "agx_ntt_keyswitch_create": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32]),
+    "agx_ntt_keyswitch_destroy": (_int, [_vp]),
+    "agx_ntt_keyswitch_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_int)]),
+    "agx_ntt_keyswitch_scratch_words": (_int, [_vp, _u64, _p64]),
+    "agx_ntt_keyswitch_apply": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
@@ -178,7 +184,7 @@ def kernel_source_sha16():
     import hashlib
 
     h = hashlib.sha256()
-    files = glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + [os.path.join(_HERE, "csrc", f) for f in ("rb_frame.hpp", "rb_kernels.hpp", "rb32_kernels.hpp", "wp_kernels.hpp", "rb_stream_opts.hpp", "rb_registry.hpp", "modarith.hpp", "ntt_kernels.hpp")]
+    files = glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + [os.path.join(_HERE, "csrc", f) for f in ("rb_frame.hpp", "rb_kernels.hpp", "rb32_kernels.hpp", "wp_kernels.hpp", "rb_stream_opts.hpp", "rb_registry.hpp", "modarith.hpp", "inner_reduce.hpp", "ntt_kernels.hpp")]
     for f in sorted(files):
         h.update(os.path.relpath(f, _HERE).encode())
         h.update(open(f, "rb").read())
@@ -331,6 +337,15 @@ class Plan:
         """Basis(self, ...): the fast base conversion from primes [src_first, src_first + src_count) to [dst_first, dst_first + dst_count)"""
         return Basis(self, src_first, src_count, dst_first, dst_count)
 
+    def inner_product(self, d_a, d_bhat, d_c, batch, terms, outputs=1, bhat_batch=None, stream=0):
+        """c_o = sum_t a_t o bhat_{t,o} mod q in one launch: d_a [terms][P][batch][n], d_bhat [terms][outputs][P][bhat_batch][n], d_c
+        [outputs][P][batch][n]; inputs in [0,4q), c fully reduced, out of place; bhat_batch: None = batch, or 1 (one key frame per prime)"""
+        _check(lib().agx_ntt_inner_product(self._h, d_a, d_bhat, d_c, batch, batch if bhat_batch is None else bhat_batch, terms, outputs, stream), "inner_product")
+
+    def keyswitch(self, q_count, p_first, p_count, alpha):
+        """KeySwitch(self, ...): the hybrid key switch at level Q = primes [0, q_count) with special primes [p_first, p_first + p_count)"""
+        return KeySwitch(self, q_count, p_first, p_count, alpha)
+
     def fill_synthetic(self, d_out, batch, first_poly=0, seed=42, stream=0):
         _check(lib().agx_ntt_fill_synthetic(self._h, d_out, batch, first_poly, seed, stream), "fill_synthetic")
 
@@ -397,6 +412,50 @@ class Basis:
     def close(self):
         if self._h:
             lib().agx_ntt_basis_destroy(self._h)
+            self._h = _vp(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+KEYSWITCH_MAX_DIGITS = 16
+INNER_MAX_TERMS, INNER_MAX_OUTPUTS = 16, 2
+
+
+class KeySwitch:
+    """One hybrid key switch (agx_ntt_keyswitch_*) on a plan: Q = primes [0, q_count), special primes [p_first, p_first + p_count) with
+    p_first >= q_count, digits of alpha primes.  `plan` is a Plan or a raw plan handle (one handle per DeviceGroup shard); it must outlive
+    the handle, and its device must be current here and at every call."""
+
+    def __init__(self, plan, q_count, p_first, p_count, alpha):
+        self.plan = plan      # keeps a Plan alive
+        self._h = _vp(None)
+        handle = plan._h if isinstance(plan, Plan) else plan
+        _check(lib().agx_ntt_keyswitch_create(ctypes.byref(self._h), handle, q_count, p_first, p_count, alpha), "keyswitch_create")
+
+    def info(self):
+        """(q_count, p_first, p_count, alpha, digits, launches): the shape, and the kernel launches of one apply under the plan's current variant"""
+        v = [_u32(0) for _ in range(5)]
+        launches = _int(0)
+        _check(lib().agx_ntt_keyswitch_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(launches)), "keyswitch_info")
+        return tuple(x.value for x in v) + (launches.value,)
+
+    def scratch_words(self, batch):
+        words = _u64(0)
+        _check(lib().agx_ntt_keyswitch_scratch_words(self._h, batch, ctypes.byref(words)), "keyswitch_scratch_words")
+        return words.value
+
+    def apply(self, d_chat, d_keyhat, d_out, d_scratch, batch, stream=0):
+        """d_chat [q_count][batch][n] and d_keyhat [digits][2][A][n] in NTT form (reduced or lazy) -> d_out [2][q_count][batch][n], fully
+        reduced; d_scratch: scratch_words(batch) words; no two of the four may touch"""
+        _check(lib().agx_ntt_keyswitch_apply(self._h, d_chat, d_keyhat, d_out, d_scratch, batch, stream), "keyswitch_apply")
+
+    def close(self):
+        if self._h:
+            lib().agx_ntt_keyswitch_destroy(self._h)
             self._h = _vp(None)
 
     def __del__(self):

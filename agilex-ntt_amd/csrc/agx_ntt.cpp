@@ -832,6 +832,139 @@ int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, con
     return AGX_OK;
 }
 
+int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
+                          uint32_t terms, uint32_t outputs, void* stream) {
+    if (!plan || !d_a || !d_bhat || !d_c) return AGX_ERR_NULL_POINTER;
+    if (terms == 0 || terms > AGX_INNER_MAX_TERMS || outputs == 0 || outputs > AGX_INNER_MAX_OUTPUTS || (bhat_batch != batch && bhat_batch != 1)) return AGX_ERR_BAD_ARGUMENT;
+    if (!aligned8(d_a) || !aligned8(d_bhat) || !aligned8(d_c)) return AGX_ERR_BAD_ARGUMENT;
+    if (!batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;      // from here on batch n < 2^46
+    // every operand is one dense range of `slabs` x frames x n words: layout_fits forms slabs frames n in 128 bits (terms outputs P <= 32 65535 slabs)
+    const uint32_t P = plan->num_primes, n = plan->n;
+    auto fits = [&](uint32_t slabs, uint64_t frames) { return layout_fits(n, slabs, frames, (int64_t)(frames * n), (int64_t)n); };
+    if (!fits(terms * P, batch) || !fits(terms * outputs * P, bhat_batch) || !fits(outputs * P, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t slab = batch * n, a_words = terms * P * slab, b_words = (uint64_t)terms * outputs * P * bhat_batch * n, c_words = outputs * P * slab;      // each <= 2^60
+    // out of place only, equal pointers included: c_o of a word is written once, but by a thread that other threads' reads of a and bhat do not wait for
+    if (ranges_touch(addr(d_c), c_words, addr(d_a), a_words) || ranges_touch(addr(d_c), c_words, addr(d_bhat), b_words)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (batch == 0) return AGX_OK;
+    AGX_HIP(launch_inner_product(plan->routes.forward, inner_primes{P, P, 0}, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, static_cast<hipStream_t>(stream)));
+    return AGX_OK;
+}
+
+int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha) {
+    if (!ks) return AGX_ERR_NULL_POINTER;
+    *ks = nullptr;
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    const keyswitch_shape shape{q_count, p_first, p_count, alpha};
+    if (!keyswitch_shape_ok(shape, plan->num_primes)) return AGX_ERR_BAD_ARGUMENT;
+    // two equal moduli among the active primes: some D_i or D_P has no inverse where ModUp or ModDown needs one
+    const uint32_t A = shape.active();
+    auto modulus = [&](uint32_t slot) { return plan->moduli[slot < q_count ? slot : p_first + (slot - q_count)]; };
+    for (uint32_t i = 0; i < A; ++i)
+        for (uint32_t j = i + 1; j < A; ++j)
+            if (modulus(i) == modulus(j)) return AGX_ERR_BAD_MODULUS;
+    if (int rc = check_plan(plan)) return rc;
+    return guarded([&]() -> int {
+        std::unique_ptr<agx_ntt_keyswitch> k(new (std::nothrow) agx_ntt_keyswitch);
+        if (!k) return AGX_ERR_ALLOC;
+        k->plan = plan, k->shape = shape;
+        k->up.reserve(2 * shape.digits());
+        auto add = [&](uint32_t sf, uint32_t sc, uint32_t df, uint32_t dc) {
+            agx_ntt_basis* b = nullptr;
+            const int rc = agx_ntt_basis_create(&b, plan, sf, sc, df, dc);
+            if (rc == AGX_OK) k->up.push_back(b);      // capacity reserved: the handle owns b from here
+            return rc;
+        };
+        for (uint32_t d = 0; d < shape.digits(); ++d) {
+            uint32_t first, count;
+            keyswitch_digit(shape, d, &first, &count);
+            if (!shape.apart()) {
+                if (int rc = add(first, count, 0, A)) return rc;
+            } else {
+                if (int rc = add(first, count, 0, q_count)) return rc;
+                if (int rc = add(first, count, p_first, p_count)) return rc;
+            }
+        }
+        if (int rc = agx_ntt_basis_create(&k->down, plan, p_first, p_count, 0, q_count)) return rc;
+        *ks = k.release();
+        return AGX_OK;
+    });
+}
+
+int agx_ntt_keyswitch_destroy(agx_ntt_keyswitch* ks) {
+    delete ks;      // the bases go with it
+    return AGX_OK;
+}
+
+int agx_ntt_keyswitch_info(const agx_ntt_keyswitch* ks, uint32_t* q_count, uint32_t* p_first, uint32_t* p_count, uint32_t* alpha, uint32_t* digits, int* launches) {
+    if (!ks) return AGX_ERR_NULL_POINTER;
+    if (q_count) *q_count = ks->shape.q_count;
+    if (p_first) *p_first = ks->shape.p_first;
+    if (p_count) *p_count = ks->shape.p_count;
+    if (alpha) *alpha = ks->shape.alpha;
+    if (digits) *digits = ks->shape.digits();
+    if (launches) {
+        // the inverse on Q + what every ModUp basis reports + the inner product + two ModDown calls, each under the plan's current variant
+        int extend[2 * kKeyswitchMaxDigits], down = 0;
+        for (size_t i = 0; i < ks->up.size(); ++i) (void)agx_ntt_basis_info(ks->up[i], nullptr, nullptr, nullptr, nullptr, &extend[i]);
+        (void)agx_ntt_basis_mod_down_info(ks->down, &down);
+        *launches = keyswitch_launches(inverse_launches(ks->plan), extend, (uint32_t)ks->up.size(), down);
+    }
+    return AGX_OK;
+}
+
+int agx_ntt_keyswitch_scratch_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* words) {
+    if (!ks || !words) return AGX_ERR_NULL_POINTER;
+    keyswitch_scratch part;
+    if (!keyswitch_scratch_partition(ks->shape, ks->plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;
+    *words = part.total;
+    return AGX_OK;
+}
+
+int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!ks || !d_chat || !d_keyhat || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    const uint32_t Q = k.q_count, A = k.active(), digits = k.digits(), n = plan->n;
+    if (!aligned8(d_chat) || !aligned8(d_keyhat) || !aligned8(d_out) || !aligned8(d_scratch)) return AGX_ERR_BAD_ARGUMENT;
+    // batch past the grid limit; A workgroups per group of frames on the one-launch ModUp and the two-launch ModDown (at least one frame per workgroup)
+    if (!batch_fits_grid(plan, batch) || (uint64_t)A * batch > 0x7fffffffull) return AGX_ERR_BAD_ARGUMENT;
+    keyswitch_scratch part;
+    if (!keyswitch_scratch_partition(k, n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;      // every extent below is a part of the scratch's or smaller
+    const uint64_t slab = batch * n, chat_words = Q * slab, out_words = 2 * chat_words, key_words = (uint64_t)digits * 2 * A * n;
+    const uintptr_t base[4] = {addr(d_chat), addr(d_keyhat), addr(d_out), addr(d_scratch)};
+    const uint64_t words[4] = {chat_words, key_words, out_words, part.total};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j)
+            if (ranges_touch(base[i], words[i], base[j], words[j])) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint64_t *coeff = d_scratch + part.coeff, *ext = d_scratch + part.ext, *acc = d_scratch + part.acc;
+    // (1) coeff_j <- INTT_j(chat_j) in [0, q_j): the plan's inverse on the view of primes [0, Q), as ModDown runs it on its sources: no second plan
+    const frame_layout fl = dense(plan, batch);
+    const route qr = prime_range(plan->routes.inverse, 0, Q);
+    AGX_HIP(qr.rb ? qr.rb->launch_inv(qr, d_chat, nullptr, coeff, fl, s) : launch_inverse_radix2(qr, d_chat, coeff, fl, s));
+    // (2) ext_d <- NTT_j(e_{d,j}) for every active j: agx_ntt_basis_extend of digit d's slabs of coeff, routes as that call chooses them.  A digit's
+    // own slabs are transformed again (they come out as chat_j reduced); copying them instead was not measured, so it is not done.
+    for (uint32_t d = 0, b = 0; d < digits; ++d) {
+        const uint64_t* x = coeff + (uint64_t)d * k.alpha * slab;
+        uint64_t* e = ext + (uint64_t)d * A * slab;
+        if (int rc = agx_ntt_basis_extend(ks->up[b++], x, e, batch, AGX_FORM_NTT, stream)) return rc;
+        if (k.apart())
+            if (int rc = agx_ntt_basis_extend(ks->up[b++], x, e + Q * slab, batch, AGX_FORM_NTT, stream)) return rc;
+    }
+    // (3) acc_o <- sum_d ext_d o key_{d,o} over the active primes: one launch, the key broadcast over the batch
+    AGX_HIP(launch_inner_product(plan->routes.forward, inner_primes{A, Q, k.p_first - Q}, ext, d_keyhat, acc, batch, 1, digits, 2, s));
+    // (4) out_o <- ModDown of acc_o, its special slabs given up as the scratch
+    for (uint32_t o = 0; o < 2; ++o) {
+        uint64_t* xq = acc + (uint64_t)o * A * slab;
+        if (int rc = agx_ntt_basis_mod_down(ks->down, xq, xq + Q * slab, d_out + o * chat_words, xq + Q * slab, batch, stream)) return rc;
+    }
+    return AGX_OK;
+}
+
 int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly, uint64_t seed, void* stream) {
     if (!plan || !d_out) return AGX_ERR_NULL_POINTER;
     int rc = check_plan(plan);

@@ -10,6 +10,7 @@
 // by VALU integer multiply issue and HBM bandwidth.
 #include "rb_registry.hpp"
 #include "modarith.hpp"
+#include "inner_reduce.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -199,6 +200,65 @@ __global__ void pointwise_bhat_kernel(uint64_t* __restrict__ c, const uint64_t* 
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint64_t v = bp[(int64_t)(i >> log_n) * bhat_poly_stride + (int64_t)(i & ((1ull << log_n) - 1ull))];
         cp[i] = mul_mod_barrett(reduce_4q(cp[i], k.q, q2), reduce_4q(v, k.q, q2), bk);
+    }
+}
+
+// agx_ntt_inner_product: c_o = sum_t a_t o bhat_{t,o} mod q on NTT-form frames.  A streaming kernel: no LDS, no barrier, no table; blockIdx.y is
+// the slot of a prime in the call's list, grid-stride over the slot's batch x n words.  W is one word or a 16-byte pair (all three bases 16-byte
+// aligned; n is even, so every stride below is a whole number of pairs).  Inputs in [0, 4q) are reduced first, the products are summed in 128
+// bits and reduced once (inner_reduce.hpp has the range argument).  terms and OUT are wave-uniform.  The terms go in groups of up to four: the
+// loads of a group -- 4 words of a and 4 OUT of the key, per lane of W -- are all issued before the arithmetic on them, and the unrolled next
+// group's loads do not depend on it; a group of sixteen would hold 48 W in registers.  A broadcast key (one frame per prime) is re-read by every
+// frame: the repeats hit L2, nothing is kept across frames.  A twin that held the key words in registers across eight frames was built and measured
+// (profiles/r10_keyswitch.md): 1 ... 3 % slower at n = 4096, 3 ... 8 % faster at n = 16384 with a spill in its two-output pair form; deleted.
+struct inner_args {
+    uint64_t per_prime;                      // W per slot of a and c: batch n / lanes
+    uint64_t a_term, c_out;                  // strides in W: A per_prime
+    uint64_t b_prime, b_out, b_term;         // key strides in W: bhat_batch n / lanes, A b_prime, outputs b_out
+    uint32_t frame_mask, broadcast;          // n / lanes - 1; 1: the key index is the position within the frame
+    uint32_t terms, split, skip;             // slot y serves plan prime y (y < split) or y + skip: Q followed by special primes that lie apart
+};
+
+__device__ __forceinline__ void inner_lanes(acc128* s, uint64_t a, uint64_t b, uint64_t q, uint64_t q2) { acc_mul_add(s[0], reduce_4q(a, q, q2), reduce_4q(b, q, q2)); }
+__device__ __forceinline__ void inner_lanes(acc128* s, ulonglong2 a, ulonglong2 b, uint64_t q, uint64_t q2) {
+    acc_mul_add(s[0], reduce_4q(a.x, q, q2), reduce_4q(b.x, q, q2));
+    acc_mul_add(s[1], reduce_4q(a.y, q, q2), reduce_4q(b.y, q, q2));
+}
+__device__ __forceinline__ void inner_store(uint64_t* p, const acc128* s, const prime_consts& k) { *p = acc_reduce(s[0], k.q, k.mu_hi, k.mu_lo); }
+__device__ __forceinline__ void inner_store(ulonglong2* p, const acc128* s, const prime_consts& k) {
+    *p = make_ulonglong2(acc_reduce(s[0], k.q, k.mu_hi, k.mu_lo), acc_reduce(s[1], k.q, k.mu_hi, k.mu_lo));
+}
+
+template <int OUT, class W>
+__global__ void inner_product_kernel(const W* __restrict__ a, const W* __restrict__ bhat, W* __restrict__ c, const prime_consts* __restrict__ consts, inner_args g) {
+    constexpr int kLanes = sizeof(W) / 8, kGroup = 4;
+    const uint32_t slot = blockIdx.y;
+    const prime_consts k = consts[slot < g.split ? slot : slot + g.skip];
+    const uint64_t q2 = k.q << 1;
+    const W* ap = a + (uint64_t)slot * g.per_prime;
+    const W* bp = bhat + (uint64_t)slot * g.b_prime;
+    W* cp = c + (uint64_t)slot * g.per_prime;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t bi = g.broadcast ? (i & g.frame_mask) : i;
+        acc128 s[OUT][kLanes];
+        for (uint32_t t0 = 0; t0 < g.terms; t0 += kGroup) {
+            W av[kGroup], bv[kGroup][OUT];
+#pragma unroll
+            for (int u = 0; u < kGroup; ++u)
+                if (t0 + u < g.terms) {
+                    av[u] = ap[(t0 + u) * g.a_term + i];
+#pragma unroll
+                    for (int o = 0; o < OUT; ++o) bv[u][o] = bp[(t0 + u) * g.b_term + o * g.b_out + bi];
+                }
+#pragma unroll
+            for (int u = 0; u < kGroup; ++u)
+                if (t0 + u < g.terms) {
+#pragma unroll
+                    for (int o = 0; o < OUT; ++o) inner_lanes(s[o], av[u], bv[u][o], k.q, q2);
+                }
+        }
+#pragma unroll
+        for (int o = 0; o < OUT; ++o) inner_store(cp + o * g.c_out + i, s[o], k);
     }
 }
 
@@ -493,6 +553,33 @@ hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64
     const uint64_t per_prime = batch << pv.log_n;
     dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
     hipLaunchKernelGGL(pointwise_kernel, grid, dim3(256), 0, s, a, b, c, pv.consts, per_prime);
+    return hipGetLastError();
+}
+
+hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
+                                uint64_t bhat_batch, uint32_t terms, uint32_t outputs, hipStream_t s) {
+    const bool pairs = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bhat) | reinterpret_cast<uintptr_t>(c)) & 15u) == 0;
+    const uint32_t shift = pairs ? 1 : 0;      // n >= 2 is even: a frame is a whole number of pairs
+    inner_args g;
+    g.per_prime = (batch << pv.log_n) >> shift;
+    g.a_term = g.c_out = ip.count * g.per_prime;
+    g.b_prime = (bhat_batch << pv.log_n) >> shift;
+    g.b_out = ip.count * g.b_prime;
+    g.b_term = outputs * g.b_out;
+    g.frame_mask = (pv.n >> shift) - 1u;
+    g.broadcast = bhat_batch == 1 && batch != 1 ? 1u : 0u;
+    g.terms = terms, g.split = ip.split, g.skip = ip.skip;
+    const dim3 grid(grid_1d(g.per_prime, 256), ip.count);
+    auto go = [&](auto kernel, auto* ap, auto* bp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, cp, pv.consts, g); };
+    if (pairs) {
+        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2*>(a), *b2 = reinterpret_cast<const ulonglong2*>(bhat);
+        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(c);
+        if (outputs == 1) go(inner_product_kernel<1, ulonglong2>, a2, b2, c2);
+        else go(inner_product_kernel<2, ulonglong2>, a2, b2, c2);
+    } else {
+        if (outputs == 1) go(inner_product_kernel<1, uint64_t>, a, bhat, c);
+        else go(inner_product_kernel<2, uint64_t>, a, bhat, c);
+    }
     return hipGetLastError();
 }
 

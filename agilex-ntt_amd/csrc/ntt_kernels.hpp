@@ -83,6 +83,16 @@ hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64
 // c <- c o bhat in place on the dense [prime][batch][n] layout, bhat with strides of its own as above (the generic path of agx_ntt_polymul_ntt)
 hipError_t launch_pointwise_bhat(const plan_view& pv, uint64_t* c, const uint64_t* bhat, uint64_t batch, int64_t bhat_prime_stride,
                                  int64_t bhat_poly_stride, hipStream_t s);
+// agx_ntt_inner_product: c_o = sum_t a_t o bhat_{t,o} mod q for `count` primes of the plan in a given order: slot y of the operands is under plan
+// prime y for y < split and y + skip behind it (the public call: count = split = P; a key switch below the top level: Q, then the special primes).
+struct inner_primes {
+    uint32_t count = 0, split = 0, skip = 0;
+};
+// a dense [terms][count][batch][n], bhat dense [terms][outputs][count][bhat_batch][n] (bhat_batch = batch, or 1: one key frame per prime for every
+// frame), c dense [outputs][count][batch][n]; inputs in [0,4q), c in [0,q); out of place (c touches neither input).  pv: a view of the WHOLE plan
+// (only its constants are read).  16-byte accesses when all three bases allow them.  terms 1 .. 16, outputs 1 or 2.  One launch.
+hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
+                                uint64_t bhat_batch, uint32_t terms, uint32_t outputs, hipStream_t s);
 // the coefficient-domain step of agx_ntt_rescale's generic route: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i on the dense [prime][batch][n]
 // layout of pv's primes (a view of primes 0 .. P-2), u_i the lift of t[k] ([batch][n], coefficients of the last slab in [0, q_L)) to q_i
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s);

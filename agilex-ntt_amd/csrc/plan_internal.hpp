@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "keyswitch_layout.hpp"
 #include "ntt_kernels.hpp"
 
 constexpr int kMaxDevices = 64;          // size of every per-device table (kernel attributes set once, staging pool, one-shot plans); devices past it work uncached
@@ -118,6 +119,24 @@ struct agx_ntt_basis {
     // view of the source primes with `consts` pointing here writes y_i = INTT_i(x_i) D_i^-1 mod q_i in [0,q_i): every inverse family reads its
     // last-stage constants from its view's consts, and the transform is linear.
     agx::device_buf<agx::prime_consts> d_src_consts;
+};
+
+// agx_ntt_keyswitch_*: the shape and the bases of one hybrid key switch, and nothing of the plan but a pointer (as a basis: the plan outlives the
+// handle, agx_ntt_plan_set_variant between calls stays legal).  ModUp: one basis per digit with every active prime as a target when the special
+// primes follow Q directly; two per digit, targets Q and then targets P, when they lie apart (a basis names one contiguous range).  One ModDown
+// basis, sources the special primes, targets Q.
+struct agx_ntt_keyswitch {
+    const agx_ntt_plan* plan = nullptr;
+    agx::keyswitch_shape shape;
+    std::vector<agx_ntt_basis*> up;      // [digits] or [digits][2]
+    agx_ntt_basis* down = nullptr;
+    agx_ntt_keyswitch() = default;
+    agx_ntt_keyswitch(const agx_ntt_keyswitch&) = delete;
+    agx_ntt_keyswitch& operator=(const agx_ntt_keyswitch&) = delete;
+    ~agx_ntt_keyswitch() {
+        for (agx_ntt_basis* b : up) delete b;
+        delete down;
+    }
 };
 
 namespace agx {

@@ -39,9 +39,9 @@ typedef enum agx_status {
     AGX_OK = 0,
     AGX_ERR_NULL_POINTER = 1,   /* a required pointer argument is NULL                      */
     AGX_ERR_BAD_SIZE = 2,       /* n is not a power of two in [AGX_NTT_MIN_N, AGX_NTT_MAX_N] */
-    AGX_ERR_BAD_MODULUS = 3,    /* q >= 2^62, q even, q != 1 (mod 2n) or (plan_create_auto) q composite; rescale: q_i == q_last; mod_down: a target modulus equal to a source modulus */
+    AGX_ERR_BAD_MODULUS = 3,    /* q >= 2^62, q even, q != 1 (mod 2n) or (plan_create_auto) q composite; rescale: q_i == q_last; mod_down: a target modulus equal to a source modulus; keyswitch_create: two equal active moduli */
     AGX_ERR_BAD_ROOT = 4,       /* psi is not a primitive 2n-th root of unity mod q           */
-    AGX_ERR_BAD_ARGUMENT = 5,   /* zero primes, negative stride, a layout extent past 2^60 words, overlapping in/out, an even or too large Galois element, an unknown form or mode, ... */
+    AGX_ERR_BAD_ARGUMENT = 5,   /* zero primes, negative stride, a layout extent past 2^60 words, overlapping in/out, an even or too large Galois element, an unknown form or mode, a term, output or digit count out of range, ... */
     AGX_ERR_NO_DEVICE = 6,      /* no usable HIP device                                       */
     AGX_ERR_HIP = 7,            /* a HIP runtime call failed (agx_ntt_last_hip_error)         */
     AGX_ERR_ALLOC = 8,          /* host or device allocation failed                           */
@@ -300,6 +300,73 @@ AGX_API int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x
 AGX_API int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch,
                                    uint64_t batch, void* stream);
 AGX_API int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launches);
+
+/* The inner product of NTT-form frames: c_o = sum_t a_t o bhat_{t,o} mod q for o < outputs, one launch -- the centre of a hybrid key switch (the sum over
+ * the decomposition digits of digit times key), and any other multiply-accumulate against operands kept in NTT form.  P = the plan's primes:
+ *   d_a    dense [terms][P][batch][n]
+ *   d_bhat dense [terms][outputs][P][bhat_batch][n], bhat_batch == batch (frame by frame) or bhat_batch == 1 (one key frame per prime, used for every frame
+ *          of the batch: the key is stored once, not once per frame)
+ *   d_c    dense [outputs][P][batch][n]
+ * Every input word may lie in [0, 4 q_p), as agx_ntt_forward_lazy leaves them and agx_ntt_pointwise accepts them; the output is fully reduced.  Per word
+ *   c_o[p][b][i] = (sum_t (a_t[p][b][i] mod q_p) (bhat_{t,o}[p][b or 0][i] mod q_p)) mod q_p,
+ * exact against big-integer arithmetic.  Positions are not interpreted: any order that both operands share.  terms = outputs = 1 with bhat_batch == batch is
+ * agx_ntt_pointwise word for word.  terms <= AGX_INNER_MAX_TERMS = 16 is part of the contract: reduced operands give products below 2^124, sixteen of them
+ * stay below 2^128, so the sum is kept in 128 bits and reduced ONCE (the argument of AGX_BASIS_MAX_SRC; csrc/inner_reduce.hpp has the reduction's).
+ * Every plan serves, whatever its variant, size and moduli; no inverse tables are needed and plan creation is unchanged.
+ * Status order: a NULL pointer: AGX_ERR_NULL_POINTER; terms 0 or above 16, outputs 0 or above AGX_INNER_MAX_OUTPUTS = 2, bhat_batch neither batch nor 1; a
+ * pointer not 8-byte aligned; a batch past the grid limit or an operand's extent past 2^60 words; d_c's range touching d_a's or d_bhat's anywhere, equal
+ * pointers included (OUT OF PLACE ONLY, as agx_ntt_automorphism); the plan's device not current: AGX_ERR_BAD_ARGUMENT, nothing written; batch == 0: AGX_OK,
+ * nothing launched.  Asynchronous on `stream`, allocates and synchronises nothing, touches no plan state (capturable into a hipGraph).
+ * ONE launch: a grid-stride streaming kernel, no LDS, no barrier, no table; 16-byte accesses when all three bases are 16-byte aligned, 8-byte ones otherwise.
+ * It moves 8 (terms + outputs) bytes per word of a frame plus the key (8 terms outputs more per word with bhat_batch == batch; with bhat_batch == 1 the key's
+ * own size once, its repeats served by L2), where terms x outputs agx_ntt_pointwise calls and caller-side adds move about 24 per term and output.  Measured
+ * (profiles/r10_keyswitch.md; four 60-bit primes, two outputs, terms 2 ... 4, n = 4096 with 4,096 frames per prime and n = 16384 with 1,024): 0.89 ... 1.16 of the
+ * time of a device copy of the model's bytes; 0.17 ... 0.22 (bhat_batch == 1) and 0.36 ... 0.41 (bhat_batch == batch) of the pointwise-and-add form's. */
+#define AGX_INNER_MAX_TERMS 16
+#define AGX_INNER_MAX_OUTPUTS 2
+AGX_API int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
+                                  uint32_t terms, uint32_t outputs, void* stream);
+
+/* The RNS hybrid key switch of one ciphertext component in one call: NTT form in, NTT form out, at any level.
+ * Primes.  Q, the ciphertext's current level, is the plan's primes [0, q_count).  The special primes are [p_first, p_first + p_count), p_first >= q_count:
+ * they need not follow Q directly, which is what a level below the top looks like.  The ACTIVE primes are Q followed by the special primes, A = q_count +
+ * p_count of them.  Digit d is the primes [d alpha, min((d + 1) alpha, q_count)) -- the last digit may be short -- and digits = ceil(q_count / alpha).
+ *   d_chat    [q_count][batch][n]    NTT form of this plan, values in [0,q) or lazy; left unchanged
+ *   d_keyhat  [digits][2][A][n]      NTT form under the active primes in that order, reduced or lazy; shared by every frame of the batch
+ *   d_out     [2][q_count][batch][n] NTT form, fully reduced
+ *   d_scratch the words agx_ntt_keyswitch_scratch_words reports ((q_count + (digits + 2) A) batch n); contents unspecified afterwards
+ * Definition, per coefficient, from the formulas above:
+ *   1. c_j = INTT_j(chat_j) in [0, q_j) for j in Q.
+ *   2. For digit d with sources S_d, D_d = prod q_i and D_{d,i} = D_d / q_i:  y_i = c_i D_{d,i}^-1 mod q_i,  V_d = sum_i y_i D_{d,i},  e_{d,j} = V_d mod q_j for
+ *      every active j: agx_ntt_basis_extend's conversion (so e_{d,j} = c_j for j in S_d).
+ *   3. acc_{o,j} = sum_d NTT_j(e_{d,j}) o key_{d,o,j} mod q_j for o = 0, 1 and every active j: one agx_ntt_inner_product over the active primes.
+ *   4. out_{o,j} = agx_ntt_basis_mod_down's result with targets Q and sources the special primes on acc_o: (acc_{o,j} - NTT_j(V mod q_j)) D_P^-1 mod q_j.
+ * A deterministic integer formula: every output word is exact against big-integer arithmetic.
+ * A handle owns the bases -- one ModUp basis per digit when p_first == q_count, two per digit (targets Q, targets P) when the special primes lie apart, one
+ * ModDown basis -- and a pointer to the plan, none of its tables: the plan must outlive it, agx_ntt_plan_set_variant between calls stays legal, and the
+ * plan's device must be current at creation and at every apply.  Step 1 is the plan's inverse on the view of primes [0, q_count): no second plan.  Steps 2
+ * and 4 are the public calls themselves, so their route choices (profiles/r08_basis_extend.md, r09_mod_down.md) apply unchanged; ModDown's scratch is the
+ * special slabs of acc_o.  Everything is issued on the one stream passed.
+ *   create : NULL: AGX_ERR_NULL_POINTER; q_count == 0, p_count == 0, alpha == 0, alpha or p_count above AGX_BASIS_MAX_SRC, digits above
+ *            AGX_KEYSWITCH_MAX_DIGITS = 16, p_first < q_count, a range past P: AGX_ERR_BAD_ARGUMENT; two equal moduli among the active primes:
+ *            AGX_ERR_BAD_MODULUS.        destroy: NULL is fine.
+ *   info   : the shape, digits, and launches = the kernel launches of one apply under the plan's CURRENT variant: the inverse on Q + what agx_ntt_basis_info
+ *            reports for every ModUp basis + 1 (the inner product) + 2 x what agx_ntt_basis_mod_down_info reports.  Any out-pointer may be NULL.
+ *   scratch_words : NULL: AGX_ERR_NULL_POINTER; a count past 2^60 words: AGX_ERR_BAD_ARGUMENT.
+ *   apply  : status order: a NULL pointer: AGX_ERR_NULL_POINTER; a pointer not 8-byte aligned, a batch past the grid limit or with A batch above 2^31 - 1, an
+ *            extent past 2^60 words, any two of chat / keyhat / out / scratch touching anywhere, the plan's device not current: AGX_ERR_BAD_ARGUMENT, nothing
+ *            written; a plan without inverse tables: AGX_ERR_NO_INVERSE; batch == 0: AGX_OK, nothing launched.  Ranges that meet end to end do not touch.
+ *            Asynchronous on `stream`, allocates and synchronises nothing (capturable into a hipGraph).
+ * Groups: no group form, as for bases: each shard makes one handle on its own plan. */
+#define AGX_KEYSWITCH_MAX_DIGITS 16
+typedef struct agx_ntt_keyswitch agx_ntt_keyswitch;
+AGX_API int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha);
+AGX_API int agx_ntt_keyswitch_destroy(agx_ntt_keyswitch* ks);
+AGX_API int agx_ntt_keyswitch_info(const agx_ntt_keyswitch* ks, uint32_t* q_count, uint32_t* p_first, uint32_t* p_count, uint32_t* alpha, uint32_t* digits,
+                                   int* launches);
+AGX_API int agx_ntt_keyswitch_scratch_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* words);
+AGX_API int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch,
+                                    uint64_t batch, void* stream);
 
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */

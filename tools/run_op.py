@@ -4,6 +4,8 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op auto --form {coeff,ntt} --galois G [--odd --reps 5 ...]   (agx_ntt_automorphism beside a device copy of the same words)
        python3 tools/run_op.py --op extend --src S [--dst T --only {both,fused,pair} --reps 5 ...]   (agx_ntt_basis_extend to NTT form beside the unfused pair)
        python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent} --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
+       python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
+       python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
 Under the profiler: rocprofv3 ... -- python3 tools/run_op.py ...   (the interpreter itself after `--`, never this file: an
 `env` shebang hop after the profiler's preload has initialised the GPU is a forbidden exec on this pool)."""
 import argparse
@@ -18,7 +20,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "inner", "keyswitch"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -38,15 +40,24 @@ ap.add_argument("--odd", action="store_true", help="auto: both bases one word pa
 ap.add_argument("--reps", type=int, default=5, help="auto: timed repetitions of --launches calls each, alternating with the copy; medians are reported")
 ap.add_argument("--src", type=int, default=2, help="extend: source primes [0, S)")
 ap.add_argument("--dst", type=int, default=0, help="extend: target primes [0, T); 0 = every prime of the plan")
-ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent"], default=None,
+ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "inner", "copy"], default=None,
                 help="extend: time the AGX_FORM_NTT call (fused), the unfused pair, or both alternating (default); moddown: the two-launch route (fused), the "
                      "four-launch route on the same plan (generic: needs lib/libagxntt_diag.so through AGX_NTT_LIB), inverse + extend as before mod_down existed "
                      "(parent), or all alternating (default).  A counter run wants one")
+ap.add_argument("--terms", type=int, default=2, help="inner: terms of the sum (1 .. 16)")
+ap.add_argument("--outputs", type=int, default=2, help="inner: outputs (1 or 2)")
+ap.add_argument("--qcount", type=int, default=4, help="keyswitch: Q = primes [0, qcount)")
+ap.add_argument("--pfirst", type=int, default=None, help="keyswitch: the special primes start here (default: qcount, the top level)")
+ap.add_argument("--pcount", type=int, default=2, help="keyswitch: special primes")
+ap.add_argument("--alpha", type=int, default=2, help="keyswitch: primes per digit")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
 if args.op == "moddown":
     args.dst = args.dst or 4
     args.primes = args.src + args.dst      # targets [0, T), sources [T, T + S)
+if args.op == "keyswitch":
+    args.pfirst = args.qcount if args.pfirst is None else args.pfirst
+    args.primes = args.pfirst + args.pcount
 args.only = args.only or ("all" if args.op == "moddown" else "both")
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
 if args.variant is not None:
@@ -247,6 +258,201 @@ def run_moddown():
     plan.close()
 
 
+def _alternate(todo):
+    """0.5 s of the forms first (clock ramp), then --reps repetitions of groups of --launches calls, the forms alternating group by group, device
+    events around every group: {name: [us per call]}"""
+    import time
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / args.launches
+
+    t_end = time.perf_counter() + args.ramp_seconds
+    while True:
+        for fn in todo:
+            for _ in range(4):
+                fn()
+        torch.cuda.synchronize()
+        if time.perf_counter() >= t_end:
+            break
+    times = {fn.__name__: [] for fn in todo}
+    for _ in range(args.reps):
+        for fn in todo:
+            times[fn.__name__].append(timed(fn))
+    return times
+
+
+def _fmt(t):
+    import statistics
+
+    return f"{statistics.median(t):.1f} ({min(t):.1f} ... {max(t):.1f})"
+
+
+def _pointwise_and_add(p, a_ptr, key_rep, acc, tmp, batch, terms, outputs, qcol):
+    """step 3 without agx_ntt_inner_product, at its cheapest: terms x outputs agx_ntt_pointwise calls against a key REPLICATED over the batch
+    (pointwise cannot broadcast), the products of terms >= 1 added in torch without a reduction (four 60-bit residues fit int64) and one
+    remainder per output at the end.  a: [terms][P][batch][n] at a_ptr; key_rep: [terms][outputs][P][batch][n]; acc: [outputs][P][batch][n]"""
+    words = p.num_primes * batch * p.n
+    for o in range(outputs):
+        out = acc[o * words:(o + 1) * words]
+        for t in range(terms):
+            dst = out if t == 0 else tmp
+            p.pointwise(a_ptr + 8 * t * words, key_rep.data_ptr() + 8 * (t * outputs + o) * words, dst.data_ptr(), batch, stream)
+            if t:
+                out.add_(tmp)
+        if terms > 1:
+            out.view(p.num_primes, -1).remainder_(qcol)
+
+
+def run_inner():
+    """agx_ntt_inner_product with --terms terms and --outputs outputs over the plan's primes, three ways alternating in one process:
+      inner  -- the one call (--bcast: one key frame per prime, bhat_batch = 1);
+      copy   -- a device-to-device copy that reads and writes, together, the bytes of the call's traffic model 8 (terms + outputs) per word + the key;
+      parent -- _pointwise_and_add above, the key replicated over the batch.
+    Prints us per call (median (min ... max) of --reps groups of --launches calls), the model traffic as GB/s, and the ratios."""
+    import statistics
+
+    T, O, P, words = args.terms, args.outputs, args.primes, args.primes * args.batch * args.n
+    kb = 1 if args.bcast else args.batch
+    a = torch.empty(T * words, dtype=torch.int64, device="cuda")
+    for t in range(T):
+        plan.fill_synthetic(a.data_ptr() + 8 * t * words, args.batch, t * args.batch, 42, stream)
+    key_rep = torch.empty(T * O * words, dtype=torch.int64, device="cuda")      # [terms][outputs][P][batch][n]: every frame of a prime the same when --bcast
+    for k in range(T * O):
+        plan.fill_synthetic(key_rep.data_ptr() + 8 * k * words, args.batch, 0 if args.bcast else (T + k) * args.batch, 43, stream)
+    if args.bcast:
+        key_rep.view(T * O * P, args.batch, args.n)[:, 1:] = key_rep.view(T * O * P, args.batch, args.n)[:, :1]
+    key = key_rep.view(T * O * P, args.batch, args.n)[:, :kb].contiguous().view(-1)      # [terms][outputs][P][kb][n]
+    c, acc, tmp = (torch.empty(n_, dtype=torch.int64, device="cuda") for n_ in (O * words, O * words, words))
+    qcol = torch.tensor(plan.moduli, dtype=torch.int64, device="cuda")[:, None]
+    model = 8.0 * ((T + O) * words + key.numel())
+    half = int(model // 16)
+    src, dst = (torch.empty(half, dtype=torch.int64, device="cuda") for _ in range(2))
+    src.zero_()
+
+    def inner():
+        plan.inner_product(a.data_ptr(), key.data_ptr(), c.data_ptr(), args.batch, T, O, kb, stream)
+
+    def copy():
+        dst.copy_(src)
+
+    def parent():
+        _pointwise_and_add(plan, a.data_ptr(), key_rep, acc, tmp, args.batch, T, O, qcol)
+
+    inner()
+    parent()
+    torch.cuda.synchronize()
+    assert torch.equal(c, acc), "the one call and the pointwise-and-add form differ"
+    times = _alternate([f for f in (inner, copy, parent) if args.only in ("all", "both", f.__name__)])
+    med = {k: statistics.median(v) for k, v in times.items()}
+    head = f"inner n={args.n} P={P} batch={args.batch} terms={T} outputs={O} key={'broadcast' if args.bcast else 'per frame'} bits={args.bits}:"
+    parts = [f"{k} {_fmt(v)} us" + (f", {model / med[k] / 1e3:.0f} GB/s of model traffic" if k != "parent" else "") for k, v in times.items()]
+    parts += [f"ratio inner/{o} {med['inner'] / med[o]:.3f}" for o in ("copy", "parent") if "inner" in med and o in med]
+    print(head, "; ".join(parts))
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "model_bytes": model}, open(args.report, "w"))
+    plan.close()
+
+
+def run_keyswitch():
+    """agx_ntt_keyswitch_apply at the shape (--qcount, --pfirst, --pcount, --alpha) on a plan of pfirst + pcount primes, beside the composition of
+    public calls a caller had before it: agx_ntt_inverse on a second plan over Q, agx_ntt_basis_extend per digit, step 3 by _pointwise_and_add on a
+    third plan over the active primes with the key replicated over the batch, two agx_ntt_basis_mod_down.  Then the stages of the composition one
+    by one (step 3 both ways): the split by launch.  us per call, median (min ... max)."""
+    import statistics
+
+    Q, pf, pc, alpha, n, B = args.qcount, args.pfirst, args.pcount, args.alpha, args.n, args.batch
+    A, slab = Q + pc, args.batch * args.n
+    act = list(range(Q)) + list(range(pf, pf + pc))
+    psi = [plan.psi(p) for p in range(plan.num_primes)]
+    qplan = agx.Plan(n, plan.moduli[:Q], psi=psi[:Q])
+    aplan = agx.Plan(n, [plan.moduli[p] for p in act], psi=[psi[p] for p in act])
+    ks = plan.keyswitch(Q, pf, pc, alpha)
+    digs = [(f, min(alpha, Q - f)) for f in range(0, Q, alpha)]
+    D = len(digs)
+    ups = [[plan.basis(f, cnt, 0, A)] if pf == Q else [plan.basis(f, cnt, 0, Q), plan.basis(f, cnt, pf, pc)] for f, cnt in digs]
+    down = plan.basis(pf, pc, 0, Q)
+    chat = torch.empty(plan.num_primes * slab, dtype=torch.int64, device="cuda")      # synthetic residues taken as NTT-form words; slabs [0, Q) are read
+    plan.fill_synthetic(chat.data_ptr(), B, 0, 42, stream)
+    key_rep = torch.empty(D * 2 * A * slab, dtype=torch.int64, device="cuda")
+    for k in range(D * 2):
+        aplan.fill_synthetic(key_rep.data_ptr() + 8 * k * A * slab, B, 0, 43 + k, stream)
+    kv = key_rep.view(D * 2 * A, B, n)
+    kv[:, 1:] = kv[:, :1]
+    key = kv[:, 0].contiguous().view(-1)      # [digits][2][A][n]
+    out, out2 = (torch.empty(2 * Q * slab, dtype=torch.int64, device="cuda") for _ in range(2))
+    scratch = torch.empty(ks.scratch_words(B), dtype=torch.int64, device="cuda")
+    coeff, ext, acc, tmp = (torch.empty(k * slab, dtype=torch.int64, device="cuda") for k in (Q, D * A, 2 * A, A))
+    qcol = torch.tensor(aplan.moduli, dtype=torch.int64, device="cuda")[:, None]
+
+    def one_call():
+        ks.apply(chat.data_ptr(), key.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, stream)
+
+    def inverse():
+        qplan.inverse(chat.data_ptr(), coeff.data_ptr(), B, stream)
+
+    def mod_up():
+        for d, (f, cnt) in enumerate(digs):
+            e = ext.data_ptr() + 8 * d * A * slab
+            ups[d][0].extend(coeff.data_ptr() + 8 * f * slab, e, B, agx.FORM_NTT, stream)
+            if pf != Q:
+                ups[d][1].extend(coeff.data_ptr() + 8 * f * slab, e + 8 * Q * slab, B, agx.FORM_NTT, stream)
+
+    def inner_product():
+        aplan.inner_product(ext.data_ptr(), key.data_ptr(), acc.data_ptr(), B, D, 2, 1, stream)
+
+    def pointwise_and_add():
+        _pointwise_and_add(aplan, ext.data_ptr(), key_rep, acc, tmp, B, D, 2, qcol)
+
+    def mod_down():
+        for o in range(2):
+            xq = acc.data_ptr() + 8 * o * A * slab
+            down.mod_down(xq, xq + 8 * Q * slab, out2.data_ptr() + 8 * o * Q * slab, xq + 8 * Q * slab, B, stream)
+
+    def composition():
+        inverse()
+        mod_up()
+        pointwise_and_add()
+        mod_down()
+
+    one_call()
+    composition()
+    torch.cuda.synchronize()
+    assert torch.equal(out, out2), "the one call and the composition of public calls differ"
+    whole = _alternate([one_call, composition])
+    stages = _alternate([inverse, mod_up, inner_product, pointwise_and_add])
+    inner_product()      # mod_down gives its special slabs up: refill acc before every group by timing it alone, on whatever words it left
+    stages.update(_alternate([mod_down]))
+    med = {k: statistics.median(v) for k, v in {**whole, **stages}.items()}
+    print(f"keyswitch n={n} shape=({Q}, {pf}, {pc}, {alpha}) batch={B} bits={args.bits} launches={ks.info()[5]}: one call {_fmt(whole['one_call'])} us; composition "
+          f"{_fmt(whole['composition'])} us; ratio {med['one_call'] / med['composition']:.3f}")
+    print("  stages: " + "; ".join(f"{k} {_fmt(v)} us" for k, v in stages.items())
+          + f"; sum with inner_product {med['inverse'] + med['mod_up'] + med['inner_product'] + med['mod_down']:.1f} us")
+    if args.report:
+        import json
+
+        json.dump({"us": {**whole, **stages}, "launches": args.launches, "kernel_launches": ks.info()[5]}, open(args.report, "w"))
+    for b in [x for pair in ups for x in pair] + [down]:
+        b.close()
+    ks.close()
+    qplan.close()
+    aplan.close()
+    plan.close()
+
+
+if args.op == "inner":
+    run_inner()
+    sys.exit(0)
+if args.op == "keyswitch":
+    run_keyswitch()
+    sys.exit(0)
 if args.op == "auto":
     run_auto()
     sys.exit(0)
