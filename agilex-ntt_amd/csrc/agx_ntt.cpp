@@ -139,13 +139,15 @@ void free_plan(agx_ntt_plan* p) {
     delete p;      // the device memory goes with its owners
 }
 
-// the pass tables of `e` for every prime, from natural-index {w, w'} tables ([num_primes][n]) of one direction
-static std::vector<ulonglong2> build_pass_table(const rb_entry* e, const std::vector<ulonglong2>& pairs, uint32_t num_primes, uint32_t n) {
+// the pass tables of `e` for every prime, from natural-index {w, w'} tables ([num_primes][n]) of one direction; what a slot holds is the
+// entry's business (rb_entry::build), which is why it is told the modulus
+static std::vector<ulonglong2> build_pass_table(const rb_entry* e, const std::vector<ulonglong2>& pairs, const std::vector<uint64_t>& moduli, uint32_t n) {
+    const uint32_t num_primes = (uint32_t)moduli.size();
     std::vector<ulonglong2> out;
     std::vector<uint64_t> w(n), wp(n);
     for (uint32_t k = 0; k < num_primes; ++k) {
         for (uint32_t j = 0; j < n; ++j) w[j] = pairs[(size_t)k * n + j].x, wp[j] = pairs[(size_t)k * n + j].y;
-        e->build(w.data(), wp.data(), out);
+        e->build(w.data(), wp.data(), moduli[k], out);
     }
     return out;
 }
@@ -277,8 +279,8 @@ void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const 
         else img.rescale_legal = false;
     }
     const rb_selection& c = img.chosen;
-    if (c.main) img.tables.push_back({c.main, build_pass_table(c.main, img.tw_pairs, num_primes, n), itw ? build_pass_table(c.main, img.itw_pairs, num_primes, n) : std::vector<ulonglong2>{}});
-    if (c.forward_large && c.forward_large != c.main) img.tables.push_back({c.forward_large, build_pass_table(c.forward_large, img.tw_pairs, num_primes, n), {}});
+    if (c.main) img.tables.push_back({c.main, build_pass_table(c.main, img.tw_pairs, img.moduli, n), itw ? build_pass_table(c.main, img.itw_pairs, img.moduli, n) : std::vector<ulonglong2>{}});
+    if (c.forward_large && c.forward_large != c.main) img.tables.push_back({c.forward_large, build_pass_table(c.forward_large, img.tw_pairs, img.moduli, n), {}});
 }
 
 static int upload_pass_tables(pass_tables& dst, const host_pass_tables& src) {
@@ -388,10 +390,10 @@ static int plan_set_variant_impl(agx_ntt_plan* plan, int variant) {
             host_pass_tables host{sel.main, {}, {}};
             std::vector<ulonglong2> pairs((size_t)plan->num_primes * plan->n);
             AGX_HIP(hipMemcpy(pairs.data(), plan->d_tw, pairs.size() * sizeof(ulonglong2), hipMemcpyDeviceToHost));
-            host.fwd = build_pass_table(sel.main, pairs, plan->num_primes, plan->n);
+            host.fwd = build_pass_table(sel.main, pairs, plan->moduli, plan->n);
             if (plan->d_itw) {
                 AGX_HIP(hipMemcpy(pairs.data(), plan->d_itw, pairs.size() * sizeof(ulonglong2), hipMemcpyDeviceToHost));
-                host.inv = build_pass_table(sel.main, pairs, plan->num_primes, plan->n);
+                host.inv = build_pass_table(sel.main, pairs, plan->moduli, plan->n);
             }
             pass_tables fresh;
             if (int rc = upload_pass_tables(fresh, host)) return rc;

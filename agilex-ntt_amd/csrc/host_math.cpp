@@ -92,6 +92,11 @@ bool inv_mod_euclid(uint64_t a, uint64_t q, uint64_t* inv) {
 
 uint64_t shoup_quotient(uint64_t w, uint64_t q) { return (uint64_t)(((u128)w << 64) / q); }
 
+fold_twiddle fold_twiddle_pack(uint64_t w, uint64_t q) {
+    const uint64_t low29 = (1ull << 29) - 1, wc = mul_mod(w, 1ull << 32, q);
+    return {(w & low29) | (w >> 29) << 32, (wc & low29) | (wc >> 29) << 32};
+}
+
 void power_tables_bitrev(uint64_t q, uint64_t base, uint32_t n, uint64_t* tw, uint64_t* pre) {
     const int lg = log2u(n);
     std::vector<uint64_t> pw(n);

@@ -32,6 +32,14 @@ uint64_t shoup_quotient(uint64_t w, uint64_t q);
 // tw[j] = base^bitrev(j) mod q, pre[j] = shoup_quotient(tw[j])
 void power_tables_bitrev(uint64_t q, uint64_t base, uint32_t n, uint64_t* tw, uint64_t* pre);
 
+// The table entry of the two-twiddle butterfly for q = 2^60 - c, 0 < c < 2^28 (csrc/modarith.hpp: ct_butterfly_q60c_fold), from a twiddle
+// w < q alone: wC = w 2^32 mod q, and each of the two split at bit 29 into the words of one 64-bit value --
+//   w_packed = (w mod 2^29) | (w >> 29) << 32,   wc_packed = (wC mod 2^29) | (wC >> 29) << 32;   the high halves are below 2^31.
+struct fold_twiddle {
+    uint64_t w_packed, wc_packed;
+};
+fold_twiddle fold_twiddle_pack(uint64_t w, uint64_t q);
+
 // The constants of a fast RNS base conversion (agx_ntt_basis_extend) from the moduli src[0 .. S) to the moduli dst[0 .. T), every modulus
 // odd, > 1 and < 2^62.  With D = prod src[i] and D_i = D / src[i]:
 //   dinv[i] = D_i^-1 mod src[i],   mat[j * S + i] = D_i mod dst[j],   dinv_p / mat_p their precomputed quotients (shoup_quotient).

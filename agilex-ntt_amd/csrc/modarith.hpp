@@ -147,6 +147,8 @@ struct bf_consts {
     uint32_t one_a, one_b;  // two separate opaque_one() values (see add64_32)
     float est_inv;          // slightly below 2^32 / q, or 0 when q < 2^58 (reduce_final_est)
     uint32_t c, c8;         // q = 2^60 - c kernels only (below): c and 8c
+    uint32_t c2, p29;       // two-twiddle form of those kernels only (ct_butterfly_q60c_fold): 2c, and 2^29 in a form the optimiser cannot see through
+    uint64_t m8;            // ... and 8q
 };
 
 // x in [0,2m) -> x - (x >= m ? m : 0) through the sign of x - m; needs 2m <= 2^63... see callers
@@ -444,6 +446,55 @@ __device__ __forceinline__ uint64_t reduce_final_q60c(uint64_t v, const bf_const
     r.y &= 0x0fffffffu;
     const uint64_t t = mad64(kq, k.c, __builtin_bit_cast(uint64_t, r));
     return lazy_out ? t : csub_select_c(t, f.nq1);
+}
+
+// ---------------------------------------------------------------------------------------
+// TWO-TWIDDLE form for the same class of moduli: six multiply-adds per butterfly, no quotient estimate.  The 124-bit product y w is never
+// built; y = y0 + y1 2^32 meets a second twiddle wC = w 2^32 mod q (kept in the table slot where the other forms keep w'), so that
+//   y w = y0 w + y1 wC (mod q).
+// Both twiddles are split at bit 29 (wl = w mod 2^29, wh = w >> 29 < 2^31 because w < q < 2^60; wCl, wCh likewise):
+//   hi = y0 wh + y1 wCh,   lo = y0 wl + y1 wCl,   y0 w + y1 wC = lo + hi 2^29 = lo + hl 2^29 + hh 2^61   (hl, hh: the words of hi)
+// and 2^61 = 2c (mod q):  Q = lo + hl 2^29 + hh 2c = y w (mod q).  The whole right-hand side is ONE chain of v_mad_u64_u32 that lands on tx:
+//   x' = tx + Q,   y' = tx + 8q - Q = 2 tx + 8q - x'.
+// Coefficients travel between stages as arbitrary 64-bit words; every stage but the first brings x below 2^63 + 8c with the sign-bit
+// subtract (csub_8q_q60c), the first one's inputs are below 4q.  q60c_fold_bounds proves that no partial sum wraps, for the whole class.
+// reduce_final_q60c takes any 64-bit word, so the last stage and the output contract are those of the form above.
+// ---------------------------------------------------------------------------------------
+struct q60c_fold_bounds {
+    typedef unsigned __int128 u128;
+    static constexpr u128 two64 = (u128)1 << 64, w32 = 0xffffffffull;
+    static constexpr u128 c_max = (1ull << 28) - 1, q_min = (1ull << 60) - (uint64_t)c_max, q_max = (1ull << 60) - 1;
+    static constexpr u128 wh_max = (uint64_t)q_max >> 29, wl_max = (1ull << 29) - 1;      // halves of a twiddle below q
+    static constexpr u128 hi_max = 2 * w32 * wh_max;                                         // y0 wh + y1 wCh
+    static constexpr u128 lo_max = 2 * w32 * wl_max;                                         // y0 wl + y1 wCl
+    static constexpr u128 Q_max = lo_max + w32 * ((u128)1 << 29) + w32 * 2 * c_max;          // lo + hl 2^29 + hh 2c, the largest c
+    static constexpr u128 tx_max = ((u128)1 << 63) + 8 * c_max - 1, tx_max_c1 = ((u128)1 << 63) + 8 - 1;      // after csub_8q_q60c, the largest c and c = 1; a first-stage input is below 4q < 2^62
+    static_assert(wh_max < ((u128)1 << 31), "the high half of a twiddle fits 31 bits");
+    static_assert(hi_max < two64, "hi fits 64 bits");
+    static_assert(tx_max + Q_max < two64, "x' = tx + Q does not wrap (every partial sum of the chain is below this one)");
+    static_assert(Q_max <= 8 * q_min, "y' = tx + 8q - Q is not negative");
+    static_assert(tx_max + 8 * q_min < two64 && tx_max_c1 + 8 * q_max < two64, "y' <= tx + 8q = 2^64 - 1 for every c");
+};
+
+// 2^29 as opaque_one() gives 1: the factor of hl stays a multiply-add
+__device__ __forceinline__ uint32_t opaque_two29() {
+    uint32_t v;
+    asm("s_mov_b32 %0, 0x20000000" : "=s"(v));
+    return v;
+}
+
+template <bool DO_CSUB>
+__device__ __forceinline__ void ct_butterfly_q60c_fold(uint64_t& x, uint64_t& y, uint64_t w, uint64_t wC, const bf_consts& k) {
+    const uint32_t y0 = (uint32_t)y, y1 = (uint32_t)(y >> 32);
+    const uint32_t wl = (uint32_t)w, wh = (uint32_t)(w >> 32), wCl = (uint32_t)wC, wCh = (uint32_t)(wC >> 32);      // the slot holds the halves a word each
+    const uint64_t tx = DO_CSUB ? csub_8q_q60c(x, k) : x;
+    const uint64_t hi = mad64(y1, wCh, mul64(y0, wh));
+    uint64_t xn = keep64(mad64(y0, wl, tx));      // pinned: left free, the sum is reassociated into a chain from zero plus a 64-bit add of tx
+    xn = mad64(y1, wCl, xn);
+    xn = mad64((uint32_t)hi, k.p29, xn);      // a visible 2^29 would become shifts and a carry pair
+    xn = mad64((uint32_t)(hi >> 32), k.c2, xn);
+    y = (tx << 1) + k.m8 - xn;                                              // tx + 8q - Q
+    x = xn;
 }
 
 // w*d - c*q (mod 2^64) with the quotient estimate of the chosen arithmetic:

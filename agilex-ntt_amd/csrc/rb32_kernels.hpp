@@ -352,7 +352,7 @@ polymul_q32(const uint64_t* __restrict__ pa, const uint64_t* __restrict__ pb, ui
 // ---- host side: table and registry entry (the launch glue is rb_kernels.hpp's) ------------------------------------------------------------
 // build_table_t's geometry (for_each_table_slot), entries {w, precon >> 32}; appended to `out` as raw bytes (two entries per ulonglong2)
 template <int L, int R>
-void build_table32_t(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
+void build_table32_t(const uint64_t* tw, const uint64_t* pre, uint64_t, std::vector<ulonglong2>& out) {
     using G = rb_geom<L, R>;
     static_assert(G::table_pairs % 2 == 0, "two 8-byte entries per 16-byte slot");
     std::vector<uint2> t((size_t)G::table_pairs, make_uint2(0, 0));

@@ -186,6 +186,8 @@ constexpr int kOptPinBf = 1 << 26;         // with kOptStreamTw: butterflies are
                                            // the 128 a 1024-thread workgroup may use; one wave cannot issue faster than one VALU per ~8 clocks anyway (ILP buys nothing there)
 constexpr int kOptQ60c = 1 << 27;          // with kOptEstReduce, forward only: every modulus is 2^60 - c, 0 < c < 2^28 (arithmetic level 3): sign-bit conditional subtracts and the
                                            // final reduction by the top four bits (modarith.hpp: q60c_tailfree)
+constexpr int kOptQ60cFold = 1 << 28;      // with kOptQ60c: the two-twiddle butterfly (modarith.hpp: ct_butterfly_q60c_fold) -- six multiply-adds, no quotient estimate; the pass
+                                           // table's slots hold {w, w 2^32 mod q}, each split at bit 29, instead of {w, w'} (rb_kernels.hpp: build_table_fold_t)
 constexpr int kOptStreamCh1 = 1 << 29;     // with kOptStreamTw: one table entry per chunk instead of two or four (R = 4 passes then fit 64 VGPRs: 8 waves/SIMD)
 // Measured and removed in round 4 (the records stay in profiles/ and DESIGN.md 3.4-3.6): the XOR-swizzled image, cross products as 32-bit multiplies,
 // the inverse's twiddle-first / priority policies, timing ablations, persistent streaming / loop forms of the forward, resident sub-blocks with
@@ -213,6 +215,8 @@ struct rb2_frame {
     static constexpr bool TWA_INV = (OPT & kOptTwAheadInv) != 0 && R == 3;
     static constexpr bool EST = LAZY16 && SEL && (OPT & kOptEstReduce) != 0;
     static constexpr bool Q60C = EST && (OPT & kOptQ60c) != 0;
+    static constexpr bool Q60C_FOLD = Q60C && (OPT & kOptQ60cFold) != 0;
+    static_assert((OPT & kOptQ60cFold) == 0 || Q60C, "the two-twiddle butterfly is a form of the q = 2^60 - c kernels");
     static constexpr bool SPLIT = (OPT & kOptSplitWord) != 0;
     static constexpr bool STREAM_TW = (OPT & kOptStreamTw) != 0, PIN_BF = (OPT & kOptPinBf) != 0, STREAM_CH1 = (OPT & kOptStreamCh1) != 0;
     static_assert(!EST || lazy16_tailfree::valid(L), "tail-free schedule must keep every stage within 16q");
@@ -281,12 +285,18 @@ struct rb2_frame {
             k.c = (uint32_t)(est >> 32);      // the host sets it for the plans this kernel may serve (prime_consts::est)
             k.c8 = k.c << 3;
         }
+        if constexpr (Q60C_FOLD) {
+            k.c2 = k.c << 1;
+            k.p29 = opaque_two29();
+            k.m8 = q << 3;
+        }
     }
 
     // forward butterfly number `stage` of the whole transform in this frame's arithmetic
     template <int stage>
     __device__ __forceinline__ void butterfly(uint64_t& a, uint64_t& b, const twpair& w) const {
-        if constexpr (Q60C) ct_butterfly_q60c<lazy16_tailfree::subtracts(stage, L)>(a, b, w.x, w.y, k);
+        if constexpr (Q60C_FOLD) ct_butterfly_q60c_fold<(stage >= 1)>(a, b, w.x, w.y, k);      // the slot holds {w, wC} (kOptQ60cFold); first-stage inputs are below 4q
+        else if constexpr (Q60C) ct_butterfly_q60c<lazy16_tailfree::subtracts(stage, L)>(a, b, w.x, w.y, k);
         else if constexpr (EST) ct_butterfly_lazy16<SEL, lazy16_tailfree::subtracts(stage, L), false>(a, b, w.x, w.y, k, fc);
         else if constexpr (LAZY16) ct_butterfly_lazy16<SEL, lazy16_schedule::subtracts(stage), stage == L - 1>(a, b, w.x, w.y, k, fc);
         else if constexpr (FAST) ct_butterfly_fast<SEL>(a, b, w.x, w.y, k);

@@ -3,6 +3,7 @@
 // reg_*.hip translation units, each of which instantiates one group of registry entries under its own namespace AGX_TU.
 #pragma once
 #include "rb_frame.hpp"
+#include "host_math.hpp"
 
 // mulhat_rb2 of a shape tuned for 8 waves/SIMD (n = 4096: 64 VGPRs) is compiled for 6 (80 VGPRs): with bhat's 16 words per thread
 // requested ahead of the last forward pass it needs 69-80 registers, 64 cost 12-92 bytes of scratch per lane, and 512-thread
@@ -617,7 +618,8 @@ moddown_rb2(const uint64_t* xq, const uint64_t* __restrict__ y, uint64_t* out, c
 // (the 32-bit kernels of rb32_kernels.hpp and the wave-packed kernels of wp_kernels.hpp bring their own shape struct and nothing else)
 
 // The geometry of one prime's pass table: f(at, idx) for every slot `at` in [0, rb_geom<L, R>::table_pairs) that holds a twiddle, idx = its
-// natural twiddle index.  What a slot stores is the builder's business ({w, w'} here, {(u32)w, w' >> 32} in build_table32_t).
+// natural twiddle index.  What a slot stores is the builder's business ({w, w'} in build_table_t, the two split twiddles in build_table_fold_t,
+// {(u32)w, w' >> 32} in build_table32_t); rb_entry::build hands every builder the prime's modulus.
 template <int L, int R, class F>
 void for_each_table_slot(F&& f) {
     using G = rb2_geom<L, R>;
@@ -641,10 +643,20 @@ void for_each_table_slot(F&& f) {
 }
 
 template <int L, int R>
-void build_table_t(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out) {
+void build_table_t(const uint64_t* tw, const uint64_t* pre, uint64_t, std::vector<ulonglong2>& out) {
     const size_t start = out.size();
     out.resize(start + (size_t)rb_geom<L, R>::table_pairs, make_ulonglong2(0, 0));
     for_each_table_slot<L, R>([&](size_t at, uint32_t idx) { out[start + at] = make_ulonglong2(tw[idx], pre[idx]); });
+}
+// the same geometry for the kernels of the two-twiddle butterfly (kOptQ60cFold): a slot holds fold_twiddle_pack(w, q), made from w alone
+template <int L, int R>
+void build_table_fold_t(const uint64_t* tw, const uint64_t*, uint64_t q, std::vector<ulonglong2>& out) {
+    const size_t start = out.size();
+    out.resize(start + (size_t)rb_geom<L, R>::table_pairs, make_ulonglong2(0, 0));
+    for_each_table_slot<L, R>([&](size_t at, uint32_t idx) {
+        const fold_twiddle f = fold_twiddle_pack(tw[idx], q);
+        out[start + at] = make_ulonglong2(f.w_packed, f.wc_packed);
+    });
 }
 
 template <class F>
@@ -664,7 +676,7 @@ struct rb2_shape : lazy_flag {
     static constexpr int log_n = L, r = R, fpb = PPB, threads = rb_geom<L, R>::T * PPB, min_waves = MINW, arith = rb2_arith_level<frame_of<L, R, ARITH>>(), narrow = 0;
     static constexpr uint32_t table_pairs = rb_geom<L, R>::table_pairs;
     static constexpr size_t lds = (size_t)frame_of<L, R, ARITH>::image_bytes * PPB;
-    static constexpr auto build = &build_table_t<L, R>;
+    static constexpr auto build = frame_of<L, R, ARITH>::Q60C_FOLD ? &build_table_fold_t<L, R> : &build_table_t<L, R>;
 };
 
 // the one place the registry kernels' dynamic LDS is allowed: BYTES on each of K

@@ -13,7 +13,7 @@ struct rb_entry {
     int min_waves;
     uint32_t table_pairs;   // pass-table length per prime, in {w,w'} pairs
     size_t lds_bytes;
-    void (*build)(const uint64_t* tw, const uint64_t* pre, std::vector<ulonglong2>& out);      // appends one prime's pass table
+    void (*build)(const uint64_t* tw, const uint64_t* pre, uint64_t q, std::vector<ulonglong2>& out);      // appends the pass table of one prime q
     hipError_t (*launch)(const plan_view&, const uint64_t*, uint64_t*, const frame_layout&, hipStream_t);
     hipError_t (*init)();    // allows every kernel the entry launches the dynamic LDS it is launched with
     int arith;   // 0: exact (reference op sequence, q < 2^62); 1: fast (q <= 2^61); 2: 16q-lazy (q <= 2^60); 3: 16q-lazy for q = 2^60 - c, 0 < c < 2^28

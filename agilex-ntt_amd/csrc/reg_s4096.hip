@@ -11,10 +11,13 @@ const rb_entry kEntries[] = {
     // 59.5 vs 58.2 M NTT/s, 18.5 vs 18.9 uJ per NTT at the same 1400 W (profiles/r03_energy_ab.txt); its inverse (-1 %) and parked
     // product (-4 %) lose to id 93's, so only the forward kernel ships (A/B twin with all three transforms: id 147)
     make_entry_single_fwd<12, 5, kLazy | (kOptPrio << 1), 4>(159),
-    // the same kernel for plans whose moduli are all 2^60 - c, 0 < c < 2^28 (arithmetic level 3): sign-bit conditional subtracts, final reduction by
-    // the top four bits; takes id 159's place as the forward companion of such plans (ntt_kernels.hip: kCompanionDefaults)
-    make_entry_single_fwd<12, 5, kLazy | ((kOptPrio | kOptQ60c) << 1), 4>(165),
+    // the same shape for plans whose moduli are all 2^60 - c, 0 < c < 2^28 (arithmetic level 3): the two-twiddle butterfly (six multiply-adds, a sign-bit
+    // subtract on every stage but the first, slots {w, w 2^32 mod q} split at bit 29), final reduction by the top four bits; takes id 159's place as
+    // the forward companion of such plans (ntt_kernels.hip: kCompanionDefaults)
+    make_entry_single_fwd<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold) << 1), 4>(165),
 #ifdef AGX_DIAG
+    // A/B twin of id 165 with the butterfly it had before: quotient estimate from {w, w'}, sign-bit subtracts on the tail-free schedule (tools/energy_ab.py)
+    make_entry_single_fwd<12, 5, kLazy | ((kOptPrio | kOptQ60c) << 1), 4>(167),
     // A/B twins kept in lib/libagxntt_diag.so: all three transforms in this shape with the load priority (147: its inverse -1 %, its parked
     // product -4 % against id 93's), and R = 4 streamed one table entry at a time at 8 waves/SIMD (161: equal to the default within 1 %)
     make_entry_single<12, 5, kLazy | (kOptPrio << 1), 4>(147),

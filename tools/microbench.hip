@@ -258,7 +258,8 @@ static void time_bw(const char* name, size_t bytes_moved, F launch) {
 // The product's own butterfly forms (csrc/modarith.hpp) on register-resident coefficients, no
 // memory traffic inside the loop: what the VALU alone can sustain, i.e. the ceiling the NTT kernels
 // are measured against.  One radix-8 pass (12 butterflies on 8 coefficients) per iteration.
-template <int FORM, bool SGPR_TW>   // FORM 0 exact, 1 fast, 2 16q-lazy (every 12th..: 5 of 12 butterflies subtract), 3 = 2 with 32-bit cross products
+template <int FORM, bool SGPR_TW>   // FORM 0 exact, 1 fast, 2 16q-lazy (every 12th..: 5 of 12 butterflies subtract), 3 = 2 with 32-bit cross products,
+                                    // 4 q = 2^60 - c with the quotient estimate (5 of 12 subtract), 5 q = 2^60 - c two-twiddle form (11 of 12 subtract, as at n = 4096)
 __global__ void __launch_bounds__(512, 8) bf_kernel(uint64_t* out, const uint64_t* tw, uint64_t q, int iters) {
     using namespace agx;
     bf_consts k;
@@ -271,6 +272,10 @@ __global__ void __launch_bounds__(512, 8) bf_kernel(uint64_t* out, const uint64_
     final_consts fc;
     fc.q2 = q << 1; fc.nq2 = opaque_sgpr64(0 - fc.q2); fc.q1 = q; fc.nq1 = opaque_sgpr64(0 - q);
     fc.q8 = q << 3; fc.nq8 = opaque_sgpr64(0 - fc.q8);
+    if constexpr (FORM >= 4) {      // q = 2^60 - c
+        k.c = (uint32_t)((1ull << 60) - q); k.c8 = k.c << 3;
+        k.c2 = k.c << 1; k.p29 = opaque_two29(); k.m8 = q << 3;
+    }
     uint64_t x[8];
     for (int r = 0; r < 8; ++r) x[r] = (tw[(threadIdx.x * 8 + r) & 1023] >> 3);
     // per-lane variant: 3 distinct twiddle pairs per thread stay in VGPRs (12 registers), as many as
@@ -281,6 +286,10 @@ __global__ void __launch_bounds__(512, 8) bf_kernel(uint64_t* out, const uint64_
         const size_t idx = SGPR_TW ? (size_t)(j * 2) : (size_t)((threadIdx.x & 63) * 16 + j * 2);
         w[j] = tw[idx] % q;
         wp[j] = tw[idx + 1];
+        if constexpr (FORM == 5) {      // a table slot of the two-twiddle form: random halves below 2^29 and 2^31
+            w[j] = tw[idx] & 0x7fffffff1fffffffull;
+            wp[j] = tw[idx + 1] & 0x7fffffff1fffffffull;
+        }
     }
     for (int it = 0; it < iters; ++it) {
 #pragma unroll
@@ -295,6 +304,14 @@ __global__ void __launch_bounds__(512, 8) bf_kernel(uint64_t* out, const uint64_
                 else if constexpr (FORM == 3) {     // 16q-lazy with the cross products as 32-bit multiplies (energy A/B)
                     if (stage == 1 || (stage == 2 && b == 0)) ct_butterfly_lazy16<true, true, false, 1>(x[r0], x[r1], w[j], wp[j], k, fc);
                     else ct_butterfly_lazy16<true, false, false, 1>(x[r0], x[r1], w[j], wp[j], k, fc);
+                }
+                else if constexpr (FORM == 4) {
+                    if (stage == 1 || (stage == 2 && b == 0)) ct_butterfly_q60c<true>(x[r0], x[r1], w[j], wp[j], k);
+                    else ct_butterfly_q60c<false>(x[r0], x[r1], w[j], wp[j], k);
+                }
+                else if constexpr (FORM == 5) {
+                    if (stage == 0 && b == 0) ct_butterfly_q60c_fold<false>(x[r0], x[r1], w[j], wp[j], k);
+                    else ct_butterfly_q60c_fold<true>(x[r0], x[r1], w[j], wp[j], k);
                 }
                 else if (stage == 1 || (stage == 2 && b == 0)) ct_butterfly_lazy16<true, true>(x[r0], x[r1], w[j], wp[j], k, fc);   // 5 of 12
                 else ct_butterfly_lazy16<true, false>(x[r0], x[r1], w[j], wp[j], k, fc);
@@ -436,8 +453,11 @@ struct SysfsProbe {
     }
 };
 
+struct PowerReading {
+    double watts, units_per_s;
+};
 template <typename F>
-static void power_phase(const SysfsProbe& probe, const char* name, F launch, double units_per_launch, const char* unit) {
+static PowerReading power_phase(const SysfsProbe& probe, const char* name, F launch, double units_per_launch, const char* unit) {
     launch(); CK(hipDeviceSynchronize());
     std::atomic<bool> stop{false};
     std::vector<double> watts; std::vector<int> mhz;
@@ -460,6 +480,7 @@ static void power_phase(const SysfsProbe& probe, const char* name, F launch, dou
     std::sort(watts.begin(), watts.end()); std::sort(mhz.begin(), mhz.end());
     printf("  %-52s %8.1f W median (%4zu samples)  sclk %4d MHz   %9.3f %s\n", name, watts.empty() ? 0.0 : watts[watts.size() / 2], watts.size(),
            mhz.empty() ? 0 : mhz[mhz.size() / 2], units_per_launch * launches / (ms * 1e-3) / 1e9, unit);
+    return {watts.empty() ? 0.0 : watts[watts.size() / 2], units_per_launch * launches / (ms * 1e-3)};
 }
 
 static void run_power() {
@@ -491,9 +512,21 @@ static void run_power() {
         power_phase(probe, "16q-lazy butterflies on registers (random data), 8 waves/SIMD", [&] { bf_kernel<2, false><<<bl, 512>>>(d_o, d_tw, q, it); }, (double)bl * 512 * it * 12, "G butterflies/s");
         power_phase(probe, "16q-lazy, wave-uniform (SGPR) twiddles", [&] { bf_kernel<2, true><<<bl, 512>>>(d_o, d_tw, q, it); }, (double)bl * 512 * it * 12, "G butterflies/s");
         power_phase(probe, "16q-lazy, cross products as 32-bit v_mul_lo_u32", [&] { bf_kernel<3, false><<<bl, 512>>>(d_o, d_tw, q, it); }, (double)bl * 512 * it * 12, "G butterflies/s");
+        // the two forms for q = 2^60 - c side by side, as energy per lane-butterfly above idle (idle sampled here, after the loops above have drained)
+        {
+            std::this_thread::sleep_for(std::chrono::milliseconds(500));
+            std::vector<double> idle;
+            for (int i = 0; i < 15; ++i) { double w; int m; probe.read(w, m); if (w > 0) idle.push_back(w); std::this_thread::sleep_for(std::chrono::milliseconds(20)); }
+            std::sort(idle.begin(), idle.end());
+            const double idle_w = idle.empty() ? 0.0 : idle[idle.size() / 2];
+            const PowerReading est = power_phase(probe, "q = 2^60 - c, quotient-estimate butterflies (random data)", [&] { bf_kernel<4, false><<<bl, 512>>>(d_o, d_tw, q, it); }, (double)bl * 512 * it * 12, "G butterflies/s");
+            const PowerReading fold = power_phase(probe, "q = 2^60 - c, two-twiddle butterflies (random data)", [&] { bf_kernel<5, false><<<bl, 512>>>(d_o, d_tw, q, it); }, (double)bl * 512 * it * 12, "G butterflies/s");
+            printf("  energy per lane-butterfly above idle (%.0f W): quotient estimate %.3f nJ, two-twiddle %.3f nJ\n", idle_w, (est.watts - idle_w) / est.units_per_s * 1e9,
+                   (fold.watts - idle_w) / fold.units_per_s * 1e9);
+        }
         std::fill(h.begin(), h.end(), 0ull);
         CK(hipMemcpy(d_tw, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-        power_phase(probe, "the same on all-zero data and twiddles", [&] { bf_kernel<2, false><<<bl, 512>>>(d_o, d_tw, q, it); }, (double)bl * 512 * it * 12, "G butterflies/s");
+        power_phase(probe, "16q-lazy butterflies on all-zero data and twiddles", [&] { bf_kernel<2, false><<<bl, 512>>>(d_o, d_tw, q, it); }, (double)bl * 512 * it * 12, "G butterflies/s");
         CK(hipFree(d_tw)); CK(hipFree(d_o));
     }
     {
