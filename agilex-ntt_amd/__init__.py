@@ -63,11 +63,16 @@ ABI = {
     "agx_ntt_basis_mod_down": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_basis_mod_down_info": (_int, [_vp, ctypes.POINTER(_int)]),
     "agx_ntt_inner_product": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _vp]),
+    "agx_ntt_inner_product_galois": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp]),
     "agx_ntt_keyswitch_create": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32]),
     "agx_ntt_keyswitch_destroy": (_int, [_vp]),
     "agx_ntt_keyswitch_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_int)]),
     "agx_ntt_keyswitch_scratch_words": (_int, [_vp, _u64, _p64]),
     "agx_ntt_keyswitch_apply": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "agx_ntt_keyswitch_hoisted_words": (_int, [_vp, _u64, _p64, _p64, _p64]),
+    "agx_ntt_keyswitch_decompose": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "agx_ntt_keyswitch_apply_decomposed": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp]),
+    "agx_ntt_keyswitch_hoisted_info": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
@@ -342,6 +347,12 @@ class Plan:
         [outputs][P][batch][n]; inputs in [0,4q), c fully reduced, out of place; bhat_batch: None = batch, or 1 (one key frame per prime)"""
         _check(lib().agx_ntt_inner_product(self._h, d_a, d_bhat, d_c, batch, batch if bhat_batch is None else bhat_batch, terms, outputs, stream), "inner_product")
 
+    def inner_product_galois(self, d_a, d_bhat, d_c, batch, terms, galois_elt, outputs=1, bhat_batch=None, stream=0):
+        """inner_product with a read through the automorphism X -> X^galois_elt: c_o[i] = sum_t a_t[pi_g(i)] o bhat_{t,o}[i], one launch, no
+        permuted copy of a; galois_elt odd, below 2n (1: inner_product itself)"""
+        _check(lib().agx_ntt_inner_product_galois(self._h, d_a, d_bhat, d_c, batch, batch if bhat_batch is None else bhat_batch, terms, outputs, galois_elt, stream),
+               "inner_product_galois")
+
     def keyswitch(self, q_count, p_first, p_count, alpha):
         """KeySwitch(self, ...): the hybrid key switch at level Q = primes [0, q_count) with special primes [p_first, p_first + p_count)"""
         return KeySwitch(self, q_count, p_first, p_count, alpha)
@@ -452,6 +463,28 @@ class KeySwitch:
         """d_chat [q_count][batch][n] and d_keyhat [digits][2][A][n] in NTT form (reduced or lazy) -> d_out [2][q_count][batch][n], fully
         reduced; d_scratch: scratch_words(batch) words; no two of the four may touch"""
         _check(lib().agx_ntt_keyswitch_apply(self._h, d_chat, d_keyhat, d_out, d_scratch, batch, stream), "keyswitch_apply")
+
+    def hoisted_words(self, batch):
+        """(ext, decompose_scratch, apply_scratch): the sizes in words of the buffers of decompose and apply_decomposed"""
+        v = [_u64(0) for _ in range(3)]
+        _check(lib().agx_ntt_keyswitch_hoisted_words(self._h, batch, *[ctypes.byref(x) for x in v]), "keyswitch_hoisted_words")
+        return tuple(x.value for x in v)
+
+    def decompose(self, d_chat, d_ext, d_scratch, batch, stream=0):
+        """the half of apply that depends on the ciphertext alone: d_chat [q_count][batch][n] -> d_ext [digits][A][batch][n], every digit raised to
+        the active primes in NTT form; d_scratch: q_count*batch*n words"""
+        _check(lib().agx_ntt_keyswitch_decompose(self._h, d_chat, d_ext, d_scratch, batch, stream), "keyswitch_decompose")
+
+    def apply_decomposed(self, d_ext, d_keyhat, d_out, d_scratch, batch, galois_elt, stream=0):
+        """the other half, with d_ext (unchanged) read through X -> X^galois_elt: key-switches sigma_g(c) with d_keyhat, a key for sigma_g(s) -> s,
+        into d_out [2][q_count][batch][n]; d_scratch: 2*A*batch*n words; galois_elt = 1 after decompose is apply word for word"""
+        _check(lib().agx_ntt_keyswitch_apply_decomposed(self._h, d_ext, d_keyhat, d_out, d_scratch, batch, galois_elt, stream), "keyswitch_apply_decomposed")
+
+    def hoisted_info(self):
+        """(launches_decompose, launches_apply_decomposed) under the plan's current variant; their sum is info()'s launches"""
+        v = [_int(0), _int(0)]
+        _check(lib().agx_ntt_keyswitch_hoisted_info(self._h, ctypes.byref(v[0]), ctypes.byref(v[1])), "keyswitch_hoisted_info")
+        return v[0].value, v[1].value
 
     def close(self):
         if self._h:

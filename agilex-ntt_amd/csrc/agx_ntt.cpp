@@ -834,8 +834,9 @@ int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, con
     return AGX_OK;
 }
 
-int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
-                          uint32_t terms, uint32_t outputs, void* stream) {
+// agx_ntt_inner_product and agx_ntt_inner_product_galois: one statement of the rules, the Galois element's between the overlap rule and the device's
+static int inner_product_call(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
+                              uint32_t terms, uint32_t outputs, uint32_t galois_elt, void* stream) {
     if (!plan || !d_a || !d_bhat || !d_c) return AGX_ERR_NULL_POINTER;
     if (terms == 0 || terms > AGX_INNER_MAX_TERMS || outputs == 0 || outputs > AGX_INNER_MAX_OUTPUTS || (bhat_batch != batch && bhat_batch != 1)) return AGX_ERR_BAD_ARGUMENT;
     if (!aligned8(d_a) || !aligned8(d_bhat) || !aligned8(d_c)) return AGX_ERR_BAD_ARGUMENT;
@@ -847,10 +848,21 @@ int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const u
     const uint64_t slab = batch * n, a_words = terms * P * slab, b_words = (uint64_t)terms * outputs * P * bhat_batch * n, c_words = outputs * P * slab;      // each <= 2^60
     // out of place only, equal pointers included: c_o of a word is written once, but by a thread that other threads' reads of a and bhat do not wait for
     if (ranges_touch(addr(d_c), c_words, addr(d_a), a_words) || ranges_touch(addr(d_c), c_words, addr(d_bhat), b_words)) return AGX_ERR_BAD_ARGUMENT;
+    if (!(galois_elt & 1u) || galois_elt >= 2u * n) return AGX_ERR_BAD_ARGUMENT;
     if (int rc = check_plan(plan)) return rc;
     if (batch == 0) return AGX_OK;
-    AGX_HIP(launch_inner_product(plan->routes.forward, inner_primes{P, P, 0}, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, static_cast<hipStream_t>(stream)));
+    AGX_HIP(launch_inner_product_galois(plan->routes.forward, inner_primes{P, P, 0}, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, galois_elt, static_cast<hipStream_t>(stream)));
     return AGX_OK;
+}
+
+int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
+                          uint32_t terms, uint32_t outputs, void* stream) {
+    return inner_product_call(plan, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, 1, stream);      // g = 1 (n >= 2: legal on every plan): the un-gathered kernel
+}
+
+int agx_ntt_inner_product_galois(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
+                                 uint32_t terms, uint32_t outputs, uint32_t galois_elt, void* stream) {
+    return inner_product_call(plan, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, galois_elt, stream);
 }
 
 int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha) {
@@ -923,6 +935,116 @@ int agx_ntt_keyswitch_scratch_words(const agx_ntt_keyswitch* ks, uint64_t batch,
     return AGX_OK;
 }
 
+int agx_ntt_keyswitch_hoisted_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* ext_words, uint64_t* decompose_scratch_words, uint64_t* apply_scratch_words) {
+    if (!ks) return AGX_ERR_NULL_POINTER;
+    keyswitch_hoisted part;
+    if (!keyswitch_hoisted_partition(ks->shape, ks->plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;
+    if (ext_words) *ext_words = part.ext;
+    if (decompose_scratch_words) *decompose_scratch_words = part.decompose_scratch;
+    if (apply_scratch_words) *apply_scratch_words = part.apply_scratch;
+    return AGX_OK;
+}
+
+int agx_ntt_keyswitch_hoisted_info(const agx_ntt_keyswitch* ks, int* launches_decompose, int* launches_apply_decomposed) {
+    if (!ks) return AGX_ERR_NULL_POINTER;
+    // the two halves of agx_ntt_keyswitch_info's sum, each under the plan's current variant
+    if (launches_decompose) {
+        int extend[2 * kKeyswitchMaxDigits];
+        for (size_t i = 0; i < ks->up.size(); ++i) (void)agx_ntt_basis_info(ks->up[i], nullptr, nullptr, nullptr, nullptr, &extend[i]);
+        *launches_decompose = keyswitch_launches_decompose(inverse_launches(ks->plan), extend, (uint32_t)ks->up.size());
+    }
+    if (launches_apply_decomposed) {
+        int down = 0;
+        (void)agx_ntt_basis_mod_down_info(ks->down, &down);
+        *launches_apply_decomposed = keyswitch_launches_apply_decomposed(down);
+    }
+    return AGX_OK;
+}
+
+// Steps 1 and 2 of a key switch, every argument checked by the caller: coeff [Q][batch][n] <- INTT(chat), ext [digits][A][batch][n] <- ModUp of every digit
+static int keyswitch_decompose_steps(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, uint64_t* ext, uint64_t* coeff, uint64_t batch, void* stream) {
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    const uint32_t Q = k.q_count, A = k.active(), digits = k.digits();
+    const uint64_t slab = batch * plan->n;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // (1) coeff_j <- INTT_j(chat_j) in [0, q_j): the plan's inverse on the view of primes [0, Q), as ModDown runs it on its sources: no second plan
+    const frame_layout fl = dense(plan, batch);
+    const route qr = prime_range(plan->routes.inverse, 0, Q);
+    AGX_HIP(qr.rb ? qr.rb->launch_inv(qr, d_chat, nullptr, coeff, fl, s) : launch_inverse_radix2(qr, d_chat, coeff, fl, s));
+    // (2) ext_d <- NTT_j(e_{d,j}) for every active j: agx_ntt_basis_extend of digit d's slabs of coeff, routes as that call chooses them.  A digit's
+    // own slabs are transformed again (they come out as chat_j reduced); copying them instead was not measured, so it is not done.
+    for (uint32_t d = 0, b = 0; d < digits; ++d) {
+        const uint64_t* x = coeff + (uint64_t)d * k.alpha * slab;
+        uint64_t* e = ext + (uint64_t)d * A * slab;
+        if (int rc = agx_ntt_basis_extend(ks->up[b++], x, e, batch, AGX_FORM_NTT, stream)) return rc;
+        if (k.apart())
+            if (int rc = agx_ntt_basis_extend(ks->up[b++], x, e + Q * slab, batch, AGX_FORM_NTT, stream)) return rc;
+    }
+    return AGX_OK;
+}
+
+// Steps 3 and 4, every argument checked by the caller: acc [2][A][batch][n] <- sum_d pi_g(ext_d) o key_{d,o}, out [2][Q][batch][n] <- ModDown of each half
+static int keyswitch_apply_steps(const agx_ntt_keyswitch* ks, const uint64_t* ext, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* acc, uint64_t batch,
+                                 uint32_t galois_elt, void* stream) {
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    const uint32_t Q = k.q_count, A = k.active();
+    const uint64_t slab = batch * plan->n;
+    // (3) acc_o <- sum_d pi_g(ext_d) o key_{d,o} over the active primes: one launch, the key broadcast over the batch; g = 1 is the un-gathered kernel
+    AGX_HIP(launch_inner_product_galois(plan->routes.forward, inner_primes{A, Q, k.p_first - Q}, ext, d_keyhat, acc, batch, 1, k.digits(), 2, galois_elt,
+                                        static_cast<hipStream_t>(stream)));
+    // (4) out_o <- ModDown of acc_o, its special slabs given up as the scratch
+    for (uint32_t o = 0; o < 2; ++o) {
+        uint64_t* xq = acc + (uint64_t)o * A * slab;
+        if (int rc = agx_ntt_basis_mod_down(ks->down, xq, xq + Q * slab, d_out + o * Q * slab, xq + Q * slab, batch, stream)) return rc;
+    }
+    return AGX_OK;
+}
+
+// the rules the two halves share, after the NULL rule and the 2^60 limits: alignment, the two grid limits, and no two of the call's `count` buffers touching
+static bool keyswitch_buffers_ok(const agx_ntt_keyswitch* ks, uint64_t batch, const uintptr_t* base, const uint64_t* words, int count) {
+    for (int i = 0; i < count; ++i)
+        if (base[i] & 7u) return false;
+    // batch past the grid limit; A workgroups per group of frames on the one-launch ModUp and the two-launch ModDown (at least one frame per workgroup)
+    if (!batch_fits_grid(ks->plan, batch) || (uint64_t)ks->shape.active() * batch > 0x7fffffffull) return false;
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j)
+            if (ranges_touch(base[i], words[i], base[j], words[j])) return false;
+    return true;
+}
+
+int agx_ntt_keyswitch_decompose(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, uint64_t* d_ext, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!ks || !d_chat || !d_ext || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = ks->plan;
+    keyswitch_hoisted part;
+    if (!keyswitch_hoisted_partition(ks->shape, plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;      // every extent below is one of its three
+    const uintptr_t base[3] = {addr(d_chat), addr(d_ext), addr(d_scratch)};
+    const uint64_t words[3] = {part.decompose_scratch, part.ext, part.decompose_scratch};
+    if (!keyswitch_buffers_ok(ks, batch, base, words, 3)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    return keyswitch_decompose_steps(ks, d_chat, d_ext, d_scratch, batch, stream);
+}
+
+int agx_ntt_keyswitch_apply_decomposed(const agx_ntt_keyswitch* ks, const uint64_t* d_ext, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch,
+                                       uint64_t batch, uint32_t galois_elt, void* stream) {
+    if (!ks || !d_ext || !d_keyhat || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    keyswitch_hoisted part;
+    if (!keyswitch_hoisted_partition(k, plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;
+    const uintptr_t base[4] = {addr(d_ext), addr(d_keyhat), addr(d_out), addr(d_scratch)};
+    const uint64_t words[4] = {part.ext, (uint64_t)k.digits() * 2 * k.active() * plan->n, 2 * part.decompose_scratch, part.apply_scratch};
+    if (!keyswitch_buffers_ok(ks, batch, base, words, 4)) return AGX_ERR_BAD_ARGUMENT;
+    if (!(galois_elt & 1u) || galois_elt >= 2u * plan->n) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;      // ModDown runs the plan's inverse
+    if (batch == 0) return AGX_OK;
+    return keyswitch_apply_steps(ks, d_ext, d_keyhat, d_out, d_scratch, batch, galois_elt, stream);
+}
+
 int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream) {
     if (!ks || !d_chat || !d_keyhat || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
     const agx_ntt_plan* plan = ks->plan;
@@ -942,29 +1064,9 @@ int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat,
     if (int rc = check_plan(plan)) return rc;
     if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
     if (batch == 0) return AGX_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint64_t *coeff = d_scratch + part.coeff, *ext = d_scratch + part.ext, *acc = d_scratch + part.acc;
-    // (1) coeff_j <- INTT_j(chat_j) in [0, q_j): the plan's inverse on the view of primes [0, Q), as ModDown runs it on its sources: no second plan
-    const frame_layout fl = dense(plan, batch);
-    const route qr = prime_range(plan->routes.inverse, 0, Q);
-    AGX_HIP(qr.rb ? qr.rb->launch_inv(qr, d_chat, nullptr, coeff, fl, s) : launch_inverse_radix2(qr, d_chat, coeff, fl, s));
-    // (2) ext_d <- NTT_j(e_{d,j}) for every active j: agx_ntt_basis_extend of digit d's slabs of coeff, routes as that call chooses them.  A digit's
-    // own slabs are transformed again (they come out as chat_j reduced); copying them instead was not measured, so it is not done.
-    for (uint32_t d = 0, b = 0; d < digits; ++d) {
-        const uint64_t* x = coeff + (uint64_t)d * k.alpha * slab;
-        uint64_t* e = ext + (uint64_t)d * A * slab;
-        if (int rc = agx_ntt_basis_extend(ks->up[b++], x, e, batch, AGX_FORM_NTT, stream)) return rc;
-        if (k.apart())
-            if (int rc = agx_ntt_basis_extend(ks->up[b++], x, e + Q * slab, batch, AGX_FORM_NTT, stream)) return rc;
-    }
-    // (3) acc_o <- sum_d ext_d o key_{d,o} over the active primes: one launch, the key broadcast over the batch
-    AGX_HIP(launch_inner_product(plan->routes.forward, inner_primes{A, Q, k.p_first - Q}, ext, d_keyhat, acc, batch, 1, digits, 2, s));
-    // (4) out_o <- ModDown of acc_o, its special slabs given up as the scratch
-    for (uint32_t o = 0; o < 2; ++o) {
-        uint64_t* xq = acc + (uint64_t)o * A * slab;
-        if (int rc = agx_ntt_basis_mod_down(ks->down, xq, xq + Q * slab, d_out + o * chat_words, xq + Q * slab, batch, stream)) return rc;
-    }
-    return AGX_OK;
+    // the two halves on the three parts of the one scratch, with g = 1: the un-gathered inner product
+    if (int rc = keyswitch_decompose_steps(ks, d_chat, d_scratch + part.ext, d_scratch + part.coeff, batch, stream)) return rc;
+    return keyswitch_apply_steps(ks, d_scratch + part.ext, d_keyhat, d_out, d_scratch + part.acc, batch, 1, stream);
 }
 
 int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly, uint64_t seed, void* stream) {

@@ -54,12 +54,43 @@ inline bool keyswitch_scratch_partition(const keyswitch_shape& k, uint32_t n, ui
     return true;
 }
 
-// kernel launches of one apply call: the inverse of Q, every ModUp call (extend[0 .. extend_calls): one per digit, two where the special primes lie
-// apart), one inner product, two ModDown calls
-inline int keyswitch_launches(int inverse, const int* extend, uint32_t extend_calls, int mod_down) {
-    int total = inverse + 1 + 2 * mod_down;
+// The buffers of the two halves of an apply call (agx_ntt_keyswitch_decompose, agx_ntt_keyswitch_apply_decomposed), each one dense part of the above
+// in a buffer of its own:
+//   ext               [digits][A][batch][n]   what decompose writes and apply_decomposed reads: keyswitch_scratch's ext part
+//   decompose_scratch [q_count][batch][n]     its coeff part
+//   apply_scratch     [2][A][batch][n]        its acc part
+struct keyswitch_hoisted {
+    uint64_t ext = 0, decompose_scratch = 0, apply_scratch = 0;      // sizes in words
+};
+
+// false when batch n or any of the three would pass 2^60 words (128-bit arithmetic, as above).  The three are the sizes of keyswitch_scratch's parts;
+// their sum is not limited here: no call takes the three in one buffer.
+inline bool keyswitch_hoisted_partition(const keyswitch_shape& k, uint32_t n, uint64_t batch, keyswitch_hoisted* out) {
+    using u128 = unsigned __int128;
+    const u128 limit = (u128)1 << 60;
+    const u128 slab = (u128)batch * n;
+    const u128 coeff = slab * k.q_count, ext = slab * k.active() * k.digits(), acc = slab * k.active() * 2;
+    if (slab > limit || coeff > limit || ext > limit || acc > limit) return false;
+    out->ext = (uint64_t)ext;
+    out->decompose_scratch = (uint64_t)coeff;
+    out->apply_scratch = (uint64_t)acc;
+    return true;
+}
+
+// kernel launches of the first half of an apply call: the inverse of Q and every ModUp call (extend[0 .. extend_calls): one per digit, two where the
+// special primes lie apart)
+inline int keyswitch_launches_decompose(int inverse, const int* extend, uint32_t extend_calls) {
+    int total = inverse;
     for (uint32_t i = 0; i < extend_calls; ++i) total += extend[i];
     return total;
+}
+
+// of the second half: one inner product, two ModDown calls
+inline int keyswitch_launches_apply_decomposed(int mod_down) { return 1 + 2 * mod_down; }
+
+// of one apply call: both halves
+inline int keyswitch_launches(int inverse, const int* extend, uint32_t extend_calls, int mod_down) {
+    return keyswitch_launches_decompose(inverse, extend, extend_calls) + keyswitch_launches_apply_decomposed(mod_down);
 }
 
 }  // namespace agx

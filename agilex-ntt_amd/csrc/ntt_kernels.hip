@@ -262,6 +262,61 @@ __global__ void inner_product_kernel(const W* __restrict__ a, const W* __restric
     }
 }
 
+// agx_ntt_inner_product_galois: the same sum with a read through pi(i) = brev((g brev(i) + (g-1)/2) mod n), the permutation of
+// automorphism_ntt_kernel below: c_o[i] = sum_t a_t[pi(i)] o bhat_{t,o}[i].  The key and c stay at natural positions.  The same grid-stride shape,
+// groups of four terms and 128-bit sums as inner_product_kernel; pi is formed once per work item and serves every term, since the terms of a
+// differ by a stride only.  An aligned block of 2^m output positions reads one aligned block of 2^m input positions, so a wave that produces 64
+// consecutive W reads one aligned 512-byte (pair form: 1 KiB) segment of each term in permuted lane order.  In the pair form the output pair
+// (2i, 2i+1) reads the input pair (2j, 2j+1) with the halves swapped iff the low bit of pi(2i) is set -- the argument written at
+// automorphism_ntt_x2_kernel.  No LDS, no barrier, no table.  The host sends g = 1 to inner_product_kernel.
+struct inner_galois_args {
+    inner_args in;
+    uint32_t log_n, g;                       // g odd, below 2n
+};
+
+__device__ __forceinline__ uint64_t inner_gather(uint64_t v, bool) { return v; }
+__device__ __forceinline__ ulonglong2 inner_gather(ulonglong2 v, bool swap) { return swap ? make_ulonglong2(v.y, v.x) : v; }
+
+template <int OUT, class W>
+__global__ void inner_product_galois_kernel(const W* __restrict__ a, const W* __restrict__ bhat, W* __restrict__ c, const prime_consts* __restrict__ consts,
+                                            inner_galois_args ga) {
+    constexpr int kLanes = sizeof(W) / 8, kGroup = 4;
+    const inner_args& g = ga.in;
+    const uint32_t slot = blockIdx.y;
+    const prime_consts k = consts[slot < g.split ? slot : slot + g.skip];
+    const uint64_t q2 = k.q << 1;
+    const uint32_t mask = (1u << ga.log_n) - 1u, shift = 32u - ga.log_n, half = (ga.g - 1u) >> 1;
+    const W* ap = a + (uint64_t)slot * g.per_prime;
+    const W* bp = bhat + (uint64_t)slot * g.b_prime;
+    W* cp = c + (uint64_t)slot * g.per_prime;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t w = (uint32_t)i & g.frame_mask;      // the position within the frame, in W; its first word is w kLanes (even in pair form)
+        const uint32_t j = __brev((ga.g * (__brev(w * kLanes) >> shift) + half) & mask) >> shift;      // g < 2^16, brev < 2^15
+        const uint64_t ai = (i - w) + j / kLanes;
+        const bool swap = kLanes == 2 && (j & 1u);
+        const uint64_t bi = g.broadcast ? w : i;
+        acc128 s[OUT][kLanes];
+        for (uint32_t t0 = 0; t0 < g.terms; t0 += kGroup) {
+            W av[kGroup], bv[kGroup][OUT];
+#pragma unroll
+            for (int u = 0; u < kGroup; ++u)
+                if (t0 + u < g.terms) {
+                    av[u] = ap[(t0 + u) * g.a_term + ai];
+#pragma unroll
+                    for (int o = 0; o < OUT; ++o) bv[u][o] = bp[(t0 + u) * g.b_term + o * g.b_out + bi];
+                }
+#pragma unroll
+            for (int u = 0; u < kGroup; ++u)
+                if (t0 + u < g.terms) {
+#pragma unroll
+                    for (int o = 0; o < OUT; ++o) inner_lanes(s[o], inner_gather(av[u], swap), bv[u][o], k.q, q2);
+                }
+        }
+#pragma unroll
+        for (int o = 0; o < OUT; ++o) inner_store(cp + o * g.c_out + i, s[o], k);
+    }
+}
+
 // agx_ntt_rescale, generic route, in the coefficient domain: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i with u_i the lift of t[k] to q_i
 // (rescale_lift).  out: dense [prime][batch][n] over the view's primes 0 .. P-2, values in [0,q_i) as the inverse leaves them; t: [batch][n]
 // in [0,q_L), shared by the primes.
@@ -556,9 +611,12 @@ hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64
     return hipGetLastError();
 }
 
-hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
-                                uint64_t bhat_batch, uint32_t terms, uint32_t outputs, hipStream_t s) {
-    const bool pairs = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bhat) | reinterpret_cast<uintptr_t>(c)) & 15u) == 0;
+// the 16-byte form serves when all three bases are 16-byte aligned
+static bool inner_pairs(const uint64_t* a, const uint64_t* bhat, const uint64_t* c) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bhat) | reinterpret_cast<uintptr_t>(c)) & 15u) == 0;
+}
+
+static inner_args inner_args_of(const plan_view& pv, const inner_primes& ip, uint64_t batch, uint64_t bhat_batch, uint32_t terms, uint32_t outputs, bool pairs) {
     const uint32_t shift = pairs ? 1 : 0;      // n >= 2 is even: a frame is a whole number of pairs
     inner_args g;
     g.per_prime = (batch << pv.log_n) >> shift;
@@ -569,6 +627,32 @@ hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, con
     g.frame_mask = (pv.n >> shift) - 1u;
     g.broadcast = bhat_batch == 1 && batch != 1 ? 1u : 0u;
     g.terms = terms, g.split = ip.split, g.skip = ip.skip;
+    return g;
+}
+
+hipError_t launch_inner_product_galois(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
+                                       uint64_t bhat_batch, uint32_t terms, uint32_t outputs, uint32_t galois_elt, hipStream_t s) {
+    if (galois_elt == 1) return launch_inner_product(pv, ip, a, bhat, c, batch, bhat_batch, terms, outputs, s);      // pi is the identity: the plain kernel
+    const bool pairs = inner_pairs(a, bhat, c);
+    const inner_galois_args g{inner_args_of(pv, ip, batch, bhat_batch, terms, outputs, pairs), pv.log_n, galois_elt};
+    const dim3 grid(grid_1d(g.in.per_prime, 256), ip.count);
+    auto go = [&](auto kernel, auto* ap, auto* bp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, cp, pv.consts, g); };
+    if (pairs) {
+        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2*>(a), *b2 = reinterpret_cast<const ulonglong2*>(bhat);
+        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(c);
+        if (outputs == 1) go(inner_product_galois_kernel<1, ulonglong2>, a2, b2, c2);
+        else go(inner_product_galois_kernel<2, ulonglong2>, a2, b2, c2);
+    } else {
+        if (outputs == 1) go(inner_product_galois_kernel<1, uint64_t>, a, bhat, c);
+        else go(inner_product_galois_kernel<2, uint64_t>, a, bhat, c);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
+                                uint64_t bhat_batch, uint32_t terms, uint32_t outputs, hipStream_t s) {
+    const bool pairs = inner_pairs(a, bhat, c);
+    const inner_args g = inner_args_of(pv, ip, batch, bhat_batch, terms, outputs, pairs);
     const dim3 grid(grid_1d(g.per_prime, 256), ip.count);
     auto go = [&](auto kernel, auto* ap, auto* bp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, cp, pv.consts, g); };
     if (pairs) {

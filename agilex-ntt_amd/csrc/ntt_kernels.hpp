@@ -93,6 +93,10 @@ struct inner_primes {
 // (only its constants are read).  16-byte accesses when all three bases allow them.  terms 1 .. 16, outputs 1 or 2.  One launch.
 hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
                                 uint64_t bhat_batch, uint32_t terms, uint32_t outputs, hipStream_t s);
+// agx_ntt_inner_product_galois: the same with a read through pi(i) = brev((g brev(i) + (g-1)/2) mod n) within every frame: c_o[i] = sum_t a_t[pi(i)] o
+// bhat_{t,o}[i]; g odd in [1, 2n).  No permuted copy of a is written.  One launch; g = 1 takes launch_inner_product's kernel.
+hipError_t launch_inner_product_galois(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
+                                       uint64_t bhat_batch, uint32_t terms, uint32_t outputs, uint32_t galois_elt, hipStream_t s);
 // the coefficient-domain step of agx_ntt_rescale's generic route: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i on the dense [prime][batch][n]
 // layout of pv's primes (a view of primes 0 .. P-2), u_i the lift of t[k] ([batch][n], coefficients of the last slab in [0, q_L)) to q_i
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s);

@@ -327,6 +327,22 @@ AGX_API int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launche
 AGX_API int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
                                   uint32_t terms, uint32_t outputs, void* stream);
 
+/* The inner product with `a` read through a Galois automorphism: operands, layouts, ranges, limits and status order are agx_ntt_inner_product's.  Per word,
+ * with pi_g(i) = brev((g brev(i) + (g - 1) / 2) mod n), the permutation agx_ntt_automorphism applies to an NTT-form frame,
+ *   c_o[p][b][i] = (sum_t (a_t[p][b][pi_g(i)] mod q_p) (bhat_{t,o}[p][b or 0][i] mod q_p)) mod q_p.
+ * Only `a` is read through pi_g; the key and c sit at natural positions.  Word for word this is agx_ntt_automorphism(AGX_FORM_NTT, g) on every frame of `a`
+ * followed by agx_ntt_inner_product, without the permuted copy of `a` or the scratch it would need; galois_elt = 1 is agx_ntt_inner_product itself (and runs
+ * its kernel).  One rule is added, checked after the overlap rule and before the device's: galois_elt even, 0 or >= 2n: AGX_ERR_BAD_ARGUMENT, nothing written.
+ * Out of place, asynchronous, allocates nothing, touches no plan state, capturable into a hipGraph; ONE launch on every plan: the same streaming kernel with
+ * pi_g formed once per work item, no LDS, no barrier, no table; 16-byte accesses when all three bases are 16-byte aligned (an output pair reads one input
+ * pair, its halves swapped or not), 8-byte ones otherwise.  A wave reads the same aligned segments of `a` as the plain kernel, in another lane order.
+ * Measured (profiles/r11_hoisted_rotations.md; six 60-bit primes, key switch shapes (4, 4, 2, 2) and (3, 4, 2, 2): two terms, two outputs, broadcast key over 6 and
+ * 5 primes, g = 5, n = 4096 with 4,096 frames per prime and n = 16384 with 1,024): 1.07 of the time of agx_ntt_inner_product in all four rows (737 against 686 us at n = 4096
+ * over 6 primes) -- SLOWER than the plain kernel by 7 %, the min ... max spreads do not overlap -- and 0.60 of agx_ntt_automorphism into a permuted copy followed by
+ * agx_ntt_inner_product (1227 us), which also needs terms P batch n words for that copy. */
+AGX_API int agx_ntt_inner_product_galois(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch,
+                                         uint64_t bhat_batch, uint32_t terms, uint32_t outputs, uint32_t galois_elt, void* stream);
+
 /* The RNS hybrid key switch of one ciphertext component in one call: NTT form in, NTT form out, at any level.
  * Primes.  Q, the ciphertext's current level, is the plan's primes [0, q_count).  The special primes are [p_first, p_first + p_count), p_first >= q_count:
  * they need not follow Q directly, which is what a level below the top looks like.  The ACTIVE primes are Q followed by the special primes, A = q_count +
@@ -367,6 +383,41 @@ AGX_API int agx_ntt_keyswitch_info(const agx_ntt_keyswitch* ks, uint32_t* q_coun
 AGX_API int agx_ntt_keyswitch_scratch_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* words);
 AGX_API int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch,
                                     uint64_t batch, void* stream);
+
+/* The key switch in two halves, for rotating ONE ciphertext by several steps (hoisting, Halevi-Shoup): steps 1 and 2 above depend on the ciphertext alone,
+ * so they are done once, and every Galois element g pays for steps 3 and 4 only.  Both calls work on an agx_ntt_keyswitch handle as created above.
+ *   decompose        : steps 1 and 2.  d_chat [q_count][batch][n] as for apply, left unchanged; d_ext [digits][A][batch][n] receives NTT_j(e_{d,j}), fully
+ *                      reduced: exactly the words apply forms in the ext part of its scratch; d_scratch: q_count batch n words (the coefficient form).
+ *   apply_decomposed : steps 3 and 4 with ext read through pi_g (agx_ntt_inner_product_galois): acc_{o,j} = sum_d pi_g(ext_{d,j}) o key_{d,o,j}, one launch
+ *                      over the active primes with the key broadcast, then the two agx_ntt_basis_mod_down calls of step 4, the special slabs of acc_o their
+ *                      scratch.  d_ext is const and unchanged: one decomposition serves any number of Galois elements and keys.  d_keyhat [digits][2][A][n]
+ *                      and d_out [2][q_count][batch][n] (fully reduced) as for apply; d_scratch: 2 A batch n words.
+ * What it computes.  pi_g(ext_d) is the NTT form of sigma_g(V_d) mod q_j (sigma_g: X -> X^g), consistently over every active j, and sigma_g(V_d) is an integer
+ * polynomial with coefficients in (-S D_d, S D_d), S the digit's source count, congruent to sigma_g(c) modulo D_d.  So the call key-switches sigma_g(c) with a
+ * key for sigma_g(s) -> s, and every output word is exact against big-integer arithmetic.  For g != 1 the result is NOT word-equal to agx_ntt_automorphism on
+ * chat followed by apply: the approximate lift does not commute with negation, and the two results differ by what both approximate conversions already leave
+ * to the noise.  For g = 1, decompose followed by apply_decomposed equals apply word for word (apply IS the two halves on the parts of its scratch).  Adding
+ * sigma_g(c0) to out_0 is the caller's step.
+ *   hoisted_words : the sizes in words of d_ext, decompose's scratch and apply_decomposed's scratch: the ext, coeff and acc parts of scratch_words.  A NULL
+ *                   handle: AGX_ERR_NULL_POINTER; a count past 2^60 words: AGX_ERR_BAD_ARGUMENT; any out-pointer may be NULL.
+ *   hoisted_info  : launches_decompose = the inverse on Q + what agx_ntt_basis_info reports for every ModUp basis; launches_apply_decomposed = 1 + 2 x what
+ *                   agx_ntt_basis_mod_down_info reports; their sum is agx_ntt_keyswitch_info's launches.  Under the plan's CURRENT variant; either may be NULL.
+ *   Status order of both halves, as apply: a NULL pointer: AGX_ERR_NULL_POINTER; a pointer not 8-byte aligned, a batch past the grid limit or with A batch above
+ *   2^31 - 1, an extent past 2^60 words, any two of the call's buffers touching anywhere (ranges that meet end to end do not touch); then, apply_decomposed
+ *   only, galois_elt even, 0 or >= 2n; then the plan's device not current: AGX_ERR_BAD_ARGUMENT, nothing written; a plan without inverse tables:
+ *   AGX_ERR_NO_INVERSE; batch == 0: AGX_OK, nothing launched.  Asynchronous on `stream`, allocate and synchronise nothing (capturable into a hipGraph).
+ * Measured (profiles/r11_hoisted_rotations.md; six 60-bit primes, g = 5 and its powers): at n = 4096, (4, 4, 2, 2), 4,096 frames per prime decompose takes 1434 us and
+ * one apply_decomposed 1908 us, together 1.013 of apply's 3299 us (1.010 ... 1.015 over the four rows: the gathered inner product costs 7 % more than the plain one).  Against R x
+ * (agx_ntt_automorphism on chat + apply), decompose once + R x apply_decomposed takes 0.97 at R = 1, 0.66 at R = 4 and 0.60 at R = 8 (16.75 against 27.76 ms); over both shapes and
+ * n = 4096 / 16384: 0.965 ... 0.976, 0.642 ... 0.659, 0.587 ... 0.606.  apply itself, beside the library before the split in the same session: 3327 against 3333 us, 2746 / 2747,
+ * 3840 / 3841, 3128 / 3128 -- the spreads overlap in every row.
+ * Groups: no group form, as for bases and key switches: each shard calls the halves on its own handle. */
+AGX_API int agx_ntt_keyswitch_hoisted_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* ext_words, uint64_t* decompose_scratch_words,
+                                            uint64_t* apply_scratch_words);
+AGX_API int agx_ntt_keyswitch_decompose(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, uint64_t* d_ext, uint64_t* d_scratch, uint64_t batch, void* stream);
+AGX_API int agx_ntt_keyswitch_apply_decomposed(const agx_ntt_keyswitch* ks, const uint64_t* d_ext, const uint64_t* d_keyhat, uint64_t* d_out,
+                                               uint64_t* d_scratch, uint64_t batch, uint32_t galois_elt, void* stream);
+AGX_API int agx_ntt_keyswitch_hoisted_info(const agx_ntt_keyswitch* ks, int* launches_decompose, int* launches_apply_decomposed);
 
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */

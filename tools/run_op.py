@@ -6,6 +6,8 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent} --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
        python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
+       python3 tools/run_op.py --op hoist --qcount Q --rotations R [R ...] [--galois G --pfirst F --pcount K --alpha A --reps 7 ...]   (hoisted rotations: agx_ntt_inner_product_galois
+                                                                   beside the plain kernel and automorphism + inner product; decompose + R apply_decomposed beside R automorphism + apply)
 Under the profiler: rocprofv3 ... -- python3 tools/run_op.py ...   (the interpreter itself after `--`, never this file: an
 `env` shebang hop after the profiler's preload has initialised the GPU is a forbidden exec on this pool)."""
 import argparse
@@ -20,7 +22,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "inner", "keyswitch"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "inner", "keyswitch", "hoist"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -50,12 +52,13 @@ ap.add_argument("--qcount", type=int, default=4, help="keyswitch: Q = primes [0,
 ap.add_argument("--pfirst", type=int, default=None, help="keyswitch: the special primes start here (default: qcount, the top level)")
 ap.add_argument("--pcount", type=int, default=2, help="keyswitch: special primes")
 ap.add_argument("--alpha", type=int, default=2, help="keyswitch: primes per digit")
+ap.add_argument("--rotations", type=int, nargs="+", default=[8], help="hoist: rotation counts R to time; rotation r uses the element galois^(r + 1) mod 2n")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
 if args.op == "moddown":
     args.dst = args.dst or 4
     args.primes = args.src + args.dst      # targets [0, T), sources [T, T + S)
-if args.op == "keyswitch":
+if args.op in ("keyswitch", "hoist"):
     args.pfirst = args.qcount if args.pfirst is None else args.pfirst
     args.primes = args.pfirst + args.pcount
 args.only = args.only or ("all" if args.op == "moddown" else "both")
@@ -447,8 +450,109 @@ def run_keyswitch():
     plan.close()
 
 
+def run_hoist():
+    """Hoisted rotations at the shape (--qcount, --pfirst, --pcount, --alpha), us per call, median (min ... max), the forms of a line alternating:
+      kernel    -- agx_ntt_inner_product_galois (terms = digits, two outputs, broadcast key, over the active primes, g = --galois) beside the plain
+                   agx_ntt_inner_product of the same shape and beside the pair it replaces: agx_ntt_automorphism(NTT) over the digits x A slabs into a
+                   permuted copy, then agx_ntt_inner_product;
+      halves    -- agx_ntt_keyswitch_decompose and one agx_ntt_keyswitch_apply_decomposed alone, beside agx_ntt_keyswitch_apply;
+      rotations -- for every R of --rotations: decompose once + R apply_decomposed beside R x (agx_ntt_automorphism on chat + agx_ntt_keyswitch_apply)."""
+    import statistics
+
+    Q, pf, pc, alpha, n, B = args.qcount, args.pfirst, args.pcount, args.alpha, args.n, args.batch
+    A, slab = Q + pc, args.batch * args.n
+    g0 = args.galois % (2 * n)
+    act = list(range(Q)) + list(range(pf, pf + pc))
+    psi = [plan.psi(p) for p in range(plan.num_primes)]
+    qplan = agx.Plan(n, plan.moduli[:Q], psi=psi[:Q])
+    aplan = agx.Plan(n, [plan.moduli[p] for p in act], psi=[psi[p] for p in act])
+    ks = plan.keyswitch(Q, pf, pc, alpha)
+    D = ks.info()[4]
+    ext_words, ds_words, as_words = ks.hoisted_words(B)
+    chat = torch.empty(plan.num_primes * slab, dtype=torch.int64, device="cuda")      # synthetic residues taken as NTT-form words; slabs [0, Q) are read
+    plan.fill_synthetic(chat.data_ptr(), B, 0, 42, stream)
+    key = torch.empty(D * 2 * A * n, dtype=torch.int64, device="cuda")      # [digits][2][A][n]
+    for k in range(D * 2):
+        aplan.fill_synthetic(key.data_ptr() + 8 * k * A * n, 1, k, 43, stream)
+    ext, perm = (torch.empty(ext_words, dtype=torch.int64, device="cuda") for _ in range(2))
+    rot, dscr, ascr = (torch.empty(w, dtype=torch.int64, device="cuda") for w in (Q * slab, ds_words, as_words))
+    acc, acc2 = (torch.empty(2 * A * slab, dtype=torch.int64, device="cuda") for _ in range(2))
+    out, out2 = (torch.empty(2 * Q * slab, dtype=torch.int64, device="cuda") for _ in range(2))
+    scratch = torch.empty(ks.scratch_words(B), dtype=torch.int64, device="cuda")
+
+    def galois():
+        aplan.inner_product_galois(ext.data_ptr(), key.data_ptr(), acc.data_ptr(), B, D, g0, 2, 1, stream)
+
+    def plain():
+        aplan.inner_product(ext.data_ptr(), key.data_ptr(), acc2.data_ptr(), B, D, 2, 1, stream)
+
+    def pair():
+        aplan.automorphism(ext.data_ptr(), perm.data_ptr(), D * B, g0, agx.FORM_NTT, stream)      # [D][A][B][n]: D A B frames, each permuted alike
+        aplan.inner_product(perm.data_ptr(), key.data_ptr(), acc2.data_ptr(), B, D, 2, 1, stream)
+
+    def decompose():
+        ks.decompose(chat.data_ptr(), ext.data_ptr(), dscr.data_ptr(), B, stream)
+
+    def apply_decomposed():
+        ks.apply_decomposed(ext.data_ptr(), key.data_ptr(), out.data_ptr(), ascr.data_ptr(), B, g0, stream)
+
+    def apply():
+        ks.apply(chat.data_ptr(), key.data_ptr(), out2.data_ptr(), scratch.data_ptr(), B, stream)
+
+    decompose()
+    galois()
+    pair()
+    torch.cuda.synchronize()
+    assert torch.equal(acc, acc2), "the gathered inner product and automorphism + inner product differ"
+    ks.apply_decomposed(ext.data_ptr(), key.data_ptr(), out.data_ptr(), ascr.data_ptr(), B, 1, stream)
+    apply()
+    torch.cuda.synchronize()
+    assert torch.equal(out, out2), "decompose + apply_decomposed(g = 1) and apply differ"
+    head = f"hoist n={n} shape=({Q}, {pf}, {pc}, {alpha}) batch={B} bits={args.bits} g={g0}"
+    report = {}
+    t = _alternate([galois, plain, pair])
+    report.update(t)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    print(f"{head} kernel (terms={D}, outputs=2, A={A}): galois {_fmt(t['galois'])} us; plain {_fmt(t['plain'])} us; automorphism + plain {_fmt(t['pair'])} us; "
+          f"ratio galois/plain {med['galois'] / med['plain']:.3f}; galois/pair {med['galois'] / med['pair']:.3f}")
+    t = _alternate([decompose, apply_decomposed, apply])
+    report.update(t)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    first, second = ks.hoisted_info()
+    print(f"{head} halves (launches {first} + {second}): decompose {_fmt(t['decompose'])} us; apply_decomposed {_fmt(t['apply_decomposed'])} us; apply {_fmt(t['apply'])} us; "
+          f"(decompose + apply_decomposed) / apply {(med['decompose'] + med['apply_decomposed']) / med['apply']:.3f}")
+    for R in args.rotations:
+        gs = [pow(g0, r + 1, 2 * n) for r in range(R)]
+
+        def hoisted():
+            decompose()
+            for g in gs:
+                ks.apply_decomposed(ext.data_ptr(), key.data_ptr(), out.data_ptr(), ascr.data_ptr(), B, g, stream)
+
+        def separate():
+            for g in gs:
+                qplan.automorphism(chat.data_ptr(), rot.data_ptr(), B, g, agx.FORM_NTT, stream)
+                ks.apply(rot.data_ptr(), key.data_ptr(), out2.data_ptr(), scratch.data_ptr(), B, stream)
+
+        t = _alternate([hoisted, separate])
+        report.update({f"{k}_{R}": v for k, v in t.items()})
+        med = {k: statistics.median(v) for k, v in t.items()}
+        print(f"{head} rotations R={R}: hoisted {_fmt(t['hoisted'])} us; automorphism + apply each {_fmt(t['separate'])} us; ratio {med['hoisted'] / med['separate']:.3f}")
+    if args.report:
+        import json
+
+        json.dump({"us": report, "launches": args.launches, "kernel_launches": [first, second]}, open(args.report, "w"))
+    ks.close()
+    qplan.close()
+    aplan.close()
+    plan.close()
+
+
 if args.op == "inner":
     run_inner()
+    sys.exit(0)
+if args.op == "hoist":
+    run_hoist()
     sys.exit(0)
 if args.op == "keyswitch":
     run_keyswitch()
