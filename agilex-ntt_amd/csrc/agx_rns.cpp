@@ -1,0 +1,423 @@
+// agx_rns.cpp -- the RNS calls of include/agx_ntt.h: rescale, basis extension and ModDown, the inner products and the key switch.  Each composes the
+// plan's transforms (run_forward / run_inverse on views of its routes, plan_internal.hpp) with a coefficient-domain or fused kernel; plans, routes and
+// the transform calls themselves live in agx_ntt.cpp.
+#include <cstdlib>
+#include <memory>
+
+#include "host_math.hpp"
+#include "plan_internal.hpp"
+
+using namespace agx;
+
+static bool targets_fit_grid(uint32_t T, uint64_t batch, int ppb) { return (uint64_t)T * ((batch + ppb - 1) / ppb) <= 0x7fffffffull; }      // grid limit of the fused kernels: T workgroups per group of ppb frames
+static bool dense_fits(uint32_t n, uint32_t slabs, uint64_t frames) { return layout_fits(n, slabs, frames, (int64_t)(frames * n), (int64_t)n); }      // one dense range of slabs x frames x n words (formed in 128 bits)
+static basis_view view_of(const agx_ntt_basis* b) { return basis_view{b->d_dinv, b->d_mat, b->d_dall, b->src_first, b->src_count, b->dst_first, b->dst_count}; }
+
+extern "C" {
+
+int agx_ntt_rescale(const agx_ntt_plan* plan, const uint64_t* d_x, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, int mode, void* stream) {
+    if (!plan || !d_x || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes;
+    if (P < 2 || (mode != AGX_RESCALE_FLOOR && mode != AGX_RESCALE_ROUND)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);
+    int rc = check_plan(plan);
+    if (rc || (rc = check_frames(plan, d_x, fl))) return rc;      // x: all P slabs
+    if (!aligned8(d_out) || !aligned8(d_scratch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t slab = (uint64_t)fl.prime_stride, head = (P - 1) * slab;
+    const uintptr_t x = addr(d_x), x_last = x + 8 * head;      // dense sets, one range each: x is P slabs, out P-1, the scratch one
+    if (!down_buffers_ok(x, head, x_last, slab, addr(d_out), addr(d_scratch))) return AGX_ERR_BAD_ARGUMENT;      // ModDown's rule with the last slab as xp
+    if (!plan->rescale_legal) return AGX_ERR_BAD_MODULUS;      // some q_i shares a factor with (distinct primes: equals) the last modulus
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    const bool round = mode == AGX_RESCALE_ROUND;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // scratch <- INTT_L(x_L), coefficients in [0, q_L): the plan's inverse on the view of prime P-1
+    const route last = prime_range(plan->routes.inverse, P - 1, P);
+    if (const route& r = plan->routes.rescale; r.rb) {
+        // two launches: the lift, the forward transform and (x_i - .) q_L^-1 stay on chip; a wave reads its words of x_i before it writes them
+        AGX_HIP(run_inverse(last, d_x + head, nullptr, d_scratch, fl, s));
+        AGX_HIP(r.rb->launch_rescale(prime_range(r, 0, P - 1), d_x, d_scratch, d_out, fl, round, s));
+        return AGX_OK;
+    }
+    // generic route, no more scratch: out <- INTT(x_0 .. x_{P-2}); scratch <- INTT_L(x_L); out <- (out - lift(scratch)) q_L^-1 in the
+    // coefficient domain; out <- NTT(out)
+    AGX_HIP(run_inverse(prime_range(plan->routes.inverse, 0, P - 1), d_x, nullptr, d_out, fl, s));
+    AGX_HIP(run_inverse(last, d_x + head, nullptr, d_scratch, fl, s));
+    const route head_route = prime_range(forward_route(plan, batch), 0, P - 1);
+    AGX_HIP(launch_rescale_coeff(head_route, d_out, d_scratch, batch, round, s));
+    AGX_HIP(run_forward(head_route, d_out, d_out, fl, s));
+    return AGX_OK;
+}
+
+int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    *basis = nullptr;
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes;
+    auto in_plan = [&](uint32_t first, uint32_t count) { return count >= 1 && count <= P && first <= P - count; };
+    if (!in_plan(src_first, src_count) || !in_plan(dst_first, dst_count) || src_count > AGX_BASIS_MAX_SRC) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    return guarded([&]() -> int {
+        const uint32_t S = src_count, T = dst_count;
+        std::vector<uint64_t> dinv(S), dinv_p(S), mat((size_t)T * S), mat_p((size_t)T * S);
+        // D_i must be invertible modulo q_i: two equal source moduli have no conversion
+        if (!basis_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, dinv.data(), dinv_p.data(), mat.data(), mat_p.data())) return AGX_ERR_BAD_MODULUS;
+        std::vector<ulonglong2> dinv_pairs(S), mat_pairs((size_t)T * S);
+        for (size_t k = 0; k < dinv_pairs.size(); ++k) dinv_pairs[k] = make_ulonglong2(dinv[k], dinv_p[k]);
+        for (size_t k = 0; k < mat_pairs.size(); ++k) mat_pairs[k] = make_ulonglong2(mat[k], mat_p[k]);
+        std::unique_ptr<agx_ntt_basis> b(new (std::nothrow) agx_ntt_basis);
+        if (!b) return AGX_ERR_ALLOC;
+        b->plan = plan;
+        b->src_first = src_first, b->src_count = S, b->dst_first = dst_first, b->dst_count = T;
+        if (int rc = b->d_dinv.upload(dinv_pairs)) return rc;
+        if (int rc = b->d_mat.upload(mat_pairs)) return rc;
+        // agx_ntt_basis_mod_down: D^-1 mod q_j, and the source primes' constants (the plan's host copy) with the inverse's last-stage factors scaled
+        // by D_i^-1.  A target that is a source modulus leaves the basis good for extend.
+        std::vector<prime_consts> sc(plan->consts.begin() + src_first, plan->consts.begin() + src_first + S);
+        std::vector<uint64_t> n_inv(S), w1n(S), dall(T), dall_p(T), sn(S), sn_p(S), sw(S), sw_p(S);
+        for (uint32_t i = 0; i < S; ++i) n_inv[i] = sc[i].n_inv, w1n[i] = sc[i].w1n;
+        b->moddown_legal = moddown_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, dinv.data(), n_inv.data(), w1n.data(), dall.data(),
+                                             dall_p.data(), sn.data(), sn_p.data(), sw.data(), sw_p.data());
+        for (uint32_t i = 0; i < S; ++i) sc[i].n_inv = sn[i], sc[i].n_inv_p = sn_p[i], sc[i].w1n = sw[i], sc[i].w1n_p = sw_p[i];
+        std::vector<ulonglong2> dall_pairs(T);
+        for (uint32_t j = 0; j < T; ++j) dall_pairs[j] = make_ulonglong2(dall[j], dall_p[j]);
+        if (int rc = b->d_dall.upload(dall_pairs)) return rc;
+        if (int rc = b->d_src_consts.upload(sc)) return rc;
+        *basis = b.release();
+        return AGX_OK;
+    });
+}
+
+int agx_ntt_basis_destroy(agx_ntt_basis* basis) {
+    delete basis;      // the device memory goes with its owners
+    return AGX_OK;
+}
+
+// Does an AGX_FORM_NTT call of this basis take the fused kernel?  The plan's entry must carry it, and the shape must be one at which it was measured
+// ahead of the unfused pair (profiles/r08_basis_extend.md).  Every workgroup of a frame forms the y_i again -- 2 S Shoup products per output word
+// beside the transform's log2(n) / 2 -- so the fused kernel's arithmetic grows with S while the pair's conversion stays bound by its traffic:
+//   S = 1: fused at every size (0.83 ... 0.92 of the pair's time);
+//   S = 2: fused (0.96 ... 0.99) except at n = 4096 and 16384, where it measured 1.02 and 1.01 of the pair;
+//   S >= 3: the pair (S = 4, 8, 16 measured: the fused kernel takes 1.21 ... 1.49 of its time; S = 3 not measured, taken with them).
+static bool extend_is_fused(const agx_ntt_basis* b) {
+    const agx_ntt_plan* p = b->plan;
+    if (!p->routes.extend.rb) return false;
+    return b->src_count == 1 || (b->src_count == 2 && p->log_n != 12 && p->log_n != 14);
+}
+
+int agx_ntt_basis_info(const agx_ntt_basis* basis, uint32_t* src_first, uint32_t* src_count, uint32_t* dst_first, uint32_t* dst_count, int* launches_ntt_form) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    if (src_first) *src_first = basis->src_first;
+    if (src_count) *src_count = basis->src_count;
+    if (dst_first) *dst_first = basis->dst_first;
+    if (dst_count) *dst_count = basis->dst_count;
+    if (launches_ntt_form) *launches_ntt_form = extend_is_fused(basis) ? 1 : 1 + forward_launches(basis->plan);
+    return AGX_OK;
+}
+
+int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    if (!basis || !d_x || !d_out) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = basis->plan;
+    if (out_form != AGX_FORM_COEFF && out_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    const uint32_t S = basis->src_count, T = basis->dst_count;
+    if (!aligned8(d_x) || !aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of x ([S][batch][n]) and of out ([T][batch][n]) alike
+    if (!dense_fits(plan->n, S, batch) || !dense_fits(plan->n, T, batch)) return AGX_ERR_BAD_ARGUMENT;
+    // out of place only: every workgroup of a frame reads all S source frames while others already write their targets
+    if (ranges_touch(addr(d_x), S * batch * plan->n, addr(d_out), T * batch * plan->n)) return AGX_ERR_BAD_ARGUMENT;
+    const basis_view bv = view_of(basis);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const route& r = plan->routes.extend; out_form == AGX_FORM_NTT && extend_is_fused(basis)) {
+        // one kernel: the conversion and the target prime's forward transform stay on chip
+        if (!targets_fit_grid(T, batch, r.rb->ppb)) return AGX_ERR_BAD_ARGUMENT;
+        if (batch == 0) return AGX_OK;
+        AGX_HIP(r.rb->launch_extend(r, bv, d_x, d_out, fl, s));
+        return AGX_OK;
+    }
+    if (batch == 0) return AGX_OK;
+    AGX_HIP(launch_basis_coeff(plan->routes.forward, bv, d_x, d_out, batch, s));
+    // the plan's forward on the view of the target primes, in place
+    if (out_form == AGX_FORM_NTT) AGX_HIP(run_forward(prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T), d_out, d_out, fl, s));
+    return AGX_OK;
+}
+
+// Does a mod_down call of this basis take the two-launch route?  The plan's entry must carry the fused kernel (n = 1024 ... 32768, some modulus
+// >= 2^31, not AGX_VARIANT_LDS_RADIX2); resolved at the call, so agx_ntt_plan_set_variant between calls stays legal.
+// It serves every source count: measured at S = 1, 2, 4, 8, 16 against the four-launch route on the same plan (profiles/r09_mod_down.md).
+static bool moddown_is_fused(const agx_ntt_basis* b) {
+#ifdef AGX_DIAG
+    // lib/libagxntt_diag.so only: AGX_NTT_MOD_DOWN_GENERIC=1 in the environment, read at every call, sends the call down the four-launch route on the
+    // same plan (tools/run_op.py --op moddown times the two routes side by side)
+    if (const char* e = std::getenv("AGX_NTT_MOD_DOWN_GENERIC"); e && e[0] == '1') return false;
+#endif
+    return b->plan->routes.moddown.rb != nullptr;
+}
+
+int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launches) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    // fused: the scaled inverse of the source slabs, then moddown_rb2; generic: both inverses, the coefficient-domain step, the forward
+    if (launches) *launches = moddown_is_fused(basis) ? inverse_launches(basis->plan) + 1 : 2 * inverse_launches(basis->plan) + 1 + forward_launches(basis->plan);
+    return AGX_OK;
+}
+
+int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!basis || !d_xq || !d_xp || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = basis->plan;
+    if (int rc = check_plan(plan)) return rc;
+    const uint32_t S = basis->src_count, T = basis->dst_count;
+    if (!aligned8(d_xq) || !aligned8(d_xp) || !aligned8(d_out) || !aligned8(d_scratch) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of xq and out ([T][batch][n]) and of xp and the scratch ([S][batch][n]) alike
+    if (!dense_fits(plan->n, S, batch) || !dense_fits(plan->n, T, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const bool fused = moddown_is_fused(basis);
+    const route& r = plan->routes.moddown;
+    if (fused && !targets_fit_grid(T, batch, r.rb->ppb)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t slab = (uint64_t)fl.prime_stride;      // dense sets, one range each: T slabs for xq and out, S for xp and the scratch
+    if (!down_buffers_ok(addr(d_xq), T * slab, addr(d_xp), S * slab, addr(d_out), addr(d_scratch))) return AGX_ERR_BAD_ARGUMENT;
+    if (!basis->moddown_legal) return AGX_ERR_BAD_MODULUS;      // some target modulus is a source modulus: D has no inverse there
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    const basis_view bv = view_of(basis);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // scratch <- y_i = INTT_i(xp_i) D_i^-1 mod q_i in [0, q_i): the plan's inverse on the view of the source primes, its last-stage constants the basis'
+    route scaled = prime_range(plan->routes.inverse, basis->src_first, basis->src_first + S);
+    scaled.consts = basis->d_src_consts;
+    if (fused) {
+        // two launches: the accumulation, the forward transform and (xq_j - .) D^-1 stay on chip; a wave reads its words of xq_j before it writes them
+        AGX_HIP(run_inverse(scaled, d_xp, nullptr, d_scratch, fl, s));
+        AGX_HIP(r.rb->launch_moddown(r, bv, d_xq, d_scratch, d_out, fl, s));
+        return AGX_OK;
+    }
+    // generic route, no more scratch: out <- INTT(xq) on the target primes; scratch <- the y_i; out <- (out - sum_i y_i D_i) D^-1 in the coefficient
+    // domain; out <- NTT(out) in place
+    AGX_HIP(run_inverse(prime_range(plan->routes.inverse, basis->dst_first, basis->dst_first + T), d_xq, nullptr, d_out, fl, s));
+    AGX_HIP(run_inverse(scaled, d_xp, nullptr, d_scratch, fl, s));
+    AGX_HIP(launch_moddown_coeff(plan->routes.forward, bv, d_out, d_scratch, batch, s));
+    AGX_HIP(run_forward(prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T), d_out, d_out, fl, s));
+    return AGX_OK;
+}
+
+// agx_ntt_inner_product and agx_ntt_inner_product_galois: one statement of the rules, the Galois element's between the overlap rule and the device's
+static int inner_product_call(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
+                              uint32_t terms, uint32_t outputs, uint32_t galois_elt, void* stream) {
+    if (!plan || !d_a || !d_bhat || !d_c) return AGX_ERR_NULL_POINTER;
+    if (terms == 0 || terms > AGX_INNER_MAX_TERMS || outputs == 0 || outputs > AGX_INNER_MAX_OUTPUTS || (bhat_batch != batch && bhat_batch != 1)) return AGX_ERR_BAD_ARGUMENT;
+    if (!aligned8(d_a) || !aligned8(d_bhat) || !aligned8(d_c)) return AGX_ERR_BAD_ARGUMENT;
+    if (!batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;      // from here on batch n < 2^46
+    // every operand is one dense range (terms outputs P <= 32 65535 slabs)
+    const uint32_t P = plan->num_primes, n = plan->n;
+    if (!dense_fits(n, terms * P, batch) || !dense_fits(n, terms * outputs * P, bhat_batch) || !dense_fits(n, outputs * P, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t slab = batch * n, a_words = terms * P * slab, b_words = (uint64_t)terms * outputs * P * bhat_batch * n, c_words = outputs * P * slab;      // each <= 2^60
+    // out of place only, equal pointers included: c_o of a word is written once, but by a thread that other threads' reads of a and bhat do not wait for
+    if (ranges_touch(addr(d_c), c_words, addr(d_a), a_words) || ranges_touch(addr(d_c), c_words, addr(d_bhat), b_words)) return AGX_ERR_BAD_ARGUMENT;
+    if (!galois_ok(galois_elt, n)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (batch == 0) return AGX_OK;
+    AGX_HIP(launch_inner_product_galois(plan->routes.forward, inner_primes{P, P, 0}, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, galois_elt, static_cast<hipStream_t>(stream)));
+    return AGX_OK;
+}
+
+int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
+                          uint32_t terms, uint32_t outputs, void* stream) {
+    return inner_product_call(plan, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, 1, stream);      // g = 1 (n >= 2: legal on every plan): the un-gathered kernel
+}
+
+int agx_ntt_inner_product_galois(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
+                                 uint32_t terms, uint32_t outputs, uint32_t galois_elt, void* stream) {
+    return inner_product_call(plan, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, galois_elt, stream);
+}
+
+int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha) {
+    if (!ks) return AGX_ERR_NULL_POINTER;
+    *ks = nullptr;
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    const keyswitch_shape shape{q_count, p_first, p_count, alpha};
+    if (!keyswitch_shape_ok(shape, plan->num_primes)) return AGX_ERR_BAD_ARGUMENT;
+    // two equal moduli among the active primes: some D_i or D_P has no inverse where ModUp or ModDown needs one
+    const uint32_t A = shape.active();
+    auto modulus = [&](uint32_t slot) { return plan->moduli[slot < q_count ? slot : p_first + (slot - q_count)]; };
+    for (uint32_t i = 0; i < A; ++i)
+        for (uint32_t j = i + 1; j < A; ++j)
+            if (modulus(i) == modulus(j)) return AGX_ERR_BAD_MODULUS;
+    if (int rc = check_plan(plan)) return rc;
+    return guarded([&]() -> int {
+        std::unique_ptr<agx_ntt_keyswitch> k(new (std::nothrow) agx_ntt_keyswitch);
+        if (!k) return AGX_ERR_ALLOC;
+        k->plan = plan, k->shape = shape;
+        k->up.reserve(2 * shape.digits());
+        auto add = [&](uint32_t sf, uint32_t sc, uint32_t df, uint32_t dc) {
+            agx_ntt_basis* b = nullptr;
+            const int rc = agx_ntt_basis_create(&b, plan, sf, sc, df, dc);
+            if (rc == AGX_OK) k->up.push_back(b);      // capacity reserved: the handle owns b from here
+            return rc;
+        };
+        for (uint32_t d = 0; d < shape.digits(); ++d) {
+            uint32_t first, count;
+            keyswitch_digit(shape, d, &first, &count);
+            if (!shape.apart()) {
+                if (int rc = add(first, count, 0, A)) return rc;
+            } else {
+                if (int rc = add(first, count, 0, q_count)) return rc;
+                if (int rc = add(first, count, p_first, p_count)) return rc;
+            }
+        }
+        if (int rc = agx_ntt_basis_create(&k->down, plan, p_first, p_count, 0, q_count)) return rc;
+        *ks = k.release();
+        return AGX_OK;
+    });
+}
+
+int agx_ntt_keyswitch_destroy(agx_ntt_keyswitch* ks) {
+    delete ks;      // the bases go with it
+    return AGX_OK;
+}
+
+// kernel launches of the two halves of an apply call, each under the plan's current variant: the inverse on Q + what every ModUp basis reports; the
+// inner product + two ModDown calls
+static int decompose_launches(const agx_ntt_keyswitch* ks) {
+    int extend[2 * kKeyswitchMaxDigits];
+    for (size_t i = 0; i < ks->up.size(); ++i) (void)agx_ntt_basis_info(ks->up[i], nullptr, nullptr, nullptr, nullptr, &extend[i]);
+    return keyswitch_launches_decompose(inverse_launches(ks->plan), extend, (uint32_t)ks->up.size());
+}
+static int apply_decomposed_launches(const agx_ntt_keyswitch* ks) {
+    int down = 0;
+    (void)agx_ntt_basis_mod_down_info(ks->down, &down);
+    return keyswitch_launches_apply_decomposed(down);
+}
+
+int agx_ntt_keyswitch_info(const agx_ntt_keyswitch* ks, uint32_t* q_count, uint32_t* p_first, uint32_t* p_count, uint32_t* alpha, uint32_t* digits, int* launches) {
+    if (!ks) return AGX_ERR_NULL_POINTER;
+    if (q_count) *q_count = ks->shape.q_count;
+    if (p_first) *p_first = ks->shape.p_first;
+    if (p_count) *p_count = ks->shape.p_count;
+    if (alpha) *alpha = ks->shape.alpha;
+    if (digits) *digits = ks->shape.digits();
+    if (launches) *launches = decompose_launches(ks) + apply_decomposed_launches(ks);      // what agx_ntt_keyswitch_hoisted_info reports, summed
+    return AGX_OK;
+}
+
+int agx_ntt_keyswitch_scratch_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* words) {
+    if (!ks || !words) return AGX_ERR_NULL_POINTER;
+    keyswitch_scratch part;
+    if (!keyswitch_scratch_partition(ks->shape, ks->plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;
+    *words = part.total;
+    return AGX_OK;
+}
+
+int agx_ntt_keyswitch_hoisted_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* ext_words, uint64_t* decompose_scratch_words, uint64_t* apply_scratch_words) {
+    if (!ks) return AGX_ERR_NULL_POINTER;
+    keyswitch_hoisted part;
+    if (!keyswitch_hoisted_partition(ks->shape, ks->plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;
+    if (ext_words) *ext_words = part.ext;
+    if (decompose_scratch_words) *decompose_scratch_words = part.decompose_scratch;
+    if (apply_scratch_words) *apply_scratch_words = part.apply_scratch;
+    return AGX_OK;
+}
+
+int agx_ntt_keyswitch_hoisted_info(const agx_ntt_keyswitch* ks, int* launches_decompose, int* launches_apply_decomposed) {
+    if (!ks) return AGX_ERR_NULL_POINTER;
+    if (launches_decompose) *launches_decompose = decompose_launches(ks);
+    if (launches_apply_decomposed) *launches_apply_decomposed = apply_decomposed_launches(ks);
+    return AGX_OK;
+}
+
+// Steps 1 and 2 of a key switch, every argument checked by the caller: coeff [Q][batch][n] <- INTT(chat), ext [digits][A][batch][n] <- ModUp of every digit
+static int keyswitch_decompose_steps(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, uint64_t* ext, uint64_t* coeff, uint64_t batch, void* stream) {
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    const uint32_t Q = k.q_count, A = k.active(), digits = k.digits();
+    const uint64_t slab = batch * plan->n;
+    // (1) coeff_j <- INTT_j(chat_j) in [0, q_j): the plan's inverse on the view of primes [0, Q), as ModDown runs it on its sources: no second plan
+    AGX_HIP(run_inverse(prime_range(plan->routes.inverse, 0, Q), d_chat, nullptr, coeff, dense(plan, batch), static_cast<hipStream_t>(stream)));
+    // (2) ext_d <- NTT_j(e_{d,j}) for every active j: agx_ntt_basis_extend of digit d's slabs of coeff, routes as that call chooses them.  A digit's
+    // own slabs are transformed again (they come out as chat_j reduced); copying them instead was not measured, so it is not done.
+    for (uint32_t d = 0, b = 0; d < digits; ++d) {
+        const uint64_t* x = coeff + (uint64_t)d * k.alpha * slab;
+        uint64_t* e = ext + (uint64_t)d * A * slab;
+        if (int rc = agx_ntt_basis_extend(ks->up[b++], x, e, batch, AGX_FORM_NTT, stream)) return rc;
+        if (k.apart())
+            if (int rc = agx_ntt_basis_extend(ks->up[b++], x, e + Q * slab, batch, AGX_FORM_NTT, stream)) return rc;
+    }
+    return AGX_OK;
+}
+
+// Steps 3 and 4, every argument checked by the caller: acc [2][A][batch][n] <- sum_d pi_g(ext_d) o key_{d,o}, out [2][Q][batch][n] <- ModDown of each half
+static int keyswitch_apply_steps(const agx_ntt_keyswitch* ks, const uint64_t* ext, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* acc, uint64_t batch,
+                                 uint32_t galois_elt, void* stream) {
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    const uint32_t Q = k.q_count, A = k.active();
+    const uint64_t slab = batch * plan->n;
+    // (3) acc_o <- sum_d pi_g(ext_d) o key_{d,o} over the active primes: one launch, the key broadcast over the batch; g = 1 is the un-gathered kernel
+    AGX_HIP(launch_inner_product_galois(plan->routes.forward, inner_primes{A, Q, k.p_first - Q}, ext, d_keyhat, acc, batch, 1, k.digits(), 2, galois_elt,
+                                        static_cast<hipStream_t>(stream)));
+    // (4) out_o <- ModDown of acc_o, its special slabs given up as the scratch
+    for (uint32_t o = 0; o < 2; ++o) {
+        uint64_t* xq = acc + (uint64_t)o * A * slab;
+        if (int rc = agx_ntt_basis_mod_down(ks->down, xq, xq + Q * slab, d_out + o * Q * slab, xq + Q * slab, batch, stream)) return rc;
+    }
+    return AGX_OK;
+}
+
+// the rules the key-switch calls share, after the NULL rule and the 2^60 limits: alignment, the two grid limits, and no two of the call's `count` buffers touching
+static bool keyswitch_buffers_ok(const agx_ntt_keyswitch* ks, uint64_t batch, const uintptr_t* base, const uint64_t* words, int count) {
+    for (int i = 0; i < count; ++i)
+        if (base[i] & 7u) return false;
+    // batch past the grid limit; A workgroups per group of frames on the one-launch ModUp and the two-launch ModDown (at least one frame per workgroup)
+    if (!batch_fits_grid(ks->plan, batch) || (uint64_t)ks->shape.active() * batch > 0x7fffffffull) return false;
+    for (int i = 0; i < count; ++i)
+        for (int j = i + 1; j < count; ++j)
+            if (ranges_touch(base[i], words[i], base[j], words[j])) return false;
+    return true;
+}
+
+int agx_ntt_keyswitch_decompose(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, uint64_t* d_ext, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!ks || !d_chat || !d_ext || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = ks->plan;
+    keyswitch_hoisted part;
+    if (!keyswitch_hoisted_partition(ks->shape, plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;      // every extent below is one of its three
+    const uintptr_t base[3] = {addr(d_chat), addr(d_ext), addr(d_scratch)};
+    const uint64_t words[3] = {part.decompose_scratch, part.ext, part.decompose_scratch};
+    if (!keyswitch_buffers_ok(ks, batch, base, words, 3)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    return keyswitch_decompose_steps(ks, d_chat, d_ext, d_scratch, batch, stream);
+}
+
+int agx_ntt_keyswitch_apply_decomposed(const agx_ntt_keyswitch* ks, const uint64_t* d_ext, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch,
+                                       uint64_t batch, uint32_t galois_elt, void* stream) {
+    if (!ks || !d_ext || !d_keyhat || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    keyswitch_hoisted part;
+    if (!keyswitch_hoisted_partition(k, plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;
+    const uintptr_t base[4] = {addr(d_ext), addr(d_keyhat), addr(d_out), addr(d_scratch)};
+    const uint64_t words[4] = {part.ext, (uint64_t)k.digits() * 2 * k.active() * plan->n, 2 * part.decompose_scratch, part.apply_scratch};
+    if (!keyswitch_buffers_ok(ks, batch, base, words, 4)) return AGX_ERR_BAD_ARGUMENT;
+    if (!galois_ok(galois_elt, plan->n)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;      // ModDown runs the plan's inverse
+    if (batch == 0) return AGX_OK;
+    return keyswitch_apply_steps(ks, d_ext, d_keyhat, d_out, d_scratch, batch, galois_elt, stream);
+}
+
+int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!ks || !d_chat || !d_keyhat || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    keyswitch_scratch part;
+    if (!keyswitch_scratch_partition(k, plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;      // every extent below is a part of the scratch's or smaller
+    const uint64_t chat_words = k.q_count * batch * plan->n;      // [Q][batch][n], the size of the coeff part
+    const uintptr_t base[4] = {addr(d_chat), addr(d_keyhat), addr(d_out), addr(d_scratch)};
+    const uint64_t words[4] = {chat_words, (uint64_t)k.digits() * 2 * k.active() * plan->n, 2 * chat_words, part.total};
+    if (!keyswitch_buffers_ok(ks, batch, base, words, 4)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    // the two halves on the three parts of the one scratch, with g = 1: the un-gathered inner product
+    if (int rc = keyswitch_decompose_steps(ks, d_chat, d_scratch + part.ext, d_scratch + part.coeff, batch, stream)) return rc;
+    return keyswitch_apply_steps(ks, d_scratch + part.ext, d_keyhat, d_out, d_scratch + part.acc, batch, 1, stream);
+}
+
+}  // extern "C"

@@ -630,41 +630,41 @@ static inner_args inner_args_of(const plan_view& pv, const inner_primes& ip, uin
     return g;
 }
 
+// the two kernel families of the inner products, by {outputs, word or pair}
+struct inner_plain { template <int OUT, class W> static auto kernel() { return &inner_product_kernel<OUT, W>; } };
+struct inner_galois { template <int OUT, class W> static auto kernel() { return &inner_product_galois_kernel<OUT, W>; } };
+
+// one launch of a family's instance for {outputs 1 or 2} x {word or pair}; g: the family's argument block, per_prime its inner_args' work per slot
+template <class Family, class Args>
+static hipError_t launch_inner(const plan_view& pv, uint32_t slots, uint64_t per_prime, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint32_t outputs,
+                               bool pairs, const Args& g, hipStream_t s) {
+    const dim3 grid(grid_1d(per_prime, 256), slots);
+    auto go = [&](auto kernel, auto* ap, auto* bp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, cp, pv.consts, g); };
+    if (pairs) {
+        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2*>(a), *b2 = reinterpret_cast<const ulonglong2*>(bhat);
+        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(c);
+        if (outputs == 1) go(Family::template kernel<1, ulonglong2>(), a2, b2, c2);
+        else go(Family::template kernel<2, ulonglong2>(), a2, b2, c2);
+    } else {
+        if (outputs == 1) go(Family::template kernel<1, uint64_t>(), a, bhat, c);
+        else go(Family::template kernel<2, uint64_t>(), a, bhat, c);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_inner_product_galois(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
                                        uint64_t bhat_batch, uint32_t terms, uint32_t outputs, uint32_t galois_elt, hipStream_t s) {
     if (galois_elt == 1) return launch_inner_product(pv, ip, a, bhat, c, batch, bhat_batch, terms, outputs, s);      // pi is the identity: the plain kernel
     const bool pairs = inner_pairs(a, bhat, c);
     const inner_galois_args g{inner_args_of(pv, ip, batch, bhat_batch, terms, outputs, pairs), pv.log_n, galois_elt};
-    const dim3 grid(grid_1d(g.in.per_prime, 256), ip.count);
-    auto go = [&](auto kernel, auto* ap, auto* bp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, cp, pv.consts, g); };
-    if (pairs) {
-        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2*>(a), *b2 = reinterpret_cast<const ulonglong2*>(bhat);
-        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(c);
-        if (outputs == 1) go(inner_product_galois_kernel<1, ulonglong2>, a2, b2, c2);
-        else go(inner_product_galois_kernel<2, ulonglong2>, a2, b2, c2);
-    } else {
-        if (outputs == 1) go(inner_product_galois_kernel<1, uint64_t>, a, bhat, c);
-        else go(inner_product_galois_kernel<2, uint64_t>, a, bhat, c);
-    }
-    return hipGetLastError();
+    return launch_inner<inner_galois>(pv, ip.count, g.in.per_prime, a, bhat, c, outputs, pairs, g, s);
 }
 
 hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
                                 uint64_t bhat_batch, uint32_t terms, uint32_t outputs, hipStream_t s) {
     const bool pairs = inner_pairs(a, bhat, c);
     const inner_args g = inner_args_of(pv, ip, batch, bhat_batch, terms, outputs, pairs);
-    const dim3 grid(grid_1d(g.per_prime, 256), ip.count);
-    auto go = [&](auto kernel, auto* ap, auto* bp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, cp, pv.consts, g); };
-    if (pairs) {
-        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2*>(a), *b2 = reinterpret_cast<const ulonglong2*>(bhat);
-        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(c);
-        if (outputs == 1) go(inner_product_kernel<1, ulonglong2>, a2, b2, c2);
-        else go(inner_product_kernel<2, ulonglong2>, a2, b2, c2);
-    } else {
-        if (outputs == 1) go(inner_product_kernel<1, uint64_t>, a, bhat, c);
-        else go(inner_product_kernel<2, uint64_t>, a, bhat, c);
-    }
-    return hipGetLastError();
+    return launch_inner<inner_plain>(pv, ip.count, g.per_prime, a, bhat, c, outputs, pairs, g, s);
 }
 
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s) {
@@ -695,34 +695,33 @@ hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, ui
     return hipGetLastError();
 }
 
+// the SMAX a kernel templated on its source capacity is instantiated with for S sources (at most AGX_BASIS_MAX_SRC = 16), as a compile-time constant
+template <class F>
+static void with_smax(uint32_t S, F&& f) {
+    if (S <= 1) f(std::integral_constant<int, 1>{});
+    else if (S <= 2) f(std::integral_constant<int, 2>{});
+    else if (S <= 4) f(std::integral_constant<int, 4>{});
+    else if (S <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
+
 hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const uint64_t* x, uint64_t* out, uint64_t batch, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
     const dim3 grid(grid_1d(per_prime, 256));
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, x, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, bv.dinv, bv.mat, bv.src_count,
-                           bv.dst_count, per_prime);
-    };
-    const uint32_t S = bv.src_count;      // at most AGX_BASIS_MAX_SRC = 16
-    if (S <= 1) go(basis_coeff_kernel<1>);
-    else if (S <= 2) go(basis_coeff_kernel<2>);
-    else if (S <= 4) go(basis_coeff_kernel<4>);
-    else if (S <= 8) go(basis_coeff_kernel<8>);
-    else go(basis_coeff_kernel<16>);
+    with_smax(bv.src_count, [&](auto smax) {
+        hipLaunchKernelGGL(basis_coeff_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, x, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, bv.dinv,
+                           bv.mat, bv.src_count, bv.dst_count, per_prime);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
     const dim3 grid(grid_1d(per_prime, 256));
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, out, y, pv.consts + bv.dst_first, bv.mat, bv.dall, bv.src_count, bv.dst_count, per_prime);
-    };
-    const uint32_t S = bv.src_count;      // at most AGX_BASIS_MAX_SRC = 16
-    if (S <= 1) go(moddown_coeff_kernel<1>);
-    else if (S <= 2) go(moddown_coeff_kernel<2>);
-    else if (S <= 4) go(moddown_coeff_kernel<4>);
-    else if (S <= 8) go(moddown_coeff_kernel<8>);
-    else go(moddown_coeff_kernel<16>);
+    with_smax(bv.src_count, [&](auto smax) {
+        hipLaunchKernelGGL(moddown_coeff_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, out, y, pv.consts + bv.dst_first, bv.mat, bv.dall, bv.src_count,
+                           bv.dst_count, per_prime);
+    });
     return hipGetLastError();
 }
 

@@ -79,4 +79,16 @@ inline bool ranges_touch(uintptr_t a, uint64_t a_words, uintptr_t b, uint64_t b_
     return a <= b ? (b - a) / 8 < a_words : (a - b) / 8 < b_words;
 }
 
+// The buffer rule of the calls that bring xq (qwords words) down by xp (pwords words) through a scratch of pwords words into out (qwords words):
+// agx_ntt_basis_mod_down, and agx_ntt_rescale with xq = slabs 0 .. P-2 of x and xp = its last slab.  Dense sets, one range each.
+//   out IS xq (in place) or touches nothing of it;
+//   out never touches xp or the scratch, the scratch never xq: several workgroups per frame read the scratch while others already write out, and
+//   the first launch reads xp;
+//   the scratch IS xp (the caller gives those slabs up) or does not touch it.
+inline bool down_buffers_ok(uintptr_t xq, uint64_t qwords, uintptr_t xp, uint64_t pwords, uintptr_t out, uintptr_t scratch) {
+    if (out != xq && ranges_touch(out, qwords, xq, qwords)) return false;
+    if (ranges_touch(out, qwords, xp, pwords) || ranges_touch(out, qwords, scratch, pwords) || ranges_touch(scratch, pwords, xq, qwords)) return false;
+    return scratch == xp || !ranges_touch(scratch, pwords, xp, pwords);
+}
+
 }  // namespace agx

@@ -1,5 +1,5 @@
-// plan_internal.hpp -- what agx_ntt.cpp (plans, single-device calls) and agx_group.cpp (multi-device groups) share.
-// Not installed; the public surface is include/agx_ntt.h.
+// plan_internal.hpp -- what agx_ntt.cpp (plans, transform and product calls), agx_rns.cpp (the RNS calls composed of them) and agx_group.cpp
+// (multi-device groups) share.  Host only: no device unit includes it.  Not installed; the public surface is include/agx_ntt.h.
 #pragma once
 #include "../../include/agx_ntt.h"
 
@@ -13,7 +13,8 @@
 #include <vector>
 
 #include "keyswitch_layout.hpp"
-#include "ntt_kernels.hpp"
+#include "operands.hpp"
+#include "rb_registry.hpp"
 
 constexpr int kMaxDevices = 64;          // size of every per-device table (kernel attributes set once, staging pool, one-shot plans); devices past it work uncached
 constexpr uint32_t kTicketSlots = 64;    // distinct streams of one plan that may run ticket-drawing kernels; further streams get the stateless kernels
@@ -80,6 +81,7 @@ struct agx_ntt_plan {
     int arith_level = 0;     // 0 exact only; 1: every modulus <= 2^61 (8q-lazy legal); 2: <= 2^60 (16q-lazy legal); 3: every modulus 2^60 - c, 0 < c < 2^28
     int narrow_level = 0;    // 1: every modulus < 2^31, 2: < 2^30 -- the 32-bit kernels are legal (with arith_level >= 1: tables honour the contract)
     std::vector<uint64_t> moduli, psi;  // psi = 0 when the tables came from the caller
+    std::vector<agx::prime_consts> consts;      // [P]: what d_consts holds (64 bytes per prime; the tables below stay device-only)
     agx::device_buf<agx::prime_consts> d_consts;
     agx::device_buf<agx::rescale_consts> d_rescale;      // [P-1]; null for one prime
     bool rescale_legal = false;      // P >= 2 and q_{P-1} invertible modulo every other modulus (distinct primes are); judged at the call
@@ -204,6 +206,54 @@ int check_plan(const agx_ntt_plan* plan);               // the plan exists and t
 int check_create_args(uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre);
 int build_plan(agx_ntt_plan** out, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
                const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre);
+
+// ---- what the entry points of agx_ntt.cpp and agx_rns.cpp share: each launch step and each frame rule once ----
+
+// The plan's forward / inverse on the frames a route views: the route's registry entry, or the radix-2 kernels.  in2 != null (the product in * in2
+// is transformed) only with an entry.
+inline hipError_t run_forward(const route& r, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
+    return r.rb ? r.rb->launch(r, in, out, fl, s) : launch_forward_radix2(r, in, out, fl, s);
+}
+inline hipError_t run_inverse(const route& r, const uint64_t* in, const uint64_t* in2, uint64_t* out, const frame_layout& fl, hipStream_t s) {
+    return r.rb ? r.rb->launch_inv(r, in, in2, out, fl, s) : launch_inverse_radix2(r, in, out, fl, s);
+}
+
+inline const route& forward_route(const agx_ntt_plan* p, uint64_t batch) {
+    const plan_routes& r = p->routes;
+    return r.forward_large.rb && batch * p->num_primes >= r.min_frames ? r.forward_large : r.forward;
+}
+
+// kernel launches of one forward / inverse call of the plan: a registry entry is one launch whatever the batch (forward and forward_large alike: the
+// second exists only beside a first with an entry), the radix-2 kernels say themselves how many they take
+inline int forward_launches(const agx_ntt_plan* p) { return forward_route(p, 1).rb ? 1 : forward_radix2_launches(p->log_n); }
+inline int inverse_launches(const agx_ntt_plan* p) { return p->routes.inverse.rb ? 1 : inverse_radix2_launches(p->log_n); }
+
+inline uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }      // what operands.hpp takes
+inline bool aligned8(const void* p) { return (addr(p) & 7u) == 0; }      // uint64_t data
+inline bool galois_ok(uint32_t g, uint32_t n) { return (g & 1u) && g < 2u * n; }      // a Galois element: odd, in [1, 2n)
+inline bool batch_fits_grid(const agx_ntt_plan* plan, uint64_t batch) { return batch <= (0x7fffffffull >> (plan->log_n > 14 ? plan->log_n - 14 : 0)); }      // grid.x limit (the radix-2 kernels split n = 32768 in two blocks)
+
+// The dense [prime][batch][n] layout of a plan, for the checks and the launches alike.  Nothing is multiplied for a batch past the grid
+// limit, which check_frames refuses before it looks at a stride: batch * n stays below 2^46.
+inline frame_layout dense(const agx_ntt_plan* plan, uint64_t batch) { return frame_layout{batch, batch_fits_grid(plan, batch) ? (int64_t)(batch * plan->n) : 0, (int64_t)plan->n}; }
+inline uint64_t dense_words(const agx_ntt_plan* plan, uint64_t batch) { return plan->num_primes * batch * plan->n; }      // of a bounded batch: < 2^62
+
+// Frame-set rule: the plan's frames in layout fl at `base`.  Batch first, then layout_fits: nothing after them can overflow (operands.hpp).
+inline int check_frames(const agx_ntt_plan* plan, const void* base, const frame_layout& fl) {
+    if (!base) return AGX_ERR_NULL_POINTER;
+    if (!aligned8(base) || !batch_fits_grid(plan, fl.batch)) return AGX_ERR_BAD_ARGUMENT;
+    if (fl.batch > 1 && fl.poly_stride < (int64_t)plan->n) return AGX_ERR_BAD_ARGUMENT;   // frames would overlap
+    if (!layout_fits(plan->n, plan->num_primes, fl.batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;   // a negative stride, or an extent past 2^60 words
+    if (self_overlap(plan->n, plan->num_primes, fl.batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;   // (p, b) and (p', b') share words
+    return AGX_OK;
+}
+
+// Pair rule: a second set in the layout of the checked set at `base` is that set itself (in place) or touches none of its frames.
+inline int check_pair(const agx_ntt_plan* plan, const void* base, const void* other, const frame_layout& fl) {
+    if (!other) return AGX_ERR_NULL_POINTER;
+    if (!aligned8(other)) return AGX_ERR_BAD_ARGUMENT;
+    return partial_overlap(addr(base), addr(other), plan->n, plan->num_primes, fl.batch, fl.prime_stride, fl.poly_stride) ? AGX_ERR_BAD_ARGUMENT : AGX_OK;
+}
 
 // staging resources of the host-pointer pipeline (agx_host.cpp): three slots of {pinned in, pinned out, device} on three streams
 constexpr size_t kStageChunkBytes = (size_t)32 << 20;

@@ -112,9 +112,51 @@ static void ranges() {
     CHECK(ranges_touch(0, (uint64_t)1 << 61, last, 1));      // the whole address space holds its last word
 }
 
+// The buffer rules of agx_ntt_basis_mod_down and agx_ntt_rescale as those calls spelled them out before down_buffers_ok stated the rule once: the
+// references below.  true = the call goes on, false = AGX_ERR_BAD_ARGUMENT.
+static bool mod_down_rule_as_written(uintptr_t xq, uintptr_t xp, uintptr_t out, uintptr_t scratch, uint64_t qwords, uint64_t pwords) {
+    if (out != xq && ranges_touch(out, qwords, xq, qwords)) return false;
+    if (ranges_touch(out, qwords, xp, pwords) || ranges_touch(out, qwords, scratch, pwords) || ranges_touch(scratch, pwords, xq, qwords)) return false;
+    if (scratch != xp && ranges_touch(scratch, pwords, xp, pwords)) return false;
+    return true;
+}
+static bool rescale_rule_as_written(uintptr_t x, uintptr_t out, uintptr_t scratch, uint64_t slab, uint64_t head) {
+    const uintptr_t x_last = x + 8 * head;
+    if (out != x && ranges_touch(out, head, x, head + slab)) return false;
+    if (ranges_touch(scratch, slab, out, head) || ranges_touch(scratch, slab, x, head)) return false;
+    if (scratch != x_last && ranges_touch(scratch, slab, x_last, slab)) return false;
+    return true;
+}
+
+// down_buffers_ok against both, every placement: slabs of 0 .. 3 words, 1 .. 3 source and target slabs, every base on a grid of 14 words (ranges are
+// at most 9 words: equal bases, adjacency and every partial overlap occur).  Rescale is the rule at xq = x, xp = x + 8 qwords, one source slab.
+static uint64_t down_buffers_grid() {
+    const uintptr_t base = (uintptr_t)1 << 40;
+    const int grid = 14;
+    uint64_t cases = 0;
+    auto at = [&](int w) { return base + 8 * (uintptr_t)w; };
+    for (uint64_t slab = 0; slab <= 3; ++slab)
+        for (uint32_t T = 1; T <= 3; ++T) {
+            for (uint32_t S = 1; S <= 3; ++S)
+                for (int xq = 0; xq < grid; ++xq)
+                    for (int xp = 0; xp < grid; ++xp)
+                        for (int out = 0; out < grid; ++out)
+                            for (int scratch = 0; scratch < grid; ++scratch, ++cases)
+                                CHECK(down_buffers_ok(at(xq), T * slab, at(xp), S * slab, at(out), at(scratch)) ==
+                                      mod_down_rule_as_written(at(xq), at(xp), at(out), at(scratch), T * slab, S * slab));
+            const uint64_t head = T * slab;      // a plan of P = T + 1 primes
+            for (int x = 0; x < grid; ++x)
+                for (int out = 0; out < grid; ++out)
+                    for (int scratch = 0; scratch < grid; ++scratch, ++cases)
+                        CHECK(down_buffers_ok(at(x), head, at(x) + 8 * head, slab, at(out), at(scratch)) == rescale_rule_as_written(at(x), at(out), at(scratch), slab, head));
+        }
+    return cases;
+}
+
 int main() {
     const uint64_t cases = brute_force_grid();
     std::printf("brute force: %" PRIu64 " cases\n", cases);
+    std::printf("down_buffers_ok: %" PRIu64 " placements\n", down_buffers_grid());
     layout_fits_limits();
     largest_shapes();
     ranges();

@@ -24,4 +24,8 @@ def test_operand_predicates_against_brute_force_and_at_the_limits(tmp_path):
     # n in {2, 8}, 1..3 primes, 1..4 polynomials, strides 0..5nB+3 and 0..5nP+3: 113,184 layouts asked of self_overlap, and the
     # 29,357,526 offsets (-extent-2 .. extent+2) of the 80,080 that do not overlap themselves asked of partial_overlap
     assert m and int(m.group(1)) == 29470710
+    # down_buffers_ok against the rules agx_ntt_basis_mod_down and agx_ntt_rescale used to spell out: slabs of 0..3 words, 1..3 target slabs, four
+    # bases (1..3 source slabs) resp. rescale's three on a grid of 14 words: 4 * 3 * (3 * 14**4 + 14**3) placements
+    m = re.search(r"down_buffers_ok: (\d+) placements", run.stdout)
+    assert m and int(m.group(1)) == 4 * 3 * (3 * 14**4 + 14**3) == 1415904
     assert "ok: 0 failures" in run.stdout
