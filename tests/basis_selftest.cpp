@@ -1,5 +1,5 @@
 // basis_selftest.cpp -- agx::basis_constants (csrc/host_math.cpp), the host side of agx_ntt_basis_extend, against brute force in unsigned __int128.
-// Stand-alone: built from this file and host_math.cpp by tests/test_basis_host_math.py with -fsanitize=address,undefined; no HIP, no plan.
+// Stand-alone: built from this file, tests/selftest.hpp and host_math.cpp by tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
 //   * every constant against its definition, the products taken in another order than the builder takes them: D_i^-1 D_i = 1 (mod q_i),
 //     mat[j][i] = D_i mod q_j, every quotient = floor(w 2^64 / q);
 //   * where S D fits 128 bits, the conversion itself: for X in [0, D) with residues x_i, V = sum_i y_i D_i as an exact integer is X + u D with
@@ -11,30 +11,7 @@
 #include <vector>
 
 #include "../agilex-ntt_amd/csrc/host_math.hpp"
-
-typedef unsigned __int128 u128;
-
-static long g_checks = 0, g_failures = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        ++g_checks;                                       \
-        if (!(cond)) {                                    \
-            if (++g_failures <= 20) {                     \
-                std::printf("FAIL %s:%d: ", __FILE__, __LINE__); \
-                std::printf(__VA_ARGS__);                 \
-                std::printf("\n");                        \
-            }                                             \
-        }                                                 \
-    } while (0)
-
-static uint64_t g_rng = 0x243F6A8885A308D3ull;
-static uint64_t next64() {      // splitmix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static u128 next128() { return ((u128)next64() << 64) | next64(); }
+#include "selftest.hpp"
 
 // D_i mod m, from the last factor to the first (the builder goes first to last)
 static uint64_t d_mod_brute(const std::vector<uint64_t>& src, size_t i, uint64_t m) {
@@ -159,7 +136,5 @@ int main() {
     check_conversion("mixed widths, [30, 61] -> all", {mixed[1], mixed[2]}, mixed, 500);
     check_conversion("mixed widths, [62, 17, 30] -> all", {mixed[4], mixed[5], mixed[3]}, mixed, 500);
     check_conversion("mixed widths, [17] -> all", {mixed[5]}, mixed, 500);
-    std::printf("basis_constants: %ld checks\n", g_checks);
-    std::printf("%s: %ld failures\n", g_failures ? "FAILED" : "ok", g_failures);
-    return g_failures ? 1 : 0;
+    return selftest_report("basis_constants");
 }

@@ -1,6 +1,6 @@
 // fold_selftest.cpp -- agx::fold_twiddle_pack (csrc/host_math.cpp) and the arithmetic of the two-twiddle butterfly for q = 2^60 - c, 0 < c < 2^28
 // (csrc/modarith.hpp: ct_butterfly_q60c_fold), against brute force in unsigned __int128.
-// Stand-alone: built from this file and host_math.cpp by tests/test_fold_host_math.py with -fsanitize=address,undefined; no HIP, no plan.
+// Stand-alone: built from this file, tests/selftest.hpp and host_math.cpp by tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
 //   * the packing: wC = w 2^32 mod q, low halves below 2^29, high halves below 2^31, w and wC recombine exactly from the packed words;
 //     w in {0, 1, q-1, 2^29-1, 2^29} and random, for the four benchmark primes (the largest 60-bit primes = 1 mod 8192) and both boundary primes of
 //     tests/golden/q60c_boundary.json;
@@ -12,29 +12,7 @@
 #include <vector>
 
 #include "../agilex-ntt_amd/csrc/host_math.hpp"
-
-typedef unsigned __int128 u128;
-
-static long g_checks = 0, g_failures = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        ++g_checks;                                       \
-        if (!(cond)) {                                    \
-            if (++g_failures <= 20) {                     \
-                std::printf("FAIL %s:%d: ", __FILE__, __LINE__); \
-                std::printf(__VA_ARGS__);                 \
-                std::printf("\n");                        \
-            }                                             \
-        }                                                 \
-    } while (0)
-
-static uint64_t g_rng = 0x243F6A8885A308D3ull;
-static uint64_t next64() {      // splitmix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+#include "selftest.hpp"
 
 static const u128 kTwo64 = (u128)1 << 64;
 static const uint64_t kTop = 1ull << 60, kLow29 = (1ull << 29) - 1;
@@ -128,7 +106,5 @@ int main() {
     check_class_bounds((1ull << 28) - 1);
     check_class_bounds(1);
     check_class_bounds(16383);
-    std::printf("fold_twiddle_pack / two-twiddle butterfly: %ld checks\n", g_checks);
-    std::printf("%s: %ld failures\n", g_failures ? "FAILED" : "ok", g_failures);
-    return g_failures ? 1 : 0;
+    return selftest_report("fold_twiddle_pack / two-twiddle butterfly");
 }

@@ -1,6 +1,7 @@
 """Shared support of the tests, written once: device memory (torch is only the allocator here), moduli / oracle tables / plans, the
 oracle over dense frame sets, status_of, the one stream-capture helper, the group-of-two scaffolding, guarded arenas, whole-buffer
-checkers, and the kernel registry as the tests know it.  No test module imports another test module; they import from here."""
+checkers, and the kernel registry as the tests know it.  No test module imports another test module; they import from here, and the tests of the
+RNS calls from rns_ref.py (the Python-integer reference) and rns_cases.py (cases two files share) besides."""
 import functools
 
 import numpy as np
@@ -410,6 +411,13 @@ def thin_frames(frames, keep, limit=16):
     rest = [f for f in frames if f not in set(keep)]
     room = min(max(0, limit - len(kept)), len(rest))
     return sorted(kept + [rest[(k * len(rest)) // room] for k in range(room)])
+
+
+def judged_frames(batch, limit, extra=()):
+    """the frames of a large batch to judge with Python integers: the three at either end always, and a thin sample of the boundary frames and of
+    `extra`, at most `limit` in all"""
+    edges = [0, 1, 2, batch - 3, batch - 2, batch - 1]
+    return thin_frames(boundary_frames(batch) + list(extra) + edges, edges, limit=limit)
 
 
 def spread_lazy_(torch, x, moduli, seed):

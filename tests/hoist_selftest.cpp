@@ -1,5 +1,5 @@
 // hoist_selftest.cpp -- the host-compilable parts of agx_ntt_keyswitch_decompose / _apply_decomposed and agx_ntt_inner_product_galois, by brute force.
-// Stand-alone: built from this file and csrc/keyswitch_layout.hpp alone by tests/test_hoist_host_math.py with -fsanitize=address,undefined; no HIP.
+// Stand-alone: built from this file, tests/selftest.hpp and csrc/keyswitch_layout.hpp alone by tests/test_selftests.py with -fsanitize=address,undefined; no HIP.
 //   (a) csrc/keyswitch_layout.hpp: the three buffers of the two halves are the ext, coeff and acc parts of keyswitch_scratch_partition; counts past
 //       2^60 words are reported and not wrapped; the launch counts of the two halves sum to keyswitch_launches.
 //   (b) a host restatement of pi_g(i) = brev((g brev(i) + (g - 1) / 2) mod n), in the kernels' own 32-bit operations: it is a bijection,
@@ -12,19 +12,7 @@
 #include <vector>
 
 #include "../agilex-ntt_amd/csrc/keyswitch_layout.hpp"
-
-static long g_checks = 0, g_failures = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        ++g_checks;                                       \
-        if (!(cond)) {                                    \
-            if (++g_failures <= 20) {                     \
-                std::printf("FAIL %s:%d: ", __FILE__, __LINE__); \
-                std::printf(__VA_ARGS__);                 \
-                std::printf("\n");                        \
-            }                                             \
-        }                                                 \
-    } while (0)
+#include "selftest.hpp"
 
 static void test_layout() {
     using agx::keyswitch_shape;
@@ -125,11 +113,10 @@ static void test_pair_property_every_g() {
     }
 }
 
-static uint64_t mul_mod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)((unsigned __int128)a * b % q); }
 static uint64_t pow_mod(uint64_t a, uint64_t e, uint64_t q) {
     uint64_t r = 1;
-    for (; e; e >>= 1, a = mul_mod(a, a, q))
-        if (e & 1) r = mul_mod(r, a, q);
+    for (; e; e >>= 1, a = mulmod(a, a, q))
+        if (e & 1) r = mulmod(r, a, q);
     return r;
 }
 
@@ -143,7 +130,7 @@ static void test_pi_is_the_automorphism() {
         for (uint32_t k = 0; k < n; ++k) a[k] = (k * 2654435761u + 12345u) % q;
         auto at = [&](const std::vector<uint64_t>& poly, uint64_t x) {
             uint64_t r = 0;
-            for (uint32_t k = n; k-- > 0;) r = (mul_mod(r, x, q) + poly[k]) % q;
+            for (uint32_t k = n; k-- > 0;) r = (mulmod(r, x, q) + poly[k]) % q;
             return r;
         };
         auto ntt = [&](const std::vector<uint64_t>& poly) {
@@ -168,12 +155,9 @@ static void test_pi_is_the_automorphism() {
 
 int main() {
     test_layout();
-    std::printf("hoisted_layout: %ld checks\n", g_checks);
-    const long before = g_checks;
+    selftest_section("hoisted_layout");
     test_pi_structure();
     test_pair_property_every_g();
     test_pi_is_the_automorphism();
-    std::printf("galois_pi: %ld checks\n", g_checks - before);
-    std::printf("%s: %ld failures\n", g_failures ? "FAILED" : "ok", g_failures);
-    return g_failures ? 1 : 0;
+    return selftest_report("galois_pi");
 }

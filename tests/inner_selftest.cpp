@@ -1,5 +1,5 @@
 // inner_selftest.cpp -- the host-compilable parts of agx_ntt_inner_product and agx_ntt_keyswitch_* against brute force in unsigned __int128.
-// Stand-alone: built from this file and the two headers alone by tests/test_inner_host_math.py with -fsanitize=address,undefined; no HIP, no plan.
+// Stand-alone: built from this file, tests/selftest.hpp and the two headers alone by tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
 //   (a) csrc/inner_reduce.hpp, the very text the kernel compiles: acc_mul_add / acc_reduce against (sum of products) % q for 1, 2, 15 and 16 terms,
 //       all operands q - 1 and random ones; acc_reduce on random and extreme 128-bit values; moduli of the 2-, 17-, 30-, 31-, 60-, 61- and 62-bit
 //       classes (2^62 - 57 and its neighbours included).  The largest multiple of q left before the conditional subtracts is reported (must be <= 3).
@@ -11,29 +11,7 @@
 
 #include "../agilex-ntt_amd/csrc/inner_reduce.hpp"
 #include "../agilex-ntt_amd/csrc/keyswitch_layout.hpp"
-
-typedef unsigned __int128 u128;
-
-static long g_checks = 0, g_failures = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        ++g_checks;                                       \
-        if (!(cond)) {                                    \
-            if (++g_failures <= 20) {                     \
-                std::printf("FAIL %s:%d: ", __FILE__, __LINE__); \
-                std::printf(__VA_ARGS__);                 \
-                std::printf("\n");                        \
-            }                                             \
-        }                                                 \
-    } while (0)
-
-static uint64_t g_rng = 0x243F6A8885A308D3ull;
-static uint64_t next64() {      // splitmix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+#include "selftest.hpp"
 
 static uint64_t g_worst_multiple = 0;
 
@@ -157,10 +135,7 @@ static void test_layout() {
 
 int main() {
     test_reduce();
-    std::printf("inner_reduce: %ld checks\n", g_checks);
-    const long before = g_checks;
+    selftest_section("inner_reduce");
     test_layout();
-    std::printf("keyswitch_layout: %ld checks\n", g_checks - before);
-    std::printf("%s: %ld failures\n", g_failures ? "FAILED" : "ok", g_failures);
-    return g_failures ? 1 : 0;
+    return selftest_report("keyswitch_layout");
 }

@@ -1,5 +1,5 @@
 // moddown_selftest.cpp -- agx::moddown_constants (csrc/host_math.cpp), the host side of agx_ntt_basis_mod_down, against brute force in unsigned __int128.
-// Stand-alone: built from this file and host_math.cpp by tests/test_mod_down_host_math.py with -fsanitize=address,undefined; no HIP, no plan.
+// Stand-alone: built from this file, tests/selftest.hpp and host_math.cpp by tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
 //   * dall[j] D = 1 (mod q_j) with D taken factor by factor in another order than the builder takes it, dall[j] < q_j, its quotient = floor(w 2^64 / q);
 //   * sn[i] = n^-1 D_i^-1 and sw[i] = w1n D_i^-1 (mod q_i), reduced, with their quotients; sn[i] n D_i = 1 (mod q_i) closes the loop on n^-1;
 //   * where S D fits 128 bits, ModDown itself in exact integers: X = D Y + V' (V' any CRT value of the sources) gives (a_j - V) D^-1 = Y - u (mod q_j)
@@ -11,32 +11,8 @@
 #include <vector>
 
 #include "../agilex-ntt_amd/csrc/host_math.hpp"
+#include "selftest.hpp"
 
-typedef unsigned __int128 u128;
-
-static long g_checks = 0, g_failures = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        ++g_checks;                                       \
-        if (!(cond)) {                                    \
-            if (++g_failures <= 20) {                     \
-                std::printf("FAIL %s:%d: ", __FILE__, __LINE__); \
-                std::printf(__VA_ARGS__);                 \
-                std::printf("\n");                        \
-            }                                             \
-        }                                                 \
-    } while (0)
-
-static uint64_t g_rng = 0x13198A2E03707344ull;
-static uint64_t next64() {      // splitmix64
-    uint64_t z = (g_rng += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-static u128 next128() { return ((u128)next64() << 64) | next64(); }
-
-static uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)((u128)a * b % q); }
 // D mod m (skip == S) or D_skip mod m, from the last factor to the first (the builder goes first to last)
 static uint64_t d_mod_brute(const std::vector<uint64_t>& src, size_t skip, uint64_t m) {
     u128 r = 1 % m;
@@ -147,6 +123,7 @@ static std::vector<uint64_t> primes(uint32_t bits, uint32_t n, uint32_t count) {
 static std::vector<uint64_t> slice(const std::vector<uint64_t>& v, size_t lo, size_t hi) { return std::vector<uint64_t>(v.begin() + lo, v.begin() + hi); }
 
 int main() {
+    g_rng = 0x13198A2E03707344ull;
     const struct {
         uint32_t bits, n;
     } classes[] = {{17, 8}, {30, 64}, {60, 4096}, {62, 1024}};
@@ -175,7 +152,5 @@ int main() {
     check_mod_down("mixed widths, [30, 61] -> the rest", {mixed[1], mixed[2]}, {mixed[0], mixed[3], mixed[4], mixed[5]}, 8, 500);
     check_mod_down("mixed widths, [17] -> the rest", {mixed[5]}, slice(mixed, 0, 5), 8, 500);
     check_mod_down("mixed widths, [62, 30] -> the rest", {mixed[4], mixed[3]}, {mixed[0], mixed[1], mixed[2], mixed[5]}, 8, 500);
-    std::printf("moddown_constants: %ld checks\n", g_checks);
-    std::printf("%s: %ld failures\n", g_failures ? "FAILED" : "ok", g_failures);
-    return g_failures ? 1 : 0;
+    return selftest_report("moddown_constants");
 }

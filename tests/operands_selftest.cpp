@@ -5,14 +5,9 @@
 #include <vector>
 
 #include "../agilex-ntt_amd/csrc/operands.hpp"
+#include "selftest.hpp"
 
 using namespace agx;
-
-static long g_failures = 0;
-#define CHECK(cond)                                                             \
-    do {                                                                        \
-        if (!(cond) && ++g_failures <= 20) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
-    } while (0)
 
 // Brute force over frame starts (tests/test_gpu_bench_shapes.py::_touch_expected): a layout overlaps itself iff two distinct frames start
 // less than n words apart; the set shifted by off != 0 touches the set iff some frame of one starts less than n words from a frame of
@@ -160,6 +155,5 @@ int main() {
     layout_fits_limits();
     largest_shapes();
     ranges();
-    std::printf("%s: %ld failures\n", g_failures ? "FAILED" : "ok", g_failures);
-    return g_failures ? 1 : 0;
+    return selftest_report("operand predicates");
 }

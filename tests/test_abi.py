@@ -1,6 +1,8 @@
 """CPU tests of the drop-in boundary: the C-ABI library loads, exports every symbol that
 include/agx_ntt.h declares, validates arguments, and its host math agrees with the oracle.
-No compute call can succeed here (no GPU): the product path must fail loudly, not fall back."""
+No compute call can succeed here (no GPU): the product path must fail loudly, not fall back.
+Every operation added to the boundary is a row of one of two tables: OPERATIONS (plan and group
+forms) and RNS_OPERATIONS (bases, inner products, the key switch and its two halves)."""
 import ctypes
 import os
 import re
@@ -100,6 +102,180 @@ def test_operation_fails_loudly_without_a_plan_or_a_group(agx, op):
     L = agx.lib()
     for name, args, status in OPERATIONS[op]["null_calls"]:
         assert getattr(L, name)(*args) == status, (name, args)
+
+
+# ---- the RNS calls: handles of their own (agx_ntt_basis, agx_ntt_keyswitch) or a plan, no group form --------------------------------------------
+# Arguments of a NULL-handle call that are more than a value: BUF(k) is the address k bytes into one zeroed buffer, which must still be zero after
+# every call of the operation; U32, U64 and INT are out-parameters holding 7, which must keep it; HANDLE(v) is a handle out-parameter holding v,
+# which must read NULL afterwards (cleared, or never set).
+def BUF(offset=0):
+    return ("buf", offset)
+
+
+def HANDLE(initial):
+    return ("handle", initial)
+
+
+U32, U64, INT = ("out", ctypes.c_uint32), ("out", ctypes.c_uint64), ("out", ctypes.c_int)
+
+# per operation: "names" {symbol: argument count}, every one AGX_API int; "typedefs" the opaque handle types the header declares; "methods" {class of the
+# binding: its callables}; "limits" {AGX_<name> of the header = <name> of the binding: value}; "null_calls" [(symbol, arguments, status)] without a
+# handle or a plan -- status 1 before a device or any memory is touched, whatever the other arguments say, and 0 for destroying nothing
+RNS_OPERATIONS = {
+    "basis_extend": {
+        "names": {"agx_ntt_basis_create": 6, "agx_ntt_basis_destroy": 1, "agx_ntt_basis_info": 6, "agx_ntt_basis_extend": 6},
+        "typedefs": ("agx_ntt_basis",),
+        "methods": {"Basis": ("extend", "info", "close"), "Plan": ("basis",)},
+        "limits": {"BASIS_MAX_SRC": 16},
+        "null_calls": [("agx_ntt_basis_create", (None, None, 0, 1, 0, 1), 1),
+                       ("agx_ntt_basis_create", (HANDLE(None), None, 0, 1, 0, 1), 1),      # no plan
+                       ("agx_ntt_basis_create", (HANDLE(None), None, 0, 0, 0, 0), 1),      # ... whatever the ranges
+                       ("agx_ntt_basis_info", (None, U32, U32, U32, U32, INT), 1), ("agx_ntt_basis_info", (None, None, None, None, None, None), 1),
+                       ("agx_ntt_basis_destroy", (None,), 0), ("agx_ntt_basis_destroy", (None,), 0)]
+                      + [call for form in (0, 1, 7) for call in (("agx_ntt_basis_extend", (None, BUF(), BUF(), 1, form, None), 1),
+                                                                 ("agx_ntt_basis_extend", (None, None, None, 0, form, None), 1))],
+    },
+    "basis_mod_down": {
+        "names": {"agx_ntt_basis_mod_down": 7, "agx_ntt_basis_mod_down_info": 2},
+        "typedefs": (),
+        "methods": {"Basis": ("mod_down", "mod_down_launches")},
+        "limits": {},
+        "null_calls": [("agx_ntt_basis_mod_down_info", (None, INT), 1), ("agx_ntt_basis_mod_down_info", (None, None), 1),
+                       ("agx_ntt_basis_mod_down", (None, BUF(), BUF(64), BUF(128), BUF(192), 1, None), 1),
+                       ("agx_ntt_basis_mod_down", (None, BUF(), BUF(), BUF(), BUF(), 1, None), 1),
+                       ("agx_ntt_basis_mod_down", (None, None, None, None, None, 0, None), 1)],
+    },
+    "inner_product": {
+        "names": {"agx_ntt_inner_product": 9},
+        "typedefs": (),
+        "methods": {"Plan": ("inner_product",)},
+        "limits": {"INNER_MAX_TERMS": 16, "INNER_MAX_OUTPUTS": 2},
+        "null_calls": [("agx_ntt_inner_product", (None, BUF(), BUF(128), BUF(256), 1, 1, 1, 1, None), 1),
+                       ("agx_ntt_inner_product", (None, BUF(), BUF(), BUF(), 1, 1, 2, 2, None), 1),
+                       ("agx_ntt_inner_product", (None, BUF(), BUF(128), BUF(256), 1, 1, 0, 3, None), 1),      # the NULL rule comes first
+                       ("agx_ntt_inner_product", (None, None, None, None, 0, 0, 0, 0, None), 1)],
+    },
+    "keyswitch": {
+        "names": {"agx_ntt_keyswitch_create": 6, "agx_ntt_keyswitch_destroy": 1, "agx_ntt_keyswitch_info": 7, "agx_ntt_keyswitch_scratch_words": 3,
+                  "agx_ntt_keyswitch_apply": 7},
+        "typedefs": ("agx_ntt_keyswitch",),
+        "methods": {"Plan": ("keyswitch",), "KeySwitch": ("info", "scratch_words", "apply", "close")},
+        "limits": {"KEYSWITCH_MAX_DIGITS": 16},
+        "null_calls": [("agx_ntt_keyswitch_create", (None, None, 4, 4, 2, 2), 1),
+                       ("agx_ntt_keyswitch_create", (HANDLE(0x1234), None, 4, 4, 2, 2), 1),      # the out-pointer is cleared, nothing else
+                       ("agx_ntt_keyswitch_destroy", (None,), 0),
+                       ("agx_ntt_keyswitch_info", (None, U32, U32, U32, U32, U32, INT), 1),
+                       ("agx_ntt_keyswitch_info", (None, None, None, None, None, None, None), 1),
+                       ("agx_ntt_keyswitch_scratch_words", (None, 5, U64), 1), ("agx_ntt_keyswitch_scratch_words", (None, 5, None), 1),
+                       ("agx_ntt_keyswitch_apply", (None, BUF(), BUF(128), BUF(256), BUF(384), 1, None), 1),
+                       ("agx_ntt_keyswitch_apply", (None, BUF(), BUF(), BUF(), BUF(), 1, None), 1),
+                       ("agx_ntt_keyswitch_apply", (None, None, None, None, None, 0, None), 1)],
+    },
+    "hoisted_rotations": {
+        "names": {"agx_ntt_inner_product_galois": 10, "agx_ntt_keyswitch_hoisted_words": 5, "agx_ntt_keyswitch_decompose": 6,
+                  "agx_ntt_keyswitch_apply_decomposed": 8, "agx_ntt_keyswitch_hoisted_info": 3},
+        "typedefs": (),
+        "methods": {"Plan": ("inner_product_galois",), "KeySwitch": ("hoisted_words", "decompose", "apply_decomposed", "hoisted_info")},
+        "limits": {},
+        "null_calls": [("agx_ntt_inner_product_galois", (None, BUF(), BUF(128), BUF(256), 1, 1, 1, 1, 5, None), 1),
+                       ("agx_ntt_inner_product_galois", (None, BUF(), BUF(), BUF(), 1, 1, 2, 2, 5, None), 1),
+                       # the NULL rule comes first: before the counts and the even element
+                       ("agx_ntt_inner_product_galois", (None, BUF(), BUF(128), BUF(256), 1, 1, 0, 3, 4, None), 1),
+                       ("agx_ntt_inner_product_galois", (None, None, None, None, 0, 0, 0, 0, 0, None), 1),
+                       ("agx_ntt_keyswitch_hoisted_words", (None, 5, U64, U64, U64), 1), ("agx_ntt_keyswitch_hoisted_words", (None, 5, None, None, None), 1),
+                       ("agx_ntt_keyswitch_hoisted_info", (None, INT, INT), 1), ("agx_ntt_keyswitch_hoisted_info", (None, None, None), 1),
+                       ("agx_ntt_keyswitch_decompose", (None, BUF(), BUF(128), BUF(256), 1, None), 1),
+                       ("agx_ntt_keyswitch_decompose", (None, BUF(), BUF(), BUF(), 1, None), 1),
+                       ("agx_ntt_keyswitch_decompose", (None, None, None, None, 0, None), 1),
+                       ("agx_ntt_keyswitch_apply_decomposed", (None, BUF(), BUF(128), BUF(256), BUF(384), 1, 5, None), 1),
+                       ("agx_ntt_keyswitch_apply_decomposed", (None, BUF(), BUF(), BUF(), BUF(), 1, 4, None), 1),      # before the overlap rule and the even element
+                       ("agx_ntt_keyswitch_apply_decomposed", (None, None, None, None, None, 0, 0, None), 1)],
+    },
+}
+
+
+@pytest.mark.parametrize("op", RNS_OPERATIONS)
+def test_rns_symbols_are_declared_exported_and_bound(agx, op):
+    text = _header()
+    raw = ctypes.CDLL(agx.LIB_PATH)
+    for name in RNS_OPERATIONS[op]["names"]:
+        assert re.search(r"AGX_API\s+int\s+" + name + r"\s*\(", text), name
+        assert hasattr(raw, name), name
+        assert name in agx.ABI and agx.ABI[name][0] is ctypes.c_int, name
+    for handle in RNS_OPERATIONS[op]["typedefs"]:
+        assert re.search(r"typedef\s+struct\s+" + handle + r"\s+" + handle + r"\s*;", text), handle
+
+
+@pytest.mark.parametrize("op", RNS_OPERATIONS)
+def test_rns_argument_counts_match_the_header(agx, op):
+    text = _header()
+    for name, count in RNS_OPERATIONS[op]["names"].items():
+        args = re.search(r"\b" + name + r"\s*\(([^)]*)\)\s*;", text).group(1)
+        assert len(args.split(",")) == count == len(agx.ABI[name][1]), name
+
+
+@pytest.mark.parametrize("op", RNS_OPERATIONS)
+def test_python_layer_has_the_rns_methods(agx, op):
+    for cls, methods in RNS_OPERATIONS[op]["methods"].items():
+        assert isinstance(getattr(agx, cls), type), cls
+        for method in methods:
+            assert callable(getattr(getattr(agx, cls), method)), (cls, method)
+
+
+@pytest.mark.parametrize("op", [op for op in RNS_OPERATIONS if RNS_OPERATIONS[op]["limits"]])
+def test_rns_limits_are_defined_once_and_mirrored(agx, op):
+    """AGX_BASIS_MAX_SRC, AGX_INNER_MAX_TERMS / _OUTPUTS, AGX_KEYSWITCH_MAX_DIGITS: one #define each, the same value under the binding's name"""
+    for name, value in RNS_OPERATIONS[op]["limits"].items():
+        assert re.findall(r"#define\s+AGX_" + name + r"\s+(\d+)\b", _header()) == [str(value)], name
+        assert getattr(agx, name) == value, name
+
+
+def test_no_new_form_or_rescale_constants(agx):
+    """agx_ntt_basis_extend's out_form reuses AGX_FORM_COEFF / AGX_FORM_NTT"""
+    assert sorted(re.findall(r"#define\s+(AGX_FORM_\w+|AGX_RESCALE_\w+)", _header())) == ["AGX_FORM_COEFF", "AGX_FORM_NTT", "AGX_RESCALE_FLOOR", "AGX_RESCALE_ROUND"]
+
+
+@pytest.mark.parametrize("op", RNS_OPERATIONS)
+def test_rns_call_without_a_handle_says_so_and_touches_nothing(agx, op):
+    L = agx.lib()
+    buf = (ctypes.c_uint64 * 64)()
+    for name, args, status in RNS_OPERATIONS[op]["null_calls"]:
+        outs, handles, passed = [], [], []
+        for a in args:
+            if not isinstance(a, tuple):
+                passed.append(a)
+            elif a[0] == "buf":
+                assert a[1] + 8 <= ctypes.sizeof(buf)
+                passed.append(ctypes.addressof(buf) + a[1])
+            else:
+                box = ctypes.c_void_p(a[1]) if a[0] == "handle" else a[1](7)
+                (handles if a[0] == "handle" else outs).append(box)
+                passed.append(ctypes.byref(box))
+        assert getattr(L, name)(*passed) == status, (name, args)
+        assert all(v.value == 7 for v in outs), (name, args, "an out-parameter was written")
+        assert all(h.value is None for h in handles), (name, args, "a handle was handed out")
+    assert all(w == 0 for w in buf), "a buffer was written"
+
+
+# prototypes later features promised to leave alone, character for character (whitespace runs of the header count as one blank)
+FROZEN_PROTOTYPES = [
+    "int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count);",
+    "int agx_ntt_basis_destroy(agx_ntt_basis* basis);",
+    "int agx_ntt_basis_info(const agx_ntt_basis* basis, uint32_t* src_first, uint32_t* src_count, uint32_t* dst_first, uint32_t* dst_count, int* launches_ntt_form);",
+    "int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream);",
+    "int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream);",
+    "int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launches);",
+    "int agx_ntt_pointwise(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, void* stream);",
+    "int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch, uint32_t terms, uint32_t outputs, void* stream);",
+    "int agx_ntt_keyswitch_scratch_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* words);",
+    "int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream);",
+    "int agx_ntt_automorphism(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t galois_elt, int form, void* stream);",
+]
+
+
+@pytest.mark.parametrize("proto", FROZEN_PROTOTYPES, ids=[p.split("(")[0].split()[-1] for p in FROZEN_PROTOTYPES])
+def test_frozen_prototype_is_unchanged(proto):
+    assert proto in re.sub(r"\s+", " ", _header()), proto
 
 
 def test_a_plan_cannot_be_made_without_a_device(agx):

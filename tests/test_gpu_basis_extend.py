@@ -1,15 +1,15 @@
 """agx_ntt_basis_extend on the device: fast RNS base conversion from the source primes of a basis to its target primes, in coefficient
 form and fused with the targets' forward transform.
 
-The expected words come from Python integers, from the definition: y_i = (x_i mod q_i) (D_i^-1 mod q_i) mod q_i, V = sum_i y_i D_i as an
-integer, out_j = V mod q_j; the NTT-form expectation is the CPU oracle's forward of those words.  Every comparison is word for word."""
+The expected words come from Python integers, from the definition (rns_ref.convert): y_i = (x_i mod q_i) (D_i^-1 mod q_i) mod q_i, V = sum_i y_i D_i
+as an integer, out_j = V mod q_j; the NTT-form expectation is the CPU oracle's forward of those words.  Every comparison is word for word."""
 import functools
 
 import numpy as np
 import pytest
 
-from gpu_util import (RESCALE_IDS, Layout, arena_for, boundary_frames, canary, capture, moduli_for, oracle_tables, plan_for_moduli,
-                      registry_entries, status_of, thin_frames)
+from gpu_util import RESCALE_IDS, Layout, arena_for, canary, capture, judged_frames, moduli_for, plan_for_moduli, registry_entries, status_of
+from rns_ref import convert, device_residues, oracle_forward_set, product, residues, special_values, spread
 
 pytestmark = pytest.mark.gpu
 
@@ -22,46 +22,12 @@ SHAPES = (MODUP, MODDOWN, SINGLE)
 EXTEND_IDS = RESCALE_IDS
 
 
-# ---- the reference: Python integers -----------------------------------------------------------------------------------------------
-def _product(moduli):
-    D = 1
-    for q in moduli:
-        D *= int(q)
-    return D
-
-
-def convert(x, src, dst):
-    """x: [S][count] uint64, any values (reduced mod q_i first) -> [T][count] uint64, from the definition"""
-    x = np.asarray(x, dtype=np.uint64).reshape(len(src), -1)
-    D = _product(src)
-    V = np.zeros(x.shape[1], dtype=object)
-    for i, q in enumerate(src):
-        Di = D // int(q)
-        y = (x[i] % np.uint64(q)).astype(object) * pow(Di, -1, int(q)) % int(q)
-        V = V + y * Di
-    assert all(0 <= v < len(src) * D for v in (V.min(), V.max()))
-    return np.stack([(V % int(q)).astype(np.uint64) for q in dst])
-
-
-def _special_values(src):
-    """X per coefficient whose V = X + u D lies on a multiple of D or next to one (X = 0, 1, D - 1), X = D - 1 (every residue q_i - 1),
-    their neighbours, and the X whose y_i are all q_i - 1 (the largest V) or a single 1 (V = D_k)"""
-    D = _product(src)
-    out = [0, 1, 2, D - 1, D - 2, D // 2, D // 2 + 1]
-    out.append(sum((int(q) - 1) * (D // int(q)) for q in src) % D)
-    out += [D // int(q) % D for q in src]
-    return out
-
-
-def _residues(X, src):
-    return np.array([[x % int(q) for x in X] for q in src], dtype=np.uint64)
-
-
+# ---- the cases ---------------------------------------------------------------------------------------------------------------------------------
 def make_inputs(rng, src, batch, n):
     """[S][batch][n] reduced residues.  Frame 0 opens with the special values and is random behind them; with five frames, frame 1 is all
     zero, frame 2 holds q_i - 1 everywhere (X = D - 1), frame 3 repeats the special values to its end, frame 4 is random"""
     x = np.stack([rng.integers(0, int(q), size=batch * n, dtype=np.uint64) for q in src]).reshape(len(src), batch, n)
-    special = _residues(_special_values(src), src)
+    special = residues(special_values(src), src)
     k = min(n, special.shape[1])
     x[:, 0, :k] = special[:, :k]
     if batch >= 5:
@@ -69,12 +35,6 @@ def make_inputs(rng, src, batch, n):
         x[:, 2, :] = np.array([int(q) - 1 for q in src], dtype=np.uint64)[:, None]
         x[:, 3, :] = np.tile(special, (1, n // special.shape[1] + 1))[:, :n]
     return x.reshape(len(src), -1)
-
-
-def spread(rng, x, src):
-    """the same residues spread over [0, 4 q_i)"""
-    x = np.asarray(x, dtype=np.uint64).reshape(len(src), -1)
-    return np.stack([x[i] + np.uint64(q) * rng.integers(0, 4, size=x.shape[1], dtype=np.uint64) for i, q in enumerate(src)])
 
 
 @functools.lru_cache(maxsize=None)
@@ -86,15 +46,10 @@ def _case(orc, n, moduli, shape, batch, seed):
     x = make_inputs(rng, src, batch, n)
     lazy = spread(rng, x, src)
     coeff = convert(x, src, dst)
-    want = {COEFF: coeff.reshape(-1), NTT: np.concatenate([orc.forward(np.ascontiguousarray(coeff[j]), *_fwd_args(orc, n, q)) for j, q in enumerate(dst)])}
+    want = {COEFF: coeff.reshape(-1), NTT: oracle_forward_set(orc, n, dst, coeff).reshape(-1)}
     for a in (x, lazy, *want.values()):
         a.setflags(write=False)
     return x.reshape(-1), lazy.reshape(-1), want
-
-
-def _fwd_args(orc, n, q):
-    q, _, tw, pre = oracle_tables(orc, n, q)
-    return q, tw, pre, n
 
 
 def _extend(dev, basis, x, out_words, batch, form):
@@ -162,12 +117,12 @@ def test_sixteen_sources_of_62_bits(agx, orc, dev):
     assert basis.info()[:4] == (0, 16, 0, 17)
     rng = np.random.default_rng(62)
     top = np.tile(np.array([q - 1 for q in src], dtype=np.uint64)[:, None], (1, n))
-    D = _product(src)
+    D = product(src)
     largest = np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in src])
     largest[:, :n // 2] = np.array([(q - 1) * (D // q) % q for q in src], dtype=np.uint64)[:, None]
     for name, x in (("every residue q_i - 1", top), ("every y_i = q_i - 1", largest)):
         coeff = convert(x, src, moduli)
-        want = {COEFF: coeff.reshape(-1), NTT: np.concatenate([orc.forward(np.ascontiguousarray(coeff[j]), *_fwd_args(orc, n, q)) for j, q in enumerate(moduli)])}
+        want = {COEFF: coeff.reshape(-1), NTT: oracle_forward_set(orc, n, moduli, coeff).reshape(-1)}
         for form in FORMS:
             for words in (x, spread(rng, x, src)):
                 assert np.array_equal(_extend(dev, basis, words.reshape(-1), 17 * batch * n, batch, form), want[form]), (name, "form", form)
@@ -357,29 +312,18 @@ def test_odd_placement_and_guard_bands(agx, orc, dev, n, bits, batch):
 
 
 # ---- size ---------------------------------------------------------------------------------------------------------------------------
-def _device_residues(torch, dev, moduli, batch, n, seed, bound=None):
-    """[len(moduli)][batch][n] on the device, slab i uniform below moduli[i] (or below `bound`)"""
-    g = torch.Generator(device=dev.device)
-    g.manual_seed(seed)
-    d = dev.empty(len(moduli) * batch * n)
-    v = d.view(len(moduli), -1)
-    for i, q in enumerate(moduli):
-        v[i] = torch.randint(0, int(q if bound is None else bound), (batch * n,), generator=g, device=dev.device, dtype=torch.int64)
-    return d
-
-
 def _judge_frames(dev, basis, d_x, src, dst, batch, n, frames, orc):
     """both forms of one call each; the listed frames (of every target) against Python integers"""
     S, T = len(src), len(dst)
     xs = dev.to_host(d_x.view(S, batch, n)[:, frames].contiguous()).reshape(S, -1)
-    coeff = convert(xs, src, dst).reshape(T, len(frames), n)
+    coeff = convert(xs, src, dst)
+    want = {COEFF: coeff.reshape(T, len(frames), n), NTT: oracle_forward_set(orc, n, dst, coeff).reshape(T, len(frames), n)}
     for form in FORMS:
         d_out = dev.empty(T * batch * n)
         basis.extend(d_x.data_ptr(), d_out.data_ptr(), batch, form, dev.stream)
         got = dev.to_host(d_out.view(T, batch, n)[:, frames].contiguous()).reshape(T, len(frames), n)
-        for j, q in enumerate(dst):
-            want = coeff[j] if form == COEFF else orc.forward(np.ascontiguousarray(coeff[j].reshape(-1)), *_fwd_args(orc, n, q)).reshape(len(frames), n)
-            bad = [frames[f] for f in range(len(frames)) if not np.array_equal(got[j, f], want[f])]
+        for j in range(T):
+            bad = [frames[f] for f in range(len(frames)) if not np.array_equal(got[j, f], want[form][j, f])]
             assert not bad, ("form", form, "target", j, "frames", bad[:8])
         del d_out
 
@@ -396,7 +340,7 @@ def test_generic_kernel_past_one_grid_stride_trip(agx, orc, dev):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     # S = 1, prime 0 -> prime 1, inputs below both moduli: D = q_0, D_0 = 1, so the output is the input
     one = plan.basis(0, 1, 1, 1)
-    d_x = _device_residues(torch, dev, moduli[:1], batch, n, 1, bound=min(moduli[:2]))
+    d_x = device_residues(torch, dev, moduli[:1], batch, n, 1, bound=min(moduli[:2]))
     d_out = dev.empty(batch * n)
     d_out.fill_(-1)
     one.extend(d_x.data_ptr(), d_out.data_ptr(), batch, COEFF, dev.stream)
@@ -407,7 +351,7 @@ def test_generic_kernel_past_one_grid_stride_trip(agx, orc, dev):
     # S = 2 -> three targets
     S, T = 2, 3
     two = plan.basis(0, S, 0, T)
-    d_x = _device_residues(torch, dev, moduli[:S], batch, n, 2)
+    d_x = device_residues(torch, dev, moduli[:S], batch, n, 2)
     d_out = dev.empty(T * batch * n)
     d_out.fill_(-1)
     two.extend(d_x.data_ptr(), d_out.data_ptr(), batch, COEFF, dev.stream)
@@ -420,8 +364,7 @@ def test_generic_kernel_past_one_grid_stride_trip(agx, orc, dev):
         dev.sync()
         assert torch.equal(ov[:, f0:f0 + chunk], part_out.view(T, chunk, n)), ("the large call differs from the call on frames", f0, f0 + chunk)
     del d_out, part_out
-    edges = [0, 1, 2, batch - 3, batch - 2, batch - 1]
-    frames = thin_frames(boundary_frames(batch) + list(range(0, batch, 4999)) + edges, edges, limit=48)
+    frames = judged_frames(batch, 48, extra=range(0, batch, 4999))
     _judge_frames(dev, two, d_x, moduli[:S], moduli, batch, n, frames, orc)
     two.close()
     plan.close()
@@ -438,9 +381,8 @@ def test_ntt_form_at_1100_frames(agx, orc, dev, n, S):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     basis = plan.basis(0, S, 0, 3)
     assert basis.info()[4] == (1 if _fused_expected(n, 60, S) else 2)
-    d_x = _device_residues(torch, dev, moduli[:S], batch, n, 3)
-    edges = [0, 1, 2, batch - 3, batch - 2, batch - 1]
-    frames = thin_frames(boundary_frames(batch) + edges, edges, limit=14)
+    d_x = device_residues(torch, dev, moduli[:S], batch, n, 3)
+    frames = judged_frames(batch, 14)
     _judge_frames(dev, basis, d_x, moduli[:S], moduli, batch, n, frames, orc)
     basis.close()
     plan.close()

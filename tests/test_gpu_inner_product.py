@@ -1,57 +1,15 @@
 """agx_ntt_inner_product on the device: c_o = sum_t a_t o bhat_{t,o} mod q on NTT-form frames, one launch, the key broadcast over the batch or not.
 
-The expected words come from Python integers, from the definition: per word (sum_t (a_t mod q)(bhat_{t,o} mod q)) mod q.  Positions are not
-interpreted by the call, so any words below 4q are NTT-form frames.  Every comparison is word for word."""
-import functools
-
+The expected words come from Python integers, from the definition (rns_ref.inner_ref): per word (sum_t (a_t mod q)(bhat_{t,o} mod q)) mod q.  Positions
+are not interpreted by the call, so any words below 4q are NTT-form frames.  Every comparison is word for word."""
 import numpy as np
 import pytest
 
 from gpu_util import Layout, arena_for, boundary_frames, canary, capture, moduli_for, plan_for_moduli, status_of
+from rns_cases import TRIP, device_words, inner_layouts, inner_operands
+from rns_ref import inner_ref, spread
 
 pytestmark = pytest.mark.gpu
-
-# work items one grid-stride trip of the launcher covers: at most 2048 * 8 workgroups of 256 threads (grid_1d, csrc/ntt_kernels.hip), one item a
-# 16-byte pair of words when all three bases are 16-byte aligned and one word otherwise
-TRIP = 2048 * 8 * 256
-
-
-# ---- the reference: Python integers -----------------------------------------------------------------------------------------------
-def inner_ref(a, b, moduli):
-    """a [T][P][B][n], b [T][O][P][B or 1][n] (any 64-bit words) -> [O][P][B][n] uint64, from the definition"""
-    T, P = a.shape[:2]
-    O = b.shape[1]
-    out = np.empty((O,) + a.shape[1:], dtype=np.uint64)
-    for p, q in enumerate(moduli):
-        ap = (a[:, p] % np.uint64(q)).astype(object)
-        for o in range(O):
-            s = (ap * (b[:, o, p] % np.uint64(q)).astype(object)).sum(axis=0)      # Python integers: exact
-            out[o, p] = (s % int(q)).astype(np.uint64)
-    return out
-
-
-def spread(rng, x, moduli, axis):
-    """the same residues spread over [0, 4q); `axis` is the prime axis of x"""
-    shape = [1] * x.ndim
-    shape[axis] = len(moduli)
-    return x + np.array(moduli, dtype=np.uint64).reshape(shape) * rng.integers(0, 4, size=x.shape, dtype=np.uint64)
-
-
-@functools.lru_cache(maxsize=None)
-def _operands(n, moduli, batch, seed):
-    """(a [16][P][batch][n], b [16][2][P][batch][n]) reduced, and the same spread over [0, 4q): drawn once per shape, every case takes its leading
-    terms and outputs (read-only)"""
-    rng = np.random.default_rng(seed)
-    P = len(moduli)
-    a = np.stack([rng.integers(0, q, size=(16, batch, n), dtype=np.uint64) for q in moduli], axis=1)
-    b = np.stack([rng.integers(0, q, size=(16, 2, batch, n), dtype=np.uint64) for q in moduli], axis=2)
-    a[0, :, 0, :2] = 0      # a zero word and the largest one in every prime's first frame
-    a[0, :, 0, 2:4] = b[0, 0, :, 0, 2:4] = (np.array(moduli, dtype=np.uint64) - np.uint64(1))[:, None]
-    assert a.shape == (16, P, batch, n) and b.shape == (16, 2, P, batch, n)
-    out = (a, b, spread(rng, a, moduli, 1), spread(rng, b, moduli, 2))
-    for w in out:
-        w.setflags(write=False)
-    return out
 
 
 def _run(dev, plan, a, b, batch, terms, outputs, bhat_batch):
@@ -64,7 +22,7 @@ def _run(dev, plan, a, b, batch, terms, outputs, bhat_batch):
 
 def _check(dev, plan, moduli, n, batch, terms, outputs, broadcast, seed, what):
     """reduced inputs and inputs spread over [0, 4q) must both give the reference's words"""
-    a, b, la, lb = _operands(n, tuple(moduli), batch, seed)
+    a, b, la, lb = inner_operands(n, tuple(moduli), batch, seed)
     pick = lambda x: np.ascontiguousarray(x[:terms, :outputs, :, :1] if broadcast else x[:terms, :outputs])      # noqa: E731
     want = inner_ref(a[:terms], pick(b), moduli)
     for name, aw, bw in (("reduced", a, b), ("spread", la, lb)):
@@ -129,7 +87,7 @@ def test_one_term_one_output_is_pointwise(agx, orc, dev):
     n, batch = 4096, 5
     moduli = moduli_for(orc.find_prime, n, [60, 30, 61, 60])
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    _, _, la, lb = _operands(n, tuple(moduli), batch, 77)
+    _, _, la, lb = inner_operands(n, tuple(moduli), batch, 77)
     a, b = np.ascontiguousarray(la[:1]), np.ascontiguousarray(lb[:1, :1])
     got = _run(dev, plan, a, b, batch, 1, 1, batch)
     d_a, d_b, d_c = dev.to_device(a.reshape(-1)), dev.to_device(b.reshape(-1)), dev.empty(a.size)
@@ -150,22 +108,13 @@ def test_every_variant_and_a_forward_only_plan(agx, orc, dev, n):
         want = _check(dev, plan, moduli, n, batch, terms, outputs, True, n + 3, ("variant", variant))
     plan.close()
     fwd_only, _ = plan_for_moduli(agx, orc, n, moduli, inverse=False)
-    a, b, _, _ = _operands(n, tuple(moduli), batch, n + 3)
+    a, b, _, _ = inner_operands(n, tuple(moduli), batch, n + 3)
     got = _run(dev, fwd_only, np.ascontiguousarray(a[:terms]), np.ascontiguousarray(b[:terms, :outputs, :, :1]), batch, terms, outputs, 1)
     assert np.array_equal(got, want), "a forward-only plan"
     fwd_only.close()
 
 
 # ---- placement ------------------------------------------------------------------------------------------------------------------
-def _layouts(n, P, batch, terms, outputs, bb, offsets):
-    """a, bhat and c as frame sets of terms P, terms outputs P and outputs P `primes`, placed one behind the other at the given parities"""
-    la = Layout(n, terms * P, batch, offset=offsets[0])
-    lb = Layout(n, terms * outputs * P, bb, offset=la.span() + 6 + (la.span() + 6 + offsets[1]) % 2)
-    lc = Layout(n, outputs * P, batch, offset=lb.span() + 10 + (lb.span() + 10 + offsets[2]) % 2)
-    assert [l.offset % 2 for l in (la, lb, lc)] == [o % 2 for o in offsets]
-    return la, lb, lc
-
-
 @pytest.mark.parametrize("offsets", [(0, 0, 0), (1, 1, 1), (0, 0, 1), (0, 1, 0), (1, 0, 0)], ids=["16-byte", "odd", "c odd", "key odd", "a odd"])
 @pytest.mark.parametrize("n,batch", [(8, 5), (4096, 3)])
 def test_alignment_and_guard_bands(agx, orc, dev, n, batch, offsets):
@@ -175,12 +124,12 @@ def test_alignment_and_guard_bands(agx, orc, dev, n, batch, offsets):
     moduli = moduli_for(orc.find_prime, n, [60, 30, 61, 60])
     P = len(moduli)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    _, _, la_w, lb_w = _operands(n, tuple(moduli), batch, n + 11)
+    _, _, la_w, lb_w = inner_operands(n, tuple(moduli), batch, n + 11)
     for broadcast in (True, False):
         a = np.ascontiguousarray(la_w[:terms])
         b = np.ascontiguousarray(lb_w[:terms, :outputs, :, :1] if broadcast else lb_w[:terms, :outputs])
         want = inner_ref(a, b, moduli)
-        la, lb, lc = _layouts(n, P, batch, terms, outputs, 1 if broadcast else batch, offsets)
+        la, lb, lc = inner_layouts(n, P, batch, terms, outputs, 1 if broadcast else batch, offsets)
         arena = arena_for(dev, n, (la, a), (lb, b), (lc, None))
         assert arena.address(0) % 16 == 0
         plan.inner_product(arena.address(la.offset), arena.address(lb.offset), arena.address(lc.offset), batch, terms, outputs, 1 if broadcast else batch, dev.stream)
@@ -197,7 +146,7 @@ def test_rejected_calls_write_nothing(agx, orc, dev, n):
     moduli = moduli_for(orc.find_prime, n, [60] * 2)
     P = len(moduli)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    aw, bw, _, _ = _operands(n, tuple(moduli), batch, 5 * n)
+    aw, bw, _, _ = inner_operands(n, tuple(moduli), batch, 5 * n)
     a, b = np.ascontiguousarray(aw[:terms]), np.ascontiguousarray(bw[:terms, :outputs])
     la = Layout(n, terms * P, batch, offset=0)
     lb = Layout(n, terms * outputs * P, batch, offset=la.span() + 2 * n)
@@ -244,12 +193,6 @@ def test_rejected_calls_write_nothing(agx, orc, dev, n):
 
 
 # ---- a second grid-stride trip ------------------------------------------------------------------------------------------------------
-def _device_words(torch, dev, count, q, seed):
-    g = torch.Generator(device=dev.device)
-    g.manual_seed(seed)
-    return torch.randint(0, 4 * int(q), (count,), generator=g, device=dev.device, dtype=torch.int64)      # [0, 4q)
-
-
 def test_second_trip_30_bit_every_word(agx, orc, dev):
     """n = 4096, 16-byte accesses: 2048 pairs per frame, so 2,049 frames are the fewest whose per-prime work passes one trip.  Two terms, two outputs,
     one prime, broadcast key; with a 30-bit prime products stay below 2^60 and the sum of two below 2^61, so torch int64 judges every word"""
@@ -260,7 +203,7 @@ def test_second_trip_30_bit_every_word(agx, orc, dev):
     moduli = moduli_for(orc.find_prime, n, [30])
     q = int(moduli[0])
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    d_a, d_b = _device_words(torch, dev, terms * batch * n, q, 1), _device_words(torch, dev, terms * outputs * n, q, 2)
+    d_a, d_b = device_words(torch, dev, terms * batch * n, q, 1), device_words(torch, dev, terms * outputs * n, q, 2)
     d_c = dev.empty(outputs * batch * n)
     d_c.fill_(-1)
     assert all(t.data_ptr() % 16 == 0 for t in (d_a, d_b, d_c))
@@ -285,7 +228,7 @@ def test_second_trip_60_bit_boundary_frames(agx, orc, dev):
     moduli = moduli_for(orc.find_prime, n, [60])
     q = int(moduli[0])
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    d_a, d_b = _device_words(torch, dev, terms * batch * n + 1, q, 3), _device_words(torch, dev, terms * outputs * n + 1, q, 4)
+    d_a, d_b = device_words(torch, dev, terms * batch * n + 1, q, 3), device_words(torch, dev, terms * outputs * n + 1, q, 4)
     d_c = dev.empty(outputs * batch * n + 1)
     d_c.fill_(-1)
     plan.inner_product(d_a.data_ptr() + 8, d_b.data_ptr() + 8, d_c.data_ptr() + 8, batch, terms, outputs, 1, dev.stream)
@@ -310,7 +253,7 @@ def test_calls_are_graph_capturable(agx, orc, dev, n):
     batch, terms, outputs = 5, 3, 2
     moduli = moduli_for(orc.find_prime, n, [60] * 4)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    first, second = _operands(n, tuple(moduli), batch, n + 5), _operands(n, tuple(moduli), batch, n + 6)
+    first, second = inner_operands(n, tuple(moduli), batch, n + 5), inner_operands(n, tuple(moduli), batch, n + 6)
     pick = lambda ops: (np.ascontiguousarray(ops[2][:terms]), np.ascontiguousarray(ops[3][:terms, :outputs, :, :1]))      # noqa: E731
     a, b = pick(first)
     d_a, d_b, d_c = dev.to_device(a.reshape(-1)), dev.to_device(b.reshape(-1)), dev.empty(outputs * a[0].size)

@@ -1,6 +1,6 @@
 """agx_ntt_inner_product_galois on the device: c_o[i] = sum_t a_t[pi_g(i)] o bhat_{t,o}[i] mod q, one launch, no permuted copy of a.
 
-The expected words come from Python integers: inner_ref of tests/test_gpu_inner_product.py applied to a[..., ntt_pi(n, g)].  The call is also held
+The expected words come from Python integers: rns_ref.inner_ref applied to a[..., ntt_pi(n, g)].  The call is also held
 against the device pair it replaces -- agx_ntt_automorphism(AGX_FORM_NTT, g) on a, then agx_ntt_inner_product -- and, at g = 1, against
 agx_ntt_inner_product itself.  Every comparison is word for word."""
 import functools
@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 from gpu_util import Layout, arena_for, canary, capture, moduli_for, ntt_pi, plan_for_moduli, status_of
-from test_gpu_inner_product import TRIP, _device_words, _layouts, _operands, inner_ref, spread
+from rns_cases import TRIP, device_words, inner_layouts, inner_operands
+from rns_ref import inner_ref, spread
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +23,7 @@ def elements(n):
 @functools.lru_cache(maxsize=None)
 def _want(n, moduli, batch, seed, terms, broadcast, g):
     """inner_ref on a[..., pi_g] for two outputs, once per case (read-only); one output is its first half"""
-    a, b, _, _ = _operands(n, moduli, batch, seed)
+    a, b, _, _ = inner_operands(n, moduli, batch, seed)
     bb = np.ascontiguousarray(b[:terms, :, :, :1] if broadcast else b[:terms])
     want = inner_ref(np.ascontiguousarray(a[:terms][..., ntt_pi(n, g)]), bb, moduli)
     want.setflags(write=False)
@@ -41,7 +42,7 @@ def _run(dev, plan, a, b, batch, terms, outputs, bhat_batch, g):
 
 def _check(dev, plan, moduli, n, batch, terms, seed, what):
     """outputs 1 and 2, both key forms, every element, reduced inputs and inputs spread over [0, 4q): the reference's words"""
-    a, b, la, lb = _operands(n, tuple(moduli), batch, seed)
+    a, b, la, lb = inner_operands(n, tuple(moduli), batch, seed)
     for g in elements(n):
         for broadcast in (True, False):
             want = _want(n, tuple(moduli), batch, seed, terms, broadcast, g)
@@ -90,7 +91,7 @@ def test_other_moduli(agx, orc, dev, widths):
     n, batch = 1024, 5
     moduli = moduli_for(orc.find_prime, n, widths)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    a, b, la, lb = _operands(n, tuple(moduli), batch, 1024 + widths[1])
+    a, b, la, lb = inner_operands(n, tuple(moduli), batch, 1024 + widths[1])
     for terms, outputs, broadcast, g in ((3, 2, True, 5), (16, 2, False, 2 * n - 1), (2, 1, True, 3)):
         pick = lambda x: np.ascontiguousarray(x[:terms, :outputs, :, :1] if broadcast else x[:terms, :outputs])      # noqa: E731
         want = inner_ref(a[:terms][..., ntt_pi(n, g)], pick(b), moduli)
@@ -108,7 +109,7 @@ def test_it_is_automorphism_then_inner_product(agx, orc, dev, n):
     moduli = moduli_for(orc.find_prime, n, [60, 30, 61, 60])
     P = len(moduli)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    _, _, la, lb = _operands(n, tuple(moduli), batch, n + 17)
+    _, _, la, lb = inner_operands(n, tuple(moduli), batch, n + 17)
     a = np.ascontiguousarray(la[:terms])
     for broadcast in (True, False):
         b = np.ascontiguousarray(lb[:terms, :outputs, :, :1] if broadcast else lb[:terms, :outputs])
@@ -135,12 +136,12 @@ def test_alignment_and_guard_bands(agx, orc, dev, n, batch, offsets):
     moduli = moduli_for(orc.find_prime, n, [60, 30, 61, 60])
     P = len(moduli)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    _, _, la_w, lb_w = _operands(n, tuple(moduli), batch, n + 11)
+    _, _, la_w, lb_w = inner_operands(n, tuple(moduli), batch, n + 11)
     for broadcast in (True, False):
         a = np.ascontiguousarray(la_w[:terms])
         b = np.ascontiguousarray(lb_w[:terms, :outputs, :, :1] if broadcast else lb_w[:terms, :outputs])
         want = inner_ref(a[..., ntt_pi(n, g)], b, moduli)
-        la, lb, lc = _layouts(n, P, batch, terms, outputs, 1 if broadcast else batch, offsets)
+        la, lb, lc = inner_layouts(n, P, batch, terms, outputs, 1 if broadcast else batch, offsets)
         arena = arena_for(dev, n, (la, a), (lb, b), (lc, None))
         assert arena.address(0) % 16 == 0
         plan.inner_product_galois(arena.address(la.offset), arena.address(lb.offset), arena.address(lc.offset), batch, terms, g, outputs,
@@ -158,7 +159,7 @@ def test_rejected_calls_write_nothing(agx, orc, dev, n):
     moduli = moduli_for(orc.find_prime, n, [60] * 2)
     P = len(moduli)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    aw, bw, _, _ = _operands(n, tuple(moduli), batch, 5 * n)
+    aw, bw, _, _ = inner_operands(n, tuple(moduli), batch, 5 * n)
     a, b = np.ascontiguousarray(aw[:terms]), np.ascontiguousarray(bw[:terms, :outputs])
     la = Layout(n, terms * P, batch, offset=0)
     lb = Layout(n, terms * outputs * P, batch, offset=la.span() + 2 * n)
@@ -220,7 +221,7 @@ def _second_trip(agx, orc, dev, batch, shift):
     moduli = moduli_for(orc.find_prime, n, [30])
     q = int(moduli[0])
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    d_a, d_b = _device_words(torch, dev, terms * batch * n + shift, q, 1), _device_words(torch, dev, terms * outputs * n + shift, q, 2)
+    d_a, d_b = device_words(torch, dev, terms * batch * n + shift, q, 1), device_words(torch, dev, terms * outputs * n + shift, q, 2)
     d_c = dev.empty(outputs * batch * n + shift)
     d_c.fill_(-1)
     assert all(t.data_ptr() % 16 == 0 for t in (d_a, d_b, d_c))
@@ -259,7 +260,7 @@ def test_calls_are_graph_capturable(agx, orc, dev, n):
     batch, terms, outputs, g = 5, 3, 2, 2 * n - 1
     moduli = moduli_for(orc.find_prime, n, [60] * 4)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    first, second = _operands(n, tuple(moduli), batch, n + 5), _operands(n, tuple(moduli), batch, n + 6)
+    first, second = inner_operands(n, tuple(moduli), batch, n + 5), inner_operands(n, tuple(moduli), batch, n + 6)
     pick = lambda ops: (np.ascontiguousarray(ops[2][:terms]), np.ascontiguousarray(ops[3][:terms, :outputs, :, :1]))      # noqa: E731
     a, b = pick(first)
     d_a, d_b, d_c = dev.to_device(a.reshape(-1)), dev.to_device(b.reshape(-1)), dev.empty(outputs * a[0].size)

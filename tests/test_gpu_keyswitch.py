@@ -1,147 +1,28 @@
 """agx_ntt_keyswitch_* on the device: the RNS hybrid key switch of one ciphertext component in one call, NTT form in and out, at any level.
 
-The reference is the four-step definition of include/agx_ntt.h in Python integers, with the CPU oracle's forward and inverse transforms:
+The reference is rns_ref.keyswitch_ref: the four-step definition of include/agx_ntt.h in Python integers, with the CPU oracle's forward and inverse
+transforms:
   1. c_j = INTT_j(chat_j);   2. per digit d, V_d = sum_i y_i D_{d,i} with y_i = c_i D_{d,i}^-1 mod q_i, e_{d,j} = V_d mod q_j for every active j;
   3. acc_{o,j} = sum_d NTT_j(e_{d,j}) o key_{d,o,j} mod q_j;   4. out_{o,j} = NTT_j((INTT_j(acc_{o,j}) - V) D_P^-1 mod q_j), V the lift of acc_o's special slabs.
 Every comparison is word for word."""
-import functools
-
 import numpy as np
 import pytest
 
-from gpu_util import Layout, arena_for, canary, capture, moduli_for, oracle_tables, plan_for_moduli, status_of
+from gpu_util import Layout, arena_for, capture, moduli_for, plan_for_moduli, status_of
+from rns_cases import LOWER, SHAPE_IDS, SHAPES, TOP, keyswitch_case, run_keyswitch
+from rns_ref import active_of, digits_of, oracle_forward_set, oracle_inverse_set, product, ternary
 
 pytestmark = pytest.mark.gpu
 
-# (q_count, p_first, p_count, alpha) on a plan of six primes
-TOP, LOWER, FOUR_DIGITS, ONE_DIGIT = (4, 4, 2, 2), (3, 4, 2, 2), (4, 5, 1, 1), (4, 4, 2, 4)
-SHAPES = (TOP, LOWER, FOUR_DIGITS, ONE_DIGIT)
-SHAPE_IDS = ["top", "lower", "four-digits", "one-digit"]
-
-
-# ---- the reference ----------------------------------------------------------------------------------------------------------------
-def _product(moduli):
-    D = 1
-    for q in moduli:
-        D *= int(q)
-    return D
-
-
-def digits_of(shape):
-    q_count, _, _, alpha = shape
-    return [(first, min(alpha, q_count - first)) for first in range(0, q_count, alpha)]
-
-
-def active_of(moduli, shape):
-    q_count, p_first, p_count, _ = shape
-    return tuple(moduli[:q_count]) + tuple(moduli[p_first:p_first + p_count])
-
-
-def lift(p, src):
-    """p: [S][count] residues -> V = sum_i y_i D_i per coefficient (Python integers), y_i = p_i D_i^-1 mod q_i"""
-    p = np.asarray(p, dtype=np.uint64).reshape(len(src), -1)
-    D = _product(src)
-    V = np.zeros(p.shape[1], dtype=object)
-    for i, q in enumerate(src):
-        Di = D // int(q)
-        V = V + ((p[i] % np.uint64(q)).astype(object) * pow(Di, -1, int(q)) % int(q)) * Di
-    return V
-
-
-def _residues(V, moduli):
-    return np.stack([(V % int(q)).astype(np.uint64) for q in moduli])
-
-
-def _fwd(orc, n, moduli, x):
-    """the oracle's forward of the dense [len(moduli)][...][n] set x (reduced), [len(moduli)][count]"""
-    x = np.asarray(x, dtype=np.uint64).reshape(len(moduli), -1)
-    out = []
-    for i, q in enumerate(moduli):
-        q, _, tw, pre = oracle_tables(orc, n, q)
-        out.append(orc.forward(np.ascontiguousarray(x[i]), q, tw, pre, n))
-    return np.stack(out)
-
-
-def _inv(orc, n, moduli, xhat):
-    """the oracle's inverse of NTT-form words (any words below 4q: reduced first), [len(moduli)][count]"""
-    xhat = np.asarray(xhat, dtype=np.uint64).reshape(len(moduli), -1)
-    out = []
-    for i, q in enumerate(moduli):
-        q, psi, _, _ = oracle_tables(orc, n, q)
-        out.append(orc.inverse(np.ascontiguousarray(xhat[i] % np.uint64(q)), q, orc.make_inv_tables(q, psi, n)[0], n))
-    return np.stack(out)
-
-
-def keyswitch_ref(orc, n, moduli, shape, chat, key, batch):
-    """chat [q_count][batch][n], key [digits][2][A][n] (any words below 4q) -> out [2][q_count][batch][n] uint64, by the four steps"""
-    q_count, p_first, p_count, _ = shape
-    active = active_of(moduli, shape)
-    Q, special = active[:q_count], active[q_count:]
-    A, digs = len(active), digits_of(shape)
-    key = np.asarray(key, dtype=np.uint64).reshape(len(digs), 2, A, 1, n)
-    c = _inv(orc, n, Q, chat)                                                                     # step 1
-    acc = [[np.zeros(batch * n, dtype=object) for _ in range(A)] for _ in range(2)]
-    for d, (first, count) in enumerate(digs):                                                     # step 2
-        ehat = _fwd(orc, n, active, _residues(lift(c[first:first + count], Q[first:first + count]), active))
-        for o in range(2):                                                                        # step 3
-            for j, q in enumerate(active):
-                k = np.broadcast_to((key[d, o, j] % np.uint64(q)).astype(object), (batch, n)).reshape(-1)
-                acc[o][j] = acc[o][j] + ehat[j].astype(object) * k
-    out = []
-    DP = _product(special)
-    for o in range(2):                                                                            # step 4
-        acchat = np.stack([(acc[o][j] % int(q)).astype(np.uint64) for j, q in enumerate(active)])
-        a, V = _inv(orc, n, Q, acchat[:q_count]), lift(_inv(orc, n, special, acchat[q_count:]), special)
-        coeff = np.stack([((a[j].astype(object) - V) * pow(DP, -1, int(q)) % int(q)).astype(np.uint64) for j, q in enumerate(Q)])
-        out.append(_fwd(orc, n, Q, coeff))
-    return np.stack(out).reshape(2, q_count, batch, n)
-
-
-def spread(rng, x, moduli):
-    """[len(moduli)][...] words spread over [0, 4q)"""
-    x = np.asarray(x, dtype=np.uint64)
-    flat = x.reshape(len(moduli), -1)
-    return np.stack([flat[i] + np.uint64(q) * rng.integers(0, 4, size=flat.shape[1], dtype=np.uint64) for i, q in enumerate(moduli)]).reshape(x.shape)
-
-
-@functools.lru_cache(maxsize=None)
-def _case(orc, n, moduli, shape, batch, seed):
-    """(chat, key reduced; chat, key spread over [0,4q); the expected words), all flat, computed once per case (read-only).  Any residues are
-    NTT-form frames; the first frame opens with words 0 and q - 1"""
-    q_count = shape[0]
-    active = active_of(moduli, shape)
-    A, D = len(active), len(digits_of(shape))
-    rng = np.random.default_rng(seed)
-    chat = np.stack([rng.integers(0, int(q), size=(batch, n), dtype=np.uint64) for q in active[:q_count]])
-    chat[:, 0, 0] = 0
-    chat[:, 0, 1] = np.array(active[:q_count], dtype=np.uint64) - np.uint64(1)
-    key = np.stack([rng.integers(0, int(q), size=(D, 2, n), dtype=np.uint64) for q in active], axis=2)      # [D][2][A][n]
-    want = keyswitch_ref(orc, n, moduli, shape, chat, key, batch)
-    lkey = np.moveaxis(spread(rng, np.moveaxis(key, 2, 0), active), 0, 2)
-    out = (chat.reshape(-1), key.reshape(-1), spread(rng, chat, active[:q_count]).reshape(-1), np.ascontiguousarray(lkey).reshape(-1), want.reshape(-1))
-    for w in out:
-        w.setflags(write=False)
-    return out
-
-
-def _run(dev, ks, chat, key, batch):
-    """into a canary-filled out with a scratch of exactly the reported size; returns the output words and checks chat and key unchanged"""
-    d_chat, d_key = dev.to_device(chat), dev.to_device(key)
-    d_out, d_s = dev.to_device(canary(0, 2 * chat.size)), dev.empty(ks.scratch_words(batch))
-    ks.apply(d_chat.data_ptr(), d_key.data_ptr(), d_out.data_ptr(), d_s.data_ptr(), batch, dev.stream)
-    got = dev.to_host(d_out)
-    assert np.array_equal(dev.to_host(d_chat), chat) and np.array_equal(dev.to_host(d_key), key), "an input changed"
-    return got
-
 
 def _check(orc, dev, plan, n, moduli, shape, batch, seed, what):
-    chat, key, lchat, lkey, want = _case(orc, n, tuple(moduli), shape, batch, seed)
+    chat, key, lchat, lkey, want = keyswitch_case(orc, n, tuple(moduli), shape, batch, seed)
     ks = plan.keyswitch(*shape)
     q_count, p_first, p_count, alpha, digits, _ = ks.info()
     assert (q_count, p_first, p_count, alpha) == shape and digits == len(digits_of(shape))
     assert ks.scratch_words(batch) == (q_count + (digits + 2) * (q_count + p_count)) * batch * n
     for name, c_words, k_words in (("reduced", chat, key), ("spread", lchat, lkey)):
-        got = _run(dev, ks, c_words, k_words, batch)
+        got = run_keyswitch(dev, ks, c_words, k_words, batch)
         bad = np.flatnonzero(got != want)
         assert bad.size == 0, (what, name, "first differing words", bad[:4].tolist(), got[bad[:4]].tolist(), want[bad[:4]].tolist())
     ks.close()
@@ -185,9 +66,9 @@ def test_one_call_equals_the_public_calls(agx, orc, dev, n):
     moduli = moduli_for(orc.find_prime, n, [60] * 6)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     qplan, _ = plan_for_moduli(agx, orc, n, moduli[:q_count])
-    _, _, lchat, lkey, want = _case(orc, n, tuple(moduli), shape, batch, n + 41)
+    _, _, lchat, lkey, want = keyswitch_case(orc, n, tuple(moduli), shape, batch, n + 41)
     ks = plan.keyswitch(*shape)
-    assert np.array_equal(_run(dev, ks, lchat, lkey, batch), want)
+    assert np.array_equal(run_keyswitch(dev, ks, lchat, lkey, batch), want)
     A, digs, slab, st = q_count + p_count, digits_of(shape), batch * n, dev.stream
     d_chat, d_key = dev.to_device(lchat), dev.to_device(lkey)
     d_c, d_ext, d_acc, d_out = dev.empty(q_count * slab), dev.empty(len(digs) * A * slab), dev.empty(2 * A * slab), dev.empty(2 * q_count * slab)
@@ -210,14 +91,6 @@ def test_one_call_equals_the_public_calls(agx, orc, dev, n):
 
 
 # ---- it switches keys -----------------------------------------------------------------------------------------------------------
-def _ternary(rng, n, weight=None):
-    s = np.zeros(n, dtype=np.int64)
-    if weight is None:
-        return rng.integers(-1, 2, size=n)
-    s[rng.choice(n, size=weight, replace=False)] = rng.choice([-1, 1], size=weight)
-    return s
-
-
 @pytest.mark.parametrize("shape", SHAPES + ((3, 3, 3, 2),), ids=SHAPE_IDS + ["three-special"])
 def test_it_switches_keys(agx, orc, dev, shape):
     """A noise-free key: key_{d,1} = a_d random, key_{d,0} = -a_d s + D_P G_d s' with G_d = (Q / D_d) [(Q / D_d)^-1 mod D_d], ternary s of Hamming
@@ -229,14 +102,14 @@ def test_it_switches_keys(agx, orc, dev, shape):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     active = active_of(moduli, shape)
     Q, A, digs = active[:q_count], len(active), digits_of(shape)
-    Qp, DP = _product(Q), _product(active[q_count:])
+    Qp, DP = product(Q), product(active[q_count:])
     rng = np.random.default_rng(1000 + sum(shape))
-    s, s2 = _ternary(rng, n, 8), _ternary(rng, n)
-    shat = _fwd(orc, n, active, np.stack([(s % int(q)).astype(np.uint64) for q in active]))
-    s2hat = _fwd(orc, n, active, np.stack([(s2 % int(q)).astype(np.uint64) for q in active]))
+    s, s2 = ternary(rng, n, 8), ternary(rng, n)
+    shat = oracle_forward_set(orc, n, active, np.stack([(s % int(q)).astype(np.uint64) for q in active]))
+    s2hat = oracle_forward_set(orc, n, active, np.stack([(s2 % int(q)).astype(np.uint64) for q in active]))
     key = np.empty((len(digs), 2, A, n), dtype=np.uint64)
     for d, (first, count) in enumerate(digs):
-        Dd = _product(Q[first:first + count])
+        Dd = product(Q[first:first + count])
         G = (Qp // Dd) * pow(Qp // Dd, -1, Dd)
         for j, q in enumerate(active):
             ahat = rng.integers(0, int(q), size=n, dtype=np.uint64)
@@ -244,13 +117,13 @@ def test_it_switches_keys(agx, orc, dev, shape):
             key[d, 0, j] = ((DP * G % int(q)) * s2hat[j].astype(object) - ahat.astype(object) * shat[j].astype(object)) % int(q)
     chat = np.stack([rng.integers(0, int(q), size=(batch, n), dtype=np.uint64) for q in Q])
     ks = plan.keyswitch(*shape)
-    out = _run(dev, ks, chat.reshape(-1), key.reshape(-1), batch).reshape(2, q_count, batch, n)
+    out = run_keyswitch(dev, ks, chat.reshape(-1), key.reshape(-1), batch).reshape(2, q_count, batch, n)
     ks.close()
     plan.close()
     # (out_0 + out_1 s - c s') per prime of Q in NTT form, back through the oracle's inverse, then CRT to the centred range
     dhat = np.stack([((out[0, j].astype(object) + out[1, j].astype(object) * shat[j].astype(object) - chat[j].astype(object) * s2hat[j].astype(object)) % int(q)).astype(np.uint64)
                      for j, q in enumerate(Q)])
-    dev_res = _inv(orc, n, Q, dhat)
+    dev_res = oracle_inverse_set(orc, n, Q, dhat)
     X = np.zeros(batch * n, dtype=object)
     for j, q in enumerate(Q):
         X = X + dev_res[j].astype(object) * ((Qp // int(q)) * pow(Qp // int(q), -1, int(q)))
@@ -272,7 +145,7 @@ def test_guard_bands_and_odd_placement(agx, orc, dev, n, odd, shape):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     ks = plan.keyswitch(*shape)
     q_count, A, D = shape[0], shape[0] + shape[2], len(digits_of(shape))
-    _, _, chat, key, want = _case(orc, n, tuple(moduli), shape, batch, n + 23)
+    _, _, chat, key, want = keyswitch_case(orc, n, tuple(moduli), shape, batch, n + 23)
     place = lambda off: off + (off % 2 != (1 if odd else 0))      # noqa: E731
     lc = Layout(n, q_count, batch, offset=place(0))
     lk = Layout(n, D * 2 * A, 1, offset=place(lc.span() + 5))
@@ -325,7 +198,7 @@ def test_rejected_applies_write_nothing(agx, orc, dev, n, shape):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     ks = plan.keyswitch(*shape)
     q_count, A, D = shape[0], shape[0] + shape[2], len(digits_of(shape))
-    chat, key, _, _, want = _case(orc, n, tuple(moduli), shape, batch, 3 * n)
+    chat, key, _, _, want = keyswitch_case(orc, n, tuple(moduli), shape, batch, 3 * n)
     sizes = [chat.size, key.size, 2 * chat.size, ks.scratch_words(batch)]
     lc = Layout(n, q_count, batch, offset=0)
     lk = Layout(n, D * 2 * A, 1, offset=lc.span() + 2 * n)
@@ -412,12 +285,12 @@ def test_every_route_gives_the_same_words(agx, orc, dev, n, shape):
     batch = 5
     moduli = moduli_for(orc.find_prime, n, [60] * 6)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
-    _, _, lchat, lkey, want = _case(orc, n, tuple(moduli), shape, batch, n * 7 + batch + shape[0])
+    _, _, lchat, lkey, want = keyswitch_case(orc, n, tuple(moduli), shape, batch, n * 7 + batch + shape[0])
     ks = plan.keyswitch(*shape)
     for variant in (agx.VARIANT_AUTO, agx.VARIANT_LDS_RADIX2, agx.VARIANT_REGBLOCK, agx.VARIANT_AUTO):
         plan.set_variant(variant)
         assert ks.info()[5] == _expected_launches(agx, plan, shape, variant)
-        assert np.array_equal(_run(dev, ks, lchat, lkey, batch), want), ("variant", variant)
+        assert np.array_equal(run_keyswitch(dev, ks, lchat, lkey, batch), want), ("variant", variant)
     ks.close()
     plan.close()
 
@@ -431,7 +304,7 @@ def test_apply_is_graph_capturable(agx, orc, dev, n, shape):
     moduli = moduli_for(orc.find_prime, n, [60] * 6)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     ks = plan.keyswitch(*shape)
-    cases = [_case(orc, n, tuple(moduli), shape, batch, n * 7 + batch + shape[0]), _case(orc, n, tuple(moduli), shape, batch, n + 99)]
+    cases = [keyswitch_case(orc, n, tuple(moduli), shape, batch, n * 7 + batch + shape[0]), keyswitch_case(orc, n, tuple(moduli), shape, batch, n + 99)]
     d_chat, d_key = dev.to_device(cases[0][2]), dev.to_device(cases[0][3])
     d_out, d_s = dev.empty(2 * cases[0][0].size), dev.empty(ks.scratch_words(batch))
 

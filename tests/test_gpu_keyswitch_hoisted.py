@@ -1,22 +1,18 @@
 """The key switch in two halves on the device: agx_ntt_keyswitch_decompose (steps 1 and 2: done once per ciphertext) and
 agx_ntt_keyswitch_apply_decomposed (steps 3 and 4 with every digit read through pi_g: done once per rotation).
 
-The reference is tests/hoist_util.py: the four-step Python-integer reference of tests/test_gpu_keyswitch.py cut in two, with the NTT-form digits
-indexed by gpu_util.ntt_pi(n, g).  Every comparison is word for word."""
+The reference is rns_ref.decompose_ref and rns_ref.apply_decomposed_ref: the four-step Python-integer reference of the one call cut in two, with the
+NTT-form digits indexed by gpu_util.ntt_pi(n, g).  Every comparison is word for word."""
 import functools
 
 import numpy as np
 import pytest
 
 from gpu_util import Layout, arena_for, canary, capture, moduli_for, plan_for_moduli, status_of
-from hoist_util import apply_decomposed_ref, decompose_ref, rotation_bound, rotation_deviation, rotation_key_case
-from test_gpu_keyswitch import LOWER, SHAPE_IDS, SHAPES, TOP, _case, active_of, digits_of
-from test_gpu_keyswitch import _run as run_apply
+from rns_cases import FIVE, FIVE_IDS, LOWER, SHAPE_IDS, SHAPES, TOP, keyswitch_case, run_keyswitch
+from rns_ref import active_of, apply_decomposed_ref, decompose_ref, digits_of, rotation_bound, rotation_deviation, rotation_key_case, spread
 
 pytestmark = pytest.mark.gpu
-
-FIVE = SHAPES + ((3, 3, 3, 2),)
-FIVE_IDS = SHAPE_IDS + ["three-special"]
 
 
 def elements(n):
@@ -32,23 +28,23 @@ def sizes_of(shape, n, batch):
 
 @functools.lru_cache(maxsize=None)
 def _ext(orc, n, moduli, shape, batch, seed):
-    """the words decompose must write for _case's chat (reduced and spread alike), flat, once per case (read-only)"""
-    ext = decompose_ref(orc, n, moduli, shape, _case(orc, n, moduli, shape, batch, seed)[0]).reshape(-1)
+    """the words decompose must write for keyswitch_case's chat (reduced and spread alike), flat, once per case (read-only)"""
+    ext = decompose_ref(orc, n, moduli, shape, keyswitch_case(orc, n, moduli, shape, batch, seed)[0]).reshape(-1)
     ext.setflags(write=False)
     return ext
 
 
 @functools.lru_cache(maxsize=None)
 def _keys(orc, n, moduli, shape, batch, seed, g):
-    """(key reduced, key spread over [0,4q), the expected out) for element g, flat: a key of its own per element; g = 1 takes _case's key, whose
+    """(key reduced, key spread over [0,4q), the expected out) for element g, flat: a key of its own per element; g = 1 takes keyswitch_case's key, whose
     expected words are keyswitch_ref's (the one call's)"""
-    case = _case(orc, n, moduli, shape, batch, seed)
+    case = keyswitch_case(orc, n, moduli, shape, batch, seed)
     if g == 1:
         return case[1], case[3], case[4]
     active = active_of(moduli, shape)
     rng = np.random.default_rng(seed * 131 + g)
     key = np.stack([rng.integers(0, int(q), size=(len(digits_of(shape)), 2, n), dtype=np.uint64) for q in active], axis=2)
-    lkey = key + np.array(active, dtype=np.uint64)[None, None, :, None] * rng.integers(0, 4, size=key.shape, dtype=np.uint64)
+    lkey = spread(rng, key, active, axis=2)
     want = apply_decomposed_ref(orc, n, moduli, shape, _ext(orc, n, moduli, shape, batch, seed), key, batch, g)
     out = (key.reshape(-1), lkey.reshape(-1), want.reshape(-1))
     for w in out:
@@ -82,7 +78,7 @@ def _first_bad(got, want):
 
 # ---- decompose ------------------------------------------------------------------------------------------------------------------------
 def _check_decompose(orc, dev, plan, n, moduli, shape, batch, seed):
-    chat, _, lchat, _, _ = _case(orc, n, tuple(moduli), shape, batch, seed)
+    chat, _, lchat, _, _ = keyswitch_case(orc, n, tuple(moduli), shape, batch, seed)
     want = _ext(orc, n, tuple(moduli), shape, batch, seed)
     ks = plan.keyswitch(*shape)
     assert ks.hoisted_words(batch) == sizes_of(shape, n, batch)[3:]
@@ -116,7 +112,7 @@ def _check_apply(agx, orc, dev, plan, n, moduli, shape, batch, seed):
     """one decomposition, every element with a key of its own against hoisted_ref, reduced and spread keys; ext unchanged afterwards; g = 1 is the
     one call word for word, on the device too"""
     moduli = tuple(moduli)
-    _, _, lchat, _, _ = _case(orc, n, moduli, shape, batch, seed)
+    _, _, lchat, _, _ = keyswitch_case(orc, n, moduli, shape, batch, seed)
     ext = _ext(orc, n, moduli, shape, batch, seed)
     ks = plan.keyswitch(*shape)
     d_ext = _decompose(dev, ks, lchat, batch)
@@ -127,7 +123,7 @@ def _check_apply(agx, orc, dev, plan, n, moduli, shape, batch, seed):
             got = _apply(dev, ks, d_ext, k_words, batch, g, out_words)
             assert np.array_equal(got, want), (n, shape, batch, g, name, "first differing words", _first_bad(got, want))
         if g == 1:
-            assert np.array_equal(run_apply(dev, ks, lchat, lkey, batch), want), "apply differs from the two halves at g = 1"
+            assert np.array_equal(run_keyswitch(dev, ks, lchat, lkey, batch), want), "apply differs from the two halves at g = 1"
     assert np.array_equal(dev.to_host(d_ext), ext), "ext changed"
     ks.close()
 
@@ -153,7 +149,7 @@ def test_apply_decomposed_other_moduli(agx, orc, dev, n, widths):
 @pytest.mark.parametrize("g", [5, 127])
 @pytest.mark.parametrize("shape", FIVE, ids=FIVE_IDS)
 def test_it_switches_rotated_keys(agx, orc, dev, shape, g):
-    """the device's outputs with the noise-free rotation key of hoist_util.rotation_key_case: out_0 + out_1 s - sigma_g(c) sigma_g(s), CRT-centred
+    """the device's outputs with the noise-free rotation key of rns_ref.rotation_key_case: out_0 + out_1 s - sigma_g(c) sigma_g(s), CRT-centred
     modulo Q, is at most p_count (1 + ||s||_1) at every coefficient -- a condition, not a measurement"""
     n, batch = 64, 2
     assert g in (5, 2 * n - 1)
@@ -196,7 +192,7 @@ def test_every_route_gives_the_same_words(agx, orc, dev, n, shape):
     moduli = moduli_for(orc.find_prime, n, [60] * 6)
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     seed = n * 7 + batch + shape[0]
-    _, _, lchat, _, _ = _case(orc, n, tuple(moduli), shape, batch, seed)
+    _, _, lchat, _, _ = keyswitch_case(orc, n, tuple(moduli), shape, batch, seed)
     ext = _ext(orc, n, tuple(moduli), shape, batch, seed)
     _, lkey, want = _keys(orc, n, tuple(moduli), shape, batch, seed, g)
     ks = plan.keyswitch(*shape)
@@ -221,7 +217,7 @@ def test_guard_bands_and_odd_placement(agx, orc, dev, n, odd, shape):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     ks = plan.keyswitch(*shape)
     seed = n + 23
-    _, _, chat, _, _ = _case(orc, n, tuple(moduli), shape, batch, seed)
+    _, _, chat, _, _ = keyswitch_case(orc, n, tuple(moduli), shape, batch, seed)
     ext = _ext(orc, n, tuple(moduli), shape, batch, seed)
     _, key, want = _keys(orc, n, tuple(moduli), shape, batch, seed, g)
     words = ks.hoisted_words(batch)
@@ -257,7 +253,7 @@ def test_rejected_calls_write_nothing(agx, orc, dev, n, shape):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     ks = plan.keyswitch(*shape)
     seed = 3 * n
-    chat, _, _, _, _ = _case(orc, n, tuple(moduli), shape, batch, seed)
+    chat, _, _, _, _ = keyswitch_case(orc, n, tuple(moduli), shape, batch, seed)
     ext = _ext(orc, n, tuple(moduli), shape, batch, seed)
     key, _, want = _keys(orc, n, tuple(moduli), shape, batch, seed, g)
     chat_w, key_w, out_w, ext_w, ds_w, as_w = sizes_of(shape, n, batch)
@@ -346,7 +342,7 @@ def test_the_halves_are_graph_capturable(agx, orc, dev, n, shape):
     d_keys, d_outs = [dev.empty(key_w) for _ in gs], [dev.empty(out_w) for _ in gs]
 
     def load(seed):
-        d_chat.copy_(torch.from_numpy(_case(orc, n, moduli, shape, batch, seed)[2].view(np.int64).copy()))
+        d_chat.copy_(torch.from_numpy(keyswitch_case(orc, n, moduli, shape, batch, seed)[2].view(np.int64).copy()))
         for d_key, d_out, g in zip(d_keys, d_outs, gs):
             d_key.copy_(torch.from_numpy(_keys(orc, n, moduli, shape, batch, seed, g)[1].view(np.int64).copy()))
             d_out.zero_()

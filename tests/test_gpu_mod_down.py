@@ -1,15 +1,15 @@
 """agx_ntt_basis_mod_down on the device: ModDown of a hybrid key switch on NTT-form frames, by the two-launch route and by the generic one.
 
-The expected words come from Python integers, from the definition: with a_j, p_i the coefficient forms of the slabs, y_i = p_i (D_i^-1 mod q_i)
-mod q_i, V = sum_i y_i D_i as an integer, out_j = (a_j - V) (D^-1 mod q_j) mod q_j; the GPU gets the CPU oracle's forward of a_j and p_i and must
-return the oracle's forward of out_j.  Every comparison is word for word."""
+The expected words come from Python integers, from the definition (rns_ref.mod_down): with a_j, p_i the coefficient forms of the slabs,
+y_i = p_i (D_i^-1 mod q_i) mod q_i, V = sum_i y_i D_i as an integer, out_j = (a_j - V) (D^-1 mod q_j) mod q_j; the GPU gets the CPU oracle's forward
+of a_j and p_i and must return the oracle's forward of out_j.  Every comparison is word for word."""
 import functools
 
 import numpy as np
 import pytest
 
-from gpu_util import (RESCALE_IDS, Layout, arena_for, boundary_frames, canary, capture, moduli_for, oracle_tables, plan_for_moduli,
-                      registry_entries, status_of, thin_frames)
+from gpu_util import RESCALE_IDS, Layout, arena_for, canary, capture, judged_frames, moduli_for, plan_for_moduli, registry_entries, status_of
+from rns_ref import device_residues, lift, mod_down, mod_down_ntt, oracle_forward_set, product, residues, special_values, spread
 
 pytestmark = pytest.mark.gpu
 
@@ -19,47 +19,7 @@ SHAPES = (KEYSWITCH, DROPPED, SINGLE, BELOW)
 SHAPE_IDS = ["keyswitch", "dropped", "single", "below"]
 
 
-# ---- the reference: Python integers -----------------------------------------------------------------------------------------------
-def _product(moduli):
-    D = 1
-    for q in moduli:
-        D *= int(q)
-    return D
-
-
-def lift(p, src):
-    """p: [S][count] residues -> V = sum_i y_i D_i per coefficient (Python integers), y_i = p_i D_i^-1 mod q_i"""
-    p = np.asarray(p, dtype=np.uint64).reshape(len(src), -1)
-    D = _product(src)
-    V = np.zeros(p.shape[1], dtype=object)
-    for i, q in enumerate(src):
-        Di = D // int(q)
-        V = V + ((p[i] % np.uint64(q)).astype(object) * pow(Di, -1, int(q)) % int(q)) * Di
-    assert all(0 <= v < len(src) * D for v in (V.min(), V.max()))
-    return V
-
-
-def mod_down(a, p, src, dst):
-    """a: [T][count], p: [S][count] coefficient-form residues -> [T][count] uint64, from the definition"""
-    a = np.asarray(a, dtype=np.uint64).reshape(len(dst), -1)
-    V, D = lift(p, src), _product(src)
-    return np.stack([((a[j].astype(object) - V) * pow(D, -1, int(q)) % int(q)).astype(np.uint64) for j, q in enumerate(dst)])
-
-
-def _special_values(src):
-    """X_P per coefficient whose V = X_P + u D lies on a multiple of D or next to one, X_P = D - 1 (every residue q_i - 1), the X_P whose y_i are all
-    q_i - 1 (the largest V) or a single 1 (V = D_k)"""
-    D = _product(src)
-    out = [0, 1, 2, D - 1, D - 2, D // 2, D // 2 + 1]
-    out.append(sum((int(q) - 1) * (D // int(q)) for q in src) % D)
-    out += [D // int(q) % D for q in src]
-    return out
-
-
-def _residues(X, moduli):
-    return np.array([[int(x) % int(q) for x in X] for q in moduli], dtype=np.uint64)
-
-
+# ---- the cases ---------------------------------------------------------------------------------------------------------------------------------
 def make_inputs(rng, src, dst, batch, n):
     """(a [T][batch][n], p [S][batch][n], exact): reduced coefficient-form residues and the (frame, first, last, kind) regions whose result is
     known in closed form.  Frame 0 opens with the special values of the sources under random targets; its third quarter is X = D Y + V with small
@@ -68,47 +28,21 @@ def make_inputs(rng, src, dst, batch, n):
     S, T = len(src), len(dst)
     a = np.stack([rng.integers(0, int(q), size=batch * n, dtype=np.uint64) for q in dst]).reshape(T, batch, n)
     p = np.stack([rng.integers(0, int(q), size=batch * n, dtype=np.uint64) for q in src]).reshape(S, batch, n)
-    special = _residues(_special_values(src), src)
+    special = residues(special_values(src), src)
     k = min(n // 2, special.shape[1])
     p[:, 0, :k] = special[:, :k]
     if batch >= 5:
         p[:, 1, :] = 0
         p[:, 2, :] = np.array([int(q) - 1 for q in src], dtype=np.uint64)[:, None]
-    D = _product(src)
+    D = product(src)
     regions = [(0, n // 2, 3 * n // 4, "quotient"), (0, 3 * n // 4, n, "zero")] + ([(3, 0, n, "quotient"), (4, 0, n, "zero")] if batch >= 5 else [])
     exact = []
     for f, lo, hi, kind in regions:
         V = lift(p[:, f, lo:hi], src)
         Y = rng.integers(0, 1 << 20, size=hi - lo).astype(object) if kind == "quotient" else np.zeros(hi - lo, dtype=object)
-        a[:, f, lo:hi] = _residues(D * Y + V, dst)
-        exact.append((f, lo, hi, _residues(Y, dst)))
+        a[:, f, lo:hi] = residues(D * Y + V, dst)
+        exact.append((f, lo, hi, residues(Y, dst)))
     return a, p, exact
-
-
-def spread(rng, x, moduli):
-    """the same words spread over [0, 4 q)"""
-    x = np.asarray(x, dtype=np.uint64).reshape(len(moduli), -1)
-    return np.stack([x[i] + np.uint64(q) * rng.integers(0, 4, size=x.shape[1], dtype=np.uint64) for i, q in enumerate(moduli)])
-
-
-def _fwd(orc, n, moduli, x):
-    """the oracle's forward of the dense [len(moduli)][...][n] set x, [len(moduli)][count]"""
-    x = np.asarray(x, dtype=np.uint64).reshape(len(moduli), -1)
-    out = []
-    for i, q in enumerate(moduli):
-        q, _, tw, pre = oracle_tables(orc, n, q)
-        out.append(orc.forward(np.ascontiguousarray(x[i]), q, tw, pre, n))
-    return np.stack(out)
-
-
-def _inv(orc, n, moduli, xhat):
-    """the oracle's inverse of NTT-form words, [len(moduli)][count]"""
-    xhat = np.asarray(xhat, dtype=np.uint64).reshape(len(moduli), -1)
-    out = []
-    for i, q in enumerate(moduli):
-        q, psi, _, _ = oracle_tables(orc, n, q)
-        out.append(orc.inverse(np.ascontiguousarray(xhat[i]), q, orc.make_inv_tables(q, psi, n)[0], n))
-    return np.stack(out)
 
 
 @functools.lru_cache(maxsize=None)
@@ -121,8 +55,8 @@ def _case(orc, n, moduli, shape, batch, seed):
     coeff = mod_down(a, p, src, dst).reshape(T, batch, n)
     for f, lo, hi, want in exact:      # the closed forms hold for the reference itself
         assert np.array_equal(coeff[:, f, lo:hi], want)
-    xq, xp = _fwd(orc, n, dst, a), _fwd(orc, n, src, p)
-    out = (xq.reshape(-1), xp.reshape(-1), spread(rng, xq, dst).reshape(-1), spread(rng, xp, src).reshape(-1), _fwd(orc, n, dst, coeff).reshape(-1))
+    xq, xp = oracle_forward_set(orc, n, dst, a), oracle_forward_set(orc, n, src, p)
+    out = (xq.reshape(-1), xp.reshape(-1), spread(rng, xq, dst).reshape(-1), spread(rng, xp, src).reshape(-1), oracle_forward_set(orc, n, dst, coeff).reshape(-1))
     for w in out:
         w.setflags(write=False)
     return out
@@ -197,13 +131,13 @@ def test_sixteen_sources_of_62_bits(agx, orc, dev):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     basis = plan.basis(0, 16, 16, 1)
     rng = np.random.default_rng(62)
-    D = _product(src)
+    D = product(src)
     p = np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in src])
     p[:, :n // 2] = np.array([(q - 1) * (D // q) % q for q in src], dtype=np.uint64)[:, None]
     assert lift(p[:, :1], src)[0] == sum((q - 1) * (D // q) for q in src)
     a = rng.integers(0, dst[0], size=(1, n), dtype=np.uint64)
-    want = _fwd(orc, n, dst, mod_down(a, p, src, dst)).reshape(-1)
-    xq, xp = _fwd(orc, n, dst, a), _fwd(orc, n, src, p)
+    want = oracle_forward_set(orc, n, dst, mod_down(a, p, src, dst)).reshape(-1)
+    xq, xp = oracle_forward_set(orc, n, dst, a), oracle_forward_set(orc, n, src, p)
     for q_words, p_words in ((xq, xp), (spread(rng, xq, dst), spread(rng, xp, src))):
         assert np.array_equal(_run(dev, basis, q_words.reshape(-1), p_words.reshape(-1), batch), want)
     basis.close()
@@ -425,23 +359,12 @@ def test_odd_placement_and_guard_bands(agx, orc, dev, n, bits, batch):
 
 
 # ---- size ---------------------------------------------------------------------------------------------------------------------------
-def _device_residues(torch, dev, moduli, batch, n, seed):
-    """[len(moduli)][batch][n] on the device, slab i uniform below moduli[i]: any such words are NTT-form frames"""
-    g = torch.Generator(device=dev.device)
-    g.manual_seed(seed)
-    d = dev.empty(len(moduli) * batch * n)
-    v = d.view(len(moduli), -1)
-    for i, q in enumerate(moduli):
-        v[i] = torch.randint(0, int(q), (batch * n,), generator=g, device=dev.device, dtype=torch.int64)
-    return d
-
-
 def _judge_frames(orc, dev, d_xq, d_xp, d_out, src, dst, batch, n, frames):
     """the listed frames (of every target) against Python integers"""
     S, T = len(src), len(dst)
     pick = lambda d, k: dev.to_host(d.view(k, batch, n)[:, frames].contiguous()).reshape(k, -1)      # noqa: E731
-    coeff = mod_down(_inv(orc, n, dst, pick(d_xq, T)), _inv(orc, n, src, pick(d_xp, S)), src, dst)
-    want, got = _fwd(orc, n, dst, coeff).reshape(T, len(frames), n), pick(d_out, T).reshape(T, len(frames), n)
+    want = mod_down_ntt(orc, n, pick(d_xq, T), pick(d_xp, S), src, dst).reshape(T, len(frames), n)
+    got = pick(d_out, T).reshape(T, len(frames), n)
     bad = [(j, frames[f]) for j in range(T) for f in range(len(frames)) if not np.array_equal(got[j, f], want[j, f])]
     assert not bad, ("(target, frame)", bad[:8])
 
@@ -454,12 +377,11 @@ def test_1100_frames_at_4096(agx, orc, dev):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     basis = plan.basis(3, S, 0, T)
     assert basis.mod_down_launches() == (2 if _fused_expected(n, 60, S) else 4)
-    d_xq, d_xp = _device_residues(torch, dev, moduli[:T], batch, n, 3), _device_residues(torch, dev, moduli[3:], batch, n, 4)
+    d_xq, d_xp = device_residues(torch, dev, moduli[:T], batch, n, 3), device_residues(torch, dev, moduli[3:], batch, n, 4)
     d_out, d_s = dev.empty(T * batch * n), dev.empty(S * batch * n)
     d_out.fill_(-1)
     basis.mod_down(d_xq.data_ptr(), d_xp.data_ptr(), d_out.data_ptr(), d_s.data_ptr(), batch, dev.stream)
-    edges = [0, 1, 2, batch - 3, batch - 2, batch - 1]
-    frames = thin_frames(boundary_frames(batch) + edges, edges, limit=14)
+    frames = judged_frames(batch, 14)
     _judge_frames(orc, dev, d_xq, d_xp, d_out, moduli[3:], moduli[:T], batch, n, frames)
     basis.close()
     plan.close()
@@ -475,7 +397,7 @@ def test_generic_kernel_past_one_grid_stride_trip(agx, orc, dev):
     plan, _ = plan_for_moduli(agx, orc, n, moduli)
     basis = plan.basis(3, S, 0, T)
     assert basis.mod_down_launches() == 4
-    d_xq, d_xp = _device_residues(torch, dev, moduli[:T], batch, n, 5), _device_residues(torch, dev, moduli[3:], batch, n, 6)
+    d_xq, d_xp = device_residues(torch, dev, moduli[:T], batch, n, 5), device_residues(torch, dev, moduli[3:], batch, n, 6)
     d_out, d_s = dev.empty(T * batch * n), dev.empty(S * batch * n)
     d_out.fill_(-1)
     basis.mod_down(d_xq.data_ptr(), d_xp.data_ptr(), d_out.data_ptr(), d_s.data_ptr(), batch, dev.stream)
@@ -487,8 +409,7 @@ def test_generic_kernel_past_one_grid_stride_trip(agx, orc, dev):
         basis.mod_down(part_q.data_ptr(), part_p.data_ptr(), part_out.data_ptr(), part_s.data_ptr(), chunk, dev.stream)
         dev.sync()
         assert torch.equal(ov[:, f0:f0 + chunk], part_out.view(T, chunk, n)), ("the large call differs from the call on frames", f0, f0 + chunk)
-    edges = [0, 1, 2, batch - 3, batch - 2, batch - 1]
-    frames = thin_frames(boundary_frames(batch) + list(range(0, batch, 4999)) + edges, edges, limit=48)
+    frames = judged_frames(batch, 48, extra=range(0, batch, 4999))
     _judge_frames(orc, dev, d_xq, d_xp, d_out, moduli[3:], moduli[:T], batch, n, frames)
     basis.close()
     plan.close()

@@ -1,16 +1,14 @@
-"""The reference of the hoisted key switch alone, no device: hoisted_ref (tests/hoist_util.py) is keyswitch_ref with every NTT-form digit read
+"""The reference of the hoisted key switch alone, no device: hoisted_ref (tests/rns_ref.py) is keyswitch_ref with every NTT-form digit read
 through pi_g.  With g = 1 it is keyswitch_ref word for word; with a noise-free rotation key it switches sigma_g(c) from sigma_g(s) to s within
 the bound of test_it_switches_keys.  What the device tests compare against is therefore what a rotation needs."""
 import numpy as np
 import pytest
 
 from gpu_util import moduli_for
-from hoist_util import hoisted_ref, rotation_bound, rotation_deviation, rotation_key_case
-from test_gpu_keyswitch import SHAPE_IDS, SHAPES, active_of, digits_of, keyswitch_ref
+from rns_cases import FIVE, FIVE_IDS
+from rns_ref import active_of, digits_of, hoisted_ref, keyswitch_ref, rotation_bound, rotation_deviation, rotation_key_case
 
 N, BATCH = 64, 2
-FIVE = SHAPES + ((3, 3, 3, 2),)
-FIVE_IDS = SHAPE_IDS + ["three-special"]
 ELEMENTS = (1, 5, 25, 2 * N - 1, 3, 77)
 
 
