@@ -64,6 +64,11 @@ ABI = {
     "agx_ntt_basis_mod_down_info": (_int, [_vp, ctypes.POINTER(_int)]),
     "agx_ntt_inner_product": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _vp]),
     "agx_ntt_inner_product_galois": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp]),
+    "agx_ntt_add": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp]),
+    "agx_ntt_sub": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp]),
+    "agx_ntt_negate": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _vp]),
+    "agx_ntt_add_galois": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp]),
+    "agx_ntt_tensor": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp]),
     "agx_ntt_keyswitch_create": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32]),
     "agx_ntt_keyswitch_destroy": (_int, [_vp]),
     "agx_ntt_keyswitch_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_int)]),
@@ -189,7 +194,7 @@ def kernel_source_sha16():
     import hashlib
 
     h = hashlib.sha256()
-    files = glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + [os.path.join(_HERE, "csrc", f) for f in ("rb_frame.hpp", "rb_kernels.hpp", "rb32_kernels.hpp", "wp_kernels.hpp", "rb_stream_opts.hpp", "rb_registry.hpp", "modarith.hpp", "inner_reduce.hpp", "ntt_kernels.hpp")]
+    files = glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + [os.path.join(_HERE, "csrc", f) for f in ("rb_frame.hpp", "rb_kernels.hpp", "rb32_kernels.hpp", "wp_kernels.hpp", "rb_stream_opts.hpp", "rb_registry.hpp", "modarith.hpp", "inner_reduce.hpp", "ring_arith.hpp", "ring_kernels.hpp", "ntt_kernels.hpp")]
     for f in sorted(files):
         h.update(os.path.relpath(f, _HERE).encode())
         h.update(open(f, "rb").read())
@@ -352,6 +357,32 @@ class Plan:
         permuted copy of a; galois_elt odd, below 2n (1: inner_product itself)"""
         _check(lib().agx_ntt_inner_product_galois(self._h, d_a, d_bhat, d_c, batch, batch if bhat_batch is None else bhat_batch, terms, outputs, galois_elt, stream),
                "inner_product_galois")
+
+    def _prime_range(self, prime_first, prime_count):
+        return prime_first, self.num_primes if prime_count is None else prime_count
+
+    def add(self, d_a, d_b, d_c, batch, prime_first=0, prime_count=None, stream=0):
+        """c = a + b mod q on the plan primes [prime_first, prime_first + prime_count) (None: all of the plan's), one launch: every operand dense
+        [prime_count][batch][n]; inputs in [0,4q), c fully reduced; d_c may be d_a, d_b or both"""
+        _check(lib().agx_ntt_add(self._h, d_a, d_b, d_c, batch, *self._prime_range(prime_first, prime_count), stream), "add")
+
+    def sub(self, d_a, d_b, d_c, batch, prime_first=0, prime_count=None, stream=0):
+        """c = a - b mod q, as add"""
+        _check(lib().agx_ntt_sub(self._h, d_a, d_b, d_c, batch, *self._prime_range(prime_first, prime_count), stream), "sub")
+
+    def negate(self, d_a, d_c, batch, prime_first=0, prime_count=None, stream=0):
+        """c = -a mod q (-0 = 0), as add; d_c may be d_a"""
+        _check(lib().agx_ntt_negate(self._h, d_a, d_c, batch, *self._prime_range(prime_first, prime_count), stream), "negate")
+
+    def add_galois(self, d_a, d_b, d_c, batch, galois_elt, prime_first=0, prime_count=None, stream=0):
+        """c[i] = a[i] + b[pi_g(i)] mod q within every frame: a plus the NTT-form automorphism X -> X^galois_elt of b, one launch, no permuted copy of b;
+        d_c may be d_a and may not touch d_b; galois_elt odd, below 2n (1: add itself)"""
+        _check(lib().agx_ntt_add_galois(self._h, d_a, d_b, d_c, batch, *self._prime_range(prime_first, prime_count), galois_elt, stream), "add_galois")
+
+    def tensor(self, d_a, d_b, d_c, batch, prime_first=0, prime_count=None, stream=0):
+        """(c_0, c_1, c_2) = (a_0 o b_0, a_0 o b_1 + a_1 o b_0, a_1 o b_1) mod q in one launch: d_a, d_b [2][prime_count][batch][n], d_c
+        [3][prime_count][batch][n], out of place (d_a may be d_b)"""
+        _check(lib().agx_ntt_tensor(self._h, d_a, d_b, d_c, batch, *self._prime_range(prime_first, prime_count), stream), "tensor")
 
     def keyswitch(self, q_count, p_first, p_count, alpha):
         """KeySwitch(self, ...): the hybrid key switch at level Q = primes [0, q_count) with special primes [p_first, p_first + p_count)"""

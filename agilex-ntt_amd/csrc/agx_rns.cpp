@@ -1,4 +1,5 @@
-// agx_rns.cpp -- the RNS calls of include/agx_ntt.h: rescale, basis extension and ModDown, the inner products and the key switch.  Each composes the
+// agx_rns.cpp -- the RNS calls of include/agx_ntt.h: rescale, basis extension and ModDown, the inner products, the ring arithmetic on a range of the
+// plan's primes (add, sub, negate, add_galois, tensor: one streaming kernel each) and the key switch.  Each of the others composes the
 // plan's transforms (run_forward / run_inverse on views of its routes, plan_internal.hpp) with a coefficient-domain or fused kernel; plans, routes and
 // the transform calls themselves live in agx_ntt.cpp.
 #include <cstdlib>
@@ -225,6 +226,67 @@ int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a, const u
 int agx_ntt_inner_product_galois(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
                                  uint32_t terms, uint32_t outputs, uint32_t galois_elt, void* stream) {
     return inner_product_call(plan, d_a, d_bhat, d_c, batch, bhat_batch, terms, outputs, galois_elt, stream);
+}
+
+}  // extern "C"
+
+// agx_ntt_add, _sub, _negate, _add_galois and _tensor: one statement of the rules, in the inner products' order.  d_b is d_a for the negation, which has
+// one operand; galois_elt is 1 for every call but add_galois.
+enum ring_kind { kRingAdd, kRingSub, kRingNegate, kRingAddGalois, kRingTensor };
+
+static int ring_call(ring_kind kind, const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first,
+                     uint32_t prime_count, uint32_t galois_elt, void* stream) {
+    if (!plan || !d_a || !d_b || !d_c) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes, n = plan->n;
+    if (prime_count == 0 || prime_count > P || prime_first > P - prime_count) return AGX_ERR_BAD_ARGUMENT;
+    if (!aligned8(d_a) || !aligned8(d_b) || !aligned8(d_c)) return AGX_ERR_BAD_ARGUMENT;
+    if (!batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;      // from here on batch n < 2^46
+    // every operand is one dense range: prime_count slabs, two and three times as many for the tensor product (at most 3 x 65535)
+    const uint32_t in_slabs = (kind == kRingTensor ? 2 : 1) * prime_count, out_slabs = (kind == kRingTensor ? 3 : 1) * prime_count;
+    if (!dense_fits(n, in_slabs, batch) || !dense_fits(n, out_slabs, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t in_words = in_slabs * batch * n, out_words = out_slabs * batch * n;      // each <= 2^60
+    // c IS an operand it may equal, or touches nothing of it: add and sub either operand, negate and add_galois a (every work item reads its own words
+    // before it writes them).  add_galois reads b across the frame and the tensor product writes three words for two read: c touches those nowhere;
+    // g = 1 is agx_ntt_add and takes its rule.
+    const bool may_equal_a = kind != kRingTensor, may_equal_b = kind == kRingAdd || kind == kRingSub || kind == kRingNegate || (kind == kRingAddGalois && galois_elt == 1);
+    auto apart = [&](const uint64_t* x, bool may_equal) { return (may_equal && x == d_c) || !ranges_touch(addr(d_c), out_words, addr(x), in_words); };
+    if (!apart(d_a, may_equal_a) || !apart(d_b, may_equal_b)) return AGX_ERR_BAD_ARGUMENT;
+    if (!galois_ok(galois_elt, n)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (batch == 0) return AGX_OK;
+    const route& r = plan->routes.forward;      // the whole plan's view: only its constants are read, at [prime_first, prime_first + prime_count)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (kind) {
+        case kRingAdd: AGX_HIP(launch_ring_add(r, prime_first, prime_count, d_a, d_b, d_c, batch, s)); break;
+        case kRingSub: AGX_HIP(launch_ring_sub(r, prime_first, prime_count, d_a, d_b, d_c, batch, s)); break;
+        case kRingNegate: AGX_HIP(launch_ring_negate(r, prime_first, prime_count, d_a, d_c, batch, s)); break;
+        case kRingAddGalois: AGX_HIP(launch_ring_add_galois(r, prime_first, prime_count, d_a, d_b, d_c, batch, galois_elt, s)); break;
+        case kRingTensor: AGX_HIP(launch_ring_tensor(r, prime_first, prime_count, d_a, d_b, d_c, batch, s)); break;
+    }
+    return AGX_OK;
+}
+
+extern "C" {
+
+int agx_ntt_add(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first, uint32_t prime_count, void* stream) {
+    return ring_call(kRingAdd, plan, d_a, d_b, d_c, batch, prime_first, prime_count, 1, stream);
+}
+
+int agx_ntt_sub(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first, uint32_t prime_count, void* stream) {
+    return ring_call(kRingSub, plan, d_a, d_b, d_c, batch, prime_first, prime_count, 1, stream);
+}
+
+int agx_ntt_negate(const agx_ntt_plan* plan, const uint64_t* d_a, uint64_t* d_c, uint64_t batch, uint32_t prime_first, uint32_t prime_count, void* stream) {
+    return ring_call(kRingNegate, plan, d_a, d_a, d_c, batch, prime_first, prime_count, 1, stream);
+}
+
+int agx_ntt_add_galois(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first, uint32_t prime_count,
+                       uint32_t galois_elt, void* stream) {
+    return ring_call(kRingAddGalois, plan, d_a, d_b, d_c, batch, prime_first, prime_count, galois_elt, stream);
+}
+
+int agx_ntt_tensor(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first, uint32_t prime_count, void* stream) {
+    return ring_call(kRingTensor, plan, d_a, d_b, d_c, batch, prime_first, prime_count, 1, stream);
 }
 
 int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha) {

@@ -276,6 +276,15 @@ struct inner_galois_args {
 
 __device__ __forceinline__ uint64_t inner_gather(uint64_t v, bool) { return v; }
 __device__ __forceinline__ ulonglong2 inner_gather(ulonglong2 v, bool swap) { return swap ? make_ulonglong2(v.y, v.x) : v; }
+// the index text: work item i (in W of kLanes words, w its position within the frame) reads the W at the returned index, `swap`: with its halves exchanged
+template <int kLanes>
+__device__ __forceinline__ uint64_t galois_read_index(uint64_t i, uint32_t frame_mask, uint32_t log_n, uint32_t g, bool& swap) {
+    const uint32_t mask = (1u << log_n) - 1u, shift = 32u - log_n, half = (g - 1u) >> 1;
+    const uint32_t w = (uint32_t)i & frame_mask;      // the position within the frame, in W; its first word is w kLanes (even in pair form)
+    const uint32_t j = __brev((g * (__brev(w * kLanes) >> shift) + half) & mask) >> shift;      // g < 2^16, brev < 2^15
+    swap = kLanes == 2 && (j & 1u);
+    return (i - w) + j / kLanes;
+}
 
 template <int OUT, class W>
 __global__ void inner_product_galois_kernel(const W* __restrict__ a, const W* __restrict__ bhat, W* __restrict__ c, const prime_consts* __restrict__ consts,
@@ -285,16 +294,13 @@ __global__ void inner_product_galois_kernel(const W* __restrict__ a, const W* __
     const uint32_t slot = blockIdx.y;
     const prime_consts k = consts[slot < g.split ? slot : slot + g.skip];
     const uint64_t q2 = k.q << 1;
-    const uint32_t mask = (1u << ga.log_n) - 1u, shift = 32u - ga.log_n, half = (ga.g - 1u) >> 1;
     const W* ap = a + (uint64_t)slot * g.per_prime;
     const W* bp = bhat + (uint64_t)slot * g.b_prime;
     W* cp = c + (uint64_t)slot * g.per_prime;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t w = (uint32_t)i & g.frame_mask;      // the position within the frame, in W; its first word is w kLanes (even in pair form)
-        const uint32_t j = __brev((ga.g * (__brev(w * kLanes) >> shift) + half) & mask) >> shift;      // g < 2^16, brev < 2^15
-        const uint64_t ai = (i - w) + j / kLanes;
-        const bool swap = kLanes == 2 && (j & 1u);
-        const uint64_t bi = g.broadcast ? w : i;
+        bool swap;
+        const uint64_t ai = galois_read_index<kLanes>(i, g.frame_mask, ga.log_n, ga.g, swap);
+        const uint64_t bi = g.broadcast ? (i & g.frame_mask) : i;
         acc128 s[OUT][kLanes];
         for (uint32_t t0 = 0; t0 < g.terms; t0 += kGroup) {
             W av[kGroup], bv[kGroup][OUT];
@@ -316,6 +322,12 @@ __global__ void inner_product_galois_kernel(const W* __restrict__ a, const W* __
         for (int o = 0; o < OUT; ++o) inner_store(cp + o * g.c_out + i, s[o], k);
     }
 }
+
+}  // namespace agx
+
+#include "ring_kernels.hpp"      // agx_ntt_add / _sub / _negate / _add_galois / _tensor: behind inner_gather and galois_read_index, which it reuses
+
+namespace agx {
 
 // agx_ntt_rescale, generic route, in the coefficient domain: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i with u_i the lift of t[k] to q_i
 // (rescale_lift).  out: dense [prime][batch][n] over the view's primes 0 .. P-2, values in [0,q_i) as the inverse leaves them; t: [batch][n]
@@ -665,6 +677,50 @@ hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, con
     const bool pairs = inner_pairs(a, bhat, c);
     const inner_args g = inner_args_of(pv, ip, batch, bhat_batch, terms, outputs, pairs);
     return launch_inner<inner_plain>(pv, ip.count, g.per_prime, a, bhat, c, outputs, pairs, g, s);
+}
+
+// The ring calls: one launch each over the plan primes [first, first + count), 256 threads, the 16-byte form when every base of the call allows it
+template <class W, class Args>
+static hipError_t launch_ring(void (*kernel)(const W*, const W*, W*, const prime_consts*, Args), const plan_view& pv, uint32_t count, uint64_t per_prime, const void* a,
+                              const void* b, void* c, const Args& g, hipStream_t s) {
+    hipLaunchKernelGGL(kernel, dim3(grid_1d(per_prime, 256), count), dim3(256), 0, s, static_cast<const W*>(a), static_cast<const W*>(b), static_cast<W*>(c), pv.consts, g);
+    return hipGetLastError();
+}
+
+static hipError_t launch_ring_linear(const plan_view& pv, uint32_t first, uint32_t count, int op, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
+    const bool pairs = inner_pairs(a, b, c);      // a negation passes a for b
+    const ring_args g{(batch << pv.log_n) >> (pairs ? 1 : 0), first};
+    auto go = [&](auto kernel) { return launch_ring(kernel, pv, count, g.per_prime, a, b, c, g, s); };
+    if (pairs) return op == RING_ADD ? go(&ring_linear_kernel<RING_ADD, ulonglong2>) : op == RING_SUB ? go(&ring_linear_kernel<RING_SUB, ulonglong2>) : go(&ring_linear_kernel<RING_NEG, ulonglong2>);
+    return op == RING_ADD ? go(&ring_linear_kernel<RING_ADD, uint64_t>) : op == RING_SUB ? go(&ring_linear_kernel<RING_SUB, uint64_t>) : go(&ring_linear_kernel<RING_NEG, uint64_t>);
+}
+
+hipError_t launch_ring_add(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
+    return launch_ring_linear(pv, first, count, RING_ADD, a, b, c, batch, s);
+}
+hipError_t launch_ring_sub(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
+    return launch_ring_linear(pv, first, count, RING_SUB, a, b, c, batch, s);
+}
+hipError_t launch_ring_negate(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, uint64_t* c, uint64_t batch, hipStream_t s) {
+    return launch_ring_linear(pv, first, count, RING_NEG, a, a, c, batch, s);
+}
+
+hipError_t launch_ring_add_galois(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch,
+                                  uint32_t galois_elt, hipStream_t s) {
+    if (galois_elt == 1) return launch_ring_add(pv, first, count, a, b, c, batch, s);      // pi is the identity: the plain kernel
+    const bool pairs = inner_pairs(a, b, c);
+    const uint32_t shift = pairs ? 1 : 0;
+    const ring_galois_args g{ring_args{(batch << pv.log_n) >> shift, first}, (pv.n >> shift) - 1u, pv.log_n, galois_elt};
+    if (pairs) return launch_ring(&ring_add_galois_kernel<ulonglong2>, pv, count, g.in.per_prime, a, b, c, g, s);
+    return launch_ring(&ring_add_galois_kernel<uint64_t>, pv, count, g.in.per_prime, a, b, c, g, s);
+}
+
+hipError_t launch_ring_tensor(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
+    const bool pairs = inner_pairs(a, b, c);      // a component lies count batch n words behind the one before: an even number
+    const uint64_t per_prime = (batch << pv.log_n) >> (pairs ? 1 : 0);
+    const ring_tensor_args g{per_prime, count * per_prime, first};
+    if (pairs) return launch_ring(&ring_tensor_kernel<ulonglong2>, pv, count, per_prime, a, b, c, g, s);
+    return launch_ring(&ring_tensor_kernel<uint64_t>, pv, count, per_prime, a, b, c, g, s);
 }
 
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s) {

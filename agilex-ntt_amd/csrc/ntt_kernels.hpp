@@ -97,6 +97,16 @@ hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, con
 // bhat_{t,o}[i]; g odd in [1, 2n).  No permuted copy of a is written.  One launch; g = 1 takes launch_inner_product's kernel.
 hipError_t launch_inner_product_galois(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
                                        uint64_t bhat_batch, uint32_t terms, uint32_t outputs, uint32_t galois_elt, hipStream_t s);
+// agx_ntt_add / _sub / _negate / _add_galois / _tensor on the plan primes [first, first + count): every operand set dense [count][batch][n] (the tensor
+// product: a, b [2][count][batch][n], c [3][count][batch][n]), slab i under plan prime first + i; inputs in [0,4q), c in [0,q).  pv: a view of the WHOLE
+// plan (only its constants are read).  c may be a or b (add, sub), a (negate, add_galois; there c touches b nowhere), neither (tensor; a may be b).
+// 16-byte accesses when all bases of the call allow them.  One launch each; add_galois with g = 1 takes launch_ring_add's kernel.
+hipError_t launch_ring_add(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
+hipError_t launch_ring_sub(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
+hipError_t launch_ring_negate(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, uint64_t* c, uint64_t batch, hipStream_t s);
+hipError_t launch_ring_add_galois(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch,
+                                  uint32_t galois_elt, hipStream_t s);
+hipError_t launch_ring_tensor(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
 // the coefficient-domain step of agx_ntt_rescale's generic route: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i on the dense [prime][batch][n]
 // layout of pv's primes (a view of primes 0 .. P-2), u_i the lift of t[k] ([batch][n], coefficients of the last slab in [0, q_L)) to q_i
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s);

@@ -343,6 +343,46 @@ AGX_API int agx_ntt_inner_product(const agx_ntt_plan* plan, const uint64_t* d_a,
 AGX_API int agx_ntt_inner_product_galois(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch,
                                          uint64_t bhat_batch, uint32_t terms, uint32_t outputs, uint32_t galois_elt, void* stream);
 
+/* Ring arithmetic on NTT-form frames over a RANGE of the plan's primes: add, subtract, negate, add through a Galois automorphism, and the tensor product of
+ * two ciphertexts.  With them a homomorphic multiplication (tensor, agx_ntt_keyswitch_apply on c_2, two adds, agx_ntt_rescale) and a hoisted rotation
+ * (decompose, apply_decomposed, add_galois) run on library calls alone, at any level of one plan.
+ * All five serve the plan primes [prime_first, prime_first + prime_count); every operand set is dense [prime_count][batch][n], slab i under plan prime
+ * prime_first + i, as agx_ntt_basis_create names its ranges; a ciphertext at level q_count passes (0, q_count).  For agx_ntt_tensor a and b are
+ * [2][prime_count][batch][n] and c is [3][prime_count][batch][n].  Every input word may lie in [0, 4 q_p), as agx_ntt_forward_lazy leaves them; every output
+ * is fully reduced and exact against big-integer arithmetic on the residues.  Positions are not interpreted -- any order that all operands share -- except by
+ * add_galois.  Per word, with x' = x mod q_p:
+ *   add        c = (a' + b') mod q_p                 sub     c = (a' - b') mod q_p                 negate  c = (-a') mod q_p, -0 = 0
+ *   add_galois c[p][f][i] = (a[p][f][i]' + b[p][f][pi_g(i)]') mod q_p, pi_g(i) = brev((g brev(i) + (g - 1) / 2) mod n): a + agx_ntt_automorphism(AGX_FORM_NTT, g) of b,
+ *              without the permuted copy of b; galois_elt = 1 is agx_ntt_add word for word and runs its kernel
+ *   tensor     c_0 = a_0 o b_0,   c_1 = a_0 o b_1 + a_1 o b_0,   c_2 = a_1 o b_1, all mod q_p; the cross term is summed in 128 bits and reduced once
+ * Every plan serves, whatever its variant, size and moduli; no inverse tables are needed and plan creation is unchanged.
+ * Aliasing.  add, sub: d_c may be exactly d_a, exactly d_b, or both; d_a and d_b may overlap in any way (both are only read).  negate: d_c may be exactly d_a.
+ * add_galois: d_c may be exactly d_a (the in-place out_0 += sigma_g(c0)); d_c may not touch d_b anywhere, since b is gathered across the frame -- with
+ * galois_elt = 1, as for add, it may be d_b.  tensor: OUT OF PLACE ONLY, d_c's range touches neither d_a's nor d_b's; d_a == d_b squares, and they may overlap
+ * freely.  Every other contact -- a partial overlap of c with an operand it may equal, any contact with one it may not touch -- is AGX_ERR_BAD_ARGUMENT.
+ * Ranges that meet end to end do not touch.
+ * Status order of the five, agx_ntt_inner_product's: a NULL plan or pointer: AGX_ERR_NULL_POINTER; prime_count == 0 or a range past P; a pointer not 8-byte
+ * aligned; a batch past the grid limit; an operand's extent past 2^60 words; the aliasing rules above; add_galois only: galois_elt even, 0 or >= 2n; the
+ * plan's device not current: AGX_ERR_BAD_ARGUMENT, nothing written; batch == 0: AGX_OK, nothing launched.
+ * Asynchronous on `stream`; they allocate nothing, synchronise nothing and touch no plan state (capturable into a hipGraph).  ONE launch each: a grid-stride
+ * streaming kernel, no LDS, no barrier, no table; 16-byte accesses when ALL bases of the call are 16-byte aligned, 8-byte ones otherwise.  They move 24 bytes
+ * per word (add, sub, add_galois), 16 (negate) and 56 per word of a frame (tensor: four words read, three written), where four agx_ntt_pointwise launches
+ * move 96 and leave the cross term's add to the caller, and agx_ntt_automorphism into a copy followed by an add moves 40 and needs the copy's memory.
+ * Measured (profiles/r12_ring_ops.md; six 60-bit primes, range (0, 4), n = 4096 with 4,096 frames per prime and n = 16384 with 1,024, 16-byte bases, g = 5), beside a
+ * device copy of the model's bytes in the same process: add 280 / 281 us (0.94 / 0.89 of the copy), sub 281 / 283 (0.94 / 0.85), negate 180 / 181 (0.90 / 0.94), add_galois
+ * 284 / 293 (0.91 / 0.95; 1 % and 4 % above the plain add, the spreads apart) and 0.40 / 0.41 of agx_ntt_automorphism into a copy plus an add; tensor 699 / 745 us: 0.94 of the
+ * copy at n = 4096 and 1.00 at n = 16384, where its spread and the copy's overlap -- level with the copy there, not ahead -- and 0.65 / 0.68 of four agx_ntt_pointwise launches.
+ * Groups: no group form, as for the other RNS calls: each shard calls them on its own plan. */
+AGX_API int agx_ntt_add(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first,
+                        uint32_t prime_count, void* stream);
+AGX_API int agx_ntt_sub(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first,
+                        uint32_t prime_count, void* stream);
+AGX_API int agx_ntt_negate(const agx_ntt_plan* plan, const uint64_t* d_a, uint64_t* d_c, uint64_t batch, uint32_t prime_first, uint32_t prime_count, void* stream);
+AGX_API int agx_ntt_add_galois(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first,
+                               uint32_t prime_count, uint32_t galois_elt, void* stream);
+AGX_API int agx_ntt_tensor(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first,
+                           uint32_t prime_count, void* stream);
+
 /* The RNS hybrid key switch of one ciphertext component in one call: NTT form in, NTT form out, at any level.
  * Primes.  Q, the ciphertext's current level, is the plan's primes [0, q_count).  The special primes are [p_first, p_first + p_count), p_first >= q_count:
  * they need not follow Q directly, which is what a level below the top looks like.  The ACTIVE primes are Q followed by the special primes, A = q_count +
@@ -397,7 +437,7 @@ AGX_API int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t*
  * key for sigma_g(s) -> s, and every output word is exact against big-integer arithmetic.  For g != 1 the result is NOT word-equal to agx_ntt_automorphism on
  * chat followed by apply: the approximate lift does not commute with negation, and the two results differ by what both approximate conversions already leave
  * to the noise.  For g = 1, decompose followed by apply_decomposed equals apply word for word (apply IS the two halves on the parts of its scratch).  Adding
- * sigma_g(c0) to out_0 is the caller's step.
+ * sigma_g(c0) to out_0 is agx_ntt_add_galois(plan, out_0, c0, out_0, batch, 0, q_count, g, stream), in place.
  *   hoisted_words : the sizes in words of d_ext, decompose's scratch and apply_decomposed's scratch: the ext, coeff and acc parts of scratch_words.  A NULL
  *                   handle: AGX_ERR_NULL_POINTER; a count past 2^60 words: AGX_ERR_BAD_ARGUMENT; any out-pointer may be NULL.
  *   hoisted_info  : launches_decompose = the inverse on Q + what agx_ntt_basis_info reports for every ModUp basis; launches_apply_decomposed = 1 + 2 x what

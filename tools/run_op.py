@@ -5,6 +5,7 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op extend --src S [--dst T --only {both,fused,pair} --reps 5 ...]   (agx_ntt_basis_extend to NTT form beside the unfused pair)
        python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent} --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
+       python3 tools/run_op.py --op ring --kind {add,sub,negate,add_galois,tensor} [--primes 6 --first 0 --count 4 --galois G --only {all,ring,copy,parent} --reps 7 ...]   (a ring call beside a copy of its model bytes and what it replaces)
        python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
        python3 tools/run_op.py --op hoist --qcount Q --rotations R [R ...] [--galois G --pfirst F --pcount K --alpha A --reps 7 ...]   (hoisted rotations: agx_ntt_inner_product_galois
                                                                    beside the plain kernel and automorphism + inner product; decompose + R apply_decomposed beside R automorphism + apply)
@@ -22,7 +23,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "inner", "keyswitch", "hoist"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "inner", "keyswitch", "hoist", "ring"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -42,12 +43,15 @@ ap.add_argument("--odd", action="store_true", help="auto: both bases one word pa
 ap.add_argument("--reps", type=int, default=5, help="auto: timed repetitions of --launches calls each, alternating with the copy; medians are reported")
 ap.add_argument("--src", type=int, default=2, help="extend: source primes [0, S)")
 ap.add_argument("--dst", type=int, default=0, help="extend: target primes [0, T); 0 = every prime of the plan")
-ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "inner", "copy"], default=None,
+ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "inner", "copy", "ring"], default=None,
                 help="extend: time the AGX_FORM_NTT call (fused), the unfused pair, or both alternating (default); moddown: the two-launch route (fused), the "
                      "four-launch route on the same plan (generic: needs lib/libagxntt_diag.so through AGX_NTT_LIB), inverse + extend as before mod_down existed "
                      "(parent), or all alternating (default).  A counter run wants one")
 ap.add_argument("--terms", type=int, default=2, help="inner: terms of the sum (1 .. 16)")
 ap.add_argument("--outputs", type=int, default=2, help="inner: outputs (1 or 2)")
+ap.add_argument("--kind", choices=["add", "sub", "negate", "add_galois", "tensor"], default="add", help="ring: the call to time")
+ap.add_argument("--first", type=int, default=0, help="ring: the first plan prime of the range")
+ap.add_argument("--count", type=int, default=4, help="ring: primes in the range")
 ap.add_argument("--qcount", type=int, default=4, help="keyswitch: Q = primes [0, qcount)")
 ap.add_argument("--pfirst", type=int, default=None, help="keyswitch: the special primes start here (default: qcount, the top level)")
 ap.add_argument("--pcount", type=int, default=2, help="keyswitch: special primes")
@@ -548,6 +552,92 @@ def run_hoist():
     plan.close()
 
 
+def run_ring():
+    """One ring call (--kind add, sub, negate, add_galois or tensor) on the primes [--first, --first + --count) of a plan of --primes primes, alternating
+    in one process with
+      copy   -- a device-to-device copy that reads and writes, together, the call's model bytes: 24 / 24 / 16 / 24 / 56 per word;
+      parent -- what a caller had before: tensor: four agx_ntt_pointwise launches into four buffers on a second plan over the range's primes (the
+                cross term's add not included); add_galois: agx_ntt_automorphism into a copy on that plan, then a torch add and remainder.
+    Prints us per call (median (min ... max) of --reps groups of --launches calls), the model traffic as GB/s, and the ratios."""
+    import statistics
+
+    kind, first, count = args.kind, args.first, args.count
+    words = count * args.batch * args.n
+    k_in, k_out = (2, 3) if kind == "tensor" else (1, 1)
+    moduli = plan.moduli[first:first + count]
+    qplan = agx.Plan(args.n, moduli)      # only to fill the operands and for the parent's calls, which take all primes of their plan
+    a, b = (torch.empty(k_in * words, dtype=torch.int64, device="cuda") for _ in range(2))
+    for k in range(k_in):
+        qplan.fill_synthetic(a.data_ptr() + 8 * k * words, args.batch, k * args.batch, 42, stream)
+        qplan.fill_synthetic(b.data_ptr() + 8 * k * words, args.batch, (2 + k) * args.batch, 43, stream)
+    c, ref, tmp = (torch.empty(k_out * words, dtype=torch.int64, device="cuda") for _ in range(3))
+    extra = torch.empty(words, dtype=torch.int64, device="cuda")
+    qcol = torch.tensor(moduli, dtype=torch.int64, device="cuda")[:, None]
+    g = args.galois % (2 * args.n)
+    model = 8.0 * words * {"add": 3, "sub": 3, "negate": 2, "add_galois": 3, "tensor": 7}[kind]
+    half = int(model // 16)
+    src, dst = (torch.empty(half, dtype=torch.int64, device="cuda") for _ in range(2))
+    src.zero_()
+    pa, pb, pc = a.data_ptr(), b.data_ptr(), c.data_ptr()
+
+    def ring():
+        if kind == "add":
+            plan.add(pa, pb, pc, args.batch, first, count, stream)
+        elif kind == "sub":
+            plan.sub(pa, pb, pc, args.batch, first, count, stream)
+        elif kind == "negate":
+            plan.negate(pa, pc, args.batch, first, count, stream)
+        elif kind == "add_galois":
+            plan.add_galois(pa, pb, pc, args.batch, g, first, count, stream)
+        else:
+            plan.tensor(pa, pb, pc, args.batch, first, count, stream)
+
+    def copy():
+        dst.copy_(src)
+
+    def parent():
+        if kind == "tensor":      # c_0, the two halves of c_1, c_2
+            for i, (x, y, out) in enumerate(((0, 0, ref), (0, 1, tmp), (1, 0, extra), (1, 1, ref))):
+                qplan.pointwise(pa + 8 * x * words, pb + 8 * y * words, out.data_ptr() + (16 * words if i == 3 else 0), args.batch, stream)
+        else:
+            qplan.automorphism(pb, tmp.data_ptr(), args.batch, g, agx.FORM_NTT, stream)
+            torch.add(a, tmp, out=ref)
+            ref.view(count, -1).remainder_(qcol)
+
+    todo = [ring, copy] + ([parent] if kind in ("tensor", "add_galois") else [])
+    ring()
+    torch.cuda.synchronize()
+    av, bv = a.view(k_in, count, -1), b.view(k_in, count, -1)
+    if kind == "tensor":
+        parent()
+        torch.cuda.synchronize()
+        cv, rv = c.view(3, count, -1), ref.view(3, count, -1)
+        assert torch.equal(cv[0], rv[0]) and torch.equal(cv[2], rv[2]), "c_0 or c_2 differs from agx_ntt_pointwise"
+        assert torch.equal(cv[1], (tmp[:words].view(count, -1) + extra.view(count, -1)) % qcol), "c_1 differs from the sum of the two pointwise products"
+    elif kind == "add_galois":
+        parent()
+        torch.cuda.synchronize()
+        assert torch.equal(c, ref), "the one call and automorphism-plus-add differ"
+    else:
+        want = {"add": (av[0] + bv[0]) % qcol, "sub": (av[0] - bv[0]) % qcol, "negate": (-av[0]) % qcol}[kind]
+        assert torch.equal(c.view(count, -1), want), "the call's words differ from torch's"
+    times = _alternate([f for f in todo if args.only in ("all", "both", f.__name__)])
+    med = {k: statistics.median(v) for k, v in times.items()}
+    head = f"ring {kind} n={args.n} P={args.primes} range=({first}, {count}) batch={args.batch} bits={args.bits}" + (f" g={g}" if kind == "add_galois" else "") + ":"
+    parts = [f"{k} {_fmt(v)} us" + (f", {model / med[k] / 1e3:.0f} GB/s of model traffic" if k != "parent" else "") for k, v in times.items()]
+    parts += [f"ratio ring/{o} {med['ring'] / med[o]:.3f}" for o in ("copy", "parent") if "ring" in med and o in med]
+    print(head, "; ".join(parts))
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "model_bytes": model}, open(args.report, "w"))
+    qplan.close()
+    plan.close()
+
+
+if args.op == "ring":
+    run_ring()
+    sys.exit(0)
 if args.op == "inner":
     run_inner()
     sys.exit(0)
