@@ -625,6 +625,10 @@ REGISTRY = [
     (215, 32, 60), (220, 512, 60), (221, 512, 60), (222, 256, 60), (224, 32, 60), (235, 32, 30), (236, 512, 30),
 ]
 
+# the product entry that admits only moduli 2^60 - c, 0 < c < 2^28 (arithmetic level 3): the forward companion of such plans at n = 4096.  It stands
+# apart from REGISTRY, every entry of which the id-parametrised tests select under its widest modulus and under a 30-bit one
+Q60C_REGISTRY = [(165, 4096, 60)]
+
 # the product library's registry entries that carry launch_rescale (the A/B twins 70, 114, 115, 147, 160, 161, 221 carry it too; they
 # live in the diagnostics library only)
 RESCALE_IDS = [91, 92, 93, 150, 151, 152, 153, 154, 155, 156, 157, 158, 117, 120, 122, 119, 121, 123]

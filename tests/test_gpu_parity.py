@@ -8,7 +8,9 @@ import pytest
 
 from gpu_util import PRODUCT_IDS, REGISTRY, capture, oracle_forward_rns, rand_coeffs, select_entry, tables_for
 from gpu_util import oracle_polymul as _oracle_polymul
+from gpu_util import plan_for_moduli as _plan_for_moduli
 from gpu_util import plan_from_oracle_tables as _plan_from_oracle_tables
+from modulus_cases import prime_above, prime_below
 
 pytestmark = pytest.mark.gpu
 
@@ -223,13 +225,15 @@ def test_n4096_kernel_registry_variants(agx, orc, dev, bits, config):
 @pytest.mark.parametrize("n,bits,config", [(4096, 60, None), (4096, 61, None), (4096, 62, None), (4096, 60, 93), (4096, 59, 93), (4096, 58, 93), (4096, 45, 93),
                                            (16384, 60, 117), (16384, 59, 117), (16384, 58, 117), (16384, 45, 117), (16384, 61, None), (16384, 62, None),
                                            (32768, 60, 119), (32768, 59, 119), (32768, 58, 119), (32768, 45, 119), (32768, 61, None), (32768, 62, None),
-                                           (1024, 60, None), (2048, 60, None), (8192, 60, None)])
+                                           (1024, 60, None), (2048, 60, None), (8192, 60, None),
+                                           (4096, "above58", 93), (16384, "above58", 117), (32768, "above58", 119)])
 def test_extreme_coefficients(agx, orc, dev, n, bits, config):
     """worst-case lazy ranges: all coefficients 4q-1 / q-1 / 0 under the largest 60-, 61- and
     62-bit moduli (16q-lazy, fast and exact forms respectively); configs 93 / 117 / 119 = the kernels with the tail-free schedule
     whose outputs reach 16q before the quotient-estimate reduction (n = 4096, 16384, 32768), at 60/59-bit moduli (estimate path;
-    59 bits = the smallest top words it sees), at 58 and 45 bits (q < 2^58: the four-step fallback)"""
-    q = orc.find_prime(bits, n)
+    59 bits = the largest prime below 2^59), at the first prime above 2^58 ("above58": the smallest modulus that takes the estimate,
+    so the smallest top words it sees), at 58 and 45 bits (q < 2^58: the four-step fallback)"""
+    q = prime_above(orc, 1 << 58, n) if bits == "above58" else orc.find_prime(bits, n)
     psi = orc.min_root(q, n)
     tw, pre = orc.make_tables(q, psi, n)
     plan = agx.Plan(n, [q], psi=[psi])
@@ -1199,16 +1203,21 @@ def test_harness_binary_passes(agx):
 
 def test_randomised_shapes_against_oracle(agx, orc, dev):
     """40 random (n, modulus size, primes, batch, in/out of place, lazy) forward + inverse cases:
-    every size class, every arithmetic form, ragged batches"""
+    every size class, every arithmetic form, ragged batches.  The modulus width is uniform over n.bit_length() + 2 ... 62 bits, and the
+    moduli are the primes next to either end of that width by a coin: the largest below 2^bits or the smallest above 2^(bits-1) (the
+    latter also where fewer than `primes` admitted primes lie below 2^bits)"""
     rng = np.random.default_rng(20261004)
     for case in range(40):
         n = 1 << int(rng.integers(1, 16))
-        bits = int(rng.choice([max(20, n.bit_length() + 2), 30, 45, 59, 60, 61, 62]))
-        if bits <= n.bit_length() + 1:
-            bits = n.bit_length() + 4
+        bits = int(rng.integers(n.bit_length() + 2, 63))
+        top = bool(rng.integers(0, 2))
         primes = int(rng.integers(1, 4)) if n <= 8192 else 1
         batch = int(rng.integers(1, 8)) if n <= 8192 else int(rng.integers(1, 3))
-        plan, tabs = _plan_from_oracle_tables(agx, orc, n, bits, primes)
+        try:
+            moduli = tuple(prime_below(orc, 1 << bits, n, k) if top else prime_above(orc, 1 << (bits - 1), n, k) for k in range(primes))
+        except ValueError:
+            moduli = tuple(prime_above(orc, 1 << (bits - 1), n, k) for k in range(primes))
+        plan, tabs = _plan_for_moduli(agx, orc, n, moduli)
         x = np.concatenate([rand_coeffs(rng, batch * n, t[0], hi_mult=int(rng.integers(1, 5))) for t in tabs])
         d_x = dev.to_device(x)
         in_place = bool(rng.integers(0, 2))
