@@ -69,6 +69,7 @@ ABI = {
     "agx_ntt_negate": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _vp]),
     "agx_ntt_add_galois": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp]),
     "agx_ntt_tensor": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp]),
+    "agx_ntt_mul_add_galois": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _u32, _u32, _u32, _int, _vp]),
     "agx_ntt_keyswitch_create": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32]),
     "agx_ntt_keyswitch_destroy": (_int, [_vp]),
     "agx_ntt_keyswitch_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_int)]),
@@ -78,6 +79,8 @@ ABI = {
     "agx_ntt_keyswitch_decompose": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_keyswitch_apply_decomposed": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp]),
     "agx_ntt_keyswitch_hoisted_info": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "agx_ntt_keyswitch_accumulate_decomposed": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _int, _vp]),
+    "agx_ntt_keyswitch_mod_down": (_int, [_vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
@@ -194,7 +197,7 @@ def kernel_source_sha16():
     import hashlib
 
     h = hashlib.sha256()
-    files = glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + [os.path.join(_HERE, "csrc", f) for f in ("rb_frame.hpp", "rb_kernels.hpp", "rb32_kernels.hpp", "wp_kernels.hpp", "rb_stream_opts.hpp", "rb_registry.hpp", "modarith.hpp", "inner_reduce.hpp", "ring_arith.hpp", "ring_kernels.hpp", "ntt_kernels.hpp")]
+    files = glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + [os.path.join(_HERE, "csrc", f) for f in ("rb_frame.hpp", "rb_kernels.hpp", "rb32_kernels.hpp", "wp_kernels.hpp", "rb_stream_opts.hpp", "rb_registry.hpp", "modarith.hpp", "inner_reduce.hpp", "ring_arith.hpp", "ring_kernels.hpp", "weighted_arith.hpp", "weighted_kernels.hpp", "ntt_kernels.hpp")]
     for f in sorted(files):
         h.update(os.path.relpath(f, _HERE).encode())
         h.update(open(f, "rb").read())
@@ -384,6 +387,13 @@ class Plan:
         [3][prime_count][batch][n], out of place (d_a may be d_b)"""
         _check(lib().agx_ntt_tensor(self._h, d_a, d_b, d_c, batch, *self._prime_range(prime_first, prime_count), stream), "tensor")
 
+    def mul_add_galois(self, d_w, d_b, d_c, batch, galois_elt=1, w_batch=None, accumulate=False, prime_first=0, prime_count=None, stream=0):
+        """c[i] = (c[i] if accumulate) + w[i] o b[pi_g(i)] mod q within every frame, one launch: d_w [prime_count][w_batch][n] (w_batch: None = batch, or 1:
+        one frame per prime for the whole batch), d_b and d_c [prime_count][batch][n]; galois_elt = 1 without accumulate is the ranged plaintext product,
+        where d_c may be d_b; otherwise d_c touches neither"""
+        _check(lib().agx_ntt_mul_add_galois(self._h, d_w, batch if w_batch is None else w_batch, d_b, d_c, batch, *self._prime_range(prime_first, prime_count),
+                                            galois_elt, int(accumulate), stream), "mul_add_galois")
+
     def keyswitch(self, q_count, p_first, p_count, alpha):
         """KeySwitch(self, ...): the hybrid key switch at level Q = primes [0, q_count) with special primes [p_first, p_first + p_count)"""
         return KeySwitch(self, q_count, p_first, p_count, alpha)
@@ -510,6 +520,19 @@ class KeySwitch:
         """the other half, with d_ext (unchanged) read through X -> X^galois_elt: key-switches sigma_g(c) with d_keyhat, a key for sigma_g(s) -> s,
         into d_out [2][q_count][batch][n]; d_scratch: 2*A*batch*n words; galois_elt = 1 after decompose is apply word for word"""
         _check(lib().agx_ntt_keyswitch_apply_decomposed(self._h, d_ext, d_keyhat, d_out, d_scratch, batch, galois_elt, stream), "keyswitch_apply_decomposed")
+
+    def accumulate_decomposed(self, d_ext, d_keyhat, d_acc, batch, galois_elt, d_weight=None, weight_batch=None, accumulate=False, stream=0):
+        """the inner-product half of apply_decomposed alone, weighted and accumulating: d_acc [2][A][batch][n] (hoisted_words' apply scratch) = (d_acc if
+        accumulate) + d_weight o sum_d pi_g(ext_d) o key_{d,o}, one launch, fully reduced; d_weight [A][weight_batch][n] (weight_batch: None = batch, or 1:
+        one frame per prime), None: w = 1.  A sum of rotations is formed here and brought down once by mod_down"""
+        wb = 0 if d_weight is None else batch if weight_batch is None else weight_batch
+        _check(lib().agx_ntt_keyswitch_accumulate_decomposed(self._h, d_ext, d_keyhat, d_weight, wb, d_acc, batch, galois_elt, int(accumulate), stream),
+               "keyswitch_accumulate_decomposed")
+
+    def mod_down(self, d_acc, d_out, batch, stream=0):
+        """the ModDown half of apply_decomposed alone: d_out [2][q_count][batch][n] <- d_acc [2][A][batch][n] divided by the special primes; the special
+        slabs of d_acc are its scratch and overwritten"""
+        _check(lib().agx_ntt_keyswitch_mod_down(self._h, d_acc, d_out, batch, stream), "keyswitch_mod_down")
 
     def hoisted_info(self):
         """(launches_decompose, launches_apply_decomposed) under the plan's current variant; their sum is info()'s launches"""

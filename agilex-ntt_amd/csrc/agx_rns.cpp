@@ -1,5 +1,6 @@
 // agx_rns.cpp -- the RNS calls of include/agx_ntt.h: rescale, basis extension and ModDown, the inner products, the ring arithmetic on a range of the
-// plan's primes (add, sub, negate, add_galois, tensor: one streaming kernel each) and the key switch.  Each of the others composes the
+// plan's primes (add, sub, negate, add_galois, tensor, mul_add_galois: one streaming kernel each) and the key switch, whole, in two halves, and with its
+// second half in two (accumulate_decomposed: the weighted, accumulating inner product; keyswitch_mod_down).  Each of the others composes the
 // plan's transforms (run_forward / run_inverse on views of its routes, plan_internal.hpp) with a coefficient-domain or fused kernel; plans, routes and
 // the transform calls themselves live in agx_ntt.cpp.
 #include <cstdlib>
@@ -289,6 +290,28 @@ int agx_ntt_tensor(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t
     return ring_call(kRingTensor, plan, d_a, d_b, d_c, batch, prime_first, prime_count, 1, stream);
 }
 
+// c (+)= w o pi_g(b): the ring calls' rules in their order, the w_batch and accumulate rules beside the range rule.  c touches w nowhere; it touches b
+// nowhere either, b being gathered across the frame -- with g = 1 it may be exactly b (every work item reads its own word first).  w and b are only read.
+int agx_ntt_mul_add_galois(const agx_ntt_plan* plan, const uint64_t* d_w, uint64_t w_batch, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first,
+                           uint32_t prime_count, uint32_t galois_elt, int accumulate, void* stream) {
+    if (!plan || !d_w || !d_b || !d_c) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes, n = plan->n;
+    if (prime_count == 0 || prime_count > P || prime_first > P - prime_count) return AGX_ERR_BAD_ARGUMENT;
+    if ((w_batch != batch && w_batch != 1) || (accumulate != 0 && accumulate != 1)) return AGX_ERR_BAD_ARGUMENT;
+    if (!aligned8(d_w) || !aligned8(d_b) || !aligned8(d_c)) return AGX_ERR_BAD_ARGUMENT;
+    if (!batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;      // from here on batch n < 2^46
+    if (!dense_fits(n, prime_count, batch) || !dense_fits(n, prime_count, w_batch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t words = prime_count * batch * n, w_words = prime_count * w_batch * n;      // each <= 2^60
+    if (ranges_touch(addr(d_c), words, addr(d_w), w_words)) return AGX_ERR_BAD_ARGUMENT;
+    if (!(galois_elt == 1 && d_b == d_c) && ranges_touch(addr(d_c), words, addr(d_b), words)) return AGX_ERR_BAD_ARGUMENT;
+    if (!galois_ok(galois_elt, n)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (batch == 0) return AGX_OK;
+    AGX_HIP(launch_ring_mul_add_galois(plan->routes.forward, prime_first, prime_count, d_w, w_batch, d_b, d_c, batch, galois_elt, accumulate != 0,
+                                       static_cast<hipStream_t>(stream)));
+    return AGX_OK;
+}
+
 int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha) {
     if (!ks) return AGX_ERR_NULL_POINTER;
     *ks = nullptr;
@@ -403,22 +426,36 @@ static int keyswitch_decompose_steps(const agx_ntt_keyswitch* ks, const uint64_t
     return AGX_OK;
 }
 
-// Steps 3 and 4, every argument checked by the caller: acc [2][A][batch][n] <- sum_d pi_g(ext_d) o key_{d,o}, out [2][Q][batch][n] <- ModDown of each half
-static int keyswitch_apply_steps(const agx_ntt_keyswitch* ks, const uint64_t* ext, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* acc, uint64_t batch,
-                                 uint32_t galois_elt, void* stream) {
+// Step 3, every argument checked by the caller: acc_o [A][batch][n] <- (accumulate ? acc_o : 0) + weight o sum_d pi_g(ext_d) o key_{d,o} over the active
+// primes: one launch, the key broadcast over the batch; g = 1 is the un-gathered kernel.  Without a weight and an old acc it is the inner product itself,
+// and launches that kernel: what apply and apply_decomposed run is what they ran before this step had a weight.
+static int keyswitch_accumulate_step(const agx_ntt_keyswitch* ks, const uint64_t* ext, const uint64_t* d_keyhat, const uint64_t* weight, uint64_t weight_batch,
+                                     uint64_t* acc, uint64_t batch, uint32_t galois_elt, bool accumulate, void* stream) {
     const agx_ntt_plan* plan = ks->plan;
     const keyswitch_shape& k = ks->shape;
-    const uint32_t Q = k.q_count, A = k.active();
-    const uint64_t slab = batch * plan->n;
-    // (3) acc_o <- sum_d pi_g(ext_d) o key_{d,o} over the active primes: one launch, the key broadcast over the batch; g = 1 is the un-gathered kernel
-    AGX_HIP(launch_inner_product_galois(plan->routes.forward, inner_primes{A, Q, k.p_first - Q}, ext, d_keyhat, acc, batch, 1, k.digits(), 2, galois_elt,
-                                        static_cast<hipStream_t>(stream)));
-    // (4) out_o <- ModDown of acc_o, its special slabs given up as the scratch
+    const inner_primes active{k.active(), k.q_count, k.p_first - k.q_count};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!weight && !accumulate) AGX_HIP(launch_inner_product_galois(plan->routes.forward, active, ext, d_keyhat, acc, batch, 1, k.digits(), 2, galois_elt, s));
+    else AGX_HIP(launch_inner_weighted(plan->routes.forward, active, ext, d_keyhat, weight, weight_batch, acc, batch, k.digits(), galois_elt, accumulate, s));
+    return AGX_OK;
+}
+
+// Step 4, every argument checked by the caller: out_o [Q][batch][n] <- ModDown of acc_o, its special slabs given up as the scratch
+static int keyswitch_mod_down_step(const agx_ntt_keyswitch* ks, uint64_t* acc, uint64_t* d_out, uint64_t batch, void* stream) {
+    const uint32_t Q = ks->shape.q_count, A = ks->shape.active();
+    const uint64_t slab = batch * ks->plan->n;
     for (uint32_t o = 0; o < 2; ++o) {
         uint64_t* xq = acc + (uint64_t)o * A * slab;
         if (int rc = agx_ntt_basis_mod_down(ks->down, xq, xq + Q * slab, d_out + o * Q * slab, xq + Q * slab, batch, stream)) return rc;
     }
     return AGX_OK;
+}
+
+// Steps 3 and 4: the two halves with no weight and nothing accumulated
+static int keyswitch_apply_steps(const agx_ntt_keyswitch* ks, const uint64_t* ext, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* acc, uint64_t batch,
+                                 uint32_t galois_elt, void* stream) {
+    if (int rc = keyswitch_accumulate_step(ks, ext, d_keyhat, nullptr, 0, acc, batch, galois_elt, false, stream)) return rc;
+    return keyswitch_mod_down_step(ks, acc, d_out, batch, stream);
 }
 
 // the rules the key-switch calls share, after the NULL rule and the 2^60 limits: alignment, the two grid limits, and no two of the call's `count` buffers touching
@@ -462,6 +499,41 @@ int agx_ntt_keyswitch_apply_decomposed(const agx_ntt_keyswitch* ks, const uint64
     if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;      // ModDown runs the plan's inverse
     if (batch == 0) return AGX_OK;
     return keyswitch_apply_steps(ks, d_ext, d_keyhat, d_out, d_scratch, batch, galois_elt, stream);
+}
+
+// Step 3 alone, weighted and accumulating: apply_decomposed's rules in its order, the weight one more buffer of the overlap rule, the weight_batch and
+// accumulate rules in front of it.  It runs no inverse: a forward-only plan serves.
+int agx_ntt_keyswitch_accumulate_decomposed(const agx_ntt_keyswitch* ks, const uint64_t* d_ext, const uint64_t* d_keyhat, const uint64_t* d_weight, uint64_t weight_batch,
+                                            uint64_t* d_acc, uint64_t batch, uint32_t galois_elt, int accumulate, void* stream) {
+    if (!ks || !d_ext || !d_keyhat || !d_acc) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = ks->plan;
+    const keyswitch_shape& k = ks->shape;
+    keyswitch_hoisted part;
+    if (!keyswitch_hoisted_partition(k, plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;
+    if ((d_weight && weight_batch != batch && weight_batch != 1) || (accumulate != 0 && accumulate != 1)) return AGX_ERR_BAD_ARGUMENT;
+    // the weight's extent is half of acc's or smaller; without a weight it is an empty range, which touches nothing and is aligned
+    const uintptr_t base[4] = {addr(d_ext), addr(d_keyhat), addr(d_acc), addr(d_weight)};
+    const uint64_t words[4] = {part.ext, (uint64_t)k.digits() * 2 * k.active() * plan->n, part.apply_scratch, d_weight ? k.active() * weight_batch * plan->n : 0};
+    if (!keyswitch_buffers_ok(ks, batch, base, words, 4)) return AGX_ERR_BAD_ARGUMENT;
+    if (!galois_ok(galois_elt, plan->n)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (batch == 0) return AGX_OK;
+    return keyswitch_accumulate_step(ks, d_ext, d_keyhat, d_weight, weight_batch, d_acc, batch, galois_elt, accumulate != 0, stream);
+}
+
+// Step 4 alone: apply_decomposed's rules without the key and the Galois element
+int agx_ntt_keyswitch_mod_down(const agx_ntt_keyswitch* ks, uint64_t* d_acc, uint64_t* d_out, uint64_t batch, void* stream) {
+    if (!ks || !d_acc || !d_out) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = ks->plan;
+    keyswitch_hoisted part;
+    if (!keyswitch_hoisted_partition(ks->shape, plan->n, batch, &part)) return AGX_ERR_BAD_ARGUMENT;
+    const uintptr_t base[2] = {addr(d_acc), addr(d_out)};
+    const uint64_t words[2] = {part.apply_scratch, 2 * part.decompose_scratch};
+    if (!keyswitch_buffers_ok(ks, batch, base, words, 2)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;      // ModDown runs the plan's inverse
+    if (batch == 0) return AGX_OK;
+    return keyswitch_mod_down_step(ks, d_acc, d_out, batch, stream);
 }
 
 int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream) {

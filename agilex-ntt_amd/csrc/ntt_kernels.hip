@@ -326,6 +326,7 @@ __global__ void inner_product_galois_kernel(const W* __restrict__ a, const W* __
 }  // namespace agx
 
 #include "ring_kernels.hpp"      // agx_ntt_add / _sub / _negate / _add_galois / _tensor: behind inner_gather and galois_read_index, which it reuses
+#include "weighted_kernels.hpp"  // agx_ntt_keyswitch_accumulate_decomposed / agx_ntt_mul_add_galois: behind inner_args, inner_lanes and the ring arithmetic
 
 namespace agx {
 
@@ -721,6 +722,44 @@ hipError_t launch_ring_tensor(const plan_view& pv, uint32_t first, uint32_t coun
     const ring_tensor_args g{per_prime, count * per_prime, first};
     if (pairs) return launch_ring(&ring_tensor_kernel<ulonglong2>, pv, count, per_prime, a, b, c, g, s);
     return launch_ring(&ring_tensor_kernel<uint64_t>, pv, count, per_prime, a, b, c, g, s);
+}
+
+// The weighted, accumulating inner product of a key switch (two outputs, the key one frame per prime): one launch of inner_weighted_kernel; g = 1 takes
+// its un-gathered instance.  The 16-byte form serves when ext, the key, acc and (where there is one) the weight are all 16-byte aligned.
+hipError_t launch_inner_weighted(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, const uint64_t* weight, uint64_t weight_batch,
+                                 uint64_t* acc, uint64_t batch, uint32_t terms, uint32_t galois_elt, bool accumulate, hipStream_t s) {
+    const uint64_t* wt = weight ? weight : a;      // no weight: never read; a valid base keeps the slot arithmetic defined
+    const bool pairs = inner_pairs(a, bhat, acc) && inner_pairs(wt, wt, wt);
+    const uint32_t shift = pairs ? 1 : 0;
+    weighted_args g;
+    g.in = inner_args_of(pv, ip, batch, 1, terms, 2, pairs);
+    g.w_prime = weight ? (weight_batch << pv.log_n) >> shift : 0;
+    g.log_n = pv.log_n, g.g = galois_elt;
+    g.has_weight = weight ? 1u : 0u, g.w_broadcast = weight_batch == 1 ? 1u : 0u, g.accumulate = accumulate ? 1u : 0u;
+    const dim3 grid(grid_1d(g.in.per_prime, 256), ip.count);
+    auto go = [&](auto kernel, auto* ap, auto* bp, auto* wp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, wp, cp, pv.consts, g); };
+    if (pairs) {
+        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2*>(a), *b2 = reinterpret_cast<const ulonglong2*>(bhat), *w2 = reinterpret_cast<const ulonglong2*>(wt);
+        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(acc);
+        if (galois_elt == 1) go(&inner_weighted_kernel<false, ulonglong2>, a2, b2, w2, c2);
+        else go(&inner_weighted_kernel<true, ulonglong2>, a2, b2, w2, c2);
+    } else {
+        if (galois_elt == 1) go(&inner_weighted_kernel<false, uint64_t>, a, bhat, wt, acc);
+        else go(&inner_weighted_kernel<true, uint64_t>, a, bhat, wt, acc);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_ring_mul_add_galois(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* w, uint64_t w_batch, const uint64_t* b, uint64_t* c,
+                                      uint64_t batch, uint32_t galois_elt, bool accumulate, hipStream_t s) {
+    const bool pairs = inner_pairs(w, b, c);
+    const uint32_t shift = pairs ? 1 : 0;
+    const mul_add_args g{ring_args{(batch << pv.log_n) >> shift, first}, (w_batch << pv.log_n) >> shift, (pv.n >> shift) - 1u, pv.log_n, galois_elt,
+                         w_batch == 1 ? 1u : 0u, accumulate ? 1u : 0u};
+    if (pairs) return galois_elt == 1 ? launch_ring(&ring_mul_add_kernel<false, ulonglong2>, pv, count, g.in.per_prime, w, b, c, g, s)
+                                      : launch_ring(&ring_mul_add_kernel<true, ulonglong2>, pv, count, g.in.per_prime, w, b, c, g, s);
+    return galois_elt == 1 ? launch_ring(&ring_mul_add_kernel<false, uint64_t>, pv, count, g.in.per_prime, w, b, c, g, s)
+                           : launch_ring(&ring_mul_add_kernel<true, uint64_t>, pv, count, g.in.per_prime, w, b, c, g, s);
 }
 
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s) {

@@ -107,6 +107,14 @@ hipError_t launch_ring_negate(const plan_view& pv, uint32_t first, uint32_t coun
 hipError_t launch_ring_add_galois(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch,
                                   uint32_t galois_elt, hipStream_t s);
 hipError_t launch_ring_tensor(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
+// agx_ntt_mul_add_galois: c[i] = (accumulate ? c[i] : 0) + w[i] o b[pi_g(i)] over the same range; w is [count][w_batch][n], w_batch = batch or 1 (one
+// frame per prime for every frame of the batch).  One launch; g = 1 takes the un-gathered instance.
+hipError_t launch_ring_mul_add_galois(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* w, uint64_t w_batch, const uint64_t* b, uint64_t* c,
+                                      uint64_t batch, uint32_t galois_elt, bool accumulate, hipStream_t s);
+// agx_ntt_keyswitch_accumulate_decomposed: launch_inner_product_galois with two outputs and a broadcast key, then acc_o = (accumulate ? acc_o : 0) +
+// weight o (the sum) per word; weight [ip.count][weight_batch][n] or nullptr (w = 1).  One launch; g = 1 takes the un-gathered instance.
+hipError_t launch_inner_weighted(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, const uint64_t* weight, uint64_t weight_batch,
+                                 uint64_t* acc, uint64_t batch, uint32_t terms, uint32_t galois_elt, bool accumulate, hipStream_t s);
 // the coefficient-domain step of agx_ntt_rescale's generic route: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i on the dense [prime][batch][n]
 // layout of pv's primes (a view of primes 0 .. P-2), u_i the lift of t[k] ([batch][n], coefficients of the last slab in [0, q_L)) to q_i
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s);

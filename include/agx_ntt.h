@@ -383,6 +383,28 @@ AGX_API int agx_ntt_add_galois(const agx_ntt_plan* plan, const uint64_t* d_a, co
 AGX_API int agx_ntt_tensor(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, uint32_t prime_first,
                            uint32_t prime_count, void* stream);
 
+/* Multiply-accumulate on a range of the plan's primes with a broadcast operand, read through a Galois automorphism: the plaintext x ciphertext product at a
+ * level, and the way the sigma_g(c0) terms and an unrotated diagonal join a linear transform's sum (agx_ntt_keyswitch_accumulate_decomposed below).  The range
+ * and the operands are the ring calls' above: d_b and d_c are [prime_count][batch][n]; d_w is [prime_count][w_batch][n] with w_batch = batch or 1 (1: one
+ * frame per prime for every frame of the batch).  Per word, with x' = x mod q_p and pi_g as for add_galois:
+ *   c[p][f][i] = ((accumulate ? c[p][f][i]' : 0) + w[p][f or 0][i]' b[p][f][pi_g(i)]') mod q_p
+ * Inputs (the old words of c included) may be lazy, below 4 q_p; the output is fully reduced and exact: w' b' + c' < 2^124 + 2^62 is kept in 128 bits and
+ * reduced once.  accumulate is 0 or 1.  With galois_elt = 1 and accumulate = 0 this is the ranged plaintext product; with w_batch == batch over the whole
+ * plan it equals agx_ntt_pointwise word for word; with w all ones it is agx_ntt_automorphism(AGX_FORM_NTT, g) reduced (accumulate = 0) or agx_ntt_add_galois
+ * (accumulate = 1).
+ * Aliasing.  d_c touches d_w nowhere.  d_c touches d_b nowhere, except that with galois_elt = 1 it may be exactly d_b (the in-place plaintext multiply).
+ * d_w and d_b may overlap freely (both are only read).  Ranges that meet end to end do not touch.
+ * Status order, agx_ntt_add_galois's: a NULL plan or pointer: AGX_ERR_NULL_POINTER; prime_count == 0 or a range past P, w_batch neither batch nor 1, accumulate
+ * neither 0 nor 1; a pointer not 8-byte aligned; a batch past the grid limit; an operand's extent past 2^60 words; the aliasing rules above; galois_elt even, 0
+ * or >= 2n; the plan's device not current: AGX_ERR_BAD_ARGUMENT, nothing written; batch == 0: AGX_OK, nothing launched.
+ * Asynchronous on `stream`; allocates nothing, synchronises nothing, touches no plan state (capturable into a hipGraph).  ONE launch on every plan: a
+ * grid-stride streaming kernel, no LDS, no barrier, no table; 16-byte accesses when all three bases are 16-byte aligned; galois_elt = 1 takes an un-gathered
+ * kernel.  It moves 16 bytes per word of a frame, 8 more with accumulate = 1 and 8 more with w_batch == batch.
+ * Measured: not measured yet on its own; within a linear transform, see agx_ntt_keyswitch_accumulate_decomposed (profiles/r13_double_hoisting.md).
+ * Groups: no group form, as for the other RNS calls. */
+AGX_API int agx_ntt_mul_add_galois(const agx_ntt_plan* plan, const uint64_t* d_w, uint64_t w_batch, const uint64_t* d_b, uint64_t* d_c, uint64_t batch,
+                                   uint32_t prime_first, uint32_t prime_count, uint32_t galois_elt, int accumulate, void* stream);
+
 /* The RNS hybrid key switch of one ciphertext component in one call: NTT form in, NTT form out, at any level.
  * Primes.  Q, the ciphertext's current level, is the plan's primes [0, q_count).  The special primes are [p_first, p_first + p_count), p_first >= q_count:
  * they need not follow Q directly, which is what a level below the top looks like.  The ACTIVE primes are Q followed by the special primes, A = q_count +
@@ -458,6 +480,47 @@ AGX_API int agx_ntt_keyswitch_decompose(const agx_ntt_keyswitch* ks, const uint6
 AGX_API int agx_ntt_keyswitch_apply_decomposed(const agx_ntt_keyswitch* ks, const uint64_t* d_ext, const uint64_t* d_keyhat, uint64_t* d_out,
                                                uint64_t* d_scratch, uint64_t batch, uint32_t galois_elt, void* stream);
 AGX_API int agx_ntt_keyswitch_hoisted_info(const agx_ntt_keyswitch* ks, int* launches_decompose, int* launches_apply_decomposed);
+
+/* apply_decomposed in ITS two halves, for a linear transform out = sum_r w_r o sigma_{g_r}(ct) (matrix-vector products by diagonals, the BSGS inner loop,
+ * CoeffToSlot / SlotToCoeff): ModDown is linear, so the sum over the rotations is formed in the extended basis Q u P and divided by P ONCE ("double hoisting",
+ * Bossuat et al., Eurocrypt 2021):   out_o = ModDown(sum_r w_r o sum_d pi_{g_r}(ext_d) o key_{r,d,o}).   An R-term transform runs one ModDown pair instead of R.
+ *   accumulate_decomposed : step 3 alone, weighted and accumulating.  d_ext [digits][A][batch][n] (const) and d_keyhat [digits][2][A][n] as for apply_decomposed;
+ *                      d_weight [A][weight_batch][n], NTT form under the active primes in that order, words in [0, 4q), weight_batch = batch or 1 (1: one
+ *                      weight frame per prime for every frame of the batch); d_weight == NULL means w = 1, and weight_batch is then ignored; d_acc
+ *                      [2][A][batch][n] (hoisted_words' apply_scratch_words), the output, read when accumulate = 1 (its old words may be lazy, below 4q).
+ *                      Per word, for o = 0, 1, every active slot j with modulus q, every frame f and position i, x' = x mod q:
+ *                        t = (sum_d ext_d[j][f][pi_g(i)]' key_{d,o}[j][i]') mod q          -- the word apply_decomposed forms in its scratch
+ *                        acc_o[j][f][i] = ((accumulate ? acc_o[j][f][i]' : 0) + w[j][f or 0][i]' t) mod q, fully reduced, exact against big integers:
+ *                      w' t + old' < 2^124 + 2^62 is kept in 128 bits and reduced once.  ONE launch on every plan: a streaming kernel, no LDS, no barrier, no
+ *                      table; 16-byte accesses when ext, keyhat, acc and the weight are all 16-byte aligned; galois_elt = 1 takes an un-gathered kernel.  No
+ *                      inverse tables are needed: a forward-only plan serves.  With d_weight == NULL and accumulate = 0 it is step 3 of apply_decomposed word
+ *                      for word (and launches its kernel).
+ *   mod_down         : step 4 alone: for o = 0, 1, agx_ntt_basis_mod_down of acc_o with targets Q and sources the special primes, the special slabs of acc_o
+ *                      its scratch: they are overwritten, its Q slabs are left unchanged.  acc may hold lazy words; d_out [2][q_count][batch][n], fully
+ *                      reduced.  Launches: 2 x what agx_ntt_basis_mod_down_info reports.
+ * accumulate_decomposed(w = NULL, accumulate = 0, g) followed by mod_down IS apply_decomposed(g), word for word.  The weight's first q_count slabs are the
+ * weight under Q, its last p_count the same plaintext under the special primes.  The sigma_g(c0) terms and an unrotated diagonal join the sum through
+ * agx_ntt_mul_add_galois below, after the ModDown ("Linear transforms").
+ * Noise.  sum_r w_r acc_r = P M (mod QP) exactly, and the lifts V_o of the special slabs satisfy V_0 + V_1 s = 0 (mod P) with coefficients below
+ * p_count P (1 + ||s||_1): what the ONE approximate ModDown leaves is at most p_count (1 + ||s||_1) whatever R and the weights are, where a ModDown per
+ * rotation leaves that much multiplied by each weight (tests/test_dhoist_reference.py holds both statements).
+ *   Status order of accumulate_decomposed: a NULL ks, ext, keyhat or acc: AGX_ERR_NULL_POINTER; an extent past 2^60 words; weight_batch neither batch nor 1
+ *   (with a weight) or accumulate neither 0 nor 1; a pointer not 8-byte aligned, a batch past the grid limit or with A batch above 2^31 - 1, any two of ext /
+ *   keyhat / weight / acc touching anywhere (ranges that meet end to end do not touch); galois_elt even, 0 or >= 2n; the plan's device not current:
+ *   AGX_ERR_BAD_ARGUMENT, nothing written; batch == 0: AGX_OK, nothing launched.  Of mod_down: NULL; an extent past 2^60 words; alignment, the two grid
+ *   limits, acc and out touching anywhere; the device: AGX_ERR_BAD_ARGUMENT; a plan without inverse tables: AGX_ERR_NO_INVERSE; batch == 0: AGX_OK.
+ *   Asynchronous on `stream`, allocate and synchronise nothing (capturable into a hipGraph).
+ * Measured (profiles/r13_double_hoisting.md, tools/run_op.py --op dhoist; six 60-bit primes, one-frame weights, g = 5 and its powers; (4, 4, 2, 2) at n = 4096 with 4,096
+ * frames per prime): an R-term transform by the listing of INTEGRATION.md (decompose, R accumulate_decomposed, ONE mod_down, R mul_add_galois) takes 0.99 / 0.68 / 0.61 of
+ * the single-hoisted route's time (decompose, then per rotation apply_decomposed into a temporary and three mul_add_galois) at R = 1 / 4 / 8 -- 14.53 against 23.91 ms at R = 8;
+ * over both shapes and n = 4096 / 16384: 0.987 ... 0.995 at R = 1 (level: the spreads overlap in two of the four rows), 0.659 ... 0.688, 0.582 ... 0.615.  One weighted,
+ * accumulating call takes 1268 us there: 1.29 of a device copy of its model bytes (1.28 ... 1.36 over the four rows) and 1.64 of agx_ntt_inner_product_galois of the same shape
+ * (772 us) -- NOT at the speed of the copy: the weight costs a third product and a second 128-bit reduction per output word, arithmetic and not traffic.  apply and
+ * apply_decomposed beside the parent commit's library in the same session: 3433 against 3444 us and 1998 against 1997 us; the spreads overlap in all sixteen pairs of rows.
+ * Groups: no group form, as for the other RNS calls. */
+AGX_API int agx_ntt_keyswitch_accumulate_decomposed(const agx_ntt_keyswitch* ks, const uint64_t* d_ext, const uint64_t* d_keyhat, const uint64_t* d_weight,
+                                                    uint64_t weight_batch, uint64_t* d_acc, uint64_t batch, uint32_t galois_elt, int accumulate, void* stream);
+AGX_API int agx_ntt_keyswitch_mod_down(const agx_ntt_keyswitch* ks, uint64_t* d_acc, uint64_t* d_out, uint64_t batch, void* stream);
 
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */

@@ -9,6 +9,9 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
        python3 tools/run_op.py --op hoist --qcount Q --rotations R [R ...] [--galois G --pfirst F --pcount K --alpha A --reps 7 ...]   (hoisted rotations: agx_ntt_inner_product_galois
                                                                    beside the plain kernel and automorphism + inner product; decompose + R apply_decomposed beside R automorphism + apply)
+       python3 tools/run_op.py --op dhoist --qcount Q --rotations R [R ...] [--galois G --pfirst F --pcount K --alpha A --reps 7 ...]   (double-hoisted linear transforms:
+                                                                   agx_ntt_keyswitch_accumulate_decomposed beside the gathered inner product and a copy of its model bytes; an R-term
+                                                                   transform with ONE ModDown pair beside apply_decomposed per rotation)
 Under the profiler: rocprofv3 ... -- python3 tools/run_op.py ...   (the interpreter itself after `--`, never this file: an
 `env` shebang hop after the profiler's preload has initialised the GPU is a forbidden exec on this pool)."""
 import argparse
@@ -23,7 +26,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "inner", "keyswitch", "hoist", "ring"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "inner", "keyswitch", "hoist", "dhoist", "ring"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -56,13 +59,13 @@ ap.add_argument("--qcount", type=int, default=4, help="keyswitch: Q = primes [0,
 ap.add_argument("--pfirst", type=int, default=None, help="keyswitch: the special primes start here (default: qcount, the top level)")
 ap.add_argument("--pcount", type=int, default=2, help="keyswitch: special primes")
 ap.add_argument("--alpha", type=int, default=2, help="keyswitch: primes per digit")
-ap.add_argument("--rotations", type=int, nargs="+", default=[8], help="hoist: rotation counts R to time; rotation r uses the element galois^(r + 1) mod 2n")
+ap.add_argument("--rotations", type=int, nargs="+", default=[8], help="hoist, dhoist: rotation counts R to time; rotation r uses the element galois^(r + 1) mod 2n")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
 if args.op == "moddown":
     args.dst = args.dst or 4
     args.primes = args.src + args.dst      # targets [0, T), sources [T, T + S)
-if args.op in ("keyswitch", "hoist"):
+if args.op in ("keyswitch", "hoist", "dhoist"):
     args.pfirst = args.qcount if args.pfirst is None else args.pfirst
     args.primes = args.pfirst + args.pcount
 args.only = args.only or ("all" if args.op == "moddown" else "both")
@@ -552,6 +555,107 @@ def run_hoist():
     plan.close()
 
 
+def run_dhoist():
+    """Double-hoisted linear transforms at the shape (--qcount, --pfirst, --pcount, --alpha), us per call, median (min ... max), the forms of a line alternating:
+      kernel    -- one agx_ntt_keyswitch_accumulate_decomposed with a one-frame weight, accumulating (g = --galois), beside the same call without the
+                   accumulate, beside agx_ntt_inner_product_galois of the same shape (terms = digits, two outputs, broadcast key, over the active primes) and
+                   beside a device copy of the accumulating call's model bytes: 8 (digits + 2 + 2 accumulate) per word of a frame per active prime, plus the
+                   key and the weight once;
+      transform -- for every R of --rotations, out = sum_r w_r o sigma_{g_r}(ct) by two routes on this library, both from chat = c1 and c0:
+                   double: decompose, R accumulate_decomposed, ONE keyswitch_mod_down, R mul_add_galois of c0;
+                   single: decompose, then per rotation apply_decomposed into a temporary and three mul_add_galois (w o tmp_0, w o tmp_1, w o sigma_g(c0))."""
+    import statistics
+
+    Q, pf, pc, alpha, n, B = args.qcount, args.pfirst, args.pcount, args.alpha, args.n, args.batch
+    A, slab = Q + pc, args.batch * args.n
+    g0 = args.galois % (2 * n)
+    act = list(range(Q)) + list(range(pf, pf + pc))
+    psi = [plan.psi(p) for p in range(plan.num_primes)]
+    aplan = agx.Plan(n, [plan.moduli[p] for p in act], psi=[psi[p] for p in act])
+    ks = plan.keyswitch(Q, pf, pc, alpha)
+    D = ks.info()[4]
+    ext_words, ds_words, as_words = ks.hoisted_words(B)
+    R_max = max(args.rotations)
+    chat = torch.empty(plan.num_primes * slab, dtype=torch.int64, device="cuda")      # synthetic residues taken as NTT-form words; slabs [0, Q) are c1, and c0 too
+    plan.fill_synthetic(chat.data_ptr(), B, 0, 42, stream)
+    key = torch.empty(D * 2 * A * n, dtype=torch.int64, device="cuda")      # [digits][2][A][n], one key for every rotation: the time does not depend on its words
+    for k in range(D * 2):
+        aplan.fill_synthetic(key.data_ptr() + 8 * k * A * n, 1, k, 43, stream)
+    weights = torch.empty(R_max * A * n, dtype=torch.int64, device="cuda")      # [R][A][1][n]
+    aplan.fill_synthetic(weights.data_ptr(), 1, 0, 44, stream)
+    for r in range(1, R_max):
+        aplan.fill_synthetic(weights.data_ptr() + 8 * r * A * n, 1, r, 44, stream)
+    w_ptr = [weights.data_ptr() + 8 * r * A * n for r in range(R_max)]
+    ext = torch.empty(ext_words, dtype=torch.int64, device="cuda")
+    dscr, acc, acc2, ascr = (torch.empty(w, dtype=torch.int64, device="cuda") for w in (ds_words, as_words, as_words, as_words))
+    out, out2, tmp = (torch.empty(2 * Q * slab, dtype=torch.int64, device="cuda") for _ in range(3))
+    model = 8.0 * ((D + 2 + 2) * A * slab + D * 2 * A * n + A * n)
+    src, dst = (torch.empty(int(model // 16), dtype=torch.int64, device="cuda") for _ in range(2))
+    src.zero_()
+    acc.zero_()
+    c0 = chat.data_ptr()
+
+    def weighted_acc():
+        ks.accumulate_decomposed(ext.data_ptr(), key.data_ptr(), acc.data_ptr(), B, g0, w_ptr[0], 1, True, stream)
+
+    def weighted():
+        ks.accumulate_decomposed(ext.data_ptr(), key.data_ptr(), acc2.data_ptr(), B, g0, w_ptr[0], 1, False, stream)
+
+    def galois():
+        aplan.inner_product_galois(ext.data_ptr(), key.data_ptr(), acc2.data_ptr(), B, D, g0, 2, 1, stream)
+
+    def copy():
+        dst.copy_(src)
+
+    ks.decompose(chat.data_ptr(), ext.data_ptr(), dscr.data_ptr(), B, stream)
+    # accumulate(no weight, nothing accumulated) + mod_down is apply_decomposed
+    ks.accumulate_decomposed(ext.data_ptr(), key.data_ptr(), acc2.data_ptr(), B, g0, stream=stream)
+    ks.mod_down(acc2.data_ptr(), out.data_ptr(), B, stream)
+    ks.apply_decomposed(ext.data_ptr(), key.data_ptr(), out2.data_ptr(), ascr.data_ptr(), B, g0, stream)
+    torch.cuda.synchronize()
+    assert torch.equal(out, out2), "accumulate_decomposed + keyswitch_mod_down and apply_decomposed differ"
+    head = f"dhoist n={n} shape=({Q}, {pf}, {pc}, {alpha}) batch={B} bits={args.bits} g={g0}"
+    report = {}
+    t = _alternate([weighted_acc, weighted, galois, copy])
+    report.update(t)
+    med = {k: statistics.median(v) for k, v in t.items()}
+    print(f"{head} kernel (terms={D}, A={A}, model {model / 1e6:.1f} MB): weighted+accumulate {_fmt(t['weighted_acc'])} us; weighted {_fmt(t['weighted'])} us; "
+          f"galois {_fmt(t['galois'])} us; copy {_fmt(t['copy'])} us; ratio weighted_acc/copy {med['weighted_acc'] / med['copy']:.3f}; "
+          f"weighted_acc/galois {med['weighted_acc'] / med['galois']:.3f}; weighted/galois {med['weighted'] / med['galois']:.3f}")
+    down = ks.hoisted_info()[1] - 1
+    for R in args.rotations:
+        gs = [pow(g0, r + 1, 2 * n) for r in range(R)]
+
+        def double():
+            ks.decompose(chat.data_ptr(), ext.data_ptr(), dscr.data_ptr(), B, stream)
+            for r, g in enumerate(gs):
+                ks.accumulate_decomposed(ext.data_ptr(), key.data_ptr(), acc.data_ptr(), B, g, w_ptr[r], 1, r > 0, stream)
+            ks.mod_down(acc.data_ptr(), out.data_ptr(), B, stream)
+            for r, g in enumerate(gs):
+                plan.mul_add_galois(w_ptr[r], c0, out.data_ptr(), B, g, 1, True, 0, Q, stream)
+
+        def single():
+            ks.decompose(chat.data_ptr(), ext.data_ptr(), dscr.data_ptr(), B, stream)
+            for r, g in enumerate(gs):
+                ks.apply_decomposed(ext.data_ptr(), key.data_ptr(), tmp.data_ptr(), ascr.data_ptr(), B, g, stream)
+                plan.mul_add_galois(w_ptr[r], tmp.data_ptr(), out2.data_ptr(), B, 1, 1, r > 0, 0, Q, stream)
+                plan.mul_add_galois(w_ptr[r], tmp.data_ptr() + 8 * Q * slab, out2.data_ptr() + 8 * Q * slab, B, 1, 1, r > 0, 0, Q, stream)
+                plan.mul_add_galois(w_ptr[r], c0, out2.data_ptr(), B, g, 1, True, 0, Q, stream)
+
+        t = _alternate([double, single])
+        report.update({f"{k}_{R}": v for k, v in t.items()})
+        med = {k: statistics.median(v) for k, v in t.items()}
+        print(f"{head} transform R={R} (ModDown launches {down} against {R * down}): double-hoisted {_fmt(t['double'])} us; single-hoisted {_fmt(t['single'])} us; "
+              f"ratio double/single {med['double'] / med['single']:.3f}")
+    if args.report:
+        import json
+
+        json.dump({"us": report, "launches": args.launches, "model_bytes": model}, open(args.report, "w"))
+    ks.close()
+    aplan.close()
+    plan.close()
+
+
 def run_ring():
     """One ring call (--kind add, sub, negate, add_galois or tensor) on the primes [--first, --first + --count) of a plan of --primes primes, alternating
     in one process with
@@ -643,6 +747,9 @@ if args.op == "inner":
     sys.exit(0)
 if args.op == "hoist":
     run_hoist()
+    sys.exit(0)
+if args.op == "dhoist":
+    run_dhoist()
     sys.exit(0)
 if args.op == "keyswitch":
     run_keyswitch()
