@@ -16,6 +16,7 @@
 
 #include "host_math.hpp"
 #include "plan_internal.hpp"
+#include "q60c_class.hpp"
 #ifdef AGX_DIAG
 #include "../../tools/agx_ntt_diag.h"
 #endif
@@ -157,7 +158,7 @@ static std::vector<ulonglong2> build_pass_table(const rb_entry* e, const std::ve
 static void resolve_routes(agx_ntt_plan* p) {
     route generic;
     generic.n = p->n, generic.log_n = p->log_n, generic.num_primes = p->num_primes;
-    generic.consts = p->d_consts, generic.tw = p->d_tw, generic.itw = p->d_itw, generic.rescale = p->d_rescale;
+    generic.consts = p->d_consts, generic.tw = p->d_tw, generic.itw = p->d_itw, generic.rescale = p->d_rescale, generic.q60c_skip = p->q60c_skip;
     generic.ticket_for = &plan_ticket_for, generic.ticket_launched = &plan_ticket_launched;
     generic.ticket_ctx = p;      // the plan is heap-allocated and never moves
     auto through = [&](const pass_tables& t) {
@@ -181,12 +182,6 @@ static void resolve_routes(agx_ntt_plan* p) {
     r.rescale = inv && e->launch_rescale ? main : generic;
     r.extend = e && e->launch_extend ? main : generic;      // forward tables only
     r.moddown = inv && e->launch_moddown ? main : generic;      // pairs with `inverse` on the source primes, as rescale does on the last
-}
-
-// c of a modulus q = 2^60 - c with 0 < c < 2^28, or 0 for any other modulus
-static uint32_t q60c_of(uint64_t q) {
-    const uint64_t top = 1ull << 60;
-    return q < top && top - q < (1ull << 28) ? (uint32_t)(top - q) : 0u;
 }
 
 void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
@@ -222,6 +217,9 @@ void prepare_plan_image(plan_image& img, uint32_t n, uint32_t num_primes, const 
             }
         }
     }
+    // within level 3: every c at or below the limit up to which the two-twiddle butterfly may reduce on every second stage only (modarith.hpp:
+    // q60c_skip_bounds); one larger c, and the whole plan keeps the every-stage kernel
+    img.q60c_skip = img.arith_level == 3 && q60c_skip_class(moduli, num_primes);
     img.narrow_level = 2;
     for (uint32_t k = 0; k < num_primes; ++k) {
         if (moduli[k] >= (1ull << 30)) img.narrow_level = std::min(img.narrow_level, 1);
@@ -303,7 +301,7 @@ int instantiate_plan(agx_ntt_plan** out, const plan_image& img) {
     std::unique_ptr<agx_ntt_plan, void (*)(agx_ntt_plan*)> p(new (std::nothrow) agx_ntt_plan, &free_plan);
     if (!p) return AGX_ERR_ALLOC;
     p->n = img.n, p->log_n = img.log_n, p->num_primes = img.num_primes;
-    p->has_inverse = img.has_inverse, p->arith_level = img.arith_level, p->narrow_level = img.narrow_level;
+    p->has_inverse = img.has_inverse, p->arith_level = img.arith_level, p->narrow_level = img.narrow_level, p->q60c_skip = img.q60c_skip;
     p->chosen = img.chosen;
     p->rescale_legal = img.rescale_legal;
     p->ticket_streams.reserve(kTicketSlots);      // plan_ticket_for() runs inside unguarded launch calls: it must never allocate

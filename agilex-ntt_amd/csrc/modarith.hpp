@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "q60c_class.hpp"      // kQ60cSkipMaxC: the class limit that q60c_skip_bounds proves and the host tests
+
 namespace agx {
 
 // {w, w'} with w' = floor(w * 2^64 / q): one 16-byte load fetches both
@@ -148,7 +150,7 @@ struct bf_consts {
     float est_inv;          // slightly below 2^32 / q, or 0 when q < 2^58 (reduce_final_est)
     uint32_t c, c8;         // q = 2^60 - c kernels only (below): c and 8c
     uint32_t c2, p29;       // two-twiddle form of those kernels only (ct_butterfly_q60c_fold): 2c, and 2^29 in a form the optimiser cannot see through
-    uint64_t m8;            // ... and 8q
+    uint64_t mfold;         // ... and its lazy-range constant: 8q (sign-bit subtract on every stage), or 7q (top-four-bit reduction on every second stage)
 };
 
 // x in [0,2m) -> x - (x >= m ? m : 0) through the sign of x - m; needs 2m <= 2^63... see callers
@@ -439,12 +441,20 @@ __device__ __forceinline__ void ct_butterfly_q60c(uint64_t& x, uint64_t& y, uint
 // any v < 2^64 (the transform's outputs are below 16q + 8c) -> [0,q), or only below 2q for lazy outputs.  v = k 2^60 + r with
 // k = v >> 60 <= 15 and r < 2^60; 2^60 = c (mod q), so v = r + k c (mod q), and with c < 2^28: k c < 15 2^28 < 2^32,
 // r + k c < 2^60 + 2^32 < 2^61 - 2^29 < 2q.  One conditional subtract of q finishes (r + k c < 2^63: the sign test is exact).
-__device__ __forceinline__ uint64_t reduce_final_q60c(uint64_t v, const bf_consts& k, const final_consts& f, bool lazy_out) {
+// The fold itself: any x < 2^64 -> (x mod 2^60) + (x >> 60) c <= 2^60 - 1 + 15c, the same residue: shift, mask, one multiply-add.
+// PIN (the butterflies of the skip form): the shifted word passes through an empty asm statement, as csub_8q_q60c's does -- no instruction, but the
+// n = 4096 kernel is then allocated 111 VGPRs, as with the sign-bit subtract, instead of 115 (about 92 values are live either way).
+template <bool PIN = false>
+__device__ __forceinline__ uint64_t reduce_top4_q60c(uint64_t x, const bf_consts& k) {
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    u32x2 r = __builtin_bit_cast(u32x2, v);
-    const uint32_t kq = r.y >> 28;
+    u32x2 r = __builtin_bit_cast(u32x2, x);
+    uint32_t kq = r.y >> 28;
+    if constexpr (PIN) asm("" : "+v"(kq));
     r.y &= 0x0fffffffu;
-    const uint64_t t = mad64(kq, k.c, __builtin_bit_cast(uint64_t, r));
+    return mad64(kq, k.c, __builtin_bit_cast(uint64_t, r));
+}
+__device__ __forceinline__ uint64_t reduce_final_q60c(uint64_t v, const bf_consts& k, const final_consts& f, bool lazy_out) {
+    const uint64_t t = reduce_top4_q60c(v, k);
     return lazy_out ? t : csub_select_c(t, f.nq1);
 }
 
@@ -458,6 +468,7 @@ __device__ __forceinline__ uint64_t reduce_final_q60c(uint64_t v, const bf_const
 //   x' = tx + Q,   y' = tx + 8q - Q = 2 tx + 8q - x'.
 // Coefficients travel between stages as arbitrary 64-bit words; every stage but the first brings x below 2^63 + 8c with the sign-bit
 // subtract (csub_8q_q60c), the first one's inputs are below 4q.  q60c_fold_bounds proves that no partial sum wraps, for the whole class.
+// (For c <= 2^27 half of those subtracts go: the skip form below, 7q in place of 8q.)
 // reduce_final_q60c takes any 64-bit word, so the last stage and the output contract are those of the form above.
 // ---------------------------------------------------------------------------------------
 struct q60c_fold_bounds {
@@ -483,17 +494,54 @@ __device__ __forceinline__ uint32_t opaque_two29() {
     return v;
 }
 
-template <bool DO_CSUB>
+// SKIP form of the same butterfly for c <= kQ60cSkipMaxC = 2^27: the lazy-range constant is 7q (y' = tx + 7q - Q), and x is reduced by its top four
+// bits (reduce_top4_q60c: the same three instructions as the sign-bit subtract) on every SECOND stage only; the stages between reduce nothing.
+//   reducing stage, any 64-bit x:   tx <= 2^60 - 1 + 15c,   x' = tx + Q and y' = tx + 7q - Q are at most tx + 7q = 8q + 16c - 1 = 2^63 + 8c - 1
+//   the stage behind it, tx = x:    x' and y' are at most 15q + 16c - 1 = 2^64 - q - 1
+// because Q <= 7q for this class (lo + hl 2^29 < 6q, hh 2c < 2^33 c <= 2^60; 7q is also what keeps y' from going negative).  2 tx may pass 2^64 in
+// y' = 2 tx + 7q - x'; the value itself lies in [0, 2^64), so arithmetic mod 2^64 returns it.  y-inputs may be any 64-bit word, as above, and so may the
+// inputs of stage 0, which reduces.  q60c_skip_bounds proves it for the whole class; the schedule says which stages reduce.
+struct q60c_skip_schedule {
+    static constexpr bool reduces(int s) { return (s & 1) == 0; }
+    // stage 0 takes any word, and no unreduced stage follows another: the proof covers one reduced stage plus one unreduced stage.  The last stage
+    // may be either: reduce_final_q60c takes any word.
+    static constexpr bool valid(int total) {
+        for (int s = 1; s < total; ++s)
+            if (!reduces(s) && !reduces(s - 1)) return false;
+        return total >= 1 && reduces(0);
+    }
+};
+struct q60c_skip_bounds {
+    typedef unsigned __int128 u128;
+    using F = q60c_fold_bounds;
+    static constexpr u128 two64 = F::two64, w32 = F::w32;
+    static constexpr u128 c_max = kQ60cSkipMaxC, q_min = (1ull << 60) - (uint64_t)c_max;
+    static constexpr u128 Q_max = F::lo_max + w32 * ((u128)1 << 29) + w32 * 2 * c_max;      // lo + hl 2^29 + hh 2c; grows with c, while q falls: the largest c decides
+    static constexpr u128 r_max = ((u128)1 << 60) - 1 + 15 * c_max;                          // after reduce_top4_q60c
+    static constexpr u128 out1_max = r_max + 7 * q_min;                                      // x', y' of a reducing stage (Q <= 7q): 2^63 + 8c - 1, largest at the largest c
+    static_assert(c_max < ((u128)1 << 28), "a subclass of the moduli of q60c_fold_bounds: hi and the halves of a twiddle are bounded there");
+    static_assert(15 * c_max < ((u128)1 << 32), "the fold's product fits a word");
+    static_assert(Q_max <= 7 * q_min, "y' = tx + 7q - Q is not negative, on either kind of stage");
+    static_assert(out1_max == ((u128)1 << 63) + 8 * c_max - 1, "8q + 16c - 1");
+    static_assert(r_max + Q_max < two64, "reducing stage: x' does not wrap (every partial sum of the chain is below this one)");
+    static_assert(out1_max + Q_max < two64, "the stage behind it: x' does not wrap (every partial sum of the chain is below this one)");
+    static_assert(out1_max + 7 * q_min < two64, "... and y' <= tx + 7q = 15 2^60 + c - 1 (grows with c) stays below 2^64");
+};
+
+// FORM 0 / 1: lazy-range constant 8q (k.mfold), x as it comes / after the sign-bit subtract.  FORM 2 / 3: the skip form, lazy-range constant 7q,
+// x after the reduction by its top four bits / as it comes.
+template <int FORM>
 __device__ __forceinline__ void ct_butterfly_q60c_fold(uint64_t& x, uint64_t& y, uint64_t w, uint64_t wC, const bf_consts& k) {
+    static_assert(FORM >= 0 && FORM <= 3, "no such form");
     const uint32_t y0 = (uint32_t)y, y1 = (uint32_t)(y >> 32);
     const uint32_t wl = (uint32_t)w, wh = (uint32_t)(w >> 32), wCl = (uint32_t)wC, wCh = (uint32_t)(wC >> 32);      // the slot holds the halves a word each
-    const uint64_t tx = DO_CSUB ? csub_8q_q60c(x, k) : x;
+    const uint64_t tx = FORM == 1 ? csub_8q_q60c(x, k) : FORM == 2 ? reduce_top4_q60c<true>(x, k) : x;
     const uint64_t hi = mad64(y1, wCh, mul64(y0, wh));
     uint64_t xn = keep64(mad64(y0, wl, tx));      // pinned: left free, the sum is reassociated into a chain from zero plus a 64-bit add of tx
     xn = mad64(y1, wCl, xn);
     xn = mad64((uint32_t)hi, k.p29, xn);      // a visible 2^29 would become shifts and a carry pair
     xn = mad64((uint32_t)(hi >> 32), k.c2, xn);
-    y = (tx << 1) + k.m8 - xn;                                              // tx + 8q - Q
+    y = (tx << 1) + k.mfold - xn;                                           // tx + 8q - Q (skip form: 7q)
     x = xn;
 }
 

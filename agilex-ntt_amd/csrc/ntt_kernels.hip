@@ -549,7 +549,8 @@ rb_selection regblock_select(uint32_t n, int config_id, int arith_level, int nar
     if (!sel.main || sel.main->fwd_companion <= 0) return sel;
     // tuned defaults among the forward companions: {companion, its twin for a narrower class of moduli}; the twin serves the plans whose moduli
     // allow it (same shape and table geometry; the companion's table is built by the entry that is chosen here)
-    static const int kCompanionDefaults[][2] = {{159, 165}};      // n = 4096: moduli 2^60 - c, 0 < c < 2^28 (arithmetic level 3)
+    static const int kCompanionDefaults[][2] = {{159, 165}};      // n = 4096: moduli 2^60 - c, 0 < c < 2^28 (arithmetic level 3); which of id 165's two kernels
+                                                                  // a launch gets (every c <= kQ60cSkipMaxC or not) is that entry's launch function's business
     int id = sel.main->fwd_companion;
     for (const auto& d : kCompanionDefaults)
         if (d[0] == id && find(d[1])) id = d[1];

@@ -44,6 +44,8 @@ struct plan_view {
     const ulonglong2* tw_rb = nullptr;     // [P][rb->table_pairs]: the entry's pass tables from the forward tables
     const ulonglong2* itw_rb = nullptr;    // same layout from the inverse tables, or null
     const rescale_consts* rescale = nullptr;   // [P-1], or null (one prime)
+    bool q60c_skip = false;                // every modulus of the PLAN is 2^60 - c with 0 < c <= kQ60cSkipMaxC of q60c_class.hpp (so is every range of its primes): an entry
+                                           // with a kernel for that class launches it (rb_kernels.hpp: launch_fwd_q60c_skip_t), any other plan gets the entry's general kernel
     // Kernels that hand out frames through a counter ask for a {next frame, retired workgroups} pair of the plan HERE, at launch time and
     // only if they need one: the pair is keyed by the stream (launches on one stream serialise, so they may share a pair; the last
     // workgroup out zeroes it).  nullptr = no pair can be proven free (too many distinct streams): take the stateless fixed-stride form.

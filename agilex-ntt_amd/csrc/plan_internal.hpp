@@ -80,6 +80,7 @@ struct agx_ntt_plan {
     bool has_inverse = false;
     int arith_level = 0;     // 0 exact only; 1: every modulus <= 2^61 (8q-lazy legal); 2: <= 2^60 (16q-lazy legal); 3: every modulus 2^60 - c, 0 < c < 2^28
     int narrow_level = 0;    // 1: every modulus < 2^31, 2: < 2^30 -- the 32-bit kernels are legal (with arith_level >= 1: tables honour the contract)
+    bool q60c_skip = false;  // arith_level 3 and every c <= kQ60cSkipMaxC: every route carries it (plan_view::q60c_skip), the n = 4096 forward companion (id 165) launches its skip-form kernel
     std::vector<uint64_t> moduli, psi;  // psi = 0 when the tables came from the caller
     std::vector<agx::prime_consts> consts;      // [P]: what d_consts holds (64 bytes per prime; the tables below stay device-only)
     agx::device_buf<agx::prime_consts> d_consts;
@@ -181,6 +182,7 @@ struct plan_image {
     uint32_t n = 0, log_n = 0, num_primes = 0;
     bool has_inverse = false;
     int arith_level = 0, narrow_level = 0;
+    bool q60c_skip = false;      // arith_level 3 and every modulus 2^60 - c has c <= kQ60cSkipMaxC
     std::vector<uint64_t> moduli, psi;
     rb_selection chosen;
     std::vector<prime_consts> consts;

@@ -188,6 +188,8 @@ constexpr int kOptQ60c = 1 << 27;          // with kOptEstReduce, forward only: 
                                            // final reduction by the top four bits (modarith.hpp: q60c_tailfree)
 constexpr int kOptQ60cFold = 1 << 28;      // with kOptQ60c: the two-twiddle butterfly (modarith.hpp: ct_butterfly_q60c_fold) -- six multiply-adds, no quotient estimate; the pass
                                            // table's slots hold {w, w 2^32 mod q}, each split at bit 29, instead of {w, w'} (rb_kernels.hpp: build_table_fold_t)
+constexpr int kOptQ60cSkip = 1 << 21;      // with kOptQ60cFold, every modulus 2^60 - c with c <= kQ60cSkipMaxC = 2^27 (the launch chooses: plan_view::q60c_skip): x is reduced by its top four
+                                           // bits on every second stage only, lazy-range constant 7q (modarith.hpp: q60c_skip_schedule, q60c_skip_bounds); same table
 constexpr int kOptStreamCh1 = 1 << 29;     // with kOptStreamTw: one table entry per chunk instead of two or four (R = 4 passes then fit 64 VGPRs: 8 waves/SIMD)
 // Measured and removed in round 4 (the records stay in profiles/ and DESIGN.md 3.4-3.6): the XOR-swizzled image, cross products as 32-bit multiplies,
 // the inverse's twiddle-first / priority policies, timing ablations, persistent streaming / loop forms of the forward, resident sub-blocks with
@@ -217,6 +219,9 @@ struct rb2_frame {
     static constexpr bool Q60C = EST && (OPT & kOptQ60c) != 0;
     static constexpr bool Q60C_FOLD = Q60C && (OPT & kOptQ60cFold) != 0;
     static_assert((OPT & kOptQ60cFold) == 0 || Q60C, "the two-twiddle butterfly is a form of the q = 2^60 - c kernels");
+    static constexpr bool Q60C_SKIP = Q60C_FOLD && (OPT & kOptQ60cSkip) != 0;
+    static_assert((OPT & kOptQ60cSkip) == 0 || Q60C_FOLD, "the reduction on every second stage is a form of the two-twiddle butterfly");
+    static_assert(!Q60C_SKIP || q60c_skip_schedule::valid(L), "no unreduced stage may follow another, and stage 0 reduces");
     static constexpr bool SPLIT = (OPT & kOptSplitWord) != 0;
     static constexpr bool STREAM_TW = (OPT & kOptStreamTw) != 0, PIN_BF = (OPT & kOptPinBf) != 0, STREAM_CH1 = (OPT & kOptStreamCh1) != 0;
     static_assert(!EST || lazy16_tailfree::valid(L), "tail-free schedule must keep every stage within 16q");
@@ -288,14 +293,16 @@ struct rb2_frame {
         if constexpr (Q60C_FOLD) {
             k.c2 = k.c << 1;
             k.p29 = opaque_two29();
-            k.m8 = q << 3;
+            if constexpr (Q60C_SKIP) k.mfold = opaque_sgpr64((q << 3) - q);      // 7q, opaque: a visible 7 q joins the butterfly's chain as one more multiply-add per y'
+            else k.mfold = q << 3;
         }
     }
 
     // forward butterfly number `stage` of the whole transform in this frame's arithmetic
     template <int stage>
     __device__ __forceinline__ void butterfly(uint64_t& a, uint64_t& b, const twpair& w) const {
-        if constexpr (Q60C_FOLD) ct_butterfly_q60c_fold<(stage >= 1)>(a, b, w.x, w.y, k);      // the slot holds {w, wC} (kOptQ60cFold); first-stage inputs are below 4q
+        if constexpr (Q60C_SKIP) ct_butterfly_q60c_fold<(q60c_skip_schedule::reduces(stage) ? 2 : 3)>(a, b, w.x, w.y, k);      // stage 0 reduces: any 64-bit input
+        else if constexpr (Q60C_FOLD) ct_butterfly_q60c_fold<(stage >= 1 ? 1 : 0)>(a, b, w.x, w.y, k);      // the slot holds {w, wC} (kOptQ60cFold); first-stage inputs are below 4q
         else if constexpr (Q60C) ct_butterfly_q60c<lazy16_tailfree::subtracts(stage, L)>(a, b, w.x, w.y, k);
         else if constexpr (EST) ct_butterfly_lazy16<SEL, lazy16_tailfree::subtracts(stage, L), false>(a, b, w.x, w.y, k, fc);
         else if constexpr (LAZY16) ct_butterfly_lazy16<SEL, lazy16_schedule::subtracts(stage), stage == L - 1>(a, b, w.x, w.y, k, fc);

@@ -861,6 +861,26 @@ constexpr rb_entry make_entry_single_fwd(int id) {
     return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd>, nullptr, nullptr);
 }
 
+// ... with two kernels of one shape and one table behind the id, chosen on the host per launch: the skip form of the two-twiddle butterfly
+// (ARITH | kOptQ60cSkip) for plans whose moduli are all 2^60 - c with c <= kQ60cSkipMaxC (plan_view::q60c_skip), the kernel of ARITH itself for every other
+// plan the entry may serve -- mixed plans included, bit for bit what the entry launched before it had the first.  No kernel branches on c.
+template <class S, auto SKIP, auto GENERAL>
+hipError_t launch_fwd_q60c_skip_t(const plan_view& pv, const uint64_t* in, uint64_t* out, const frame_layout& fl, hipStream_t s) {
+    return pv.q60c_skip ? launch_fwd_t<S, SKIP>(pv, in, out, fl, s) : launch_fwd_t<S, GENERAL>(pv, in, out, fl, s);
+}
+template <int L, int R, int ARITH, int MINW>
+constexpr rb_entry make_entry_single_fwd_q60c_skip(int id) {
+    constexpr int ARITH_SKIP = ARITH | (kOptQ60cSkip << 1);
+    using S = rb2_shape<L, R, 1, ARITH, MINW>;
+    using SS = rb2_shape<L, R, 1, ARITH_SKIP, MINW>;
+    static_assert(frame_of<L, R, ARITH>::Q60C_FOLD && !frame_of<L, R, ARITH>::Q60C_SKIP && frame_of<L, R, ARITH_SKIP>::Q60C_SKIP, "the general kernel is the two-twiddle form without the skip");
+    static_assert(S::lds == SS::lds && S::threads == SS::threads && S::table_pairs == SS::table_pairs && S::build == SS::build && S::arith == SS::arith,
+                  "one launch shape and one pass table serve both kernels");
+    constexpr auto skip = &fwd_rb2<L, R, 1, ARITH_SKIP, MINW>;
+    constexpr auto general = &fwd_rb2<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_q60c_skip_t<S, skip, general>, &allow_lds<S::lds, skip, general>, nullptr, nullptr);
+}
+
 // the streamed single-frame kernels (reg_s<n>.hip): one frame in registers per workgroup at any time (R = 5: a second frame cannot
 // be held): forward, inverse, the fused product by polymul_rb2_park / polysquare_rb2, the product by a pre-transformed operand, the rescale kernel, the base-extension and ModDown kernels
 template <int L, int R, int ARITH, int MINW>

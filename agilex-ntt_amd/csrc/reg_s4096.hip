@@ -13,9 +13,13 @@ const rb_entry kEntries[] = {
     make_entry_single_fwd<12, 5, kLazy | (kOptPrio << 1), 4>(159),
     // the same shape for plans whose moduli are all 2^60 - c, 0 < c < 2^28 (arithmetic level 3): the two-twiddle butterfly (six multiply-adds, a sign-bit
     // subtract on every stage but the first, slots {w, w 2^32 mod q} split at bit 29), final reduction by the top four bits; takes id 159's place as
-    // the forward companion of such plans (ntt_kernels.hip: kCompanionDefaults)
-    make_entry_single_fwd<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold) << 1), 4>(165),
+    // the forward companion of such plans (ntt_kernels.hip: kCompanionDefaults).  Two kernels behind the id, one table: a plan whose moduli all have
+    // c <= 2^27 (kQ60cSkipMaxC; the flag is the plan's, plan_view::q60c_skip) gets the skip form -- reduction by the top four bits on the even stages
+    // only, 7q in place of 8q, any 64-bit input -- and every other plan, mixed ones included, the every-stage kernel above
+    make_entry_single_fwd_q60c_skip<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold) << 1), 4>(165),
 #ifdef AGX_DIAG
+    // A/B twin of id 165 that always launches the every-stage kernel, whatever the plan's moduli (tools/energy_ab.py)
+    make_entry_single_fwd<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold) << 1), 4>(168),
     // A/B twin of id 165 with the butterfly it had before: quotient estimate from {w, w'}, sign-bit subtracts on the tail-free schedule (tools/energy_ab.py)
     make_entry_single_fwd<12, 5, kLazy | ((kOptPrio | kOptQ60c) << 1), 4>(167),
     // A/B twins kept in lib/libagxntt_diag.so: all three transforms in this shape with the load priority (147: its inverse -1 %, its parked

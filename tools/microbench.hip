@@ -274,7 +274,7 @@ __global__ void __launch_bounds__(512, 8) bf_kernel(uint64_t* out, const uint64_
     fc.q8 = q << 3; fc.nq8 = opaque_sgpr64(0 - fc.q8);
     if constexpr (FORM >= 4) {      // q = 2^60 - c
         k.c = (uint32_t)((1ull << 60) - q); k.c8 = k.c << 3;
-        k.c2 = k.c << 1; k.p29 = opaque_two29(); k.m8 = q << 3;
+        k.c2 = k.c << 1; k.p29 = opaque_two29(); k.mfold = q << 3;
     }
     uint64_t x[8];
     for (int r = 0; r < 8; ++r) x[r] = (tw[(threadIdx.x * 8 + r) & 1023] >> 3);
@@ -310,8 +310,8 @@ __global__ void __launch_bounds__(512, 8) bf_kernel(uint64_t* out, const uint64_
                     else ct_butterfly_q60c<false>(x[r0], x[r1], w[j], wp[j], k);
                 }
                 else if constexpr (FORM == 5) {
-                    if (stage == 0 && b == 0) ct_butterfly_q60c_fold<false>(x[r0], x[r1], w[j], wp[j], k);
-                    else ct_butterfly_q60c_fold<true>(x[r0], x[r1], w[j], wp[j], k);
+                    if (stage == 0 && b == 0) ct_butterfly_q60c_fold<0>(x[r0], x[r1], w[j], wp[j], k);
+                    else ct_butterfly_q60c_fold<1>(x[r0], x[r1], w[j], wp[j], k);
                 }
                 else if (stage == 1 || (stage == 2 && b == 0)) ct_butterfly_lazy16<true, true>(x[r0], x[r1], w[j], wp[j], k, fc);   // 5 of 12
                 else ct_butterfly_lazy16<true, false>(x[r0], x[r1], w[j], wp[j], k, fc);
