@@ -62,6 +62,9 @@ ABI = {
     "agx_ntt_basis_extend": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_basis_mod_down": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_basis_mod_down_info": (_int, [_vp, ctypes.POINTER(_int)]),
+    "agx_ntt_basis_create_plain": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32, _u64]),
+    "agx_ntt_basis_mod_down_mode": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _int, _vp]),
+    "agx_ntt_keyswitch_create_plain": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32, _u64]),
     "agx_ntt_inner_product": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _vp]),
     "agx_ntt_inner_product_galois": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp]),
     "agx_ntt_add": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp]),
@@ -346,9 +349,10 @@ class Plan:
         FORM_COEFF moves and negates coefficients (inputs in [0,4q), outputs in [0,q)); galois_elt odd, below 2n"""
         _check(lib().agx_ntt_automorphism(self._h, d_in, d_out, batch, galois_elt, form, stream), "automorphism")
 
-    def basis(self, src_first, src_count, dst_first, dst_count):
-        """Basis(self, ...): the fast base conversion from primes [src_first, src_first + src_count) to [dst_first, dst_first + dst_count)"""
-        return Basis(self, src_first, src_count, dst_first, dst_count)
+    def basis(self, src_first, src_count, dst_first, dst_count, t=1):
+        """Basis(self, ...): the fast base conversion from primes [src_first, src_first + src_count) to [dst_first, dst_first + dst_count); t: the
+        plaintext modulus its ModDown keeps the value modulo (BGV), 1 for none"""
+        return Basis(self, src_first, src_count, dst_first, dst_count, t)
 
     def inner_product(self, d_a, d_bhat, d_c, batch, terms, outputs=1, bhat_batch=None, stream=0):
         """c_o = sum_t a_t o bhat_{t,o} mod q in one launch: d_a [terms][P][batch][n], d_bhat [terms][outputs][P][bhat_batch][n], d_c
@@ -394,9 +398,10 @@ class Plan:
         _check(lib().agx_ntt_mul_add_galois(self._h, d_w, batch if w_batch is None else w_batch, d_b, d_c, batch, *self._prime_range(prime_first, prime_count),
                                             galois_elt, int(accumulate), stream), "mul_add_galois")
 
-    def keyswitch(self, q_count, p_first, p_count, alpha):
-        """KeySwitch(self, ...): the hybrid key switch at level Q = primes [0, q_count) with special primes [p_first, p_first + p_count)"""
-        return KeySwitch(self, q_count, p_first, p_count, alpha)
+    def keyswitch(self, q_count, p_first, p_count, alpha, t=1):
+        """KeySwitch(self, ...): the hybrid key switch at level Q = primes [0, q_count) with special primes [p_first, p_first + p_count); t: the
+        plaintext modulus its ModDown keeps the value modulo (BGV), 1 for none"""
+        return KeySwitch(self, q_count, p_first, p_count, alpha, t)
 
     def fill_synthetic(self, d_out, batch, first_poly=0, seed=42, stream=0):
         _check(lib().agx_ntt_fill_synthetic(self._h, d_out, batch, first_poly, seed, stream), "fill_synthetic")
@@ -428,13 +433,14 @@ class Plan:
 class Basis:
     """The constants of a fast RNS base conversion (agx_ntt_basis_*) from the plan's primes [src_first, src_first + src_count) to
     [dst_first, dst_first + dst_count).  `plan` is a Plan, or a raw plan handle (a DeviceGroup shard's: one basis per shard); it must
-    outlive the basis, and its device must be current here and at every call."""
+    outlive the basis, and its device must be current here and at every call.  t: a plaintext modulus (agx_ntt_basis_create_plain), a property
+    of mod_down alone -- extend writes what it writes with t = 1, and t = 1 is the ordinary basis in every call."""
 
-    def __init__(self, plan, src_first, src_count, dst_first, dst_count):
+    def __init__(self, plan, src_first, src_count, dst_first, dst_count, t=1):
         self.plan = plan      # keeps a Plan alive
         self._h = _vp(None)
         handle = plan._h if isinstance(plan, Plan) else plan
-        _check(lib().agx_ntt_basis_create(ctypes.byref(self._h), handle, src_first, src_count, dst_first, dst_count), "basis_create")
+        _check(lib().agx_ntt_basis_create_plain(ctypes.byref(self._h), handle, src_first, src_count, dst_first, dst_count, t), "basis_create_plain")
 
     def info(self):
         """(src_first, src_count, dst_first, dst_count, launches_ntt_form): the ranges, and the kernel launches a FORM_NTT call takes
@@ -449,11 +455,12 @@ class Basis:
         mod q_i; no correction term), as coefficients (FORM_COEFF) or transformed as Plan.forward writes it (FORM_NTT); out of place"""
         _check(lib().agx_ntt_basis_extend(self._h, d_x, d_out, batch, form, stream), "basis_extend")
 
-    def mod_down(self, d_xq, d_xp, d_out, d_scratch, batch, stream=0):
+    def mod_down(self, d_xq, d_xp, d_out, d_scratch, batch, stream=0, mode=RESCALE_FLOOR):
         """ModDown on NTT-form frames: d_xq [dst_count][batch][n] and d_xp [src_count][batch][n] as Plan.forward / forward_lazy write them ->
-        d_out [dst_count][batch][n] = (xq_j - NTT_j(sum_i y_i D_i)) D^-1 mod q_j, y_i = INTT_i(xp_i) D_i^-1 mod q_i; d_out may be d_xq;
-        d_scratch: src_count*batch*n words, or d_xp itself (which is then overwritten)"""
-        _check(lib().agx_ntt_basis_mod_down(self._h, d_xq, d_xp, d_out, d_scratch, batch, stream), "basis_mod_down")
+        d_out [dst_count][batch][n] = (xq_j - NTT_j(t (V - h))) D^-1 mod q_j, V = sum_i y_i D_i, y_i = (INTT_i(xp_i) t^-1 + h) D_i^-1 mod q_i, with
+        h = floor(D / 2) under RESCALE_ROUND and 0 under RESCALE_FLOOR, t the basis' plaintext modulus; d_out may be d_xq; d_scratch:
+        src_count*batch*n words, or d_xp itself (which is then overwritten)"""
+        _check(lib().agx_ntt_basis_mod_down_mode(self._h, d_xq, d_xp, d_out, d_scratch, batch, mode, stream), "basis_mod_down_mode")
 
     def mod_down_launches(self):
         """the kernel launches a mod_down call takes under the plan's current variant"""
@@ -480,13 +487,14 @@ INNER_MAX_TERMS, INNER_MAX_OUTPUTS = 16, 2
 class KeySwitch:
     """One hybrid key switch (agx_ntt_keyswitch_*) on a plan: Q = primes [0, q_count), special primes [p_first, p_first + p_count) with
     p_first >= q_count, digits of alpha primes.  `plan` is a Plan or a raw plan handle (one handle per DeviceGroup shard); it must outlive
-    the handle, and its device must be current here and at every call."""
+    the handle, and its device must be current here and at every call.  t: a plaintext modulus (agx_ntt_keyswitch_create_plain): every call on
+    the handle then divides by P keeping the value modulo t (BGV); 1 for none."""
 
-    def __init__(self, plan, q_count, p_first, p_count, alpha):
+    def __init__(self, plan, q_count, p_first, p_count, alpha, t=1):
         self.plan = plan      # keeps a Plan alive
         self._h = _vp(None)
         handle = plan._h if isinstance(plan, Plan) else plan
-        _check(lib().agx_ntt_keyswitch_create(ctypes.byref(self._h), handle, q_count, p_first, p_count, alpha), "keyswitch_create")
+        _check(lib().agx_ntt_keyswitch_create_plain(ctypes.byref(self._h), handle, q_count, p_first, p_count, alpha, t), "keyswitch_create_plain")
 
     def info(self):
         """(q_count, p_first, p_count, alpha, digits, launches): the shape, and the kernel launches of one apply under the plan's current variant"""

@@ -13,7 +13,9 @@ using namespace agx;
 
 static bool targets_fit_grid(uint32_t T, uint64_t batch, int ppb) { return (uint64_t)T * ((batch + ppb - 1) / ppb) <= 0x7fffffffull; }      // grid limit of the fused kernels: T workgroups per group of ppb frames
 static bool dense_fits(uint32_t n, uint32_t slabs, uint64_t frames) { return layout_fits(n, slabs, frames, (int64_t)(frames * n), (int64_t)n); }      // one dense range of slabs x frames x n words (formed in 128 bits)
-static basis_view view_of(const agx_ntt_basis* b) { return basis_view{b->d_dinv, b->d_mat, b->d_dall, b->src_first, b->src_count, b->dst_first, b->dst_count}; }
+static basis_view view_of(const agx_ntt_basis* b) {
+    return basis_view{b->d_dinv, b->d_mat, b->d_dall, b->d_down_mat, b->d_round_src, b->d_round_dst, b->src_first, b->src_count, b->dst_first, b->dst_count};
+}
 
 extern "C" {
 
@@ -52,6 +54,12 @@ int agx_ntt_rescale(const agx_ntt_plan* plan, const uint64_t* d_x, uint64_t* d_o
 }
 
 int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count) {
+    return agx_ntt_basis_create_plain(basis, plan, src_first, src_count, dst_first, dst_count, 1);      // t = 1: every constant is what it was without a t
+}
+
+// agx_ntt_basis_create's rules in its order, then t: 0 is a bad argument, a t without an inverse modulo a source a bad modulus
+int agx_ntt_basis_create_plain(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count,
+                               uint64_t t) {
     if (!basis) return AGX_ERR_NULL_POINTER;
     *basis = nullptr;
     if (!plan) return AGX_ERR_NULL_POINTER;
@@ -64,6 +72,7 @@ int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32
         std::vector<uint64_t> dinv(S), dinv_p(S), mat((size_t)T * S), mat_p((size_t)T * S);
         // D_i must be invertible modulo q_i: two equal source moduli have no conversion
         if (!basis_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, dinv.data(), dinv_p.data(), mat.data(), mat_p.data())) return AGX_ERR_BAD_MODULUS;
+        if (t == 0) return AGX_ERR_BAD_ARGUMENT;
         std::vector<ulonglong2> dinv_pairs(S), mat_pairs((size_t)T * S);
         for (size_t k = 0; k < dinv_pairs.size(); ++k) dinv_pairs[k] = make_ulonglong2(dinv[k], dinv_p[k]);
         for (size_t k = 0; k < mat_pairs.size(); ++k) mat_pairs[k] = make_ulonglong2(mat[k], mat_p[k]);
@@ -80,7 +89,19 @@ int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32
         for (uint32_t i = 0; i < S; ++i) n_inv[i] = sc[i].n_inv, w1n[i] = sc[i].w1n;
         b->moddown_legal = moddown_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, dinv.data(), n_inv.data(), w1n.data(), dall.data(),
                                              dall_p.data(), sn.data(), sn_p.data(), sw.data(), sw_p.data());
+        // agx_ntt_basis_mod_down_mode and the plaintext modulus: t^-1 into the scaled inverse's constants, ModDown's own matrix t D_i mod q_j, and the two
+        // constant sets of AGX_RESCALE_ROUND.  t = 1 leaves sn, sw as they are and makes the matrix a copy of mat.
+        std::vector<uint64_t> dmat((size_t)T * S), dmat_p((size_t)T * S), cadd(S), hq(T);
+        if (!moddown_mode_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, t, dinv.data(), mat.data(), sn.data(), sn_p.data(), sw.data(), sw_p.data(),
+                                    dmat.data(), dmat_p.data(), cadd.data(), hq.data()))
+            return AGX_ERR_BAD_MODULUS;
         for (uint32_t i = 0; i < S; ++i) sc[i].n_inv = sn[i], sc[i].n_inv_p = sn_p[i], sc[i].w1n = sw[i], sc[i].w1n_p = sw_p[i];
+        std::vector<ulonglong2> dmat_pairs((size_t)T * S), round_src(S);
+        for (size_t k = 0; k < dmat_pairs.size(); ++k) dmat_pairs[k] = make_ulonglong2(dmat[k], dmat_p[k]);
+        for (uint32_t i = 0; i < S; ++i) round_src[i] = make_ulonglong2(cadd[i], plan->moduli[src_first + i]);
+        if (int rc = b->d_down_mat.upload(dmat_pairs)) return rc;
+        if (int rc = b->d_round_src.upload(round_src)) return rc;
+        if (int rc = b->d_round_dst.upload(hq)) return rc;
         std::vector<ulonglong2> dall_pairs(T);
         for (uint32_t j = 0; j < T; ++j) dall_pairs[j] = make_ulonglong2(dall[j], dall_p[j]);
         if (int rc = b->d_dall.upload(dall_pairs)) return rc;
@@ -164,7 +185,16 @@ int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launches) {
 }
 
 int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    return agx_ntt_basis_mod_down_mode(basis, d_xq, d_xp, d_out, d_scratch, batch, AGX_RESCALE_FLOOR, stream);
+}
+
+// agx_ntt_basis_mod_down's rules in its order, the mode rule right behind the NULL rule (as agx_ntt_rescale has it).  FLOOR launches what mod_down always
+// launched; ROUND the kernels with the two per-word steps of moddown_arith.hpp.  The basis' t is in its constants: both modes serve every basis.
+int agx_ntt_basis_mod_down_mode(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, int mode,
+                                void* stream) {
     if (!basis || !d_xq || !d_xp || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    if (mode != AGX_RESCALE_FLOOR && mode != AGX_RESCALE_ROUND) return AGX_ERR_BAD_ARGUMENT;
+    const bool round = mode == AGX_RESCALE_ROUND;
     const agx_ntt_plan* plan = basis->plan;
     if (int rc = check_plan(plan)) return rc;
     const uint32_t S = basis->src_count, T = basis->dst_count;
@@ -181,20 +211,20 @@ int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, con
     if (batch == 0) return AGX_OK;
     const basis_view bv = view_of(basis);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // scratch <- y_i = INTT_i(xp_i) D_i^-1 mod q_i in [0, q_i): the plan's inverse on the view of the source primes, its last-stage constants the basis'
+    // scratch <- y_i = INTT_i(xp_i) t^-1 D_i^-1 mod q_i in [0, q_i): the plan's inverse on the view of the source primes, its last-stage constants the basis'
     route scaled = prime_range(plan->routes.inverse, basis->src_first, basis->src_first + S);
     scaled.consts = basis->d_src_consts;
     if (fused) {
         // two launches: the accumulation, the forward transform and (xq_j - .) D^-1 stay on chip; a wave reads its words of xq_j before it writes them
         AGX_HIP(run_inverse(scaled, d_xp, nullptr, d_scratch, fl, s));
-        AGX_HIP(r.rb->launch_moddown(r, bv, d_xq, d_scratch, d_out, fl, s));
+        AGX_HIP(r.rb->launch_moddown(r, bv, d_xq, d_scratch, d_out, fl, round, s));
         return AGX_OK;
     }
     // generic route, no more scratch: out <- INTT(xq) on the target primes; scratch <- the y_i; out <- (out - sum_i y_i D_i) D^-1 in the coefficient
     // domain; out <- NTT(out) in place
     AGX_HIP(run_inverse(prime_range(plan->routes.inverse, basis->dst_first, basis->dst_first + T), d_xq, nullptr, d_out, fl, s));
     AGX_HIP(run_inverse(scaled, d_xp, nullptr, d_scratch, fl, s));
-    AGX_HIP(launch_moddown_coeff(plan->routes.forward, bv, d_out, d_scratch, batch, s));
+    AGX_HIP(launch_moddown_coeff(plan->routes.forward, bv, d_out, d_scratch, batch, round, s));
     AGX_HIP(run_forward(prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T), d_out, d_out, fl, s));
     return AGX_OK;
 }
@@ -313,6 +343,12 @@ int agx_ntt_mul_add_galois(const agx_ntt_plan* plan, const uint64_t* d_w, uint64
 }
 
 int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha) {
+    return agx_ntt_keyswitch_create_plain(ks, plan, q_count, p_first, p_count, alpha, 1);
+}
+
+// agx_ntt_keyswitch_create with the ModDown basis made by agx_ntt_basis_create_plain(..., t); the ModUp bases are the ordinary ones.  t = 0 is a bad
+// argument behind keyswitch_create's own rules; a t without an inverse modulo a special prime is what the ModDown basis reports: a bad modulus.
+int agx_ntt_keyswitch_create_plain(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha, uint64_t t) {
     if (!ks) return AGX_ERR_NULL_POINTER;
     *ks = nullptr;
     if (!plan) return AGX_ERR_NULL_POINTER;
@@ -325,6 +361,7 @@ int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, u
         for (uint32_t j = i + 1; j < A; ++j)
             if (modulus(i) == modulus(j)) return AGX_ERR_BAD_MODULUS;
     if (int rc = check_plan(plan)) return rc;
+    if (t == 0) return AGX_ERR_BAD_ARGUMENT;
     return guarded([&]() -> int {
         std::unique_ptr<agx_ntt_keyswitch> k(new (std::nothrow) agx_ntt_keyswitch);
         if (!k) return AGX_ERR_ALLOC;
@@ -346,7 +383,7 @@ int agx_ntt_keyswitch_create(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, u
                 if (int rc = add(first, count, p_first, p_count)) return rc;
             }
         }
-        if (int rc = agx_ntt_basis_create(&k->down, plan, p_first, p_count, 0, q_count)) return rc;
+        if (int rc = agx_ntt_basis_create_plain(&k->down, plan, p_first, p_count, 0, q_count, t)) return rc;
         *ks = k.release();
         return AGX_OK;
     });

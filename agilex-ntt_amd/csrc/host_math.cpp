@@ -147,4 +147,35 @@ bool moddown_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uin
     return all;
 }
 
+uint64_t half_product_mod(const uint64_t* src, uint32_t S, uint64_t q) {
+    uint64_t d = 1 % q;      // D mod q, one factor at a time
+    for (uint32_t k = 0; k < S; ++k) d = mul_mod(d, src[k] % q, q);
+    const uint64_t d1 = d ? d - 1 : q - 1;      // (D - 1) mod q
+    return mul_mod(d1, (q >> 1) + 1, q);        // q odd: (q + 1) / 2 = 2^-1, formed without q + 1
+}
+
+bool moddown_mode_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t t, const uint64_t* dinv, const uint64_t* mat, uint64_t* sn,
+                            uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p, uint64_t* dmat, uint64_t* dmat_p, uint64_t* cadd, uint64_t* hq) {
+    for (uint32_t i = 0; i < S; ++i) {
+        const uint64_t q = src[i];
+        uint64_t tinv = 0;
+        if (!inv_mod_euclid(t % q, q, &tinv)) return false;
+        sn[i] = mul_mod(sn[i], tinv, q);
+        sn_p[i] = shoup_quotient(sn[i], q);
+        sw[i] = mul_mod(sw[i], tinv, q);
+        sw_p[i] = shoup_quotient(sw[i], q);
+        cadd[i] = mul_mod(half_product_mod(src, S, q), dinv[i], q);
+    }
+    for (uint32_t j = 0; j < T; ++j) {
+        const uint64_t q = dst[j], tq = t % q;
+        for (uint32_t i = 0; i < S; ++i) {
+            const std::size_t at = (std::size_t)j * S + i;
+            dmat[at] = mul_mod(mat[at], tq, q);
+            dmat_p[at] = shoup_quotient(dmat[at], q);
+        }
+        hq[j] = mul_mod(half_product_mod(src, S, q), tq, q);
+    }
+    return true;
+}
+
 }  // namespace agx

@@ -56,4 +56,18 @@ bool basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint3
 bool moddown_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, const uint64_t* dinv, const uint64_t* n_inv, const uint64_t* w1n,
                        uint64_t* dall, uint64_t* dall_p, uint64_t* sn, uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p);
 
+// h mod q for h = floor(D / 2), D = prod src[i] odd, q odd and > 1: h is a multi-word integer (S up to 16 moduli of 62 bits) and is never formed.
+// 2 h = D - 1 exactly, so h = (D - 1) 2^-1 (mod q) with 2^-1 = (q + 1) / 2; D mod q is taken one factor at a time in 128 bits.
+uint64_t half_product_mod(const uint64_t* src, uint32_t S, uint64_t q);
+
+// What agx_ntt_basis_mod_down_mode and a plaintext modulus t >= 1 (agx_ntt_basis_create_plain) need beyond the two sets above, for the same moduli
+// (dinv, mat as basis_constants wrote them; sn, sw as moddown_constants wrote them).  t is any 64-bit value, reduced per modulus here.
+//   sn[i], sw[i] are multiplied by t^-1 mod src[i] in place (quotients sn_p / sw_p again): the scaled inverse then writes p_i t^-1 D_i^-1 mod src[i];
+//   dmat[j * S + i] = t D_i mod dst[j] with its quotient dmat_p: ModDown's matrix, a copy of its own (agx_ntt_basis_extend keeps mat);
+//   cadd[i] = h D_i^-1 mod src[i] and hq[j] = t h mod dst[j], h = floor(D / 2): the two constants of AGX_RESCALE_ROUND (csrc/moddown_arith.hpp).
+// false, nothing promised about the outputs, when t has no inverse modulo some source (for prime sources: t = 0 modulo one of them).
+// With t = 1 nothing changes: sn, sw stay, dmat = mat.
+bool moddown_mode_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t t, const uint64_t* dinv, const uint64_t* mat, uint64_t* sn,
+                            uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p, uint64_t* dmat, uint64_t* dmat_p, uint64_t* cadd, uint64_t* hq);
+
 }  // namespace agx

@@ -11,6 +11,7 @@
 #include "rb_registry.hpp"
 #include "modarith.hpp"
 #include "inner_reduce.hpp"
+#include "moddown_arith.hpp"      // the two per-word steps of AGX_RESCALE_ROUND in moddown_coeff_round_kernel
 
 #include <algorithm>
 #include <cstdlib>
@@ -437,29 +438,25 @@ __global__ void basis_coeff_kernel(const uint64_t* __restrict__ x, uint64_t* __r
 // then reads, finishes and writes back one word of each of the T target slabs, which the inverse left in [0,q_j): 8 (S + 2T) bytes per
 // coefficient.  The sum stays in [0,2q_j) term by term (basis_accumulate) and is brought below q_j for rescale_finish's reduced form, which
 // never forms 4q: any modulus below 2^62.  Constants are wave-uniform.  SMAX >= S as in basis_coeff_kernel.
+// AGX_RESCALE_ROUND (agx_ntt_basis_mod_down_mode) adds the two per-word steps of moddown_arith.hpp: c_i joins y_i modulo q_i as it is read, and
+// t h mod q_j leaves the sum, which stays in [0,2q_j), before it is brought below q_j.  One body (moddown_coeff_body.hpp, included in both), two
+// kernels: moddown_coeff_kernel (FLOOR: what it always was; rsrc and rdst are never read) and moddown_coeff_round_kernel.
 template <int SMAX>
 __global__ void moddown_coeff_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ y, const prime_consts* __restrict__ dst_consts,
                                      const ulonglong2* __restrict__ mat, const ulonglong2* __restrict__ dall, uint32_t S, uint32_t T, uint64_t per_prime) {
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t yi[SMAX];
-#pragma unroll
-        for (int i = 0; i < SMAX; ++i)
-            if ((uint32_t)i < S) yi[i] = y[(uint64_t)i * per_prime + e];
-        for (uint32_t j = 0; j < T; ++j) {
-            const uint64_t q = dst_consts[j].q, q2 = q << 1;
-            const ulonglong2* row = mat + (size_t)j * S;
-            const ulonglong2 d = dall[j];
-            uint64_t acc = 0;
-#pragma unroll
-            for (int i = 0; i < SMAX; ++i)
-                if ((uint32_t)i < S) {
-                    const ulonglong2 c = row[i];
-                    acc = basis_accumulate(acc, yi[i], c.x, c.y, q, q2);
-                }
-            uint64_t* o = out + (uint64_t)j * per_prime + e;
-            *o = rescale_finish<false>(*o, csub(acc, q), d.x, d.y, q);
-        }
-    }
+    [[maybe_unused]] constexpr bool ROUND = false;
+    [[maybe_unused]] constexpr const ulonglong2* rsrc = nullptr;
+    [[maybe_unused]] constexpr const uint64_t* rdst = nullptr;
+#include "moddown_coeff_body.hpp"
+}
+
+// rsrc: [S] {c_i = h D_i^-1 mod q_i, q_i}; rdst: [T] t h mod q_j
+template <int SMAX>
+__global__ void moddown_coeff_round_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ y, const prime_consts* __restrict__ dst_consts,
+                                           const ulonglong2* __restrict__ mat, const ulonglong2* __restrict__ dall, uint32_t S, uint32_t T, uint64_t per_prime,
+                                           const ulonglong2* __restrict__ rsrc, const uint64_t* __restrict__ rdst) {
+    [[maybe_unused]] constexpr bool ROUND = true;
+#include "moddown_coeff_body.hpp"
 }
 
 __device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
@@ -811,12 +808,16 @@ hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const u
     return hipGetLastError();
 }
 
-hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, hipStream_t s) {
+hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, bool round, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
     const dim3 grid(grid_1d(per_prime, 256));
     with_smax(bv.src_count, [&](auto smax) {
-        hipLaunchKernelGGL(moddown_coeff_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, out, y, pv.consts + bv.dst_first, bv.mat, bv.dall, bv.src_count,
-                           bv.dst_count, per_prime);
+        if (round)
+            hipLaunchKernelGGL(moddown_coeff_round_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, out, y, pv.consts + bv.dst_first, bv.down_mat, bv.dall,
+                               bv.src_count, bv.dst_count, per_prime, bv.round_src, bv.round_dst);
+        else
+            hipLaunchKernelGGL(moddown_coeff_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, out, y, pv.consts + bv.dst_first, bv.down_mat, bv.dall, bv.src_count,
+                               bv.dst_count, per_prime);
     });
     return hipGetLastError();
 }

@@ -29,6 +29,10 @@ struct basis_view {
     const ulonglong2* dinv = nullptr;   // [S] {D_i^-1 mod q_i, its precomputed quotient}, q_i the modulus of plan prime src_first + i, D_i = prod_{k != i} q_k
     const ulonglong2* mat = nullptr;    // [T][S] {D_i mod q_j, its precomputed quotient}, q_j the modulus of plan prime dst_first + j
     const ulonglong2* dall = nullptr;   // [T] {D^-1 mod q_j, its precomputed quotient}, D = prod_i q_i (agx_ntt_basis_mod_down; {0, 0} where it does not exist)
+    // agx_ntt_basis_mod_down / _mod_down_mode only (null in the view agx_ntt_basis_extend hands out)
+    const ulonglong2* down_mat = nullptr;   // [T][S] {t D_i mod q_j, its precomputed quotient}, t the basis' plaintext modulus (1: the words of mat)
+    const ulonglong2* round_src = nullptr;  // [S] {c_i = h D_i^-1 mod q_i, q_i}, h = floor(D / 2)                     (AGX_RESCALE_ROUND)
+    const uint64_t* round_dst = nullptr;    // [T] t h mod q_j                                                          (AGX_RESCALE_ROUND)
     uint32_t src_first = 0, src_count = 0, dst_first = 0, dst_count = 0;
 };
 
@@ -131,8 +135,9 @@ hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, ui
 hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const uint64_t* x, uint64_t* out, uint64_t batch, hipStream_t s);
 // the coefficient-domain step of agx_ntt_basis_mod_down's generic route: out_j[k] <- (out_j[k] - sum_i y_i[k] (D_i mod q_j)) D^-1 mod q_j in place on
 // out, dense [T][batch][n] in coefficient form with values in [0,q_j) (slab j under plan prime dst_first + j); y: dense [S][batch][n], y_i in
-// [0,q_i) as the scaled inverse of the source slabs left them.  pv: a view of the WHOLE plan (only its constants are read).  One launch.
-hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, hipStream_t s);
+// [0,q_i) as the scaled inverse of the source slabs left them.  pv: a view of the WHOLE plan (only its constants are read).  One launch.  The matrix is
+// bv.down_mat; round: AGX_RESCALE_ROUND, with bv.round_src and bv.round_dst (moddown_arith.hpp).
+hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, bool round, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

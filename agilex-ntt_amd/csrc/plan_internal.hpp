@@ -122,6 +122,12 @@ struct agx_ntt_basis {
     // view of the source primes with `consts` pointing here writes y_i = INTT_i(x_i) D_i^-1 mod q_i in [0,q_i): every inverse family reads its
     // last-stage constants from its view's consts, and the transform is linear.
     agx::device_buf<agx::prime_consts> d_src_consts;
+    // The plaintext modulus t of agx_ntt_basis_create_plain (1: agx_ntt_basis_create) is a property of ModDown alone and lives in constants only:
+    // d_src_consts carry t^-1 mod q_i as well, and ModDown reads a matrix of its own, so agx_ntt_basis_extend keeps d_mat.
+    agx::device_buf<ulonglong2> d_down_mat;  // [T][S] {t D_i mod q_j, quotient}
+    // AGX_RESCALE_ROUND (agx_ntt_basis_mod_down_mode), h = floor(D / 2); AGX_RESCALE_FLOOR never reads them
+    agx::device_buf<ulonglong2> d_round_src; // [S]    {h D_i^-1 mod q_i, q_i}
+    agx::device_buf<uint64_t> d_round_dst;   // [T]    t h mod q_j
 };
 
 // agx_ntt_keyswitch_*: the shape and the bases of one hybrid key switch, and nothing of the plan but a pointer (as a basis: the plan outlives the

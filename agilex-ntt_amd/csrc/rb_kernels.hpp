@@ -4,6 +4,7 @@
 #pragma once
 #include "rb_frame.hpp"
 #include "host_math.hpp"
+#include "moddown_arith.hpp"      // the two per-word steps of AGX_RESCALE_ROUND in moddown_round_rb2
 
 // mulhat_rb2 of a shape tuned for 8 waves/SIMD (n = 4096: 64 VGPRs) is compiled for 6 (80 VGPRs): with bhat's 16 words per thread
 // requested ahead of the last forward pass it needs 69-80 registers, 64 cost 12-92 bytes of scratch per lane, and 512-thread
@@ -524,94 +525,31 @@ extend_rb2(const uint64_t* __restrict__ x, uint64_t* __restrict__ out, const pri
 // out may BE xq (in place), by rescale_rb2's argument: a wave stores exactly the 64 C contiguous words its own lanes loaded from xq, and
 // store_last_layout relays them through the image behind a wavefront-scope release / acquire pair.  xq and out are therefore not __restrict__.
 // Block order and the three pinned scalars (group, base, yf) as in extend_rb2.
+// AGX_RESCALE_ROUND (agx_ntt_basis_mod_down_mode) is the same text with the two per-word steps of moddown_arith.hpp: every y_i gets c_i = rsrc[i].x added
+// modulo q_i = rsrc[i].y as it streams in, and hq_j = rdst[j] leaves the accumulators, which stay in [0,2q_j), before the forward passes: S + 1
+// add-and-conditional-subtract pairs per word.  The body is written once, in moddown_rb2_body.hpp, and included in its two kernels: moddown_rb2 (FLOOR:
+// what it always was, rsrc and rdst never read) and moddown_round_rb2.  A plaintext modulus t is in the constants alone (mat = t D_i mod q_j, the scaled
+// inverse's t^-1).
 template <int L, int R, int PPB, int ARITH, int MINW>
 __global__ void __launch_bounds__((1 << (L - R)) * PPB, (MINW > AGX_MULHAT_MAXW ? AGX_MULHAT_MAXW : MINW))
 moddown_rb2(const uint64_t* xq, const uint64_t* __restrict__ y, uint64_t* out, const prime_consts* __restrict__ consts, const ulonglong2* __restrict__ mat,
             const ulonglong2* __restrict__ dall, const twpair* __restrict__ tw_rb, uint32_t pairs_per_prime, uint64_t frames_x, int64_t prime_stride,
             int64_t poly_stride, uint32_t num_src, uint32_t dst_first, uint32_t num_dst) {
-    using F = frame_of<L, R, ARITH>;
-    constexpr int C = F::C, T = F::T;
-    static_assert(T >= 64, "one frame must span whole waves");
-    F f;
-    f.tid = threadIdx.x & (T - 1);
-    const uint32_t slot = PPB == 1 ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / T));      // a frame spans whole waves: wave-uniform
-    uint32_t group = blockIdx.x / num_dst;      // out of the vector unit: pinned to a scalar register (extend_rb2)
-    asm volatile("" : "+s"(group));
-    const uint32_t j = blockIdx.x - group * num_dst;
-    uint64_t fx = (uint64_t)group * PPB + slot;
-    const bool live = fx < frames_x;
-    if (!live) fx = frames_x - 1;                         // keep every thread on the barriers
-    const uint32_t prime = dst_first + j;
-    const uint64_t q = consts[prime].q, q2 = q << 1;
-    f.init_consts(q, consts[prime].est);
-    // q <= 2^60: rescale_finish takes both operands in [0,4q), so the transform may skip its last conditional subtracts and xq_j needs no reduction
-    f.lazy_out = F::LAZY16;
-    f.slab = reinterpret_cast<uint64_t*>(agx_dyn_lds) + (size_t)slot * F::slab_elems;
-    int64_t base = (int64_t)j * prime_stride + (int64_t)fx * poly_stride;
-    constexpr int GRP = 4, NG = C / GRP;      // registers per group of loads (y: GRP words; xq: two 16-byte loads), groups per thread
-    static_assert(C % GRP == 0 && NG % 2 == 0, "whole groups, and group 0 of every source in buffer 0");
-    const uint64_t* yf = y + (int64_t)fx * poly_stride;      // the frame under source 0 (wave-uniform: lanes add tid)
-    asm volatile("" : "+s"(base), "+s"(yf));      // wave-uniform, scalar registers of their own (extend_rb2)
-    const ulonglong2* row = mat + (size_t)j * num_src;
-    uint64_t acc[C];
-    {
-        uint64_t z[2][GRP];
-#pragma unroll
-        for (int r = 0; r < C; ++r) acc[r] = 0;
-        static_for<0, GRP>([&](auto I) { z[0][I] = yf[f.tid + (uint32_t)(int)I * T]; });
-        for (uint32_t i = 0; i < num_src; ++i) {      // wave-uniform
-            const ulonglong2 c = row[i];
-            const uint64_t* cur = yf + (int64_t)i * prime_stride;
-            const uint64_t* nxt = yf + (int64_t)(i + 1 < num_src ? i + 1 : i) * prime_stride;      // behind the last source: its own first group again (a cache hit, dropped)
-            static_for<0, NG>([&](auto Gq) {
-                constexpr int g = Gq;
-                const uint64_t* pg = g + 1 < NG ? cur + (uint32_t)((g + 1) * GRP) * T : nxt;      // opaque and scalar: every group shares the GRP lane offsets (extend_rb2)
-                asm volatile("" : "+s"(pg));
-                static_for<0, GRP>([&](auto I) { z[(g + 1) & 1][I] = pg[f.tid + (uint32_t)(int)I * T]; });
-                __builtin_amdgcn_sched_barrier(0);
-                static_for<0, GRP>([&](auto I) {
-                    constexpr int r = g * GRP + (int)I;
-                    asm volatile("" : "+v"(acc[r]));
-                    acc[r] = basis_accumulate(acc[r], z[g & 1][I], c.x, c.y, q, q2);
-                    asm volatile("" : "+v"(acc[r]));
-                });
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        }
-    }
-    const ulonglong2 d = dall[j];      // {D^-1 mod q_j, quotient}: wave-uniform
-    constexpr bool EARLY = !F::STREAM_TW && !F::SPLIT && F::NP >= 2 && NG <= 2;      // as mulhat_rb2 / rescale_rb2
-    const bhat_pair* xp = reinterpret_cast<const bhat_pair*>(xq + base + (uint32_t)f.tid * C);
-    bhat_pair w[EARLY ? NG : 2][GRP / 2];
-    auto request = [&](auto Gq) {
-        constexpr int g = Gq;
-        static_for<0, GRP / 2>([&](auto I) { w[EARLY ? g : (g & 1)][I] = xp[g * (GRP / 2) + (int)I]; });
-    };
-    if constexpr (EARLY) {
-        f.template forward_passes<0, F::NP - 1>(acc, tw_rb + (size_t)prime * pairs_per_prime);
-        static_for<0, NG>(request);
-        f.template forward_passes<F::NP - 1, F::NP>(acc, tw_rb + (size_t)prime * pairs_per_prime);
-    } else {
-        f.forward(acc, tw_rb + (size_t)prime * pairs_per_prime);
-        request(std::integral_constant<int, 0>{});
-    }
-    static_for<0, NG>([&](auto Gq) {
-        constexpr int g = Gq;
-        if constexpr (!EARLY && g + 1 < NG) request(std::integral_constant<int, g + 1>{});
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<0, GRP>([&](auto I) {
-            constexpr int i = I, r = g * GRP + i;
-            uint64_t v = w[EARLY ? g : (g & 1)][i / 2][i & 1];
-            // beyond 2^60 the difference wants xq_j (lazy: below 4q, which may not fit 64 bits -- reduce_4q never forms it) and the transform's
-            // result, which is then fully reduced, below q
-            if constexpr (!F::LAZY16) v = reduce_4q(v, q, q2);
-            asm volatile("" : "+v"(acc[r]));
-            acc[r] = rescale_finish<F::LAZY16>(v, acc[r], d.x, d.y, q);
-            asm volatile("" : "+v"(acc[r]));
-        });
-        __builtin_amdgcn_sched_barrier(0);
-    });
-    f.store_last_layout(acc, out, base, live);
+    [[maybe_unused]] constexpr bool ROUND = false;
+    [[maybe_unused]] constexpr const ulonglong2* rsrc = nullptr;
+    [[maybe_unused]] constexpr const uint64_t* rdst = nullptr;
+#include "moddown_rb2_body.hpp"
+}
+
+// rsrc: [S] {c_i = h D_i^-1 mod q_i, q_i}; rdst: [T] t h mod q_j (agx_ntt_basis: d_round_src, d_round_dst)
+template <int L, int R, int PPB, int ARITH, int MINW>
+__global__ void __launch_bounds__((1 << (L - R)) * PPB, (MINW > AGX_MULHAT_MAXW ? AGX_MULHAT_MAXW : MINW))
+moddown_round_rb2(const uint64_t* xq, const uint64_t* __restrict__ y, uint64_t* out, const prime_consts* __restrict__ consts, const ulonglong2* __restrict__ mat,
+                  const ulonglong2* __restrict__ dall, const twpair* __restrict__ tw_rb, uint32_t pairs_per_prime, uint64_t frames_x, int64_t prime_stride,
+                  int64_t poly_stride, uint32_t num_src, uint32_t dst_first, uint32_t num_dst, const ulonglong2* __restrict__ rsrc,
+                  const uint64_t* __restrict__ rdst) {
+    [[maybe_unused]] constexpr bool ROUND = true;
+#include "moddown_rb2_body.hpp"
 }
 
 // ---- host side: pass tables, launch glue and registry entries, written once for every kernel family ---------------------------------
@@ -746,12 +684,18 @@ hipError_t launch_extend_t(const plan_view& pv, const basis_view& bv, const uint
 
 // agx_ntt_basis_mod_down's second launch: pv is the view of the whole plan, the frame layout describes xq, y and out alike (dense); a linear grid, the
 // target prime fastest (moddown_rb2)
-template <class S, auto K>
-hipError_t launch_moddown_t(const plan_view& pv, const basis_view& bv, const uint64_t* xq, const uint64_t* y, uint64_t* out, const frame_layout& fl, hipStream_t s) {
+// K is the FLOOR kernel (what agx_ntt_basis_mod_down always launched), KR the ROUND one; the matrix is ModDown's own (bv.down_mat: t D_i mod q_j)
+template <class S, auto K, auto KR>
+hipError_t launch_moddown_t(const plan_view& pv, const basis_view& bv, const uint64_t* xq, const uint64_t* y, uint64_t* out, const frame_layout& fl, bool round,
+                            hipStream_t s) {
     const uint64_t blocks = (uint64_t)bv.dst_count * ((fl.batch + S::fpb - 1) / S::fpb);
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(K, dim3((unsigned)blocks), dim3(S::threads), S::lds, s, xq, y, out, pv.consts, bv.mat, bv.dall, pv.tw_rb, pv.rb->table_pairs, fl.batch,
-                       fl.prime_stride, fl.poly_stride, bv.src_count, bv.dst_first, bv.dst_count);
+    if (round)
+        hipLaunchKernelGGL(KR, dim3((unsigned)blocks), dim3(S::threads), S::lds, s, xq, y, out, pv.consts, bv.down_mat, bv.dall, pv.tw_rb, pv.rb->table_pairs, fl.batch,
+                           fl.prime_stride, fl.poly_stride, bv.src_count, bv.dst_first, bv.dst_count, bv.round_src, bv.round_dst);
+    else
+        hipLaunchKernelGGL(K, dim3((unsigned)blocks), dim3(S::threads), S::lds, s, xq, y, out, pv.consts, bv.down_mat, bv.dall, pv.tw_rb, pv.rb->table_pairs, fl.batch,
+                           fl.prime_stride, fl.poly_stride, bv.src_count, bv.dst_first, bv.dst_count);
     return hipGetLastError();
 }
 
@@ -849,8 +793,9 @@ constexpr rb_entry make_entry2(int id) {
     constexpr auto rescale = &rescale_rb2<L, R, PPB, ARITH, MINW>;
     constexpr auto extend = &extend_rb2<L, R, PPB, ARITH, MINW>;
     constexpr auto moddown = &moddown_rb2<L, R, PPB, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat, rescale, extend, moddown>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>,
-                          &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>, &launch_moddown_t<S, moddown>);
+    constexpr auto moddown_round = &moddown_round_rb2<L, R, PPB, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, mul, mulhat, rescale, extend, moddown, moddown_round>, &launch_inv_t<S, inv>, &launch_mul_t<S, mul>, &launch_mulhat_t<S, mulhat>,
+                          &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>, &launch_moddown_t<S, moddown, moddown_round>);
 }
 
 // forward kernel only (a plan's forward companion: rb_entry::fwd_companion), one frame per workgroup
@@ -892,9 +837,10 @@ constexpr rb_entry make_entry_single(int id) {
     constexpr auto rescale = &rescale_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto extend = &extend_rb2<L, R, 1, ARITH, MINW>;
     constexpr auto moddown = &moddown_rb2<L, R, 1, ARITH, MINW>;
-    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat, rescale, extend, moddown>,
+    constexpr auto moddown_round = &moddown_round_rb2<L, R, 1, ARITH, MINW>;
+    return shape_entry<S>(id, &launch_fwd_t<S, fwd>, &allow_lds<S::lds, fwd, inv, &polymul_rb2_park<L, R, ARITH, MINW>, &polysquare_rb2<L, R, ARITH, MINW>, mulhat, rescale, extend, moddown, moddown_round>,
                           &launch_inv_t<S, inv>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, mulhat>, &launch_rescale_t<S, rescale>, &launch_extend_t<S, extend>,
-                          &launch_moddown_t<S, moddown>);
+                          &launch_moddown_t<S, moddown, moddown_round>);
 }
 
 // entry e with forward calls of its plans routed to the forward-only entry `id` (rb_entry::fwd_companion)
@@ -910,7 +856,7 @@ hipError_t init_rb2_single_invloop_t() {
     using S = rb2_shape<L, R, 1, ARITH, MINW>;
     const hipError_t e = allow_lds<S::lds, &fwd_rb2<L, R, 1, ARITH, MINW>, &inv_rb2_loop<L, R, ARITH, MINW>, &polymul_rb2_park<L, R, ARITH, MINW>,
                                    &polysquare_rb2<L, R, ARITH, MINW>, &mulhat_rb2<L, R, 1, ARITH, MINW>, &rescale_rb2<L, R, 1, ARITH, MINW>, &extend_rb2<L, R, 1, ARITH, MINW>,
-                                   &moddown_rb2<L, R, 1, ARITH, MINW>>();
+                                   &moddown_rb2<L, R, 1, ARITH, MINW>, &moddown_round_rb2<L, R, 1, ARITH, MINW>>();
     return e != hipSuccess ? e : allow_lds<S::lds + kDloopMailboxBytes, &inv_rb2_dloop<L, R, ARITH, MINW>>();
 }
 template <int L, int R, int ARITH, int MINW>
@@ -919,7 +865,7 @@ constexpr rb_entry make_entry_single_invloop(int id) {
     return shape_entry<S>(id, &launch_fwd_t<S, &fwd_rb2<L, R, 1, ARITH, MINW>>, &init_rb2_single_invloop_t<L, R, ARITH, MINW>,
                           &launch_inv_rb2_dloop_t<L, R, ARITH, MINW>, &launch_mul_park_t<L, R, ARITH, MINW>, &launch_mulhat_t<S, &mulhat_rb2<L, R, 1, ARITH, MINW>>,
                           &launch_rescale_t<S, &rescale_rb2<L, R, 1, ARITH, MINW>>, &launch_extend_t<S, &extend_rb2<L, R, 1, ARITH, MINW>>,
-                          &launch_moddown_t<S, &moddown_rb2<L, R, 1, ARITH, MINW>>);
+                          &launch_moddown_t<S, &moddown_rb2<L, R, 1, ARITH, MINW>, &moddown_round_rb2<L, R, 1, ARITH, MINW>>);
 }
 
 }  // namespace AGX_TU

@@ -37,8 +37,10 @@ struct rb_entry {
     // agx_ntt_basis_mod_down's second launch, on a view of the WHOLE plan: out_j = (xq_j - NTT_j(sum_i y_i (D_i mod q_j))) D^-1 mod q_j for the basis'
     // targets, y dense [S][batch][n] (the scaled coefficient form of the source slabs, y_i in [0,q_i)), xq and out dense [T][batch][n] in NTT form (the
     // frame layout's strides serve all three); out may be xq.  The caller keeps T ceil(batch / ppb) workgroups within the grid limit.  null: the
-    // entry's plans take the generic route
-    hipError_t (*launch_moddown)(const plan_view&, const basis_view&, const uint64_t* xq, const uint64_t* y, uint64_t* out, const frame_layout&, hipStream_t) = nullptr;
+    // entry's plans take the generic route.  The matrix is the basis' down_mat (t D_i mod q_j); round: AGX_RESCALE_ROUND, a kernel of its own that also
+    // reads round_src and round_dst (moddown_round_rb2) -- without it the kernel agx_ntt_basis_mod_down always launched
+    hipError_t (*launch_moddown)(const plan_view&, const basis_view&, const uint64_t* xq, const uint64_t* y, uint64_t* out, const frame_layout&, bool round,
+                                 hipStream_t) = nullptr;
 };
 
 // The view of primes [lo, hi) of a route: every per-prime array starts at prime lo, so the launchers run on one slab or on the first

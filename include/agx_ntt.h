@@ -190,7 +190,9 @@ AGX_API int agx_ntt_polymul(const agx_ntt_plan* plan, const uint64_t* d_a, const
 AGX_API int agx_ntt_polymul_ntt(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c,
                                 uint64_t batch, uint64_t bhat_batch, void* stream);
 
-/* Exact division by the plan's LAST modulus q_L = q_{P-1} on NTT-form frames (CKKS "rescale", BGV / BFV modulus switching), P >= 2.
+/* Exact division by the plan's LAST modulus q_L = q_{P-1} on NTT-form frames, P >= 2: the CKKS "rescale" and the BFV form of modulus switching.
+ * It takes no plaintext modulus t, so it is NOT the BGV modulus switch, which must keep the value modulo t: that is agx_ntt_basis_create_plain with
+ * agx_ntt_basis_mod_down_mode below, which also rounds at any level of one plan (this call divides by the plan's last prime only).
  * Per coefficient, with X in [0, q_0 ... q_{P-1}) the integer the P residues represent and h = (q_L - 1) / 2:
  *   AGX_RESCALE_FLOOR: Y = floor(X / q_L)         AGX_RESCALE_ROUND: Y = floor((X + h) / q_L)
  * and out holds Y mod q_i for i < P-1, fully reduced.  Input and output are in NTT form (bit-reversed order, as agx_ntt_forward of this
@@ -268,6 +270,13 @@ AGX_API int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan
 AGX_API int agx_ntt_basis_destroy(agx_ntt_basis* basis);
 AGX_API int agx_ntt_basis_info(const agx_ntt_basis* basis, uint32_t* src_first, uint32_t* src_count, uint32_t* dst_first, uint32_t* dst_count, int* launches_ntt_form);
 AGX_API int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream);
+/* A basis with a PLAINTEXT MODULUS t for its ModDown (BGV): agx_ntt_basis_create's rules in its status order, then t == 0: AGX_ERR_BAD_ARGUMENT, and t = 0
+ * modulo a source modulus (t has no inverse there): AGX_ERR_BAD_MODULUS; the out-pointer stays NULL.  Any other 64-bit t is taken -- even, composite, above
+ * every modulus -- and reduced per modulus on the host.  t is a property of the basis' ModDown only (agx_ntt_basis_mod_down, _mod_down_mode below):
+ * agx_ntt_basis_extend on such a basis writes exactly the words it writes on the ordinary one.  t = 1 gives a basis whose every call equals the ordinary
+ * basis' call word for word; agx_ntt_basis_create is this call with t = 1. */
+AGX_API int agx_ntt_basis_create_plain(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count,
+                                       uint64_t t);
 
 /* ModDown of a hybrid key switch on NTT-form frames: the division of a polynomial known modulo the targets AND the sources of a basis by D = prod q_i
  * over the sources (the special primes), in one call.  Inputs, both in NTT form exactly as agx_ntt_forward / agx_ntt_forward_lazy of the plan write
@@ -276,8 +285,8 @@ AGX_API int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x
  *   y_i = p_i (D_i^-1 mod q_i) mod q_i in [0, q_i),    V = sum_i y_i D_i (an integer, V = X_P + u D, 0 <= u < S),    out_j = (a_j - V) (D^-1 mod q_j) mod q_j,
  * and d_out, dense [T][batch][n], holds NTT_j(out_j), fully reduced: d_out_j = (xq_j - NTT_j(V mod q_j)) D^-1 mod q_j word for word.  This is the
  * APPROXIMATE ModDown of every hybrid key switch, floor(X / D) - u with the u of agx_ntt_basis_extend: a deterministic integer formula, exact against
- * big-integer arithmetic.  With S = 1 it is agx_ntt_rescale(..., AGX_RESCALE_FLOOR) word for word.  There is NO ROUNDING MODE here (adding
- * floor(D / 2) first is a follow-up).
+ * big-integer arithmetic.  With S = 1 it is agx_ntt_rescale(..., AGX_RESCALE_FLOOR) word for word.  This call is the FLOOR mode; agx_ntt_basis_mod_down_mode
+ * below has the rounding mode, and on a basis made by agx_ntt_basis_create_plain both keep the value modulo its t.
  * d_scratch: S*batch*n words of device memory; it receives the scaled coefficient form y_i of the source slabs, its contents afterwards are
  * unspecified.  It may be exactly d_xp: the caller thereby GIVES THOSE SLABS UP, as agx_ntt_rescale allows for its last slab; otherwise it is disjoint
  * from d_xp and d_xp is left unchanged.  Aliasing: d_out == d_xq is allowed (in place); any other contact between d_out and d_xq, d_out touching d_xp or
@@ -300,6 +309,27 @@ AGX_API int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x
 AGX_API int agx_ntt_basis_mod_down(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch,
                                    uint64_t batch, void* stream);
 AGX_API int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launches);
+/* ModDown with a rounding mode and the basis' plaintext modulus t (1 on a basis of agx_ntt_basis_create).  Per coefficient, with a_j, p_i, D and D_i as
+ * above, h = floor(D / 2) under AGX_RESCALE_ROUND and h = 0 under AGX_RESCALE_FLOOR:
+ *   y_i   = ((p_i t^-1 mod q_i) + (h mod q_i)) D_i^-1 mod q_i        in [0, q_i)
+ *   V     = sum_i y_i D_i                                             (an integer, 0 <= V < S D)
+ *   out_j = (a_j - (t mod q_j) ((V - h) mod q_j)) D^-1 mod q_j        fully reduced
+ * delta = t (V - h) satisfies delta = X (mod D) and delta = 0 (mod t), so (X - delta) / D is an exact integer that equals X D^-1 modulo t: the BGV modulus
+ * switch and key-switch ModDown (the outputs carry the factor D^-1 mod t, which the caller tracks).  With t = 1: FLOOR is agx_ntt_basis_mod_down word for
+ * word, ROUND is floor((X + h) / D) - u with the same 0 <= u < S; with S = 1 and t = 1 it is agx_ntt_rescale in the same mode word for word (u = 0) -- at
+ * ANY level of one plan: sources {L - 1}, targets [0, L - 1).  A deterministic integer formula, exact against big-integer arithmetic.
+ * Operands, scratch rule, aliasing, status order, launch counts (agx_ntt_basis_mod_down_info serves both modes) and graph capturability are
+ * agx_ntt_basis_mod_down's, with one rule right behind the NULL rule, as in agx_ntt_rescale: a mode other than the two: AGX_ERR_BAD_ARGUMENT, nothing
+ * written.  agx_ntt_basis_mod_down on any basis is this call with AGX_RESCALE_FLOOR, and FLOOR launches the kernels that call always launched: t lives in
+ * the basis' constants alone (t^-1 in the scaled inverse's, a matrix t D_i mod q_j of ModDown's own) and costs no instruction.  ROUND launches kernels of
+ * its own with two more steps per word, both with wave-uniform constants: c_i = h D_i^-1 mod q_i joins y_i modulo q_i as the sources stream in, and
+ * t h mod q_j leaves the accumulators before the forward passes: S + 1 add-and-conditional-subtract pairs per word beside S Shoup products and a
+ * transform.  Measured (profiles/r14_mod_down_modes.md; S = 1, 2, 4 -> T = 4, 60-bit, n = 4096 with 4,096 frames per prime and n = 16384 with 1,024): ROUND takes
+ * 1.03 ... 1.05 of FLOOR's time, outside FLOOR's run-to-run spread in five of the six rows (469 against 449 us at S = 1, n = 4096; 1037 against 1005 us at S = 4,
+ * n = 16384); a basis with t = 65537 takes 0.995 ... 1.007 of the ordinary basis' time, inside the spread; FLOOR is level with what agx_ntt_basis_mod_down took
+ * before this call existed. */
+AGX_API int agx_ntt_basis_mod_down_mode(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch,
+                                        uint64_t batch, int mode, void* stream);
 
 /* The inner product of NTT-form frames: c_o = sum_t a_t o bhat_{t,o} mod q for o < outputs, one launch -- the centre of a hybrid key switch (the sum over
  * the decomposition digits of digit times key), and any other multiply-accumulate against operands kept in NTT form.  P = the plan's primes:
@@ -445,6 +475,13 @@ AGX_API int agx_ntt_keyswitch_info(const agx_ntt_keyswitch* ks, uint32_t* q_coun
 AGX_API int agx_ntt_keyswitch_scratch_words(const agx_ntt_keyswitch* ks, uint64_t batch, uint64_t* words);
 AGX_API int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat, const uint64_t* d_keyhat, uint64_t* d_out, uint64_t* d_scratch,
                                     uint64_t batch, void* stream);
+/* agx_ntt_keyswitch_create with the ModDown basis made by agx_ntt_basis_create_plain(..., t): the BGV key switch.  The ModUp bases are unchanged.  Every
+ * call on the handle then divides by P keeping the value modulo t (step 4 above in the FLOOR mode of agx_ntt_basis_mod_down_mode): apply, apply_decomposed,
+ * agx_ntt_keyswitch_mod_down and the double-hoisted route.  Status: agx_ntt_keyswitch_create's rules in its order, then t == 0: AGX_ERR_BAD_ARGUMENT; t = 0
+ * modulo a special prime: AGX_ERR_BAD_MODULUS; the out-pointer stays NULL.  t = 1 is agx_ntt_keyswitch_create.  There is no rounding inside the key
+ * switch's ModDown. */
+AGX_API int agx_ntt_keyswitch_create_plain(agx_ntt_keyswitch** ks, const agx_ntt_plan* plan, uint32_t q_count, uint32_t p_first, uint32_t p_count, uint32_t alpha,
+                                           uint64_t t);
 
 /* The key switch in two halves, for rotating ONE ciphertext by several steps (hoisting, Halevi-Shoup): steps 1 and 2 above depend on the ciphertext alone,
  * so they are done once, and every Galois element g pays for steps 3 and 4 only.  Both calls work on an agx_ntt_keyswitch handle as created above.

@@ -3,7 +3,7 @@ runs on paths bench.py's headline does not cover).
 Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes P --batch B --bits 60 --oop --launches K --variant ID]
        python3 tools/run_op.py --op auto --form {coeff,ntt} --galois G [--odd --reps 5 ...]   (agx_ntt_automorphism beside a device copy of the same words)
        python3 tools/run_op.py --op extend --src S [--dst T --only {both,fused,pair} --reps 5 ...]   (agx_ntt_basis_extend to NTT form beside the unfused pair)
-       python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent} --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
+       python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent,modes} --mode {floor,round} --plain T --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
        python3 tools/run_op.py --op ring --kind {add,sub,negate,add_galois,tensor} [--primes 6 --first 0 --count 4 --galois G --only {all,ring,copy,parent} --reps 7 ...]   (a ring call beside a copy of its model bytes and what it replaces)
        python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
@@ -38,7 +38,9 @@ ap.add_argument("--variant", type=int, default=None, help="registry id (AGX_VARI
 ap.add_argument("--ramp-seconds", type=float, default=0.5, help="run the operation this long before the warm-up launches so the GPU clock has ramped, as bench.py does (0 = cold)")
 ap.add_argument("--mulsets", type=int, default=0, help="mul: K rotating (a, b) operand sets, c and scratch separate (bench.py's n = 32768 product line); 0 = c aliases a on the slabs")
 ap.add_argument("--bcast", action="store_true", help="mulntt: one bhat frame per prime shared by the whole batch (bhat_batch = 1)")
-ap.add_argument("--mode", choices=["floor", "round"], default="round", help="rescale: AGX_RESCALE_FLOOR / AGX_RESCALE_ROUND")
+ap.add_argument("--mode", choices=["floor", "round"], default=None,
+                help="rescale (default round), moddown (default floor: agx_ntt_basis_mod_down_mode's mode): AGX_RESCALE_FLOOR / AGX_RESCALE_ROUND")
+ap.add_argument("--plain", type=int, default=1, metavar="T", help="moddown: the basis' plaintext modulus t (agx_ntt_basis_create_plain); 1 = the ordinary basis")
 ap.add_argument("--inplace", action="store_true", help="rescale: out == x with x's last slab as the scratch (default: out and scratch of their own)")
 ap.add_argument("--form", choices=["coeff", "ntt"], default="ntt", help="auto: AGX_FORM_COEFF / AGX_FORM_NTT")
 ap.add_argument("--galois", type=int, default=5, help="auto: the Galois element g (odd, below 2n; -1 = 2n - 1, conjugation)")
@@ -46,7 +48,7 @@ ap.add_argument("--odd", action="store_true", help="auto: both bases one word pa
 ap.add_argument("--reps", type=int, default=5, help="auto: timed repetitions of --launches calls each, alternating with the copy; medians are reported")
 ap.add_argument("--src", type=int, default=2, help="extend: source primes [0, S)")
 ap.add_argument("--dst", type=int, default=0, help="extend: target primes [0, T); 0 = every prime of the plan")
-ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "inner", "copy", "ring"], default=None,
+ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "modes", "inner", "copy", "ring"], default=None,
                 help="extend: time the AGX_FORM_NTT call (fused), the unfused pair, or both alternating (default); moddown: the two-launch route (fused), the "
                      "four-launch route on the same plan (generic: needs lib/libagxntt_diag.so through AGX_NTT_LIB), inverse + extend as before mod_down existed "
                      "(parent), or all alternating (default).  A counter run wants one")
@@ -62,6 +64,7 @@ ap.add_argument("--alpha", type=int, default=2, help="keyswitch: primes per digi
 ap.add_argument("--rotations", type=int, nargs="+", default=[8], help="hoist, dhoist: rotation counts R to time; rotation r uses the element galois^(r + 1) mod 2n")
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
+args.mode = args.mode or ("floor" if args.op == "moddown" else "round")
 if args.op == "moddown":
     args.dst = args.dst or 4
     args.primes = args.src + args.dst      # targets [0, T), sources [T, T + S)
@@ -196,12 +199,16 @@ def run_moddown():
       generic -- the same call sent down the four-launch route on the same plan (AGX_NTT_MOD_DOWN_GENERIC=1, honoured by lib/libagxntt_diag.so only);
       parent  -- what the library offered before mod_down: agx_ntt_inverse of the S source slabs on a plan over those primes, then
                  agx_ntt_basis_extend(..., AGX_FORM_NTT); strictly less work (no subtraction from xq, no product by D^-1).
+    The call is agx_ntt_basis_mod_down_mode in --mode (default floor) on a basis with the plaintext modulus --plain (default 1: the ordinary basis).
+    --only modes times that call four ways instead, alternating: floor and round on the ordinary basis, plain_floor and plain_round on a basis with
+    t = --plain (65537 when --plain is 1).
     Prints us per call (median of --reps repetitions of --launches calls, min and max beside it) and the ratios."""
     import statistics
     import time
 
     S, T = args.src, args.dst
-    basis = plan.basis(T, S, 0, T)
+    mode = agx.RESCALE_ROUND if args.mode == "round" else agx.RESCALE_FLOOR
+    basis = plan.basis(T, S, 0, T, t=args.plain)
     sources = agx.Plan(args.n, plan.moduli[T:], psi=[plan.psi(p) for p in range(T, T + S)])      # the parent's second plan, the same tables
     if args.variant is not None:
         sources.set_variant(agx.VARIANT_REGBLOCK_BASE + args.variant)
@@ -215,12 +222,12 @@ def run_moddown():
         sys.exit("--only generic / all need lib/libagxntt_diag.so: AGX_NTT_LIB=agilex-ntt_amd/lib/libagxntt_diag.so (after `make -C agilex-ntt_amd diag`)")
 
     def fused():
-        basis.mod_down(xq, xp, out.data_ptr(), scratch.data_ptr(), args.batch, stream)
+        basis.mod_down(xq, xp, out.data_ptr(), scratch.data_ptr(), args.batch, stream, mode)
 
     def generic():
         os.environ["AGX_NTT_MOD_DOWN_GENERIC"] = "1"
         try:
-            basis.mod_down(xq, xp, out.data_ptr(), scratch.data_ptr(), args.batch, stream)
+            basis.mod_down(xq, xp, out.data_ptr(), scratch.data_ptr(), args.batch, stream, mode)
         finally:
             os.environ["AGX_NTT_MOD_DOWN_GENERIC"] = "0"
 
@@ -234,6 +241,20 @@ def run_moddown():
         launches["generic"] = basis.mod_down_launches()
         os.environ["AGX_NTT_MOD_DOWN_GENERIC"] = "0"
     todo = [f for f in (fused, generic, parent) if args.only in ("all", f.__name__)]
+    plain = None
+    if args.only == "modes":
+        plain = plan.basis(T, S, 0, T, t=65537 if args.plain == 1 else args.plain)
+        ordinary = plan.basis(T, S, 0, T)
+
+        def form(name, b, m):
+            def call():
+                b.mod_down(xq, xp, out.data_ptr(), scratch.data_ptr(), args.batch, stream, m)
+            call.__name__ = name
+            launches[name] = b.mod_down_launches()
+            return call
+
+        todo = [form("floor", ordinary, agx.RESCALE_FLOOR), form("round", ordinary, agx.RESCALE_ROUND), form("plain_floor", plain, agx.RESCALE_FLOOR),
+                form("plain_round", plain, agx.RESCALE_ROUND)]
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -255,15 +276,19 @@ def run_moddown():
         for fn in todo:
             times[fn.__name__].append(timed(fn))
     med = {k: statistics.median(t) for k, t in times.items()}
-    head = f"moddown n={args.n} S={S} T={T} batch={args.batch} bits={args.bits}:"
+    head = f"moddown n={args.n} S={S} T={T} batch={args.batch} bits={args.bits} mode={args.mode} t={args.plain}:"
     parts = [f"{name} ({launches[name]} launches) {med[name]:.1f} us per call (min {min(t):.1f} max {max(t):.1f})" for name, t in times.items()]
     parts += [f"ratio fused/{other} {med['fused'] / med[other]:.3f}" for other in ("generic", "parent") if "fused" in med and other in med]
+    parts += [f"ratio {name}/floor {med[name] / med['floor']:.3f}" for name in ("round", "plain_floor", "plain_round") if "floor" in med and name in med]
     print(head, "; ".join(parts))
     if args.report:
         import json
 
         json.dump({"us": times, "launches": args.launches, "kernel_launches": launches}, open(args.report, "w"))
     basis.close()
+    if plain is not None:
+        plain.close()
+        ordinary.close()
     sources.close()
     plan.close()
 
