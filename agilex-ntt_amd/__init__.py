@@ -65,6 +65,10 @@ ABI = {
     "agx_ntt_basis_create_plain": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32, _u64]),
     "agx_ntt_basis_mod_down_mode": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_keyswitch_create_plain": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32, _u64]),
+    "agx_ntt_basis_create_aux": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32, _u32]),
+    "agx_ntt_basis_aux_info": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_u32), ctypes.POINTER(_int)]),
+    "agx_ntt_basis_extend_exact": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp]),
+    "agx_ntt_basis_extend_mont": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_inner_product": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _vp]),
     "agx_ntt_inner_product_galois": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp]),
     "agx_ntt_add": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp]),
@@ -354,6 +358,11 @@ class Plan:
         plaintext modulus its ModDown keeps the value modulo (BGV), 1 for none"""
         return Basis(self, src_first, src_count, dst_first, dst_count, t)
 
+    def basis_aux(self, src_first, src_count, dst_first, dst_count, aux_prime):
+        """Basis.with_aux(self, ...): that basis (t = 1) with the plan prime aux_prime, outside both ranges, as its auxiliary prime: the one that
+        extend_exact and extend_mont (the exact conversions of a BFV multiplication) need"""
+        return Basis.with_aux(self, src_first, src_count, dst_first, dst_count, aux_prime)
+
     def inner_product(self, d_a, d_bhat, d_c, batch, terms, outputs=1, bhat_batch=None, stream=0):
         """c_o = sum_t a_t o bhat_{t,o} mod q in one launch: d_a [terms][P][batch][n], d_bhat [terms][outputs][P][bhat_batch][n], d_c
         [outputs][P][batch][n]; inputs in [0,4q), c fully reduced, out of place; bhat_batch: None = batch, or 1 (one key frame per prime)"""
@@ -441,6 +450,35 @@ class Basis:
         self._h = _vp(None)
         handle = plan._h if isinstance(plan, Plan) else plan
         _check(lib().agx_ntt_basis_create_plain(ctypes.byref(self._h), handle, src_first, src_count, dst_first, dst_count, t), "basis_create_plain")
+
+    @classmethod
+    def with_aux(cls, plan, src_first, src_count, dst_first, dst_count, aux_prime):
+        """the basis of Basis(plan, src_first, src_count, dst_first, dst_count) with an auxiliary prime (agx_ntt_basis_create_aux): plan prime aux_prime,
+        outside both ranges.  Every other call behaves on it as on the ordinary basis; extend_exact and extend_mont need it."""
+        self = cls.__new__(cls)
+        self.plan = plan      # keeps a Plan alive
+        self._h = _vp(None)
+        handle = plan._h if isinstance(plan, Plan) else plan
+        _check(lib().agx_ntt_basis_create_aux(ctypes.byref(self._h), handle, src_first, src_count, dst_first, dst_count, aux_prime), "basis_create_aux")
+        return self
+
+    def aux_info(self):
+        """(has_aux, aux_prime, launches_ntt_form): whether the basis has an auxiliary prime, its index in the plan, and the kernel launches a FORM_NTT
+        call of extend_exact or extend_mont takes under the plan's current variant"""
+        has, prime, launches = _int(0), _u32(0), _int(0)
+        _check(lib().agx_ntt_basis_aux_info(self._h, ctypes.byref(has), ctypes.byref(prime), ctypes.byref(launches)), "basis_aux_info")
+        return bool(has.value), prime.value, launches.value
+
+    def extend_exact(self, d_x, d_xaux, d_out, batch, form=FORM_NTT, stream=0):
+        """the Shenoy-Kumaresan conversion: d_x [src_count][batch][n] and d_xaux [1][batch][n] (the residues modulo the auxiliary prime m), coefficient form,
+        lazy values allowed -> d_out [dst_count][batch][n]: (V - alpha D) mod q_j with V = sum_i y_i D_i and alpha = centre((V - r) D^-1 mod m): X' itself for
+        every |X'| < ((m - 1) / 2 - src_count) D; out of place, d_x and d_xaux may overlap"""
+        _check(lib().agx_ntt_basis_extend_exact(self._h, d_x, d_xaux, d_out, batch, form, stream), "basis_extend_exact")
+
+    def extend_mont(self, d_x, d_out, batch, form=FORM_NTT, stream=0):
+        """BEHZ's FastBConv_m~ and small Montgomery reduction: d_x [src_count][batch][n], coefficient form -> d_out [dst_count][batch][n]:
+        (V + alpha D) m^-1 mod q_j with y_i = x_i m D_i^-1 mod q_i, V = sum_i y_i D_i and alpha = centre(-V D^-1 mod m): X or X - D; out of place"""
+        _check(lib().agx_ntt_basis_extend_mont(self._h, d_x, d_out, batch, form, stream), "basis_extend_mont")
 
     def info(self):
         """(src_first, src_count, dst_first, dst_count, launches_ntt_form): the ranges, and the kernel launches a FORM_NTT call takes

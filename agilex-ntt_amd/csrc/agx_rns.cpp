@@ -229,6 +229,86 @@ int agx_ntt_basis_mod_down_mode(const agx_ntt_basis* basis, const uint64_t* d_xq
     return AGX_OK;
 }
 
+// agx_ntt_basis_create's rules in its order (the basis is made by it), then the auxiliary prime's: outside the plan or inside a range of the basis is a bad
+// argument, a modulus that is a source's or a target's a bad modulus
+int agx_ntt_basis_create_aux(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count,
+                             uint32_t aux_prime) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    *basis = nullptr;
+    agx_ntt_basis* made = nullptr;
+    if (int rc = agx_ntt_basis_create_plain(&made, plan, src_first, src_count, dst_first, dst_count, 1)) return rc;      // t = 1
+    std::unique_ptr<agx_ntt_basis> b(made);
+    auto inside = [&](uint32_t first, uint32_t count) { return aux_prime >= first && aux_prime - first < count; };
+    if (aux_prime >= plan->num_primes || inside(src_first, src_count) || inside(dst_first, dst_count)) return AGX_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        const uint32_t S = src_count, T = dst_count;
+        const uint64_t *src = &plan->moduli[src_first], *dst = &plan->moduli[dst_first], m = plan->moduli[aux_prime];
+        std::vector<uint64_t> dinv(S), dinv_p(S), mat((size_t)T * S), mat_p((size_t)T * S);
+        aux_constants c;
+        if (!basis_constants(src, S, dst, T, dinv.data(), dinv_p.data(), mat.data(), mat_p.data()) || !aux_basis_constants(src, S, dst, T, m, dinv.data(), mat.data(), &c))
+            return AGX_ERR_BAD_MODULUS;
+        auto pairs = [](const std::vector<uint64_t>& w, const std::vector<uint64_t>& p) {
+            std::vector<ulonglong2> v(w.size());
+            for (size_t k = 0; k < v.size(); ++k) v[k] = make_ulonglong2(w[k], p[k]);
+            return v;
+        };
+        if (int rc = b->d_aux_row.upload(pairs(c.row, c.row_p))) return rc;
+        if (int rc = b->d_aux_corr_exact.upload(pairs(c.corr_exact, c.corr_exact_p))) return rc;
+        if (int rc = b->d_aux_mdinv.upload(pairs(c.mdinv, c.mdinv_p))) return rc;
+        if (int rc = b->d_aux_mmat.upload(pairs(c.mmat, c.mmat_p))) return rc;
+        if (int rc = b->d_aux_corr_mont.upload(pairs(c.corr_mont, c.corr_mont_p))) return rc;
+        b->has_aux = true, b->aux_prime = aux_prime, b->aux_m = m;
+        b->aux_k_exact = c.k_exact, b->aux_k_exact_p = c.k_exact_p, b->aux_k_mont = c.k_mont, b->aux_k_mont_p = c.k_mont_p;
+        *basis = b.release();
+        return AGX_OK;
+    });
+}
+
+int agx_ntt_basis_aux_info(const agx_ntt_basis* basis, int* has_aux, uint32_t* aux_prime, int* launches_ntt_form) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    if (has_aux) *has_aux = basis->has_aux ? 1 : 0;
+    if (aux_prime) *aux_prime = basis->aux_prime;
+    if (launches_ntt_form) *launches_ntt_form = 1 + forward_launches(basis->plan);      // the coefficient-form launch, then the plan's forward on the targets
+    return AGX_OK;
+}
+
+// agx_ntt_basis_extend_exact (d_xaux set by its caller's NULL rule) and agx_ntt_basis_extend_mont (d_xaux null: an empty range): agx_ntt_basis_extend's rules
+// in its order, the auxiliary prime's right behind the NULL rule
+static int extend_aux_call(const agx_ntt_basis* basis, bool exact, const uint64_t* d_x, const uint64_t* d_xaux, uint64_t* d_out, uint64_t batch, int out_form,
+                           void* stream) {
+    if (!basis->has_aux) return AGX_ERR_BAD_ARGUMENT;
+    const agx_ntt_plan* plan = basis->plan;
+    if (out_form != AGX_FORM_COEFF && out_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    const uint32_t S = basis->src_count, T = basis->dst_count;
+    if (!aligned8(d_x) || !aligned8(d_xaux) || !aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of x ([S][batch][n]), xaux ([1][batch][n]) and out ([T][batch][n]) alike
+    if (!dense_fits(plan->n, S, batch) || !dense_fits(plan->n, T, batch)) return AGX_ERR_BAD_ARGUMENT;
+    // out of place only: out touches neither input; the inputs are only read and may overlap freely
+    const uint64_t slab = batch * plan->n;
+    if (ranges_touch(addr(d_x), S * slab, addr(d_out), T * slab) || ranges_touch(addr(d_xaux), exact ? slab : 0, addr(d_out), T * slab)) return AGX_ERR_BAD_ARGUMENT;
+    if (batch == 0) return AGX_OK;
+    aux_view av;
+    av.row = basis->d_aux_row, av.m = basis->aux_m;
+    av.exact = aux_set{basis->d_dinv, basis->d_mat, basis->d_aux_corr_exact, basis->aux_k_exact, basis->aux_k_exact_p};
+    av.mont = aux_set{basis->d_aux_mdinv, basis->d_aux_mmat, basis->d_aux_corr_mont, basis->aux_k_mont, basis->aux_k_mont_p};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AGX_HIP(launch_basis_aux_coeff(plan->routes.forward, view_of(basis), av, exact, d_x, d_xaux, d_out, batch, s));
+    // the plan's forward on the view of the target primes, in place
+    if (out_form == AGX_FORM_NTT) AGX_HIP(run_forward(prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T), d_out, d_out, fl, s));
+    return AGX_OK;
+}
+
+int agx_ntt_basis_extend_exact(const agx_ntt_basis* basis, const uint64_t* d_x, const uint64_t* d_xaux, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    if (!basis || !d_x || !d_xaux || !d_out) return AGX_ERR_NULL_POINTER;
+    return extend_aux_call(basis, true, d_x, d_xaux, d_out, batch, out_form, stream);
+}
+
+int agx_ntt_basis_extend_mont(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    if (!basis || !d_x || !d_out) return AGX_ERR_NULL_POINTER;
+    return extend_aux_call(basis, false, d_x, nullptr, d_out, batch, out_form, stream);
+}
+
 // agx_ntt_inner_product and agx_ntt_inner_product_galois: one statement of the rules, the Galois element's between the overlap rule and the device's
 static int inner_product_call(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_bhat, uint64_t* d_c, uint64_t batch, uint64_t bhat_batch,
                               uint32_t terms, uint32_t outputs, uint32_t galois_elt, void* stream) {

@@ -178,4 +178,38 @@ bool moddown_mode_constants(const uint64_t* src, uint32_t S, const uint64_t* dst
     return true;
 }
 
+bool aux_basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t m, const uint64_t* dinv, const uint64_t* mat, aux_constants* out) {
+    // D mod q (skip == S) or D_skip mod q, one factor at a time
+    auto d_mod = [&](uint32_t skip, uint64_t q) {
+        uint64_t r = 1 % q;
+        for (uint32_t k = 0; k < S; ++k)
+            if (k != skip) r = mul_mod(r, src[k] % q, q);
+        return r;
+    };
+    auto neg = [](uint64_t v, uint64_t q) { return v ? q - v : 0; };
+    aux_constants& c = *out;
+    for (auto* v : {&c.row, &c.row_p, &c.mdinv, &c.mdinv_p}) v->assign(S, 0);
+    for (auto* v : {&c.corr_exact, &c.corr_exact_p, &c.corr_mont, &c.corr_mont_p}) v->assign(T, 0);
+    c.mmat.assign((std::size_t)T * S, 0), c.mmat_p.assign((std::size_t)T * S, 0);
+    if (!inv_mod_euclid(d_mod(S, m), m, &c.k_exact)) return false;
+    c.k_mont = neg(c.k_exact, m);
+    c.k_exact_p = shoup_quotient(c.k_exact, m), c.k_mont_p = shoup_quotient(c.k_mont, m);
+    for (uint32_t i = 0; i < S; ++i) {
+        c.row[i] = d_mod(i, m), c.row_p[i] = shoup_quotient(c.row[i], m);
+        c.mdinv[i] = mul_mod(dinv[i], m % src[i], src[i]), c.mdinv_p[i] = shoup_quotient(c.mdinv[i], src[i]);
+    }
+    for (uint32_t j = 0; j < T; ++j) {
+        const uint64_t q = dst[j];
+        uint64_t minv = 0;
+        if (!inv_mod_euclid(m % q, q, &minv)) return false;
+        c.corr_exact[j] = d_mod(S, q), c.corr_exact_p[j] = shoup_quotient(c.corr_exact[j], q);
+        c.corr_mont[j] = neg(mul_mod(c.corr_exact[j], minv, q), q), c.corr_mont_p[j] = shoup_quotient(c.corr_mont[j], q);
+        for (uint32_t i = 0; i < S; ++i) {
+            const std::size_t at = (std::size_t)j * S + i;
+            c.mmat[at] = mul_mod(mat[at], minv, q), c.mmat_p[at] = shoup_quotient(c.mmat[at], q);
+        }
+    }
+    return true;
+}
+
 }  // namespace agx

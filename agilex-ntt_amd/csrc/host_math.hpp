@@ -70,4 +70,16 @@ uint64_t half_product_mod(const uint64_t* src, uint32_t S, uint64_t q);
 bool moddown_mode_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t t, const uint64_t* dinv, const uint64_t* mat, uint64_t* sn,
                             uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p, uint64_t* dmat, uint64_t* dmat_p, uint64_t* cadd, uint64_t* hq);
 
+// What agx_ntt_basis_extend_exact and agx_ntt_basis_extend_mont need beyond basis_constants (dinv, mat as it wrote them), for the same moduli and an
+// auxiliary modulus m, odd, > 1 and < 2^62 (csrc/bfv_conv_arith.hpp has the formulas); every word comes with its quotient (_p):
+//   row[i] = D_i mod m;   k_exact = D^-1 mod m,   k_mont = -D^-1 mod m;
+//   corr_exact[j] = D mod dst[j];
+//   mdinv[i] = m dinv[i] mod src[i],   mmat[j * S + i] = mat[j * S + i] m^-1 mod dst[j],   corr_mont[j] = -D m^-1 mod dst[j].
+// false, nothing promised about the outputs, when D has no inverse modulo m or m none modulo some target (for primes: m equals a source or a target).
+struct aux_constants {
+    std::vector<uint64_t> row, row_p, corr_exact, corr_exact_p, mdinv, mdinv_p, mmat, mmat_p, corr_mont, corr_mont_p;
+    uint64_t k_exact = 0, k_exact_p = 0, k_mont = 0, k_mont_p = 0;
+};
+bool aux_basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t m, const uint64_t* dinv, const uint64_t* mat, aux_constants* out);
+
 }  // namespace agx

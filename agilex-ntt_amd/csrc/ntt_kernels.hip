@@ -12,6 +12,7 @@
 #include "modarith.hpp"
 #include "inner_reduce.hpp"
 #include "moddown_arith.hpp"      // the two per-word steps of AGX_RESCALE_ROUND in moddown_coeff_round_kernel
+#include "bfv_conv_arith.hpp"     // the per-word steps of agx_ntt_basis_extend_exact / _mont in basis_aux_coeff_kernel
 
 #include <algorithm>
 #include <cstdlib>
@@ -433,6 +434,47 @@ __global__ void basis_coeff_kernel(const uint64_t* __restrict__ x, uint64_t* __r
     }
 }
 
+// agx_ntt_basis_extend_exact (EXACT) and agx_ntt_basis_extend_mont, coefficient form: basis_coeff_kernel's shape -- one thread per (frame, coefficient),
+// the y_i in registers under SMAX, wave-uniform constants -- with the correction by the auxiliary prime m (bfv_conv_arith.hpp).  A thread reads its S source
+// words (and, EXACT, its word of the auxiliary slab), forms V mod m through one more constant row {D_i mod m} as it forms the y_i, then alpha ONCE (one
+// Shoup product by k and the centring), and finishes every target with one Shoup product |alpha| c_j, added or subtracted by alpha's sign: 8 (S + 1 + T)
+// bytes per coefficient (EXACT) or 8 (S + T).  The two forms differ in their constants alone (aux_set): the Montgomery form's m and m^-1 are folded into
+// dinv, mat and c, and it reads no auxiliary word.
+template <int SMAX, bool EXACT>
+__global__ void basis_aux_coeff_kernel(const uint64_t* __restrict__ x, const uint64_t* __restrict__ xaux, uint64_t* __restrict__ out,
+                                       const prime_consts* __restrict__ src_consts, const prime_consts* __restrict__ dst_consts, const ulonglong2* __restrict__ dinv,
+                                       const ulonglong2* __restrict__ mat, const ulonglong2* __restrict__ row, const ulonglong2* __restrict__ corr, uint64_t m,
+                                       uint64_t k, uint64_t kp, uint32_t S, uint32_t T, uint64_t per_prime) {
+    const uint64_t m2 = m << 1;
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t y[SMAX];
+        uint64_t vm = 0;
+#pragma unroll
+        for (int i = 0; i < SMAX; ++i)
+            if ((uint32_t)i < S) {
+                const ulonglong2 d = dinv[i], c = row[i];
+                y[i] = basis_scale(x[(uint64_t)i * per_prime + e], d.x, d.y, src_consts[i].q);
+                vm = basis_accumulate(vm, y[i], c.x, c.y, m, m2);
+            }
+        const uint64_t r = EXACT ? bfv_reduce_lazy(xaux[e], m) : 0;
+        bool negative;
+        const uint64_t mag = bfv_centre(bfv_alpha(csub(vm, m), r, k, kp, m), m, &negative);
+        for (uint32_t j = 0; j < T; ++j) {
+            const uint64_t q = dst_consts[j].q, q2 = q << 1;
+            const ulonglong2* mrow = mat + (size_t)j * S;
+            uint64_t acc = 0;
+#pragma unroll
+            for (int i = 0; i < SMAX; ++i)
+                if ((uint32_t)i < S) {
+                    const ulonglong2 c = mrow[i];
+                    acc = basis_accumulate(acc, y[i], c.x, c.y, q, q2);
+                }
+            const ulonglong2 c = corr[j];
+            out[(uint64_t)j * per_prime + e] = bfv_correct(acc, mag, negative, c.x, c.y, q);
+        }
+    }
+}
+
 // agx_ntt_basis_mod_down, generic route, in the coefficient domain: out_j[e] <- (out_j[e] - sum_i y_i[e] (D_i mod q_j)) D^-1 mod q_j.  One thread
 // per (frame, coefficient): it reads its S words of y (y_i in [0,q_i), as the scaled inverse of the source slabs wrote them: no basis_scale here),
 // then reads, finishes and writes back one word of each of the T target slabs, which the inverse left in [0,q_j): 8 (S + 2T) bytes per
@@ -804,6 +846,22 @@ hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const u
     with_smax(bv.src_count, [&](auto smax) {
         hipLaunchKernelGGL(basis_coeff_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, x, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, bv.dinv,
                            bv.mat, bv.src_count, bv.dst_count, per_prime);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_basis_aux_coeff(const plan_view& pv, const basis_view& bv, const aux_view& av, bool exact, const uint64_t* x, const uint64_t* xaux, uint64_t* out,
+                                  uint64_t batch, hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    const dim3 grid(grid_1d(per_prime, 256));
+    const aux_set& c = exact ? av.exact : av.mont;
+    with_smax(bv.src_count, [&](auto smax) {
+        if (exact)
+            hipLaunchKernelGGL((basis_aux_coeff_kernel<decltype(smax)::value, true>), grid, dim3(256), 0, s, x, xaux, out, pv.consts + bv.src_first,
+                               pv.consts + bv.dst_first, c.dinv, c.mat, av.row, c.corr, av.m, c.k, c.kp, bv.src_count, bv.dst_count, per_prime);
+        else
+            hipLaunchKernelGGL((basis_aux_coeff_kernel<decltype(smax)::value, false>), grid, dim3(256), 0, s, x, xaux, out, pv.consts + bv.src_first,
+                               pv.consts + bv.dst_first, c.dinv, c.mat, av.row, c.corr, av.m, c.k, c.kp, bv.src_count, bv.dst_count, per_prime);
     });
     return hipGetLastError();
 }

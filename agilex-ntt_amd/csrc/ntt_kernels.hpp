@@ -36,6 +36,20 @@ struct basis_view {
     uint32_t src_first = 0, src_count = 0, dst_first = 0, dst_count = 0;
 };
 
+// agx_ntt_basis_extend_exact / _mont: what a basis with an auxiliary prime m keeps beside the above (bfv_conv_arith.hpp has the formulas).  One
+// constant set per form, of one shape, so that one kernel body serves both.
+struct aux_set {
+    const ulonglong2* dinv = nullptr;   // [S] exact: {D_i^-1 mod q_i, quotient} (the words of basis_view::dinv); mont: {m D_i^-1 mod q_i, quotient}
+    const ulonglong2* mat = nullptr;    // [T][S] exact: {D_i mod q_j, quotient} (the words of basis_view::mat); mont: {D_i m^-1 mod q_j, quotient}
+    const ulonglong2* corr = nullptr;   // [T] exact: {D mod q_j, quotient}; mont: {-D m^-1 mod q_j, quotient}
+    uint64_t k = 0, kp = 0;             // exact: D^-1 mod m; mont: -D^-1 mod m; and the quotient
+};
+struct aux_view {
+    const ulonglong2* row = nullptr;    // [S] {D_i mod m, quotient}
+    uint64_t m = 0;
+    aux_set exact, mont;
+};
+
 struct rb_entry;   // one configuration of the kernel registry (rb_registry.hpp): static storage, valid for the life of the library
 
 // device-side view of a plan
@@ -133,6 +147,10 @@ hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, ui
 // [T][batch][n] (slab j under plan prime dst_first + j), out_j = sum_i y_i (D_i mod q_j) mod q_j in [0,q_j), y_i = x_i D_i^-1 mod q_i in [0,q_i).
 // pv: a view of the WHOLE plan (only its constants are read); out of place (the ranges must not touch).  One launch.
 hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const uint64_t* x, uint64_t* out, uint64_t batch, hipStream_t s);
+// agx_ntt_basis_extend_exact (exact: xaux dense [1][batch][n] under the auxiliary prime, values in [0,4m)) and agx_ntt_basis_extend_mont (xaux is not read)
+// in coefficient form: x and out as launch_basis_coeff takes them, out fully reduced; out touches neither input.  One launch.
+hipError_t launch_basis_aux_coeff(const plan_view& pv, const basis_view& bv, const aux_view& av, bool exact, const uint64_t* x, const uint64_t* xaux, uint64_t* out,
+                                  uint64_t batch, hipStream_t s);
 // the coefficient-domain step of agx_ntt_basis_mod_down's generic route: out_j[k] <- (out_j[k] - sum_i y_i[k] (D_i mod q_j)) D^-1 mod q_j in place on
 // out, dense [T][batch][n] in coefficient form with values in [0,q_j) (slab j under plan prime dst_first + j); y: dense [S][batch][n], y_i in
 // [0,q_i) as the scaled inverse of the source slabs left them.  pv: a view of the WHOLE plan (only its constants are read).  One launch.  The matrix is

@@ -128,6 +128,16 @@ struct agx_ntt_basis {
     // AGX_RESCALE_ROUND (agx_ntt_basis_mod_down_mode), h = floor(D / 2); AGX_RESCALE_FLOOR never reads them
     agx::device_buf<ulonglong2> d_round_src; // [S]    {h D_i^-1 mod q_i, q_i}
     agx::device_buf<uint64_t> d_round_dst;   // [T]    t h mod q_j
+    // agx_ntt_basis_create_aux only: the auxiliary prime m = the modulus of plan prime aux_prime, and the constants of agx_ntt_basis_extend_exact and
+    // agx_ntt_basis_extend_mont (host_math.hpp: aux_basis_constants).  The exact form reads d_dinv and d_mat as agx_ntt_basis_extend does.
+    bool has_aux = false;
+    uint32_t aux_prime = 0;
+    uint64_t aux_m = 0, aux_k_exact = 0, aux_k_exact_p = 0, aux_k_mont = 0, aux_k_mont_p = 0;
+    agx::device_buf<ulonglong2> d_aux_row;         // [S]    {D_i mod m, quotient}
+    agx::device_buf<ulonglong2> d_aux_corr_exact;  // [T]    {D mod q_j, quotient}
+    agx::device_buf<ulonglong2> d_aux_mdinv;       // [S]    {m D_i^-1 mod q_i, quotient}
+    agx::device_buf<ulonglong2> d_aux_mmat;        // [T][S] {D_i m^-1 mod q_j, quotient}
+    agx::device_buf<ulonglong2> d_aux_corr_mont;   // [T]    {-D m^-1 mod q_j, quotient}
 };
 
 // agx_ntt_keyswitch_*: the shape and the bases of one hybrid key switch, and nothing of the plan but a pointer (as a basis: the plan outlives the

@@ -331,6 +331,48 @@ AGX_API int agx_ntt_basis_mod_down_info(const agx_ntt_basis* basis, int* launche
 AGX_API int agx_ntt_basis_mod_down_mode(const agx_ntt_basis* basis, const uint64_t* d_xq, const uint64_t* d_xp, uint64_t* d_out, uint64_t* d_scratch,
                                         uint64_t batch, int mode, void* stream);
 
+/* The two EXACT base conversions of a BFV multiplication (BEHZ: Bajard, Eynard, Hasan, Zucca, SAC 2016), on a basis with an AUXILIARY PRIME m: one more prime
+ * of the plan, outside both ranges of the basis.  agx_ntt_basis_extend leaves V = X + u D with 0 <= u < S; these two remove u D by integer formulas through m
+ * -- no floating point, no rounded quotient estimate; exact against big-integer arithmetic like every RNS call here.  With D, D_i as above, x' = x mod q and
+ * centre(a) = a for a in [0, (m - 1) / 2], a - m for a above (m is odd, so centre(-a mod m) = -centre(a)):
+ * agx_ntt_basis_extend_exact, the Shenoy-Kumaresan conversion.  Inputs in coefficient form: x_i under the S sources, values in [0, 4 q_i); r under m, values
+ * in [0, 4m).
+ *   y_i = x_i' D_i^-1 mod q_i in [0, q_i),    V = sum_i y_i D_i,    alpha = centre(((V - r') D^-1) mod m),    out_j = (V - alpha D) mod q_j, fully reduced.
+ * Property: let X' be an integer with X' = x_i (mod q_i) for every source and r = X' (mod m); write X' = X + k D with X in [0, D), and V = X + u D.  Whenever
+ * |u - k| <= (m - 1) / 2, out_j = X' mod q_j exactly: it is exact for every X' with |X'| < ((m - 1) / 2 - S) D, negative ones included.  The formula, not the
+ * property, is the contract; it is defined for every input.
+ * agx_ntt_basis_extend_mont, BEHZ's FastBConv_m~ followed by SmMRq_m~ (the small Montgomery reduction).  Inputs: x_i under the sources, coefficient form,
+ * values in [0, 4 q_i).
+ *   y_i = x_i' (m D_i^-1) mod q_i,    V = sum_i y_i D_i,    alpha = centre((-V D^-1) mod m),    out_j = (V + alpha D) m^-1 mod q_j, fully reduced.
+ * Property: W = (V + alpha D) / m is an exact integer and W = X (mod D); when m > 2S, W is X - D or X, with -D/2 < W < D/2 + S D / m: the u D of the approximate
+ * conversion shrinks to at most one D, on the centred side, which keeps the noise of the tensor product small.  out_j = W mod q_j.
+ *   create_aux : agx_ntt_basis_create's rules in its status order, then aux_prime >= P or inside the source or the target range: AGX_ERR_BAD_ARGUMENT; m equal
+ *                to a source or target modulus: AGX_ERR_BAD_MODULUS.  On any failure the out-pointer is cleared.  The basis has t = 1, and
+ *                agx_ntt_basis_extend, _mod_down and _mod_down_mode behave on it word for word as on the basis of agx_ntt_basis_create with the same ranges.
+ *   aux_info   : has_aux (0 on an ordinary basis), the auxiliary prime's index, and launches_ntt_form = 1 + the launches of the plan's forward under its
+ *                CURRENT variant.  Any out-pointer may be NULL.
+ *   the calls  : d_x dense [S][batch][n], d_xaux dense [1][batch][n], d_out dense [T][batch][n]; out_form as in agx_ntt_basis_extend.  Pointers need 8-byte
+ *                alignment only.  OUT OF PLACE ONLY: d_out touches neither d_x nor d_xaux; d_x and d_xaux may overlap freely (in a BFV multiplication d_xaux
+ *                is the slab that follows d_x's); ranges that meet end to end do not touch.  Status order: agx_ntt_basis_extend's, with one rule right behind
+ *                the NULL rule: a basis without an auxiliary prime: AGX_ERR_BAD_ARGUMENT, nothing written.  batch == 0: AGX_OK, nothing launched.
+ *                Asynchronous on `stream`, allocates and synchronises nothing (capturable into a hipGraph).  Any plan serves, forward-only plans included.
+ * AGX_FORM_COEFF is ONE launch on every plan, the shape of agx_ntt_basis_extend's: one thread per coefficient reads its S source words (S + 1: exact), forms
+ * V mod m through one more constant row {D_i mod m}, alpha once (one Shoup product by D^-1 mod m and the centring), walks the T targets and finishes each with
+ * one Shoup product |alpha| (D mod q_j), added or subtracted by alpha's sign: 8 (S + 1 + T) bytes per coefficient (exact), 8 (S + T) (mont).  m is folded
+ * into the D_i^-1 constants and m^-1 into the matrix and D mod q_j: the Montgomery form costs no instruction beyond the exact form, the two are one body
+ * with two constant sets (csrc/bfv_conv_arith.hpp has the per-word steps and their range arguments, for any odd modulus below 2^62).  AGX_FORM_NTT is that
+ * launch followed by the plan's forward on the target slabs in place; there is no fused one-launch form.  Measured (profiles/r15_bfv_conversions.md; coefficient form, S = 2, 4 -> T = 3, 5, 60-bit, n = 4096 with 4,096
+ * frames per prime and n = 16384 with 1,024): exact takes 1.28 ... 1.44 and mont 1.21 ... 1.38 of the time of agx_ntt_basis_extend of the same S into T + 1 targets, outside its
+ * run-to-run spread in every row (217 against 153 us at S = 2, T = 3; 464 against 351 us at S = 4, T = 5), and 1.49 ... 1.93 / 1.65 ... 2.01 of a device copy of their model bytes:
+ * the kernel is bound by its S + 1 + T additional Shoup products, not by its traffic.  mont's median is 0.94 ... 0.96 of exact's; their spreads overlap in half of the rows.
+ * INTEGRATION.md, "BFV multiplication (BEHZ)", has a whole multiplication on these calls.  Groups: no group form, as for agx_ntt_basis_extend. */
+AGX_API int agx_ntt_basis_create_aux(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count,
+                                     uint32_t aux_prime);
+AGX_API int agx_ntt_basis_aux_info(const agx_ntt_basis* basis, int* has_aux, uint32_t* aux_prime, int* launches_ntt_form);
+AGX_API int agx_ntt_basis_extend_exact(const agx_ntt_basis* basis, const uint64_t* d_x, const uint64_t* d_xaux, uint64_t* d_out, uint64_t batch, int out_form,
+                                       void* stream);
+AGX_API int agx_ntt_basis_extend_mont(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream);
+
 /* The inner product of NTT-form frames: c_o = sum_t a_t o bhat_{t,o} mod q for o < outputs, one launch -- the centre of a hybrid key switch (the sum over
  * the decomposition digits of digit times key), and any other multiply-accumulate against operands kept in NTT form.  P = the plan's primes:
  *   d_a    dense [terms][P][batch][n]

@@ -4,6 +4,7 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op auto --form {coeff,ntt} --galois G [--odd --reps 5 ...]   (agx_ntt_automorphism beside a device copy of the same words)
        python3 tools/run_op.py --op extend --src S [--dst T --only {both,fused,pair} --reps 5 ...]   (agx_ntt_basis_extend to NTT form beside the unfused pair)
        python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent,modes} --mode {floor,round} --plain T --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
+       python3 tools/run_op.py --op bfvconv --src S --dst T [--only {all,exact,mont,parent,copy} --reps 7 ...]   (agx_ntt_basis_extend_exact / _mont, coefficient form, beside agx_ntt_basis_extend into T + 1 targets and a copy of the model's bytes)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
        python3 tools/run_op.py --op ring --kind {add,sub,negate,add_galois,tensor} [--primes 6 --first 0 --count 4 --galois G --only {all,ring,copy,parent} --reps 7 ...]   (a ring call beside a copy of its model bytes and what it replaces)
        python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
@@ -26,7 +27,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "inner", "keyswitch", "hoist", "dhoist", "ring"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -48,7 +49,7 @@ ap.add_argument("--odd", action="store_true", help="auto: both bases one word pa
 ap.add_argument("--reps", type=int, default=5, help="auto: timed repetitions of --launches calls each, alternating with the copy; medians are reported")
 ap.add_argument("--src", type=int, default=2, help="extend: source primes [0, S)")
 ap.add_argument("--dst", type=int, default=0, help="extend: target primes [0, T); 0 = every prime of the plan")
-ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "modes", "inner", "copy", "ring"], default=None,
+ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "modes", "inner", "copy", "ring", "exact", "mont"], default=None,
                 help="extend: time the AGX_FORM_NTT call (fused), the unfused pair, or both alternating (default); moddown: the two-launch route (fused), the "
                      "four-launch route on the same plan (generic: needs lib/libagxntt_diag.so through AGX_NTT_LIB), inverse + extend as before mod_down existed "
                      "(parent), or all alternating (default).  A counter run wants one")
@@ -68,10 +69,13 @@ args.mode = args.mode or ("floor" if args.op == "moddown" else "round")
 if args.op == "moddown":
     args.dst = args.dst or 4
     args.primes = args.src + args.dst      # targets [0, T), sources [T, T + S)
+if args.op == "bfvconv":
+    args.dst = args.dst or 3
+    args.primes = args.src + args.dst + 1      # sources [0, S), targets [S, S + T), the auxiliary prime S + T
 if args.op in ("keyswitch", "hoist", "dhoist"):
     args.pfirst = args.qcount if args.pfirst is None else args.pfirst
     args.primes = args.pfirst + args.pcount
-args.only = args.only or ("all" if args.op == "moddown" else "both")
+args.only = args.only or ("all" if args.op in ("moddown", "bfvconv") else "both")
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
 if args.variant is not None:
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + args.variant)
@@ -326,6 +330,61 @@ def _fmt(t):
     import statistics
 
     return f"{statistics.median(t):.1f} ({min(t):.1f} ... {max(t):.1f})"
+
+
+def run_bfvconv():
+    """agx_ntt_basis_extend_exact and agx_ntt_basis_extend_mont in coefficient form from the sources [0, S) to the targets [S, S + T) with the auxiliary
+    prime S + T, alternating in one process with two yardsticks: agx_ntt_basis_extend (AGX_FORM_COEFF) of the same S sources into the T + 1 primes
+    [S, S + T + 1) -- the same matrix work, the auxiliary row included, without the correction -- and a device copy that moves the exact form's model bytes,
+    8 (S + 1 + T) per coefficient.  Prints us per call: median (min ... max) of --reps groups of --launches calls."""
+    import statistics
+
+    S, T = args.src, args.dst
+    words = args.batch * args.n
+    basis = plan.basis_aux(0, S, S, T, S + T)
+    parent = plan.basis(0, S, S, T + 1)
+    # fill_synthetic writes a slab for EVERY prime of the plan: x holds the S source slabs, then T unused ones, then the auxiliary slab at S + T
+    x = torch.empty(args.primes * words, dtype=torch.int64, device="cuda")
+    out = torch.empty((T + 1) * words, dtype=torch.int64, device="cuda")
+    plan.fill_synthetic(x.data_ptr(), args.batch, 0, 42, stream)
+    xaux = x.data_ptr() + 8 * (S + T) * words
+    half = (S + 1 + T) * words // 2      # a copy reads and writes this many words: together the model's bytes
+    c_src, c_dst = (torch.empty(half, dtype=torch.int64, device="cuda") for _ in range(2))
+
+    def exact():
+        basis.extend_exact(x.data_ptr(), xaux, out.data_ptr(), args.batch, agx.FORM_COEFF, stream)
+
+    def mont():
+        basis.extend_mont(x.data_ptr(), out.data_ptr(), args.batch, agx.FORM_COEFF, stream)
+
+    def extend():
+        parent.extend(x.data_ptr(), out.data_ptr(), args.batch, agx.FORM_COEFF, stream)
+
+    def copy():
+        c_dst.copy_(c_src)
+
+    todo = [f for name, f in (("exact", exact), ("mont", mont), ("parent", extend), ("copy", copy)) if args.only in ("all", name)]
+    times = _alternate(todo)
+    model = {"exact": 8.0 * words * (S + 1 + T), "mont": 8.0 * words * (S + T), "extend": 8.0 * words * (S + T + 1), "copy": 16.0 * half}
+    print(f"bfvconv n={args.n} S={S} T={T} batch={args.batch} bits={args.bits} launches_ntt_form={basis.aux_info()[2]}:",
+          "; ".join(f"{name} {_fmt(t)} us, {model[name] / statistics.median(t) / 1e3:.0f} GB/s of model traffic" for name, t in times.items()))
+    if "copy" in times:
+        for name in ("exact", "mont", "extend"):
+            if name in times:
+                print(f"  {name}/copy {statistics.median(times[name]) / statistics.median(times['copy']):.3f}", end="")
+        print()
+    if "extend" in times:
+        for name in ("exact", "mont"):
+            if name in times:
+                print(f"  {name}/extend {statistics.median(times[name]) / statistics.median(times['extend']):.3f}", end="")
+        print()
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "model_bytes": model}, open(args.report, "w"))
+    basis.close()
+    parent.close()
+    plan.close()
 
 
 def _pointwise_and_add(p, a_ptr, key_rep, acc, tmp, batch, terms, outputs, qcol):
@@ -787,6 +846,9 @@ if args.op == "moddown":
     sys.exit(0)
 if args.op == "extend":
     run_extend()
+    sys.exit(0)
+if args.op == "bfvconv":
+    run_bfvconv()
     sys.exit(0)
 slabs = [torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(args.slabs)]
 for i, s in enumerate(slabs):
