@@ -300,7 +300,8 @@ AGX_API int agx_ntt_basis_create_plain(agx_ntt_basis** basis, const agx_ntt_plan
  * TWO launches for n = 1024 ... 32768 whenever some modulus is 2^31 or larger: the plan's inverse of the S source slabs into the scratch with
  * n^-1 D_i^-1 in the place of n^-1 (the inverse is linear, so it writes y_i itself, at no cost: the constants live in the basis, plan creation is
  * unchanged and no second plan is needed); then, one target prime's frame on chip, the sum over the sources, the forward transform and the difference
- * with xq_j as it streams in (T workgroups per frame; S Shoup products per output word) -- at every S up to 16 (profiles/r09_mod_down.md).
+ * with xq_j as it streams in (T workgroups per frame; S Shoup products per output word) -- at every S up to 16 (timed at S = 1, 2 and 4:
+ * profiles/r09_mod_down.md; tested word for word at every S = 1 ... 16, on this route and on the four-launch one: tests/test_gpu_source_counts.py).
  * Otherwise -- n <= 512, plans whose moduli are all below 2^31, plans forced onto AGX_VARIANT_LDS_RADIX2 -- the inverse of xq into out, the scaled
  * inverse of xp into the scratch, one coefficient-domain pass over out and the plan's forward of out in place: four launches (seven at n = 32768 under
  * AGX_VARIANT_LDS_RADIX2, whose transforms take two each); no memory beyond the scratch, and in place works as in agx_ntt_rescale.

@@ -1,12 +1,15 @@
 """The case builders and runners that more than one GPU test file of the RNS calls uses: the key switch's shapes, cases and one-call runner
 (test_gpu_keyswitch.py, test_gpu_keyswitch_hoisted.py, test_hoist_reference.py) and the inner product's operands, layouts and device words
-(test_gpu_inner_product.py, test_gpu_inner_product_galois.py).  The expected words come from rns_ref.py.  Cases are computed once and read-only."""
+(test_gpu_inner_product.py, test_gpu_inner_product_galois.py), the key switch's wide shapes (test_gpu_keyswitch_wide.py, test_hoist_reference.py) and the
+bases and cases of the sweep over every source count (test_gpu_source_counts.py, test_rns_ref.py).  The expected words come from rns_ref.py and
+moddown_modes_ref.py.  Cases are computed once and read-only."""
 import functools
 
 import numpy as np
 
 from gpu_util import Layout, canary
-from rns_ref import active_of, digits_of, keyswitch_ref, spread
+from moddown_modes_ref import mod_down_mode, special_sources
+from rns_ref import active_of, convert, digits_of, keyswitch_ref, oracle_forward_set, residues, special_values, spread
 
 # ---- the key switch: (q_count, p_first, p_count, alpha) on a plan of six primes ----------------------------------------------------------------
 TOP, LOWER, FOUR_DIGITS, ONE_DIGIT = (4, 4, 2, 2), (3, 4, 2, 2), (4, 5, 1, 1), (4, 4, 2, 4)
@@ -45,6 +48,73 @@ def run_keyswitch(dev, ks, chat, key, batch):
     got = dev.to_host(d_out)
     assert np.array_equal(dev.to_host(d_chat), chat) and np.array_equal(dev.to_host(d_key), key), "an input changed"
     return got
+
+
+# ---- the key switch at wide shapes, on a plan of 33 primes (test_gpu_keyswitch_wide.py, test_hoist_reference.py) ---------------------------------
+WIDE_PRIMES = 33
+TWO_FULL_DIGITS = (12, 12, 6, 6)      # two full digits, six sources both ways
+WIDE = (TWO_FULL_DIGITS,
+        (13, 14, 7, 5),               # special primes apart (two ModUp bases per digit), a short last digit of 3
+        (16, 16, 1, 1),               # sixteen digits, the limit: a 16-term inner product
+        (24, 24, 8, 8),               # A = 32
+        (16, 16, 16, 16),             # alpha and p_count at their limits, one digit
+        (9, 20, 9, 9))                # capacity 16 partly filled, far-apart special primes
+WIDE_IDS = ["two-full-digits", "apart-short-last", "sixteen-digits", "thirty-two-active", "limits-one-digit", "nine-far-apart"]
+
+
+# ---- every source count: bases on a plan of 19 primes (test_gpu_source_counts.py, test_rns_ref.py) -------------------------------------------------
+SWEEP_PRIMES = 19
+SOURCE_COUNTS = tuple(range(1, 17))
+MIXED_WIDTHS = tuple([30, 60, 61, 62][k % 4] for k in range(SWEEP_PRIMES))
+
+
+def extend_shape(S):
+    """(source first, source count, target first, target count): sources [0, S), targets [S - 1, S + 2) -- the first target is the last source, the
+    other two are foreign"""
+    return 0, S, S - 1, 3
+
+
+def mod_down_shape(S):
+    """targets [0, 3), sources [3, 3 + S)"""
+    return 3, S, 0, 3
+
+
+@functools.lru_cache(maxsize=None)
+def extend_sweep_case(orc, n, moduli, S, batch, seed):
+    """agx_ntt_basis_extend on extend_shape(S): (x reduced, x spread over [0,4q), {0: the coefficient-form words, 1: their NTT form}), flat, computed
+    once per case (read-only).  Frame 0 opens with rns_ref.special_values (8 + S of them), random behind; the first target's words are x_{S-1}"""
+    sf, S, df, T = extend_shape(S)
+    src, dst = moduli[sf:sf + S], moduli[df:df + T]
+    rng = np.random.default_rng(seed)
+    x = np.stack([rng.integers(0, int(q), size=(batch, n), dtype=np.uint64) for q in src])
+    special = residues(special_values(src), src)
+    assert special.shape[1] == 8 + S <= n
+    x[:, 0, :special.shape[1]] = special
+    coeff = convert(x, src, dst)
+    assert np.array_equal(coeff[0], x[S - 1].reshape(-1)), "a target that is a source must get its residue back"
+    out = (x.reshape(-1), spread(rng, x, src).reshape(-1), {0: coeff.reshape(-1), 1: oracle_forward_set(orc, n, dst, coeff).reshape(-1)})
+    for w in (*out[:2], *out[2].values()):
+        w.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def mod_down_sweep_case(orc, n, moduli, S, batch, seed, t, mode):
+    """agx_ntt_basis_mod_down_mode on mod_down_shape(S): (xq, xp reduced; xq, xp spread over [0,4q); the expected words [3][batch][n]), NTT form, flat,
+    computed once per case (read-only).  The sources' coefficient form opens frame 0 with moddown_modes_ref.special_sources(src, t, mode)"""
+    sf, S, df, T = mod_down_shape(S)
+    src, dst = moduli[sf:sf + S], moduli[df:df + T]
+    rng = np.random.default_rng(seed)
+    a = np.stack([rng.integers(0, int(q), size=(batch, n), dtype=np.uint64) for q in dst])
+    p = np.stack([rng.integers(0, int(q), size=(batch, n), dtype=np.uint64) for q in src])
+    special = special_sources(src, t, mode)
+    p[:, 0, :special.shape[1]] = special
+    xq, xp = oracle_forward_set(orc, n, dst, a), oracle_forward_set(orc, n, src, p)
+    want = oracle_forward_set(orc, n, dst, mod_down_mode(a, p, src, dst, t, mode))
+    out = (xq.reshape(-1), xp.reshape(-1), spread(rng, xq, dst).reshape(-1), spread(rng, xp, src).reshape(-1), want.reshape(-1))
+    for w in out:
+        w.setflags(write=False)
+    return out
 
 
 # ---- the inner product ------------------------------------------------------------------------------------------------------------------------

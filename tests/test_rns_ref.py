@@ -6,15 +6,27 @@ import numpy as np
 import pytest
 
 from gpu_util import moduli_for, oracle_tables, rescale_reference
+from rns_cases import MIXED_WIDTHS, SWEEP_PRIMES, extend_shape, mod_down_shape
 from rns_ref import convert, lift, mod_down, oracle_forward_set, oracle_inverse_set, product, residues, special_values, spread
 
 SIZES = (8, 64)
+WIDE_SOURCE_COUNTS = (5, 8, 9, 15)      # inside and at the ends of the kernels' source capacities 8 and 16 (test_gpu_source_counts.py sweeps 1 ... 16)
 
 
 def _bases(orc, n):
     """(source moduli, target moduli) of mixed widths: one, two and three sources, targets that contain the sources and targets apart from them"""
     m = moduli_for(orc.find_prime, n, [60, 30, 61, 30, 60, 60])
     return [(m[2:3], m), (m[1:3], m), (m[4:6], m[:4]), (m[3:6], m[:3])]
+
+
+def _wide_bases(orc, n, S):
+    """the bases of test_gpu_source_counts.py at S sources on 19 primes, all 60-bit and of mixed widths: [extend's (the first target is the last source),
+    ModDown's (targets apart from the sources)] per plan"""
+    out = []
+    for widths in ([60] * SWEEP_PRIMES, MIXED_WIDTHS):
+        m = moduli_for(orc.find_prime, n, widths)
+        out += [(m[sf:sf + sc], m[df:df + dc]) for sf, sc, df, dc in (extend_shape(S), mod_down_shape(S))]
+    return out
 
 
 def _random_residues(rng, moduli, count):
@@ -25,8 +37,18 @@ def _random_residues(rng, moduli, count):
 def test_convert_is_the_residues_of_the_lift(orc, n):
     """on the special values and on random residues, reduced and spread over [0, 4q): out_j = V mod q_j with V = X + u D, 0 <= u < S; a target that is
     a source gets its residue back"""
-    rng = np.random.default_rng(n)
-    for src, dst in _bases(orc, n):
+    _check_convert(np.random.default_rng(n), n, _bases(orc, n))
+
+
+@pytest.mark.parametrize("S", WIDE_SOURCE_COUNTS)
+@pytest.mark.parametrize("n", SIZES)
+def test_convert_is_the_residues_of_the_lift_at_wide_source_counts(orc, n, S):
+    """the same properties on the sweep's bases: S = 5, 8, 9, 15 sources"""
+    _check_convert(np.random.default_rng(n + S), n, _wide_bases(orc, n, S))
+
+
+def _check_convert(rng, n, bases):
+    for src, dst in bases:
         D, special = product(src), special_values(src)
         x = np.concatenate([residues(special, src), _random_residues(rng, src, 4 * n)], axis=1)
         V = lift(x, src)
@@ -55,8 +77,18 @@ def test_mod_down_from_one_source_is_the_rescale_in_floor_mode(orc, n):
 def test_closed_form_regions_of_the_mod_down_inputs(orc, n):
     """X = D Y + V with V the lift of the sources gives Y mod q_j ("quotient"), and a_j = V mod q_j gives zero: the two constructions test_gpu_mod_down's
     make_inputs plants, here on random sources and on the special values"""
-    rng = np.random.default_rng(n + 2)
-    for src, dst in _bases(orc, n)[2:]:
+    _check_closed_forms(np.random.default_rng(n + 2), n, _bases(orc, n)[2:])
+
+
+@pytest.mark.parametrize("S", WIDE_SOURCE_COUNTS)
+@pytest.mark.parametrize("n", SIZES)
+def test_closed_form_regions_of_the_mod_down_inputs_at_wide_source_counts(orc, n, S):
+    """the same constructions from S = 5, 8, 9, 15 sources into three targets apart from them"""
+    _check_closed_forms(np.random.default_rng(n + 2 + S), n, _wide_bases(orc, n, S)[1::2])
+
+
+def _check_closed_forms(rng, n, bases):
+    for src, dst in bases:
         D = product(src)
         p = np.concatenate([residues(special_values(src), src), _random_residues(rng, src, 2 * n)], axis=1)
         V = lift(p, src)
