@@ -13,8 +13,64 @@ using namespace agx;
 
 static bool targets_fit_grid(uint32_t T, uint64_t batch, int ppb) { return (uint64_t)T * ((batch + ppb - 1) / ppb) <= 0x7fffffffull; }      // grid limit of the fused kernels: T workgroups per group of ppb frames
 static bool dense_fits(uint32_t n, uint32_t slabs, uint64_t frames) { return layout_fits(n, slabs, frames, (int64_t)(frames * n), (int64_t)n); }      // one dense range of slabs x frames x n words (formed in 128 bits)
-static basis_view view_of(const agx_ntt_basis* b) {
-    return basis_view{b->d_dinv, b->d_mat, b->d_dall, b->d_down_mat, b->d_round_src, b->d_round_dst, b->src_first, b->src_count, b->dst_first, b->dst_count};
+
+// A basis on the current device from its image: the buffers, then the views every call of the basis hands to its kernel
+static int instantiate_basis(agx_ntt_basis** out, const agx_ntt_plan* plan, uint32_t src_first, uint32_t dst_first, uint32_t aux_prime, const basis_request& rq,
+                             const basis_image& img) {
+    std::unique_ptr<agx_ntt_basis> b(new (std::nothrow) agx_ntt_basis);
+    if (!b) return AGX_ERR_ALLOC;
+    b->plan = plan, b->moddown_legal = img.moddown_legal, b->has_aux = rq.m != 0, b->aux_prime = b->has_aux ? aux_prime : 0;
+    // the source primes' constants (the plan's host copy) with the inverse's last-stage factors scaled by t^-1 D_i^-1
+    std::vector<prime_consts> sc(plan->consts.begin() + src_first, plan->consts.begin() + src_first + rq.S);
+    for (uint32_t i = 0; i < rq.S; ++i) sc[i].n_inv = img.sn[i].w, sc[i].n_inv_p = img.sn[i].p, sc[i].w1n = img.sw[i].w, sc[i].w1n_p = img.sw[i].p;
+    int rc = AGX_OK;
+    auto put = [&](device_buf<ulonglong2>& to, const std::vector<shoup_pair>& pairs) { if (rc == AGX_OK) rc = upload_pairs(to, pairs); };
+    put(b->d_dinv, img.dinv), put(b->d_mat, img.mat), put(b->d_down_mat, img.down_mat), put(b->d_round_src, img.round_src);
+    if (rc == AGX_OK) rc = b->d_round_dst.upload(img.round_dst);
+    put(b->d_dall, img.dall);
+    if (rc == AGX_OK) rc = b->d_src_consts.upload(sc);
+    if (b->has_aux) put(b->d_aux_row, img.aux_row), put(b->d_aux_corr_exact, img.aux_corr_exact), put(b->d_aux_mdinv, img.aux_mdinv), put(b->d_aux_mmat, img.aux_mmat), put(b->d_aux_corr_mont, img.aux_corr_mont);
+    if (rc) return rc;
+    basis_view& v = b->view;
+    v.dinv = b->d_dinv, v.mat = b->d_mat, v.dall = b->d_dall, v.down_mat = b->d_down_mat, v.round_src = b->d_round_src, v.round_dst = b->d_round_dst;
+    v.src_first = src_first, v.src_count = rq.S, v.dst_first = dst_first, v.dst_count = rq.T;
+    if (b->has_aux) {
+        aux_view& a = b->aux;
+        a.row = b->d_aux_row, a.m = rq.m;
+        a.exact.dinv = b->d_dinv, a.exact.mat = b->d_mat, a.exact.corr = b->d_aux_corr_exact, a.exact.k = img.k_exact.w, a.exact.kp = img.k_exact.p;
+        a.mont.dinv = b->d_aux_mdinv, a.mont.mat = b->d_aux_mmat, a.mont.corr = b->d_aux_corr_mont, a.mont.k = img.k_mont.w, a.mont.kp = img.k_mont.p;
+    }
+    *out = b.release();
+    return AGX_OK;
+}
+
+// agx_ntt_basis_create_plain and (t = 1, aux set) agx_ntt_basis_create_aux: validate, build the image, instantiate.  The rules in their order: NULL; the
+// ranges; the plan; sources that share a factor, a bad modulus; t = 0, a bad argument; t without an inverse modulo a source, a bad modulus; then the auxiliary
+// prime's: outside the plan or inside a range of the basis is a bad argument, a modulus that is a source's or a target's a bad modulus.
+static int create_basis(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count, uint64_t t,
+                        bool aux, uint32_t aux_prime) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    *basis = nullptr;
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes;
+    auto in_plan = [&](uint32_t first, uint32_t count) { return count >= 1 && count <= P && first <= P - count; };
+    if (!in_plan(src_first, src_count) || !in_plan(dst_first, dst_count) || src_count > AGX_BASIS_MAX_SRC) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    return guarded([&]() -> int {
+        auto inside = [&](uint32_t first, uint32_t count) { return aux_prime >= first && aux_prime - first < count; };
+        const bool aux_placed = aux && aux_prime < P && !inside(src_first, src_count) && !inside(dst_first, dst_count);
+        std::vector<uint64_t> n_inv(src_count), w1n(src_count);
+        for (uint32_t i = 0; i < src_count; ++i) n_inv[i] = plan->consts[src_first + i].n_inv, w1n[i] = plan->consts[src_first + i].w1n;
+        const basis_request rq{&plan->moduli[src_first], src_count, &plan->moduli[dst_first], dst_count, n_inv.data(), w1n.data(), t, aux_placed ? plan->moduli[aux_prime] : 0};
+        basis_image img;
+        const basis_fault fault = prepare_basis_image(img, rq);      // reports the first of source, t, aux
+        if (fault == basis_fault::source) return AGX_ERR_BAD_MODULUS;
+        if (t == 0) return AGX_ERR_BAD_ARGUMENT;
+        if (fault == basis_fault::t) return AGX_ERR_BAD_MODULUS;
+        if (aux && !aux_placed) return AGX_ERR_BAD_ARGUMENT;
+        if (fault == basis_fault::aux) return AGX_ERR_BAD_MODULUS;
+        return instantiate_basis(basis, plan, src_first, dst_first, aux_prime, rq, img);
+    });
 }
 
 extern "C" {
@@ -57,58 +113,14 @@ int agx_ntt_basis_create(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32
     return agx_ntt_basis_create_plain(basis, plan, src_first, src_count, dst_first, dst_count, 1);      // t = 1: every constant is what it was without a t
 }
 
-// agx_ntt_basis_create's rules in its order, then t: 0 is a bad argument, a t without an inverse modulo a source a bad modulus
 int agx_ntt_basis_create_plain(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count,
                                uint64_t t) {
-    if (!basis) return AGX_ERR_NULL_POINTER;
-    *basis = nullptr;
-    if (!plan) return AGX_ERR_NULL_POINTER;
-    const uint32_t P = plan->num_primes;
-    auto in_plan = [&](uint32_t first, uint32_t count) { return count >= 1 && count <= P && first <= P - count; };
-    if (!in_plan(src_first, src_count) || !in_plan(dst_first, dst_count) || src_count > AGX_BASIS_MAX_SRC) return AGX_ERR_BAD_ARGUMENT;
-    if (int rc = check_plan(plan)) return rc;
-    return guarded([&]() -> int {
-        const uint32_t S = src_count, T = dst_count;
-        std::vector<uint64_t> dinv(S), dinv_p(S), mat((size_t)T * S), mat_p((size_t)T * S);
-        // D_i must be invertible modulo q_i: two equal source moduli have no conversion
-        if (!basis_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, dinv.data(), dinv_p.data(), mat.data(), mat_p.data())) return AGX_ERR_BAD_MODULUS;
-        if (t == 0) return AGX_ERR_BAD_ARGUMENT;
-        std::vector<ulonglong2> dinv_pairs(S), mat_pairs((size_t)T * S);
-        for (size_t k = 0; k < dinv_pairs.size(); ++k) dinv_pairs[k] = make_ulonglong2(dinv[k], dinv_p[k]);
-        for (size_t k = 0; k < mat_pairs.size(); ++k) mat_pairs[k] = make_ulonglong2(mat[k], mat_p[k]);
-        std::unique_ptr<agx_ntt_basis> b(new (std::nothrow) agx_ntt_basis);
-        if (!b) return AGX_ERR_ALLOC;
-        b->plan = plan;
-        b->src_first = src_first, b->src_count = S, b->dst_first = dst_first, b->dst_count = T;
-        if (int rc = b->d_dinv.upload(dinv_pairs)) return rc;
-        if (int rc = b->d_mat.upload(mat_pairs)) return rc;
-        // agx_ntt_basis_mod_down: D^-1 mod q_j, and the source primes' constants (the plan's host copy) with the inverse's last-stage factors scaled
-        // by D_i^-1.  A target that is a source modulus leaves the basis good for extend.
-        std::vector<prime_consts> sc(plan->consts.begin() + src_first, plan->consts.begin() + src_first + S);
-        std::vector<uint64_t> n_inv(S), w1n(S), dall(T), dall_p(T), sn(S), sn_p(S), sw(S), sw_p(S);
-        for (uint32_t i = 0; i < S; ++i) n_inv[i] = sc[i].n_inv, w1n[i] = sc[i].w1n;
-        b->moddown_legal = moddown_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, dinv.data(), n_inv.data(), w1n.data(), dall.data(),
-                                             dall_p.data(), sn.data(), sn_p.data(), sw.data(), sw_p.data());
-        // agx_ntt_basis_mod_down_mode and the plaintext modulus: t^-1 into the scaled inverse's constants, ModDown's own matrix t D_i mod q_j, and the two
-        // constant sets of AGX_RESCALE_ROUND.  t = 1 leaves sn, sw as they are and makes the matrix a copy of mat.
-        std::vector<uint64_t> dmat((size_t)T * S), dmat_p((size_t)T * S), cadd(S), hq(T);
-        if (!moddown_mode_constants(&plan->moduli[src_first], S, &plan->moduli[dst_first], T, t, dinv.data(), mat.data(), sn.data(), sn_p.data(), sw.data(), sw_p.data(),
-                                    dmat.data(), dmat_p.data(), cadd.data(), hq.data()))
-            return AGX_ERR_BAD_MODULUS;
-        for (uint32_t i = 0; i < S; ++i) sc[i].n_inv = sn[i], sc[i].n_inv_p = sn_p[i], sc[i].w1n = sw[i], sc[i].w1n_p = sw_p[i];
-        std::vector<ulonglong2> dmat_pairs((size_t)T * S), round_src(S);
-        for (size_t k = 0; k < dmat_pairs.size(); ++k) dmat_pairs[k] = make_ulonglong2(dmat[k], dmat_p[k]);
-        for (uint32_t i = 0; i < S; ++i) round_src[i] = make_ulonglong2(cadd[i], plan->moduli[src_first + i]);
-        if (int rc = b->d_down_mat.upload(dmat_pairs)) return rc;
-        if (int rc = b->d_round_src.upload(round_src)) return rc;
-        if (int rc = b->d_round_dst.upload(hq)) return rc;
-        std::vector<ulonglong2> dall_pairs(T);
-        for (uint32_t j = 0; j < T; ++j) dall_pairs[j] = make_ulonglong2(dall[j], dall_p[j]);
-        if (int rc = b->d_dall.upload(dall_pairs)) return rc;
-        if (int rc = b->d_src_consts.upload(sc)) return rc;
-        *basis = b.release();
-        return AGX_OK;
-    });
+    return create_basis(basis, plan, src_first, src_count, dst_first, dst_count, t, false, 0);
+}
+
+int agx_ntt_basis_create_aux(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count,
+                             uint32_t aux_prime) {
+    return create_basis(basis, plan, src_first, src_count, dst_first, dst_count, 1, true, aux_prime);
 }
 
 int agx_ntt_basis_destroy(agx_ntt_basis* basis) {
@@ -125,33 +137,40 @@ int agx_ntt_basis_destroy(agx_ntt_basis* basis) {
 static bool extend_is_fused(const agx_ntt_basis* b) {
     const agx_ntt_plan* p = b->plan;
     if (!p->routes.extend.rb) return false;
-    return b->src_count == 1 || (b->src_count == 2 && p->log_n != 12 && p->log_n != 14);
+    return b->view.src_count == 1 || (b->view.src_count == 2 && p->log_n != 12 && p->log_n != 14);
 }
 
 int agx_ntt_basis_info(const agx_ntt_basis* basis, uint32_t* src_first, uint32_t* src_count, uint32_t* dst_first, uint32_t* dst_count, int* launches_ntt_form) {
     if (!basis) return AGX_ERR_NULL_POINTER;
-    if (src_first) *src_first = basis->src_first;
-    if (src_count) *src_count = basis->src_count;
-    if (dst_first) *dst_first = basis->dst_first;
-    if (dst_count) *dst_count = basis->dst_count;
+    if (src_first) *src_first = basis->view.src_first;
+    if (src_count) *src_count = basis->view.src_count;
+    if (dst_first) *dst_first = basis->view.dst_first;
+    if (dst_count) *dst_count = basis->view.dst_count;
     if (launches_ntt_form) *launches_ntt_form = extend_is_fused(basis) ? 1 : 1 + forward_launches(basis->plan);
     return AGX_OK;
 }
 
-int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
-    if (!basis || !d_x || !d_out) return AGX_ERR_NULL_POINTER;
+// agx_ntt_basis_extend, _extend_exact and _extend_mont behind their own NULL rules (d_xaux null but for exact: an empty range, aligned and touching nothing):
+// one statement of the rules, the auxiliary prime's in front of them.  Only the plain conversion has a fused kernel.
+enum extend_kind { kExtendPlain, kExtendExact, kExtendMont };
+
+static int extend_call(const agx_ntt_basis* basis, extend_kind kind, const uint64_t* d_x, const uint64_t* d_xaux, uint64_t* d_out, uint64_t batch, int out_form,
+                       void* stream) {
+    if (kind != kExtendPlain && !basis->has_aux) return AGX_ERR_BAD_ARGUMENT;
     const agx_ntt_plan* plan = basis->plan;
     if (out_form != AGX_FORM_COEFF && out_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
     if (int rc = check_plan(plan)) return rc;
-    const uint32_t S = basis->src_count, T = basis->dst_count;
-    if (!aligned8(d_x) || !aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
-    const frame_layout fl = dense(plan, batch);      // of x ([S][batch][n]) and of out ([T][batch][n]) alike
+    const basis_view& bv = basis->view;
+    const uint32_t S = bv.src_count, T = bv.dst_count;
+    if (!aligned8(d_x) || !aligned8(d_xaux) || !aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of x ([S][batch][n]), xaux ([1][batch][n]) and out ([T][batch][n]) alike
     if (!dense_fits(plan->n, S, batch) || !dense_fits(plan->n, T, batch)) return AGX_ERR_BAD_ARGUMENT;
-    // out of place only: every workgroup of a frame reads all S source frames while others already write their targets
-    if (ranges_touch(addr(d_x), S * batch * plan->n, addr(d_out), T * batch * plan->n)) return AGX_ERR_BAD_ARGUMENT;
-    const basis_view bv = view_of(basis);
+    // out of place only: every workgroup of a frame reads all S source frames while others already write their targets.  The inputs are only read and
+    // may overlap freely.
+    const uint64_t slab = batch * plan->n;
+    if (ranges_touch(addr(d_x), S * slab, addr(d_out), T * slab) || ranges_touch(addr(d_xaux), kind == kExtendExact ? slab : 0, addr(d_out), T * slab)) return AGX_ERR_BAD_ARGUMENT;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const route& r = plan->routes.extend; out_form == AGX_FORM_NTT && extend_is_fused(basis)) {
+    if (const route& r = plan->routes.extend; kind == kExtendPlain && out_form == AGX_FORM_NTT && extend_is_fused(basis)) {
         // one kernel: the conversion and the target prime's forward transform stay on chip
         if (!targets_fit_grid(T, batch, r.rb->ppb)) return AGX_ERR_BAD_ARGUMENT;
         if (batch == 0) return AGX_OK;
@@ -159,10 +178,26 @@ int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64
         return AGX_OK;
     }
     if (batch == 0) return AGX_OK;
-    AGX_HIP(launch_basis_coeff(plan->routes.forward, bv, d_x, d_out, batch, s));
+    if (kind == kExtendPlain) AGX_HIP(launch_basis_coeff(plan->routes.forward, bv, d_x, d_out, batch, s));
+    else AGX_HIP(launch_basis_aux_coeff(plan->routes.forward, bv, basis->aux, kind == kExtendExact, d_x, d_xaux, d_out, batch, s));
     // the plan's forward on the view of the target primes, in place
-    if (out_form == AGX_FORM_NTT) AGX_HIP(run_forward(prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T), d_out, d_out, fl, s));
+    if (out_form == AGX_FORM_NTT) AGX_HIP(run_forward(prime_range(forward_route(plan, batch), bv.dst_first, bv.dst_first + T), d_out, d_out, fl, s));
     return AGX_OK;
+}
+
+int agx_ntt_basis_extend(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    if (!basis || !d_x || !d_out) return AGX_ERR_NULL_POINTER;
+    return extend_call(basis, kExtendPlain, d_x, nullptr, d_out, batch, out_form, stream);
+}
+
+int agx_ntt_basis_extend_exact(const agx_ntt_basis* basis, const uint64_t* d_x, const uint64_t* d_xaux, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    if (!basis || !d_x || !d_xaux || !d_out) return AGX_ERR_NULL_POINTER;
+    return extend_call(basis, kExtendExact, d_x, d_xaux, d_out, batch, out_form, stream);
+}
+
+int agx_ntt_basis_extend_mont(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    if (!basis || !d_x || !d_out) return AGX_ERR_NULL_POINTER;
+    return extend_call(basis, kExtendMont, d_x, nullptr, d_out, batch, out_form, stream);
 }
 
 // Does a mod_down call of this basis take the two-launch route?  The plan's entry must carry the fused kernel (n = 1024 ... 32768, some modulus
@@ -197,7 +232,8 @@ int agx_ntt_basis_mod_down_mode(const agx_ntt_basis* basis, const uint64_t* d_xq
     const bool round = mode == AGX_RESCALE_ROUND;
     const agx_ntt_plan* plan = basis->plan;
     if (int rc = check_plan(plan)) return rc;
-    const uint32_t S = basis->src_count, T = basis->dst_count;
+    const basis_view& bv = basis->view;
+    const uint32_t S = bv.src_count, T = bv.dst_count;
     if (!aligned8(d_xq) || !aligned8(d_xp) || !aligned8(d_out) || !aligned8(d_scratch) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
     const frame_layout fl = dense(plan, batch);      // of xq and out ([T][batch][n]) and of xp and the scratch ([S][batch][n]) alike
     if (!dense_fits(plan->n, S, batch) || !dense_fits(plan->n, T, batch)) return AGX_ERR_BAD_ARGUMENT;
@@ -209,10 +245,9 @@ int agx_ntt_basis_mod_down_mode(const agx_ntt_basis* basis, const uint64_t* d_xq
     if (!basis->moddown_legal) return AGX_ERR_BAD_MODULUS;      // some target modulus is a source modulus: D has no inverse there
     if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
     if (batch == 0) return AGX_OK;
-    const basis_view bv = view_of(basis);
     hipStream_t s = static_cast<hipStream_t>(stream);
     // scratch <- y_i = INTT_i(xp_i) t^-1 D_i^-1 mod q_i in [0, q_i): the plan's inverse on the view of the source primes, its last-stage constants the basis'
-    route scaled = prime_range(plan->routes.inverse, basis->src_first, basis->src_first + S);
+    route scaled = prime_range(plan->routes.inverse, bv.src_first, bv.src_first + S);
     scaled.consts = basis->d_src_consts;
     if (fused) {
         // two launches: the accumulation, the forward transform and (xq_j - .) D^-1 stay on chip; a wave reads its words of xq_j before it writes them
@@ -222,46 +257,11 @@ int agx_ntt_basis_mod_down_mode(const agx_ntt_basis* basis, const uint64_t* d_xq
     }
     // generic route, no more scratch: out <- INTT(xq) on the target primes; scratch <- the y_i; out <- (out - sum_i y_i D_i) D^-1 in the coefficient
     // domain; out <- NTT(out) in place
-    AGX_HIP(run_inverse(prime_range(plan->routes.inverse, basis->dst_first, basis->dst_first + T), d_xq, nullptr, d_out, fl, s));
+    AGX_HIP(run_inverse(prime_range(plan->routes.inverse, bv.dst_first, bv.dst_first + T), d_xq, nullptr, d_out, fl, s));
     AGX_HIP(run_inverse(scaled, d_xp, nullptr, d_scratch, fl, s));
     AGX_HIP(launch_moddown_coeff(plan->routes.forward, bv, d_out, d_scratch, batch, round, s));
-    AGX_HIP(run_forward(prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T), d_out, d_out, fl, s));
+    AGX_HIP(run_forward(prime_range(forward_route(plan, batch), bv.dst_first, bv.dst_first + T), d_out, d_out, fl, s));
     return AGX_OK;
-}
-
-// agx_ntt_basis_create's rules in its order (the basis is made by it), then the auxiliary prime's: outside the plan or inside a range of the basis is a bad
-// argument, a modulus that is a source's or a target's a bad modulus
-int agx_ntt_basis_create_aux(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count,
-                             uint32_t aux_prime) {
-    if (!basis) return AGX_ERR_NULL_POINTER;
-    *basis = nullptr;
-    agx_ntt_basis* made = nullptr;
-    if (int rc = agx_ntt_basis_create_plain(&made, plan, src_first, src_count, dst_first, dst_count, 1)) return rc;      // t = 1
-    std::unique_ptr<agx_ntt_basis> b(made);
-    auto inside = [&](uint32_t first, uint32_t count) { return aux_prime >= first && aux_prime - first < count; };
-    if (aux_prime >= plan->num_primes || inside(src_first, src_count) || inside(dst_first, dst_count)) return AGX_ERR_BAD_ARGUMENT;
-    return guarded([&]() -> int {
-        const uint32_t S = src_count, T = dst_count;
-        const uint64_t *src = &plan->moduli[src_first], *dst = &plan->moduli[dst_first], m = plan->moduli[aux_prime];
-        std::vector<uint64_t> dinv(S), dinv_p(S), mat((size_t)T * S), mat_p((size_t)T * S);
-        aux_constants c;
-        if (!basis_constants(src, S, dst, T, dinv.data(), dinv_p.data(), mat.data(), mat_p.data()) || !aux_basis_constants(src, S, dst, T, m, dinv.data(), mat.data(), &c))
-            return AGX_ERR_BAD_MODULUS;
-        auto pairs = [](const std::vector<uint64_t>& w, const std::vector<uint64_t>& p) {
-            std::vector<ulonglong2> v(w.size());
-            for (size_t k = 0; k < v.size(); ++k) v[k] = make_ulonglong2(w[k], p[k]);
-            return v;
-        };
-        if (int rc = b->d_aux_row.upload(pairs(c.row, c.row_p))) return rc;
-        if (int rc = b->d_aux_corr_exact.upload(pairs(c.corr_exact, c.corr_exact_p))) return rc;
-        if (int rc = b->d_aux_mdinv.upload(pairs(c.mdinv, c.mdinv_p))) return rc;
-        if (int rc = b->d_aux_mmat.upload(pairs(c.mmat, c.mmat_p))) return rc;
-        if (int rc = b->d_aux_corr_mont.upload(pairs(c.corr_mont, c.corr_mont_p))) return rc;
-        b->has_aux = true, b->aux_prime = aux_prime, b->aux_m = m;
-        b->aux_k_exact = c.k_exact, b->aux_k_exact_p = c.k_exact_p, b->aux_k_mont = c.k_mont, b->aux_k_mont_p = c.k_mont_p;
-        *basis = b.release();
-        return AGX_OK;
-    });
 }
 
 int agx_ntt_basis_aux_info(const agx_ntt_basis* basis, int* has_aux, uint32_t* aux_prime, int* launches_ntt_form) {
@@ -270,43 +270,6 @@ int agx_ntt_basis_aux_info(const agx_ntt_basis* basis, int* has_aux, uint32_t* a
     if (aux_prime) *aux_prime = basis->aux_prime;
     if (launches_ntt_form) *launches_ntt_form = 1 + forward_launches(basis->plan);      // the coefficient-form launch, then the plan's forward on the targets
     return AGX_OK;
-}
-
-// agx_ntt_basis_extend_exact (d_xaux set by its caller's NULL rule) and agx_ntt_basis_extend_mont (d_xaux null: an empty range): agx_ntt_basis_extend's rules
-// in its order, the auxiliary prime's right behind the NULL rule
-static int extend_aux_call(const agx_ntt_basis* basis, bool exact, const uint64_t* d_x, const uint64_t* d_xaux, uint64_t* d_out, uint64_t batch, int out_form,
-                           void* stream) {
-    if (!basis->has_aux) return AGX_ERR_BAD_ARGUMENT;
-    const agx_ntt_plan* plan = basis->plan;
-    if (out_form != AGX_FORM_COEFF && out_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
-    if (int rc = check_plan(plan)) return rc;
-    const uint32_t S = basis->src_count, T = basis->dst_count;
-    if (!aligned8(d_x) || !aligned8(d_xaux) || !aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
-    const frame_layout fl = dense(plan, batch);      // of x ([S][batch][n]), xaux ([1][batch][n]) and out ([T][batch][n]) alike
-    if (!dense_fits(plan->n, S, batch) || !dense_fits(plan->n, T, batch)) return AGX_ERR_BAD_ARGUMENT;
-    // out of place only: out touches neither input; the inputs are only read and may overlap freely
-    const uint64_t slab = batch * plan->n;
-    if (ranges_touch(addr(d_x), S * slab, addr(d_out), T * slab) || ranges_touch(addr(d_xaux), exact ? slab : 0, addr(d_out), T * slab)) return AGX_ERR_BAD_ARGUMENT;
-    if (batch == 0) return AGX_OK;
-    aux_view av;
-    av.row = basis->d_aux_row, av.m = basis->aux_m;
-    av.exact = aux_set{basis->d_dinv, basis->d_mat, basis->d_aux_corr_exact, basis->aux_k_exact, basis->aux_k_exact_p};
-    av.mont = aux_set{basis->d_aux_mdinv, basis->d_aux_mmat, basis->d_aux_corr_mont, basis->aux_k_mont, basis->aux_k_mont_p};
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    AGX_HIP(launch_basis_aux_coeff(plan->routes.forward, view_of(basis), av, exact, d_x, d_xaux, d_out, batch, s));
-    // the plan's forward on the view of the target primes, in place
-    if (out_form == AGX_FORM_NTT) AGX_HIP(run_forward(prime_range(forward_route(plan, batch), basis->dst_first, basis->dst_first + T), d_out, d_out, fl, s));
-    return AGX_OK;
-}
-
-int agx_ntt_basis_extend_exact(const agx_ntt_basis* basis, const uint64_t* d_x, const uint64_t* d_xaux, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
-    if (!basis || !d_x || !d_xaux || !d_out) return AGX_ERR_NULL_POINTER;
-    return extend_aux_call(basis, true, d_x, d_xaux, d_out, batch, out_form, stream);
-}
-
-int agx_ntt_basis_extend_mont(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
-    if (!basis || !d_x || !d_out) return AGX_ERR_NULL_POINTER;
-    return extend_aux_call(basis, false, d_x, nullptr, d_out, batch, out_form, stream);
 }
 
 // agx_ntt_inner_product and agx_ntt_inner_product_galois: one statement of the rules, the Galois element's between the overlap rule and the device's

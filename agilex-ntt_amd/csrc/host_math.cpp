@@ -108,108 +108,70 @@ void power_tables_bitrev(uint64_t q, uint64_t base, uint32_t n, uint64_t* tw, ui
     }
 }
 
-bool basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t* dinv, uint64_t* dinv_p, uint64_t* mat, uint64_t* mat_p) {
-    // D_i mod m, one factor at a time: S (S - 1) products per modulus, S <= 16
-    auto d_mod = [&](uint32_t i, uint64_t m) {
-        uint64_t r = 1 % m;
-        for (uint32_t k = 0; k < S; ++k)
-            if (k != i) r = mul_mod(r, src[k] % m, m);
-        return r;
-    };
-    for (uint32_t i = 0; i < S; ++i) {
-        if (!inv_mod_euclid(d_mod(i, src[i]), src[i], &dinv[i])) return false;
-        dinv_p[i] = shoup_quotient(dinv[i], src[i]);
-    }
-    for (uint32_t j = 0; j < T; ++j)
-        for (uint32_t i = 0; i < S; ++i) {
-            mat[(std::size_t)j * S + i] = d_mod(i, dst[j]);
-            mat_p[(std::size_t)j * S + i] = shoup_quotient(mat[(std::size_t)j * S + i], dst[j]);
-        }
-    return true;
+// D mod q (skip == S) or D_skip mod q, one factor at a time: at most S products per call, S <= 16
+static uint64_t product_mod(const uint64_t* src, uint32_t S, uint32_t skip, uint64_t q) {
+    uint64_t r = 1 % q;
+    for (uint32_t k = 0; k < S; ++k)
+        if (k != skip) r = mul_mod(r, src[k] % q, q);
+    return r;
 }
 
-bool moddown_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, const uint64_t* dinv, const uint64_t* n_inv, const uint64_t* w1n,
-                       uint64_t* dall, uint64_t* dall_p, uint64_t* sn, uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p) {
-    for (uint32_t i = 0; i < S; ++i) {
-        sn[i] = mul_mod(n_inv[i], dinv[i], src[i]);
-        sn_p[i] = shoup_quotient(sn[i], src[i]);
-        sw[i] = mul_mod(w1n[i], dinv[i], src[i]);
-        sw_p[i] = shoup_quotient(sw[i], src[i]);
-    }
-    bool all = true;
-    for (uint32_t j = 0; j < T; ++j) {
-        uint64_t d = 1 % dst[j];      // D mod dst[j], one factor at a time
-        for (uint32_t k = 0; k < S; ++k) d = mul_mod(d, src[k] % dst[j], dst[j]);
-        dall[j] = dall_p[j] = 0;
-        if (inv_mod_euclid(d, dst[j], &dall[j])) dall_p[j] = shoup_quotient(dall[j], dst[j]);
-        else all = false;
-    }
-    return all;
+uint64_t half_product_mod(uint64_t d_mod_q, uint64_t q) {
+    const uint64_t d1 = d_mod_q ? d_mod_q - 1 : q - 1;      // (D - 1) mod q
+    return mul_mod(d1, (q >> 1) + 1, q);                     // q odd: (q + 1) / 2 = 2^-1, formed without q + 1
 }
+uint64_t half_product_mod(const uint64_t* src, uint32_t S, uint64_t q) { return half_product_mod(product_mod(src, S, S, q), q); }
 
-uint64_t half_product_mod(const uint64_t* src, uint32_t S, uint64_t q) {
-    uint64_t d = 1 % q;      // D mod q, one factor at a time
-    for (uint32_t k = 0; k < S; ++k) d = mul_mod(d, src[k] % q, q);
-    const uint64_t d1 = d ? d - 1 : q - 1;      // (D - 1) mod q
-    return mul_mod(d1, (q >> 1) + 1, q);        // q odd: (q + 1) / 2 = 2^-1, formed without q + 1
-}
-
-bool moddown_mode_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t t, const uint64_t* dinv, const uint64_t* mat, uint64_t* sn,
-                            uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p, uint64_t* dmat, uint64_t* dmat_p, uint64_t* cadd, uint64_t* hq) {
-    for (uint32_t i = 0; i < S; ++i) {
-        const uint64_t q = src[i];
-        uint64_t tinv = 0;
-        if (!inv_mod_euclid(t % q, q, &tinv)) return false;
-        sn[i] = mul_mod(sn[i], tinv, q);
-        sn_p[i] = shoup_quotient(sn[i], q);
-        sw[i] = mul_mod(sw[i], tinv, q);
-        sw_p[i] = shoup_quotient(sw[i], q);
-        cadd[i] = mul_mod(half_product_mod(src, S, q), dinv[i], q);
-    }
-    for (uint32_t j = 0; j < T; ++j) {
-        const uint64_t q = dst[j], tq = t % q;
-        for (uint32_t i = 0; i < S; ++i) {
-            const std::size_t at = (std::size_t)j * S + i;
-            dmat[at] = mul_mod(mat[at], tq, q);
-            dmat_p[at] = shoup_quotient(dmat[at], q);
-        }
-        hq[j] = mul_mod(half_product_mod(src, S, q), tq, q);
-    }
-    return true;
-}
-
-bool aux_basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t m, const uint64_t* dinv, const uint64_t* mat, aux_constants* out) {
-    // D mod q (skip == S) or D_skip mod q, one factor at a time
-    auto d_mod = [&](uint32_t skip, uint64_t q) {
-        uint64_t r = 1 % q;
-        for (uint32_t k = 0; k < S; ++k)
-            if (k != skip) r = mul_mod(r, src[k] % q, q);
-        return r;
-    };
+basis_fault prepare_basis_image(basis_image& img, const basis_request& rq) {
+    const uint32_t S = rq.S, T = rq.T;
+    const uint64_t m = rq.m;
     auto neg = [](uint64_t v, uint64_t q) { return v ? q - v : 0; };
-    aux_constants& c = *out;
-    for (auto* v : {&c.row, &c.row_p, &c.mdinv, &c.mdinv_p}) v->assign(S, 0);
-    for (auto* v : {&c.corr_exact, &c.corr_exact_p, &c.corr_mont, &c.corr_mont_p}) v->assign(T, 0);
-    c.mmat.assign((std::size_t)T * S, 0), c.mmat_p.assign((std::size_t)T * S, 0);
-    if (!inv_mod_euclid(d_mod(S, m), m, &c.k_exact)) return false;
-    c.k_mont = neg(c.k_exact, m);
-    c.k_exact_p = shoup_quotient(c.k_exact, m), c.k_mont_p = shoup_quotient(c.k_mont, m);
+    img = basis_image{};
     for (uint32_t i = 0; i < S; ++i) {
-        c.row[i] = d_mod(i, m), c.row_p[i] = shoup_quotient(c.row[i], m);
-        c.mdinv[i] = mul_mod(dinv[i], m % src[i], src[i]), c.mdinv_p[i] = shoup_quotient(c.mdinv[i], src[i]);
+        const uint64_t q = rq.src[i];
+        uint64_t dinv = 0;
+        if (!inv_mod_euclid(product_mod(rq.src, S, i, q), q, &dinv)) return basis_fault::source;
+        img.dinv.push_back(shoup_pair::of(dinv, q));
     }
-    for (uint32_t j = 0; j < T; ++j) {
-        const uint64_t q = dst[j];
-        uint64_t minv = 0;
-        if (!inv_mod_euclid(m % q, q, &minv)) return false;
-        c.corr_exact[j] = d_mod(S, q), c.corr_exact_p[j] = shoup_quotient(c.corr_exact[j], q);
-        c.corr_mont[j] = neg(mul_mod(c.corr_exact[j], minv, q), q), c.corr_mont_p[j] = shoup_quotient(c.corr_mont[j], q);
+    for (uint32_t i = 0; i < S; ++i) {
+        const uint64_t q = rq.src[i], dinv = img.dinv[i].w;
+        uint64_t tinv = 0;
+        if (!inv_mod_euclid(rq.t % q, q, &tinv)) return basis_fault::t;
+        const uint64_t scale = mul_mod(dinv, tinv, q);      // t^-1 D_i^-1
+        img.sn.push_back(shoup_pair::of(mul_mod(rq.n_inv[i], scale, q), q));
+        img.sw.push_back(shoup_pair::of(mul_mod(rq.w1n[i], scale, q), q));
+        img.round_src.push_back({mul_mod(half_product_mod(product_mod(rq.src, S, S, q), q), dinv, q), q});
+    }
+    uint64_t k = 0;
+    if (m) {
+        if (!inv_mod_euclid(product_mod(rq.src, S, S, m), m, &k)) return basis_fault::aux;
+        img.k_exact = shoup_pair::of(k, m), img.k_mont = shoup_pair::of(neg(k, m), m);
         for (uint32_t i = 0; i < S; ++i) {
-            const std::size_t at = (std::size_t)j * S + i;
-            c.mmat[at] = mul_mod(mat[at], minv, q), c.mmat_p[at] = shoup_quotient(c.mmat[at], q);
+            const uint64_t q = rq.src[i];
+            img.aux_row.push_back(shoup_pair::of(product_mod(rq.src, S, i, m), m));
+            img.aux_mdinv.push_back(shoup_pair::of(mul_mod(img.dinv[i].w, m % q, q), q));
         }
     }
-    return true;
+    img.moddown_legal = true;
+    for (uint32_t j = 0; j < T; ++j) {
+        const uint64_t q = rq.dst[j], tq = rq.t % q, d = product_mod(rq.src, S, S, q);
+        uint64_t dall = 0, minv = 0;
+        if (inv_mod_euclid(d, q, &dall)) img.dall.push_back(shoup_pair::of(dall, q));
+        else img.dall.push_back({0, 0}), img.moddown_legal = false;
+        img.round_dst.push_back(mul_mod(half_product_mod(d, q), tq, q));
+        if (m) {
+            if (!inv_mod_euclid(m % q, q, &minv)) return basis_fault::aux;
+            img.aux_corr_exact.push_back(shoup_pair::of(d, q));
+            img.aux_corr_mont.push_back(shoup_pair::of(neg(mul_mod(d, minv, q), q), q));
+        }
+        for (uint32_t i = 0; i < S; ++i) {
+            const uint64_t di = product_mod(rq.src, S, i, q);
+            img.mat.push_back(shoup_pair::of(di, q));
+            img.down_mat.push_back(shoup_pair::of(mul_mod(di, tq, q), q));
+            if (m) img.aux_mmat.push_back(shoup_pair::of(mul_mod(di, minv, q), q));
+        }
+    }
+    return basis_fault::none;
 }
 
 }  // namespace agx

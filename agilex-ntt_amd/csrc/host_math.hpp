@@ -40,46 +40,61 @@ struct fold_twiddle {
 };
 fold_twiddle fold_twiddle_pack(uint64_t w, uint64_t q);
 
-// The constants of a fast RNS base conversion (agx_ntt_basis_extend) from the moduli src[0 .. S) to the moduli dst[0 .. T), every modulus
-// odd, > 1 and < 2^62.  With D = prod src[i] and D_i = D / src[i]:
-//   dinv[i] = D_i^-1 mod src[i],   mat[j * S + i] = D_i mod dst[j],   dinv_p / mat_p their precomputed quotients (shoup_quotient).
-// false, nothing promised about the outputs, when some D_i is not invertible modulo src[i]: two source moduli share a factor (for primes:
-// are equal).  A target that is itself source k gets D_i mod dst[j] = 0 for i != k, so the conversion hands that residue through.
-bool basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t* dinv, uint64_t* dinv_p, uint64_t* mat, uint64_t* mat_p);
-
-// What agx_ntt_basis_mod_down needs beyond basis_constants, for the same moduli (dinv as basis_constants wrote it):
-//   dall[j] = D^-1 mod dst[j] with its quotient dall_p[j] -- {0, 0} where D is not invertible modulo dst[j] (dst[j] shares a factor with a source;
-//     for primes: equals one); the return value says whether every one exists;
-//   sn[i] = n_inv[i] dinv[i] mod src[i] and sw[i] = w1n[i] dinv[i] mod src[i] with their quotients sn_p / sw_p: the two constants of an inverse
-//     transform's last stage (n^-1 mod src[i] and inv_twiddle[1] n^-1 mod src[i], both below src[i]) scaled by D_i^-1, so that the inverse of
-//     the source slabs writes y_i = p_i D_i^-1 mod src[i] itself.
-bool moddown_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, const uint64_t* dinv, const uint64_t* n_inv, const uint64_t* w1n,
-                       uint64_t* dall, uint64_t* dall_p, uint64_t* sn, uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p);
+// A word w < q with its precomputed quotient floor(w 2^64 / q): what one Shoup product reads.  The device reads it as a ulonglong2 (plan_internal.hpp
+// asserts size and alignment).
+struct alignas(16) shoup_pair {
+    uint64_t w, p;
+    static shoup_pair of(uint64_t w, uint64_t q) { return {w, shoup_quotient(w, q)}; }
+};
 
 // h mod q for h = floor(D / 2), D = prod src[i] odd, q odd and > 1: h is a multi-word integer (S up to 16 moduli of 62 bits) and is never formed.
-// 2 h = D - 1 exactly, so h = (D - 1) 2^-1 (mod q) with 2^-1 = (q + 1) / 2; D mod q is taken one factor at a time in 128 bits.
+// 2 h = D - 1 exactly, so h = (D - 1) 2^-1 (mod q) with 2^-1 = (q + 1) / 2; D mod q is taken one factor at a time in 128 bits, or is the caller's.
 uint64_t half_product_mod(const uint64_t* src, uint32_t S, uint64_t q);
+uint64_t half_product_mod(uint64_t d_mod_q, uint64_t q);
 
-// What agx_ntt_basis_mod_down_mode and a plaintext modulus t >= 1 (agx_ntt_basis_create_plain) need beyond the two sets above, for the same moduli
-// (dinv, mat as basis_constants wrote them; sn, sw as moddown_constants wrote them).  t is any 64-bit value, reduced per modulus here.
-//   sn[i], sw[i] are multiplied by t^-1 mod src[i] in place (quotients sn_p / sw_p again): the scaled inverse then writes p_i t^-1 D_i^-1 mod src[i];
-//   dmat[j * S + i] = t D_i mod dst[j] with its quotient dmat_p: ModDown's matrix, a copy of its own (agx_ntt_basis_extend keeps mat);
-//   cadd[i] = h D_i^-1 mod src[i] and hq[j] = t h mod dst[j], h = floor(D / 2): the two constants of AGX_RESCALE_ROUND (csrc/moddown_arith.hpp).
-// false, nothing promised about the outputs, when t has no inverse modulo some source (for prime sources: t = 0 modulo one of them).
-// With t = 1 nothing changes: sn, sw stay, dmat = mat.
-bool moddown_mode_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t t, const uint64_t* dinv, const uint64_t* mat, uint64_t* sn,
-                            uint64_t* sn_p, uint64_t* sw, uint64_t* sw_p, uint64_t* dmat, uint64_t* dmat_p, uint64_t* cadd, uint64_t* hq);
-
-// What agx_ntt_basis_extend_exact and agx_ntt_basis_extend_mont need beyond basis_constants (dinv, mat as it wrote them), for the same moduli and an
-// auxiliary modulus m, odd, > 1 and < 2^62 (csrc/bfv_conv_arith.hpp has the formulas); every word comes with its quotient (_p):
-//   row[i] = D_i mod m;   k_exact = D^-1 mod m,   k_mont = -D^-1 mod m;
-//   corr_exact[j] = D mod dst[j];
-//   mdinv[i] = m dinv[i] mod src[i],   mmat[j * S + i] = mat[j * S + i] m^-1 mod dst[j],   corr_mont[j] = -D m^-1 mod dst[j].
-// false, nothing promised about the outputs, when D has no inverse modulo m or m none modulo some target (for primes: m equals a source or a target).
-struct aux_constants {
-    std::vector<uint64_t> row, row_p, corr_exact, corr_exact_p, mdinv, mdinv_p, mmat, mmat_p, corr_mont, corr_mont_p;
-    uint64_t k_exact = 0, k_exact_p = 0, k_mont = 0, k_mont_p = 0;
+// What a basis is asked for: a fast RNS base conversion from the moduli src[0 .. S) to the moduli dst[0 .. T), every modulus odd, > 1 and < 2^62.
+struct basis_request {
+    const uint64_t* src;
+    uint32_t S;
+    const uint64_t* dst;
+    uint32_t T;
+    const uint64_t *n_inv, *w1n;      // [S]: the two constants of an inverse transform's last stage, n^-1 mod src[i] and inv_twiddle[1] n^-1 mod src[i], both below src[i]
+    uint64_t t = 1;                   // the plaintext modulus of agx_ntt_basis_create_plain: any 64-bit value, reduced per modulus here
+    uint64_t m = 0;                   // the auxiliary modulus of agx_ntt_basis_create_aux, odd, > 1 and < 2^62; 0: none
 };
-bool aux_basis_constants(const uint64_t* src, uint32_t S, const uint64_t* dst, uint32_t T, uint64_t m, const uint64_t* dinv, const uint64_t* mat, aux_constants* out);
+
+// Everything a basis keeps on the device, built once on the host.  With D = prod src[i], D_i = D / src[i], q_i = src[i], q_j = dst[j], every pair
+// {word, its quotient for the modulus the word is reduced by}:
+struct basis_image {
+    // agx_ntt_basis_extend
+    std::vector<shoup_pair> dinv;      // [S]    D_i^-1 mod q_i
+    std::vector<shoup_pair> mat;       // [T][S] D_i mod q_j.  A target that is itself source k gets 0 for i != k, so the conversion hands that residue through.
+    // agx_ntt_basis_mod_down
+    std::vector<shoup_pair> dall;      // [T]    D^-1 mod q_j -- {0, 0} where D is not invertible modulo q_j (q_j shares a factor with a source; for primes: equals one)
+    bool moddown_legal = false;        // every dall[j] exists
+    // [S]: n_inv[i] t^-1 D_i^-1 mod q_i and w1n[i] t^-1 D_i^-1 mod q_i, the last stage's constants scaled so that the inverse of the source slabs writes
+    // y_i = p_i t^-1 D_i^-1 mod q_i itself.  With t = 1 they are n_inv[i] D_i^-1 and w1n[i] D_i^-1: nothing changes.
+    std::vector<shoup_pair> sn, sw;
+    std::vector<shoup_pair> down_mat;  // [T][S] t D_i mod q_j: ModDown's matrix, a copy of its own (agx_ntt_basis_extend keeps mat); with t = 1 the words of mat
+    // the two constant sets of AGX_RESCALE_ROUND (csrc/moddown_arith.hpp), h = floor(D / 2)
+    std::vector<shoup_pair> round_src; // [S]    {c_i = h D_i^-1 mod q_i, q_i}: the second word is the modulus, not a quotient
+    std::vector<uint64_t> round_dst;   // [T]    t h mod q_j
+    // agx_ntt_basis_extend_exact and agx_ntt_basis_extend_mont (csrc/bfv_conv_arith.hpp has the formulas): filled when the request has an m, else empty
+    std::vector<shoup_pair> aux_row;         // [S]    D_i mod m
+    std::vector<shoup_pair> aux_corr_exact;  // [T]    D mod q_j
+    std::vector<shoup_pair> aux_mdinv;       // [S]    m D_i^-1 mod q_i
+    std::vector<shoup_pair> aux_mmat;        // [T][S] D_i m^-1 mod q_j
+    std::vector<shoup_pair> aux_corr_mont;   // [T]    -D m^-1 mod q_j
+    shoup_pair k_exact = {0, 0}, k_mont = {0, 0};      // D^-1 mod m, -D^-1 mod m
+};
+
+// Which rule refused a request, the first in this order; nothing is promised about the image then.
+enum class basis_fault {
+    none,
+    source,      // some D_i is not invertible modulo src[i]: two source moduli share a factor (for primes: are equal)
+    t,           // t has no inverse modulo some source (for prime sources: t = 0 modulo one of them)
+    aux,         // D has no inverse modulo m, or m none modulo some target (for primes: m equals a source or a target)
+};
+basis_fault prepare_basis_image(basis_image& img, const basis_request& rq);
 
 }  // namespace agx

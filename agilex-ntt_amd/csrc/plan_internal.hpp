@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "host_math.hpp"
 #include "keyswitch_layout.hpp"
 #include "operands.hpp"
 #include "rb_registry.hpp"
@@ -39,12 +40,17 @@ struct device_buf {
     device_buf& operator=(device_buf&& o) noexcept { return std::swap(p, o.p), *this; }      // the old memory goes with `o`
     ~device_buf() { if (p) (void)hipFree(p); }
     operator T*() const { return p; }
-    int upload(const std::vector<T>& src) {      // into an empty owner
-        AGX_HIP(hipMalloc(reinterpret_cast<void**>(&p), src.size() * sizeof(T)));
-        AGX_HIP(hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    int upload(const T* src, size_t count) {      // into an empty owner
+        AGX_HIP(hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)));
+        AGX_HIP(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
         return AGX_OK;
     }
+    int upload(const std::vector<T>& src) { return upload(src.data(), src.size()); }
 };
+
+// host_math.hpp knows no HIP type: a vector of its pairs goes to the device as the ulonglong2 the kernels read
+static_assert(sizeof(shoup_pair) == sizeof(ulonglong2) && alignof(shoup_pair) == alignof(ulonglong2), "shoup_pair is uploaded as ulonglong2");
+inline int upload_pairs(device_buf<ulonglong2>& to, const std::vector<shoup_pair>& pairs) { return to.upload(reinterpret_cast<const ulonglong2*>(pairs.data()), pairs.size()); }
 
 // the pass tables of one registry entry for every prime of a plan ([P][entry->table_pairs] each), on the host and on the device
 template <class Table>
@@ -110,34 +116,30 @@ struct agx_ntt_plan {
 
 // agx_ntt_basis_extend: the constants of one (plan, source range, target range) on the plan's device, and nothing of the plan but a pointer --
 // the kernels come from the plan's routes at every call, so agx_ntt_plan_set_variant between calls stays legal.  The plan outlives the basis.
+// Made from a basis_image (host_math.hpp, whose fields say what each buffer holds) by one function of agx_rns.cpp, which also fills the two views, once:
+// a call hands them to its kernel as they are.  The ranges live in `view`; m and the two k of the auxiliary forms in `aux` only.
 struct agx_ntt_basis {
     const agx_ntt_plan* plan = nullptr;
-    uint32_t src_first = 0, src_count = 0, dst_first = 0, dst_count = 0;
-    agx::device_buf<ulonglong2> d_dinv;      // [S]    {D_i^-1 mod q_i, quotient}
-    agx::device_buf<ulonglong2> d_mat;       // [T][S] {D_i mod q_j, quotient}
+    agx::device_buf<ulonglong2> d_dinv, d_mat;      // agx_ntt_basis_extend
     // agx_ntt_basis_mod_down
-    agx::device_buf<ulonglong2> d_dall;      // [T]    {D^-1 mod q_j, quotient}; {0, 0} where D is not invertible modulo q_j
+    agx::device_buf<ulonglong2> d_dall;
     bool moddown_legal = false;              // every D^-1 mod q_j exists (no target modulus is a source modulus); judged at the call
-    // [S]: the plan's prime_consts of the source primes with n_inv, w1n and their quotients multiplied by D_i^-1 mod q_i.  The plan's inverse on the
-    // view of the source primes with `consts` pointing here writes y_i = INTT_i(x_i) D_i^-1 mod q_i in [0,q_i): every inverse family reads its
+    // [S]: the plan's prime_consts of the source primes with n_inv, w1n and their quotients replaced by the image's sn, sw.  The plan's inverse on the
+    // view of the source primes with `consts` pointing here writes y_i = INTT_i(x_i) t^-1 D_i^-1 mod q_i in [0,q_i): every inverse family reads its
     // last-stage constants from its view's consts, and the transform is linear.
     agx::device_buf<agx::prime_consts> d_src_consts;
     // The plaintext modulus t of agx_ntt_basis_create_plain (1: agx_ntt_basis_create) is a property of ModDown alone and lives in constants only:
     // d_src_consts carry t^-1 mod q_i as well, and ModDown reads a matrix of its own, so agx_ntt_basis_extend keeps d_mat.
-    agx::device_buf<ulonglong2> d_down_mat;  // [T][S] {t D_i mod q_j, quotient}
-    // AGX_RESCALE_ROUND (agx_ntt_basis_mod_down_mode), h = floor(D / 2); AGX_RESCALE_FLOOR never reads them
-    agx::device_buf<ulonglong2> d_round_src; // [S]    {h D_i^-1 mod q_i, q_i}
-    agx::device_buf<uint64_t> d_round_dst;   // [T]    t h mod q_j
+    agx::device_buf<ulonglong2> d_down_mat;
+    agx::device_buf<ulonglong2> d_round_src;      // AGX_RESCALE_ROUND (agx_ntt_basis_mod_down_mode); AGX_RESCALE_FLOOR never reads the two
+    agx::device_buf<uint64_t> d_round_dst;
+    agx::basis_view view;
     // agx_ntt_basis_create_aux only: the auxiliary prime m = the modulus of plan prime aux_prime, and the constants of agx_ntt_basis_extend_exact and
-    // agx_ntt_basis_extend_mont (host_math.hpp: aux_basis_constants).  The exact form reads d_dinv and d_mat as agx_ntt_basis_extend does.
+    // agx_ntt_basis_extend_mont.  The exact form reads d_dinv and d_mat as agx_ntt_basis_extend does.
     bool has_aux = false;
     uint32_t aux_prime = 0;
-    uint64_t aux_m = 0, aux_k_exact = 0, aux_k_exact_p = 0, aux_k_mont = 0, aux_k_mont_p = 0;
-    agx::device_buf<ulonglong2> d_aux_row;         // [S]    {D_i mod m, quotient}
-    agx::device_buf<ulonglong2> d_aux_corr_exact;  // [T]    {D mod q_j, quotient}
-    agx::device_buf<ulonglong2> d_aux_mdinv;       // [S]    {m D_i^-1 mod q_i, quotient}
-    agx::device_buf<ulonglong2> d_aux_mmat;        // [T][S] {D_i m^-1 mod q_j, quotient}
-    agx::device_buf<ulonglong2> d_aux_corr_mont;   // [T]    {-D m^-1 mod q_j, quotient}
+    agx::device_buf<ulonglong2> d_aux_row, d_aux_corr_exact, d_aux_mdinv, d_aux_mmat, d_aux_corr_mont;
+    agx::aux_view aux;
 };
 
 // agx_ntt_keyswitch_*: the shape and the bases of one hybrid key switch, and nothing of the plan but a pointer (as a basis: the plan outlives the

@@ -1,6 +1,6 @@
 // bfv_conv_selftest.cpp -- the host side of agx_ntt_basis_extend_exact and agx_ntt_basis_extend_mont against brute force: csrc/bfv_conv_arith.hpp, the per-word
-// steps and the very text the kernel compiles, and agx::aux_basis_constants (csrc/host_math.cpp).  Stand-alone: built from this file, tests/selftest.hpp,
-// bfv_conv_arith.hpp, inner_reduce.hpp and host_math.cpp by tests/test_bfv_conv_selftest.py with -fsanitize=address,undefined; no HIP, no plan.
+// steps and the very text the kernel compiles, and agx::prepare_basis_image (csrc/host_math.cpp).  Stand-alone: built from this file, tests/selftest.hpp,
+// bfv_conv_arith.hpp, inner_reduce.hpp and host_math.cpp by tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
 //   Moduli: the arguments (the class edges of tests/modulus_cases.py: the primes next to 2^31, 2^60, 2^61 and 2^62, those next to 2^60 - 2^28, the
 //   smallest admitted primes), at least 20 distinct odd primes.  S = 1, 2 and 16 sources taken from every position of the list, three targets behind them
 //   and the auxiliary prime m behind those: m comes from every class, tiny ones included.
@@ -79,46 +79,44 @@ static void check_steps(uint64_t q) {
     }
 }
 
+// the image of a request with t = 1 and the auxiliary modulus m; the last-stage constants, which the conversions do not read, are ones
 struct built {
     bool ok = false;
-    std::vector<uint64_t> dinv, dinv_p, mat, mat_p;
-    agx::aux_constants c;
+    agx::basis_image img;
 };
 
 static built build(const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst, uint64_t m) {
-    const size_t S = src.size(), T = dst.size();
+    const std::vector<uint64_t> one(src.size(), 1);
     built b;
-    b.dinv.resize(S), b.dinv_p.resize(S), b.mat.resize(T * S), b.mat_p.resize(T * S);      // exact sizes: the sanitizer sees a write past [S] or [T][S]
-    if (!agx::basis_constants(src.data(), (uint32_t)S, dst.data(), (uint32_t)T, b.dinv.data(), b.dinv_p.data(), b.mat.data(), b.mat_p.data())) return b;
-    b.ok = agx::aux_basis_constants(src.data(), (uint32_t)S, dst.data(), (uint32_t)T, m, b.dinv.data(), b.mat.data(), &b.c);
+    b.ok = agx::prepare_basis_image(b.img, {src.data(), (uint32_t)src.size(), dst.data(), (uint32_t)dst.size(), one.data(), one.data(), 1, m}) == agx::basis_fault::none;
     return b;
 }
 
 static void check_constants(const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst, uint64_t m, const built& b) {
     const size_t S = src.size(), T = dst.size();
-    const agx::aux_constants& c = b.c;
-    CHECK(c.row.size() == S && c.row_p.size() == S && c.mdinv.size() == S && c.mdinv_p.size() == S, "sizes [S]");
-    CHECK(c.corr_exact.size() == T && c.corr_exact_p.size() == T && c.corr_mont.size() == T && c.corr_mont_p.size() == T, "sizes [T]");
-    CHECK(c.mmat.size() == T * S && c.mmat_p.size() == T * S, "sizes [T][S]");
+    const agx::basis_image& c = b.img;
+    CHECK(c.aux_row.size() == S && c.aux_mdinv.size() == S, "sizes [S]");
+    CHECK(c.aux_corr_exact.size() == T && c.aux_corr_mont.size() == T, "sizes [T]");
+    CHECK(c.aux_mmat.size() == T * S, "sizes [T][S]");
     const uint64_t Dm = d_mod_brute(src, S, m);
-    CHECK(c.k_exact < m && mulmod(c.k_exact, Dm, m) == 1 % m, "S=%zu m=%llu: k_exact", S, (ull)m);
-    CHECK(c.k_mont < m && (c.k_exact + c.k_mont) % m == 0, "S=%zu m=%llu: k_mont", S, (ull)m);
-    CHECK(c.k_exact_p == quotient(c.k_exact, m) && c.k_mont_p == quotient(c.k_mont, m), "quotients of k");
+    CHECK(c.k_exact.w < m && mulmod(c.k_exact.w, Dm, m) == 1 % m, "S=%zu m=%llu: k_exact", S, (ull)m);
+    CHECK(c.k_mont.w < m && (c.k_exact.w + c.k_mont.w) % m == 0, "S=%zu m=%llu: k_mont", S, (ull)m);
+    CHECK(c.k_exact.p == quotient(c.k_exact.w, m) && c.k_mont.p == quotient(c.k_mont.w, m), "quotients of k");
     for (size_t i = 0; i < S; ++i) {
         const uint64_t q = src[i];
-        CHECK(c.row[i] == d_mod_brute(src, i, m) && c.row_p[i] == quotient(c.row[i], m), "S=%zu m=%llu: row[%zu]", S, (ull)m, i);
-        CHECK(c.mdinv[i] < q && mulmod(c.mdinv[i], d_mod_brute(src, i, q), q) == m % q, "S=%zu m=%llu: mdinv[%zu]", S, (ull)m, i);
-        CHECK(c.mdinv_p[i] == quotient(c.mdinv[i], q), "quotient of mdinv[%zu]", i);
+        CHECK(c.aux_row[i].w == d_mod_brute(src, i, m) && c.aux_row[i].p == quotient(c.aux_row[i].w, m), "S=%zu m=%llu: row[%zu]", S, (ull)m, i);
+        CHECK(c.aux_mdinv[i].w < q && mulmod(c.aux_mdinv[i].w, d_mod_brute(src, i, q), q) == m % q, "S=%zu m=%llu: mdinv[%zu]", S, (ull)m, i);
+        CHECK(c.aux_mdinv[i].p == quotient(c.aux_mdinv[i].w, q), "quotient of mdinv[%zu]", i);
     }
     for (size_t j = 0; j < T; ++j) {
         const uint64_t q = dst[j], Dq = d_mod_brute(src, S, q);
-        CHECK(c.corr_exact[j] == Dq && c.corr_exact_p[j] == quotient(Dq, q), "S=%zu: corr_exact[%zu]", S, j);
-        CHECK(c.corr_mont[j] < q && (mulmod(c.corr_mont[j], m % q, q) + Dq) % q == 0, "S=%zu m=%llu: corr_mont[%zu]", S, (ull)m, j);
-        CHECK(c.corr_mont_p[j] == quotient(c.corr_mont[j], q), "quotient of corr_mont[%zu]", j);
+        CHECK(c.aux_corr_exact[j].w == Dq && c.aux_corr_exact[j].p == quotient(Dq, q), "S=%zu: corr_exact[%zu]", S, j);
+        CHECK(c.aux_corr_mont[j].w < q && (mulmod(c.aux_corr_mont[j].w, m % q, q) + Dq) % q == 0, "S=%zu m=%llu: corr_mont[%zu]", S, (ull)m, j);
+        CHECK(c.aux_corr_mont[j].p == quotient(c.aux_corr_mont[j].w, q), "quotient of corr_mont[%zu]", j);
         for (size_t i = 0; i < S; ++i) {
             const size_t at = j * S + i;
-            CHECK(c.mmat[at] < q && mulmod(c.mmat[at], m % q, q) == d_mod_brute(src, i, q), "S=%zu m=%llu: mmat[%zu][%zu]", S, (ull)m, j, i);
-            CHECK(c.mmat_p[at] == quotient(c.mmat[at], q), "quotient of mmat[%zu][%zu]", j, i);
+            CHECK(c.aux_mmat[at].w < q && mulmod(c.aux_mmat[at].w, m % q, q) == d_mod_brute(src, i, q), "S=%zu m=%llu: mmat[%zu][%zu]", S, (ull)m, j, i);
+            CHECK(c.aux_mmat[at].p == quotient(c.aux_mmat[at].w, q), "quotient of mmat[%zu][%zu]", j, i);
         }
     }
 }
@@ -133,25 +131,25 @@ static int bits_of(u128 v) {
 static std::vector<uint64_t> kernel_word(const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst, uint64_t m, const built& b, bool exact,
                                          const std::vector<uint64_t>& x, uint64_t xaux) {
     const size_t S = src.size(), T = dst.size();
-    const agx::aux_constants& c = b.c;
+    const agx::basis_image& c = b.img;
     std::vector<uint64_t> y(S), out(T);
     uint64_t vm = 0;
     for (size_t i = 0; i < S; ++i) {
-        y[i] = agx::bfv_shoup(x[i], exact ? b.dinv[i] : c.mdinv[i], exact ? b.dinv_p[i] : c.mdinv_p[i], src[i]);
-        vm = (uint64_t)(((u128)vm + agx::bfv_shoup(y[i], c.row[i], c.row_p[i], m)) % m);
+        y[i] = agx::bfv_shoup(x[i], exact ? b.img.dinv[i].w : c.aux_mdinv[i].w, exact ? b.img.dinv[i].p : c.aux_mdinv[i].p, src[i]);
+        vm = (uint64_t)(((u128)vm + agx::bfv_shoup(y[i], c.aux_row[i].w, c.aux_row[i].p, m)) % m);
     }
     const uint64_t r = exact ? agx::bfv_reduce_lazy(xaux, m) : 0;
     bool negative = false;
-    const uint64_t mag = agx::bfv_centre(agx::bfv_alpha(vm, r, exact ? c.k_exact : c.k_mont, exact ? c.k_exact_p : c.k_mont_p, m), m, &negative);
+    const uint64_t mag = agx::bfv_centre(agx::bfv_alpha(vm, r, exact ? c.k_exact.w : c.k_mont.w, exact ? c.k_exact.p : c.k_mont.p, m), m, &negative);
     for (size_t j = 0; j < T; ++j) {
         const uint64_t q = dst[j];
         uint64_t acc = 0;
         for (size_t i = 0; i < S; ++i) {
             const size_t at = j * S + i;
-            acc = (uint64_t)(((u128)acc + agx::bfv_shoup(y[i], exact ? b.mat[at] : c.mmat[at], exact ? b.mat_p[at] : c.mmat_p[at], q)) % q);
+            acc = (uint64_t)(((u128)acc + agx::bfv_shoup(y[i], exact ? b.img.mat[at].w : c.aux_mmat[at].w, exact ? b.img.mat[at].p : c.aux_mmat[at].p, q)) % q);
         }
         if (next64() & 1) acc += q;
-        out[j] = agx::bfv_correct(acc, mag, negative, exact ? c.corr_exact[j] : c.corr_mont[j], exact ? c.corr_exact_p[j] : c.corr_mont_p[j], q);
+        out[j] = agx::bfv_correct(acc, mag, negative, exact ? c.aux_corr_exact[j].w : c.aux_corr_mont[j].w, exact ? c.aux_corr_exact[j].p : c.aux_corr_mont[j].p, q);
     }
     return out;
 }
@@ -191,7 +189,7 @@ static void check_conversions(const std::vector<uint64_t>& src, const std::vecto
         for (size_t i = 0; i < S; ++i) {
             const uint64_t xr = k == 0 ? 0 : k == 1 ? src[i] - 1 : k == 2 ? 1 % src[i] : next64() % src[i];
             x[i] = xr + (next64() & 3) * src[i];
-            y[i] = mulmod(mulmod(xr, m % src[i], src[i]), b.dinv[i], src[i]);      // x_i' m D_i^-1 mod q_i
+            y[i] = mulmod(mulmod(xr, m % src[i], src[i]), b.img.dinv[i].w, src[i]);      // x_i' m D_i^-1 mod q_i
         }
         uint64_t dm_inv = 0;
         CHECK(agx::inv_mod_euclid(d_mod_brute(src, S, m), m, &dm_inv), "D has no inverse modulo m");
@@ -211,7 +209,7 @@ static void check_conversions(const std::vector<uint64_t>& src, const std::vecto
         for (uint64_t q : src) D *= q;
         for (size_t i = 0; i < S; ++i) {
             V += (u128)y[i] * (D / src[i]);
-            X += (u128)mulmod(x[i] % src[i], b.dinv[i], src[i]) * (D / src[i]);
+            X += (u128)mulmod(x[i] % src[i], b.img.dinv[i].w, src[i]) * (D / src[i]);
         }
         X %= D;
         const i128 num = (i128)V + (negative ? -(i128)mag : (i128)mag) * (i128)D;

@@ -1,7 +1,7 @@
 // moddown_modes_selftest.cpp -- the host side of agx_ntt_basis_mod_down_mode and agx_ntt_basis_create_plain against brute force: csrc/moddown_arith.hpp,
-// the two per-word steps of AGX_RESCALE_ROUND and the very text the kernels compile, and agx::half_product_mod / agx::moddown_mode_constants
+// the two per-word steps of AGX_RESCALE_ROUND and the very text the kernels compile, and agx::half_product_mod / agx::prepare_basis_image
 // (csrc/host_math.cpp).  Stand-alone: built from this file, tests/selftest.hpp, moddown_arith.hpp, inner_reduce.hpp and host_math.cpp by
-// tests/test_moddown_modes_selftest.py with -fsanitize=address,undefined; no HIP, no plan.
+// tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
 //   Moduli: the arguments (the class edges of tests/modulus_cases.py: the primes next to 2^31, 2^60, 2^61 and 2^62, those next to 2^60 - 2^28, the
 //   smallest admitted primes), at least 20 distinct odd primes.  S = 1, 2 and 16 sources taken from every position of the list, three targets behind them.
 //   t = 1, 2, 65537, 2^64 - 59, and t = a source modulus and twice it, which must be refused.
@@ -49,28 +49,26 @@ static uint64_t d_mod_brute(const std::vector<uint64_t>& src, size_t skip, uint6
     return (uint64_t)r;
 }
 
+// a request without an m, its image, and the image of the same request with t = 1; ok: accepted, and every target has its D^-1
 struct built {
     bool ok = false;
-    std::vector<uint64_t> dinv, dinv_p, mat, mat_p, n_inv, w1n, dall, dall_p, sn, sn_p, sw, sw_p, sn0, sw0, dmat, dmat_p, cadd, hq;
+    std::vector<uint64_t> n_inv, w1n;
+    agx::basis_image img, plain;
 };
 
 static built build(const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst, uint32_t n, uint64_t t) {
     const size_t S = src.size(), T = dst.size();
-    auto v = [](size_t k) { return std::vector<uint64_t>(k); };      // exact sizes: the sanitizer sees a write past [S], [T] or [T][S]
     built b;
-    b.dinv = v(S), b.dinv_p = v(S), b.mat = v(T * S), b.mat_p = v(T * S), b.n_inv = v(S), b.w1n = v(S), b.dall = v(T), b.dall_p = v(T);
-    b.sn = v(S), b.sn_p = v(S), b.sw = v(S), b.sw_p = v(S), b.dmat = v(T * S), b.dmat_p = v(T * S), b.cadd = v(S), b.hq = v(T);
-    if (!agx::basis_constants(src.data(), (uint32_t)S, dst.data(), (uint32_t)T, b.dinv.data(), b.dinv_p.data(), b.mat.data(), b.mat_p.data())) return b;
+    b.n_inv.resize(S), b.w1n.resize(S);
     for (size_t i = 0; i < S; ++i) {
         CHECK(agx::inv_mod_euclid(n % src[i], src[i], &b.n_inv[i]), "n has no inverse modulo an odd prime");
         b.w1n[i] = next64() % src[i];
     }
-    if (!agx::moddown_constants(src.data(), (uint32_t)S, dst.data(), (uint32_t)T, b.dinv.data(), b.n_inv.data(), b.w1n.data(), b.dall.data(), b.dall_p.data(),
-                                b.sn.data(), b.sn_p.data(), b.sw.data(), b.sw_p.data()))
-        return b;
-    b.sn0 = b.sn, b.sw0 = b.sw;
-    b.ok = agx::moddown_mode_constants(src.data(), (uint32_t)S, dst.data(), (uint32_t)T, t, b.dinv.data(), b.mat.data(), b.sn.data(), b.sn_p.data(), b.sw.data(),
-                                       b.sw_p.data(), b.dmat.data(), b.dmat_p.data(), b.cadd.data(), b.hq.data());
+    agx::basis_request rq{src.data(), (uint32_t)S, dst.data(), (uint32_t)T, b.n_inv.data(), b.w1n.data()};
+    if (agx::prepare_basis_image(b.plain, rq) != agx::basis_fault::none || !b.plain.moddown_legal) return b;
+    rq.t = t;
+    b.ok = agx::prepare_basis_image(b.img, rq) == agx::basis_fault::none;
+    if (b.ok) CHECK(b.img.sn.size() == S && b.img.sw.size() == S && b.img.round_src.size() == S && b.img.round_dst.size() == T && b.img.down_mat.size() == T * S, "sizes [S], [T], [T][S]");
     return b;
 }
 
@@ -82,21 +80,23 @@ static void check_constants(const std::vector<uint64_t>& src, const std::vector<
     for (size_t i = 0; i < S; ++i) {
         const uint64_t q = src[i], h = half_mod_brute(src, q);
         CHECK(agx::half_product_mod(src.data(), (uint32_t)S, q) == h, "S=%zu: h mod source %zu", S, i);
-        CHECK(b.sn[i] < q && b.sw[i] < q && b.cadd[i] < q, "S=%zu: constants of source %zu not reduced", S, i);
-        CHECK(mulmod(b.sn[i], t % q, q) == b.sn0[i] && mulmod(b.sw[i], t % q, q) == b.sw0[i], "S=%zu t=%llu: sn, sw of source %zu times t", S, (ull)t, i);
-        CHECK(b.sn_p[i] == (uint64_t)(((u128)b.sn[i] << 64) / q) && b.sw_p[i] == (uint64_t)(((u128)b.sw[i] << 64) / q), "S=%zu: quotients of source %zu", S, i);
-        CHECK(mulmod(b.cadd[i], d_mod_brute(src, i, q), q) == h, "S=%zu: c_%zu D_i != h", S, i);
-        if (t == 1) CHECK(b.sn[i] == b.sn0[i] && b.sw[i] == b.sw0[i], "t = 1 changed sn or sw");
+        CHECK(b.img.sn[i].w < q && b.img.sw[i].w < q && b.img.round_src[i].w < q, "S=%zu: constants of source %zu not reduced", S, i);
+        CHECK(mulmod(b.img.sn[i].w, t % q, q) == b.plain.sn[i].w && mulmod(b.img.sw[i].w, t % q, q) == b.plain.sw[i].w, "S=%zu t=%llu: sn, sw of source %zu times t", S, (ull)t, i);
+        CHECK(b.img.sn[i].p == (uint64_t)(((u128)b.img.sn[i].w << 64) / q) && b.img.sw[i].p == (uint64_t)(((u128)b.img.sw[i].w << 64) / q), "S=%zu: quotients of source %zu", S, i);
+        CHECK(mulmod(b.img.round_src[i].w, d_mod_brute(src, i, q), q) == h, "S=%zu: c_%zu D_i != h", S, i);
+        CHECK(b.plain.sn[i].w == mulmod(b.n_inv[i], b.img.dinv[i].w, q) && b.plain.sw[i].w == mulmod(b.w1n[i], b.img.dinv[i].w, q), "S=%zu: sn, sw of source %zu with t = 1", S, i);
+        CHECK(b.img.round_src[i].p == q, "S=%zu: the second word of round_src[%zu] is not the modulus", S, i);
+        if (t == 1) CHECK(b.img.sn[i].w == b.plain.sn[i].w && b.img.sw[i].w == b.plain.sw[i].w, "t = 1 changed sn or sw");
     }
     for (size_t j = 0; j < T; ++j) {
         const uint64_t q = dst[j], h = half_mod_brute(src, q);
         CHECK(agx::half_product_mod(src.data(), (uint32_t)S, q) == h, "S=%zu: h mod target %zu", S, j);
-        CHECK(b.hq[j] == mulmod(t % q, h, q), "S=%zu t=%llu: hq[%zu]", S, (ull)t, j);
+        CHECK(b.img.round_dst[j] == mulmod(t % q, h, q), "S=%zu t=%llu: hq[%zu]", S, (ull)t, j);
         for (size_t i = 0; i < S; ++i) {
             const size_t at = j * S + i;
-            CHECK(b.dmat[at] == mulmod(t % q, d_mod_brute(src, i, q), q), "S=%zu t=%llu: matrix [%zu][%zu]", S, (ull)t, j, i);
-            CHECK(b.dmat_p[at] == (uint64_t)(((u128)b.dmat[at] << 64) / q), "S=%zu: quotient of matrix [%zu][%zu]", S, j, i);
-            if (t == 1) CHECK(b.dmat[at] == b.mat[at] && b.dmat_p[at] == b.mat_p[at], "t = 1 changed the matrix");
+            CHECK(b.img.down_mat[at].w == mulmod(t % q, d_mod_brute(src, i, q), q), "S=%zu t=%llu: matrix [%zu][%zu]", S, (ull)t, j, i);
+            CHECK(b.img.down_mat[at].p == (uint64_t)(((u128)b.img.down_mat[at].w << 64) / q), "S=%zu: quotient of matrix [%zu][%zu]", S, j, i);
+            if (t == 1) CHECK(b.img.down_mat[at].w == b.img.mat[at].w && b.img.down_mat[at].p == b.img.mat[at].p, "t = 1 changed the matrix");
         }
     }
 }
@@ -160,8 +160,8 @@ static void check_mod_down(const std::vector<uint64_t>& src, const std::vector<u
             std::vector<uint64_t> y(S);
             for (size_t i = 0; i < S; ++i) {
                 const uint64_t q = src[i];
-                y[i] = mulmod(mulmod((uint64_t)(r % q), n % q, q), b.sn[i], q);      // what the scaled inverse writes: p_i t^-1 D_i^-1
-                if (round) y[i] = agx::moddown_round_y(y[i], b.cadd[i], q);
+                y[i] = mulmod(mulmod((uint64_t)(r % q), n % q, q), b.img.sn[i].w, q);      // what the scaled inverse writes: p_i t^-1 D_i^-1
+                if (round) y[i] = agx::moddown_round_y(y[i], b.img.round_src[i].w, q);
                 V += (u128)y[i] * Di[i];
             }
             CHECK(V / D < S, "V is not below S D");
@@ -172,9 +172,9 @@ static void check_mod_down(const std::vector<uint64_t>& src, const std::vector<u
             for (size_t j = 0; j < T; ++j) {
                 const uint64_t q = dst[j];
                 uint64_t acc = 0;
-                for (size_t i = 0; i < S; ++i) acc = (acc + mulmod(y[i] % q, b.dmat[j * S + i], q)) % (2 * q);      // in [0, 2q), as basis_accumulate leaves it
-                if (round) acc = agx::moddown_round_acc(acc, b.hq[j], q);
-                const uint64_t got = mulmod((uint64_t)((X % q + 2 * (u128)q - acc) % q), b.dall[j], q);
+                for (size_t i = 0; i < S; ++i) acc = (acc + mulmod(y[i] % q, b.img.down_mat[j * S + i].w, q)) % (2 * q);      // in [0, 2q), as basis_accumulate leaves it
+                if (round) acc = agx::moddown_round_acc(acc, b.img.round_dst[j], q);
+                const uint64_t got = mulmod((uint64_t)((X % q + 2 * (u128)q - acc) % q), b.img.dall[j].w, q);
                 const i128 m = quotient % (i128)q;
                 CHECK(got == (uint64_t)(m < 0 ? m + (i128)q : m), "S=%zu t=%llu mode %d: target %zu", S, (ull)t, round, j);
             }

@@ -1,4 +1,4 @@
-// moddown_selftest.cpp -- agx::moddown_constants (csrc/host_math.cpp), the host side of agx_ntt_basis_mod_down, against brute force in unsigned __int128.
+// moddown_selftest.cpp -- agx::prepare_basis_image (csrc/host_math.cpp), the host side of agx_ntt_basis_mod_down, against brute force in unsigned __int128.
 // Stand-alone: built from this file, tests/selftest.hpp and host_math.cpp by tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
 //   * dall[j] D = 1 (mod q_j) with D taken factor by factor in another order than the builder takes it, dall[j] < q_j, its quotient = floor(w 2^64 / q);
 //   * sn[i] = n^-1 D_i^-1 and sw[i] = w1n D_i^-1 (mod q_i), reduced, with their quotients; sn[i] n D_i = 1 (mod q_i) closes the loop on n^-1;
@@ -21,55 +21,51 @@ static uint64_t d_mod_brute(const std::vector<uint64_t>& src, size_t skip, uint6
     return (uint64_t)r;
 }
 
+// a request with t = 1 and no m, and its image
 struct built {
-    bool basis_ok, all;
-    std::vector<uint64_t> dinv, dinv_p, mat, mat_p, n_inv, w1n, dall, dall_p, sn, sn_p, sw, sw_p;
+    bool ok;
+    std::vector<uint64_t> n_inv, w1n;
+    agx::basis_image img;
 };
 // n: the transform size whose n^-1 the constants carry; w1n: any residue stands for inv_twiddle[1] n^-1
 static built build(const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst, uint32_t n) {
     const size_t S = src.size(), T = dst.size();
-    auto v = [](size_t k) { return std::vector<uint64_t>(k); };      // exact sizes: the sanitizer sees a write past [S] or [T]
-    built b{false, false, v(S), v(S), v(T * S), v(T * S), v(S), v(S), v(T), v(T), v(S), v(S), v(S), v(S)};
-    b.basis_ok = agx::basis_constants(src.data(), (uint32_t)S, dst.data(), (uint32_t)T, b.dinv.data(), b.dinv_p.data(), b.mat.data(), b.mat_p.data());
-    if (!b.basis_ok) return b;
+    built b{false, std::vector<uint64_t>(S), std::vector<uint64_t>(S), {}};
     for (size_t i = 0; i < S; ++i) {
-        uint64_t ninv = 0;
-        CHECK(agx::inv_mod_euclid(n % src[i], src[i], &ninv), "n has no inverse modulo an odd prime");
-        b.n_inv[i] = ninv;
+        CHECK(agx::inv_mod_euclid(n % src[i], src[i], &b.n_inv[i]), "n has no inverse modulo an odd prime");
         b.w1n[i] = next64() % src[i];
     }
-    for (size_t j = 0; j < T; ++j) b.dall[j] = b.dall_p[j] = 0xDEADBEEFull;      // every entry must be written
-    b.all = agx::moddown_constants(src.data(), (uint32_t)S, dst.data(), (uint32_t)T, b.dinv.data(), b.n_inv.data(), b.w1n.data(), b.dall.data(), b.dall_p.data(),
-                                   b.sn.data(), b.sn_p.data(), b.sw.data(), b.sw_p.data());
+    b.ok = agx::prepare_basis_image(b.img, {src.data(), (uint32_t)S, dst.data(), (uint32_t)T, b.n_inv.data(), b.w1n.data()}) == agx::basis_fault::none;
+    if (b.ok) CHECK(b.img.sn.size() == S && b.img.sw.size() == S && b.img.dall.size() == T, "sizes [S], [T]: every entry must be written");
     return b;
 }
 
 static void check_constants(const char* what, const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst, uint32_t n, bool expect_all) {
     const size_t S = src.size(), T = dst.size();
     const built b = build(src, dst, n);
-    CHECK(b.basis_ok, "%s: basis refused", what);
-    if (!b.basis_ok) return;
-    CHECK(b.all == expect_all, "%s: reported %d, expected %d", what, (int)b.all, (int)expect_all);
+    CHECK(b.ok, "%s: basis refused", what);
+    if (!b.ok) return;
+    CHECK(b.img.moddown_legal == expect_all, "%s: reported %d, expected %d", what, (int)b.img.moddown_legal, (int)expect_all);
     for (size_t i = 0; i < S; ++i) {
         const uint64_t q = src[i], di = d_mod_brute(src, i, q);
-        CHECK(b.sn[i] < q && b.sw[i] < q, "%s: scaled constants of source %zu not reduced", what, i);
-        CHECK(mulmod(mulmod(b.sn[i], n % q, q), di, q) == 1 % q, "%s: sn[%zu] n D_i != 1", what, i);
-        CHECK(b.sn[i] == mulmod(b.n_inv[i], b.dinv[i], q), "%s: sn[%zu]", what, i);
-        CHECK(mulmod(b.sw[i], di, q) == b.w1n[i], "%s: sw[%zu] D_i != w1n", what, i);
-        CHECK(b.sn_p[i] == (uint64_t)(((u128)b.sn[i] << 64) / q), "%s: quotient of sn[%zu]", what, i);
-        CHECK(b.sw_p[i] == (uint64_t)(((u128)b.sw[i] << 64) / q), "%s: quotient of sw[%zu]", what, i);
+        CHECK(b.img.sn[i].w < q && b.img.sw[i].w < q, "%s: scaled constants of source %zu not reduced", what, i);
+        CHECK(mulmod(mulmod(b.img.sn[i].w, n % q, q), di, q) == 1 % q, "%s: sn[%zu] n D_i != 1", what, i);
+        CHECK(b.img.sn[i].w == mulmod(b.n_inv[i], b.img.dinv[i].w, q), "%s: sn[%zu]", what, i);
+        CHECK(mulmod(b.img.sw[i].w, di, q) == b.w1n[i], "%s: sw[%zu] D_i != w1n", what, i);
+        CHECK(b.img.sn[i].p == (uint64_t)(((u128)b.img.sn[i].w << 64) / q), "%s: quotient of sn[%zu]", what, i);
+        CHECK(b.img.sw[i].p == (uint64_t)(((u128)b.img.sw[i].w << 64) / q), "%s: quotient of sw[%zu]", what, i);
     }
     for (size_t j = 0; j < T; ++j) {
         const uint64_t q = dst[j], d = d_mod_brute(src, S, q);
         bool is_source = false;
         for (size_t k = 0; k < S; ++k) is_source |= src[k] == q;
         if (is_source) {
-            CHECK(d == 0 && b.dall[j] == 0 && b.dall_p[j] == 0, "%s: target %zu is a source but has constants", what, j);
+            CHECK(d == 0 && b.img.dall[j].w == 0 && b.img.dall[j].p == 0, "%s: target %zu is a source but has constants", what, j);
             continue;
         }
-        CHECK(b.dall[j] < q, "%s: dall[%zu] not reduced", what, j);
-        CHECK(mulmod(b.dall[j], d, q) == 1 % q, "%s: dall[%zu] is not the inverse of D", what, j);
-        CHECK(b.dall_p[j] == (uint64_t)(((u128)b.dall[j] << 64) / q), "%s: quotient of dall[%zu]", what, j);
+        CHECK(b.img.dall[j].w < q, "%s: dall[%zu] not reduced", what, j);
+        CHECK(mulmod(b.img.dall[j].w, d, q) == 1 % q, "%s: dall[%zu] is not the inverse of D", what, j);
+        CHECK(b.img.dall[j].p == (uint64_t)(((u128)b.img.dall[j].w << 64) / q), "%s: quotient of dall[%zu]", what, j);
     }
 }
 
@@ -77,8 +73,8 @@ static void check_constants(const char* what, const std::vector<uint64_t>& src, 
 static void check_mod_down(const char* what, const std::vector<uint64_t>& src, const std::vector<uint64_t>& dst, uint32_t n, int random_values) {
     const size_t S = src.size(), T = dst.size();
     const built b = build(src, dst, n);
-    CHECK(b.basis_ok && b.all, "%s: refused", what);
-    if (!b.basis_ok || !b.all) return;
+    CHECK(b.ok && b.img.moddown_legal, "%s: refused", what);
+    if (!b.ok || !b.img.moddown_legal) return;
     u128 D = 1;
     std::vector<u128> Di(S, 1);
     for (size_t i = 0; i < S; ++i) {
@@ -96,8 +92,8 @@ static void check_mod_down(const char* what, const std::vector<uint64_t>& src, c
         std::vector<uint64_t> y(S);
         for (size_t i = 0; i < S; ++i) {
             const uint64_t q = src[i];
-            y[i] = mulmod(mulmod((uint64_t)(r % q), n % q, q), b.sn[i], q);
-            CHECK(y[i] == mulmod((uint64_t)(r % q), b.dinv[i], q), "%s: the scaled inverse constant does not give y_%zu", what, i);
+            y[i] = mulmod(mulmod((uint64_t)(r % q), n % q, q), b.img.sn[i].w, q);
+            CHECK(y[i] == mulmod((uint64_t)(r % q), b.img.dinv[i].w, q), "%s: the scaled inverse constant does not give y_%zu", what, i);
             V += (u128)y[i] * Di[i];
         }
         CHECK(V % D == r, "%s: V is not congruent to the sources' value", what);
@@ -106,9 +102,9 @@ static void check_mod_down(const char* what, const std::vector<uint64_t>& src, c
         for (size_t j = 0; j < T; ++j) {
             const uint64_t q = dst[j];
             u128 acc = 0;
-            for (size_t i = 0; i < S; ++i) acc += (u128)y[i] * b.mat[j * S + i];
+            for (size_t i = 0; i < S; ++i) acc += (u128)y[i] * b.img.mat[j * S + i].w;
             const uint64_t a = (uint64_t)(X % q), v = (uint64_t)(acc % q);
-            const uint64_t got = mulmod((a + q - v) % q, b.dall[j], q);
+            const uint64_t got = mulmod((a + q - v) % q, b.img.dall[j].w, q);
             const uint64_t want = (uint64_t)((Y % q + q - (uint64_t)(u % q)) % q);      // floor(X / D) - u
             CHECK(got == want, "%s: target %zu", what, j);
         }

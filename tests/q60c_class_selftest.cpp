@@ -1,4 +1,4 @@
-// q60c_class_selftest.cpp -- stand-alone CPU program (own main; tests/test_q60c_class_selftest.py builds and runs it under the sanitizers): the two questions
+// q60c_class_selftest.cpp -- stand-alone CPU program (own main; tests/test_selftests.py builds and runs it under the sanitizers): the two questions
 // csrc/q60c_class.hpp answers about a plan's moduli, against their definitions.  q60c_of: c for q = 2^60 - c with 0 < c < 2^28, 0 otherwise, on both edges.
 // q60c_skip_class, the per-plan flag that makes registry id 165 launch its skip-form kernel: true exactly when EVERY modulus has 0 < c <= 2^27 -- one
 // modulus outside, as first, last or any middle entry of the set, clears it, so a flag taken from one end of the list alone would show here.

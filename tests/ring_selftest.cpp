@@ -1,6 +1,6 @@
 // ring_selftest.cpp -- csrc/ring_arith.hpp, the per-word arithmetic of agx_ntt_add / _sub / _negate / _add_galois / _tensor and the very text the kernels
 // compile, against unsigned __int128.  Stand-alone: built from this file, tests/selftest.hpp, ring_arith.hpp and inner_reduce.hpp alone by
-// tests/test_ring_selftest.py with -fsanitize=address,undefined; no HIP, no plan.
+// tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
 //   add, sub, negate: every pair of the edge words 0, 1, q - 1, q, q + 1, 2q - 1, 2q, 2q + 1, 3q, 4q - 1 of the lazy input range, and random words over
 //   the whole of [0, 4q); every result equals the big-integer one and lies below q; -0 = 0.
 //   the tensor triple: a0 = a1 = b0 = b1 = q - 1 reduced and in every lazy representative, edge words, random words; squaring (a = b).

@@ -1,7 +1,7 @@
 // weighted_selftest.cpp -- csrc/weighted_arith.hpp, the per-word finish of agx_ntt_keyswitch_accumulate_decomposed and agx_ntt_mul_add_galois and the very
 // text the kernels compile, against unsigned __int128.  Stand-alone: built from this file, tests/selftest.hpp, weighted_arith.hpp, ring_arith.hpp and
-// inner_reduce.hpp alone by tests/test_weighted_selftest.py with -fsanitize=address,undefined; no HIP, no plan.
-//   Moduli: the arguments (tests/test_weighted_selftest.py passes the class edges of tests/modulus_cases.py: the primes next to 2^31, 2^60 and 2^62, those
+// inner_reduce.hpp alone by tests/test_selftests.py with -fsanitize=address,undefined; no HIP, no plan.
+//   Moduli: the arguments (tests/test_selftests.py passes the class edges of tests/modulus_cases.py: the primes next to 2^31, 2^60 and 2^62, those
 //   next to 2^60 - 2^28, the smallest admitted primes), and always the built-in list below.  The finish asks for an odd q < 2^62 only.
 //   Operands: the weight and the old word at 0, 1, q - 1, q, 2q, 4q - 1 (and 2^64 - 1 where 4q exceeds it, which no admitted modulus reaches: 4q < 2^64),
 //   t at 0, 1, q - 1; random words over the whole ranges; with the old word present and absent, with the weight present and absent.
