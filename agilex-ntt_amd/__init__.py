@@ -51,6 +51,8 @@ ABI = {
     "agx_ntt_inverse": (_int, [_vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_forward_strided": (_int, [_vp, _vp, _vp, _u64, _i64, _i64, _vp]),
     "agx_ntt_inverse_strided": (_int, [_vp, _vp, _vp, _u64, _i64, _i64, _vp]),
+    "agx_ntt_forward_range": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _vp]),
+    "agx_ntt_inverse_range": (_int, [_vp, _vp, _vp, _u64, _u32, _u32, _vp]),
     "agx_ntt_pointwise": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_polymul": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_polymul_ntt": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp]),
@@ -69,6 +71,9 @@ ABI = {
     "agx_ntt_basis_aux_info": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_u32), ctypes.POINTER(_int)]),
     "agx_ntt_basis_extend_exact": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_basis_extend_mont": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
+    "agx_ntt_basis_create_quotient": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u32, _u32, _u64]),
+    "agx_ntt_basis_quotient_info": (_int, [_vp, ctypes.POINTER(_int), _p64, ctypes.POINTER(_int)]),
+    "agx_ntt_basis_quotient": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_inner_product": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _vp]),
     "agx_ntt_inner_product_galois": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _u32, _u32, _u32, _vp]),
     "agx_ntt_add": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _vp]),
@@ -326,6 +331,15 @@ class Plan:
     def inverse(self, d_in, d_out, batch, stream=0):
         _check(lib().agx_ntt_inverse(self._h, d_in, d_out, batch, stream), "inverse")
 
+    def forward_range(self, d_in, d_out, batch, prime_first, prime_count, stream=0):
+        """forward on the plan primes [prime_first, prime_first + prime_count): d_in, d_out dense [prime_count][batch][n], the words a plan over those
+        primes with the same roots would write; in place allowed"""
+        _check(lib().agx_ntt_forward_range(self._h, d_in, d_out, batch, prime_first, prime_count, stream), "forward_range")
+
+    def inverse_range(self, d_in, d_out, batch, prime_first, prime_count, stream=0):
+        """inverse on the plan primes [prime_first, prime_first + prime_count), as forward_range"""
+        _check(lib().agx_ntt_inverse_range(self._h, d_in, d_out, batch, prime_first, prime_count, stream), "inverse_range")
+
     def forward_strided(self, d_in, d_out, batch, prime_stride, poly_stride, stream=0):
         _check(lib().agx_ntt_forward_strided(self._h, d_in, d_out, batch, prime_stride, poly_stride, stream), "forward_strided")
 
@@ -362,6 +376,11 @@ class Plan:
         """Basis.with_aux(self, ...): that basis (t = 1) with the plan prime aux_prime, outside both ranges, as its auxiliary prime: the one that
         extend_exact and extend_mont (the exact conversions of a BFV multiplication) need"""
         return Basis.with_aux(self, src_first, src_count, dst_first, dst_count, aux_prime)
+
+    def basis_quotient(self, b_first, b_count, q_first, q_count, aux_prime, t):
+        """Basis.with_quotient(self, ...): the basis of basis_aux(b_first, b_count, q_first, q_count, aux_prime) with the constants of Basis.quotient for
+        the plaintext modulus t: BFV's divide-and-return in one call"""
+        return Basis.with_quotient(self, b_first, b_count, q_first, q_count, aux_prime, t)
 
     def inner_product(self, d_a, d_bhat, d_c, batch, terms, outputs=1, bhat_batch=None, stream=0):
         """c_o = sum_t a_t o bhat_{t,o} mod q in one launch: d_a [terms][P][batch][n], d_bhat [terms][outputs][P][bhat_batch][n], d_c
@@ -461,6 +480,30 @@ class Basis:
         handle = plan._h if isinstance(plan, Plan) else plan
         _check(lib().agx_ntt_basis_create_aux(ctypes.byref(self._h), handle, src_first, src_count, dst_first, dst_count, aux_prime), "basis_create_aux")
         return self
+
+    @classmethod
+    def with_quotient(cls, plan, b_first, b_count, q_first, q_count, aux_prime, t):
+        """the basis of Basis.with_aux(plan, b_first, b_count, q_first, q_count, aux_prime) -- sources B, targets Q, auxiliary prime m, every other call
+        unchanged -- with the constants of quotient for the plaintext modulus t (agx_ntt_basis_create_quotient): any 64-bit t >= 1"""
+        self = cls.__new__(cls)
+        self.plan = plan      # keeps a Plan alive
+        self._h = _vp(None)
+        handle = plan._h if isinstance(plan, Plan) else plan
+        _check(lib().agx_ntt_basis_create_quotient(ctypes.byref(self._h), handle, b_first, b_count, q_first, q_count, aux_prime, t), "basis_create_quotient")
+        return self
+
+    def quotient_info(self):
+        """(has_quotient, t, launches): whether the basis carries the quotient's constants, their t (0 without), and the kernel launches a quotient call
+        takes under the plan's current variant"""
+        has, t, launches = _int(0), _u64(0), _int(0)
+        _check(lib().agx_ntt_basis_quotient_info(self._h, ctypes.byref(has), ctypes.byref(t), ctypes.byref(launches)), "basis_quotient_info")
+        return bool(has.value), t.value, launches.value
+
+    def quotient(self, d_x, d_out, d_scratch, batch, stream=0):
+        """steps 4 to 7 of a BFV multiplication in one call: d_x [q_count + b_count + 1][batch][n] in NTT form (the slabs of Q, of B, of m: one component
+        of the tensor product) -> d_out [q_count][batch][n] in NTT form: extend_exact of the fast floor of t x / Q, word for word; d_scratch: as many
+        words as d_x, or d_x itself (which is then overwritten); d_out touches neither"""
+        _check(lib().agx_ntt_basis_quotient(self._h, d_x, d_out, d_scratch, batch, stream), "basis_quotient")
 
     def aux_info(self):
         """(has_aux, aux_prime, launches_ntt_form): whether the basis has an auxiliary prime, its index in the plan, and the kernel launches a FORM_NTT

@@ -504,6 +504,32 @@ int agx_ntt_inverse(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_
     return agx_ntt_inverse_strided(plan, d_in, d_out, batch, fl.prime_stride, fl.poly_stride, stream);
 }
 
+// agx_ntt_forward_range and agx_ntt_inverse_range: the whole-plan calls' rules in their order on the dense frames of `count` primes, the ring calls' range
+// rule right behind the NULL rule; then the plan's route for this batch viewed on the range, as the RNS calls run it
+static int range_call(bool inverse, const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t first, uint32_t count, void* stream) {
+    if (!plan || !d_in || !d_out) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes, n = plan->n;
+    if (count == 0 || count > P || first > P - count) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    const frame_layout fl = dense(plan, batch);
+    if (!aligned8(d_in) || !batch_fits_grid(plan, batch) || !layout_fits(n, count, batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;
+    if (!aligned8(d_out) || partial_overlap(addr(d_in), addr(d_out), n, count, batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;      // out may BE in, never straddle it
+    if (inverse && !plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (inverse) AGX_HIP(run_inverse(prime_range(plan->routes.inverse, first, first + count), d_in, nullptr, d_out, fl, s));
+    else AGX_HIP(run_forward(prime_range(forward_route(plan, batch), first, first + count), d_in, d_out, fl, s));
+    return AGX_OK;
+}
+
+int agx_ntt_forward_range(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t prime_first, uint32_t prime_count, void* stream) {
+    return range_call(false, plan, d_in, d_out, batch, prime_first, prime_count, stream);
+}
+
+int agx_ntt_inverse_range(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t prime_first, uint32_t prime_count, void* stream) {
+    return range_call(true, plan, d_in, d_out, batch, prime_first, prime_count, stream);
+}
+
 int agx_ntt_pointwise(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c, uint64_t batch, void* stream) {
     if (!plan || !d_a || !d_b || !d_c) return AGX_ERR_NULL_POINTER;
     const frame_layout fl = dense(plan, batch);

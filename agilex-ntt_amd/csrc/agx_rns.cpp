@@ -30,6 +30,18 @@ static int instantiate_basis(agx_ntt_basis** out, const agx_ntt_plan* plan, uint
     put(b->d_dall, img.dall);
     if (rc == AGX_OK) rc = b->d_src_consts.upload(sc);
     if (b->has_aux) put(b->d_aux_row, img.aux_row), put(b->d_aux_corr_exact, img.aux_corr_exact), put(b->d_aux_mdinv, img.aux_mdinv), put(b->d_aux_mmat, img.aux_mmat), put(b->d_aux_corr_mont, img.aux_corr_mont);
+    if (b->has_aux && rq.quot_t) {
+        // the quotient: the target primes' constants and the sources' followed by m's, their last-stage factors the image's
+        b->has_quotient = true, b->quot_t = rq.quot_t, b->aux_follows = aux_prime == src_first + rq.S;
+        std::vector<prime_consts> dc(plan->consts.begin() + dst_first, plan->consts.begin() + dst_first + rq.T), qc(sc);
+        qc.push_back(plan->consts[aux_prime]);
+        auto scale = [](prime_consts& c, const shoup_pair& n, const shoup_pair& w) { c.n_inv = n.w, c.n_inv_p = n.p, c.w1n = w.w, c.w1n_p = w.p; };
+        for (uint32_t j = 0; j < rq.T; ++j) scale(dc[j], img.quot_dn[j], img.quot_dw[j]);
+        for (uint32_t i = 0; i <= rq.S; ++i) scale(qc[i], img.quot_sn[i], img.quot_sw[i]);
+        put(b->d_quot_mat, img.quot_mat);
+        if (rc == AGX_OK) rc = b->d_quot_dst_consts.upload(dc);
+        if (rc == AGX_OK) rc = b->d_quot_src_consts.upload(qc);
+    }
     if (rc) return rc;
     basis_view& v = b->view;
     v.dinv = b->d_dinv, v.mat = b->d_mat, v.dall = b->d_dall, v.down_mat = b->d_down_mat, v.round_src = b->d_round_src, v.round_dst = b->d_round_dst;
@@ -44,31 +56,52 @@ static int instantiate_basis(agx_ntt_basis** out, const agx_ntt_plan* plan, uint
     return AGX_OK;
 }
 
-// agx_ntt_basis_create_plain and (t = 1, aux set) agx_ntt_basis_create_aux: validate, build the image, instantiate.  The rules in their order: NULL; the
-// ranges; the plan; sources that share a factor, a bad modulus; t = 0, a bad argument; t without an inverse modulo a source, a bad modulus; then the auxiliary
-// prime's: outside the plan or inside a range of the basis is a bad argument, a modulus that is a source's or a target's a bad modulus.
+// agx_ntt_basis_create_plain, (t = 1, aux set) agx_ntt_basis_create_aux and (quotient set, quot_t its t: the basis' own t stays 1)
+// agx_ntt_basis_create_quotient: validate, build the image, instantiate.  The rules in their order: NULL; the ranges; the plan; sources that share a factor,
+// a bad modulus; t = 0, a bad argument; t without an inverse modulo a source, a bad modulus; then the auxiliary prime's: outside the plan or inside a range of
+// the basis is a bad argument, a modulus that is a source's or a target's a bad modulus; then the quotient's: more targets than AGX_BASIS_MAX_SRC stands with
+// the ranges; ranges that overlap, a bad argument; two equal moduli among the sources, the targets and m, a bad modulus; quot_t = 0, a bad argument.
 static int create_basis(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t src_first, uint32_t src_count, uint32_t dst_first, uint32_t dst_count, uint64_t t,
-                        bool aux, uint32_t aux_prime) {
+                        bool aux, uint32_t aux_prime, bool quotient = false, uint64_t quot_t = 0) {
     if (!basis) return AGX_ERR_NULL_POINTER;
     *basis = nullptr;
     if (!plan) return AGX_ERR_NULL_POINTER;
     const uint32_t P = plan->num_primes;
     auto in_plan = [&](uint32_t first, uint32_t count) { return count >= 1 && count <= P && first <= P - count; };
     if (!in_plan(src_first, src_count) || !in_plan(dst_first, dst_count) || src_count > AGX_BASIS_MAX_SRC) return AGX_ERR_BAD_ARGUMENT;
+    if (quotient && dst_count > AGX_BASIS_MAX_SRC) return AGX_ERR_BAD_ARGUMENT;
     if (int rc = check_plan(plan)) return rc;
     return guarded([&]() -> int {
         auto inside = [&](uint32_t first, uint32_t count) { return aux_prime >= first && aux_prime - first < count; };
         const bool aux_placed = aux && aux_prime < P && !inside(src_first, src_count) && !inside(dst_first, dst_count);
         std::vector<uint64_t> n_inv(src_count), w1n(src_count);
         for (uint32_t i = 0; i < src_count; ++i) n_inv[i] = plan->consts[src_first + i].n_inv, w1n[i] = plan->consts[src_first + i].w1n;
-        const basis_request rq{&plan->moduli[src_first], src_count, &plan->moduli[dst_first], dst_count, n_inv.data(), w1n.data(), t, aux_placed ? plan->moduli[aux_prime] : 0};
+        basis_request rq{&plan->moduli[src_first], src_count, &plan->moduli[dst_first], dst_count, n_inv.data(), w1n.data(), t, aux_placed ? plan->moduli[aux_prime] : 0};
+        std::vector<uint64_t> dst_n_inv(dst_count), dst_w1n(dst_count);
+        if (quotient && aux_placed) {
+            for (uint32_t j = 0; j < dst_count; ++j) dst_n_inv[j] = plan->consts[dst_first + j].n_inv, dst_w1n[j] = plan->consts[dst_first + j].w1n;
+            rq.quot_t = quot_t, rq.dst_n_inv = dst_n_inv.data(), rq.dst_w1n = dst_w1n.data();
+            rq.aux_n_inv = plan->consts[aux_prime].n_inv, rq.aux_w1n = plan->consts[aux_prime].w1n;
+        }
         basis_image img;
-        const basis_fault fault = prepare_basis_image(img, rq);      // reports the first of source, t, aux
+        const basis_fault fault = prepare_basis_image(img, rq);      // reports the first of source, t, aux, quotient
         if (fault == basis_fault::source) return AGX_ERR_BAD_MODULUS;
         if (t == 0) return AGX_ERR_BAD_ARGUMENT;
         if (fault == basis_fault::t) return AGX_ERR_BAD_MODULUS;
         if (aux && !aux_placed) return AGX_ERR_BAD_ARGUMENT;
         if (fault == basis_fault::aux) return AGX_ERR_BAD_MODULUS;
+        if (quotient) {
+            if (src_first < dst_first ? dst_first - src_first < src_count : src_first - dst_first < dst_count) return AGX_ERR_BAD_ARGUMENT;
+            // m differs from every source and target (the aux rule above) and the sources from each other (the source rule): targets remain
+            for (uint32_t j = 0; j < dst_count; ++j) {
+                for (uint32_t k = j + 1; k < dst_count; ++k)
+                    if (rq.dst[j] == rq.dst[k]) return AGX_ERR_BAD_MODULUS;
+                for (uint32_t i = 0; i < src_count; ++i)
+                    if (rq.dst[j] == rq.src[i]) return AGX_ERR_BAD_MODULUS;
+            }
+            if (fault == basis_fault::quotient) return AGX_ERR_BAD_MODULUS;
+            if (quot_t == 0) return AGX_ERR_BAD_ARGUMENT;
+        }
         return instantiate_basis(basis, plan, src_first, dst_first, aux_prime, rq, img);
     });
 }
@@ -269,6 +302,57 @@ int agx_ntt_basis_aux_info(const agx_ntt_basis* basis, int* has_aux, uint32_t* a
     if (has_aux) *has_aux = basis->has_aux ? 1 : 0;
     if (aux_prime) *aux_prime = basis->aux_prime;
     if (launches_ntt_form) *launches_ntt_form = 1 + forward_launches(basis->plan);      // the coefficient-form launch, then the plan's forward on the targets
+    return AGX_OK;
+}
+
+// The basis of agx_ntt_basis_create_aux(plan, b_first, b_count, q_first, q_count, aux_prime) -- sources B, targets Q, t = 1 in every call it had -- with the
+// constants of agx_ntt_basis_quotient for this t.
+int agx_ntt_basis_create_quotient(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t b_first, uint32_t b_count, uint32_t q_first, uint32_t q_count,
+                                  uint32_t aux_prime, uint64_t t) {
+    return create_basis(basis, plan, b_first, b_count, q_first, q_count, 1, true, aux_prime, true, t);
+}
+
+// the inverse launches of one quotient call: Q, then Bsk -- in one where m is the plan prime right behind B, else B and m apart
+static int quotient_inverses(const agx_ntt_basis* b) { return b->aux_follows ? 2 : 3; }
+
+int agx_ntt_basis_quotient_info(const agx_ntt_basis* basis, int* has_quotient, uint64_t* t, int* launches) {
+    if (!basis) return AGX_ERR_NULL_POINTER;
+    if (has_quotient) *has_quotient = basis->has_quotient ? 1 : 0;
+    if (t) *t = basis->quot_t;
+    if (launches) *launches = quotient_inverses(basis) * inverse_launches(basis->plan) + 1 + forward_launches(basis->plan);
+    return AGX_OK;
+}
+
+// Steps 4 to 7 of a BFV multiplication in the coefficient domain (include/agx_ntt.h has the contract): the scaled inverses of the Q slabs and of the Bsk
+// slabs into the scratch, ONE kernel for the fast floor and the Shenoy-Kumaresan return, the plan's forward on Q in place in d_out.
+int agx_ntt_basis_quotient(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!basis || !d_x || !d_out || !d_scratch) return AGX_ERR_NULL_POINTER;
+    if (!basis->has_quotient) return AGX_ERR_BAD_ARGUMENT;
+    const agx_ntt_plan* plan = basis->plan;
+    if (int rc = check_plan(plan)) return rc;
+    const basis_view& bv = basis->view;
+    const uint32_t K = bv.src_count, L = bv.dst_count, W = L + K + 1;
+    if (!aligned8(d_x) || !aligned8(d_out) || !aligned8(d_scratch) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of x and the scratch ([W][batch][n]) and of out ([L][batch][n]) alike
+    if (!dense_fits(plan->n, W, batch)) return AGX_ERR_BAD_ARGUMENT;
+    // the scratch IS x (every inverse then runs in place, as agx_ntt_inverse may) or touches none of it; out touches neither
+    const uint64_t slab = (uint64_t)fl.prime_stride;
+    if (d_scratch != d_x && ranges_touch(addr(d_scratch), W * slab, addr(d_x), W * slab)) return AGX_ERR_BAD_ARGUMENT;
+    if (ranges_touch(addr(d_out), L * slab, addr(d_x), W * slab) || ranges_touch(addr(d_out), L * slab, addr(d_scratch), W * slab)) return AGX_ERR_BAD_ARGUMENT;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // scratch <- the y_i on Q, then the s_j on B and s_m: the plan's inverse on those views, its last-stage constants the basis'
+    auto scaled_inverse = [&](uint32_t first, uint32_t count, const prime_consts* consts, uint64_t at) {
+        route r = prime_range(plan->routes.inverse, first, first + count);
+        r.consts = consts;
+        return run_inverse(r, d_x + at * slab, nullptr, d_scratch + at * slab, fl, s);
+    };
+    AGX_HIP(scaled_inverse(bv.dst_first, L, basis->d_quot_dst_consts, 0));
+    AGX_HIP(scaled_inverse(bv.src_first, basis->aux_follows ? K + 1 : K, basis->d_quot_src_consts, L));
+    if (!basis->aux_follows) AGX_HIP(scaled_inverse(basis->aux_prime, 1, basis->d_quot_src_consts + K, L + K));
+    AGX_HIP(launch_basis_quotient(plan->routes.forward, bv, basis->aux, basis->d_quot_mat, d_scratch, d_out, batch, s));
+    AGX_HIP(run_forward(prime_range(forward_route(plan, batch), bv.dst_first, bv.dst_first + L), d_out, d_out, fl, s));
     return AGX_OK;
 }
 

@@ -171,6 +171,31 @@ basis_fault prepare_basis_image(basis_image& img, const basis_request& rq) {
             if (m) img.aux_mmat.push_back(shoup_pair::of(mul_mod(di, minv, q), q));
         }
     }
+    if (!m || !rq.quot_t) return basis_fault::none;
+    // the quotient: E = prod dst[j]
+    for (uint32_t j = 0; j < T; ++j) {
+        const uint64_t q = rq.dst[j];
+        uint64_t ejinv = 0;
+        if (!inv_mod_euclid(product_mod(rq.dst, T, j, q), q, &ejinv)) return basis_fault::quotient;
+        const uint64_t scale = mul_mod(ejinv, rq.quot_t % q, q);      // t E_j^-1
+        img.quot_dn.push_back(shoup_pair::of(mul_mod(rq.dst_n_inv[j], scale, q), q));
+        img.quot_dw.push_back(shoup_pair::of(mul_mod(rq.dst_w1n[j], scale, q), q));
+    }
+    for (uint32_t i = 0; i <= S; ++i) {
+        const uint64_t q = i < S ? rq.src[i] : m;
+        uint64_t einv = 0;
+        if (!inv_mod_euclid(product_mod(rq.dst, T, T, q), q, &einv)) return basis_fault::quotient;
+        const uint64_t scale = mul_mod(mul_mod(einv, rq.quot_t % q, q), i < S ? img.dinv[i].w : 1 % q, q);      // t E^-1 D_i^-1; for m: t E^-1
+        img.quot_sn.push_back(shoup_pair::of(mul_mod(i < S ? rq.n_inv[i] : rq.aux_n_inv, scale, q), q));
+        img.quot_sw.push_back(shoup_pair::of(mul_mod(i < S ? rq.w1n[i] : rq.aux_w1n, scale, q), q));
+    }
+    for (uint32_t j = 0; j < T; ++j)
+        for (uint32_t i = 0; i <= S; ++i) {
+            const uint64_t q = i < S ? rq.src[i] : m;
+            uint64_t qjinv = 0;
+            if (!inv_mod_euclid(rq.dst[j] % q, q, &qjinv)) return basis_fault::quotient;
+            img.quot_mat.push_back(shoup_pair::of(mul_mod(qjinv, i < S ? img.dinv[i].w : 1 % q, q), q));
+        }
     return basis_fault::none;
 }
 

@@ -61,6 +61,11 @@ struct basis_request {
     const uint64_t *n_inv, *w1n;      // [S]: the two constants of an inverse transform's last stage, n^-1 mod src[i] and inv_twiddle[1] n^-1 mod src[i], both below src[i]
     uint64_t t = 1;                   // the plaintext modulus of agx_ntt_basis_create_plain: any 64-bit value, reduced per modulus here
     uint64_t m = 0;                   // the auxiliary modulus of agx_ntt_basis_create_aux, odd, > 1 and < 2^62; 0: none
+    // agx_ntt_basis_create_quotient only (it needs an m): quot_t != 0 asks for the quotient's constants.  The quotient runs the inverse on the TARGETS
+    // and on m as well, so it needs their last-stage constants: dst_n_inv, dst_w1n [T] and the two of m, as n_inv and w1n are the sources'.
+    uint64_t quot_t = 0;              // the t of the quotient: any 64-bit value, reduced per modulus here; 0: no quotient
+    const uint64_t *dst_n_inv = nullptr, *dst_w1n = nullptr;
+    uint64_t aux_n_inv = 0, aux_w1n = 0;
 };
 
 // Everything a basis keeps on the device, built once on the host.  With D = prod src[i], D_i = D / src[i], q_i = src[i], q_j = dst[j], every pair
@@ -86,6 +91,13 @@ struct basis_image {
     std::vector<shoup_pair> aux_mmat;        // [T][S] D_i m^-1 mod q_j
     std::vector<shoup_pair> aux_corr_mont;   // [T]    -D m^-1 mod q_j
     shoup_pair k_exact = {0, 0}, k_mont = {0, 0};      // D^-1 mod m, -D^-1 mod m
+    // agx_ntt_basis_quotient (csrc/bfv_quotient_arith.hpp has the formulas): filled when the request has a quot_t, else empty.  The quotient divides by the
+    // product of the TARGETS, E = prod q_j, E_j = E / q_j, and returns through the sources: D, D_i and m are the above.  The scaled last-stage constants
+    // make the inverse of the target slabs write y_j = t a_j E_j^-1 mod q_j and the inverse of the source slabs and of m's write s_i = t a_i E^-1 D_i^-1
+    // mod q_i and s_m = t a_m E^-1 mod m.
+    std::vector<shoup_pair> quot_dn, quot_dw;  // [T]     dst_n_inv[j] t E_j^-1 mod q_j and dst_w1n[j] t E_j^-1 mod q_j
+    std::vector<shoup_pair> quot_sn, quot_sw;  // [S + 1] n_inv[i] t E^-1 D_i^-1 mod q_i and w1n[i] t E^-1 D_i^-1 mod q_i; entry S: aux_n_inv t E^-1 mod m, aux_w1n t E^-1 mod m
+    std::vector<shoup_pair> quot_mat;          // [T][S + 1] q_j^-1 D_i^-1 mod q_i (= E_j E^-1 D_i^-1); column S: q_j^-1 mod m
 };
 
 // Which rule refused a request, the first in this order; nothing is promised about the image then.
@@ -94,6 +106,7 @@ enum class basis_fault {
     source,      // some D_i is not invertible modulo src[i]: two source moduli share a factor (for primes: are equal)
     t,           // t has no inverse modulo some source (for prime sources: t = 0 modulo one of them)
     aux,         // D has no inverse modulo m, or m none modulo some target (for primes: m equals a source or a target)
+    quotient,    // some E_j has no inverse modulo its target, or E none modulo a source or m (for primes: two targets are equal, or a target is a source or m)
 };
 basis_fault prepare_basis_image(basis_image& img, const basis_request& rq);
 

@@ -13,6 +13,7 @@
 #include "inner_reduce.hpp"
 #include "moddown_arith.hpp"      // the two per-word steps of AGX_RESCALE_ROUND in moddown_coeff_round_kernel
 #include "bfv_conv_arith.hpp"     // the per-word steps of agx_ntt_basis_extend_exact / _mont in basis_aux_coeff_kernel
+#include "bfv_quotient_arith.hpp" // those of agx_ntt_basis_quotient in basis_quotient_kernel
 
 #include <algorithm>
 #include <cstdlib>
@@ -475,6 +476,66 @@ __global__ void basis_aux_coeff_kernel(const uint64_t* __restrict__ x, const uin
     }
 }
 
+// agx_ntt_basis_quotient, the coefficient-domain step: the fast floor on Bsk and the Shenoy-Kumaresan return to Q in one pass (bfv_quotient_arith.hpp has
+// the formulas; S = K sources B, T = L targets Q, as the basis names them).  One thread per (frame, coefficient), basis_aux_coeff_kernel's shape: it reads
+// the T words y_i that the scaled inverse of the Q slabs wrote (slab i at y + i per_prime) and adds each, as it arrives, into the S accumulators of the
+// z_j and into f_m's through one row of qmat ([T][S + 1]) -- no y_i is kept -- then reads its S + 1 words s_j, s_m of the scaled inverse of the Bsk slabs
+// (behind the y_i), finishes the z_j in [0, b_j) and f_m in [0, m), forms W mod m as it goes, alpha ONCE, and walks the T targets as the exact conversion
+// does: 8 (2T + S + 1) bytes per coefficient and (2T + 1)(S + 1) Shoup products.  SMAX >= S bounds the z_j kept in registers (the loops over j are
+// unrolled and guarded, never indexed); the loops over the T targets are not unrolled and keep nothing.  The constants are wave-uniform (scalar loads).
+// No LDS, no barrier; out touches y nowhere.
+template <int SMAX>
+__global__ void basis_quotient_kernel(const uint64_t* __restrict__ y, uint64_t* __restrict__ out, const prime_consts* __restrict__ src_consts,
+                                      const prime_consts* __restrict__ dst_consts, const ulonglong2* __restrict__ qmat, const ulonglong2* __restrict__ mat,
+                                      const ulonglong2* __restrict__ row, const ulonglong2* __restrict__ corr, uint64_t m, uint64_t k, uint64_t kp, uint32_t S,
+                                      uint32_t T, uint64_t per_prime) {
+    const uint64_t m2 = m << 1;
+    const uint64_t* __restrict__ sb = y + (uint64_t)T * per_prime;      // the S slabs s_j, then s_m's
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t z[SMAX];
+        uint64_t fm = 0;
+#pragma unroll
+        for (int j = 0; j < SMAX; ++j) z[j] = 0;
+        for (uint32_t i = 0; i < T; ++i) {
+            const uint64_t yi = y[(uint64_t)i * per_prime + e];
+            const ulonglong2* qrow = qmat + (size_t)i * (S + 1);
+#pragma unroll
+            for (int j = 0; j < SMAX; ++j)
+                if ((uint32_t)j < S) {
+                    const ulonglong2 c = qrow[j];
+                    const uint64_t b = src_consts[j].q;
+                    z[j] = quot_accumulate(z[j], yi, c.x, c.y, b, b << 1);
+                }
+            const ulonglong2 c = qrow[S];
+            fm = quot_accumulate(fm, yi, c.x, c.y, m, m2);
+        }
+        uint64_t wm = 0;
+#pragma unroll
+        for (int j = 0; j < SMAX; ++j)
+            if ((uint32_t)j < S) {
+                const ulonglong2 c = row[j];
+                z[j] = quot_residue(sb[(uint64_t)j * per_prime + e], z[j], src_consts[j].q);
+                wm = quot_accumulate(wm, z[j], c.x, c.y, m, m2);
+            }
+        fm = quot_residue(sb[(uint64_t)S * per_prime + e], fm, m);
+        bool negative;
+        const uint64_t mag = bfv_centre(bfv_alpha(csub(wm, m), fm, k, kp, m), m, &negative);
+        for (uint32_t i = 0; i < T; ++i) {
+            const uint64_t q = dst_consts[i].q, q2 = q << 1;
+            const ulonglong2* mrow = mat + (size_t)i * S;
+            uint64_t acc = 0;
+#pragma unroll
+            for (int j = 0; j < SMAX; ++j)
+                if ((uint32_t)j < S) {
+                    const ulonglong2 c = mrow[j];
+                    acc = quot_accumulate(acc, z[j], c.x, c.y, q, q2);
+                }
+            const ulonglong2 c = corr[i];
+            out[(uint64_t)i * per_prime + e] = bfv_correct(acc, mag, negative, c.x, c.y, q);
+        }
+    }
+}
+
 // agx_ntt_basis_mod_down, generic route, in the coefficient domain: out_j[e] <- (out_j[e] - sum_i y_i[e] (D_i mod q_j)) D^-1 mod q_j.  One thread
 // per (frame, coefficient): it reads its S words of y (y_i in [0,q_i), as the scaled inverse of the source slabs wrote them: no basis_scale here),
 // then reads, finishes and writes back one word of each of the T target slabs, which the inverse left in [0,q_j): 8 (S + 2T) bytes per
@@ -862,6 +923,17 @@ hipError_t launch_basis_aux_coeff(const plan_view& pv, const basis_view& bv, con
         else
             hipLaunchKernelGGL((basis_aux_coeff_kernel<decltype(smax)::value, false>), grid, dim3(256), 0, s, x, xaux, out, pv.consts + bv.src_first,
                                pv.consts + bv.dst_first, c.dinv, c.mat, av.row, c.corr, av.m, c.k, c.kp, bv.src_count, bv.dst_count, per_prime);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_basis_quotient(const plan_view& pv, const basis_view& bv, const aux_view& av, const ulonglong2* qmat, const uint64_t* y, uint64_t* out, uint64_t batch,
+                                 hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    const dim3 grid(grid_1d(per_prime, 256));
+    with_smax(bv.src_count, [&](auto smax) {
+        hipLaunchKernelGGL(basis_quotient_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, y, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, qmat,
+                           av.exact.mat, av.row, av.exact.corr, av.m, av.exact.k, av.exact.kp, bv.src_count, bv.dst_count, per_prime);
     });
     return hipGetLastError();
 }

@@ -151,6 +151,13 @@ hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const u
 // in coefficient form: x and out as launch_basis_coeff takes them, out fully reduced; out touches neither input.  One launch.
 hipError_t launch_basis_aux_coeff(const plan_view& pv, const basis_view& bv, const aux_view& av, bool exact, const uint64_t* x, const uint64_t* xaux, uint64_t* out,
                                   uint64_t batch, hipStream_t s);
+// the coefficient-domain step of agx_ntt_basis_quotient on a basis with sources B (S = K), targets Q (T = L) and the auxiliary prime m: y dense
+// [T + S + 1][batch][n] as the scaled inverses left it -- the y_i in [0,q_i) under Q, then the s_j in [0,b_j) under B, then s_m in [0,m) -- and qmat [T][S + 1]
+// {q_i^-1 B_j^-1 mod b_j, quotient}, column S {q_i^-1 mod m, quotient} -> out dense [T][batch][n] in coefficient form, fully reduced
+// (bfv_quotient_arith.hpp).  The return reads the exact conversion's constants of av.  pv: a view of the WHOLE plan (only its constants are read); out
+// touches y nowhere.  One launch.
+hipError_t launch_basis_quotient(const plan_view& pv, const basis_view& bv, const aux_view& av, const ulonglong2* qmat, const uint64_t* y, uint64_t* out, uint64_t batch,
+                                 hipStream_t s);
 // the coefficient-domain step of agx_ntt_basis_mod_down's generic route: out_j[k] <- (out_j[k] - sum_i y_i[k] (D_i mod q_j)) D^-1 mod q_j in place on
 // out, dense [T][batch][n] in coefficient form with values in [0,q_j) (slab j under plan prime dst_first + j); y: dense [S][batch][n], y_i in
 // [0,q_i) as the scaled inverse of the source slabs left them.  pv: a view of the WHOLE plan (only its constants are read).  One launch.  The matrix is

@@ -140,6 +140,14 @@ struct agx_ntt_basis {
     uint32_t aux_prime = 0;
     agx::device_buf<ulonglong2> d_aux_row, d_aux_corr_exact, d_aux_mdinv, d_aux_mmat, d_aux_corr_mont;
     agx::aux_view aux;
+    // agx_ntt_basis_create_quotient only (such a basis has an auxiliary prime): the constants of agx_ntt_basis_quotient.  The prime_consts of the TARGET
+    // primes ([T]) and of the sources followed by m ([S + 1]) with the last-stage factors replaced as d_src_consts has them, by the image's quot_dn / quot_dw
+    // and quot_sn / quot_sw: the plan's inverse on those views writes the y_i, the s_j and s_m of bfv_quotient_arith.hpp.  aux_follows: m is the plan prime
+    // right behind the sources, so one inverse launch serves Bsk.
+    bool has_quotient = false, aux_follows = false;
+    uint64_t quot_t = 0;
+    agx::device_buf<agx::prime_consts> d_quot_dst_consts, d_quot_src_consts;
+    agx::device_buf<ulonglong2> d_quot_mat;      // [T][S + 1]
 };
 
 // agx_ntt_keyswitch_*: the shape and the bases of one hybrid key switch, and nothing of the plan but a pointer (as a basis: the plan outlives the

@@ -161,6 +161,17 @@ AGX_API int agx_ntt_forward_strided(const agx_ntt_plan* plan, const uint64_t* d_
                             int64_t prime_stride, int64_t poly_stride, void* stream);
 AGX_API int agx_ntt_inverse_strided(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch,
                             int64_t prime_stride, int64_t poly_stride, void* stream);
+/* agx_ntt_forward / agx_ntt_inverse on the plan primes [prime_first, prime_first + prime_count), the range convention of the ring calls below: d_in and
+ * d_out dense [prime_count][batch][n], slab i under plan prime prime_first + i.  The words are exactly what a plan over those primes with the same roots
+ * would write, so no second plan is needed to transform the Q slabs of a ciphertext on a plan that also carries special or auxiliary primes; over
+ * (0, P) the calls are agx_ntt_forward / agx_ntt_inverse word for word and launch their kernels.  In place is allowed.  Rules: those of agx_ntt_forward /
+ * agx_ntt_inverse in their order (the frames are the range's), with the range rule right behind the NULL rule: prime_count == 0 or a range past P:
+ * AGX_ERR_BAD_ARGUMENT, nothing written.  Route: the plan's own route for this batch, viewed on the range (the views the RNS calls run internally): no new
+ * kernel, the launch counts of the whole-plan calls, capturable as they are. */
+AGX_API int agx_ntt_forward_range(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t prime_first, uint32_t prime_count,
+                                  void* stream);
+AGX_API int agx_ntt_inverse_range(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t prime_first, uint32_t prime_count,
+                                  void* stream);
 
 /* c = a o b (coefficient-wise product mod q_p), dense [prime][batch][n] layout; c may alias a or b */
 AGX_API int agx_ntt_pointwise(const agx_ntt_plan* plan, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_c,
@@ -373,6 +384,50 @@ AGX_API int agx_ntt_basis_aux_info(const agx_ntt_basis* basis, int* has_aux, uin
 AGX_API int agx_ntt_basis_extend_exact(const agx_ntt_basis* basis, const uint64_t* d_x, const uint64_t* d_xaux, uint64_t* d_out, uint64_t batch, int out_form,
                                        void* stream);
 AGX_API int agx_ntt_basis_extend_mont(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t batch, int out_form, void* stream);
+/* BFV's divide-and-return in one pass: steps 4 to 7 of a BEHZ multiplication ("BFV multiplication (BEHZ)") -- times t, the fast floor of
+ * t X / Q on Bsk, and the Shenoy-Kumaresan return to Q -- on one component of the tensor product.  Q = the plan primes [q_first, q_first + L) with product
+ * D, Q_i = D / q_i; B = [b_first, b_first + K) with product B, B_j = B / b_j; m = the plan prime aux_prime; Bsk = B u {m}; x' = x mod its modulus; centre as
+ * for agx_ntt_basis_extend_exact.  Per coefficient, with a_. the coefficient forms of the slabs of d_x:
+ *   y_i   = (t a_i') Q_i^-1 mod q_i  in [0, q_i),        V = sum_i y_i Q_i                     (i in Q)
+ *   f_j   = (t a_j' - V) D^-1 mod b_j                                                          (j in B and j = m): floor(t X / D) - u on Bsk
+ *   z_j   = f_j B_j^-1 mod b_j       in [0, b_j),        W = sum_j z_j B_j                     (j in B)
+ *   alpha = centre((W - f_m) B^-1 mod m),                out_i = (W - alpha B) mod q_i         (i in Q)
+ *   d_out = NTT_i(out_i)
+ * which is, word for word, agx_ntt_mul_add_galois by a frame of t's, agx_ntt_basis_mod_down on the basis (sources Q, targets Bsk), the inverse on Bsk and
+ * agx_ntt_basis_extend_exact(..., AGX_FORM_NTT): six launches, 2L + 2K + 2 frame transforms and a multiply pass, of which the forward and the inverse on
+ * Bsk undo each other.  Every formula is an exact integer formula, so this call runs the chain in the coefficient domain: 2L + K + 1 frame transforms,
+ * no pass for t, no frame of t's, no second plan.  The return is exact under agx_ntt_basis_extend_exact's bound.
+ *   create_quotient : the basis agx_ntt_basis_create_aux(plan, b_first, b_count, q_first, q_count, aux_prime) makes -- sources B, targets Q, auxiliary prime
+ *                     m: every call it had (extend, extend_exact, extend_mont, mod_down, mod_down_mode, info, aux_info) behaves on it word for word as on
+ *                     that basis -- with the constants of the quotient.  Rules: agx_ntt_basis_create_aux's in its order, with q_count > 16 beside
+ *                     b_count > 16; then ranges that overlap: AGX_ERR_BAD_ARGUMENT; two equal moduli among Q, B and m: AGX_ERR_BAD_MODULUS; t == 0:
+ *                     AGX_ERR_BAD_ARGUMENT.  Any other 64-bit t is taken and reduced per modulus on the host (t is only multiplied: it needs no
+ *                     inverse anywhere).  On any failure the out-pointer is cleared.
+ *   quotient_info   : has_quotient (0 on every other basis, where t reads 0), t, and the kernel launches of one call under the plan's CURRENT variant:
+ *                     2 x the plan's inverse + 1 + the plan's forward where m is the plan prime right behind B (aux_prime = b_first + b_count: Bsk is one
+ *                     range, the layout of the listing), and one inverse more where it is not.  Any out-pointer may be NULL.
+ *   quotient        : d_x dense [L + K + 1][batch][n] in NTT form as agx_ntt_forward / _forward_lazy of the plan write it (reduced or lazy), the slabs of Q,
+ *                     then of B, then of m: one component of the tensor product on Q u Bsk.  d_out dense [L][batch][n], NTT form under Q, fully reduced.
+ *                     d_scratch: (L + K + 1) batch n words; it may be exactly d_x, which is then given up (as agx_ntt_rescale and agx_ntt_basis_mod_down
+ *                     allow), otherwise it touches d_x nowhere and d_x is left unchanged; d_out touches neither; ranges that meet end to end do not touch.
+ *                     Status order: NULL: AGX_ERR_NULL_POINTER; a basis without the quotient's constants: AGX_ERR_BAD_ARGUMENT; the plan's device not
+ *                     current: AGX_ERR_BAD_ARGUMENT; 8-byte alignment, the batch grid limit, an extent past 2^60 words, the overlap rules:
+ *                     AGX_ERR_BAD_ARGUMENT, nothing written; a plan without inverse tables: AGX_ERR_NO_INVERSE; batch == 0: AGX_OK, nothing launched.
+ *                     Asynchronous; allocates and synchronises nothing (capturable into a hipGraph); agx_ntt_plan_set_variant between calls stays legal.
+ * Route, one for every plan: the plan's inverse on the view of Q into the scratch with n^-1 t Q_i^-1 in the place of n^-1, so it writes the y_i (the
+ * mechanism of agx_ntt_basis_mod_down); the plan's inverse on the view of Bsk with n^-1 t D^-1 B_j^-1 (m: n^-1 t D^-1); ONE streaming kernel, one thread
+ * per coefficient, no LDS: z_j = s_j - sum_i y_i (q_i^-1 B_j^-1 mod b_j) since D^-1 Q_i = q_i^-1, f_m by the row q_i^-1 mod m, W mod m, alpha by one Shoup
+ * product and the centring, out_i = sum_j z_j (B_j mod q_i) -+ |alpha| (B mod q_i) -- 8 (2L + K + 1) bytes per coefficient, K + 2 words live; then the plan's
+ * forward on the view of Q, in place in d_out.
+ * Measured on an MI355X (profiles/r16_bfv_quotient.md, tools/run_op.py --op quotient; 60-bit primes, L = K = 2 and 4, n = 4096 with 4,096 frames per prime and
+ * n = 16384 with 1,024, the scratch the operand): 0.62 ... 0.66 of the time of the six-call composition on the same buffer, outside the spreads in every row
+ * (L = K = 2 at n = 4096: 753 us against 1216 us; L = K = 4: 1556 against 2371), and 4.1 ... 5.0 of the time of a device copy of its model bytes,
+ * 8 (2L + K + 1) per coefficient: the call is three transform launches and the kernel, and moves three times those bytes.
+ * Groups: no group form, as for agx_ntt_basis_extend. */
+AGX_API int agx_ntt_basis_create_quotient(agx_ntt_basis** basis, const agx_ntt_plan* plan, uint32_t b_first, uint32_t b_count, uint32_t q_first, uint32_t q_count,
+                                          uint32_t aux_prime, uint64_t t);
+AGX_API int agx_ntt_basis_quotient_info(const agx_ntt_basis* basis, int* has_quotient, uint64_t* t, int* launches);
+AGX_API int agx_ntt_basis_quotient(const agx_ntt_basis* basis, const uint64_t* d_x, uint64_t* d_out, uint64_t* d_scratch, uint64_t batch, void* stream);
 
 /* The inner product of NTT-form frames: c_o = sum_t a_t o bhat_{t,o} mod q for o < outputs, one launch -- the centre of a hybrid key switch (the sum over
  * the decomposition digits of digit times key), and any other multiply-accumulate against operands kept in NTT form.  P = the plan's primes:

@@ -5,6 +5,7 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op extend --src S [--dst T --only {both,fused,pair} --reps 5 ...]   (agx_ntt_basis_extend to NTT form beside the unfused pair)
        python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent,modes} --mode {floor,round} --plain T --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
        python3 tools/run_op.py --op bfvconv --src S --dst T [--only {all,exact,mont,parent,copy} --reps 7 ...]   (agx_ntt_basis_extend_exact / _mont, coefficient form, beside agx_ntt_basis_extend into T + 1 targets and a copy of the model's bytes)
+       python3 tools/run_op.py --op quotient --qcount L --src K [--only {all,quotient,composition,copy} --reps 7 ...]   (agx_ntt_basis_quotient beside the six-call composition it replaces and a copy of its model bytes)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
        python3 tools/run_op.py --op ring --kind {add,sub,negate,add_galois,tensor} [--primes 6 --first 0 --count 4 --galois G --only {all,ring,copy,parent} --reps 7 ...]   (a ring call beside a copy of its model bytes and what it replaces)
        python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
@@ -27,7 +28,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -49,7 +50,7 @@ ap.add_argument("--odd", action="store_true", help="auto: both bases one word pa
 ap.add_argument("--reps", type=int, default=5, help="auto: timed repetitions of --launches calls each, alternating with the copy; medians are reported")
 ap.add_argument("--src", type=int, default=2, help="extend: source primes [0, S)")
 ap.add_argument("--dst", type=int, default=0, help="extend: target primes [0, T); 0 = every prime of the plan")
-ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "modes", "inner", "copy", "ring", "exact", "mont"], default=None,
+ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "parent", "modes", "inner", "copy", "ring", "exact", "mont", "quotient", "composition"], default=None,
                 help="extend: time the AGX_FORM_NTT call (fused), the unfused pair, or both alternating (default); moddown: the two-launch route (fused), the "
                      "four-launch route on the same plan (generic: needs lib/libagxntt_diag.so through AGX_NTT_LIB), inverse + extend as before mod_down existed "
                      "(parent), or all alternating (default).  A counter run wants one")
@@ -75,7 +76,9 @@ if args.op == "bfvconv":
 if args.op in ("keyswitch", "hoist", "dhoist"):
     args.pfirst = args.qcount if args.pfirst is None else args.pfirst
     args.primes = args.pfirst + args.pcount
-args.only = args.only or ("all" if args.op in ("moddown", "bfvconv") else "both")
+if args.op == "quotient":
+    args.primes = args.qcount + args.src + 1      # Q = [0, L), B = [L, L + K), the auxiliary prime L + K
+args.only = args.only or ("all" if args.op in ("moddown", "bfvconv", "quotient") else "both")
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
 if args.variant is not None:
     plan.set_variant(agx.VARIANT_REGBLOCK_BASE + args.variant)
@@ -330,6 +333,56 @@ def _fmt(t):
     import statistics
 
     return f"{statistics.median(t):.1f} ({min(t):.1f} ... {max(t):.1f})"
+
+
+def run_quotient():
+    """agx_ntt_basis_quotient with Q = [0, L), B = [L, L + K) and m = L + K (--qcount L, --src K), the scratch the operand as in the INTEGRATION.md listing,
+    alternating in one process with the six-call composition it replaces -- agx_ntt_mul_add_galois by a frame of t's, agx_ntt_basis_mod_down (sources Q,
+    targets Bsk, the Q slabs given up), agx_ntt_inverse on Bsk through a second plan, agx_ntt_basis_extend_exact to NTT form -- and with a device copy of
+    the call's model bytes, 8 (2L + K + 1) per coefficient (L + K + 1 slabs read, L written).  Both forms overwrite their operand; any words are NTT-form
+    words, so the groups run on what the last call left.  Prints us per call: median (min ... max) of --reps groups of --launches calls."""
+    import statistics
+
+    L, K, t = args.qcount, args.src, 65537
+    W, words = L + K + 1, args.batch * args.n
+    basis = plan.basis_quotient(L, K, 0, L, L + K, t)
+    fast_floor, to_q = plan.basis(0, L, L, K + 1), plan.basis_aux(L, K, 0, L, L + K)
+    plan_bsk = agx.Plan(args.n, plan.moduli[L:], psi=[plan.psi(k) for k in range(L, W)])
+    x = torch.empty(W * words, dtype=torch.int64, device="cuda")
+    out = torch.empty(L * words, dtype=torch.int64, device="cuda")
+    floor_hat, floor_coeff = (torch.empty((K + 1) * words, dtype=torch.int64, device="cuda") for _ in range(2))
+    t_hat = torch.full((W * args.n,), t, dtype=torch.int64, device="cuda")
+    plan.fill_synthetic(x.data_ptr(), args.batch, 0, 42, stream)
+    half = (2 * L + K + 1) * words // 2      # a copy reads and writes this many words: together the model's bytes
+    c_src, c_dst = (torch.empty(half, dtype=torch.int64, device="cuda") for _ in range(2))
+    p = x.data_ptr()
+
+    def quotient():
+        basis.quotient(p, out.data_ptr(), p, args.batch, stream)
+
+    def composition():
+        plan.mul_add_galois(t_hat.data_ptr(), p, p, args.batch, 1, 1, False, 0, W, stream)
+        fast_floor.mod_down(p + 8 * L * words, p, floor_hat.data_ptr(), p, args.batch, stream)
+        plan_bsk.inverse(floor_hat.data_ptr(), floor_coeff.data_ptr(), args.batch, stream)
+        to_q.extend_exact(floor_coeff.data_ptr(), floor_coeff.data_ptr() + 8 * K * words, out.data_ptr(), args.batch, agx.FORM_NTT, stream)
+
+    def copy():
+        c_dst.copy_(c_src)
+
+    todo = [f for name, f in (("quotient", quotient), ("composition", composition), ("copy", copy)) if args.only in ("all", name)]
+    times = _alternate(todo)
+    launches = {"quotient": basis.quotient_info()[2], "composition": 1 + fast_floor.mod_down_launches() + 1 + to_q.aux_info()[2]}
+    print(f"quotient n={args.n} L={L} K={K} batch={args.batch} bits={args.bits} launches {launches}:", "; ".join(f"{name} {_fmt(v)} us" for name, v in times.items()))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    if "quotient" in med:
+        print("  " + "  ".join(f"quotient/{name} {med['quotient'] / med[name]:.3f}" for name in ("composition", "copy") if name in med))
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "kernel_launches": launches, "model_bytes": 16.0 * half}, open(args.report, "w"))
+    for h in (basis, fast_floor, to_q, plan_bsk):
+        h.close()
+    plan.close()
 
 
 def run_bfvconv():
@@ -849,6 +902,9 @@ if args.op == "extend":
     sys.exit(0)
 if args.op == "bfvconv":
     run_bfvconv()
+    sys.exit(0)
+if args.op == "quotient":
+    run_quotient()
     sys.exit(0)
 slabs = [torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(args.slabs)]
 for i, s in enumerate(slabs):
