@@ -201,16 +201,33 @@ def _out_array(out, count):
     return np.zeros(count, dtype=np.uint64) if out is None else out
 
 
-def kernel_source_sha16():
-    """sha256[:16] over the DEVICE sources the kernels are built from (csrc/*.hip and the headers they include, sorted by
-    name; not the host-side agx_ntt.cpp / host_math.*): ties a committed PMC figure (profiles/hbm_traffic.json) to the
-    kernels it was measured on"""
+def kernel_source_files():
+    """the DEVICE sources the kernels are built from, sorted: every csrc/*.hip and whatever of csrc/ they include, directly or
+    through another such file (their `#include "..."` lines, wherever in a file they stand); not the host-side *.cpp"""
     import glob
+    import re
+
+    csrc = os.path.join(_HERE, "csrc")
+    todo, seen = glob.glob(os.path.join(csrc, "*.hip")), set()
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.add(f)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(f).read(), flags=re.M):
+            inc = os.path.normpath(os.path.join(csrc, inc))
+            if os.path.dirname(inc) == csrc and os.path.exists(inc):
+                todo.append(inc)
+    return sorted(seen)
+
+
+def kernel_source_sha16():
+    """sha256[:16] over kernel_source_files(), names and contents: ties a committed PMC figure (profiles/hbm_traffic.json) to
+    the kernels it was measured on"""
     import hashlib
 
     h = hashlib.sha256()
-    files = glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + [os.path.join(_HERE, "csrc", f) for f in ("rb_frame.hpp", "rb_kernels.hpp", "rb32_kernels.hpp", "wp_kernels.hpp", "rb_stream_opts.hpp", "rb_registry.hpp", "modarith.hpp", "inner_reduce.hpp", "ring_arith.hpp", "ring_kernels.hpp", "weighted_arith.hpp", "weighted_kernels.hpp", "ntt_kernels.hpp", "q60c_class.hpp")]
-    for f in sorted(files):
+    for f in kernel_source_files():
         h.update(os.path.relpath(f, _HERE).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()[:16]

@@ -414,13 +414,8 @@ static int ring_call(ring_kind kind, const agx_ntt_plan* plan, const uint64_t* d
     if (batch == 0) return AGX_OK;
     const route& r = plan->routes.forward;      // the whole plan's view: only its constants are read, at [prime_first, prime_first + prime_count)
     hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (kind) {
-        case kRingAdd: AGX_HIP(launch_ring_add(r, prime_first, prime_count, d_a, d_b, d_c, batch, s)); break;
-        case kRingSub: AGX_HIP(launch_ring_sub(r, prime_first, prime_count, d_a, d_b, d_c, batch, s)); break;
-        case kRingNegate: AGX_HIP(launch_ring_negate(r, prime_first, prime_count, d_a, d_c, batch, s)); break;
-        case kRingAddGalois: AGX_HIP(launch_ring_add_galois(r, prime_first, prime_count, d_a, d_b, d_c, batch, galois_elt, s)); break;
-        case kRingTensor: AGX_HIP(launch_ring_tensor(r, prime_first, prime_count, d_a, d_b, d_c, batch, s)); break;
-    }
+    if (kind == kRingTensor) AGX_HIP(launch_ring_tensor(r, prime_first, prime_count, d_a, d_b, d_c, batch, s));
+    else AGX_HIP(launch_ring_linear(r, prime_first, prime_count, kind == kRingSub ? RING_SUB : kind == kRingNegate ? RING_NEG : RING_ADD, d_a, d_b, d_c, batch, galois_elt, s));
     return AGX_OK;
 }
 

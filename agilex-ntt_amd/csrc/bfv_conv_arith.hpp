@@ -1,6 +1,6 @@
 // bfv_conv_arith.hpp -- the per-word steps that agx_ntt_basis_extend_exact (Shenoy-Kumaresan) and agx_ntt_basis_extend_mont (BEHZ: FastBConv_m~ followed
 // by the small Montgomery reduction) add to the fast base conversion, all with wave-uniform constants.  Compiles for the device (basis_aux_coeff_kernel of
-// ntt_kernels.hip) and for the host (tests/bfv_conv_selftest.cpp runs this same text against unsigned __int128), as moddown_arith.hpp does: no HIP header
+// basis_coeff_kernels.hpp) and for the host (tests/bfv_conv_selftest.cpp runs this same text against unsigned __int128), as moddown_arith.hpp does: no HIP header
 // is needed on the host.
 //
 // With D = prod of the sources q_i, D_i = D / q_i, the auxiliary prime m, V = sum_i y_i D_i and centre(a) = a for a <= (m - 1) / 2, a - m above:

@@ -1,6 +1,6 @@
 // bfv_quotient_arith.hpp -- the per-word steps of agx_ntt_basis_quotient (BFV's divide-and-return: the fast floor of t X / Q on Bsk and the Shenoy-Kumaresan
 // return to Q, in one coefficient-domain kernel), beside those of bfv_conv_arith.hpp, which it also uses.  Compiles for the device
-// (basis_quotient_kernel of ntt_kernels.hip) and for the host (tests/bfv_quotient_selftest.cpp runs this same text against unsigned __int128).
+// (basis_quotient_kernel of basis_coeff_kernels.hpp) and for the host (tests/bfv_quotient_selftest.cpp runs this same text against unsigned __int128).
 //
 // With Q = prod q_i over the L primes of Q, Q_i = Q / q_i, B = prod b_j over the K primes of B, B_j = B / b_j and m the auxiliary prime, the scaled
 // inverses hand the kernel, per coefficient (a_. the coefficient forms of the input slabs, reduced),

@@ -1,5 +1,5 @@
 // inner_reduce.hpp -- the accumulate-and-reduce step of agx_ntt_inner_product: sum_t a_t b_t kept in 128 bits, reduced modulo q once.
-// Compiles for the device (inner_product_kernel, ntt_kernels.hip) and for the host (tests/inner_selftest.cpp runs this same text against
+// Compiles for the device (inner_product_kernel, inner_kernels.hpp) and for the host (tests/inner_selftest.cpp runs this same text against
 // unsigned __int128 %): no HIP header is needed on the host, the high product is portable there.
 //
 // Range argument.

@@ -1,5 +1,5 @@
 // moddown_arith.hpp -- the two per-word steps that AGX_RESCALE_ROUND adds to agx_ntt_basis_mod_down_mode, both with wave-uniform constants.
-// Compiles for the device (moddown_round_rb2 of rb_kernels.hpp, moddown_coeff_kernel of ntt_kernels.hip) and for the host
+// Compiles for the device (moddown_round_rb2 of rb_kernels.hpp, moddown_coeff_round_kernel of basis_coeff_kernels.hpp) and for the host
 // (tests/moddown_modes_selftest.cpp runs this same text against unsigned __int128), as ring_arith.hpp and weighted_arith.hpp do: no HIP header is
 // needed on the host.
 //

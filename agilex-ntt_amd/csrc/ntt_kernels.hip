@@ -8,12 +8,16 @@
 //
 // No MFMA: this is 64-bit integer modular arithmetic (v_mad_u64_u32 / v_mul_hi_u32), bounded
 // by VALU integer multiply issue and HBM bandwidth.
+//
+// The streaming kernels of the RNS calls (a grid-stride over one slot's batch x n words, no LDS, no barrier) are compiled here from headers of their own;
+// this file holds their launchers with every other, and the registry look-up.
 #include "rb_registry.hpp"
 #include "modarith.hpp"
-#include "inner_reduce.hpp"
-#include "moddown_arith.hpp"      // the two per-word steps of AGX_RESCALE_ROUND in moddown_coeff_round_kernel
-#include "bfv_conv_arith.hpp"     // the per-word steps of agx_ntt_basis_extend_exact / _mont in basis_aux_coeff_kernel
-#include "bfv_quotient_arith.hpp" // those of agx_ntt_basis_quotient in basis_quotient_kernel
+#include "inner_kernels.hpp"           // agx_ntt_inner_product / _inner_product_galois, and the Galois index text of every gathered kernel
+#include "ring_kernels.hpp"            // agx_ntt_add / _sub / _negate / _add_galois / _tensor
+#include "weighted_kernels.hpp"        // agx_ntt_keyswitch_accumulate_decomposed / agx_ntt_mul_add_galois
+#include "automorphism_kernels.hpp"    // agx_ntt_automorphism
+#include "basis_coeff_kernels.hpp"     // the coefficient-domain steps of agx_ntt_basis_extend / _extend_exact / _extend_mont / _quotient / _mod_down
 
 #include <algorithm>
 #include <cstdlib>
@@ -206,133 +210,6 @@ __global__ void pointwise_bhat_kernel(uint64_t* __restrict__ c, const uint64_t* 
     }
 }
 
-// agx_ntt_inner_product: c_o = sum_t a_t o bhat_{t,o} mod q on NTT-form frames.  A streaming kernel: no LDS, no barrier, no table; blockIdx.y is
-// the slot of a prime in the call's list, grid-stride over the slot's batch x n words.  W is one word or a 16-byte pair (all three bases 16-byte
-// aligned; n is even, so every stride below is a whole number of pairs).  Inputs in [0, 4q) are reduced first, the products are summed in 128
-// bits and reduced once (inner_reduce.hpp has the range argument).  terms and OUT are wave-uniform.  The terms go in groups of up to four: the
-// loads of a group -- 4 words of a and 4 OUT of the key, per lane of W -- are all issued before the arithmetic on them, and the unrolled next
-// group's loads do not depend on it; a group of sixteen would hold 48 W in registers.  A broadcast key (one frame per prime) is re-read by every
-// frame: the repeats hit L2, nothing is kept across frames.  A twin that held the key words in registers across eight frames was built and measured
-// (profiles/r10_keyswitch.md): 1 ... 3 % slower at n = 4096, 3 ... 8 % faster at n = 16384 with a spill in its two-output pair form; deleted.
-struct inner_args {
-    uint64_t per_prime;                      // W per slot of a and c: batch n / lanes
-    uint64_t a_term, c_out;                  // strides in W: A per_prime
-    uint64_t b_prime, b_out, b_term;         // key strides in W: bhat_batch n / lanes, A b_prime, outputs b_out
-    uint32_t frame_mask, broadcast;          // n / lanes - 1; 1: the key index is the position within the frame
-    uint32_t terms, split, skip;             // slot y serves plan prime y (y < split) or y + skip: Q followed by special primes that lie apart
-};
-
-__device__ __forceinline__ void inner_lanes(acc128* s, uint64_t a, uint64_t b, uint64_t q, uint64_t q2) { acc_mul_add(s[0], reduce_4q(a, q, q2), reduce_4q(b, q, q2)); }
-__device__ __forceinline__ void inner_lanes(acc128* s, ulonglong2 a, ulonglong2 b, uint64_t q, uint64_t q2) {
-    acc_mul_add(s[0], reduce_4q(a.x, q, q2), reduce_4q(b.x, q, q2));
-    acc_mul_add(s[1], reduce_4q(a.y, q, q2), reduce_4q(b.y, q, q2));
-}
-__device__ __forceinline__ void inner_store(uint64_t* p, const acc128* s, const prime_consts& k) { *p = acc_reduce(s[0], k.q, k.mu_hi, k.mu_lo); }
-__device__ __forceinline__ void inner_store(ulonglong2* p, const acc128* s, const prime_consts& k) {
-    *p = make_ulonglong2(acc_reduce(s[0], k.q, k.mu_hi, k.mu_lo), acc_reduce(s[1], k.q, k.mu_hi, k.mu_lo));
-}
-
-template <int OUT, class W>
-__global__ void inner_product_kernel(const W* __restrict__ a, const W* __restrict__ bhat, W* __restrict__ c, const prime_consts* __restrict__ consts, inner_args g) {
-    constexpr int kLanes = sizeof(W) / 8, kGroup = 4;
-    const uint32_t slot = blockIdx.y;
-    const prime_consts k = consts[slot < g.split ? slot : slot + g.skip];
-    const uint64_t q2 = k.q << 1;
-    const W* ap = a + (uint64_t)slot * g.per_prime;
-    const W* bp = bhat + (uint64_t)slot * g.b_prime;
-    W* cp = c + (uint64_t)slot * g.per_prime;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t bi = g.broadcast ? (i & g.frame_mask) : i;
-        acc128 s[OUT][kLanes];
-        for (uint32_t t0 = 0; t0 < g.terms; t0 += kGroup) {
-            W av[kGroup], bv[kGroup][OUT];
-#pragma unroll
-            for (int u = 0; u < kGroup; ++u)
-                if (t0 + u < g.terms) {
-                    av[u] = ap[(t0 + u) * g.a_term + i];
-#pragma unroll
-                    for (int o = 0; o < OUT; ++o) bv[u][o] = bp[(t0 + u) * g.b_term + o * g.b_out + bi];
-                }
-#pragma unroll
-            for (int u = 0; u < kGroup; ++u)
-                if (t0 + u < g.terms) {
-#pragma unroll
-                    for (int o = 0; o < OUT; ++o) inner_lanes(s[o], av[u], bv[u][o], k.q, q2);
-                }
-        }
-#pragma unroll
-        for (int o = 0; o < OUT; ++o) inner_store(cp + o * g.c_out + i, s[o], k);
-    }
-}
-
-// agx_ntt_inner_product_galois: the same sum with a read through pi(i) = brev((g brev(i) + (g-1)/2) mod n), the permutation of
-// automorphism_ntt_kernel below: c_o[i] = sum_t a_t[pi(i)] o bhat_{t,o}[i].  The key and c stay at natural positions.  The same grid-stride shape,
-// groups of four terms and 128-bit sums as inner_product_kernel; pi is formed once per work item and serves every term, since the terms of a
-// differ by a stride only.  An aligned block of 2^m output positions reads one aligned block of 2^m input positions, so a wave that produces 64
-// consecutive W reads one aligned 512-byte (pair form: 1 KiB) segment of each term in permuted lane order.  In the pair form the output pair
-// (2i, 2i+1) reads the input pair (2j, 2j+1) with the halves swapped iff the low bit of pi(2i) is set -- the argument written at
-// automorphism_ntt_x2_kernel.  No LDS, no barrier, no table.  The host sends g = 1 to inner_product_kernel.
-struct inner_galois_args {
-    inner_args in;
-    uint32_t log_n, g;                       // g odd, below 2n
-};
-
-__device__ __forceinline__ uint64_t inner_gather(uint64_t v, bool) { return v; }
-__device__ __forceinline__ ulonglong2 inner_gather(ulonglong2 v, bool swap) { return swap ? make_ulonglong2(v.y, v.x) : v; }
-// the index text: work item i (in W of kLanes words, w its position within the frame) reads the W at the returned index, `swap`: with its halves exchanged
-template <int kLanes>
-__device__ __forceinline__ uint64_t galois_read_index(uint64_t i, uint32_t frame_mask, uint32_t log_n, uint32_t g, bool& swap) {
-    const uint32_t mask = (1u << log_n) - 1u, shift = 32u - log_n, half = (g - 1u) >> 1;
-    const uint32_t w = (uint32_t)i & frame_mask;      // the position within the frame, in W; its first word is w kLanes (even in pair form)
-    const uint32_t j = __brev((g * (__brev(w * kLanes) >> shift) + half) & mask) >> shift;      // g < 2^16, brev < 2^15
-    swap = kLanes == 2 && (j & 1u);
-    return (i - w) + j / kLanes;
-}
-
-template <int OUT, class W>
-__global__ void inner_product_galois_kernel(const W* __restrict__ a, const W* __restrict__ bhat, W* __restrict__ c, const prime_consts* __restrict__ consts,
-                                            inner_galois_args ga) {
-    constexpr int kLanes = sizeof(W) / 8, kGroup = 4;
-    const inner_args& g = ga.in;
-    const uint32_t slot = blockIdx.y;
-    const prime_consts k = consts[slot < g.split ? slot : slot + g.skip];
-    const uint64_t q2 = k.q << 1;
-    const W* ap = a + (uint64_t)slot * g.per_prime;
-    const W* bp = bhat + (uint64_t)slot * g.b_prime;
-    W* cp = c + (uint64_t)slot * g.per_prime;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
-        bool swap;
-        const uint64_t ai = galois_read_index<kLanes>(i, g.frame_mask, ga.log_n, ga.g, swap);
-        const uint64_t bi = g.broadcast ? (i & g.frame_mask) : i;
-        acc128 s[OUT][kLanes];
-        for (uint32_t t0 = 0; t0 < g.terms; t0 += kGroup) {
-            W av[kGroup], bv[kGroup][OUT];
-#pragma unroll
-            for (int u = 0; u < kGroup; ++u)
-                if (t0 + u < g.terms) {
-                    av[u] = ap[(t0 + u) * g.a_term + ai];
-#pragma unroll
-                    for (int o = 0; o < OUT; ++o) bv[u][o] = bp[(t0 + u) * g.b_term + o * g.b_out + bi];
-                }
-#pragma unroll
-            for (int u = 0; u < kGroup; ++u)
-                if (t0 + u < g.terms) {
-#pragma unroll
-                    for (int o = 0; o < OUT; ++o) inner_lanes(s[o], inner_gather(av[u], swap), bv[u][o], k.q, q2);
-                }
-        }
-#pragma unroll
-        for (int o = 0; o < OUT; ++o) inner_store(cp + o * g.c_out + i, s[o], k);
-    }
-}
-
-}  // namespace agx
-
-#include "ring_kernels.hpp"      // agx_ntt_add / _sub / _negate / _add_galois / _tensor: behind inner_gather and galois_read_index, which it reuses
-#include "weighted_kernels.hpp"  // agx_ntt_keyswitch_accumulate_decomposed / agx_ntt_mul_add_galois: behind inner_args, inner_lanes and the ring arithmetic
-
-namespace agx {
-
 // agx_ntt_rescale, generic route, in the coefficient domain: out_i[k] <- (out_i[k] - u_i[k]) q_L^-1 mod q_i with u_i the lift of t[k] to q_i
 // (rescale_lift).  out: dense [prime][batch][n] over the view's primes 0 .. P-2, values in [0,q_i) as the inverse leaves them; t: [batch][n]
 // in [0,q_L), shared by the primes.
@@ -346,220 +223,6 @@ __global__ void rescale_coeff_kernel(uint64_t* __restrict__ out, const uint64_t*
     uint64_t* op = out + (uint64_t)prime * per_prime;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_prime; i += (uint64_t)gridDim.x * blockDim.x)
         op[i] = rescale_finish<false>(op[i], rescale_lift(t[i], h, hq, rc.q_last, bk), rc.qlinv, rc.qlinv_p, k.q);
-}
-
-// ---------------------------------------------------------------------------------------
-// agx_ntt_automorphism: a(X) -> a(X^g) mod (X^n + 1), g odd, dense [prime][batch][n], out of place
-// ---------------------------------------------------------------------------------------
-// NTT form (bit-reversed order): out[p] = in[pi(p)], pi(p) = brev((g brev(p) + (g-1)/2) mod n), words moved unchanged (no modulus).
-// The high bits of k only move the high bits of g k + c, so an aligned block of 2^m output positions reads one aligned block of 2^m
-// input positions: a wave that writes consecutive words reads one contiguous segment in permuted lane order.  No LDS, no barrier.
-// One thread per word over all primes * batch * n words, 64-bit offsets.
-__global__ void automorphism_ntt_kernel(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t log_n, uint64_t total,
-                                        uint32_t g) {
-    const uint32_t mask = (1u << log_n) - 1u, shift = 32u - log_n, c = (g - 1u) >> 1;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t p = (uint32_t)i & mask;
-        const uint32_t k = (g * (__brev(p) >> shift) + c) & mask;      // g < 2^16, brev(p) < 2^15
-        out[i] = in[(i - p) + (__brev(k) >> shift)];
-    }
-}
-
-// The same with 16-byte accesses (both bases 16-byte aligned): the output pair (2i, 2i+1) reads the input pair (2j, 2j+1) -- the odd
-// member's k is the even member's plus n/2, which after the odd factor g still flips the top bit only -- swapped iff that top bit,
-// the low bit of pi(2i), is set.  One thread per pair.
-__global__ void automorphism_ntt_x2_kernel(const ulonglong2* __restrict__ in, ulonglong2* __restrict__ out, uint32_t log_n, uint64_t pairs,
-                                           uint32_t g) {
-    const uint32_t mask = (1u << log_n) - 1u, shift = 32u - log_n, c = (g - 1u) >> 1;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t p = ((uint32_t)i << 1) & mask;
-        const uint32_t j = __brev((g * (__brev(p) >> shift) + c) & mask) >> shift;
-        const ulonglong2 v = in[(i - (p >> 1)) + (j >> 1)];
-        out[i] = (j & 1u) ? make_ulonglong2(v.y, v.x) : v;
-    }
-}
-
-// Coefficient form (natural order): out[i] = +-in[j mod n], j = h i mod 2n with h = g^-1 mod 2n, minus iff j >= n; inputs in [0,4q),
-// outputs fully reduced (so -0 = 0)
-__device__ __forceinline__ uint64_t automorphism_coeff_word(uint64_t v, bool negate, uint64_t q, uint64_t q2) {
-    v = reduce_4q(v, q, q2);
-    return negate ? (v ? q - v : 0) : v;
-}
-
-// Gathered straight from global memory, one thread per output word: a frame comes from HBM once and the stride-h repeats hit L2.  Staging
-// the frame in LDS (coalesced load, barrier, permuted LDS read) was measured at n = 64 ... 16384 and is nowhere faster: 0.4 ... 8 % slower at
-// n = 512 ... 4096, 9 % at n = 64, 32 ... 38 % at n = 16384, where one 128 KiB workgroup per CU cannot overlap its loads with its stores
-// (profiles/r07_automorphism.md)
-__global__ void automorphism_coeff_gather_kernel(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, const prime_consts* __restrict__ consts,
-                                                 uint32_t log_n, uint64_t per_prime, uint32_t h) {
-    const uint32_t prime = blockIdx.y;
-    const uint64_t q = consts[prime].q, q2 = q << 1;
-    const uint64_t off = (uint64_t)prime * per_prime;
-    const uint32_t mask = (1u << log_n) - 1u, mask2 = (2u << log_n) - 1u;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t i = (uint32_t)e & mask, j = (h * i) & mask2;
-        out[off + e] = automorphism_coeff_word(in[off + (e - i) + (j & mask)], j > mask, q, q2);
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// agx_ntt_basis_extend, coefficient form: fast RNS base conversion from S source primes to T target primes, dense layouts, out of place
-// ---------------------------------------------------------------------------------------
-// One thread per (frame, coefficient): it reads its S source words (slab i at x + i per_prime), forms every y_i = x_i D_i^-1 mod q_i once,
-// then walks the T targets and writes one word each: 8 (S + T) bytes per coefficient, no source word read twice.  The constants are
-// wave-uniform (scalar loads).  SMAX >= S bounds the y_i kept in registers (the loops over i are unrolled and guarded, never indexed).
-template <int SMAX>
-__global__ void basis_coeff_kernel(const uint64_t* __restrict__ x, uint64_t* __restrict__ out, const prime_consts* __restrict__ src_consts,
-                                   const prime_consts* __restrict__ dst_consts, const ulonglong2* __restrict__ dinv, const ulonglong2* __restrict__ mat,
-                                   uint32_t S, uint32_t T, uint64_t per_prime) {
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t y[SMAX];
-#pragma unroll
-        for (int i = 0; i < SMAX; ++i)
-            if ((uint32_t)i < S) {
-                const ulonglong2 d = dinv[i];
-                y[i] = basis_scale(x[(uint64_t)i * per_prime + e], d.x, d.y, src_consts[i].q);
-            }
-        for (uint32_t j = 0; j < T; ++j) {
-            const uint64_t q = dst_consts[j].q, q2 = q << 1;
-            const ulonglong2* row = mat + (size_t)j * S;
-            uint64_t acc = 0;
-#pragma unroll
-            for (int i = 0; i < SMAX; ++i)
-                if ((uint32_t)i < S) {
-                    const ulonglong2 c = row[i];
-                    acc = basis_accumulate(acc, y[i], c.x, c.y, q, q2);
-                }
-            out[(uint64_t)j * per_prime + e] = csub(acc, q);
-        }
-    }
-}
-
-// agx_ntt_basis_extend_exact (EXACT) and agx_ntt_basis_extend_mont, coefficient form: basis_coeff_kernel's shape -- one thread per (frame, coefficient),
-// the y_i in registers under SMAX, wave-uniform constants -- with the correction by the auxiliary prime m (bfv_conv_arith.hpp).  A thread reads its S source
-// words (and, EXACT, its word of the auxiliary slab), forms V mod m through one more constant row {D_i mod m} as it forms the y_i, then alpha ONCE (one
-// Shoup product by k and the centring), and finishes every target with one Shoup product |alpha| c_j, added or subtracted by alpha's sign: 8 (S + 1 + T)
-// bytes per coefficient (EXACT) or 8 (S + T).  The two forms differ in their constants alone (aux_set): the Montgomery form's m and m^-1 are folded into
-// dinv, mat and c, and it reads no auxiliary word.
-template <int SMAX, bool EXACT>
-__global__ void basis_aux_coeff_kernel(const uint64_t* __restrict__ x, const uint64_t* __restrict__ xaux, uint64_t* __restrict__ out,
-                                       const prime_consts* __restrict__ src_consts, const prime_consts* __restrict__ dst_consts, const ulonglong2* __restrict__ dinv,
-                                       const ulonglong2* __restrict__ mat, const ulonglong2* __restrict__ row, const ulonglong2* __restrict__ corr, uint64_t m,
-                                       uint64_t k, uint64_t kp, uint32_t S, uint32_t T, uint64_t per_prime) {
-    const uint64_t m2 = m << 1;
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t y[SMAX];
-        uint64_t vm = 0;
-#pragma unroll
-        for (int i = 0; i < SMAX; ++i)
-            if ((uint32_t)i < S) {
-                const ulonglong2 d = dinv[i], c = row[i];
-                y[i] = basis_scale(x[(uint64_t)i * per_prime + e], d.x, d.y, src_consts[i].q);
-                vm = basis_accumulate(vm, y[i], c.x, c.y, m, m2);
-            }
-        const uint64_t r = EXACT ? bfv_reduce_lazy(xaux[e], m) : 0;
-        bool negative;
-        const uint64_t mag = bfv_centre(bfv_alpha(csub(vm, m), r, k, kp, m), m, &negative);
-        for (uint32_t j = 0; j < T; ++j) {
-            const uint64_t q = dst_consts[j].q, q2 = q << 1;
-            const ulonglong2* mrow = mat + (size_t)j * S;
-            uint64_t acc = 0;
-#pragma unroll
-            for (int i = 0; i < SMAX; ++i)
-                if ((uint32_t)i < S) {
-                    const ulonglong2 c = mrow[i];
-                    acc = basis_accumulate(acc, y[i], c.x, c.y, q, q2);
-                }
-            const ulonglong2 c = corr[j];
-            out[(uint64_t)j * per_prime + e] = bfv_correct(acc, mag, negative, c.x, c.y, q);
-        }
-    }
-}
-
-// agx_ntt_basis_quotient, the coefficient-domain step: the fast floor on Bsk and the Shenoy-Kumaresan return to Q in one pass (bfv_quotient_arith.hpp has
-// the formulas; S = K sources B, T = L targets Q, as the basis names them).  One thread per (frame, coefficient), basis_aux_coeff_kernel's shape: it reads
-// the T words y_i that the scaled inverse of the Q slabs wrote (slab i at y + i per_prime) and adds each, as it arrives, into the S accumulators of the
-// z_j and into f_m's through one row of qmat ([T][S + 1]) -- no y_i is kept -- then reads its S + 1 words s_j, s_m of the scaled inverse of the Bsk slabs
-// (behind the y_i), finishes the z_j in [0, b_j) and f_m in [0, m), forms W mod m as it goes, alpha ONCE, and walks the T targets as the exact conversion
-// does: 8 (2T + S + 1) bytes per coefficient and (2T + 1)(S + 1) Shoup products.  SMAX >= S bounds the z_j kept in registers (the loops over j are
-// unrolled and guarded, never indexed); the loops over the T targets are not unrolled and keep nothing.  The constants are wave-uniform (scalar loads).
-// No LDS, no barrier; out touches y nowhere.
-template <int SMAX>
-__global__ void basis_quotient_kernel(const uint64_t* __restrict__ y, uint64_t* __restrict__ out, const prime_consts* __restrict__ src_consts,
-                                      const prime_consts* __restrict__ dst_consts, const ulonglong2* __restrict__ qmat, const ulonglong2* __restrict__ mat,
-                                      const ulonglong2* __restrict__ row, const ulonglong2* __restrict__ corr, uint64_t m, uint64_t k, uint64_t kp, uint32_t S,
-                                      uint32_t T, uint64_t per_prime) {
-    const uint64_t m2 = m << 1;
-    const uint64_t* __restrict__ sb = y + (uint64_t)T * per_prime;      // the S slabs s_j, then s_m's
-    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t z[SMAX];
-        uint64_t fm = 0;
-#pragma unroll
-        for (int j = 0; j < SMAX; ++j) z[j] = 0;
-        for (uint32_t i = 0; i < T; ++i) {
-            const uint64_t yi = y[(uint64_t)i * per_prime + e];
-            const ulonglong2* qrow = qmat + (size_t)i * (S + 1);
-#pragma unroll
-            for (int j = 0; j < SMAX; ++j)
-                if ((uint32_t)j < S) {
-                    const ulonglong2 c = qrow[j];
-                    const uint64_t b = src_consts[j].q;
-                    z[j] = quot_accumulate(z[j], yi, c.x, c.y, b, b << 1);
-                }
-            const ulonglong2 c = qrow[S];
-            fm = quot_accumulate(fm, yi, c.x, c.y, m, m2);
-        }
-        uint64_t wm = 0;
-#pragma unroll
-        for (int j = 0; j < SMAX; ++j)
-            if ((uint32_t)j < S) {
-                const ulonglong2 c = row[j];
-                z[j] = quot_residue(sb[(uint64_t)j * per_prime + e], z[j], src_consts[j].q);
-                wm = quot_accumulate(wm, z[j], c.x, c.y, m, m2);
-            }
-        fm = quot_residue(sb[(uint64_t)S * per_prime + e], fm, m);
-        bool negative;
-        const uint64_t mag = bfv_centre(bfv_alpha(csub(wm, m), fm, k, kp, m), m, &negative);
-        for (uint32_t i = 0; i < T; ++i) {
-            const uint64_t q = dst_consts[i].q, q2 = q << 1;
-            const ulonglong2* mrow = mat + (size_t)i * S;
-            uint64_t acc = 0;
-#pragma unroll
-            for (int j = 0; j < SMAX; ++j)
-                if ((uint32_t)j < S) {
-                    const ulonglong2 c = mrow[j];
-                    acc = quot_accumulate(acc, z[j], c.x, c.y, q, q2);
-                }
-            const ulonglong2 c = corr[i];
-            out[(uint64_t)i * per_prime + e] = bfv_correct(acc, mag, negative, c.x, c.y, q);
-        }
-    }
-}
-
-// agx_ntt_basis_mod_down, generic route, in the coefficient domain: out_j[e] <- (out_j[e] - sum_i y_i[e] (D_i mod q_j)) D^-1 mod q_j.  One thread
-// per (frame, coefficient): it reads its S words of y (y_i in [0,q_i), as the scaled inverse of the source slabs wrote them: no basis_scale here),
-// then reads, finishes and writes back one word of each of the T target slabs, which the inverse left in [0,q_j): 8 (S + 2T) bytes per
-// coefficient.  The sum stays in [0,2q_j) term by term (basis_accumulate) and is brought below q_j for rescale_finish's reduced form, which
-// never forms 4q: any modulus below 2^62.  Constants are wave-uniform.  SMAX >= S as in basis_coeff_kernel.
-// AGX_RESCALE_ROUND (agx_ntt_basis_mod_down_mode) adds the two per-word steps of moddown_arith.hpp: c_i joins y_i modulo q_i as it is read, and
-// t h mod q_j leaves the sum, which stays in [0,2q_j), before it is brought below q_j.  One body (moddown_coeff_body.hpp, included in both), two
-// kernels: moddown_coeff_kernel (FLOOR: what it always was; rsrc and rdst are never read) and moddown_coeff_round_kernel.
-template <int SMAX>
-__global__ void moddown_coeff_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ y, const prime_consts* __restrict__ dst_consts,
-                                     const ulonglong2* __restrict__ mat, const ulonglong2* __restrict__ dall, uint32_t S, uint32_t T, uint64_t per_prime) {
-    [[maybe_unused]] constexpr bool ROUND = false;
-    [[maybe_unused]] constexpr const ulonglong2* rsrc = nullptr;
-    [[maybe_unused]] constexpr const uint64_t* rdst = nullptr;
-#include "moddown_coeff_body.hpp"
-}
-
-// rsrc: [S] {c_i = h D_i^-1 mod q_i, q_i}; rdst: [T] t h mod q_j
-template <int SMAX>
-__global__ void moddown_coeff_round_kernel(uint64_t* __restrict__ out, const uint64_t* __restrict__ y, const prime_consts* __restrict__ dst_consts,
-                                           const ulonglong2* __restrict__ mat, const ulonglong2* __restrict__ dall, uint32_t S, uint32_t T, uint64_t per_prime,
-                                           const ulonglong2* __restrict__ rsrc, const uint64_t* __restrict__ rdst) {
-    [[maybe_unused]] constexpr bool ROUND = true;
-#include "moddown_coeff_body.hpp"
 }
 
 __device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
@@ -710,24 +373,58 @@ hipError_t launch_inverse_radix2(const plan_view& pv, const uint64_t* in, uint64
     return hipGetLastError();
 }
 
+// One launch of a streaming kernel: grid_1d(work_items, 256) blocks of 256 threads by `slots` rows (blockIdx.y: the slot of a prime; 1 for a kernel that does
+// not read it), the kernel's own arguments behind
+template <class... P, class... A>
+static hipError_t launch_stream(void (*kernel)(P...), uint64_t work_items, uint32_t slots, hipStream_t s, const A&... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_1d(work_items, 256), slots), dim3(256), 0, s, args...);
+    return hipGetLastError();
+}
+
 hipError_t launch_pointwise_bhat(const plan_view& pv, uint64_t* c, const uint64_t* bhat, uint64_t batch, int64_t bhat_prime_stride,
                                  int64_t bhat_poly_stride, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
-    dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
-    hipLaunchKernelGGL(pointwise_bhat_kernel, grid, dim3(256), 0, s, c, bhat, pv.consts, pv.log_n, per_prime, bhat_prime_stride, bhat_poly_stride);
-    return hipGetLastError();
+    return launch_stream(pointwise_bhat_kernel, per_prime, pv.num_primes, s, c, bhat, pv.consts, pv.log_n, per_prime, bhat_prime_stride, bhat_poly_stride);
 }
 
 hipError_t launch_pointwise(const plan_view& pv, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
-    dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
-    hipLaunchKernelGGL(pointwise_kernel, grid, dim3(256), 0, s, a, b, c, pv.consts, per_prime);
-    return hipGetLastError();
+    return launch_stream(pointwise_kernel, per_prime, pv.num_primes, s, a, b, c, pv.consts, per_prime);
 }
 
-// the 16-byte form serves when all three bases are 16-byte aligned
+// The kernels templated on a word type W, on gathered or not and on a small number (outputs, an op): the 16-byte form serves when all three bases are 16-byte
+// aligned
 static bool inner_pairs(const uint64_t* a, const uint64_t* bhat, const uint64_t* c) {
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bhat) | reinterpret_cast<uintptr_t>(c)) & 15u) == 0;
+}
+template <class W> static const W* words(const uint64_t* p) { return reinterpret_cast<const W*>(p); }
+template <class W> static W* words(uint64_t* p) { return reinterpret_cast<W*>(p); }
+
+// The instance a call gets, in with_smax's style: f(w, gathered, v) with w a value of the word type -- a 16-byte pair when `pairs`, else one word --,
+// gathered a std::bool_constant and v, a std::integral_constant, the one of Vs that `value` is (a call without such a number: <0> and 0).  g = 1 takes the
+// un-gathered instance: pi is the identity.  f launches and returns the status.
+template <int... Vs, class F>
+static hipError_t with_instance(bool pairs, uint32_t galois_elt, int value, F&& f) {
+    hipError_t e = hipErrorInvalidValue;      // `value` is none of Vs: nothing is launched (the C boundary lets no such call through)
+    auto pick = [&](auto w, auto gathered) { (void)((value == Vs && ((e = f(w, gathered, std::integral_constant<int, Vs>{})), true)) || ...); };
+    auto word = [&](auto gathered) { if (pairs) pick(ulonglong2{}, gathered); else pick(uint64_t{}, gathered); };
+    if (galois_elt == 1) word(std::false_type{});
+    else word(std::true_type{});
+    return e;
+}
+
+// the argument block of an instance: a gathered one takes the whole of ga, an un-gathered one its first member
+template <bool GALOIS, class A>
+static const auto& args_of(const A& ga) {
+    if constexpr (GALOIS) return ga;
+    else return ga.in;
+}
+
+// one launch of the shape (a, b, c, consts, args) over `slots` primes of per_prime W each
+template <class W, class Args>
+static hipError_t launch_abc(void (*kernel)(const W*, const W*, W*, const prime_consts*, Args), const plan_view& pv, uint32_t slots, uint64_t per_prime, const uint64_t* a,
+                             const uint64_t* b, uint64_t* c, const Args& g, hipStream_t s) {
+    return launch_stream(kernel, per_prime, slots, s, words<W>(a), words<W>(b), words<W>(c), pv.consts, g);
 }
 
 static inner_args inner_args_of(const plan_view& pv, const inner_primes& ip, uint64_t batch, uint64_t bhat_batch, uint32_t terms, uint32_t outputs, bool pairs) {
@@ -744,89 +441,36 @@ static inner_args inner_args_of(const plan_view& pv, const inner_primes& ip, uin
     return g;
 }
 
-// the two kernel families of the inner products, by {outputs, word or pair}
-struct inner_plain { template <int OUT, class W> static auto kernel() { return &inner_product_kernel<OUT, W>; } };
-struct inner_galois { template <int OUT, class W> static auto kernel() { return &inner_product_galois_kernel<OUT, W>; } };
-
-// one launch of a family's instance for {outputs 1 or 2} x {word or pair}; g: the family's argument block, per_prime its inner_args' work per slot
-template <class Family, class Args>
-static hipError_t launch_inner(const plan_view& pv, uint32_t slots, uint64_t per_prime, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint32_t outputs,
-                               bool pairs, const Args& g, hipStream_t s) {
-    const dim3 grid(grid_1d(per_prime, 256), slots);
-    auto go = [&](auto kernel, auto* ap, auto* bp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, cp, pv.consts, g); };
-    if (pairs) {
-        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2*>(a), *b2 = reinterpret_cast<const ulonglong2*>(bhat);
-        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(c);
-        if (outputs == 1) go(Family::template kernel<1, ulonglong2>(), a2, b2, c2);
-        else go(Family::template kernel<2, ulonglong2>(), a2, b2, c2);
-    } else {
-        if (outputs == 1) go(Family::template kernel<1, uint64_t>(), a, bhat, c);
-        else go(Family::template kernel<2, uint64_t>(), a, bhat, c);
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_inner_product_galois(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
                                        uint64_t bhat_batch, uint32_t terms, uint32_t outputs, uint32_t galois_elt, hipStream_t s) {
-    if (galois_elt == 1) return launch_inner_product(pv, ip, a, bhat, c, batch, bhat_batch, terms, outputs, s);      // pi is the identity: the plain kernel
     const bool pairs = inner_pairs(a, bhat, c);
-    const inner_galois_args g{inner_args_of(pv, ip, batch, bhat_batch, terms, outputs, pairs), pv.log_n, galois_elt};
-    return launch_inner<inner_galois>(pv, ip.count, g.in.per_prime, a, bhat, c, outputs, pairs, g, s);
+    const inner_galois_args ga{inner_args_of(pv, ip, batch, bhat_batch, terms, outputs, pairs), pv.log_n, galois_elt};
+    return with_instance<1, 2>(pairs, galois_elt, (int)outputs, [&](auto w, auto gathered, auto out) {
+        return launch_abc(&inner_product_kernel<gathered, out, decltype(w)>, pv, ip.count, ga.in.per_prime, a, bhat, c, args_of<gathered>(ga), s);
+    });
 }
 
-hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
-                                uint64_t bhat_batch, uint32_t terms, uint32_t outputs, hipStream_t s) {
-    const bool pairs = inner_pairs(a, bhat, c);
-    const inner_args g = inner_args_of(pv, ip, batch, bhat_batch, terms, outputs, pairs);
-    return launch_inner<inner_plain>(pv, ip.count, g.per_prime, a, bhat, c, outputs, pairs, g, s);
-}
-
-// The ring calls: one launch each over the plan primes [first, first + count), 256 threads, the 16-byte form when every base of the call allows it
-template <class W, class Args>
-static hipError_t launch_ring(void (*kernel)(const W*, const W*, W*, const prime_consts*, Args), const plan_view& pv, uint32_t count, uint64_t per_prime, const void* a,
-                              const void* b, void* c, const Args& g, hipStream_t s) {
-    hipLaunchKernelGGL(kernel, dim3(grid_1d(per_prime, 256), count), dim3(256), 0, s, static_cast<const W*>(a), static_cast<const W*>(b), static_cast<W*>(c), pv.consts, g);
-    return hipGetLastError();
-}
-
-static hipError_t launch_ring_linear(const plan_view& pv, uint32_t first, uint32_t count, int op, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
+// The ring calls: one launch each over the plan primes [first, first + count), the 16-byte form when every base of the call allows it
+hipError_t launch_ring_linear(const plan_view& pv, uint32_t first, uint32_t count, ring_op op, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch,
+                              uint32_t galois_elt, hipStream_t s) {
     const bool pairs = inner_pairs(a, b, c);      // a negation passes a for b
-    const ring_args g{(batch << pv.log_n) >> (pairs ? 1 : 0), first};
-    auto go = [&](auto kernel) { return launch_ring(kernel, pv, count, g.per_prime, a, b, c, g, s); };
-    if (pairs) return op == RING_ADD ? go(&ring_linear_kernel<RING_ADD, ulonglong2>) : op == RING_SUB ? go(&ring_linear_kernel<RING_SUB, ulonglong2>) : go(&ring_linear_kernel<RING_NEG, ulonglong2>);
-    return op == RING_ADD ? go(&ring_linear_kernel<RING_ADD, uint64_t>) : op == RING_SUB ? go(&ring_linear_kernel<RING_SUB, uint64_t>) : go(&ring_linear_kernel<RING_NEG, uint64_t>);
-}
-
-hipError_t launch_ring_add(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
-    return launch_ring_linear(pv, first, count, RING_ADD, a, b, c, batch, s);
-}
-hipError_t launch_ring_sub(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
-    return launch_ring_linear(pv, first, count, RING_SUB, a, b, c, batch, s);
-}
-hipError_t launch_ring_negate(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, uint64_t* c, uint64_t batch, hipStream_t s) {
-    return launch_ring_linear(pv, first, count, RING_NEG, a, a, c, batch, s);
-}
-
-hipError_t launch_ring_add_galois(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch,
-                                  uint32_t galois_elt, hipStream_t s) {
-    if (galois_elt == 1) return launch_ring_add(pv, first, count, a, b, c, batch, s);      // pi is the identity: the plain kernel
-    const bool pairs = inner_pairs(a, b, c);
     const uint32_t shift = pairs ? 1 : 0;
-    const ring_galois_args g{ring_args{(batch << pv.log_n) >> shift, first}, (pv.n >> shift) - 1u, pv.log_n, galois_elt};
-    if (pairs) return launch_ring(&ring_add_galois_kernel<ulonglong2>, pv, count, g.in.per_prime, a, b, c, g, s);
-    return launch_ring(&ring_add_galois_kernel<uint64_t>, pv, count, g.in.per_prime, a, b, c, g, s);
+    const ring_galois_args ga{ring_args{(batch << pv.log_n) >> shift, first}, (pv.n >> shift) - 1u, pv.log_n, galois_elt};
+    return with_instance<RING_ADD, RING_SUB, RING_NEG>(pairs, galois_elt, op, [&](auto w, auto gathered, auto opc) {
+        if constexpr (gathered && opc != RING_ADD) return hipErrorInvalidValue;      // the add alone has a gathered instance
+        else return launch_abc(&ring_linear_kernel<opc, gathered, decltype(w)>, pv, count, ga.in.per_prime, a, b, c, args_of<gathered>(ga), s);
+    });
 }
 
 hipError_t launch_ring_tensor(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s) {
     const bool pairs = inner_pairs(a, b, c);      // a component lies count batch n words behind the one before: an even number
     const uint64_t per_prime = (batch << pv.log_n) >> (pairs ? 1 : 0);
     const ring_tensor_args g{per_prime, count * per_prime, first};
-    if (pairs) return launch_ring(&ring_tensor_kernel<ulonglong2>, pv, count, per_prime, a, b, c, g, s);
-    return launch_ring(&ring_tensor_kernel<uint64_t>, pv, count, per_prime, a, b, c, g, s);
+    return with_instance<0>(pairs, 1, 0, [&](auto w, auto, auto) { return launch_abc(&ring_tensor_kernel<decltype(w)>, pv, count, per_prime, a, b, c, g, s); });
 }
 
-// The weighted, accumulating inner product of a key switch (two outputs, the key one frame per prime): one launch of inner_weighted_kernel; g = 1 takes
-// its un-gathered instance.  The 16-byte form serves when ext, the key, acc and (where there is one) the weight are all 16-byte aligned.
+// The weighted, accumulating inner product of a key switch (two outputs, the key one frame per prime): one launch of inner_weighted_kernel.  The 16-byte
+// form serves when ext, the key, acc and (where there is one) the weight are all 16-byte aligned.
 hipError_t launch_inner_weighted(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, const uint64_t* weight, uint64_t weight_batch,
                                  uint64_t* acc, uint64_t batch, uint32_t terms, uint32_t galois_elt, bool accumulate, hipStream_t s) {
     const uint64_t* wt = weight ? weight : a;      // no weight: never read; a valid base keeps the slot arithmetic defined
@@ -837,18 +481,10 @@ hipError_t launch_inner_weighted(const plan_view& pv, const inner_primes& ip, co
     g.w_prime = weight ? (weight_batch << pv.log_n) >> shift : 0;
     g.log_n = pv.log_n, g.g = galois_elt;
     g.has_weight = weight ? 1u : 0u, g.w_broadcast = weight_batch == 1 ? 1u : 0u, g.accumulate = accumulate ? 1u : 0u;
-    const dim3 grid(grid_1d(g.in.per_prime, 256), ip.count);
-    auto go = [&](auto kernel, auto* ap, auto* bp, auto* wp, auto* cp) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, ap, bp, wp, cp, pv.consts, g); };
-    if (pairs) {
-        const ulonglong2 *a2 = reinterpret_cast<const ulonglong2*>(a), *b2 = reinterpret_cast<const ulonglong2*>(bhat), *w2 = reinterpret_cast<const ulonglong2*>(wt);
-        ulonglong2* c2 = reinterpret_cast<ulonglong2*>(acc);
-        if (galois_elt == 1) go(&inner_weighted_kernel<false, ulonglong2>, a2, b2, w2, c2);
-        else go(&inner_weighted_kernel<true, ulonglong2>, a2, b2, w2, c2);
-    } else {
-        if (galois_elt == 1) go(&inner_weighted_kernel<false, uint64_t>, a, bhat, wt, acc);
-        else go(&inner_weighted_kernel<true, uint64_t>, a, bhat, wt, acc);
-    }
-    return hipGetLastError();
+    return with_instance<0>(pairs, galois_elt, 0, [&](auto w, auto gathered, auto) {
+        using W = decltype(w);
+        return launch_stream(&inner_weighted_kernel<gathered, W>, g.in.per_prime, ip.count, s, words<W>(a), words<W>(bhat), words<W>(wt), words<W>(acc), pv.consts, g);
+    });
 }
 
 hipError_t launch_ring_mul_add_galois(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* w, uint64_t w_batch, const uint64_t* b, uint64_t* c,
@@ -857,28 +493,20 @@ hipError_t launch_ring_mul_add_galois(const plan_view& pv, uint32_t first, uint3
     const uint32_t shift = pairs ? 1 : 0;
     const mul_add_args g{ring_args{(batch << pv.log_n) >> shift, first}, (w_batch << pv.log_n) >> shift, (pv.n >> shift) - 1u, pv.log_n, galois_elt,
                          w_batch == 1 ? 1u : 0u, accumulate ? 1u : 0u};
-    if (pairs) return galois_elt == 1 ? launch_ring(&ring_mul_add_kernel<false, ulonglong2>, pv, count, g.in.per_prime, w, b, c, g, s)
-                                      : launch_ring(&ring_mul_add_kernel<true, ulonglong2>, pv, count, g.in.per_prime, w, b, c, g, s);
-    return galois_elt == 1 ? launch_ring(&ring_mul_add_kernel<false, uint64_t>, pv, count, g.in.per_prime, w, b, c, g, s)
-                           : launch_ring(&ring_mul_add_kernel<true, uint64_t>, pv, count, g.in.per_prime, w, b, c, g, s);
+    return with_instance<0>(pairs, galois_elt, 0, [&](auto wd, auto gathered, auto) {
+        return launch_abc(&ring_mul_add_kernel<gathered, decltype(wd)>, pv, count, g.in.per_prime, w, b, c, g, s);
+    });
 }
 
 hipError_t launch_rescale_coeff(const plan_view& pv, uint64_t* out, const uint64_t* t, uint64_t batch, bool round, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
-    dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
-    hipLaunchKernelGGL(rescale_coeff_kernel, grid, dim3(256), 0, s, out, t, pv.consts, pv.rescale, per_prime, round ? 1u : 0u);
-    return hipGetLastError();
+    return launch_stream(rescale_coeff_kernel, per_prime, pv.num_primes, s, out, t, pv.consts, pv.rescale, per_prime, round ? 1u : 0u);
 }
 
 hipError_t launch_automorphism_ntt(const plan_view& pv, const uint64_t* in, uint64_t* out, uint64_t batch, uint32_t g, hipStream_t s) {
     const uint64_t total = ((uint64_t)pv.num_primes * batch) << pv.log_n;
-    if (((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0) {
-        hipLaunchKernelGGL(automorphism_ntt_x2_kernel, dim3(grid_1d(total >> 1, 256)), dim3(256), 0, s, reinterpret_cast<const ulonglong2*>(in),
-                           reinterpret_cast<ulonglong2*>(out), pv.log_n, total >> 1, g);
-    } else {
-        hipLaunchKernelGGL(automorphism_ntt_kernel, dim3(grid_1d(total, 256)), dim3(256), 0, s, in, out, pv.log_n, total, g);
-    }
-    return hipGetLastError();
+    if (inner_pairs(in, in, out)) return launch_stream(automorphism_ntt_x2_kernel, total >> 1, 1, s, words<ulonglong2>(in), words<ulonglong2>(out), pv.log_n, total >> 1, g);
+    return launch_stream(automorphism_ntt_kernel, total, 1, s, in, out, pv.log_n, total, g);
 }
 
 hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, uint64_t* out, uint64_t batch, uint32_t g, hipStream_t s) {
@@ -886,76 +514,59 @@ hipError_t launch_automorphism_coeff(const plan_view& pv, const uint64_t* in, ui
     for (int it = 0; it < 3; ++it) h *= 2u - g * h;
     h &= (2u << pv.log_n) - 1u;
     const uint64_t per_prime = batch << pv.log_n;
-    dim3 grid(grid_1d(per_prime, 256), pv.num_primes);
-    hipLaunchKernelGGL(automorphism_coeff_gather_kernel, grid, dim3(256), 0, s, in, out, pv.consts, pv.log_n, per_prime, h);
-    return hipGetLastError();
+    return launch_stream(automorphism_coeff_gather_kernel, per_prime, pv.num_primes, s, in, out, pv.consts, pv.log_n, per_prime, h);
 }
 
+// The coefficient-domain basis kernels: one thread per (frame, coefficient), no slots.
 // the SMAX a kernel templated on its source capacity is instantiated with for S sources (at most AGX_BASIS_MAX_SRC = 16), as a compile-time constant
 template <class F>
-static void with_smax(uint32_t S, F&& f) {
-    if (S <= 1) f(std::integral_constant<int, 1>{});
-    else if (S <= 2) f(std::integral_constant<int, 2>{});
-    else if (S <= 4) f(std::integral_constant<int, 4>{});
-    else if (S <= 8) f(std::integral_constant<int, 8>{});
-    else f(std::integral_constant<int, 16>{});
+static hipError_t with_smax(uint32_t S, F&& f) {
+    if (S <= 1) return f(std::integral_constant<int, 1>{});
+    if (S <= 2) return f(std::integral_constant<int, 2>{});
+    if (S <= 4) return f(std::integral_constant<int, 4>{});
+    if (S <= 8) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 16>{});
 }
 
 hipError_t launch_basis_coeff(const plan_view& pv, const basis_view& bv, const uint64_t* x, uint64_t* out, uint64_t batch, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
-    const dim3 grid(grid_1d(per_prime, 256));
-    with_smax(bv.src_count, [&](auto smax) {
-        hipLaunchKernelGGL(basis_coeff_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, x, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, bv.dinv,
-                           bv.mat, bv.src_count, bv.dst_count, per_prime);
+    return with_smax(bv.src_count, [&](auto smax) {
+        return launch_stream(&basis_coeff_kernel<smax>, per_prime, 1, s, x, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, bv.dinv, bv.mat, bv.src_count,
+                             bv.dst_count, per_prime);
     });
-    return hipGetLastError();
 }
 
 hipError_t launch_basis_aux_coeff(const plan_view& pv, const basis_view& bv, const aux_view& av, bool exact, const uint64_t* x, const uint64_t* xaux, uint64_t* out,
                                   uint64_t batch, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
-    const dim3 grid(grid_1d(per_prime, 256));
     const aux_set& c = exact ? av.exact : av.mont;
-    with_smax(bv.src_count, [&](auto smax) {
-        if (exact)
-            hipLaunchKernelGGL((basis_aux_coeff_kernel<decltype(smax)::value, true>), grid, dim3(256), 0, s, x, xaux, out, pv.consts + bv.src_first,
-                               pv.consts + bv.dst_first, c.dinv, c.mat, av.row, c.corr, av.m, c.k, c.kp, bv.src_count, bv.dst_count, per_prime);
-        else
-            hipLaunchKernelGGL((basis_aux_coeff_kernel<decltype(smax)::value, false>), grid, dim3(256), 0, s, x, xaux, out, pv.consts + bv.src_first,
-                               pv.consts + bv.dst_first, c.dinv, c.mat, av.row, c.corr, av.m, c.k, c.kp, bv.src_count, bv.dst_count, per_prime);
+    return with_smax(bv.src_count, [&](auto smax) {
+        return launch_stream(exact ? &basis_aux_coeff_kernel<smax, true> : &basis_aux_coeff_kernel<smax, false>, per_prime, 1, s, x, xaux, out, pv.consts + bv.src_first,
+                             pv.consts + bv.dst_first, c.dinv, c.mat, av.row, c.corr, av.m, c.k, c.kp, bv.src_count, bv.dst_count, per_prime);
     });
-    return hipGetLastError();
 }
 
 hipError_t launch_basis_quotient(const plan_view& pv, const basis_view& bv, const aux_view& av, const ulonglong2* qmat, const uint64_t* y, uint64_t* out, uint64_t batch,
                                  hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
-    const dim3 grid(grid_1d(per_prime, 256));
-    with_smax(bv.src_count, [&](auto smax) {
-        hipLaunchKernelGGL(basis_quotient_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, y, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, qmat,
-                           av.exact.mat, av.row, av.exact.corr, av.m, av.exact.k, av.exact.kp, bv.src_count, bv.dst_count, per_prime);
+    return with_smax(bv.src_count, [&](auto smax) {
+        return launch_stream(&basis_quotient_kernel<smax>, per_prime, 1, s, y, out, pv.consts + bv.src_first, pv.consts + bv.dst_first, qmat, av.exact.mat, av.row,
+                             av.exact.corr, av.m, av.exact.k, av.exact.kp, bv.src_count, bv.dst_count, per_prime);
     });
-    return hipGetLastError();
 }
 
 hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, bool round, hipStream_t s) {
     const uint64_t per_prime = batch << pv.log_n;
-    const dim3 grid(grid_1d(per_prime, 256));
-    with_smax(bv.src_count, [&](auto smax) {
+    return with_smax(bv.src_count, [&](auto smax) {
         if (round)
-            hipLaunchKernelGGL(moddown_coeff_round_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, out, y, pv.consts + bv.dst_first, bv.down_mat, bv.dall,
-                               bv.src_count, bv.dst_count, per_prime, bv.round_src, bv.round_dst);
-        else
-            hipLaunchKernelGGL(moddown_coeff_kernel<decltype(smax)::value>, grid, dim3(256), 0, s, out, y, pv.consts + bv.dst_first, bv.down_mat, bv.dall, bv.src_count,
-                               bv.dst_count, per_prime);
+            return launch_stream(&moddown_coeff_round_kernel<smax>, per_prime, 1, s, out, y, pv.consts + bv.dst_first, bv.down_mat, bv.dall, bv.src_count, bv.dst_count,
+                                 per_prime, bv.round_src, bv.round_dst);
+        return launch_stream(&moddown_coeff_kernel<smax>, per_prime, 1, s, out, y, pv.consts + bv.dst_first, bv.down_mat, bv.dall, bv.src_count, bv.dst_count, per_prime);
     });
-    return hipGetLastError();
 }
 
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s) {
-    dim3 grid(grid_1d(batch << pv.log_n, 256), pv.num_primes);
-    hipLaunchKernelGGL(fill_kernel, grid, dim3(256), 0, s, out, pv.consts, pv.log_n, batch, first_poly, seed);
-    return hipGetLastError();
+    return launch_stream(fill_kernel, batch << pv.log_n, pv.num_primes, s, out, pv.consts, pv.log_n, batch, first_poly, seed);
 }
 
 }  // namespace agx

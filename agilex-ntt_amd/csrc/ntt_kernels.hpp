@@ -110,22 +110,19 @@ struct inner_primes {
 };
 // a dense [terms][count][batch][n], bhat dense [terms][outputs][count][bhat_batch][n] (bhat_batch = batch, or 1: one key frame per prime for every
 // frame), c dense [outputs][count][batch][n]; inputs in [0,4q), c in [0,q); out of place (c touches neither input).  pv: a view of the WHOLE plan
-// (only its constants are read).  16-byte accesses when all three bases allow them.  terms 1 .. 16, outputs 1 or 2.  One launch.
-hipError_t launch_inner_product(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
-                                uint64_t bhat_batch, uint32_t terms, uint32_t outputs, hipStream_t s);
-// agx_ntt_inner_product_galois: the same with a read through pi(i) = brev((g brev(i) + (g-1)/2) mod n) within every frame: c_o[i] = sum_t a_t[pi(i)] o
-// bhat_{t,o}[i]; g odd in [1, 2n).  No permuted copy of a is written.  One launch; g = 1 takes launch_inner_product's kernel.
+// (only its constants are read).  16-byte accesses when all three bases allow them.  terms 1 .. 16, outputs 1 or 2.
+// agx_ntt_inner_product_galois: a is read through pi(i) = brev((g brev(i) + (g-1)/2) mod n) within every frame: c_o[i] = sum_t a_t[pi(i)] o bhat_{t,o}[i];
+// g odd in [1, 2n).  No permuted copy of a is written.  One launch; g = 1 (agx_ntt_inner_product) takes the un-gathered instance.
 hipError_t launch_inner_product_galois(const plan_view& pv, const inner_primes& ip, const uint64_t* a, const uint64_t* bhat, uint64_t* c, uint64_t batch,
                                        uint64_t bhat_batch, uint32_t terms, uint32_t outputs, uint32_t galois_elt, hipStream_t s);
 // agx_ntt_add / _sub / _negate / _add_galois / _tensor on the plan primes [first, first + count): every operand set dense [count][batch][n] (the tensor
 // product: a, b [2][count][batch][n], c [3][count][batch][n]), slab i under plan prime first + i; inputs in [0,4q), c in [0,q).  pv: a view of the WHOLE
 // plan (only its constants are read).  c may be a or b (add, sub), a (negate, add_galois; there c touches b nowhere), neither (tensor; a may be b).
-// 16-byte accesses when all bases of the call allow them.  One launch each; add_galois with g = 1 takes launch_ring_add's kernel.
-hipError_t launch_ring_add(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
-hipError_t launch_ring_sub(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
-hipError_t launch_ring_negate(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, uint64_t* c, uint64_t batch, hipStream_t s);
-hipError_t launch_ring_add_galois(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch,
-                                  uint32_t galois_elt, hipStream_t s);
+// 16-byte accesses when all bases of the call allow them.  One launch each.  The linear calls: c = a + b[pi_g], a - b or -a (which reads no b: pass a); g is 1
+// but for add_galois, where g = 1 takes the plain add's instance.
+enum ring_op { RING_ADD, RING_SUB, RING_NEG };
+hipError_t launch_ring_linear(const plan_view& pv, uint32_t first, uint32_t count, ring_op op, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch,
+                              uint32_t galois_elt, hipStream_t s);
 hipError_t launch_ring_tensor(const plan_view& pv, uint32_t first, uint32_t count, const uint64_t* a, const uint64_t* b, uint64_t* c, uint64_t batch, hipStream_t s);
 // agx_ntt_mul_add_galois: c[i] = (accumulate ? c[i] : 0) + w[i] o b[pi_g(i)] over the same range; w is [count][w_batch][n], w_batch = batch or 1 (one
 // frame per prime for every frame of the batch).  One launch; g = 1 takes the un-gathered instance.

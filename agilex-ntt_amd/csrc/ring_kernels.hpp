@@ -1,14 +1,17 @@
 // ring_kernels.hpp -- the kernels of agx_ntt_add, _sub, _negate, _add_galois and _tensor: linear arithmetic and the tensor product on NTT-form frames.
-// Included by ntt_kernels.hip alone, behind inner_gather and galois_read_index (the pair form's half swap and the index text of
-// inner_product_galois_kernel, used here as they stand).  The per-word arithmetic is csrc/ring_arith.hpp, which tests/ring_selftest.cpp compiles too.
+// Compiled in ntt_kernels.hip.  The gathered add reads through galois_read_index and inner_gather (inner_kernels.hpp: the index text and the pair form's
+// half swap of the gathered inner product).  The per-word arithmetic is csrc/ring_arith.hpp, which tests/ring_selftest.cpp compiles too.
 //
 // All of them have the streaming shape of inner_product_kernel: blockIdx.y is the slot of a prime in the call's range and its constants are
 // consts[first + slot]; grid-stride over the slot's batch x n words; no LDS, no barrier, no table.  W is one word, or a 16-byte pair when ALL bases of
 // the call are 16-byte aligned (n is even, so a slot is a whole number of pairs).  Inputs in [0, 4q), outputs in [0, q).
-// Pointers the calls allow to coincide carry no __restrict__: c with a or b in the linear kernel, c with a in the gathered one, a with b in the tensor
+// Pointers the calls allow to coincide carry no __restrict__: c with a or b in the linear kernel (its gathered instance: c with a), a with b in the tensor
 // kernel.  A work item reads its own words of the operands c may equal before it writes them, and no other work item reads or writes those words.
 #pragma once
+#include "inner_kernels.hpp"
 #include "ring_arith.hpp"
+
+#include <type_traits>
 
 namespace agx {
 
@@ -16,8 +19,6 @@ struct ring_args {
     uint64_t per_prime;      // W per slot: batch n / lanes
     uint32_t first;          // slot y serves plan prime first + y
 };
-
-enum ring_op { RING_ADD, RING_SUB, RING_NEG };
 
 template <int OP>
 __device__ __forceinline__ uint64_t ring_word(uint64_t a, uint64_t b, uint64_t q, uint64_t q2) {
@@ -32,39 +33,37 @@ __device__ __forceinline__ ulonglong2 ring_lanes(ulonglong2 a, ulonglong2 b, uin
     return make_ulonglong2(ring_word<OP>(a.x, b.x, q, q2), ring_word<OP>(a.y, b.y, q, q2));
 }
 
-// c = a + b, a - b or -a: 24 bytes per word, 16 for the negation (which reads no b)
-template <int OP, class W>
-__global__ void ring_linear_kernel(const W* a, const W* b, W* c, const prime_consts* __restrict__ consts, ring_args g) {
-    const uint32_t slot = blockIdx.y;
-    const uint64_t q = consts[g.first + slot].q, q2 = q << 1;
-    const uint64_t off = (uint64_t)slot * g.per_prime;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
-        const W x = a[off + i];
-        W y = x;
-        if constexpr (OP != RING_NEG) y = b[off + i];
-        c[off + i] = ring_lanes<OP>(x, y, q, q2);
-    }
-}
-
-// c[i] = a[i] + b[pi_g(i)] within every frame: the linear kernel with b read through galois_read_index, formed once per work item; in the pair form an
-// output pair reads one input pair, its halves swapped or not (inner_gather).  c may be a; it touches b nowhere.  The host sends g = 1 to ring_linear_kernel.
+// the gathered instance's arguments: the un-gathered ones keep ring_args as it is
 struct ring_galois_args {
     ring_args in;
     uint32_t frame_mask, log_n, g;      // n / lanes - 1; g odd, below 2n
 };
 
-template <class W>
-__global__ void ring_add_galois_kernel(const W* a, const W* b, W* c, const prime_consts* __restrict__ consts, ring_galois_args ga) {
-    constexpr int kLanes = sizeof(W) / 8;
-    const ring_args& g = ga.in;
+__device__ __forceinline__ const ring_args& ring_part(const ring_args& g) { return g; }
+__device__ __forceinline__ const ring_args& ring_part(const ring_galois_args& ga) { return ga.in; }
+
+// c = a + b, a - b or -a: 24 bytes per word, 16 for the negation (which reads no b).  GALOIS (the add alone): c[i] = a[i] + b[pi_g(i)] within every frame, b
+// read through galois_read_index, formed once per work item; in the pair form an output pair reads one input pair, its halves swapped or not (inner_gather).
+// There c may be a and touches b nowhere.  The host sends g = 1 to the un-gathered instance.
+template <int OP, bool GALOIS, class W>
+__global__ void ring_linear_kernel(const W* a, const W* b, W* c, const prime_consts* __restrict__ consts, std::conditional_t<GALOIS, ring_galois_args, ring_args> ga) {
+    static_assert(!GALOIS || OP == RING_ADD, "the add alone has a gathered instance");
+    const ring_args& g = ring_part(ga);
     const uint32_t slot = blockIdx.y;
     const uint64_t q = consts[g.first + slot].q, q2 = q << 1;
     const uint64_t off = (uint64_t)slot * g.per_prime;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < g.per_prime; i += (uint64_t)gridDim.x * blockDim.x) {
-        bool swap;
-        const uint64_t bi = galois_read_index<kLanes>(i, ga.frame_mask, ga.log_n, ga.g, swap);
-        const W x = a[off + i], y = b[off + bi];
-        c[off + i] = ring_lanes<RING_ADD>(x, inner_gather(y, swap), q, q2);
+        if constexpr (GALOIS) {
+            bool swap;
+            const uint64_t bi = galois_read_index<sizeof(W) / 8>(i, ga.frame_mask, ga.log_n, ga.g, swap);
+            const W x = a[off + i], y = b[off + bi];
+            c[off + i] = ring_lanes<OP>(x, inner_gather(y, swap), q, q2);
+        } else {
+            const W x = a[off + i];
+            W y = x;
+            if constexpr (OP != RING_NEG) y = b[off + i];
+            c[off + i] = ring_lanes<OP>(x, y, q, q2);
+        }
     }
 }
 

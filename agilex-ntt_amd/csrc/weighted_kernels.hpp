@@ -1,7 +1,7 @@
 // weighted_kernels.hpp -- the kernels of agx_ntt_keyswitch_accumulate_decomposed and agx_ntt_mul_add_galois: a linear transform's sum over rotations,
-// formed in the extended basis before ONE ModDown (include/agx_ntt.h).  Included by ntt_kernels.hip alone, behind inner_product_galois_kernel and
-// ring_kernels.hpp, whose inner_args, inner_lanes, inner_gather and galois_read_index serve here as they stand.  The per-word finish is
-// csrc/weighted_arith.hpp, which tests/weighted_selftest.cpp compiles too.
+// formed in the extended basis before ONE ModDown (include/agx_ntt.h).  Compiled in ntt_kernels.hip.  inner_args, inner_lanes, inner_gather and
+// galois_read_index of inner_kernels.hpp and ring_args of ring_kernels.hpp serve here as they stand.  The per-word finish is csrc/weighted_arith.hpp,
+// which tests/weighted_selftest.cpp compiles too.
 //
 // Both have the streaming shape of inner_product_kernel: blockIdx.y is the slot of a prime, grid-stride over the slot's batch x n words; no LDS, no
 // barrier, no table; W is one word, or a 16-byte pair when ALL bases of the call are 16-byte aligned.  pi_g is formed once per work item; GALOIS =
@@ -9,6 +9,8 @@
 // the same index, so it carries no __restrict__; the host rules keep it apart from every other operand (c may be exactly b at g = 1: a work item then
 // reads its own word of b before it writes it).  has_weight, accumulate and the broadcasts are wave-uniform.
 #pragma once
+#include "inner_kernels.hpp"
+#include "ring_kernels.hpp"
 #include "weighted_arith.hpp"
 
 namespace agx {
@@ -21,7 +23,7 @@ __device__ __forceinline__ ulonglong2 weighted_lanes(const acc128* s, bool has_w
                            weighted_finish(acc_reduce(s[1], k.q, k.mu_hi, k.mu_lo), has_w, w.y, has_old, old.y, k.q, q2, k.mu_hi, k.mu_lo));
 }
 
-// acc_o[i] = (accumulate ? acc_o[i]' : 0) + w[i or its position in the frame]' (sum_t a_t[pi_g(i)]' key_{t,o}[i]') for o = 0, 1: inner_product_galois_kernel's
+// acc_o[i] = (accumulate ? acc_o[i]' : 0) + w[i or its position in the frame]' (sum_t a_t[pi_g(i)]' key_{t,o}[i]') for o = 0, 1: inner_product_kernel's
 // sum with two outputs, its groups of four terms and its 128-bit sums, then weighted_finish per word.  The weight's and the old words' loads are issued in
 // front of the terms', so that they are in flight with them: 2 + 2 W more per work item than the plain kernel holds beside a group's 12.
 struct weighted_args {
@@ -78,7 +80,7 @@ __global__ void inner_weighted_kernel(const W* __restrict__ a, const W* __restri
 }
 
 // agx_ntt_mul_add_galois: c[i] = (accumulate ? c[i]' : 0) + w[i or its position in the frame]' b[pi_g(i)]' on the plan primes [first, first + count): the
-// gathered add's shape (ring_add_galois_kernel) with a product.  32 bytes per word with a weight per frame and an old word, 16 with neither.
+// gathered add's shape (ring_linear_kernel, GALOIS) with a product.  32 bytes per word with a weight per frame and an old word, 16 with neither.
 struct mul_add_args {
     ring_args in;
     uint64_t w_prime;                        // W per slot of w: w_batch n / lanes

@@ -65,7 +65,7 @@ static uint32_t brev32(uint32_t x) {
     return ((x & 0xaaaaaaaau) >> 1) | ((x & 0x55555555u) << 1);
 }
 
-// pi_g(p) in the kernel's operations (inner_product_galois_kernel, automorphism_ntt_kernel)
+// pi_g(p) in the kernel's operations (galois_read_index of csrc/inner_kernels.hpp, automorphism_ntt_kernel)
 static uint32_t pi(uint32_t log_n, uint32_t g, uint32_t p) {
     const uint32_t mask = (1u << log_n) - 1u, shift = 32u - log_n, c = (g - 1u) >> 1;
     return brev32((g * (brev32(p) >> shift) + c) & mask) >> shift;

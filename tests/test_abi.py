@@ -446,6 +446,22 @@ def test_kernel_source_hash_tracks_the_sources(agx, tmp_path):
     assert re.fullmatch(r"[0-9a-f]{16}", h) and h == agx.kernel_source_sha16()
 
 
+def test_kernel_source_hash_covers_every_included_device_source(agx):
+    """what kernel_source_sha16() hashes is every csrc/*.hip and the closure of their #include "..." lines within csrc/, found here by a walk of its own"""
+    csrc = os.path.join(ROOT, "agilex-ntt_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert names
+    for name in names:      # grows as it is walked
+        for inc in re.findall(r'(?m)^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(os.path.join(csrc, name)).read()):
+            if "/" not in inc and os.path.exists(os.path.join(csrc, inc)) and inc not in names:
+                names.append(inc)
+    assert sorted(os.path.relpath(f, csrc) for f in agx.kernel_source_files()) == sorted(names)
+    for header in ("moddown_arith.hpp", "bfv_conv_arith.hpp", "bfv_quotient_arith.hpp", "moddown_coeff_body.hpp", "moddown_rb2_body.hpp",
+                   "inner_kernels.hpp", "automorphism_kernels.hpp", "basis_coeff_kernels.hpp", "ring_kernels.hpp", "weighted_kernels.hpp"):
+        assert header in names, header
+    assert not [n for n in names if n.endswith(".cpp")]
+
+
 def test_bench_power_sampler_reads_amdgpu_sysfs_layout(tmp_path):
     """bench.py's PowerSampler on a fake amdgpu sysfs tree: microwatts -> watts, the starred pp_dpm_sclk level, window medians"""
     import importlib.util
