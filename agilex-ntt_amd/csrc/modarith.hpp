@@ -487,6 +487,26 @@ struct q60c_fold_bounds {
     static_assert(tx_max + 8 * q_min < two64 && tx_max_c1 + 8 * q_max < two64, "y' <= tx + 8q = 2^64 - 1 for every c");
 };
 
+// RARE last subtract (rb_frame.hpp: kOptQ60cRareSub).  A transform's output leaves the fold as t = r + k c, r < 2^60, k <= 15 (reduce_top4_q60c), and the
+// conditional subtract of q that finishes it acts only when t >= q = 2^60 - c.  With c < 2^28 the whole interval [q, 2^60 + 15c) has a high word of at
+// least 0x0FFFFFFF, so ONE 32-bit compare of the high word flags every coefficient that needs the subtract (and some that do not: t in
+// [0x0FFFFFFF 2^32, q), about 2^-28 of the residues).  The kernel ORs the flags of a wave into a scalar mask and runs the subtract, over every register,
+// only in a wave whose mask is not zero; the results are word for word those of a subtract per coefficient.
+constexpr uint32_t kQ60cTailHi = 0x0fffffffu;
+struct q60c_tail_bounds {
+    typedef unsigned __int128 u128;
+    using F = q60c_fold_bounds;
+    static constexpr u128 t_max = ((u128)1 << 60) - 1 + 15 * F::c_max;      // after reduce_top4_q60c, the largest c of the class
+    static_assert(15 * F::c_max < ((u128)1 << 32), "k c fits a word: the fold cannot carry t past bit 61");
+    static_assert(t_max < ((u128)1 << 63), "the sign test of the cold block's csub_select_c is exact");
+    static_assert((F::q_min >> 32) >= kQ60cTailHi, "t >= q implies hi32(t) >= 0x0FFFFFFF, for every c of the class (q falls as c grows)");
+    static_assert((((u128)kQ60cTailHi << 32) - 1) < F::q_min, "a coefficient that is not flagged is below q");
+};
+// wave mask of the lanes whose t may need the last subtract: one VOPC compare per output that writes an SGPR pair.  The optimiser widens the test of the
+// high word to the same predicate on the whole word, t >= 0x0FFFFFFF 2^32 (v_cmp_lt_u64); forced to 32 bits through the compare intrinsic it measured the same
+// energy, and the headline sessions that decided this form were run on the one below (profiles/r18_final_subtract_bench_runs.txt)
+__device__ __forceinline__ uint64_t q60c_tail_flag(uint64_t t) { return __builtin_amdgcn_ballot_w64((uint32_t)(t >> 32) >= kQ60cTailHi); }
+
 // 2^29 as opaque_one() gives 1: the factor of hl stays a multiply-add
 __device__ __forceinline__ uint32_t opaque_two29() {
     uint32_t v;

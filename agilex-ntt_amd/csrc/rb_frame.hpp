@@ -190,6 +190,11 @@ constexpr int kOptQ60cFold = 1 << 28;      // with kOptQ60c: the two-twiddle but
                                            // table's slots hold {w, w 2^32 mod q}, each split at bit 29, instead of {w, w'} (rb_kernels.hpp: build_table_fold_t)
 constexpr int kOptQ60cSkip = 1 << 21;      // with kOptQ60cFold, every modulus 2^60 - c with c <= kQ60cSkipMaxC = 2^27 (the launch chooses: plan_view::q60c_skip): x is reduced by its top four
                                            // bits on every second stage only, lazy-range constant 7q (modarith.hpp: q60c_skip_schedule, q60c_skip_bounds); same table
+constexpr int kOptQ60cRareSub = 1 << 22;   // with kOptQ60c and kOptStreamTw, forward only: the last stage leaves every output at the fold's t (reduce_top4_q60c), flags the ones whose high word
+                                           // admits t >= q with one 32-bit compare each, ORs the flags into a wave mask on the scalar unit and runs the conditional subtract of q -- over
+                                           // all registers, in a cold block behind ONE scalar branch -- only in a wave with a flag (modarith.hpp: q60c_tail_bounds); same results
+constexpr int kOptTwScalarBase = 1 << 23;  // with kOptStreamTw: a per-lane pass's table entries are addressed as (wave-uniform base pinned in SGPRs, advanced per chunk with scalar adds)
+                                           // + (the lane's 32-bit byte offset, computed once per pass) + (immediate): no 64-bit vector address is built for any chunk
 constexpr int kOptStreamCh1 = 1 << 29;     // with kOptStreamTw: one table entry per chunk instead of two or four (R = 4 passes then fit 64 VGPRs: 8 waves/SIMD)
 // Measured and removed in round 4 (the records stay in profiles/ and DESIGN.md 3.4-3.6): the XOR-swizzled image, cross products as 32-bit multiplies,
 // the inverse's twiddle-first / priority policies, timing ablations, persistent streaming / loop forms of the forward, resident sub-blocks with
@@ -224,6 +229,9 @@ struct rb2_frame {
     static_assert(!Q60C_SKIP || q60c_skip_schedule::valid(L), "no unreduced stage may follow another, and stage 0 reduces");
     static constexpr bool SPLIT = (OPT & kOptSplitWord) != 0;
     static constexpr bool STREAM_TW = (OPT & kOptStreamTw) != 0, PIN_BF = (OPT & kOptPinBf) != 0, STREAM_CH1 = (OPT & kOptStreamCh1) != 0;
+    static constexpr bool RARE_SUB = Q60C && STREAM_TW && (OPT & kOptQ60cRareSub) != 0, TW_SBASE = STREAM_TW && (OPT & kOptTwScalarBase) != 0;
+    static_assert((OPT & kOptQ60cRareSub) == 0 || RARE_SUB, "the rare last subtract is a form of the streamed q = 2^60 - c kernels");
+    static_assert((OPT & kOptTwScalarBase) == 0 || TW_SBASE, "scalar table bases are a form of the streamed kernels");
     static_assert(!EST || lazy16_tailfree::valid(L), "tail-free schedule must keep every stage within 16q");
     static_assert(!Q60C || q60c_tailfree::valid(L), "sign-bit subtracts must keep every stage within 16q + 8c");
     mutable uint64_t ts[12];
@@ -396,6 +404,8 @@ struct rb2_frame {
         twpair tw[C];
         const twpair* col;
         uint32_t hstride;
+        uint64_t sb;           // TW_SBASE, per-lane passes: the wave-uniform base of the chunk last requested (its first entry, column 0), in SGPRs
+        uint32_t voff;         // ... and this lane's byte offset from it, the same for every entry of the pass
     };
     template <int p>
     __device__ __forceinline__ void fetch(tw_src<p>& t, const twpair* tbl) const {
@@ -415,6 +425,10 @@ struct rb2_frame {
         } else {
             t.col = tbl;
             t.hstride = (uint32_t)H;
+            if constexpr (TW_SBASE) {
+                t.sb = reinterpret_cast<uint64_t>(tbl + G::table_off(p));
+                t.voff = (tid >> rlo) * (uint32_t)sizeof(twpair);
+            }
         }
     }
     // Entry j of per-lane pass p's table for this lane, addressed as (wave-uniform base of the entry, in SGPRs) + (32-bit lane index):
@@ -481,9 +495,31 @@ struct rb2_frame {
     struct tw_chunk {
         twpair e[CH];
     };
+    // first table entry of chunk q
+    static constexpr int st_first(int ns, int q, bool inv = false) { return (1 << st_kk(ns, st_stage(ns, q, inv), inv)) + st_chunk(ns, q, inv) * CH; }
     template <int p, int q, bool INV = false>
-    __device__ __forceinline__ void stream_load(tw_chunk& c, const tw_src<p>& t) const {
+    __device__ __forceinline__ void stream_load(tw_chunk& c, tw_src<p>& t) const {
         constexpr int ns = G::hi(p) - G::rlo(p) + 1, S = st_stage(ns, q, INV), cc = st_chunk(ns, q, INV), kk = st_kk(ns, S, INV);
+        if constexpr (TW_SBASE && !G::uniform_pass(p)) {
+            // the base steps from the previous chunk's first entry to this one's on the scalar unit (a compile-time distance); pinned, or the constant
+            // is folded back into a 64-bit vector add per chunk.  Every load is then SGPR base + 32-bit lane offset + immediate
+            constexpr int H = G::H(p), step = st_first(ns, q, INV) - (q == 0 ? 0 : st_first(ns, q - 1, INV));
+            t.sb = opaque_sgpr64(t.sb + (int64_t)step * H * (int64_t)sizeof(twpair));
+            // through the global address space: an address that went through the pin would otherwise be read with flat loads
+            // (as pointer steps, not integer sums: summed as integers, lane offset + immediate becomes one 64-bit vector value shared by all chunks)
+            typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+            typedef const u64x2 __attribute__((address_space(1))) * global_ptr;
+            typedef const unsigned char __attribute__((address_space(1))) * global_bytes;
+            static_assert(sizeof(u64x2) == sizeof(twpair), "one 16-byte load per entry");
+            asm("" : "+v"(t.voff));      // the 32-bit offset is widened in the block that loads: widened once in an earlier block, it arrives as a 64-bit vector value
+            const global_bytes lane = (global_bytes)t.sb + t.voff;
+            static_for<0, st_count(ns, S, INV)>([&](auto I) {
+                const u64x2 e = *(global_ptr)(lane + (uint32_t)I * H * (uint32_t)sizeof(twpair));
+                c.e[I].x = e.x;
+                c.e[I].y = e.y;
+            });
+            return;
+        }
         static_for<0, st_count(ns, S, INV)>([&](auto I) {
             constexpr int j = (1 << kk) + cc * CH + (int)I;
             if constexpr (G::uniform_pass(p)) c.e[I] = load_uniform(t.col + j);
@@ -493,6 +529,7 @@ struct rb2_frame {
     template <int P0, int P1>
     __device__ __forceinline__ void forward_passes_streamed(uint64_t (&x)[C], const twpair* tbl) const {
         static_assert(P0 == 0 && P1 == NP, "whole transform");
+        uint64_t tail_mask = 0;      // RARE_SUB: lanes of this wave with an output that may still need the subtract of q (scalar: an SGPR pair)
         static_for<P0, P1>([&](auto P) {
             constexpr int p = P;
             constexpr int rlo = G::rlo(p), hi = G::hi(p), ns = hi - rlo + 1, NQ = st_total(ns);
@@ -513,7 +550,11 @@ struct rb2_frame {
                         constexpr bf_regs bf = bf_pair<rb>(B);
                         constexpr int r0 = bf.r0, r1 = bf.r1;
                         if constexpr (PIN_BF) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
-                        forward_step<L - 1 - (rlo + rb), decltype(M)::value>(x[r0], x[r1], buf[q & 1].e[bf.o - cc * CH]);
+                        if constexpr (RARE_SUB && last_stage && decltype(M)::value == 0) {
+                            // both outputs stay at the fold's t (what a lazy launch stores); the subtract of q waits for the wave's mask
+                            forward_step<L - 1 - (rlo + rb), 1>(x[r0], x[r1], buf[q & 1].e[bf.o - cc * CH]);
+                            tail_mask |= q60c_tail_flag(x[r0]) | q60c_tail_flag(x[r1]);
+                        } else forward_step<L - 1 - (rlo + rb), decltype(M)::value>(x[r0], x[r1], buf[q & 1].e[bf.o - cc * CH]);
                         if constexpr (PIN_BF) asm volatile("" : "+v"(x[r0]), "+v"(x[r1]));
                     });
                 };
@@ -530,6 +571,11 @@ struct rb2_frame {
                 if constexpr (PRIO_BARRIER && !G::exchange_is_wave_local(p)) __builtin_amdgcn_s_setprio(0);
             }
         });
+        if constexpr (RARE_SUB) {
+            // cold: some lane of the wave holds a t with hi32(t) >= 0x0FFFFFFF (never set by a lazy launch).  The subtract a non-lazy launch owes, over every
+            // register: exact for the flagged ones and the identity for the rest (t < q), so false positives only cost this block
+            if (tail_mask != 0) static_for<0, C>([&](auto Rr) { constexpr int r = Rr; x[r] = csub_select_c(x[r], fc.nq1); });
+        }
     }
 
     template <int P0, int P1>

@@ -16,8 +16,16 @@ const rb_entry kEntries[] = {
     // the forward companion of such plans (ntt_kernels.hip: kCompanionDefaults).  Two kernels behind the id, one table: a plan whose moduli all have
     // c <= 2^27 (kQ60cSkipMaxC; the flag is the plan's, plan_view::q60c_skip) gets the skip form -- reduction by the top four bits on the even stages
     // only, 7q in place of 8q, any 64-bit input -- and every other plan, mixed ones included, the every-stage kernel above
-    make_entry_single_fwd_q60c_skip<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold) << 1), 4>(165),
+    // Both kernels take the last conditional subtract once per wave instead of once per coefficient (kOptQ60cRareSub: a 32-bit compare per output feeds a
+    // scalar mask, the subtract runs in a cold block behind one scalar branch) and address the per-lane table entries of passes 1 and 2 from a base
+    // advanced on the scalar unit (kOptTwScalarBase); same words out, same table
+    make_entry_single_fwd_q60c_skip<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold | kOptQ60cRareSub | kOptTwScalarBase) << 1), 4>(165),
 #ifdef AGX_DIAG
+    // A/B twins of id 165 (tools/energy_ab.py): the two kernels it launched before those two options (169), and with each option alone (170: the
+    // rare subtract, 171: the scalar table bases)
+    make_entry_single_fwd_q60c_skip<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold) << 1), 4>(169),
+    make_entry_single_fwd_q60c_skip<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold | kOptQ60cRareSub) << 1), 4>(170),
+    make_entry_single_fwd_q60c_skip<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold | kOptTwScalarBase) << 1), 4>(171),
     // A/B twin of id 165 that always launches the every-stage kernel, whatever the plan's moduli (tools/energy_ab.py)
     make_entry_single_fwd<12, 5, kLazy | ((kOptPrio | kOptQ60c | kOptQ60cFold) << 1), 4>(168),
     // A/B twin of id 165 with the butterfly it had before: quotient estimate from {w, w'}, sign-bit subtracts on the tail-free schedule (tools/energy_ab.py)

@@ -6,7 +6,7 @@ Compile every device unit of both trees to assembly, product flags and again wit
 then  python tools/compare_device_asm.py OLD NEW [RENAMES]  splits each <unit>.s per kernel symbol (label to the resource block behind
 .end_amdhsa_kernel) and compares by mangled name.  The function index in local labels and loop comments (.LBB<k>_, .Lfunc_end<k>, .Ltmp<k>,
 Header=BB<k>_, "Child Loop BB<k>_" / "Parent Loop BB<k>_") is normalised: it shifts when an earlier kernel of the unit disappears or a new one is emitted
-ahead of it.  Exit status 0: every kernel of NEW is textually identical to OLD's (so are its registers, scratch, LDS and occupancy); kernels only in OLD
+ahead of it (so is the padding between a label and its comment, which follows the index's width).  Exit status 0: every kernel of NEW is textually identical to OLD's (so are its registers, scratch, LDS and occupancy); kernels only in OLD
 are listed.  A change that adds kernels exits 1 on purpose; its RESULT line says apart how many kernels of OLD are missing or different (what must be 0
 for "the old kernels are untouched") and how many are new.
 
@@ -28,6 +28,7 @@ def kernels(path, renames={}):
         while end + 1 < len(txt) and not re.match(r"\t\.(protected|section|amdgpu_metadata|p2alignl|ident|weak|globl)\b|\s*$", txt[end + 1]):
             end += 1      # the .set block of resource counts behind the descriptor
         body = re.sub(r"(\.LBB|\.Lfunc_end|\.Ltmp|Header=BB|Loop BB)\d+", r"\1#", "\n".join(txt[start:end + 1]))
+        body = re.sub(r"(?m)^(\.LBB#_\d+:)[ \t]+;", r"\1 ;", body)      # a label's comment is padded to a column: the padding shrinks when the index gains a digit
         new = renames.get(name, name)
         out[new] = re.sub(r"(?<![\w$.])" + re.escape(name) + r"(?![\w$])", new, body) if new != name else body
     return out

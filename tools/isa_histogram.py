@@ -6,7 +6,7 @@ flags (hipcc --cuda-device-only -S; no GPU needed), finds the kernel whose mangl
   * the counts grouped by what the instruction is for, per wave and per butterfly,
   * an issue-cost estimate from the box calibration (profiles/r01g_alu_issue_calibration.txt, 8 waves/SIMD,
     cost relative to v_add_u32 = one 2-cycle issue slot).
-The n = 4096 forward companions: --tu reg_s4096.hip --butterflies 192 --kernel fwd_rb2ILi12ELi5ELi1ELi205263143 (id 159) or ...ELi1010569511 (id 165; ...ELi473698599 is what it was before the two-twiddle butterfly, ...ELi1014763815 its skip-form kernel for c <= 2^27).
+The n = 4096 forward companions: --tu reg_s4096.hip --butterflies 192 --kernel fwd_rb2ILi12ELi5ELi1ELi205263143 (id 159) or ...ELi1010569511 (id 165; ...ELi473698599 is what it was before the two-twiddle butterfly, ...ELi1014763815 its skip-form kernel for c <= 2^27 before the rare last subtract and the scalar table bases, now diag id 169; ...ELi1039929639 / ...ELi1035735335 the skip-form / every-stage kernels with both).
 Usage: python tools/isa_histogram.py [--tu reg_n4096.hip] [--kernel 'fwd_rb2ILi12ELi3ELi1ELi1850727'] [--butterflies 48] [--out FILE.md]"""
 import argparse
 import collections
