@@ -93,6 +93,12 @@ ABI = {
     "agx_ntt_keyswitch_hoisted_info": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "agx_ntt_keyswitch_accumulate_decomposed": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _u64, _u32, _int, _vp]),
     "agx_ntt_keyswitch_mod_down": (_int, [_vp, _vp, _vp, _u64, _vp]),
+    "agx_ntt_plain_create": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32, _u32, _u64]),
+    "agx_ntt_plain_destroy": (_int, [_vp]),
+    "agx_ntt_plain_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), _p64, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "agx_ntt_plain_scale_up": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
+    "agx_ntt_plain_lift": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
+    "agx_ntt_plain_scale_down": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
@@ -399,6 +405,11 @@ class Plan:
         the plaintext modulus t: BFV's divide-and-return in one call"""
         return Basis.with_quotient(self, b_first, b_count, q_first, q_count, aux_prime, t)
 
+    def plain(self, q_first, q_count, gamma_prime, t):
+        """Plain(self, ...): BFV's plaintext boundary for Q = primes [q_first, q_first + q_count), the auxiliary prime gamma_prime outside Q and the
+        plaintext modulus t in [2, 2^62): scale_up, lift and scale_down"""
+        return Plain(self, q_first, q_count, gamma_prime, t)
+
     def inner_product(self, d_a, d_bhat, d_c, batch, terms, outputs=1, bhat_batch=None, stream=0):
         """c_o = sum_t a_t o bhat_{t,o} mod q in one launch: d_a [terms][P][batch][n], d_bhat [terms][outputs][P][bhat_batch][n], d_c
         [outputs][P][batch][n]; inputs in [0,4q), c fully reduced, out of place; bhat_batch: None = batch, or 1 (one key frame per prime)"""
@@ -569,6 +580,52 @@ class Basis:
     def close(self):
         if self._h:
             lib().agx_ntt_basis_destroy(self._h)
+            self._h = _vp(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Plain:
+    """BFV's plaintext boundary (agx_ntt_plain_*) on a plan: Q = primes [q_first, q_first + q_count), the auxiliary prime gamma = plan prime gamma_prime
+    outside Q, the plaintext modulus t in [2, 2^62).  `plan` is a Plan or a raw plan handle (one handle per DeviceGroup shard); it must outlive the handle,
+    and its device must be current here and at every call."""
+
+    def __init__(self, plan, q_first, q_count, gamma_prime, t):
+        self.plan = plan      # keeps a Plan alive
+        self._h = _vp(None)
+        handle = plan._h if isinstance(plan, Plan) else plan
+        _check(lib().agx_ntt_plain_create(ctypes.byref(self._h), handle, q_first, q_count, gamma_prime, t), "plain_create")
+
+    def info(self):
+        """(q_first, q_count, gamma_prime, t, launches_scale_down, launches_ntt_form): the ranges, t, and the kernel launches of a scale_down call and of a
+        FORM_NTT scale_up / lift call under the plan's current variant"""
+        v = [_u32(0) for _ in range(3)]
+        t, down, ntt = _u64(0), _int(0), _int(0)
+        _check(lib().agx_ntt_plain_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(t), ctypes.byref(down), ctypes.byref(ntt)), "plain_info")
+        return tuple(x.value for x in v) + (t.value, down.value, ntt.value)
+
+    def scale_up(self, d_m, d_out, batch, form=FORM_NTT, stream=0):
+        """d_m [batch][n], any words, m' = m mod t -> d_out [q_count][batch][n] = floor((2 D m' + t) / (2t)) mod q_i (D m' / t rounded, halves up), as
+        coefficients (FORM_COEFF) or transformed as Plan.forward writes it (FORM_NTT); out of place"""
+        _check(lib().agx_ntt_plain_scale_up(self._h, d_m, d_out, batch, form, stream), "plain_scale_up")
+
+    def lift(self, d_m, d_out, batch, form=FORM_NTT, stream=0):
+        """d_m [batch][n], any words -> d_out [q_count][batch][n]: the centred representative of m mod t (m' below ceil(t / 2), m' - t from there on)
+        modulo q_i, forms as scale_up; out of place"""
+        _check(lib().agx_ntt_plain_lift(self._h, d_m, d_out, batch, form, stream), "plain_lift")
+
+    def scale_down(self, d_x, d_m, d_scratch, batch, stream=0):
+        """the rounding of decryption: d_x [q_count][batch][n] in NTT form (reduced or lazy) -> d_m [batch][n] in [0, t): round(t X / D) mod t wherever the
+        fraction lies within 1/2 - q_count / gamma of an integer; d_scratch: q_count*batch*n words, or d_x itself (which is then overwritten)"""
+        _check(lib().agx_ntt_plain_scale_down(self._h, d_x, d_m, d_scratch, batch, stream), "plain_scale_down")
+
+    def close(self):
+        if self._h:
+            lib().agx_ntt_plain_destroy(self._h)
             self._h = _vp(None)
 
     def __del__(self):

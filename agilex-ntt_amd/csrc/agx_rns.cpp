@@ -1,6 +1,7 @@
 // agx_rns.cpp -- the RNS calls of include/agx_ntt.h: rescale, basis extension and ModDown, the inner products, the ring arithmetic on a range of the
 // plan's primes (add, sub, negate, add_galois, tensor, mul_add_galois: one streaming kernel each) and the key switch, whole, in two halves, and with its
-// second half in two (accumulate_decomposed: the weighted, accumulating inner product; keyswitch_mod_down).  Each of the others composes the
+// second half in two (accumulate_decomposed: the weighted, accumulating inner product; keyswitch_mod_down), and BFV's plaintext boundary (agx_ntt_plain_*:
+// scale_up, lift, scale_down, at the end of the file).  Each of the others composes the
 // plan's transforms (run_forward / run_inverse on views of its routes, plan_internal.hpp) with a coefficient-domain or fused kernel; plans, routes and
 // the transform calls themselves live in agx_ntt.cpp.
 #include <cstdlib>
@@ -711,6 +712,125 @@ int agx_ntt_keyswitch_apply(const agx_ntt_keyswitch* ks, const uint64_t* d_chat,
     // the two halves on the three parts of the one scratch, with g = 1: the un-gathered inner product
     if (int rc = keyswitch_decompose_steps(ks, d_chat, d_scratch + part.ext, d_scratch + part.coeff, batch, stream)) return rc;
     return keyswitch_apply_steps(ks, d_scratch + part.ext, d_keyhat, d_out, d_scratch + part.acc, batch, 1, stream);
+}
+
+}  // extern "C"
+
+// ---- agx_ntt_plain_*: BFV's plaintext boundary (include/agx_ntt.h has the contract, plain_arith.hpp the formulas) ----
+
+// A plaintext boundary on the current device from its image: the buffers, then the view every call hands to its kernel
+static int instantiate_plain(agx_ntt_plain** out, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count, uint32_t gamma_prime, uint64_t t, const plain_image& img) {
+    std::unique_ptr<agx_ntt_plain> p(new (std::nothrow) agx_ntt_plain);
+    if (!p) return AGX_ERR_ALLOC;
+    p->plan = plan, p->gamma_prime = gamma_prime;
+    std::vector<prime_consts> sc(plan->consts.begin() + q_first, plan->consts.begin() + q_first + q_count);
+    for (uint32_t i = 0; i < q_count; ++i) sc[i].n_inv = img.sn[i].w, sc[i].n_inv_p = img.sn[i].p, sc[i].w1n = img.sw[i].w, sc[i].w1n_p = img.sw[i].p;
+    int rc = AGX_OK;
+    auto put = [&](device_buf<ulonglong2>& to, const std::vector<shoup_pair>& pairs) { if (rc == AGX_OK) rc = upload_pairs(to, pairs); };
+    put(p->d_up, img.up), put(p->d_one, img.one), put(p->d_row_t, img.row_t), put(p->d_row_g, img.row_g);
+    if (rc == AGX_OK) rc = p->d_src_consts.upload(sc);
+    if (rc) return rc;
+    plain_view& v = p->view;
+    v.up = p->d_up, v.one = p->d_one, v.row_t = p->d_row_t, v.row_g = p->d_row_g;
+    v.t = t, v.h = img.h, v.one_p = img.one_t.p, v.d = img.d_t.w, v.dp = img.d_t.p;
+    v.gamma = plan->moduli[gamma_prime], v.g = img.g_t.w, v.gp = img.g_t.p;
+    v.q_first = q_first, v.q_count = q_count;
+    *out = p.release();
+    return AGX_OK;
+}
+
+// agx_ntt_plain_scale_up and _lift: one statement of the rules, in extend_call's order.  Out of place only: d_out's L slabs touch d_m nowhere.
+static int plain_encode_call(const agx_ntt_plain* h, bool lift, const uint64_t* d_m, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    if (!h || !d_m || !d_out) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = h->plan;
+    if (out_form != AGX_FORM_COEFF && out_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    const plain_view& cv = h->view;
+    const uint32_t L = cv.q_count;
+    if (!aligned8(d_m) || !aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of m ([1][batch][n]) and out ([L][batch][n]) alike
+    if (!dense_fits(plan->n, L, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t slab = batch * plan->n;
+    if (ranges_touch(addr(d_m), slab, addr(d_out), L * slab)) return AGX_ERR_BAD_ARGUMENT;
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AGX_HIP(launch_plain_encode(plan->routes.forward, cv, lift, d_m, d_out, batch, s));
+    // the plan's forward on the view of Q, in place
+    if (out_form == AGX_FORM_NTT) AGX_HIP(run_forward(prime_range(forward_route(plan, batch), cv.q_first, cv.q_first + L), d_out, d_out, fl, s));
+    return AGX_OK;
+}
+
+extern "C" {
+
+// The rules in their order, agx_ntt_basis_create_aux's: NULL; the range and gamma's place, a bad argument; the plan; two moduli of Q that share a factor, gamma
+// sharing one with a modulus of Q, a bad modulus; t outside [2, 2^62), a bad argument; t sharing a factor with some q_i, then with gamma, a bad modulus.
+int agx_ntt_plain_create(agx_ntt_plain** h, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count, uint32_t gamma_prime, uint64_t t) {
+    if (!h) return AGX_ERR_NULL_POINTER;
+    *h = nullptr;
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes;
+    if (q_count == 0 || q_count > AGX_BASIS_MAX_SRC || q_count > P || q_first > P - q_count) return AGX_ERR_BAD_ARGUMENT;
+    if (gamma_prime >= P || (gamma_prime >= q_first && gamma_prime - q_first < q_count)) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    return guarded([&]() -> int {
+        std::vector<uint64_t> n_inv(q_count), w1n(q_count);
+        for (uint32_t i = 0; i < q_count; ++i) n_inv[i] = plan->consts[q_first + i].n_inv, w1n[i] = plan->consts[q_first + i].w1n;
+        plain_image img;
+        switch (prepare_plain_image(img, plain_request{&plan->moduli[q_first], q_count, n_inv.data(), w1n.data(), plan->moduli[gamma_prime], t})) {
+            case plain_fault::none: return instantiate_plain(h, plan, q_first, q_count, gamma_prime, t, img);
+            case plain_fault::t_range: return AGX_ERR_BAD_ARGUMENT;
+            default: return AGX_ERR_BAD_MODULUS;
+        }
+    });
+}
+
+int agx_ntt_plain_destroy(agx_ntt_plain* h) {
+    delete h;      // the device memory goes with its owners
+    return AGX_OK;
+}
+
+int agx_ntt_plain_info(const agx_ntt_plain* h, uint32_t* q_first, uint32_t* q_count, uint32_t* gamma_prime, uint64_t* t, int* launches_scale_down, int* launches_ntt_form) {
+    if (!h) return AGX_ERR_NULL_POINTER;
+    if (q_first) *q_first = h->view.q_first;
+    if (q_count) *q_count = h->view.q_count;
+    if (gamma_prime) *gamma_prime = h->gamma_prime;
+    if (t) *t = h->view.t;
+    if (launches_scale_down) *launches_scale_down = inverse_launches(h->plan) + 1;      // the scaled inverse of the Q slabs, then the streaming kernel
+    if (launches_ntt_form) *launches_ntt_form = 1 + forward_launches(h->plan);           // the coefficient-form launch, then the plan's forward on Q
+    return AGX_OK;
+}
+
+int agx_ntt_plain_scale_up(const agx_ntt_plain* h, const uint64_t* d_m, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    return plain_encode_call(h, false, d_m, d_out, batch, out_form, stream);
+}
+
+int agx_ntt_plain_lift(const agx_ntt_plain* h, const uint64_t* d_m, uint64_t* d_out, uint64_t batch, int out_form, void* stream) {
+    return plain_encode_call(h, true, d_m, d_out, batch, out_form, stream);
+}
+
+// The rounding of decryption: the scaled inverse of the Q slabs into the scratch, ONE streaming kernel.  agx_ntt_basis_quotient's rules in its order.
+int agx_ntt_plain_scale_down(const agx_ntt_plain* h, const uint64_t* d_x, uint64_t* d_m, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!h || !d_x || !d_m || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = h->plan;
+    if (int rc = check_plan(plan)) return rc;
+    const plain_view& cv = h->view;
+    const uint32_t L = cv.q_count;
+    if (!aligned8(d_x) || !aligned8(d_m) || !aligned8(d_scratch) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of x and the scratch ([L][batch][n]) and of m ([1][batch][n]) alike
+    if (!dense_fits(plan->n, L, batch)) return AGX_ERR_BAD_ARGUMENT;
+    // the scratch IS x (the inverse then runs in place, as agx_ntt_inverse may) or touches none of it; m touches neither
+    const uint64_t slab = (uint64_t)fl.prime_stride;
+    if (d_scratch != d_x && ranges_touch(addr(d_scratch), L * slab, addr(d_x), L * slab)) return AGX_ERR_BAD_ARGUMENT;
+    if (ranges_touch(addr(d_m), slab, addr(d_x), L * slab) || ranges_touch(addr(d_m), slab, addr(d_scratch), L * slab)) return AGX_ERR_BAD_ARGUMENT;
+    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // scratch <- y_i = INTT_i(x_i) gamma t Q_i^-1 mod q_i in [0, q_i): the plan's inverse on the view of Q, its last-stage constants the handle's
+    route scaled = prime_range(plan->routes.inverse, cv.q_first, cv.q_first + L);
+    scaled.consts = h->d_src_consts;
+    AGX_HIP(run_inverse(scaled, d_x, nullptr, d_scratch, fl, s));
+    AGX_HIP(launch_plain_scale_down(plan->routes.forward, cv, d_scratch, d_m, batch, s));
+    return AGX_OK;
 }
 
 }  // extern "C"

@@ -199,4 +199,42 @@ basis_fault prepare_basis_image(basis_image& img, const basis_request& rq) {
     return basis_fault::none;
 }
 
+plain_fault prepare_plain_image(plain_image& img, const plain_request& rq) {
+    const uint32_t L = rq.L;
+    const uint64_t t = rq.t, gamma = rq.gamma;
+    auto neg = [](uint64_t v, uint64_t q) { return v ? q - v : 0; };
+    img = plain_image{};
+    std::vector<uint64_t> qinv(L);      // Q_i^-1 mod q_i
+    for (uint32_t i = 0; i < L; ++i)
+        if (!inv_mod_euclid(product_mod(rq.q, L, i, rq.q[i]), rq.q[i], &qinv[i])) return plain_fault::source;
+    for (uint32_t i = 0; i < L; ++i) {
+        uint64_t w = 0;
+        if (!inv_mod_euclid(rq.q[i] % gamma, gamma, &w)) return plain_fault::gamma;
+        img.row_g.push_back(shoup_pair::of(neg(w, gamma), gamma));
+    }
+    if (t < 2 || t >= (1ull << 62)) return plain_fault::t_range;
+    for (uint32_t i = 0; i < L; ++i) {
+        const uint64_t q = rq.q[i];
+        uint64_t tinv = 0;
+        if (!inv_mod_euclid(t % q, q, &tinv)) return plain_fault::t_source;
+        const uint64_t scale = mul_mod(mul_mod(gamma % q, t % q, q), qinv[i], q);      // gamma t Q_i^-1
+        img.up.push_back(shoup_pair::of(tinv, q));
+        img.one.push_back(shoup_pair::of(1, q));
+        img.sn.push_back(shoup_pair::of(mul_mod(rq.n_inv[i], scale, q), q));
+        img.sw.push_back(shoup_pair::of(mul_mod(rq.w1n[i], scale, q), q));
+    }
+    uint64_t g = 0;
+    if (!inv_mod_euclid(gamma % t, t, &g)) return plain_fault::t_gamma;
+    for (uint32_t i = 0; i < L; ++i) {
+        uint64_t w = 0;
+        if (!inv_mod_euclid(rq.q[i] % t, t, &w)) return plain_fault::t_source;      // gcd(q_i, t) = 1 was found above: not reached
+        img.row_t.push_back(shoup_pair::of(neg(mul_mod(w, g, t), t), t));
+    }
+    img.d_t = shoup_pair::of(product_mod(rq.q, L, L, t), t);
+    img.one_t = shoup_pair::of(1, t);
+    img.g_t = shoup_pair::of(g, t);
+    img.h = t >> 1;
+    return plain_fault::none;
+}
+
 }  // namespace agx

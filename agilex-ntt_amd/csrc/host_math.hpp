@@ -110,4 +110,41 @@ enum class basis_fault {
 };
 basis_fault prepare_basis_image(basis_image& img, const basis_request& rq);
 
+// What a plaintext boundary (agx_ntt_plain_*) is asked for: Q = the moduli q[0 .. L), every one odd, > 1 and < 2^62, the auxiliary modulus gamma of the same
+// kind, the plaintext modulus t in [2, 2^62) -- even, a power of two, composite or above every q[i] alike -- and the two last-stage constants of an inverse
+// transform per q[i], as a basis_request carries them.
+struct plain_request {
+    const uint64_t* q;
+    uint32_t L;
+    const uint64_t *n_inv, *w1n;      // [L], both below q[i]
+    uint64_t gamma, t;
+};
+
+// Everything such a handle keeps on the device or hands to its kernels, built once on the host (csrc/plain_arith.hpp has the formulas).  With D = prod q[i]
+// and Q_i = D / q[i], every pair {word, its quotient for the modulus the word is reduced by}:
+struct plain_image {
+    std::vector<shoup_pair> up;        // [L] t^-1 mod q_i                                        (scale_up)
+    std::vector<shoup_pair> one;       // [L] 1 mod q_i                                           (lift)
+    // [L]: n_inv[i] gamma t Q_i^-1 mod q_i and w1n[i] gamma t Q_i^-1 mod q_i, the last stage's constants scaled so that the inverse of the Q slabs writes
+    // y_i = a_i gamma t Q_i^-1 mod q_i itself, as basis_image::sn, sw do for ModDown
+    std::vector<shoup_pair> sn, sw;
+    std::vector<shoup_pair> row_t;     // [L] -q_i^-1 gamma^-1 mod t  (= -Q_i D^-1 gamma^-1)      (scale_down)
+    std::vector<shoup_pair> row_g;     // [L] -q_i^-1 mod gamma       (= -Q_i D^-1)               (scale_down)
+    shoup_pair d_t = {0, 0};           // D mod t
+    shoup_pair one_t = {0, 0};         // 1 mod t: its quotient floor(2^64 / t) reduces any 64-bit word modulo t
+    shoup_pair g_t = {0, 0};           // gamma^-1 mod t
+    uint64_t h = 0;                    // floor(t / 2)
+};
+
+// Which rule refused a request, the first in this order; nothing is promised about the image then.
+enum class plain_fault {
+    none,
+    source,      // two moduli of Q share a factor (for primes: are equal)
+    gamma,       // gamma shares a factor with a modulus of Q (for primes: equals one)
+    t_range,     // t < 2 or t >= 2^62: the Shoup products modulo t need 2t < 2^64 and their sums 4t (csrc/bfv_conv_arith.hpp states the bound for its moduli)
+    t_source,    // t and some q_i share a factor (for a prime q_i: q_i | t): t has no inverse modulo q_i, D none modulo t
+    t_gamma,     // t and gamma share a factor (for a prime gamma: gamma | t)
+};
+plain_fault prepare_plain_image(plain_image& img, const plain_request& rq);
+
 }  // namespace agx

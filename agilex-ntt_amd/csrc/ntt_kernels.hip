@@ -18,6 +18,7 @@
 #include "weighted_kernels.hpp"        // agx_ntt_keyswitch_accumulate_decomposed / agx_ntt_mul_add_galois
 #include "automorphism_kernels.hpp"    // agx_ntt_automorphism
 #include "basis_coeff_kernels.hpp"     // the coefficient-domain steps of agx_ntt_basis_extend / _extend_exact / _extend_mont / _quotient / _mod_down
+#include "plain_kernels.hpp"           // agx_ntt_plain_scale_up / _lift / _scale_down
 
 #include <algorithm>
 #include <cstdlib>
@@ -562,6 +563,20 @@ hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint6
             return launch_stream(&moddown_coeff_round_kernel<smax>, per_prime, 1, s, out, y, pv.consts + bv.dst_first, bv.down_mat, bv.dall, bv.src_count, bv.dst_count,
                                  per_prime, bv.round_src, bv.round_dst);
         return launch_stream(&moddown_coeff_kernel<smax>, per_prime, 1, s, out, y, pv.consts + bv.dst_first, bv.down_mat, bv.dall, bv.src_count, bv.dst_count, per_prime);
+    });
+}
+
+// The plaintext boundary: one thread per (frame, coefficient), no slots; the scale-down on its source capacity as the basis kernels above
+hipError_t launch_plain_encode(const plan_view& pv, const plain_view& cv, bool lift, const uint64_t* m, uint64_t* out, uint64_t batch, hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    return launch_stream(lift ? &plain_encode_kernel<true> : &plain_encode_kernel<false>, per_prime, 1, s, m, out, pv.consts + cv.q_first, lift ? cv.one : cv.up, cv.t, cv.h,
+                         cv.one_p, cv.d, cv.dp, cv.q_count, per_prime);
+}
+
+hipError_t launch_plain_scale_down(const plan_view& pv, const plain_view& cv, const uint64_t* y, uint64_t* m, uint64_t batch, hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    return with_smax(cv.q_count, [&](auto smax) {
+        return launch_stream(&plain_scale_down_kernel<smax>, per_prime, 1, s, y, m, cv.row_t, cv.row_g, cv.t, cv.gamma, cv.g, cv.gp, cv.q_count, per_prime);
     });
 }
 

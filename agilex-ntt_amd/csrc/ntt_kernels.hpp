@@ -50,6 +50,19 @@ struct aux_view {
     aux_set exact, mont;
 };
 
+// agx_ntt_plain_*: what a plaintext boundary (plan, Q = L primes from q_first, the auxiliary prime gamma, the plaintext modulus t) keeps on the device, and
+// its scalars (plain_arith.hpp has the formulas).  Every pair is {word, its precomputed quotient for the modulus the word is reduced by}.
+struct plain_view {
+    const ulonglong2* up = nullptr;      // [L] {t^-1 mod q_i, quotient}                       (scale_up)
+    const ulonglong2* one = nullptr;     // [L] {1, floor(2^64 / q_i)}                         (lift)
+    const ulonglong2* row_t = nullptr;   // [L] {-q_i^-1 gamma^-1 mod t, quotient}             (scale_down)
+    const ulonglong2* row_g = nullptr;   // [L] {-q_i^-1 mod gamma, quotient}                  (scale_down)
+    uint64_t t = 0, h = 0, one_p = 0;    // h = floor(t / 2); one_p = floor(2^64 / t): the quotient of the constant 1 modulo t
+    uint64_t d = 0, dp = 0;              // D mod t and its quotient
+    uint64_t gamma = 0, g = 0, gp = 0;   // gamma; gamma^-1 mod t and its quotient
+    uint32_t q_first = 0, q_count = 0;
+};
+
 struct rb_entry;   // one configuration of the kernel registry (rb_registry.hpp): static storage, valid for the life of the library
 
 // device-side view of a plan
@@ -160,6 +173,12 @@ hipError_t launch_basis_quotient(const plan_view& pv, const basis_view& bv, cons
 // [0,q_i) as the scaled inverse of the source slabs left them.  pv: a view of the WHOLE plan (only its constants are read).  One launch.  The matrix is
 // bv.down_mat; round: AGX_RESCALE_ROUND, with bv.round_src and bv.round_dst (moddown_arith.hpp).
 hipError_t launch_moddown_coeff(const plan_view& pv, const basis_view& bv, uint64_t* out, const uint64_t* y, uint64_t batch, bool round, hipStream_t s);
+// agx_ntt_plain_scale_up (lift = false) and agx_ntt_plain_lift in coefficient form: m dense [batch][n], any words -> out dense [L][batch][n], slab i under
+// plan prime q_first + i, fully reduced (plain_arith.hpp).  pv: a view of the WHOLE plan (only its constants are read); out touches m nowhere.  One launch.
+hipError_t launch_plain_encode(const plan_view& pv, const plain_view& cv, bool lift, const uint64_t* m, uint64_t* out, uint64_t batch, hipStream_t s);
+// the coefficient-domain step of agx_ntt_plain_scale_down: y dense [L][batch][n], y_i in [0, q_i) as the scaled inverse of the Q slabs left them -> m dense
+// [batch][n] in [0, t).  m touches y nowhere.  One launch.
+hipError_t launch_plain_scale_down(const plan_view& pv, const plain_view& cv, const uint64_t* y, uint64_t* m, uint64_t batch, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

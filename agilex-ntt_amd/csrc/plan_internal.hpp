@@ -150,6 +150,18 @@ struct agx_ntt_basis {
     agx::device_buf<ulonglong2> d_quot_mat;      // [T][S + 1]
 };
 
+// agx_ntt_plain_*: the constants of one plaintext boundary (plan, Q, gamma, t) on the plan's device, and nothing of the plan but a pointer, as a basis: the
+// plan outlives the handle, agx_ntt_plan_set_variant between calls stays legal.  Made from a plain_image (host_math.hpp, whose fields say what each buffer
+// holds) by one function of agx_rns.cpp, which also fills the view, once.  d_src_consts: the plan's prime_consts of the Q primes with the last-stage factors
+// replaced by the image's sn, sw, as a basis' d_src_consts: the plan's inverse on the view of Q with `consts` pointing here writes the y_i of scale_down.
+struct agx_ntt_plain {
+    const agx_ntt_plan* plan = nullptr;
+    uint32_t gamma_prime = 0;
+    agx::device_buf<ulonglong2> d_up, d_one, d_row_t, d_row_g;
+    agx::device_buf<agx::prime_consts> d_src_consts;
+    agx::plain_view view;
+};
+
 // agx_ntt_keyswitch_*: the shape and the bases of one hybrid key switch, and nothing of the plan but a pointer (as a basis: the plan outlives the
 // handle, agx_ntt_plan_set_variant between calls stays legal).  ModUp: one basis per digit with every active prime as a target when the special
 // primes follow Q directly; two per digit, targets Q and then targets P, when they lie apart (a basis names one contiguous range).  One ModDown

@@ -657,6 +657,62 @@ AGX_API int agx_ntt_keyswitch_accumulate_decomposed(const agx_ntt_keyswitch* ks,
                                                     uint64_t weight_batch, uint64_t* d_acc, uint64_t batch, uint32_t galois_elt, int accumulate, void* stream);
 AGX_API int agx_ntt_keyswitch_mod_down(const agx_ntt_keyswitch* ks, uint64_t* d_acc, uint64_t* d_out, uint64_t batch, void* stream);
 
+/* BFV's plaintext boundary on the device: scaling a plaintext modulo t up into Q (encryption, add-plain), its centred lift (multiply-plain), and the rounding
+ * round(t X / Q) mod t of decryption in its exact integer RNS form through ONE auxiliary prime gamma (BEHZ: Bajard, Eynard, Hasan, Zucca, SAC 2016, section 3).
+ * With them both ends of the BFV pipeline run on library calls at any level of one plan ("BFV encryption, plain operands and decryption").
+ * Notation.  Q is the plan primes [q_first, q_first + L), L = q_count <= AGX_BASIS_MAX_SRC = 16; D their product, Q_i = D / q_i; gamma the modulus of plan prime
+ * gamma_prime, outside Q (in a BFV multiplication plan any prime of B serves); t the plaintext modulus, 2 <= t < 2^62 -- even, a power of two, composite or above
+ * every q_i alike; h = floor(t / 2); centre_gamma(a) = a for a <= (gamma - 1) / 2 and a - gamma above.  All three calls are deterministic integer formulas, exact
+ * against big-integer arithmetic.
+ *   scale_up    d_m dense [batch][n], ANY 64-bit words, m' = m mod t.  Per coefficient U = floor((2 D m' + t) / (2t)) (D m' / t rounded, halves up) and
+ *               out_i = U mod q_i, fully reduced.  d_out dense [L][batch][n], slab i under plan prime q_first + i; AGX_FORM_COEFF: natural order,
+ *               AGX_FORM_NTT: NTT_i(out_i) exactly as agx_ntt_forward of the plan writes it.  On the device, with rho = ((D mod t) m' + h) mod t:
+ *               U = (D m' + h - rho) / t and, D being 0 modulo q_i, U mod q_i = (h - rho) t^-1 mod q_i: no wide division (csrc/plain_arith.hpp).
+ *   lift        operands and forms as scale_up: out_i = m' mod q_i for m' < ceil(t / 2), (m' - t) mod q_i from there on: the centred representative.
+ *   scale_down  d_x dense [L][batch][n] in NTT form as agx_ntt_forward / _forward_lazy write it, reduced or lazy; a_i its coefficient form.  Per coefficient
+ *                 y_i = a_i' (gamma t Q_i^-1 mod q_i) mod q_i in [0, q_i),    V = sum_i y_i Q_i  (an integer: V = |gamma t X|_D + u D, 0 <= u < L),
+ *                 s_t = (-V D^-1) mod t,   s_gamma = (-V D^-1) mod gamma,   c = centre_gamma(s_gamma),   m = (s_t - c) gamma^-1 mod t  in [0, t).
+ *               d_m dense [batch][n].  The formula is the contract and is defined for every input.  Property: write t X / D = R + f with R an integer, for ANY
+ *               integer X with those residues; then m = R mod t whenever |f| <= 1/2 - L / gamma.  So for a BFV phase X = c_0 + c_1 s (+ c_2 s^2), m is the
+ *               message whenever the noise leaves that margin: with a 50- to 60-bit gamma the margin is 1/2 to within 2^-45.
+ *               d_scratch: L batch n words; it may be exactly d_x, which is then given up (as agx_ntt_basis_mod_down and agx_ntt_basis_quotient allow);
+ *               otherwise it touches d_x nowhere and d_x is left unchanged.  d_m touches neither.
+ * Handle.  It belongs to one plan, as a basis does: it holds constants and a pointer to the plan, which must outlive it; the plan's device must be current at
+ * creation and at every call; agx_ntt_plan_set_variant between calls stays legal.  The handle type is named by its struct tag, `struct agx_ntt_plain`.
+ *   create : NULL: AGX_ERR_NULL_POINTER; q_count == 0 or above 16, a range past P, gamma_prime >= P or inside the range: AGX_ERR_BAD_ARGUMENT; two equal
+ *            moduli among Q, gamma equal to a modulus of Q: AGX_ERR_BAD_MODULUS; t < 2 or t >= 2^62: AGX_ERR_BAD_ARGUMENT (the per-word products by t's
+ *            constants are Shoup products, which need 2t < 2^64: the bound csrc/bfv_conv_arith.hpp states for its moduli); q_i | t for some i (t needs an
+ *            inverse modulo each q_i, D one modulo t), then gamma | t: AGX_ERR_BAD_MODULUS.  On any failure the out-pointer is cleared.
+ *   destroy: NULL is fine.
+ *   info   : any out-pointer may be NULL; under the plan's CURRENT variant launches_scale_down = the plan's inverse launches + 1 and launches_ntt_form = 1 +
+ *            the plan's forward launches.  AGX_FORM_COEFF is ONE launch on every plan.
+ * Call rules of all three, agx_ntt_basis_extend_exact's / agx_ntt_basis_quotient's status order: a NULL pointer: AGX_ERR_NULL_POINTER; an unknown form; the
+ * plan's device not current; a pointer not 8-byte aligned; a batch past the grid limit or an extent past 2^60 words; an overlap rule broken (scale_up and lift
+ * are OUT OF PLACE ONLY; scale_down as above): AGX_ERR_BAD_ARGUMENT, nothing written; scale_down on a plan without inverse tables: AGX_ERR_NO_INVERSE;
+ * batch == 0: AGX_OK, nothing launched.  Ranges that meet end to end do not touch.  Asynchronous on `stream`; they allocate and synchronise nothing and touch
+ * no plan state (capturable into a hipGraph).
+ * Route, one for every plan.  scale_up / lift: ONE streaming kernel, one thread per coefficient (one product modulo t, then one signed Shoup product per
+ * prime), 8 (1 + L) bytes per coefficient; AGX_FORM_NTT adds the plan's forward on the view of Q, in place.  scale_down: (1) the plan's inverse on the view of
+ * Q into the scratch with n^-1 gamma t Q_i^-1 in the place of n^-1 -- the mechanism of agx_ntt_basis_mod_down's first launch: it writes the y_i itself --,
+ * (2) ONE streaming kernel, one thread per coefficient, no LDS, no barrier: the two sums through the rows -q_i^-1 gamma^-1 mod t and -q_i^-1 mod gamma
+ * (-Q_i D^-1 = -q_i^-1; gamma^-1 is folded into the t row), the centring, one Shoup product by gamma^-1 mod t, one word stored: 8 (L + 1) bytes per coefficient.
+ * Measured (profiles/r17_plain_boundary.md, tools/run_op.py --op plain; 60-bit primes, t = 65537, L = 2, 4, 8, n = 4096 with 4,096 frames per prime and n = 16384 with 1,024, beside a
+ * device copy of 8 (L + 1) bytes per coefficient and the plan's transforms alone on the same slabs): scale_up and lift in coefficient form take 0.96 ... 1.12 of the copy's time (L = 4
+ * at n = 4096: 126 and 124 us against 125); in NTT form 0.96 ... 1.03 of the plan's forward plus the copy (345 us against 222 + 125).  scale_down takes 1.42 ... 1.52 of the plan's
+ * inverse on the same slabs (466 us against 318); less the inverse alone that is 1.12 ... 1.24 of the copy of its kernel's bytes, a difference of two medians: near its traffic, not
+ * at it; which of its 2L + 1 products accounts for the rest was not measured.  agx_ntt_basis_quotient and agx_ntt_keyswitch_apply beside the parent commit's library in the same
+ * session: 753 / 752 against 747 / 752 us and 3302 / 3294 against 3309 / 3309 us at n = 4096; the spreads overlap in all eight pairs.
+ * Out of scope: BGV decryption (an exact centred Q -> t conversion); CKKS decoding; sampling of randomness (the caller supplies a and e); group forms (one
+ * handle per shard, as for a basis); a fused NTT-form scale_up. */
+struct agx_ntt_plain;
+AGX_API int agx_ntt_plain_create(struct agx_ntt_plain** h, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count, uint32_t gamma_prime, uint64_t t);
+AGX_API int agx_ntt_plain_destroy(struct agx_ntt_plain* h);
+AGX_API int agx_ntt_plain_info(const struct agx_ntt_plain* h, uint32_t* q_first, uint32_t* q_count, uint32_t* gamma_prime, uint64_t* t, int* launches_scale_down,
+                               int* launches_ntt_form);
+AGX_API int agx_ntt_plain_scale_up(const struct agx_ntt_plain* h, const uint64_t* d_m, uint64_t* d_out, uint64_t batch, int out_form, void* stream);
+AGX_API int agx_ntt_plain_lift(const struct agx_ntt_plain* h, const uint64_t* d_m, uint64_t* d_out, uint64_t batch, int out_form, void* stream);
+AGX_API int agx_ntt_plain_scale_down(const struct agx_ntt_plain* h, const uint64_t* d_x, uint64_t* d_m, uint64_t* d_scratch, uint64_t batch, void* stream);
+
 /* synthetic coefficients generated on the device: frame (p,b) element i =
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */
 AGX_API int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly,

@@ -6,6 +6,7 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op moddown --src S --dst T [--only {all,fused,generic,parent,modes} --mode {floor,round} --plain T --reps 7 ...]   (agx_ntt_basis_mod_down: its two routes and the parent's inverse + extend)
        python3 tools/run_op.py --op bfvconv --src S --dst T [--only {all,exact,mont,parent,copy} --reps 7 ...]   (agx_ntt_basis_extend_exact / _mont, coefficient form, beside agx_ntt_basis_extend into T + 1 targets and a copy of the model's bytes)
        python3 tools/run_op.py --op quotient --qcount L --src K [--only {all,quotient,composition,copy} --reps 7 ...]   (agx_ntt_basis_quotient beside the six-call composition it replaces and a copy of its model bytes)
+       python3 tools/run_op.py --op plain --qcount L [--reps 7 ...]   (agx_ntt_plain_scale_down, _scale_up and _lift in both forms beside a copy of each call's model bytes and the plan's inverse / forward alone)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
        python3 tools/run_op.py --op ring --kind {add,sub,negate,add_galois,tensor} [--primes 6 --first 0 --count 4 --galois G --only {all,ring,copy,parent} --reps 7 ...]   (a ring call beside a copy of its model bytes and what it replaces)
        python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
@@ -28,7 +29,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient", "plain"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -78,6 +79,8 @@ if args.op in ("keyswitch", "hoist", "dhoist"):
     args.primes = args.pfirst + args.pcount
 if args.op == "quotient":
     args.primes = args.qcount + args.src + 1      # Q = [0, L), B = [L, L + K), the auxiliary prime L + K
+if args.op == "plain":
+    args.primes = args.qcount + 1      # Q = [0, L), gamma = L
 args.only = args.only or ("all" if args.op in ("moddown", "bfvconv", "quotient") else "both")
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
 if args.variant is not None:
@@ -382,6 +385,68 @@ def run_quotient():
         json.dump({"us": times, "launches": args.launches, "kernel_launches": launches, "model_bytes": 16.0 * half}, open(args.report, "w"))
     for h in (basis, fast_floor, to_q, plan_bsk):
         h.close()
+    plan.close()
+
+
+def run_plain():
+    """agx_ntt_plain_scale_down (the scratch the operand), _scale_up and _lift in both forms with Q = [0, L) and gamma = plan prime L (--qcount L), t = 65537,
+    alternating in one process with the plan's inverse and forward alone on the same Q slabs (agx_ntt_inverse_range / agx_ntt_forward_range, in place) and
+    with a device copy of each call's model bytes: 8 (L + 1) per coefficient for the three streaming kernels (scale_down's, scale_up's and lift's coefficient
+    form).  scale_down overwrites its operand; any words are NTT-form words, so the groups run on what the last call left.  Prints us per call: median
+    (min ... max) of --reps groups of --launches calls; scale_down less the inverse alone and the NTT forms less the forward alone estimate the streaming
+    kernels where they cannot be timed apart."""
+    import statistics
+
+    L, t = args.qcount, 65537
+    words = args.batch * args.n
+    plain = plan.plain(0, L, L, t)
+    x = torch.empty(plan.num_primes * words, dtype=torch.int64, device="cuda")      # agx_ntt_fill_synthetic writes every slab of the plan, gamma's too; slabs [0, L) are read
+    out = torch.empty(L * words, dtype=torch.int64, device="cuda")
+    m, msg = (torch.empty(words, dtype=torch.int64, device="cuda") for _ in range(2))
+    plan.fill_synthetic(x.data_ptr(), args.batch, 0, 42, stream)
+    m.copy_(x[:words])      # any 64-bit words are plaintext words
+    half = (L + 1) * words // 2      # a copy reads and writes this many words: together the model's bytes of one streaming kernel
+    c_src, c_dst = (torch.empty(half, dtype=torch.int64, device="cuda") for _ in range(2))
+    p = x.data_ptr()
+
+    def scale_down():
+        plain.scale_down(p, msg.data_ptr(), p, args.batch, stream)
+
+    def inverse():
+        plan.inverse_range(p, p, args.batch, 0, L, stream)
+
+    def scale_up_coeff():
+        plain.scale_up(m.data_ptr(), out.data_ptr(), args.batch, agx.FORM_COEFF, stream)
+
+    def lift_coeff():
+        plain.lift(m.data_ptr(), out.data_ptr(), args.batch, agx.FORM_COEFF, stream)
+
+    def scale_up_ntt():
+        plain.scale_up(m.data_ptr(), out.data_ptr(), args.batch, agx.FORM_NTT, stream)
+
+    def lift_ntt():
+        plain.lift(m.data_ptr(), out.data_ptr(), args.batch, agx.FORM_NTT, stream)
+
+    def forward():
+        plan.forward_range(out.data_ptr(), out.data_ptr(), args.batch, 0, L, stream)
+
+    def copy():
+        c_dst.copy_(c_src)
+
+    times = _alternate([scale_down, inverse, scale_up_coeff, lift_coeff, scale_up_ntt, lift_ntt, forward, copy])
+    info = plain.info()
+    print(f"plain n={args.n} L={L} batch={args.batch} bits={args.bits} t={t} launches scale_down {info[4]} ntt form {info[5]}:")
+    for name, v in times.items():
+        print(f"  {name} {_fmt(v)} us")
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(f"  scale_down - inverse {med['scale_down'] - med['inverse']:.1f} us = {(med['scale_down'] - med['inverse']) / med['copy']:.3f} of the copy;  "
+          f"scale_up_coeff/copy {med['scale_up_coeff'] / med['copy']:.3f}  lift_coeff/copy {med['lift_coeff'] / med['copy']:.3f};  "
+          f"scale_down/inverse {med['scale_down'] / med['inverse']:.3f}  scale_up_ntt/(forward + copy) {med['scale_up_ntt'] / (med['forward'] + med['copy']):.3f}")
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "kernel_launches": {"scale_down": info[4], "ntt_form": info[5]}, "model_bytes": 16.0 * half}, open(args.report, "w"))
+    plain.close()
     plan.close()
 
 
@@ -905,6 +970,9 @@ if args.op == "bfvconv":
     sys.exit(0)
 if args.op == "quotient":
     run_quotient()
+    sys.exit(0)
+if args.op == "plain":
+    run_plain()
     sys.exit(0)
 slabs = [torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(args.slabs)]
 for i, s in enumerate(slabs):
