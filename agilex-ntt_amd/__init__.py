@@ -100,6 +100,9 @@ ABI = {
     "agx_ntt_plain_lift": (_int, [_vp, _vp, _vp, _u64, _int, _vp]),
     "agx_ntt_plain_scale_down": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "agx_ntt_fill_synthetic": (_int, [_vp, _vp, _u64, _u64, _u64, _vp]),
+    "agx_ntt_sample_uniform": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _u32, _u32, _vp]),
+    "agx_ntt_sample_ternary": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _u32, _u32, _int, _vp]),
+    "agx_ntt_sample_cbd": (_int, [_vp, _vp, _u64, _u32, _vp, _u64, _u64, _u32, _u32, _int, _vp]),
     "agx_ntt_find_primes": (_int, [_u32, _u32, _u32, _p64]),
     "agx_ntt_min_root": (_int, [_u64, _u32, _p64]),
     "agx_ntt_make_tables": (_int, [_u64, _u64, _u32, _p64, _p64]),
@@ -198,6 +201,16 @@ def _table_args(moduli, psi, tables):
     else:
         arrays = [moduli] + list(tables[:2]) + (list(tables[2:]) if len(tables) == 4 else [None, None])
     return [None if a is None else _np_ptr(np.ascontiguousarray(a, dtype=np.uint64)) for a in arrays]      # a pointer keeps its array alive
+
+
+def _key32(key):
+    """the 32 key bytes of a sampling call as a host buffer; None stays None (the library answers the NULL rule)"""
+    if key is None:
+        return None
+    key = bytes(key)
+    if len(key) != 32:
+        raise ValueError("a sampling key is 32 bytes")
+    return key
 
 
 def _out_array(out, count):
@@ -409,6 +422,23 @@ class Plan:
         """Plain(self, ...): BFV's plaintext boundary for Q = primes [q_first, q_first + q_count), the auxiliary prime gamma_prime outside Q and the
         plaintext modulus t in [2, 2^62): scale_up, lift and scale_down"""
         return Plain(self, q_first, q_count, gamma_prime, t)
+
+    def sample_uniform(self, key, nonce, d_out, batch, frame_first=0, prime_first=0, prime_count=None, stream=0):
+        """uniform words below q_i on the plan primes [prime_first, prime_first + prime_count) (None: all of the plan's), one launch: d_out
+        [prime_count][batch][n]; key: 32 bytes (the caller's seed, host memory), nonce: the 64-bit draw number, never reused under one key for one kind;
+        frame f of the call is frame frame_first + f of the draw, so split batches write what one call writes (ChaCha20 with rejection: include/agx_ntt.h)"""
+        _check(lib().agx_ntt_sample_uniform(self._h, _key32(key), nonce, d_out, batch, frame_first, *self._prime_range(prime_first, prime_count), stream), "sample_uniform")
+
+    def sample_ternary(self, key, nonce, d_out, batch, frame_first=0, prime_first=0, prime_count=None, form=FORM_NTT, stream=0):
+        """coefficients uniform in {-1, 0, +1}, the same value under every prime of the range, as sample_uniform; form: FORM_COEFF, or FORM_NTT = the
+        plan's forward on the range in place behind the draw"""
+        _check(lib().agx_ntt_sample_ternary(self._h, _key32(key), nonce, d_out, batch, frame_first, *self._prime_range(prime_first, prime_count), form, stream),
+               "sample_ternary")
+
+    def sample_cbd(self, key, nonce, eta, d_out, batch, frame_first=0, prime_first=0, prime_count=None, form=FORM_NTT, stream=0):
+        """centred-binomial coefficients of variance eta / 2 (1 <= eta <= 32; 21: sigma = 3.24), as sample_ternary"""
+        _check(lib().agx_ntt_sample_cbd(self._h, _key32(key), nonce, eta, d_out, batch, frame_first, *self._prime_range(prime_first, prime_count), form, stream),
+               "sample_cbd")
 
     def inner_product(self, d_a, d_bhat, d_c, batch, terms, outputs=1, bhat_batch=None, stream=0):
         """c_o = sum_t a_t o bhat_{t,o} mod q in one launch: d_a [terms][P][batch][n], d_bhat [terms][outputs][P][bhat_batch][n], d_c

@@ -1,7 +1,7 @@
 // agx_rns.cpp -- the RNS calls of include/agx_ntt.h: rescale, basis extension and ModDown, the inner products, the ring arithmetic on a range of the
 // plan's primes (add, sub, negate, add_galois, tensor, mul_add_galois: one streaming kernel each) and the key switch, whole, in two halves, and with its
 // second half in two (accumulate_decomposed: the weighted, accumulating inner product; keyswitch_mod_down), and BFV's plaintext boundary (agx_ntt_plain_*:
-// scale_up, lift, scale_down, at the end of the file).  Each of the others composes the
+// scale_up, lift, scale_down) and the samplers (agx_ntt_sample_*: one streaming kernel each, at the end of the file).  Each of the others composes the
 // plan's transforms (run_forward / run_inverse on views of its routes, plan_internal.hpp) with a coefficient-domain or fused kernel; plans, routes and
 // the transform calls themselves live in agx_ntt.cpp.
 #include <cstdlib>
@@ -831,6 +831,51 @@ int agx_ntt_plain_scale_down(const agx_ntt_plain* h, const uint64_t* d_x, uint64
     AGX_HIP(run_inverse(scaled, d_x, nullptr, d_scratch, fl, s));
     AGX_HIP(launch_plain_scale_down(plan->routes.forward, cv, d_scratch, d_m, batch, s));
     return AGX_OK;
+}
+
+}  // extern "C"
+
+// ---- agx_ntt_sample_*: ChaCha20 uniform, ternary and binomial sampling (include/agx_ntt.h has the definition, sample_arith.hpp the steps) ----
+
+// One statement of the three calls' rules, the ring calls' in their order: NULL; the range; the frame numbers (frame_first + batch <= 2^32, formed without
+// overflow); eta; the form; the plan's device; the pointer and the extent.  The key is HOST memory: its 32 bytes become eight little-endian words of the kernel
+// arguments, and nothing of it is kept.  NTT form: the coefficient launch, then the plan's forward on the range in place.
+static int sample_call(sample_kind kind, const agx_ntt_plan* plan, const uint8_t* key, uint64_t nonce, uint32_t eta, uint64_t* d_out, uint64_t batch, uint64_t frame_first,
+                       uint32_t prime_first, uint32_t prime_count, int out_form, void* stream) {
+    if (!plan || !key || !d_out) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes, n = plan->n;
+    if (prime_count == 0 || prime_count > P || prime_first > P - prime_count) return AGX_ERR_BAD_ARGUMENT;
+    constexpr uint64_t kFrames = (uint64_t)1 << 32;
+    if (batch > kFrames || frame_first > kFrames - batch) return AGX_ERR_BAD_ARGUMENT;
+    if (kind == SAMPLE_CBD && (eta < 1 || eta > 32)) return AGX_ERR_BAD_ARGUMENT;
+    if (out_form != AGX_FORM_COEFF && out_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;      // from here on batch n < 2^46
+    if (!dense_fits(n, prime_count, batch)) return AGX_ERR_BAD_ARGUMENT;
+    if (batch == 0) return AGX_OK;
+    uint32_t words[8];
+    for (int i = 0; i < 8; ++i) words[i] = (uint32_t)key[4 * i] | (uint32_t)key[4 * i + 1] << 8 | (uint32_t)key[4 * i + 2] << 16 | (uint32_t)key[4 * i + 3] << 24;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AGX_HIP(launch_sample(plan->routes.forward, kind, words, nonce, eta, d_out, batch, frame_first, prime_first, prime_count, s));
+    if (out_form == AGX_FORM_NTT) AGX_HIP(run_forward(prime_range(forward_route(plan, batch), prime_first, prime_first + prime_count), d_out, d_out, dense(plan, batch), s));
+    return AGX_OK;
+}
+
+extern "C" {
+
+int agx_ntt_sample_uniform(const agx_ntt_plan* plan, const uint8_t key[32], uint64_t nonce, uint64_t* d_out, uint64_t batch, uint64_t frame_first, uint32_t prime_first,
+                           uint32_t prime_count, void* stream) {
+    return sample_call(SAMPLE_UNIFORM, plan, key, nonce, 0, d_out, batch, frame_first, prime_first, prime_count, AGX_FORM_COEFF, stream);      // no form: uniform words are a uniform ring element in either
+}
+
+int agx_ntt_sample_ternary(const agx_ntt_plan* plan, const uint8_t key[32], uint64_t nonce, uint64_t* d_out, uint64_t batch, uint64_t frame_first, uint32_t prime_first,
+                           uint32_t prime_count, int out_form, void* stream) {
+    return sample_call(SAMPLE_TERNARY, plan, key, nonce, 0, d_out, batch, frame_first, prime_first, prime_count, out_form, stream);
+}
+
+int agx_ntt_sample_cbd(const agx_ntt_plan* plan, const uint8_t key[32], uint64_t nonce, uint32_t eta, uint64_t* d_out, uint64_t batch, uint64_t frame_first,
+                       uint32_t prime_first, uint32_t prime_count, int out_form, void* stream) {
+    return sample_call(SAMPLE_CBD, plan, key, nonce, eta, d_out, batch, frame_first, prime_first, prime_count, out_form, stream);
 }
 
 }  // extern "C"

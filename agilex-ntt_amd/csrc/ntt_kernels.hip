@@ -19,6 +19,7 @@
 #include "automorphism_kernels.hpp"    // agx_ntt_automorphism
 #include "basis_coeff_kernels.hpp"     // the coefficient-domain steps of agx_ntt_basis_extend / _extend_exact / _extend_mont / _quotient / _mod_down
 #include "plain_kernels.hpp"           // agx_ntt_plain_scale_up / _lift / _scale_down
+#include "sample_kernels.hpp"          // agx_ntt_sample_uniform / _ternary / _cbd
 
 #include <algorithm>
 #include <cstdlib>
@@ -578,6 +579,21 @@ hipError_t launch_plain_scale_down(const plan_view& pv, const plain_view& cv, co
     return with_smax(cv.q_count, [&](auto smax) {
         return launch_stream(&plain_scale_down_kernel<smax>, per_prime, 1, s, y, m, cv.row_t, cv.row_g, cv.t, cv.gamma, cv.g, cv.gp, cv.q_count, per_prime);
     });
+}
+
+// The samplers: one thread per cell of eight coefficients (a whole frame for n = 2 and 4); uniform over `count` slots, the small kinds walk their primes
+hipError_t launch_sample(const plan_view& pv, sample_kind kind, const uint32_t key[8], uint64_t nonce, uint32_t eta, uint64_t* out, uint64_t batch, uint64_t frame_first,
+                         uint32_t first, uint32_t count, hipStream_t s) {
+    sample_key k;
+    for (int i = 0; i < 8; ++i) k.w[i] = key[i];
+    const uint64_t cells = batch << (pv.log_n > 3 ? pv.log_n - 3 : 0);
+    const sample_shape g{pv.log_n, (uint32_t)frame_first, (uint32_t)nonce, (uint32_t)(nonce >> 32), cells, batch << pv.log_n};
+    const bool pairs = inner_pairs(out, out, out);
+    if (kind == SAMPLE_UNIFORM) return launch_stream(pairs ? &sample_uniform_kernel<true> : &sample_uniform_kernel<false>, cells, count, s, out, pv.consts, k, g, first);
+    auto small = [&](auto cbd) {
+        return launch_stream(pairs ? &sample_small_kernel<cbd, true> : &sample_small_kernel<cbd, false>, cells, 1, s, out, pv.consts + first, k, g, sample_eta_mask(eta), count);
+    };
+    return kind == SAMPLE_CBD ? small(std::true_type{}) : small(std::false_type{});
 }
 
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s) {

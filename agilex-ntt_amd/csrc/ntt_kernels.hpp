@@ -179,6 +179,12 @@ hipError_t launch_plain_encode(const plan_view& pv, const plain_view& cv, bool l
 // the coefficient-domain step of agx_ntt_plain_scale_down: y dense [L][batch][n], y_i in [0, q_i) as the scaled inverse of the Q slabs left them -> m dense
 // [batch][n] in [0, t).  m touches y nowhere.  One launch.
 hipError_t launch_plain_scale_down(const plan_view& pv, const plain_view& cv, const uint64_t* y, uint64_t* m, uint64_t batch, hipStream_t s);
+// agx_ntt_sample_uniform / _ternary / _cbd in coefficient form: out dense [count][batch][n], slab i under plan prime first + i, fully reduced; frame f of
+// the launch is frame frame_first + f of the draw (frame_first + batch <= 2^32).  key: the eight little-endian words of the caller's 32 bytes, copied into
+// the kernel arguments.  pv: a view of the WHOLE plan (only its constants are read).  One launch each; the 16-byte stores when out allows them.
+enum sample_kind { SAMPLE_UNIFORM, SAMPLE_TERNARY, SAMPLE_CBD };
+hipError_t launch_sample(const plan_view& pv, sample_kind kind, const uint32_t key[8], uint64_t nonce, uint32_t eta, uint64_t* out, uint64_t batch, uint64_t frame_first,
+                         uint32_t first, uint32_t count, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

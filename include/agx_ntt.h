@@ -702,7 +702,7 @@ AGX_API int agx_ntt_keyswitch_mod_down(const agx_ntt_keyswitch* ks, uint64_t* d_
  * inverse on the same slabs (466 us against 318); less the inverse alone that is 1.12 ... 1.24 of the copy of its kernel's bytes, a difference of two medians: near its traffic, not
  * at it; which of its 2L + 1 products accounts for the rest was not measured.  agx_ntt_basis_quotient and agx_ntt_keyswitch_apply beside the parent commit's library in the same
  * session: 753 / 752 against 747 / 752 us and 3302 / 3294 against 3309 / 3309 us at n = 4096; the spreads overlap in all eight pairs.
- * Out of scope: BGV decryption (an exact centred Q -> t conversion); CKKS decoding; sampling of randomness (the caller supplies a and e); group forms (one
+ * Out of scope: BGV decryption (an exact centred Q -> t conversion); CKKS decoding; group forms (one
  * handle per shard, as for a basis); a fused NTT-form scale_up. */
 struct agx_ntt_plain;
 AGX_API int agx_ntt_plain_create(struct agx_ntt_plain** h, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count, uint32_t gamma_prime, uint64_t t);
@@ -717,6 +717,44 @@ AGX_API int agx_ntt_plain_scale_down(const struct agx_ntt_plain* h, const uint64
  * splitmix64(seed, p, first_poly + b, i) mod q_p, a pure function of its indices (bench / tests) */
 AGX_API int agx_ntt_fill_synthetic(const agx_ntt_plan* plan, uint64_t* d_out, uint64_t batch, uint64_t first_poly,
                            uint64_t seed, void* stream);
+
+/* Sampling: the randomness of an encryption or a key, drawn on the device from a 32-byte seed.  Three stateless calls on the plan primes
+ * [prime_first, prime_first + prime_count): uniform ring elements (a public `a`: ship the 32 bytes, not the words), ternary secrets and centred-binomial
+ * errors.  Exact -- no modulo bias -- and reproducible: a word depends only on (key, nonce, kind, prime index, frame, j), never on batch, launch shape or
+ * prime_first.  agx_ntt_fill_synthetic above stays what it is: splitmix64 modulo q, biased, for benchmarks and tests.
+ * d_out: dense [prime_count][batch][n], fully reduced, slab i under plan prime prime_first + i.  key: 32 bytes of HOST memory, the caller's seed from its
+ * operating system's generator; it is copied into the kernel arguments as eight words and nothing of it is kept after the call.  nonce: the caller's 64-bit
+ * draw number, NEVER reused under one key for one kind.  frame_first: the number of the call's first frame in the caller's numbering, so a batch split over
+ * several calls or several devices writes the words one call would write (there is no group form, as for a basis).  out_form (ternary, cbd): AGX_FORM_COEFF,
+ * or AGX_FORM_NTT = the coefficient launch followed by agx_ntt_forward_range in place on d_out; uniform has no form: uniform NTT-form words are a uniform
+ * ring element.
+ * The definition.  block(key, w12, w13, w14, w15) is the ChaCha20 block function of RFC 8439 section 2.3, 20 rounds: state words 0..3 the constants, 4..11
+ * the key (little-endian), 12..15 as given; o[0..15] its output; the eight 64-bit candidates of a block are c_i = o[2i] | o[2i+1] << 32.  Throughout
+ * w13 = F = frame_first + f, w14 = nonce & 0xffffffff, w15 = nonce >> 32.  A cell is eight consecutive coefficients of one frame: c = j >> 3, covering
+ * W = min(8, n - 8c) words (for n = 2 and 4 the one cell is the frame); w12 = tag << 16 | c << 4 | k with c < 4096 and k < 16.
+ *   uniform, plan prime P (its index in the plan, <= 65534): tag = P, k = the block counter 0..15.  mask = 2^bitlen(q) - 1.  Walk the blocks k = 0, 1, ... and
+ *     their candidates i = 0..7 in order; v = c_i & mask is accepted if v < q; the r-th accepted value is word 8c + r; stop when W are accepted.  After block
+ *     15 the words still open are written 0 (probability below 2^-90 at acceptance 1/2; acceptance is above 1/2 for every q).
+ *   ternary: tag = 0xFFFF, k = 0.  w = c_(j & 7); its fields f_r = (w >> 2r) & 3, r = 0..31; the first field that is not 3 gives 0 -> 0, 1 -> +1, 2 -> -1;
+ *     if there is none (probability 2^-64) the value is 0.
+ *   cbd: tag = 0xFFFF, k = 1.  w = c_(j & 7); v = popcount(w & (2^eta - 1)) - popcount((w >> 32) & (2^eta - 1)), 1 <= eta <= 32: variance eta / 2 (eta = 21:
+ *     sigma = 3.24, the usual error width).
+ *   The small kinds write the same v under every prime of the range: v for v >= 0, q + v otherwise (reduced once more under a modulus not above |v|).
+ * uniform's running time depends on the rejected candidates only -- public data where `a` is public --; the small kinds are branch-free (a mask and a count of
+ * trailing zeros; popcounts).  Out of scope: discrete Gaussians, fixed-Hamming-weight secrets.
+ * Status.  NULL plan, key or d_out: AGX_ERR_NULL_POINTER.  A range past the plan's primes or prime_count == 0; frame_first + batch > 2^32; eta outside
+ * [1, 32]; an unknown form; the plan's device not current; a pointer not 8-byte aligned, a batch past the grid limit or an extent past 2^60 words:
+ * AGX_ERR_BAD_ARGUMENT, nothing written.  batch == 0: AGX_OK, nothing launched.  Asynchronous on `stream`; they allocate and synchronise nothing and touch no
+ * plan state (capturable into a hipGraph).
+ * Route.  ONE streaming launch each, no table, no LDS, no barrier: one thread per cell, the sixteen working words in vector registers, the key, the
+ * constants and the nonce in scalar registers, a lane's 64 contiguous bytes stored 16 at a time where d_out is 16-byte aligned.  uniform: one row of the
+ * grid per prime; the small kinds compute a cell's eight values once and walk the primes.  Measured: profiles/r19_sampling.md. */
+AGX_API int agx_ntt_sample_uniform(const agx_ntt_plan* plan, const uint8_t key[32], uint64_t nonce, uint64_t* d_out, uint64_t batch, uint64_t frame_first,
+                                   uint32_t prime_first, uint32_t prime_count, void* stream);
+AGX_API int agx_ntt_sample_ternary(const agx_ntt_plan* plan, const uint8_t key[32], uint64_t nonce, uint64_t* d_out, uint64_t batch, uint64_t frame_first,
+                                   uint32_t prime_first, uint32_t prime_count, int out_form, void* stream);
+AGX_API int agx_ntt_sample_cbd(const agx_ntt_plan* plan, const uint8_t key[32], uint64_t nonce, uint32_t eta, uint64_t* d_out, uint64_t batch,
+                               uint64_t frame_first, uint32_t prime_first, uint32_t prime_count, int out_form, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* (4) Host math the reference leaves to its caller (src/main.cpp:49-55 ships   */

@@ -7,6 +7,8 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op bfvconv --src S --dst T [--only {all,exact,mont,parent,copy} --reps 7 ...]   (agx_ntt_basis_extend_exact / _mont, coefficient form, beside agx_ntt_basis_extend into T + 1 targets and a copy of the model's bytes)
        python3 tools/run_op.py --op quotient --qcount L --src K [--only {all,quotient,composition,copy} --reps 7 ...]   (agx_ntt_basis_quotient beside the six-call composition it replaces and a copy of its model bytes)
        python3 tools/run_op.py --op plain --qcount L [--reps 7 ...]   (agx_ntt_plain_scale_down, _scale_up and _lift in both forms beside a copy of each call's model bytes and the plan's inverse / forward alone)
+       python3 tools/run_op.py --op sample --kind {uniform,ternary,cbd} [--primes L --eta 21 --reps 7 ...]   (agx_ntt_sample_*: a draw, in both forms for the small kinds, beside a device fill of the same bytes and the plan's forward;
+                                                                   uniform also under the primes just above 2^60, where every cell takes two blocks or more)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
        python3 tools/run_op.py --op ring --kind {add,sub,negate,add_galois,tensor} [--primes 6 --first 0 --count 4 --galois G --only {all,ring,copy,parent} --reps 7 ...]   (a ring call beside a copy of its model bytes and what it replaces)
        python3 tools/run_op.py --op keyswitch --qcount Q [--pfirst F --pcount K --alpha A --reps 7 ...]   (agx_ntt_keyswitch_apply beside the composition of public calls, and the stages)
@@ -29,7 +31,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient", "plain"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient", "plain", "sample"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -57,7 +59,9 @@ ap.add_argument("--only", choices=["both", "fused", "pair", "all", "generic", "p
                      "(parent), or all alternating (default).  A counter run wants one")
 ap.add_argument("--terms", type=int, default=2, help="inner: terms of the sum (1 .. 16)")
 ap.add_argument("--outputs", type=int, default=2, help="inner: outputs (1 or 2)")
-ap.add_argument("--kind", choices=["add", "sub", "negate", "add_galois", "tensor"], default="add", help="ring: the call to time")
+ap.add_argument("--kind", choices=["add", "sub", "negate", "add_galois", "tensor", "uniform", "ternary", "cbd"], default=None,
+                help="ring: the call to time (default add); sample: the draw to time (default uniform)")
+ap.add_argument("--eta", type=int, default=21, help="sample --kind cbd: the width eta (1 .. 32)")
 ap.add_argument("--first", type=int, default=0, help="ring: the first plan prime of the range")
 ap.add_argument("--count", type=int, default=4, help="ring: primes in the range")
 ap.add_argument("--qcount", type=int, default=4, help="keyswitch: Q = primes [0, qcount)")
@@ -68,6 +72,7 @@ ap.add_argument("--rotations", type=int, nargs="+", default=[8], help="hoist, dh
 ap.add_argument("--report", type=str, default=None, help="write {calls: ramp + warm-up + timed launches, ms: ...} here (tools/summarize_ops.py)")
 args = ap.parse_args()
 args.mode = args.mode or ("floor" if args.op == "moddown" else "round")
+args.kind = args.kind or ("uniform" if args.op == "sample" else "add")
 if args.op == "moddown":
     args.dst = args.dst or 4
     args.primes = args.src + args.dst      # targets [0, T), sources [T, T + S)
@@ -447,6 +452,102 @@ def run_plain():
 
         json.dump({"us": times, "launches": args.launches, "kernel_launches": {"scale_down": info[4], "ntt_form": info[5]}, "model_bytes": 16.0 * half}, open(args.report, "w"))
     plain.close()
+    plan.close()
+
+
+def _primes_above(bound, n, count):
+    """the `count` smallest primes = 1 (mod 2n) above `bound` < 2^62 (Miller-Rabin on the bases that decide every 64-bit number)"""
+    def is_prime(m):
+        if m < 2 or any(m % p == 0 and m != p for p in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37)):
+            return False
+        d, r = m - 1, 0
+        while d % 2 == 0:
+            d, r = d // 2, r + 1
+        for a in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37):
+            x = pow(a, d, m)
+            if a % m == 0 or x in (1, m - 1):
+                continue
+            for _ in range(r - 1):
+                x = x * x % m
+                if x == m - 1:
+                    break
+            else:
+                return False
+        return True
+
+    out, c = [], bound // (2 * n) * (2 * n) + 1
+    while len(out) < count:
+        if c > bound and is_prime(c):
+            out.append(c)
+        c += 2 * n
+    return out
+
+
+def run_sample():
+    """agx_ntt_sample_uniform / _ternary / _cbd (--kind) on the plan's --primes L primes (60-bit: q = 2^60 - c, one block per cell), alternating in one
+    process with (a) a device fill that writes the same 8 L bytes per coefficient and (b) the plan's forward on the same slabs, in place.  The small kinds are
+    timed in both forms; uniform, which has none, also under (c) a second plan of the L primes just above 2^60, where a candidate passes with probability
+    one half and every cell takes two blocks or more.  Prints us per call: median (min ... max) of --reps groups of --launches calls."""
+    import statistics
+
+    L, words = args.primes, args.batch * args.n
+    key = bytes(range(32))
+    out = torch.empty(L * words, dtype=torch.int64, device="cuda")
+    p = out.data_ptr()
+    plan.fill_synthetic(p, args.batch, 0, 42, stream)
+    draws = [0]      # a nonce is never reused under one key for one kind
+
+    def nonce():
+        draws[0] += 1
+        return draws[0]
+
+    def fill():
+        out.fill_(1)
+
+    def forward():
+        plan.forward_range(p, p, args.batch, 0, L, stream)
+
+    wide = None
+    if args.kind == "uniform":
+        wide = agx.Plan(args.n, _primes_above(1 << 60, args.n, L))
+
+        def uniform():
+            plan.sample_uniform(key, nonce(), p, args.batch, 0, 0, L, stream)
+
+        def uniform_above60():
+            wide.sample_uniform(key, nonce(), p, args.batch, 0, 0, L, stream)
+
+        todo = [uniform, uniform_above60, fill, forward]
+    else:
+        def draw(form):
+            if args.kind == "ternary":
+                plan.sample_ternary(key, nonce(), p, args.batch, 0, 0, L, form, stream)
+            else:
+                plan.sample_cbd(key, nonce(), args.eta, p, args.batch, 0, 0, L, form, stream)
+
+        def coeff():
+            draw(agx.FORM_COEFF)
+
+        def ntt():
+            draw(agx.FORM_NTT)
+
+        todo = [coeff, ntt, fill, forward]
+    times = _alternate(todo)
+    print(f"sample kind={args.kind}{' eta=' + str(args.eta) if args.kind == 'cbd' else ''} n={args.n} L={L} batch={args.batch} bits={args.bits} "
+          f"({8 * L * words / 2**20:.0f} MiB written):")
+    for name, v in times.items():
+        print(f"  {name} {_fmt(v)} us")
+    med = {k: statistics.median(v) for k, v in times.items()}
+    first = todo[0].__name__
+    print("  " + "  ".join(f"{name}/{ref} {med[name] / med[ref]:.3f}" for name in med if name not in ("fill", "forward") for ref in ("fill", "forward")) +
+          (f"  ntt/(coeff + forward) {med['ntt'] / (med['coeff'] + med['forward']):.3f}" if "ntt" in med else "") +
+          f"  {first}: {med[first] * 1e3 / (L * words):.4f} ns per word")
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "model_bytes": 8.0 * L * words}, open(args.report, "w"))
+    if wide is not None:
+        wide.close()
     plan.close()
 
 
@@ -973,6 +1074,9 @@ if args.op == "quotient":
     sys.exit(0)
 if args.op == "plain":
     run_plain()
+    sys.exit(0)
+if args.op == "sample":
+    run_sample()
     sys.exit(0)
 slabs = [torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(args.slabs)]
 for i, s in enumerate(slabs):
