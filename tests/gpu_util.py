@@ -420,6 +420,42 @@ def judged_frames(batch, limit, extra=()):
     return thin_frames(boundary_frames(batch) + list(extra) + edges, edges, limit=limit)
 
 
+def resident_grid(torch, n):
+    """workgroups of the loop inverse (n = 16384, 32768) that the device holds at once: 4 waves per SIMD of 2^(log n - 5) threads per frame"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return cus * (4 * 256 // (n // 32))
+
+
+def loop_batch(torch, n):
+    """a batch with more frames than resident_grid(torch, n) and a ragged last round"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    return 2 * cus + 188 if n == 16384 else cus + 144
+
+
+def companion_batches(plan, main_id, companion_id, limit=1 << 16):
+    """(b_lo, b_hi): the largest batch whose forward call the plan's main entry serves and the smallest one its forward companion serves, read back
+    through plan.forward_kernel, so that no test states the threshold itself"""
+    b_hi = next(b for b in range(1, limit) if plan.forward_kernel(b) == companion_id)
+    assert b_hi > 1 and plan.forward_kernel(b_hi - 1) == main_id and plan.forward_kernel(1) == main_id, (b_hi, plan.forward_kernel(b_hi - 1))
+    return b_hi - 1, b_hi
+
+
+def assert_equals_chunked_calls(torch, call, inputs, outputs, batch, chunk):
+    """Every word that ONE call on `batch` frames wrote must be the word the same call writes when it is made `chunk` frames at a time (`chunk` small
+    enough for one step of any grid).  inputs, outputs: tensors viewed as [slabs][batch][n], the outputs holding what the large call wrote;
+    call(ins, outs, frames) makes the call on `frames` frames: ins are dense copies of those frames of the inputs (the call may consume them), outs
+    dense buffers filled with -1, both lists in the order given here.  Launches and comparisons run on the current stream, one behind the other."""
+    for v in list(inputs) + list(outputs):
+        assert v.dim() == 3 and v.shape[1] == batch, tuple(v.shape)
+    for f0 in range(0, batch, chunk):
+        f1 = min(batch, f0 + chunk)
+        ins = [v[:, f0:f1].clone(memory_format=torch.contiguous_format) for v in inputs]
+        outs = [torch.full((v.shape[0], f1 - f0, v.shape[2]), -1, dtype=v.dtype, device=v.device) for v in outputs]
+        call(ins, outs, f1 - f0)
+        for k, (whole, part) in enumerate(zip(outputs, outs)):
+            assert torch.equal(whole[:, f0:f1], part), ("output", k, "of the large call differs from the call on frames", f0, f1)
+
+
 def spread_lazy_(torch, x, moduli, seed):
     """x ([primes][...] on any device, residues in [0, q_p)) += q_p * k in place, k uniform in 0..3 per element: the same residues spread
     over the lazy input range [0, 4q); in chunks, so the temporaries stay small"""

@@ -8,7 +8,7 @@ import functools
 import numpy as np
 import pytest
 
-from gpu_util import RESCALE_IDS, Layout, arena_for, canary, capture, judged_frames, moduli_for, plan_for_moduli, registry_entries, status_of
+from gpu_util import RESCALE_IDS, Layout, arena_for, assert_equals_chunked_calls, canary, capture, judged_frames, moduli_for, plan_for_moduli, registry_entries, status_of
 from rns_ref import convert, device_residues, oracle_forward_set, product, residues, special_values, spread
 
 pytestmark = pytest.mark.gpu
@@ -355,15 +355,9 @@ def test_generic_kernel_past_one_grid_stride_trip(agx, orc, dev):
     d_out = dev.empty(T * batch * n)
     d_out.fill_(-1)
     two.extend(d_x.data_ptr(), d_out.data_ptr(), batch, COEFF, dev.stream)
-    xv, ov = d_x.view(S, batch, n), d_out.view(T, batch, n)
-    part_out = dev.empty(T * chunk * n)
-    for f0 in range(0, batch, chunk):
-        part_x = xv[:, f0:f0 + chunk].contiguous()
-        part_out.fill_(-1)
-        two.extend(part_x.data_ptr(), part_out.data_ptr(), chunk, COEFF, dev.stream)
-        dev.sync()
-        assert torch.equal(ov[:, f0:f0 + chunk], part_out.view(T, chunk, n)), ("the large call differs from the call on frames", f0, f0 + chunk)
-    del d_out, part_out
+    assert_equals_chunked_calls(torch, lambda ins, outs, frames: two.extend(ins[0].data_ptr(), outs[0].data_ptr(), frames, COEFF, dev.stream),
+                                [d_x.view(S, batch, n)], [d_out.view(T, batch, n)], batch, chunk)
+    del d_out
     frames = judged_frames(batch, 48, extra=range(0, batch, 4999))
     _judge_frames(dev, two, d_x, moduli[:S], moduli, batch, n, frames, orc)
     two.close()

@@ -8,7 +8,7 @@ import functools
 import numpy as np
 import pytest
 
-from gpu_util import RESCALE_IDS, Layout, arena_for, canary, capture, judged_frames, moduli_for, plan_for_moduli, registry_entries, status_of
+from gpu_util import RESCALE_IDS, Layout, arena_for, assert_equals_chunked_calls, canary, capture, judged_frames, moduli_for, plan_for_moduli, registry_entries, status_of
 from rns_ref import device_residues, lift, mod_down, mod_down_ntt, oracle_forward_set, product, residues, special_values, spread
 
 pytestmark = pytest.mark.gpu
@@ -401,14 +401,9 @@ def test_generic_kernel_past_one_grid_stride_trip(agx, orc, dev):
     d_out, d_s = dev.empty(T * batch * n), dev.empty(S * batch * n)
     d_out.fill_(-1)
     basis.mod_down(d_xq.data_ptr(), d_xp.data_ptr(), d_out.data_ptr(), d_s.data_ptr(), batch, dev.stream)
-    qv, pv, ov = d_xq.view(T, batch, n), d_xp.view(S, batch, n), d_out.view(T, batch, n)
-    part_out, part_s = dev.empty(T * chunk * n), dev.empty(S * chunk * n)
-    for f0 in range(0, batch, chunk):
-        part_q, part_p = qv[:, f0:f0 + chunk].contiguous(), pv[:, f0:f0 + chunk].contiguous()
-        part_out.fill_(-1)
-        basis.mod_down(part_q.data_ptr(), part_p.data_ptr(), part_out.data_ptr(), part_s.data_ptr(), chunk, dev.stream)
-        dev.sync()
-        assert torch.equal(ov[:, f0:f0 + chunk], part_out.view(T, chunk, n)), ("the large call differs from the call on frames", f0, f0 + chunk)
+    part_s = dev.empty(S * chunk * n)
+    assert_equals_chunked_calls(torch, lambda ins, outs, frames: basis.mod_down(ins[0].data_ptr(), ins[1].data_ptr(), outs[0].data_ptr(), part_s.data_ptr(), frames, dev.stream),
+                                [d_xq.view(T, batch, n), d_xp.view(S, batch, n)], [d_out.view(T, batch, n)], batch, chunk)
     frames = judged_frames(batch, 48, extra=range(0, batch, 4999))
     _judge_frames(orc, dev, d_xq, d_xp, d_out, moduli[3:], moduli[:T], batch, n, frames)
     basis.close()

@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from gpu_util import (EDGES, OracleRef, big_memory, boundary_frames, capture, check_automorphism_coeff, check_automorphism_ntt,      # noqa: F401  (big_memory: the fixture is used by name)
-                      check_fixed_shifts, check_rescale_identity, fill_rescale_constants, frames_to_host, library_find_prime, moduli_for,
-                      radix2_twin, rescale_identity_sum_, rescale_reference, sample_frames, sigma, spread_lazy_, thin_frames)
+                      check_fixed_shifts, check_rescale_identity, fill_rescale_constants, frames_to_host, library_find_prime, loop_batch, moduli_for,
+                      radix2_twin, rescale_identity_sum_, rescale_reference, resident_grid, sample_frames, sigma, spread_lazy_, thin_frames)
 
 pytestmark = pytest.mark.gpu
 
@@ -253,17 +253,6 @@ def _check_sampled(torch, ref, out, want, batch, n, frames, what):
             assert np.array_equal(got[p, k], ref.forward(p, want[p, k])), f"{what}: frame {f} of prime {p} differs from the oracle's transform of Y mod q"
 
 
-def _resident_grid(torch, n):
-    """workgroups of the loop inverse that the device holds at once: 4 waves per SIMD of 2^(log n - 5) threads per frame"""
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    return cus * (4 * 256 // (n // 32))
-
-
-def _loop_batch(torch, n):
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    return 2 * cus + 188 if n == 16384 else cus + 144
-
-
 RESCALE = [
     # n, moduli, batch (None: from the device's CU count), what the case is there for
     (4096, (60, 60, 60), 1100, "fused"),
@@ -285,9 +274,9 @@ def test_rescale_past_one_grid_stride_trip_and_one_resident_grid(agx, orc, dev, 
     torch = dev.torch
     moduli = list(moduli_for(library_find_prime(agx), n, spec))
     P = len(moduli)
-    resident = _resident_grid(torch, n)
+    resident = resident_grid(torch, n)
     if kind == "loop":
-        batch = _loop_batch(torch, n)
+        batch = loop_batch(torch, n)
         assert batch > resident and batch % resident != 0, (batch, resident)      # the last slab alone: more frames than workgroups, a ragged last round
     else:
         assert batch * n > TRIP
@@ -334,7 +323,7 @@ def test_rescale_stateless_loop_inverse_in_a_graph(agx, orc, dev):
     n, spec = 16384, (60, 60)
     moduli = list(moduli_for(library_find_prime(agx), n, spec))
     P = len(moduli)
-    batch, resident = _loop_batch(torch, n), _resident_grid(torch, n)
+    batch, resident = loop_batch(torch, n), resident_grid(torch, n)
     assert batch > resident and batch % resident != 0, (batch, resident)
     slab, head = batch * n, (P - 1) * batch * n
     plan = agx.Plan(n, moduli)

@@ -1,4 +1,5 @@
-"""Self-test of the whole-buffer checkers of gpu_util.py that test_gpu_ops_at_scale.py relies on, on the CPU: the output of the GPU is
+"""Self-test of the whole-buffer checkers of gpu_util.py that test_gpu_ops_at_scale.py relies on (and of the chunked comparison of the RNS calls' tests
+at scale), on the CPU: the output of the GPU is
 replaced by the oracle's, once untouched and once per planted fault; every checker must pass the first and name a word of the second.
 The expected words of the rescale identity are compared with Python integers (X by CRT, Y = floor((X + {0, h}) / q_L)), the reference
 of test_gpu_rescale.py."""
@@ -8,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_util import (check_automorphism_coeff, check_automorphism_ntt, check_fixed_shifts, check_rescale_identity, fill_rescale_constants,
+from gpu_util import (assert_equals_chunked_calls, check_automorphism_coeff, check_automorphism_ntt, check_fixed_shifts, check_rescale_identity, fill_rescale_constants,
                       moduli_for, ntt_pi, oracle_polymul, rand_coeffs, rescale_identity_constants, rescale_identity_sum_, rescale_reference, sigma,
                       spread_lazy_, thin_frames)
 
@@ -181,6 +182,39 @@ def test_one_dimensional_second_trip_of_the_ntt_form(orc):
     flat[lo:lo + TRIP] = flat[lo - TRIP:lo]
     found = judge(_t(flat))
     assert found and found[0] == (lo // (BATCH * N), (lo // N) % BATCH, 0), found
+
+
+# ---- the chunked comparison of the RNS calls ----------------------------------------------------------------------------------------------------
+def _fake_call(ins, outs, frames):
+    """a stand-in for an RNS call of two inputs ([2][frames][N], [1][frames][N]) and two outputs: every output word depends on its own frame alone"""
+    assert ins[0].shape == (2, frames, N) and ins[1].shape == (1, frames, N) and all(bool((o == -1).all()) for o in outs)
+    outs[0][:] = ins[0] * 3 + ins[1]
+    outs[1][:] = ins[0][:1] - ins[1].flip(2)
+    ins[0].zero_()      # a call may consume its operands: the helper hands out copies
+
+
+@pytest.mark.parametrize("chunk", [2, 4, 9, 16])
+@pytest.mark.parametrize("fault", ["none", "dropped", "shifted", "one word of the last frame"])
+def test_chunked_comparison_fails_when_the_second_trip_is_dropped_or_shifted(fault, chunk):
+    """the large call's outputs are the fake call's own, with frames 4 .. 7 of every slab -- the second "trip" -- left unwritten, or written one frame late"""
+    g = torch.Generator().manual_seed(7)
+    inputs = [torch.randint(0, 1 << 60, (s, BATCH, N), generator=g, dtype=torch.int64) for s in (2, 1)]
+    keep = [v.clone() for v in inputs]
+    outputs = [torch.full((s, BATCH, N), -1, dtype=torch.int64) for s in (2, 1)]
+    _fake_call([v.clone() for v in inputs], outputs, BATCH)
+    first, last = TRIP // N, 2 * TRIP // N
+    if fault == "dropped":
+        outputs[1][:, first:last] = -1
+    elif fault == "shifted":
+        outputs[0][:, first + 1:last + 1] = outputs[0][:, first:last].clone()
+    elif fault != "none":
+        outputs[0][-1, -1, N - 1] ^= 1
+    if fault == "none":
+        assert_equals_chunked_calls(torch, _fake_call, inputs, outputs, BATCH, chunk)
+    else:
+        with pytest.raises(AssertionError, match="differs from the call on frames"):
+            assert_equals_chunked_calls(torch, _fake_call, inputs, outputs, BATCH, chunk)
+    assert all(torch.equal(a, b) for a, b in zip(inputs, keep)), "the helper let the call consume the inputs themselves"
 
 
 def test_thin_frames_keeps_what_it_must():
