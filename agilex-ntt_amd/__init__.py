@@ -28,6 +28,7 @@ _u32 = ctypes.c_uint32
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
 _vp = ctypes.c_void_p
+_dbl = ctypes.c_double
 _p64 = ctypes.POINTER(ctypes.c_uint64)
 
 # name -> (restype, argtypes): every symbol include/agx_ntt.h declares
@@ -108,6 +109,12 @@ ABI = {
     "agx_ntt_make_tables": (_int, [_u64, _u64, _u32, _p64, _p64]),
     "agx_ntt_make_inverse_tables": (_int, [_u64, _u64, _u32, _p64, _p64]),
     "agx_ntt_galois_element": (_int, [_u32, _i64, ctypes.POINTER(_u32)]),
+    "agx_ntt_ckks_create": (_int, [ctypes.POINTER(_vp), _vp, _u32, _u32]),
+    "agx_ntt_ckks_destroy": (_int, [_vp]),
+    "agx_ntt_ckks_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "agx_ntt_ckks_encode": (_int, [_vp, _vp, _u32, _dbl, _vp, _u64, _u32, _int, _vp]),
+    "agx_ntt_ckks_decode": (_int, [_vp, _vp, _int, _u32, _dbl, _vp, _u32, _vp, _u64, _vp]),
+    "agx_ntt_ckks_twiddle": (_int, [_u32, _u32, ctypes.POINTER(_dbl)]),
     # groups: the same calls over several GPUs (one shard, one host thread, one stream per listed device)
     "agx_ntt_shard_range": (_int, [_u64, _u32, _u32, _p64, _p64]),
     "agx_ntt_group_create": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_int), _u32, _u32, _u32, _p64, _p64, _p64, _p64, _p64]),
@@ -423,6 +430,10 @@ class Plan:
         plaintext modulus t in [2, 2^62): scale_up, lift and scale_down"""
         return Plain(self, q_first, q_count, gamma_prime, t)
 
+    def ckks(self, q_first, q_count):
+        """Ckks(self, ...): CKKS encoding and decoding on the primes [q_first, q_first + q_count), q_count <= 16; a call may use any prefix of them"""
+        return Ckks(self, q_first, q_count)
+
     def sample_uniform(self, key, nonce, d_out, batch, frame_first=0, prime_first=0, prime_count=None, stream=0):
         """uniform words below q_i on the plan primes [prime_first, prime_first + prime_count) (None: all of the plan's), one launch: d_out
         [prime_count][batch][n]; key: 32 bytes (the caller's seed, host memory), nonce: the 64-bit draw number, never reused under one key for one kind;
@@ -656,6 +667,52 @@ class Plain:
     def close(self):
         if self._h:
             lib().agx_ntt_plain_destroy(self._h)
+            self._h = _vp(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ckks_twiddle(length, j):
+    """tw(length, j) = (cos, sin) of 2 pi (5^j mod 4 length) / (4 length) as the kernels read it (agx_ntt_ckks_twiddle): host arithmetic, no device"""
+    out = (_dbl * 2)()
+    _check(lib().agx_ntt_ckks_twiddle(length, j, out), "ckks_twiddle")
+    return out[0], out[1]
+
+
+class Ckks:
+    """CKKS encoding and decoding (agx_ntt_ckks_*) on a plan's primes [q_first, q_first + q_count).  `plan` is a Plan or a raw plan handle (one handle per
+    DeviceGroup shard); it must outlive the handle, and its device must be current here and at every call.  Slot j sits at the root zeta^(5^j)."""
+
+    def __init__(self, plan, q_first, q_count):
+        self.plan = plan      # keeps a Plan alive
+        self._h = _vp(None)
+        handle = plan._h if isinstance(plan, Plan) else plan
+        _check(lib().agx_ntt_ckks_create(ctypes.byref(self._h), handle, q_first, q_count), "ckks_create")
+
+    def info(self):
+        """(q_first, q_count, max_slots, launches_encode_ntt, launches_decode_ntt) under the plan's current variant"""
+        v = [_u32(0) for _ in range(3)]
+        enc, dec = _int(0), _int(0)
+        _check(lib().agx_ntt_ckks_info(self._h, *[ctypes.byref(x) for x in v], ctypes.byref(enc), ctypes.byref(dec)), "ckks_info")
+        return tuple(x.value for x in v) + (enc.value, dec.value)
+
+    def encode(self, d_z, slots, scale, d_out, batch, count, form=FORM_NTT, stream=0):
+        """d_z [batch][slots] (re, im) doubles -> d_out [count][batch][n]: rint(scale w) mod q_i on the gap grid, w the inverse special FFT of z, as
+        coefficients (FORM_COEFF) or transformed as Plan.forward writes it (FORM_NTT); out of place"""
+        _check(lib().agx_ntt_ckks_encode(self._h, d_z, slots, scale, d_out, batch, count, form, stream), "ckks_encode")
+
+    def decode(self, d_x, form, count, scale, d_z, slots, d_scratch, batch, stream=0):
+        """d_x [count][batch][n] -> d_z [batch][slots] (re, im) doubles: the forward special FFT of the centred coefficients, over scale.  FORM_NTT: reduced
+        or lazy words, d_scratch count*batch*n words or d_x itself (then overwritten); FORM_COEFF: fully reduced words, d_scratch may be None"""
+        _check(lib().agx_ntt_ckks_decode(self._h, d_x, form, count, scale, d_z, slots, d_scratch, batch, stream), "ckks_decode")
+
+    def close(self):
+        if self._h:
+            lib().agx_ntt_ckks_destroy(self._h)
             self._h = _vp(None)
 
     def __del__(self):

@@ -879,3 +879,123 @@ int agx_ntt_sample_cbd(const agx_ntt_plan* plan, const uint8_t key[32], uint64_t
 }
 
 }  // extern "C"
+
+// ---- agx_ntt_ckks_*: CKKS encoding and decoding (include/agx_ntt.h has the definition, ckks_arith.hpp the per-word steps) ----
+
+// A CKKS boundary on the current device from its image: the buffers, then the view every call hands to its kernel
+static int instantiate_ckks(agx_ntt_ckks** out, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count, const ckks_image& img) {
+    std::unique_ptr<agx_ntt_ckks> p(new (std::nothrow) agx_ntt_ckks);
+    if (!p) return AGX_ERR_ALLOC;
+    p->plan = plan;
+    static_assert(sizeof(double2) == 2 * sizeof(double), "the twiddle table is uploaded as double2");
+    if (int rc = p->d_tw.upload(reinterpret_cast<const double2*>(img.tw.data()), img.tw.size() / 2)) return rc;
+    if (int rc = p->d_q.upload(img.q)) return rc;
+    if (!img.tri.empty())      // one prime has no Garner constant
+        if (int rc = upload_pairs(p->d_tri, img.tri)) return rc;
+    if (int rc = upload_pairs(p->d_pow2, img.pow2)) return rc;
+    ckks_view& v = p->view;
+    v.tw = p->d_tw, v.q = p->d_q, v.tri = p->d_tri, v.pow2 = p->d_pow2, v.q_first = q_first, v.q_count = q_count;
+    *out = p.release();
+    return AGX_OK;
+}
+
+// log2 of a legal slot count (a power of two in [1, n / 2]), or -1
+static int ckks_log_slots(const agx_ntt_plan* plan, uint32_t slots) {
+    if (!is_pow2(slots) || slots > plan->n / 2) return -1;
+    return log2u(slots);
+}
+
+static bool ckks_scale_ok(double scale) { return scale > 0.0 && scale <= 1.7976931348623157e308; }      // finite and positive; a NaN fails both
+
+extern "C" {
+
+// The rules in their order, agx_ntt_plain_create's: NULL; the range; the plan; two equal moduli in the range, a bad modulus.
+int agx_ntt_ckks_create(agx_ntt_ckks** h, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count) {
+    if (!h) return AGX_ERR_NULL_POINTER;
+    *h = nullptr;
+    if (!plan) return AGX_ERR_NULL_POINTER;
+    const uint32_t P = plan->num_primes;
+    if (q_count == 0 || q_count > AGX_BASIS_MAX_SRC || q_count > P || q_first > P - q_count) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    return guarded([&]() -> int {
+        ckks_image img;
+        if (!prepare_ckks_image(img, &plan->moduli[q_first], q_count, plan->n)) return AGX_ERR_BAD_MODULUS;
+        return instantiate_ckks(h, plan, q_first, q_count, img);
+    });
+}
+
+int agx_ntt_ckks_destroy(agx_ntt_ckks* h) {
+    delete h;      // the device memory goes with its owners
+    return AGX_OK;
+}
+
+int agx_ntt_ckks_info(const agx_ntt_ckks* h, uint32_t* q_first, uint32_t* q_count, uint32_t* max_slots, int* launches_encode_ntt, int* launches_decode_ntt) {
+    if (!h) return AGX_ERR_NULL_POINTER;
+    if (q_first) *q_first = h->view.q_first;
+    if (q_count) *q_count = h->view.q_count;
+    if (max_slots) *max_slots = h->plan->n / 2;
+    if (launches_encode_ntt) *launches_encode_ntt = 1 + forward_launches(h->plan);      // the coefficient-form launch, then the plan's forward on the range
+    if (launches_decode_ntt) *launches_decode_ntt = inverse_launches(h->plan) + 1;      // the plan's inverse on the range, then the decoding kernel
+    return AGX_OK;
+}
+
+// agx_ntt_plain_scale_up's rules in its order, the handle's arguments (count, slots, scale) first.  Out of place only: d_out's slabs touch d_z nowhere.
+int agx_ntt_ckks_encode(const agx_ntt_ckks* h, const double* d_z, uint32_t slots, double scale, uint64_t* d_out, uint64_t batch, uint32_t count, int out_form, void* stream) {
+    if (!h || !d_z || !d_out) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = h->plan;
+    const ckks_view& cv = h->view;
+    if (count == 0 || count > cv.q_count) return AGX_ERR_BAD_ARGUMENT;
+    const int log_s = ckks_log_slots(plan, slots);
+    if (log_s < 0 || !ckks_scale_ok(scale)) return AGX_ERR_BAD_ARGUMENT;
+    if (out_form != AGX_FORM_COEFF && out_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!aligned8(d_z) || !aligned8(d_out) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of out ([count][batch][n])
+    if (!dense_fits(plan->n, count, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t slab = batch * plan->n;
+    if (ranges_touch(addr(d_z), 2 * batch * slots, addr(d_out), count * slab)) return AGX_ERR_BAD_ARGUMENT;      // a pair of doubles is two words
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AGX_HIP(launch_ckks_encode(plan->log_n, cv, d_z, (uint32_t)log_s, scale, d_out, batch, count, s));
+    // the plan's forward on the view of the call's primes, in place
+    if (out_form == AGX_FORM_NTT) AGX_HIP(run_forward(prime_range(forward_route(plan, batch), cv.q_first, cv.q_first + count), d_out, d_out, fl, s));
+    return AGX_OK;
+}
+
+// agx_ntt_plain_scale_down's rules in its order.  Coefficient form reads d_x itself and never looks at d_scratch.
+int agx_ntt_ckks_decode(const agx_ntt_ckks* h, const uint64_t* d_x, int in_form, uint32_t count, double scale, double* d_z, uint32_t slots, uint64_t* d_scratch, uint64_t batch,
+                        void* stream) {
+    if (!h || !d_x || !d_z || (in_form == AGX_FORM_NTT && !d_scratch)) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = h->plan;
+    const ckks_view& cv = h->view;
+    if (count == 0 || count > cv.q_count) return AGX_ERR_BAD_ARGUMENT;
+    const int log_s = ckks_log_slots(plan, slots);
+    if (log_s < 0 || !ckks_scale_ok(scale)) return AGX_ERR_BAD_ARGUMENT;
+    if (in_form != AGX_FORM_COEFF && in_form != AGX_FORM_NTT) return AGX_ERR_BAD_ARGUMENT;
+    const bool ntt = in_form == AGX_FORM_NTT;
+    if (int rc = check_plan(plan)) return rc;
+    if (!aligned8(d_x) || !aligned8(d_z) || (ntt && !aligned8(d_scratch)) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of x and the scratch ([count][batch][n])
+    if (!dense_fits(plan->n, count, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const uint64_t words = count * (uint64_t)fl.prime_stride, zwords = 2 * batch * slots;
+    // the scratch IS x (the inverse then runs in place) or touches none of it; z touches neither
+    if (ntt && d_scratch != d_x && ranges_touch(addr(d_scratch), words, addr(d_x), words)) return AGX_ERR_BAD_ARGUMENT;
+    if (ranges_touch(addr(d_z), zwords, addr(d_x), words) || (ntt && ranges_touch(addr(d_z), zwords, addr(d_scratch), words))) return AGX_ERR_BAD_ARGUMENT;
+    if (ntt && !plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t* coeff = d_x;
+    if (ntt) {
+        AGX_HIP(run_inverse(prime_range(plan->routes.inverse, cv.q_first, cv.q_first + count), d_x, nullptr, d_scratch, fl, s));
+        coeff = d_scratch;
+    }
+    AGX_HIP(launch_ckks_decode(plan->log_n, cv, coeff, count, scale, d_z, (uint32_t)log_s, batch, s));
+    return AGX_OK;
+}
+
+int agx_ntt_ckks_twiddle(uint32_t len, uint32_t j, double out[2]) {
+    if (!out) return AGX_ERR_NULL_POINTER;
+    return ckks_twiddle(len, j, out) ? AGX_OK : AGX_ERR_BAD_ARGUMENT;
+}
+
+}  // extern "C"

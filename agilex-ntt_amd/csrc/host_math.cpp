@@ -237,4 +237,48 @@ plain_fault prepare_plain_image(plain_image& img, const plain_request& rq) {
     return plain_fault::none;
 }
 
+bool ckks_twiddle(uint32_t len, uint32_t j, double out[2]) {
+    if (len < 2 || len > 16384 || (len & (len - 1)) || j >= len / 2) return false;
+    const uint32_t m = 4 * len, quarter = len;                 // theta = 2 pi r / m, m >= 8
+    const uint32_t r = (uint32_t)pow_mod(5, j, m);             // odd
+    const uint32_t quadrant = r / quarter, in = r % quarter;   // theta = quadrant pi / 2 + 2 pi in / m
+    const bool swap = in > quarter / 2;                        // the complement pi / 2 - phi: cosine and sine change places
+    const uint32_t rr = swap ? quarter - in : in;              // 2 pi rr / m in [0, pi / 4]
+    const long double pi = 3.141592653589793238462643383279502884L;
+    const long double phi = (2.0L * pi * (long double)rr) / (long double)m;
+    long double c = __builtin_cosl(phi), s = __builtin_sinl(phi);
+    if (swap) { const long double t = c; c = s, s = t; }
+    switch (quadrant) {
+        case 0: out[0] = (double)c, out[1] = (double)s; break;
+        case 1: out[0] = (double)-s, out[1] = (double)c; break;
+        case 2: out[0] = (double)-c, out[1] = (double)-s; break;
+        default: out[0] = (double)s, out[1] = (double)-c; break;
+    }
+    return true;
+}
+
+bool prepare_ckks_image(ckks_image& img, const uint64_t* q, uint32_t L, uint32_t n) {
+    img = ckks_image{};
+    img.q.assign(q, q + L);
+    for (uint32_t i = 1; i < L; ++i)
+        for (uint32_t j = 0; j < i; ++j) {
+            uint64_t w = 0;
+            if (!inv_mod_euclid(q[j] % q[i], q[i], &w)) return false;
+            img.tri.push_back(shoup_pair::of(w, q[i]));
+        }
+    for (uint32_t i = 0; i < L; ++i) {
+        uint64_t w = 1 % q[i];
+        for (uint32_t e = 0; e < 1024; ++e) {
+            img.pow2.push_back(shoup_pair::of(w, q[i]));
+            w = (w << 1) >= q[i] ? (w << 1) - q[i] : w << 1;
+        }
+    }
+    const uint32_t half = n / 2 ? n / 2 : 1;
+    img.tw.assign(2 * (size_t)half, 0.0);
+    img.tw[0] = 1.0;
+    for (uint32_t len = 2; len <= n / 2; len <<= 1)
+        for (uint32_t j = 0; j < len / 2; ++j) ckks_twiddle(len, j, &img.tw[2 * (size_t)(len / 2 + j)]);
+    return true;
+}
+
 }  // namespace agx

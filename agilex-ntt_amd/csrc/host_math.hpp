@@ -147,4 +147,20 @@ enum class plain_fault {
 };
 plain_fault prepare_plain_image(plain_image& img, const plain_request& rq);
 
+// agx_ntt_ckks_twiddle: tw(len, j) = (cos theta, sin theta), theta = 2 pi (5^j mod 4 len) / (4 len), for len a power of two in [2, 16384] and j < len / 2
+// (false otherwise, out untouched).  The angle is reduced exactly in integers to [0, pi / 4] (quadrant, then the complement within it), cosine and sine
+// are taken in long double (64-bit significand) and rounded once to double: each component within 2^-53 of the real value.
+bool ckks_twiddle(uint32_t len, uint32_t j, double out[2]);
+
+// Everything a CKKS boundary (agx_ntt_ckks_*) keeps on the device, built once on the host (csrc/ckks_arith.hpp has the formulas), for the moduli q[0 .. L),
+// every one odd, > 1 and < 2^62, and the ring size n (a power of two, 2 <= n <= 32768):
+struct ckks_image {
+    std::vector<uint64_t> q;           // [L]
+    std::vector<shoup_pair> tri;       // [L (L - 1) / 2] q_j^-1 mod q_i at i (i - 1) / 2 + j, j < i: Garner's constants; a prefix serves a prefix of the moduli
+    std::vector<shoup_pair> pow2;      // [L][1024] 2^e mod q_i: the residues of a double from 2^63 on; entry 0 (the constant 1) serves every smaller one
+    std::vector<double> tw;            // [n / 2][2] tw(len, j) at len / 2 + j for len = 2 ... n / 2; entry 0 is (1, 0) and is never read
+};
+// false: two moduli share a factor (for primes: are equal); nothing is promised about the image then
+bool prepare_ckks_image(ckks_image& img, const uint64_t* q, uint32_t L, uint32_t n);
+
 }  // namespace agx

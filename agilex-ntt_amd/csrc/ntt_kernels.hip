@@ -20,6 +20,7 @@
 #include "basis_coeff_kernels.hpp"     // the coefficient-domain steps of agx_ntt_basis_extend / _extend_exact / _extend_mont / _quotient / _mod_down
 #include "plain_kernels.hpp"           // agx_ntt_plain_scale_up / _lift / _scale_down
 #include "sample_kernels.hpp"          // agx_ntt_sample_uniform / _ternary / _cbd
+#include "ckks_kernels.hpp"            // agx_ntt_ckks_encode / _decode
 
 #include <algorithm>
 #include <cstdlib>
@@ -30,6 +31,7 @@ namespace agx {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char agx_dyn_lds[];
 
+static constexpr int kCkksLdsLog = 13;  // CKKS kernels: 8192 slots = two planes of 64 KiB; 16384 slots (n = 32768, full) exchange through global memory
 static constexpr int kMaxLdsLog = 14;  // radix-2 kernels: 16384 coefficients = 128 KiB of the CU's 160 KiB LDS; n = 32768 runs as two blocks + one global stage
 
 // ---------------------------------------------------------------------------------------
@@ -330,6 +332,15 @@ hipError_t kernels_init() {
     if ((e = set_lds_attr(fwd_radix2_lds, big)) != hipSuccess) return e;
     if ((e = set_lds_attr(inv_radix2_lds, big)) != hipSuccess) return e;
     for_each_entry([&](const rb_entry& c) { if (e == hipSuccess) e = c.init(); });
+    // the CKKS kernels' planes: 16 bytes per slot, up to kCkksLdsLog slots
+    const size_t planes = (size_t)16 << kCkksLdsLog;
+    if (e == hipSuccess) e = set_lds_attr(&ckks_encode_kernel<false>, planes);
+    if (e == hipSuccess) e = set_lds_attr(&ckks_encode_kernel<true>, planes);      // the real components of 16384 slots
+    if (e == hipSuccess) e = set_lds_attr(&ckks_decode_kernel<1, false>, planes);
+    if (e == hipSuccess) e = set_lds_attr(&ckks_decode_kernel<2, false>, planes);
+    if (e == hipSuccess) e = set_lds_attr(&ckks_decode_kernel<4, false>, planes);
+    if (e == hipSuccess) e = set_lds_attr(&ckks_decode_kernel<8, false>, planes);
+    if (e == hipSuccess) e = set_lds_attr(&ckks_decode_kernel<16, false>, planes);
     return e;
 }
 
@@ -578,6 +589,38 @@ hipError_t launch_plain_scale_down(const plan_view& pv, const plain_view& cv, co
     const uint64_t per_prime = batch << pv.log_n;
     return with_smax(cv.q_count, [&](auto smax) {
         return launch_stream(&plain_scale_down_kernel<smax>, per_prime, 1, s, y, m, cv.row_t, cv.row_g, cv.t, cv.gamma, cv.g, cv.gp, cv.q_count, per_prime);
+    });
+}
+
+// The CKKS boundary: one workgroup per frame, s / 4 threads within [64, 1024]; the planes in LDS up to 2^kCkksLdsLog slots, beyond (n = 32768 with full
+// slots) the GLOBAL instances with 1024 threads
+static ckks_args ckks_args_of(uint32_t log_n, const ckks_view& cv, uint32_t log_s, uint32_t count, uint64_t batch) {
+    return ckks_args{cv.tw, cv.q, reinterpret_cast<const uint64_t*>(cv.tri), reinterpret_cast<const uint64_t*>(cv.pow2), log_n, log_s, count, batch << log_n};
+}
+
+static unsigned ckks_threads(uint32_t log_s) {
+    const uint32_t t = (1u << log_s) >> 2;
+    return t < 64 ? 64 : t > 1024 ? 1024 : t;
+}
+
+hipError_t launch_ckks_encode(uint32_t log_n, const ckks_view& cv, const double* z, uint32_t log_s, double scale, uint64_t* out, uint64_t batch, uint32_t count, hipStream_t s) {
+    const ckks_args a = ckks_args_of(log_n, cv, log_s, count, batch);
+    const bool global = log_s > (uint32_t)kCkksLdsLog;
+    const double inv_s = 1.0 / (double)(1u << log_s);
+    hipLaunchKernelGGL(global ? &ckks_encode_kernel<true> : &ckks_encode_kernel<false>, dim3((unsigned)batch), dim3(ckks_threads(log_s)), (size_t)(global ? 8 : 16) << log_s, s,
+                       reinterpret_cast<const double2*>(z), out, a, scale, inv_s);
+    return hipGetLastError();
+}
+
+hipError_t launch_ckks_decode(uint32_t log_n, const ckks_view& cv, const uint64_t* x, uint32_t count, double scale, double* z, uint32_t log_s, uint64_t batch, hipStream_t s) {
+    const ckks_args a = ckks_args_of(log_n, cv, log_s, count, batch);
+    const bool global = log_s > (uint32_t)kCkksLdsLog;
+    const double inv_delta = 1.0 / scale;
+    return with_smax(count, [&](auto smax) {
+        constexpr int S = decltype(smax)::value;
+        auto kernel = global ? &ckks_decode_kernel<S, true> : &ckks_decode_kernel<S, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(ckks_threads(log_s)), global ? 0 : (size_t)16 << log_s, s, x, reinterpret_cast<double2*>(z), a, inv_delta);
+        return hipGetLastError();
     });
 }
 

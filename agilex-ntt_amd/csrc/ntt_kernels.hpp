@@ -63,6 +63,16 @@ struct plain_view {
     uint32_t q_first = 0, q_count = 0;
 };
 
+// agx_ntt_ckks_*: what a CKKS boundary (plan, the primes [q_first, q_first + q_count)) keeps on the device (ckks_arith.hpp has the formulas; host_math.hpp's
+// ckks_image says what each table holds).  A call on count <= q_count primes reads a prefix of each.
+struct ckks_view {
+    const double2* tw = nullptr;         // [n / 2] tw(len, j) at len / 2 + j
+    const uint64_t* q = nullptr;         // [q_count]
+    const ulonglong2* tri = nullptr;     // [q_count (q_count - 1) / 2] {q_j^-1 mod q_i, quotient} at i (i - 1) / 2 + j
+    const ulonglong2* pow2 = nullptr;    // [q_count][1024] {2^e mod q_i, quotient}
+    uint32_t q_first = 0, q_count = 0;
+};
+
 struct rb_entry;   // one configuration of the kernel registry (rb_registry.hpp): static storage, valid for the life of the library
 
 // device-side view of a plan
@@ -179,6 +189,11 @@ hipError_t launch_plain_encode(const plan_view& pv, const plain_view& cv, bool l
 // the coefficient-domain step of agx_ntt_plain_scale_down: y dense [L][batch][n], y_i in [0, q_i) as the scaled inverse of the Q slabs left them -> m dense
 // [batch][n] in [0, t).  m touches y nowhere.  One launch.
 hipError_t launch_plain_scale_down(const plan_view& pv, const plain_view& cv, const uint64_t* y, uint64_t* m, uint64_t batch, hipStream_t s);
+// agx_ntt_ckks_encode in coefficient form: z dense [batch][2^log_s] pairs of doubles -> out dense [count][batch][n], slab i under plan prime q_first + i, fully
+// reduced; out touches z nowhere.  One launch, one workgroup per frame (ckks_kernels.hpp); log_s <= log_n - 1.
+hipError_t launch_ckks_encode(uint32_t log_n, const ckks_view& cv, const double* z, uint32_t log_s, double scale, uint64_t* out, uint64_t batch, uint32_t count, hipStream_t s);
+// agx_ntt_ckks_decode behind the inverse: x dense [count][batch][n], fully reduced -> z dense [batch][2^log_s] pairs; z touches x nowhere.  One launch.
+hipError_t launch_ckks_decode(uint32_t log_n, const ckks_view& cv, const uint64_t* x, uint32_t count, double scale, double* z, uint32_t log_s, uint64_t batch, hipStream_t s);
 // agx_ntt_sample_uniform / _ternary / _cbd in coefficient form: out dense [count][batch][n], slab i under plan prime first + i, fully reduced; frame f of
 // the launch is frame frame_first + f of the draw (frame_first + batch <= 2^32).  key: the eight little-endian words of the caller's 32 bytes, copied into
 // the kernel arguments.  pv: a view of the WHOLE plan (only its constants are read).  One launch each; the 16-byte stores when out allows them.

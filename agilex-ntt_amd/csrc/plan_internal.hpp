@@ -162,6 +162,17 @@ struct agx_ntt_plain {
     agx::plain_view view;
 };
 
+// agx_ntt_ckks_*: the tables of one CKKS boundary (plan, the primes [q_first, q_first + q_count)) on the plan's device, and nothing of the plan but a pointer,
+// as a basis: the plan outlives the handle, agx_ntt_plan_set_variant between calls stays legal.  Made from a ckks_image (host_math.hpp, whose fields say what
+// each buffer holds) by one function of agx_rns.cpp, which also fills the view, once.
+struct agx_ntt_ckks {
+    const agx_ntt_plan* plan = nullptr;
+    agx::device_buf<double2> d_tw;
+    agx::device_buf<uint64_t> d_q;
+    agx::device_buf<ulonglong2> d_tri, d_pow2;
+    agx::ckks_view view;
+};
+
 // agx_ntt_keyswitch_*: the shape and the bases of one hybrid key switch, and nothing of the plan but a pointer (as a basis: the plan outlives the
 // handle, agx_ntt_plan_set_variant between calls stays legal).  ModUp: one basis per digit with every active prime as a target when the special
 // primes follow Q directly; two per digit, targets Q and then targets P, when they lie apart (a basis names one contiguous range).  One ModDown

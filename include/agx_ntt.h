@@ -702,7 +702,7 @@ AGX_API int agx_ntt_keyswitch_mod_down(const agx_ntt_keyswitch* ks, uint64_t* d_
  * inverse on the same slabs (466 us against 318); less the inverse alone that is 1.12 ... 1.24 of the copy of its kernel's bytes, a difference of two medians: near its traffic, not
  * at it; which of its 2L + 1 products accounts for the rest was not measured.  agx_ntt_basis_quotient and agx_ntt_keyswitch_apply beside the parent commit's library in the same
  * session: 753 / 752 against 747 / 752 us and 3302 / 3294 against 3309 / 3309 us at n = 4096; the spreads overlap in all eight pairs.
- * Out of scope: BGV decryption (an exact centred Q -> t conversion); CKKS decoding; group forms (one
+ * Out of scope: BGV decryption (an exact centred Q -> t conversion); group forms (one
  * handle per shard, as for a basis); a fused NTT-form scale_up. */
 struct agx_ntt_plain;
 AGX_API int agx_ntt_plain_create(struct agx_ntt_plain** h, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count, uint32_t gamma_prime, uint64_t t);
@@ -768,6 +768,75 @@ AGX_API int agx_ntt_make_inverse_tables(uint64_t q, uint64_t psi, uint32_t n, ui
 /* the Galois element of a slot rotation by `step`: g = 5^step mod 2n, a negative step taking powers of 5^-1 mod 2n; always odd and below 2n.
  * (Conjugation is not a power of 5: its element is g = 2n - 1.)  Pure arithmetic, no device needed */
 AGX_API int agx_ntt_galois_element(uint32_t n, int64_t step, uint32_t* galois_elt);
+
+/* CKKS encoding and decoding on the device: a vector of complex slots <-> a plaintext polynomial in RNS form, the canonical-embedding ("special") FFT over the
+ * rotation group fused with the double <-> RNS conversions, one frame per workgroup.  With them a CKKS pipeline runs on library calls end to end
+ * ("CKKS encode, encrypt, multiply-plain, rescale, rotate, decrypt, decode"), and the slot order is stated once, here.
+ * Notation.  n the plan's size, M = 2n; slots = s, a power of two with 1 <= s <= n / 2; gap = (n / 2) / s; count = l with 1 <= l <= q_count: a call works on the
+ * plan primes [q_first, q_first + l), a PREFIX of the handle's range (a CKKS level drops primes from the end, so one handle serves every level); D the product
+ * of those l primes; Delta = scale, any finite double > 0.
+ * Layouts.  d_z dense [batch][s] of (re, im) pairs of doubles, 8-byte aligned; d_out and d_x dense [l][batch][n], slab i under plan prime q_first + i.
+ * The transform in closed form, zeta' = exp(i pi / (2s)):
+ *   decode  z_j = (1 / Delta) sum_{k < 2s} X_{k gap} zeta'^(5^j k), j < s, X the centred representative modulo D; coefficients off the gap grid are ignored.
+ *   encode  w_k = (1 / s) sum_{j < s} z_j zeta'^(-5^j k), k < s;  X_{k gap} = rint(Delta Re w_k), X_{(k + s) gap} = rint(Delta Im w_k), every other coefficient 0.
+ * Slot j sits at the root zeta^(5^j): agx_ntt_automorphism with g = agx_ntt_galois_element(n, r) rotates full slots left by r, g = 2n - 1 conjugates them.
+ * The definition is a fixed operation graph in IEEE double; no step is contracted or reassociated, so a float64 model that follows it gives the same bits
+ * (tests/ckks_ref.py), and the definition is the contract, word for word.
+ *   Twiddles.  tw(len, j) = (cos theta, sin theta), theta = 2 pi (5^j mod 4 len) / (4 len): what agx_ntt_ckks_twiddle returns, for len a power of two in
+ *     [2, 16384] and j < len / 2 (anything else, AGX_ERR_BAD_ARGUMENT; out NULL: AGX_ERR_NULL_POINTER).  Each component within 2^-53 absolute of the real
+ *     value: the angle is reduced exactly in integers to an octant, cosine and sine taken in long double and rounded once.  The value depends on neither n
+ *     nor s: one table of n / 2 - 1 entries, indexed len / 2 + j, serves every slot count.
+ *   Complex arithmetic.  a b = (a_r b_r - a_i b_i, a_r b_i + a_i b_r): four products, two sums.  The conjugate twiddle is (cos theta, -sin theta).
+ *   Decode core (forward special FFT).  v_k = (x_k, x_{k+s}) for k < s, x the doubles below; bit-reverse v; for len = 2, 4, ..., s, every block start i and
+ *     every j < len / 2:  u = v[i+j], w = v[i+j+len/2] tw(len, j), v[i+j] = u + w, v[i+j+len/2] = u - w;  z_j = v_j (1 / Delta): one product per component by
+ *     the double 1 / Delta.
+ *   Encode core (inverse special FFT).  v = z; for len = s, s / 2, ..., 2:  u = v[i+j] + v[i+j+len/2], w = (v[i+j] - v[i+j+len/2]) conj tw(len, j), stored in
+ *     their places; bit-reverse; multiply by 1 / s (exact); x = fl(Delta component); c = rint(x), ties to even, a non-finite x giving c = 0; the residue is
+ *     c mod q_i in [0, q_i), for ANY finite double: from |x| = 2^63 on x is an integer mant 2^e with mant its 53-bit significand, and the residue is
+ *     mant (2^e mod q_i) mod q_i, the second factor from a table that only those words index past its first entry.
+ *   RNS -> double (decode's input).  (1) The mixed-radix (Garner) digits of X mod D = v_1 + v_2 q_1 + v_3 q_1 q_2 + ..., v_i in [0, q_i), exact, with
+ *     word-size Shoup products.  (2) X is negative iff (v_l, ..., v_1) is greater than ((q_l - 1) / 2, ..., (q_1 - 1) / 2) compared from the top: those are
+ *     exactly the digits of (D - 1) / 2.  (3) For a negative X the magnitude digits are q_i - 1 - v_i, plus 1 with a carry from the bottom.  (4) Horner from the
+ *     top in double: acc = (double)w_l, then acc = acc (double)q_i + (double)w_i for i = l - 1 down to 1, every conversion rounding to nearest even.  (5) The
+ *     sign.  The Garner constants of a prefix are a prefix of the handle's triangular table.
+ * Handle.  It belongs to one plan, as a basis does: it holds tables (the twiddles, the Garner constants, 2^e mod q_i for e < 1024) and a pointer to the plan,
+ * which must outlive it; the plan's device must be current at creation and at every call; agx_ntt_plan_set_variant between calls stays legal.  The handle type
+ * is named by its struct tag, `struct agx_ntt_ckks`.
+ *   create : NULL: AGX_ERR_NULL_POINTER; q_count == 0 or above AGX_BASIS_MAX_SRC = 16, a range past P: AGX_ERR_BAD_ARGUMENT; two equal moduli in the range:
+ *            AGX_ERR_BAD_MODULUS.  On any failure the out-pointer is cleared.
+ *   destroy: NULL is fine.
+ *   info   : any out-pointer may be NULL; max_slots = n / 2; under the plan's CURRENT variant launches_encode_ntt = 1 + the plan's forward launches and
+ *            launches_decode_ntt = the plan's inverse launches + 1.  AGX_FORM_COEFF is ONE launch on every plan, both ways.
+ * Call rules, agx_ntt_plain_*'s status order: a NULL pointer (decode's d_scratch only in NTT form): AGX_ERR_NULL_POINTER; count == 0 or above q_count; slots
+ * not a power of two in [1, n / 2]; scale not finite or <= 0; an unknown form; the plan's device not current; a pointer not 8-byte aligned; a batch past the
+ * grid limit or an extent past 2^60 words; encode: d_z touching d_out; decode: d_z touching d_x or the scratch, the scratch touching d_x without being d_x:
+ * AGX_ERR_BAD_ARGUMENT, nothing written; NTT-form decode on a plan without inverse tables: AGX_ERR_NO_INVERSE; batch == 0: AGX_OK, nothing launched.
+ * Asynchronous on `stream`; they allocate and synchronise nothing and touch no plan state (capturable into a hipGraph).
+ * Routes.  encode: ONE kernel does the FFT, the rounding and all l residues, 16 s + 8 n l bytes per frame; AGX_FORM_NTT adds agx_ntt_forward_range in place on
+ * d_out.  decode: with AGX_FORM_NTT the plan's inverse runs on the range into d_scratch (l batch n words; it may be exactly d_x, which is then given up,
+ * agx_ntt_plain_scale_down's rules; the input may be reduced or lazy), then ONE kernel does Garner, the FFT and the store; AGX_FORM_COEFF takes fully reduced
+ * words, is one launch, never looks at d_scratch (it may be NULL) and leaves d_x unchanged.
+ * Kernel shape (csrc/ckks_kernels.hpp).  One workgroup per frame, s / 4 threads within [64, 1024]; register-blocked radix-8 passes (a thread holds eight
+ * complex values at one stride and does three stages on them; the last pass takes what is left), a workgroup barrier between passes; the exchange goes through
+ * LDS as separate real and imaginary planes of s doubles: up to s = 8192, 128 KiB.  s = 16384 (n = 32768, full slots, 256 KiB) takes another route: the same
+ * passes exchange through the frame's own output words in global memory (decode: its d_z frame; encode: its frame of slab 0, whose n words are s pairs of
+ * doubles), which no other workgroup touches, and encode moves every component off those words (the real ones into LDS, the imaginary ones into registers) and passes
+ * one more barrier before the residues overwrite them.  The grouping of stages into passes changes no bit: the radix-2 graph fixes every rounding.
+ * Measured (profiles/r20_ckks_boundary.md, tools/run_op.py --op ckks; full slots, Delta = 2^40, l = 1, 2, 4 60-bit primes, n = 4096 with 4,096 frames and n = 16384 with 1,024,
+ * beside a device copy of 16 s + 8 n l bytes per frame and the plan's transforms alone on the same slabs): in coefficient form encode takes 1.76 ... 4.19 and decode 1.73 ... 3.73 of
+ * the copy's time (l = 4 at n = 4096: 218 and 247 us against 124), the ratios falling as l grows for encode; both are bound by the FFT's passes and, decode at l = 4, by Garner's
+ * O(l^2) products, not by their traffic.  In NTT form encode takes 1.18 ... 1.90 of the plan's forward plus the copy, decode 1.16 ... 1.56 of the plan's inverse plus the copy.
+ * Out of scope: group forms; more than 16 primes per handle (two handles serve a longer chain); real-only or conjugate-invariant packings; BGV decryption. */
+struct agx_ntt_ckks;
+AGX_API int agx_ntt_ckks_create(struct agx_ntt_ckks** h, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count);
+AGX_API int agx_ntt_ckks_destroy(struct agx_ntt_ckks* h);
+AGX_API int agx_ntt_ckks_info(const struct agx_ntt_ckks* h, uint32_t* q_first, uint32_t* q_count, uint32_t* max_slots, int* launches_encode_ntt,
+                              int* launches_decode_ntt);
+AGX_API int agx_ntt_ckks_encode(const struct agx_ntt_ckks* h, const double* d_z, uint32_t slots, double scale, uint64_t* d_out, uint64_t batch, uint32_t count,
+                                int out_form, void* stream);
+AGX_API int agx_ntt_ckks_decode(const struct agx_ntt_ckks* h, const uint64_t* d_x, int in_form, uint32_t count, double scale, double* d_z, uint32_t slots,
+                                uint64_t* d_scratch, uint64_t batch, void* stream);
+AGX_API int agx_ntt_ckks_twiddle(uint32_t len, uint32_t j, double out[2]);
 
 /* ------------------------------------------------------------------------- */
 /* (5) Groups: the same calls over several GPUs of one node.                    */

@@ -7,6 +7,7 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op bfvconv --src S --dst T [--only {all,exact,mont,parent,copy} --reps 7 ...]   (agx_ntt_basis_extend_exact / _mont, coefficient form, beside agx_ntt_basis_extend into T + 1 targets and a copy of the model's bytes)
        python3 tools/run_op.py --op quotient --qcount L --src K [--only {all,quotient,composition,copy} --reps 7 ...]   (agx_ntt_basis_quotient beside the six-call composition it replaces and a copy of its model bytes)
        python3 tools/run_op.py --op plain --qcount L [--reps 7 ...]   (agx_ntt_plain_scale_down, _scale_up and _lift in both forms beside a copy of each call's model bytes and the plan's inverse / forward alone)
+       python3 tools/run_op.py --op ckks --qcount L [--reps 7 ...]   (agx_ntt_ckks_encode and _decode with full slots in both forms beside a copy of the call's model bytes and the plan's forward / inverse alone)
        python3 tools/run_op.py --op sample --kind {uniform,ternary,cbd} [--primes L --eta 21 --reps 7 ...]   (agx_ntt_sample_*: a draw, in both forms for the small kinds, beside a device fill of the same bytes and the plan's forward;
                                                                    uniform also under the primes just above 2^60, where every cell takes two blocks or more)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
@@ -31,7 +32,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient", "plain", "sample"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient", "plain", "sample", "ckks"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -86,6 +87,8 @@ if args.op == "quotient":
     args.primes = args.qcount + args.src + 1      # Q = [0, L), B = [L, L + K), the auxiliary prime L + K
 if args.op == "plain":
     args.primes = args.qcount + 1      # Q = [0, L), gamma = L
+if args.op == "ckks":
+    args.primes = args.qcount      # the handle's primes [0, L), every one in use
 args.only = args.only or ("all" if args.op in ("moddown", "bfvconv", "quotient") else "both")
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
 if args.variant is not None:
@@ -452,6 +455,61 @@ def run_plain():
 
         json.dump({"us": times, "launches": args.launches, "kernel_launches": {"scale_down": info[4], "ntt_form": info[5]}, "model_bytes": 16.0 * half}, open(args.report, "w"))
     plain.close()
+    plan.close()
+
+
+def run_ckks():
+    """agx_ntt_ckks_encode and agx_ntt_ckks_decode with full slots (s = n / 2), scale 2^40 and l = --qcount primes, in both forms, alternating in one process
+    with the plan's forward and inverse alone on the same slabs (agx_ntt_forward_range / agx_ntt_inverse_range, in place) and with a device copy of a call's
+    model bytes, 16 s + 8 n l per frame.  The slots are uniform in the unit square; decode reads what encode wrote (NTT-form decode gives up its operand, so
+    its groups run on what the last call left: any words serve).  Prints us per call: median (min ... max) of --reps groups of --launches calls."""
+    import statistics
+
+    L, n, batch, s, scale = args.qcount, args.n, args.batch, args.n // 2, 2.0 ** 40
+    ck = plan.ckks(0, L)
+    words = batch * n
+    z = torch.rand(2 * batch * s, dtype=torch.float64, device="cuda") * 2 - 1
+    back = torch.empty_like(z)
+    out = torch.empty(L * words, dtype=torch.int64, device="cuda")
+    hat = torch.empty(L * words, dtype=torch.int64, device="cuda")
+    half = (2 * batch * s + L * words) // 2      # a copy reads and writes this many words: together the model's bytes of one call
+    c_src, c_dst = (torch.empty(half, dtype=torch.int64, device="cuda") for _ in range(2))
+    ck.encode(z.data_ptr(), s, scale, hat.data_ptr(), batch, L, agx.FORM_NTT, stream)
+
+    def encode_coeff():
+        ck.encode(z.data_ptr(), s, scale, out.data_ptr(), batch, L, agx.FORM_COEFF, stream)
+
+    def encode_ntt():
+        ck.encode(z.data_ptr(), s, scale, hat.data_ptr(), batch, L, agx.FORM_NTT, stream)
+
+    def decode_coeff():
+        ck.decode(out.data_ptr(), agx.FORM_COEFF, L, scale, back.data_ptr(), s, None, batch, stream)
+
+    def decode_ntt():
+        ck.decode(hat.data_ptr(), agx.FORM_NTT, L, scale, back.data_ptr(), s, hat.data_ptr(), batch, stream)
+
+    def forward():
+        plan.forward_range(hat.data_ptr(), hat.data_ptr(), batch, 0, L, stream)
+
+    def inverse():
+        plan.inverse_range(hat.data_ptr(), hat.data_ptr(), batch, 0, L, stream)
+
+    def copy():
+        c_dst.copy_(c_src)
+
+    times = _alternate([encode_coeff, decode_coeff, encode_ntt, decode_ntt, forward, inverse, copy])
+    info = ck.info()
+    print(f"ckks n={n} l={L} batch={batch} bits={args.bits} slots={s} launches encode ntt {info[3]} decode ntt {info[4]}; model bytes per call {16 * half}:")
+    for name, v in times.items():
+        print(f"  {name} {_fmt(v)} us")
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(f"  encode_coeff/copy {med['encode_coeff'] / med['copy']:.3f}  decode_coeff/copy {med['decode_coeff'] / med['copy']:.3f};  "
+          f"encode_ntt/(forward + copy) {med['encode_ntt'] / (med['forward'] + med['copy']):.3f}  decode_ntt/(inverse + copy) {med['decode_ntt'] / (med['inverse'] + med['copy']):.3f}")
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "kernel_launches": {"encode_ntt": info[3], "decode_ntt": info[4]}, "model_bytes": 16.0 * half}, open(args.report, "w"))
+    ck.close()
     plan.close()
 
 
@@ -1077,6 +1135,9 @@ if args.op == "plain":
     sys.exit(0)
 if args.op == "sample":
     run_sample()
+    sys.exit(0)
+if args.op == "ckks":
+    run_ckks()
     sys.exit(0)
 slabs = [torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(args.slabs)]
 for i, s in enumerate(slabs):
