@@ -115,6 +115,13 @@ ABI = {
     "agx_ntt_ckks_encode": (_int, [_vp, _vp, _u32, _dbl, _vp, _u64, _u32, _int, _vp]),
     "agx_ntt_ckks_decode": (_int, [_vp, _vp, _int, _u32, _dbl, _vp, _u32, _vp, _u64, _vp]),
     "agx_ntt_ckks_twiddle": (_int, [_u32, _u32, ctypes.POINTER(_dbl)]),
+    "agx_ntt_batch_create": (_int, [ctypes.POINTER(_vp), _u32, _u64]),
+    "agx_ntt_batch_destroy": (_int, [_vp]),
+    "agx_ntt_batch_info": (_int, [_vp, ctypes.POINTER(_u32), _p64, _p64, ctypes.POINTER(_int), ctypes.POINTER(_int)]),
+    "agx_ntt_batch_plan": (_int, [_vp, ctypes.POINTER(_vp)]),
+    "agx_ntt_batch_encode": (_int, [_vp, _vp, _vp, _u64, _vp]),
+    "agx_ntt_batch_decode": (_int, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "agx_ntt_plain_reduce": (_int, [_vp, _vp, _vp, _vp, _u64, _u64, _vp]),
     # groups: the same calls over several GPUs (one shard, one host thread, one stream per listed device)
     "agx_ntt_shard_range": (_int, [_u64, _u32, _u32, _p64, _p64]),
     "agx_ntt_group_create": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_int), _u32, _u32, _u32, _p64, _p64, _p64, _p64, _p64]),
@@ -664,9 +671,55 @@ class Plain:
         fraction lies within 1/2 - q_count / gamma of an integer; d_scratch: q_count*batch*n words, or d_x itself (which is then overwritten)"""
         _check(lib().agx_ntt_plain_scale_down(self._h, d_x, d_m, d_scratch, batch, stream), "plain_scale_down")
 
+    def reduce(self, d_x, d_m, d_scratch, batch, factor=1, stream=0):
+        """BGV decryption, the exact centred conversion Q -> t: d_x [q_count][batch][n] in NTT form (reduced or lazy) -> d_m [batch][n] = (factor mod t) X mod t
+        in [0, t), X the centred representative modulo D; exact for every t; d_scratch as scale_down's"""
+        _check(lib().agx_ntt_plain_reduce(self._h, d_x, d_m, d_scratch, factor, batch, stream), "plain_reduce")
+
     def close(self):
         if self._h:
             lib().agx_ntt_plain_destroy(self._h)
+            self._h = _vp(None)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Batch:
+    """SIMD batching of BFV / BGV (agx_ntt_batch_*): n slots modulo a prime t = 1 (mod 2n), t < 2^62, <-> the plaintext polynomial with those values at
+    psi^(e_j), e_j = 5^j mod 2n on row 0 and 2n - e_j on row 1.  The handle owns a one-prime plan under t on the device current here, which must be current at
+    every call."""
+
+    def __init__(self, n, t):
+        self._h = _vp(None)
+        _check(lib().agx_ntt_batch_create(ctypes.byref(self._h), n, t), "batch_create")
+
+    def info(self):
+        """(n, t, psi, launches_encode, launches_decode) under the inner plan's current variant"""
+        n, t, psi, enc, dec = _u32(0), _u64(0), _u64(0), _int(0), _int(0)
+        _check(lib().agx_ntt_batch_info(self._h, ctypes.byref(n), ctypes.byref(t), ctypes.byref(psi), ctypes.byref(enc), ctypes.byref(dec)), "batch_info")
+        return n.value, t.value, psi.value, enc.value, dec.value
+
+    def plan(self):
+        """the inner plan's raw handle, lent: for products modulo t and agx_ntt_plan_set_variant; the Batch owns it"""
+        p = _vp(None)
+        _check(lib().agx_ntt_batch_plan(self._h, ctypes.byref(p)), "batch_plan")
+        return p.value
+
+    def encode(self, d_z, d_m, batch, stream=0):
+        """d_z [batch][n] slots, any words (taken modulo t) -> d_m [batch][n] in [0, t): the polynomial with those slot values; out of place"""
+        _check(lib().agx_ntt_batch_encode(self._h, d_z, d_m, batch, stream), "batch_encode")
+
+    def decode(self, d_m, d_z, d_scratch, batch, stream=0):
+        """d_m [batch][n] in [0, t) -> d_z [batch][n]: z_j = m(psi^(e_j)); d_scratch: batch*n words, or d_m itself (which is then overwritten)"""
+        _check(lib().agx_ntt_batch_decode(self._h, d_m, d_z, d_scratch, batch, stream), "batch_decode")
+
+    def close(self):
+        if self._h:
+            lib().agx_ntt_batch_destroy(self._h)
             self._h = _vp(None)
 
     def __del__(self):

@@ -1,7 +1,8 @@
 // agx_rns.cpp -- the RNS calls of include/agx_ntt.h: rescale, basis extension and ModDown, the inner products, the ring arithmetic on a range of the
 // plan's primes (add, sub, negate, add_galois, tensor, mul_add_galois: one streaming kernel each) and the key switch, whole, in two halves, and with its
 // second half in two (accumulate_decomposed: the weighted, accumulating inner product; keyswitch_mod_down), and BFV's plaintext boundary (agx_ntt_plain_*:
-// scale_up, lift, scale_down) and the samplers (agx_ntt_sample_*: one streaming kernel each, at the end of the file).  Each of the others composes the
+// scale_up, lift, scale_down, and reduce: BGV decryption), the samplers (agx_ntt_sample_*: one streaming kernel each), CKKS encoding and, at the end of the
+// file, batching (agx_ntt_batch_*: a handle that owns its own one-prime plan).  Each of the others composes the
 // plan's transforms (run_forward / run_inverse on views of its routes, plan_internal.hpp) with a coefficient-domain or fused kernel; plans, routes and
 // the transform calls themselves live in agx_ntt.cpp.
 #include <cstdlib>
@@ -728,15 +729,35 @@ static int instantiate_plain(agx_ntt_plain** out, const agx_ntt_plan* plan, uint
     int rc = AGX_OK;
     auto put = [&](device_buf<ulonglong2>& to, const std::vector<shoup_pair>& pairs) { if (rc == AGX_OK) rc = upload_pairs(to, pairs); };
     put(p->d_up, img.up), put(p->d_one, img.one), put(p->d_row_t, img.row_t), put(p->d_row_g, img.row_g);
+    put(p->d_radix_t, img.radix_t);
+    if (!img.tri.empty()) put(p->d_tri, img.tri);      // one prime has no Garner constant
+    if (rc == AGX_OK) rc = p->d_q.upload(img.q);
     if (rc == AGX_OK) rc = p->d_src_consts.upload(sc);
     if (rc) return rc;
     plain_view& v = p->view;
+    v.q = p->d_q, v.tri = p->d_tri, v.radix_t = p->d_radix_t;
     v.up = p->d_up, v.one = p->d_one, v.row_t = p->d_row_t, v.row_g = p->d_row_g;
     v.t = t, v.h = img.h, v.one_p = img.one_t.p, v.d = img.d_t.w, v.dp = img.d_t.p;
     v.gamma = plan->moduli[gamma_prime], v.g = img.g_t.w, v.gp = img.g_t.p;
     v.q_first = q_first, v.q_count = q_count;
     *out = p.release();
     return AGX_OK;
+}
+
+// agx_ntt_plain_scale_down and agx_ntt_plain_reduce: one statement of their rules, agx_ntt_basis_quotient's in its order, up to the empty batch (the caller's)
+static int plain_down_rules(const agx_ntt_plain* h, const uint64_t* d_x, const uint64_t* d_m, const uint64_t* d_scratch, uint64_t batch) {
+    if (!h || !d_x || !d_m || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = h->plan;
+    if (int rc = check_plan(plan)) return rc;
+    const uint32_t L = h->view.q_count;
+    if (!aligned8(d_x) || !aligned8(d_m) || !aligned8(d_scratch) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    const frame_layout fl = dense(plan, batch);      // of x and the scratch ([L][batch][n]) and of m ([1][batch][n]) alike
+    if (!dense_fits(plan->n, L, batch)) return AGX_ERR_BAD_ARGUMENT;
+    // the scratch IS x (the inverse then runs in place, as agx_ntt_inverse may) or touches none of it; m touches neither
+    const uint64_t slab = (uint64_t)fl.prime_stride;
+    if (d_scratch != d_x && ranges_touch(addr(d_scratch), L * slab, addr(d_x), L * slab)) return AGX_ERR_BAD_ARGUMENT;
+    if (ranges_touch(addr(d_m), slab, addr(d_x), L * slab) || ranges_touch(addr(d_m), slab, addr(d_scratch), L * slab)) return AGX_ERR_BAD_ARGUMENT;
+    return plan->has_inverse ? AGX_OK : AGX_ERR_NO_INVERSE;
 }
 
 // agx_ntt_plain_scale_up and _lift: one statement of the rules, in extend_call's order.  Out of place only: d_out's L slabs touch d_m nowhere.
@@ -808,28 +829,32 @@ int agx_ntt_plain_lift(const agx_ntt_plain* h, const uint64_t* d_m, uint64_t* d_
     return plain_encode_call(h, true, d_m, d_out, batch, out_form, stream);
 }
 
-// The rounding of decryption: the scaled inverse of the Q slabs into the scratch, ONE streaming kernel.  agx_ntt_basis_quotient's rules in its order.
+// The rounding of decryption: the scaled inverse of the Q slabs into the scratch, ONE streaming kernel.
 int agx_ntt_plain_scale_down(const agx_ntt_plain* h, const uint64_t* d_x, uint64_t* d_m, uint64_t* d_scratch, uint64_t batch, void* stream) {
-    if (!h || !d_x || !d_m || !d_scratch) return AGX_ERR_NULL_POINTER;
-    const agx_ntt_plan* plan = h->plan;
-    if (int rc = check_plan(plan)) return rc;
-    const plain_view& cv = h->view;
-    const uint32_t L = cv.q_count;
-    if (!aligned8(d_x) || !aligned8(d_m) || !aligned8(d_scratch) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
-    const frame_layout fl = dense(plan, batch);      // of x and the scratch ([L][batch][n]) and of m ([1][batch][n]) alike
-    if (!dense_fits(plan->n, L, batch)) return AGX_ERR_BAD_ARGUMENT;
-    // the scratch IS x (the inverse then runs in place, as agx_ntt_inverse may) or touches none of it; m touches neither
-    const uint64_t slab = (uint64_t)fl.prime_stride;
-    if (d_scratch != d_x && ranges_touch(addr(d_scratch), L * slab, addr(d_x), L * slab)) return AGX_ERR_BAD_ARGUMENT;
-    if (ranges_touch(addr(d_m), slab, addr(d_x), L * slab) || ranges_touch(addr(d_m), slab, addr(d_scratch), L * slab)) return AGX_ERR_BAD_ARGUMENT;
-    if (!plan->has_inverse) return AGX_ERR_NO_INVERSE;
+    if (int rc = plain_down_rules(h, d_x, d_m, d_scratch, batch)) return rc;
     if (batch == 0) return AGX_OK;
+    const agx_ntt_plan* plan = h->plan;
+    const plain_view& cv = h->view;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // scratch <- y_i = INTT_i(x_i) gamma t Q_i^-1 mod q_i in [0, q_i): the plan's inverse on the view of Q, its last-stage constants the handle's
-    route scaled = prime_range(plan->routes.inverse, cv.q_first, cv.q_first + L);
+    route scaled = prime_range(plan->routes.inverse, cv.q_first, cv.q_first + cv.q_count);
     scaled.consts = h->d_src_consts;
-    AGX_HIP(run_inverse(scaled, d_x, nullptr, d_scratch, fl, s));
+    AGX_HIP(run_inverse(scaled, d_x, nullptr, d_scratch, dense(plan, batch), s));
     AGX_HIP(launch_plain_scale_down(plan->routes.forward, cv, d_scratch, d_m, batch, s));
+    return AGX_OK;
+}
+
+// BGV decryption, the exact centred conversion Q -> t: the plan's inverse of the Q slabs into the scratch (its own constants: nothing is folded in), ONE
+// streaming kernel.  factor's constants are formed here, per call.
+int agx_ntt_plain_reduce(const agx_ntt_plain* h, const uint64_t* d_x, uint64_t* d_m, uint64_t* d_scratch, uint64_t factor, uint64_t batch, void* stream) {
+    if (int rc = plain_down_rules(h, d_x, d_m, d_scratch, batch)) return rc;
+    if (batch == 0) return AGX_OK;
+    const agx_ntt_plan* plan = h->plan;
+    const plain_view& cv = h->view;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint64_t f = factor % cv.t;
+    AGX_HIP(run_inverse(prime_range(plan->routes.inverse, cv.q_first, cv.q_first + cv.q_count), d_x, nullptr, d_scratch, dense(plan, batch), s));
+    AGX_HIP(launch_plain_centred_reduce(plan->routes.forward, cv, d_scratch, d_m, f, shoup_quotient(f, cv.t), batch, s));
     return AGX_OK;
 }
 
@@ -996,6 +1021,96 @@ int agx_ntt_ckks_decode(const agx_ntt_ckks* h, const uint64_t* d_x, int in_form,
 int agx_ntt_ckks_twiddle(uint32_t len, uint32_t j, double out[2]) {
     if (!out) return AGX_ERR_NULL_POINTER;
     return ckks_twiddle(len, j, out) ? AGX_OK : AGX_ERR_BAD_ARGUMENT;
+}
+
+}  // extern "C"
+
+// ---- agx_ntt_batch_*: SIMD batching of BFV / BGV (include/agx_ntt.h has the definition, batch_arith.hpp the per-word steps, host_math.hpp the tables) ----
+
+agx_ntt_batch::~agx_ntt_batch() { agx::free_plan(plan); }
+
+// the rules the two calls share behind the NULL rule, agx_ntt_plain_*'s order: the plan's device, alignment and the grid limit, the extent
+static int batch_call_rules(const agx_ntt_plan* plan, const void* a, const void* b, const void* c, uint64_t batch) {
+    if (int rc = check_plan(plan)) return rc;
+    if (!aligned8(a) || !aligned8(b) || !aligned8(c) || !batch_fits_grid(plan, batch)) return AGX_ERR_BAD_ARGUMENT;
+    return dense_fits(plan->n, 1, batch) ? AGX_OK : AGX_ERR_BAD_ARGUMENT;
+}
+
+extern "C" {
+
+// NULL; a size no plan admits, a bad argument; t at or above 2^62, not 1 modulo 2n or composite, a bad modulus; then whatever the plan's creation says
+int agx_ntt_batch_create(agx_ntt_batch** h, uint32_t n, uint64_t t) {
+    if (!h) return AGX_ERR_NULL_POINTER;
+    *h = nullptr;
+    if (check_size(n)) return AGX_ERR_BAD_ARGUMENT;
+    return guarded([&]() -> int {
+        batch_image img;
+        switch (prepare_batch_image(img, n, t)) {
+            case batch_fault::none: break;
+            case batch_fault::root: return AGX_ERR_BAD_ROOT;
+            default: return AGX_ERR_BAD_MODULUS;
+        }
+        std::unique_ptr<agx_ntt_batch> p(new (std::nothrow) agx_ntt_batch);
+        if (!p) return AGX_ERR_ALLOC;
+        if (int rc = agx_ntt_plan_create_auto(&p->plan, n, 1, &t, &img.psi)) return rc;
+        if (int rc = p->d_slot_to_word.upload(img.slot_to_word)) return rc;
+        if (int rc = p->d_word_to_slot.upload(img.word_to_slot)) return rc;
+        p->psi = img.psi;
+        p->view = batch_view{p->d_slot_to_word, p->d_word_to_slot, t, img.one_t.p};
+        *h = p.release();
+        return AGX_OK;
+    });
+}
+
+int agx_ntt_batch_destroy(agx_ntt_batch* h) {
+    delete h;      // the plan and the device memory go with their owner
+    return AGX_OK;
+}
+
+int agx_ntt_batch_info(const agx_ntt_batch* h, uint32_t* n, uint64_t* t, uint64_t* psi, int* launches_encode, int* launches_decode) {
+    if (!h) return AGX_ERR_NULL_POINTER;
+    if (n) *n = h->plan->n;
+    if (t) *t = h->view.t;
+    if (psi) *psi = h->psi;
+    if (launches_encode) *launches_encode = 1 + inverse_launches(h->plan);      // the permutation, then the inner plan's inverse in place
+    if (launches_decode) *launches_decode = forward_launches(h->plan) + 1;      // the inner plan's forward, then the permutation
+    return AGX_OK;
+}
+
+int agx_ntt_batch_plan(const agx_ntt_batch* h, agx_ntt_plan** plan) {
+    if (!h || !plan) return AGX_ERR_NULL_POINTER;
+    *plan = h->plan;
+    return AGX_OK;
+}
+
+// agx_ntt_plain_scale_up's rules in its order.  Out of place only: d_m touches d_z nowhere.
+int agx_ntt_batch_encode(const agx_ntt_batch* h, const uint64_t* d_z, uint64_t* d_m, uint64_t batch, void* stream) {
+    if (!h || !d_z || !d_m) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = h->plan;
+    if (int rc = batch_call_rules(plan, d_z, d_m, d_m, batch)) return rc;
+    const uint64_t words = batch * plan->n;
+    if (ranges_touch(addr(d_z), words, addr(d_m), words)) return AGX_ERR_BAD_ARGUMENT;
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // m <- the slots modulo t in the forward transform's order, then the inner plan's inverse in place
+    AGX_HIP(launch_batch_permute(plan->log_n, h->view, true, d_z, d_m, batch, s));
+    AGX_HIP(run_inverse(plan->routes.inverse, d_m, nullptr, d_m, dense(plan, batch), s));
+    return AGX_OK;
+}
+
+// agx_ntt_plain_scale_down's rules in its order: the scratch IS d_m (the forward then runs in place) or touches none of it; d_z touches neither.
+int agx_ntt_batch_decode(const agx_ntt_batch* h, const uint64_t* d_m, uint64_t* d_z, uint64_t* d_scratch, uint64_t batch, void* stream) {
+    if (!h || !d_m || !d_z || !d_scratch) return AGX_ERR_NULL_POINTER;
+    const agx_ntt_plan* plan = h->plan;
+    if (int rc = batch_call_rules(plan, d_m, d_z, d_scratch, batch)) return rc;
+    const uint64_t words = batch * plan->n;
+    if (d_scratch != d_m && ranges_touch(addr(d_scratch), words, addr(d_m), words)) return AGX_ERR_BAD_ARGUMENT;
+    if (ranges_touch(addr(d_z), words, addr(d_m), words) || ranges_touch(addr(d_z), words, addr(d_scratch), words)) return AGX_ERR_BAD_ARGUMENT;
+    if (batch == 0) return AGX_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    AGX_HIP(run_forward(forward_route(plan, batch), d_m, d_scratch, dense(plan, batch), s));
+    AGX_HIP(launch_batch_permute(plan->log_n, h->view, false, d_scratch, d_z, batch, s));
+    return AGX_OK;
 }
 
 }  // extern "C"

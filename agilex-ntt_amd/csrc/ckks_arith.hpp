@@ -19,6 +19,7 @@
 //                     (3) the digits of D - 1 are q_i - 1, so |X| = D - (X mod D) has the digits q_i - 1 - v_i, plus 1 with a carry from the bottom;
 //                     (4) Horner from the top in double, acc = acc (double)q_i + (double)w_i from acc = 0 (0 q + w = w exactly: the same bits as starting at
 //                         (double)w_{L-1}); every conversion rounds to nearest even, every product and sum is one operation; (5) the sign.
+//                     (1) and (2) are also functions of their own, ckks_garner_digits and ckks_digits_negative: plain_arith.hpp's plain_from_digits follows them.
 //                     tri: the triangular table, the pair of q_j^-1 mod q_i at [i (i - 1) / 2 + j], two words each: a prefix serves a prefix of the primes.
 #pragma once
 #include "bfv_conv_arith.hpp"
@@ -65,6 +66,37 @@ AGX_HD uint64_t ckks_residue(uint64_t mant, bool negative, uint64_t w, uint64_t 
     return negative && p ? q - p : p;                   // -0 = 0
 }
 
+// steps (1) and (2) of ckks_rns_to_double on their own: agx_ntt_plain_reduce (plain_arith.hpp) takes the same digits and the same sign to a residue modulo t
+template <int SMAX>
+AGX_HD void ckks_garner_digits(const uint64_t (&x)[SMAX], uint32_t L, const uint64_t* q, const uint64_t* tri, uint64_t (&v)[SMAX]) {
+#pragma unroll
+    for (int i = 0; i < SMAX; ++i) {
+        v[i] = 0;
+        if ((uint32_t)i < L) {
+            const uint64_t qi = q[i];
+            uint64_t t = x[i];
+#pragma unroll
+            for (int j = 0; j < i; ++j) {
+                const uint64_t c = tri[2 * (i * (i - 1) / 2 + j)], cp = tri[2 * (i * (i - 1) / 2 + j) + 1];
+                const uint64_t a = bfv_shoup(t, c, cp, qi), b = bfv_shoup(v[j], c, cp, qi);
+                t = a - b + (a < b ? qi : 0);
+            }
+            v[i] = t;
+        }
+    }
+}
+
+template <int SMAX>
+AGX_HD bool ckks_digits_negative(const uint64_t (&v)[SMAX], uint32_t L, const uint64_t* q) {
+    bool negative = false, decided = false;
+#pragma unroll
+    for (int i = SMAX - 1; i >= 0; --i)
+        if ((uint32_t)i < L && !decided && v[i] != (q[i] >> 1)) negative = v[i] > (q[i] >> 1), decided = true;
+    return negative;
+}
+
+// ckks_rns_to_double keeps steps (1) and (2) in its own body, the same statements as the two functions above: calling them here changed the code the compiler
+// generates for every ckks_decode_kernel instance (tools/compare_device_asm.py), and those kernels stay as they were measured.
 template <int SMAX>
 AGX_HD double ckks_rns_to_double(const uint64_t (&x)[SMAX], uint32_t L, const uint64_t* q, const uint64_t* tri) {
     uint64_t v[SMAX];

@@ -234,7 +234,21 @@ plain_fault prepare_plain_image(plain_image& img, const plain_request& rq) {
     img.one_t = shoup_pair::of(1, t);
     img.g_t = shoup_pair::of(g, t);
     img.h = t >> 1;
+    img.q.assign(rq.q, rq.q + L);
+    if (!garner_table(img.tri, rq.q, L)) return plain_fault::source;      // the moduli were found coprime above: not reached
+    for (uint32_t i = 0; i < L; ++i) img.radix_t.push_back(shoup_pair::of(product_mod(rq.q, i, i, t), t));
     return plain_fault::none;
+}
+
+bool garner_table(std::vector<shoup_pair>& tri, const uint64_t* q, uint32_t L) {
+    tri.clear();
+    for (uint32_t i = 1; i < L; ++i)
+        for (uint32_t j = 0; j < i; ++j) {
+            uint64_t w = 0;
+            if (!inv_mod_euclid(q[j] % q[i], q[i], &w)) return false;
+            tri.push_back(shoup_pair::of(w, q[i]));
+        }
+    return true;
 }
 
 bool ckks_twiddle(uint32_t len, uint32_t j, double out[2]) {
@@ -260,12 +274,7 @@ bool ckks_twiddle(uint32_t len, uint32_t j, double out[2]) {
 bool prepare_ckks_image(ckks_image& img, const uint64_t* q, uint32_t L, uint32_t n) {
     img = ckks_image{};
     img.q.assign(q, q + L);
-    for (uint32_t i = 1; i < L; ++i)
-        for (uint32_t j = 0; j < i; ++j) {
-            uint64_t w = 0;
-            if (!inv_mod_euclid(q[j] % q[i], q[i], &w)) return false;
-            img.tri.push_back(shoup_pair::of(w, q[i]));
-        }
+    if (!garner_table(img.tri, q, L)) return false;
     for (uint32_t i = 0; i < L; ++i) {
         uint64_t w = 1 % q[i];
         for (uint32_t e = 0; e < 1024; ++e) {
@@ -279,6 +288,25 @@ bool prepare_ckks_image(ckks_image& img, const uint64_t* q, uint32_t L, uint32_t
     for (uint32_t len = 2; len <= n / 2; len <<= 1)
         for (uint32_t j = 0; j < len / 2; ++j) ckks_twiddle(len, j, &img.tw[2 * (size_t)(len / 2 + j)]);
     return true;
+}
+
+batch_fault prepare_batch_image(batch_image& img, uint32_t n, uint64_t t) {
+    img = batch_image{};
+    const uint64_t M = 2ull * n;
+    if (t >= (1ull << 62) || t < 3 || (t - 1) % M || !is_prime_u64(t)) return batch_fault::modulus;
+    img.psi = min_primitive_root_2n(t, n);
+    if (!img.psi) return batch_fault::root;
+    img.one_t = shoup_pair::of(1, t);
+    const int lg = log2u(n);
+    img.slot_to_word.assign(n, 0), img.word_to_slot.assign(n, 0);
+    uint64_t e = 1;
+    for (uint32_t j = 0; j < n / 2; ++j) {
+        const uint32_t lo = bit_reverse((uint32_t)((e - 1) / 2), lg), hi = bit_reverse((uint32_t)((M - e - 1) / 2), lg);
+        img.slot_to_word[j] = lo, img.slot_to_word[n / 2 + j] = hi;
+        img.word_to_slot[lo] = j, img.word_to_slot[hi] = n / 2 + j;
+        e = e * 5 % M;
+    }
+    return batch_fault::none;
 }
 
 }  // namespace agx

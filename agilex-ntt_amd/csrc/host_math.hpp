@@ -134,6 +134,10 @@ struct plain_image {
     shoup_pair one_t = {0, 0};         // 1 mod t: its quotient floor(2^64 / t) reduces any 64-bit word modulo t
     shoup_pair g_t = {0, 0};           // gamma^-1 mod t
     uint64_t h = 0;                    // floor(t / 2)
+    // agx_ntt_plain_reduce (BGV decryption: the exact centred conversion Q -> t through mixed-radix digits; no inverse modulo t is formed, so any t serves)
+    std::vector<uint64_t> q;           // [L] the moduli of Q
+    std::vector<shoup_pair> tri;       // [L (L - 1) / 2] q_j^-1 mod q_i at i (i - 1) / 2 + j, j < i: Garner's constants, as ckks_image::tri
+    std::vector<shoup_pair> radix_t;   // [L] prod_{k < i} q_k mod t: the weight of digit i modulo t; entry 0 is 1 mod t
 };
 
 // Which rule refused a request, the first in this order; nothing is promised about the image then.
@@ -146,6 +150,10 @@ enum class plain_fault {
     t_gamma,     // t and gamma share a factor (for a prime gamma: gamma | t)
 };
 plain_fault prepare_plain_image(plain_image& img, const plain_request& rq);
+
+// Garner's constants of the moduli q[0 .. L), every one odd and > 1: the pair of q_j^-1 mod q_i at i (i - 1) / 2 + j for j < i (L (L - 1) / 2 pairs; a prefix
+// serves a prefix of the moduli).  false: two moduli share a factor; nothing is promised about the table then.
+bool garner_table(std::vector<shoup_pair>& tri, const uint64_t* q, uint32_t L);
 
 // agx_ntt_ckks_twiddle: tw(len, j) = (cos theta, sin theta), theta = 2 pi (5^j mod 4 len) / (4 len), for len a power of two in [2, 16384] and j < len / 2
 // (false otherwise, out untouched).  The angle is reduced exactly in integers to [0, pi / 4] (quadrant, then the complement within it), cosine and sine
@@ -162,5 +170,22 @@ struct ckks_image {
 };
 // false: two moduli share a factor (for primes: are equal); nothing is promised about the image then
 bool prepare_ckks_image(ckks_image& img, const uint64_t* q, uint32_t L, uint32_t n);
+
+// Everything a batching handle (agx_ntt_batch_*) derives from (n, t), built once on the host, for n a plan size (a power of two >= 2: the caller's check) and a prime t = 1 (mod 2n) below 2^62.
+// With M = 2n and the exponents e_j = 5^j mod M for j < n / 2, e_{n/2+j} = M - e_j: slot j is the value of the plaintext at psi^{e_j}, which a forward
+// transform in the library's order (out[brev(k)] = x(psi^{2k+1})) leaves at word pos(j) = brev((e_j - 1) / 2).  The e_j are the n odd residues modulo M, each
+// once, so both tables are permutations of [0, n).
+struct batch_image {
+    uint64_t psi = 0;                      // the least primitive 2n-th root of unity modulo t
+    shoup_pair one_t = {0, 0};             // 1 mod t: its quotient floor(2^64 / t) reduces any 64-bit word modulo t
+    std::vector<uint32_t> slot_to_word;    // [n] pos(j)
+    std::vector<uint32_t> word_to_slot;    // [n] its inverse
+};
+enum class batch_fault {
+    none,
+    modulus,     // t >= 2^62, t != 1 (mod 2n), or t composite
+    root,        // no primitive 2n-th root was found (min_primitive_root_2n's search bound)
+};
+batch_fault prepare_batch_image(batch_image& img, uint32_t n, uint64_t t);
 
 }  // namespace agx

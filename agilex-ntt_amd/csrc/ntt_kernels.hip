@@ -21,6 +21,7 @@
 #include "plain_kernels.hpp"           // agx_ntt_plain_scale_up / _lift / _scale_down
 #include "sample_kernels.hpp"          // agx_ntt_sample_uniform / _ternary / _cbd
 #include "ckks_kernels.hpp"            // agx_ntt_ckks_encode / _decode
+#include "batch_kernels.hpp"           // agx_ntt_batch_encode / _decode
 
 #include <algorithm>
 #include <cstdlib>
@@ -590,6 +591,35 @@ hipError_t launch_plain_scale_down(const plan_view& pv, const plain_view& cv, co
     return with_smax(cv.q_count, [&](auto smax) {
         return launch_stream(&plain_scale_down_kernel<smax>, per_prime, 1, s, y, m, cv.row_t, cv.row_g, cv.t, cv.gamma, cv.g, cv.gp, cv.q_count, per_prime);
     });
+}
+
+hipError_t launch_plain_centred_reduce(const plan_view& pv, const plain_view& cv, const uint64_t* y, uint64_t* m, uint64_t f, uint64_t fp, uint64_t batch, hipStream_t s) {
+    const uint64_t per_prime = batch << pv.log_n;
+    return with_smax(cv.q_count, [&](auto smax) {
+        return launch_stream(&plain_centred_reduce_kernel<smax>, per_prime, 1, s, y, m, cv.q, reinterpret_cast<const uint64_t*>(cv.tri), reinterpret_cast<const uint64_t*>(cv.radix_t),
+                             cv.t, cv.d, f, fp, cv.q_count, per_prime);
+    });
+}
+
+// Batching: one thread per word, or per pair of words where the contiguous side admits 16-byte accesses; no slots.  kBatchScatter names the side that ships:
+// false, the gathered READ (out[w] = in[tab[w]]).  Building with -DAGX_BATCH_SCATTER (the Makefile's EXTRA) gives the other side, contiguous loads and scattered
+// writes through the inverse table, for an A/B library: profiles/r21_batching.md has both beside a copy.
+#ifdef AGX_BATCH_SCATTER
+static constexpr bool kBatchScatter = true;
+#else
+static constexpr bool kBatchScatter = false;
+#endif
+
+hipError_t launch_batch_permute(uint32_t log_n, const batch_view& bv, bool encode, const uint64_t* in, uint64_t* out, uint64_t batch, hipStream_t s) {
+    const uint64_t words = batch << log_n;
+    // gathered: the table of the OUTPUT's order (encode writes words: word -> slot); scattered: the table of the INPUT's order (encode reads slots: slot -> word)
+    const uint32_t* tab = encode != kBatchScatter ? bv.word_to_slot : bv.slot_to_word;
+    const void* contiguous = kBatchScatter ? static_cast<const void*>(in) : static_cast<const void*>(out);
+    if ((reinterpret_cast<uintptr_t>(contiguous) & 15u) == 0)
+        return launch_stream(encode ? &batch_permute_kernel<true, true, kBatchScatter> : &batch_permute_kernel<false, true, kBatchScatter>, words >> 1, 1, s, in, out, tab, bv.t,
+                             bv.one_p, log_n, words >> 1);
+    return launch_stream(encode ? &batch_permute_kernel<true, false, kBatchScatter> : &batch_permute_kernel<false, false, kBatchScatter>, words, 1, s, in, out, tab, bv.t, bv.one_p,
+                         log_n, words);
 }
 
 // The CKKS boundary: one workgroup per frame, s / 4 threads within [64, 1024]; the planes in LDS up to 2^kCkksLdsLog slots, beyond (n = 32768 with full

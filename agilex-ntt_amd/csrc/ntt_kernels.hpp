@@ -61,6 +61,17 @@ struct plain_view {
     uint64_t d = 0, dp = 0;              // D mod t and its quotient
     uint64_t gamma = 0, g = 0, gp = 0;   // gamma; gamma^-1 mod t and its quotient
     uint32_t q_first = 0, q_count = 0;
+    // agx_ntt_plain_reduce
+    const uint64_t* q = nullptr;         // [L] the moduli of Q
+    const ulonglong2* tri = nullptr;     // [L (L - 1) / 2] {q_j^-1 mod q_i, quotient} at i (i - 1) / 2 + j: Garner's constants; null for L = 1
+    const ulonglong2* radix_t = nullptr; // [L] {prod_{k < i} q_k mod t, quotient}
+};
+
+// agx_ntt_batch_*: what a batching handle (n, t) hands its kernel: the two index tables on the device (host_math.hpp, batch_image) and t's reduction constant
+struct batch_view {
+    const uint32_t* slot_to_word = nullptr;   // [n] pos(j): decode reads the transformed words through it
+    const uint32_t* word_to_slot = nullptr;   // [n] its inverse: encode reads the slots through it
+    uint64_t t = 0, one_p = 0;                // one_p = floor(2^64 / t)
 };
 
 // agx_ntt_ckks_*: what a CKKS boundary (plan, the primes [q_first, q_first + q_count)) keeps on the device (ckks_arith.hpp has the formulas; host_math.hpp's
@@ -200,6 +211,12 @@ hipError_t launch_ckks_decode(uint32_t log_n, const ckks_view& cv, const uint64_
 enum sample_kind { SAMPLE_UNIFORM, SAMPLE_TERNARY, SAMPLE_CBD };
 hipError_t launch_sample(const plan_view& pv, sample_kind kind, const uint32_t key[8], uint64_t nonce, uint32_t eta, uint64_t* out, uint64_t batch, uint64_t frame_first,
                          uint32_t first, uint32_t count, hipStream_t s);
+// the coefficient-domain step of agx_ntt_plain_reduce: y dense [L][batch][n], y_i in [0, q_i) as the plan's inverse of the Q slabs left them -> m dense
+// [batch][n] = f X mod t in [0, t), X the centred representative, f < t with its quotient fp.  m touches y nowhere.  One launch.
+hipError_t launch_plain_centred_reduce(const plan_view& pv, const plain_view& cv, const uint64_t* y, uint64_t* m, uint64_t f, uint64_t fp, uint64_t batch, hipStream_t s);
+// the permutation of agx_ntt_batch_encode (encode = true: out[frame][w] = in[frame][word_to_slot[w]] mod t, any words in) and agx_ntt_batch_decode (out[frame][j]
+// = in[frame][slot_to_word[j]], moved as they are) on dense [batch][n] words; out touches in nowhere.  One launch; 16-byte stores when out is 16-byte aligned.
+hipError_t launch_batch_permute(uint32_t log_n, const batch_view& bv, bool encode, const uint64_t* in, uint64_t* out, uint64_t batch, hipStream_t s);
 hipError_t launch_fill(const plan_view& pv, uint64_t* out, uint64_t batch, uint64_t first_poly, uint64_t seed, hipStream_t s);
 
 }  // namespace agx

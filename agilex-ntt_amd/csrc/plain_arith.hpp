@@ -20,8 +20,14 @@
 //                   on an empty sum computes 0 - alpha c, so alpha = -(the value): the sign is handed over flipped.  -0 = 0 either way.
 //   plain_round     acc_t in [0, 2t) and acc_g in [0, 2 gamma) as quot_accumulate leaves them, gamma odd: acc_g is brought below gamma and centred
 //                   (|c| <= (gamma - 1) / 2 < 2^61, both edges as bfv_centre has them), then bfv_correct with the constant g: acc_t - c g mod t in [0, t).
+//   plain_from_digits   agx_ntt_plain_reduce (BGV decryption), after ckks_arith.hpp's Garner digits v_i in [0, q_i) of X mod D and its sign test: with the row
+//                   r_i = prod_{k < i} q_k mod t, X mod D = sum_i v_i prod_{k < i} q_k and the centred X is that, less D when negative, so
+//                   m = f ((sum_i v_i r_i) - [negative] (D mod t)) mod t.  quot_accumulate keeps the sum in [0, 2t) for ANY 64-bit v_i (a digit may exceed t);
+//                   one subtraction brings it below t, one more takes D mod t off, and ONE Shoup product by f = factor mod t gives [0, t).  No inverse
+//                   modulo t appears: an even t, a power of two and t = 2 serve as any other.
 #pragma once
 #include "bfv_quotient_arith.hpp"
+#include "ckks_arith.hpp"
 
 namespace agx {
 
@@ -44,6 +50,19 @@ AGX_HD uint64_t plain_round(uint64_t acc_t, uint64_t acc_g, uint64_t gamma, uint
     bool negative;
     const uint64_t mag = bfv_centre(acc_g >= gamma ? acc_g - gamma : acc_g, gamma, &negative);
     return bfv_correct(acc_t, mag, negative, g, gp, t);
+}
+
+// row: the pairs {r_i, quotient}, two words each (the host has no ulonglong2)
+template <int SMAX>
+AGX_HD uint64_t plain_from_digits(const uint64_t (&v)[SMAX], bool negative, uint32_t L, const uint64_t* row, uint64_t t, uint64_t d, uint64_t f, uint64_t fp) {
+    const uint64_t t2 = t << 1;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < SMAX; ++i)
+        if ((uint32_t)i < L) acc = quot_accumulate(acc, v[i], row[2 * i], row[2 * i + 1], t, t2);
+    uint64_t a = acc >= t ? acc - t : acc;
+    if (negative) a = a - d + (a < d ? t : 0);
+    return bfv_shoup(a, f, fp, t);
 }
 
 }  // namespace agx

@@ -1,5 +1,5 @@
 // plain_kernels.hpp -- the coefficient-domain kernels of agx_ntt_plain_scale_up / _lift (plain_encode_kernel) and of agx_ntt_plain_scale_down
-// (plain_scale_down_kernel).  Compiled in ntt_kernels.hip.  The shape of basis_coeff_kernels.hpp: one thread per (frame, coefficient), grid-stride over the
+// (plain_scale_down_kernel) and of agx_ntt_plain_reduce (plain_centred_reduce_kernel).  Compiled in ntt_kernels.hip.  The shape of basis_coeff_kernels.hpp: one thread per (frame, coefficient), grid-stride over the
 // batch x n coefficients, wave-uniform constants (scalar loads); dense layouts, no LDS, no barrier.  plain_arith.hpp has the formulas and the ranges.
 #pragma once
 #include "ntt_kernels.hpp"
@@ -46,6 +46,22 @@ __global__ void plain_scale_down_kernel(const uint64_t* __restrict__ y, uint64_t
                 acc_g = quot_accumulate(acc_g, yi, cg.x, cg.y, gamma, gamma2);
             }
         m[e] = plain_round(acc_t, acc_g, gamma, g, gp, t);
+    }
+}
+
+// agx_ntt_plain_reduce, the coefficient-domain step: y dense [S][batch][n], y_i in [0, q_i) as the plan's inverse of the Q slabs wrote them, -> m dense
+// [batch][n] in [0, t): m = f X mod t for the centred X.  A thread reads its S words, forms the Garner digits and the sign as CKKS decode does
+// (ckks_arith.hpp: S (S - 1) Shoup products), then S products modulo t through the row prod_{k < i} q_k mod t and one by f: 8 (S + 1) bytes per coefficient.
+// m touches y nowhere.
+template <int SMAX>
+__global__ void plain_centred_reduce_kernel(const uint64_t* __restrict__ y, uint64_t* __restrict__ m, const uint64_t* __restrict__ q, const uint64_t* __restrict__ tri,
+                                            const uint64_t* __restrict__ radix_t, uint64_t t, uint64_t d, uint64_t f, uint64_t fp, uint32_t S, uint64_t per_prime) {
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < per_prime; e += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t x[SMAX], v[SMAX];
+#pragma unroll
+        for (int i = 0; i < SMAX; ++i) x[i] = (uint32_t)i < S ? y[(uint64_t)i * per_prime + e] : 0;
+        ckks_garner_digits<SMAX>(x, S, q, tri, v);
+        m[e] = plain_from_digits<SMAX>(v, ckks_digits_negative<SMAX>(v, S, q), S, radix_t, t, d, f, fp);
     }
 }
 

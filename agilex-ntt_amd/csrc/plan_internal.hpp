@@ -159,7 +159,22 @@ struct agx_ntt_plain {
     uint32_t gamma_prime = 0;
     agx::device_buf<ulonglong2> d_up, d_one, d_row_t, d_row_g;
     agx::device_buf<agx::prime_consts> d_src_consts;
+    agx::device_buf<uint64_t> d_q;                   // agx_ntt_plain_reduce: the moduli, Garner's constants (empty for one prime), the digit weights modulo t
+    agx::device_buf<ulonglong2> d_tri, d_radix_t;
     agx::plain_view view;
+};
+
+// agx_ntt_batch_*: a batching handle (n, t) on the device it was made on.  It OWNS its one-prime plan under t (made by agx_ntt_plan_create_auto with the least
+// root and inverse tables; agx_ntt_batch_plan lends it) and the two index tables of a batch_image (host_math.hpp); the view is filled once.
+struct agx_ntt_batch {
+    agx_ntt_plan* plan = nullptr;
+    uint64_t psi = 0;
+    agx::device_buf<uint32_t> d_slot_to_word, d_word_to_slot;
+    agx::batch_view view;
+    agx_ntt_batch() = default;
+    agx_ntt_batch(const agx_ntt_batch&) = delete;
+    agx_ntt_batch& operator=(const agx_ntt_batch&) = delete;
+    ~agx_ntt_batch();      // agx_rns.cpp: the plan goes with its owner
 };
 
 // agx_ntt_ckks_*: the tables of one CKKS boundary (plan, the primes [q_first, q_first + q_count)) on the plan's device, and nothing of the plan but a pointer,

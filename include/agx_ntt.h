@@ -702,7 +702,7 @@ AGX_API int agx_ntt_keyswitch_mod_down(const agx_ntt_keyswitch* ks, uint64_t* d_
  * inverse on the same slabs (466 us against 318); less the inverse alone that is 1.12 ... 1.24 of the copy of its kernel's bytes, a difference of two medians: near its traffic, not
  * at it; which of its 2L + 1 products accounts for the rest was not measured.  agx_ntt_basis_quotient and agx_ntt_keyswitch_apply beside the parent commit's library in the same
  * session: 753 / 752 against 747 / 752 us and 3302 / 3294 against 3309 / 3309 us at n = 4096; the spreads overlap in all eight pairs.
- * Out of scope: BGV decryption (an exact centred Q -> t conversion); group forms (one
+ * BGV decryption, the exact centred conversion Q -> t, is agx_ntt_plain_reduce on this handle (section (6), below).  Out of scope: group forms (one
  * handle per shard, as for a basis); a fused NTT-form scale_up. */
 struct agx_ntt_plain;
 AGX_API int agx_ntt_plain_create(struct agx_ntt_plain** h, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count, uint32_t gamma_prime, uint64_t t);
@@ -826,7 +826,7 @@ AGX_API int agx_ntt_galois_element(uint32_t n, int64_t step, uint32_t* galois_el
  * beside a device copy of 16 s + 8 n l bytes per frame and the plan's transforms alone on the same slabs): in coefficient form encode takes 1.76 ... 4.19 and decode 1.73 ... 3.73 of
  * the copy's time (l = 4 at n = 4096: 218 and 247 us against 124), the ratios falling as l grows for encode; both are bound by the FFT's passes and, decode at l = 4, by Garner's
  * O(l^2) products, not by their traffic.  In NTT form encode takes 1.18 ... 1.90 of the plan's forward plus the copy, decode 1.16 ... 1.56 of the plan's inverse plus the copy.
- * Out of scope: group forms; more than 16 primes per handle (two handles serve a longer chain); real-only or conjugate-invariant packings; BGV decryption. */
+ * Out of scope: group forms; more than 16 primes per handle (two handles serve a longer chain); real-only or conjugate-invariant packings. */
 struct agx_ntt_ckks;
 AGX_API int agx_ntt_ckks_create(struct agx_ntt_ckks** h, const agx_ntt_plan* plan, uint32_t q_first, uint32_t q_count);
 AGX_API int agx_ntt_ckks_destroy(struct agx_ntt_ckks* h);
@@ -892,6 +892,74 @@ AGX_API int agx_ntt_group_rescale(const agx_ntt_group* group, const uint64_t* co
 AGX_API int agx_ntt_group_automorphism(const agx_ntt_group* group, const uint64_t* const* d_in, uint64_t* const* d_out, const uint64_t* batch,
                                        uint32_t galois_elt, int form);
 AGX_API int agx_ntt_group_synchronize(const agx_ntt_group* group);
+
+/* ------------------------------------------------------------------------- */
+/* (6) BFV / BGV from slots to slots: batching and exact BGV decryption.       */
+/* ------------------------------------------------------------------------- */
+/* A. SIMD batching for the integer schemes: a vector of n slots modulo t <-> the plaintext polynomial m that agx_ntt_plain_scale_up / _lift take and that
+ * agx_ntt_plain_scale_down / _reduce give back ("BFV with batching" and "BGV").  The slot order is the one that makes the rotations of
+ * agx_ntt_automorphism rotate: it is stated here, once, for the integer schemes, as the CKKS block above states it for CKKS.
+ * Definition (the contract, word for word).  M = 2n; t is prime, t = 1 (mod M), t < 2^62; psi = agx_ntt_min_root(t, n), which info returns.  Exponents:
+ * e_j = 5^j mod M for j < n / 2, and e_{n/2+j} = M - e_j.
+ *   decode  z_j = m(psi^{e_j}) mod t for j < n.  Input words lie in [0, t), as agx_ntt_plain_scale_down and agx_ntt_plain_reduce write them; larger words give
+ *           unspecified values and never an out-of-range access: no index is formed from data.
+ *   encode  the inverse of decode: d_z words are taken modulo t (ANY 64-bit word is accepted), d_m is written in [0, t).
+ * Layouts are dense [batch][n].  Slots 0 ... n / 2 - 1 are row 0, the rest are row 1.  In the library's NTT order (out[brev(k)] = x(psi^{2k+1}), brev over
+ * log2 n bits) slot j sits at word pos(j) = brev((e_j - 1) / 2).
+ * Properties.  (1) Slot-wise ring homomorphism: the slots of m + m' and of m m' mod (X^n + 1, t) are the slot-wise sums and products.  (2) sigma_g: X -> X^g
+ * with g = agx_ntt_galois_element(n, r) rotates BOTH rows left by r: the new slot j of a row is its old slot j + r mod n / 2 (e_j g = e_{j+r}).  (3) g = 2n - 1
+ * swaps the rows (e_j (M - 1) = M - e_j).  They hold for a ciphertext's plaintext as for m itself, so agx_ntt_automorphism and the hoisted rotations rotate slots.
+ * Handle.  It owns a one-prime plan under t on the device current at creation (agx_ntt_plan_create_auto(n, 1, &t, &psi), with inverse tables) -- NOT a prime of
+ * the caller's plan: a 17-bit t among 2^60 - c primes would take that plan off its specialised class -- and two uint32 index tables of n entries on the device,
+ * slot -> word and word -> slot, built once on the host.  That device must be current at every call.  The handle type is named by its struct tag.
+ *   create : NULL: AGX_ERR_NULL_POINTER; n not a size the plans admit: AGX_ERR_BAD_ARGUMENT; t composite, t != 1 (mod 2n) or t >= 2^62: AGX_ERR_BAD_MODULUS.
+ *            On any failure the out-pointer is cleared.
+ *   destroy: NULL is fine.
+ *   info   : any out-pointer may be NULL; launches_encode = 1 + the inner plan's inverse launches and launches_decode = the inner plan's forward launches + 1,
+ *            under the inner plan's CURRENT variant.
+ *   plan   : lends the inner plan, which the handle owns (never destroy it): for plaintext-side products modulo t and for agx_ntt_plan_set_variant.
+ * Call rules, agx_ntt_plain_*'s status order: a NULL pointer: AGX_ERR_NULL_POINTER; the handle's device not current; a pointer not 8-byte aligned; a batch past
+ * the grid limit or an extent past 2^60 words; an overlap rule broken: AGX_ERR_BAD_ARGUMENT, nothing written; batch == 0: AGX_OK, nothing launched.  d_z and d_m
+ * never touch each other.  decode's d_scratch (batch n words) may be exactly d_m, which is then given up (agx_ntt_plain_scale_down's rule); otherwise it touches
+ * d_m nowhere and d_m is left unchanged; d_z touches neither.  Asynchronous on `stream`; the calls allocate nothing and are capturable into a hipGraph.
+ * Routes.  encode: ONE streaming kernel (csrc/batch_kernels.hpp; it reads d_z through the word -> slot table, reduces modulo t by a precomputed reciprocal and
+ * writes d_m in contiguous runs), then the inner plan's inverse in place on d_m.  decode: the inner plan's forward from d_m into d_scratch, then the same kernel
+ * the other way: it reads d_scratch through slot -> word and writes d_z contiguously.  The kernel: no LDS, no barrier, the table read coalesced, grid-stride,
+ * 16-byte stores where the output is 16-byte aligned.  The READ is the gathered side in both directions, by the measurement below.
+ * Measured (profiles/r21_batching.md, tools/run_op.py --op batch; t = 65537, n = 4096 with 4,096 frames and n = 16384 with 1,024, beside the inner plan's transforms alone
+ * and a device copy of the permutation's 16 n bytes per frame): encode 135 us against an inner inverse of 52 and a copy of 32.5 at n = 4096, 237 against 59 and 32.7 at
+ * n = 16384; decode 133 against a forward of 48.6, and 217 against 50.  The permutation kernel (a call less its transform, a difference of two medians) takes 2.5 ... 2.6
+ * of the copy at n = 4096 and 5.1 ... 5.5 at n = 16384, far outside the copy's spread (under 2 %).  The gathered side was chosen by a number: the same kernel with
+ * contiguous 16-byte loads and scattered 8-byte writes (an A/B library built with -DAGX_BATCH_SCATTER, the two alternating in one session, two rounds) takes 4.1 of the
+ * copy for encode and 5.8 for decode at n = 4096 (133 and 188 us against 82 and 84), and 5.4 and 9.1 at n = 16384 (178 and 302 us against 176 and 167): gathered reads
+ * win or tie in all eight pairs and ship for both directions.  With equal bytes the side that moves 8 bytes at a bit-reversed stride decides the time, and the cost per
+ * word doubles from a 32 KiB frame to a 128 KiB one: that fits a bound on L2 sector traffic of the 8-byte accesses; no counter was collected to prove it.
+ *
+ * B. BGV decryption on the plaintext handle of section agx_ntt_plain_* above: the exact centred conversion Q -> t.
+ *   reduce  d_x dense [L][batch][n] in NTT form, reduced or lazy; X the representative of its coefficient form in [-(D - 1) / 2, (D - 1) / 2].  Per coefficient
+ *           m = (factor mod t) X mod t, in [0, t); d_m dense [batch][n].  Exact for every input and for EVERY t that agx_ntt_plain_create admits, even ones
+ *           included: no inverse modulo t is used.  factor = 1 is plain decryption (a BGV phase X = m + t e decrypts to m while |X| <= (D - 1) / 2);
+ *           factor = D_dropped mod t undoes the D_dropped^-1 mod t that agx_ntt_basis_mod_down_mode leaves in a BGV plaintext.
+ *           Scratch and overlap rules, status order and AGX_ERR_NO_INVERSE are agx_ntt_plain_scale_down's.  The handle's gamma_prime stays a required argument
+ *           of create and is not used by this call.
+ * Route.  The plan's inverse on the view of Q into the scratch (its own constants), then ONE streaming kernel, one thread per coefficient: the Garner digits
+ * v_i of X mod D (the steps of CKKS decode, csrc/ckks_arith.hpp), the sign by comparing them from the top with the digits (q_i - 1) / 2 of (D - 1) / 2, then
+ * sum_i v_i (prod_{k<i} q_k mod t) - [negative] (D mod t) modulo t, then one Shoup product by factor mod t, whose reciprocal the host forms per call.
+ * Measured (profiles/r21_batching.md; 60-bit primes, t = 65537, beside agx_ntt_plain_scale_down on the same slabs): 0.95 ... 0.99 of scale_down at L = 2 (245 us against
+ * 259 at n = 4096), 1.19 at L = 4 (560 against 472), 1.53 ... 1.57 at L = 8 (1415 against 903): less the plan's inverse, the kernel is at 1.05 ... 1.17 of a copy of its
+ * 8 (L + 1) bytes per coefficient at L = 2 and compute-bound from L = 4 on, by Garner's L (L - 1) products.  agx_ntt_keyswitch_apply and agx_ntt_plain_scale_down
+ * beside the parent commit's library in the same session, two rounds: 3257.8 / 3257.7 against 3256.2 / 3258.6 us and 463.5 / 462.6 against 461.5 / 464.1 us at
+ * n = 4096; the spreads overlap in all pairs.  Every kernel of the parent is textually identical in this tree (profiles/r21_batching_device_asm.txt).
+ * Out of scope: group forms (one handle per shard). */
+struct agx_ntt_batch;
+AGX_API int agx_ntt_batch_create(struct agx_ntt_batch** h, uint32_t n, uint64_t t);
+AGX_API int agx_ntt_batch_destroy(struct agx_ntt_batch* h);
+AGX_API int agx_ntt_batch_info(const struct agx_ntt_batch* h, uint32_t* n, uint64_t* t, uint64_t* psi, int* launches_encode, int* launches_decode);
+AGX_API int agx_ntt_batch_plan(const struct agx_ntt_batch* h, agx_ntt_plan** plan);
+AGX_API int agx_ntt_batch_encode(const struct agx_ntt_batch* h, const uint64_t* d_z, uint64_t* d_m, uint64_t batch, void* stream);
+AGX_API int agx_ntt_batch_decode(const struct agx_ntt_batch* h, const uint64_t* d_m, uint64_t* d_z, uint64_t* d_scratch, uint64_t batch, void* stream);
+AGX_API int agx_ntt_plain_reduce(const struct agx_ntt_plain* h, const uint64_t* d_x, uint64_t* d_m, uint64_t* d_scratch, uint64_t factor, uint64_t batch,
+                                 void* stream);
 
 #ifdef __cplusplus
 }

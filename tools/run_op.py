@@ -8,6 +8,8 @@ Usage: python3 tools/run_op.py --op {fwd,inv,mul,mulntt,rescale} [--n N --primes
        python3 tools/run_op.py --op quotient --qcount L --src K [--only {all,quotient,composition,copy} --reps 7 ...]   (agx_ntt_basis_quotient beside the six-call composition it replaces and a copy of its model bytes)
        python3 tools/run_op.py --op plain --qcount L [--reps 7 ...]   (agx_ntt_plain_scale_down, _scale_up and _lift in both forms beside a copy of each call's model bytes and the plan's inverse / forward alone)
        python3 tools/run_op.py --op ckks --qcount L [--reps 7 ...]   (agx_ntt_ckks_encode and _decode with full slots in both forms beside a copy of the call's model bytes and the plan's forward / inverse alone)
+       python3 tools/run_op.py --op batch --qcount L [--reps 7 ...]   (agx_ntt_batch_encode and _decode at t = 65537 beside the inner plan's inverse / forward alone and a copy of the permutation's 16 n bytes per frame;
+                                                                    agx_ntt_plain_reduce beside agx_ntt_plain_scale_down on the same L slabs)
        python3 tools/run_op.py --op sample --kind {uniform,ternary,cbd} [--primes L --eta 21 --reps 7 ...]   (agx_ntt_sample_*: a draw, in both forms for the small kinds, beside a device fill of the same bytes and the plan's forward;
                                                                    uniform also under the primes just above 2^60, where every cell takes two blocks or more)
        python3 tools/run_op.py --op inner --terms T [--outputs 2 --bcast --only {all,inner,copy,parent} --reps 7 ...]   (agx_ntt_inner_product beside a copy of its model traffic and pointwise-and-add)
@@ -32,7 +34,7 @@ import torch  # noqa: E402
 import agilex_ntt_amd as agx  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient", "plain", "sample", "ckks"], default="inv")
+ap.add_argument("--op", choices=["fwd", "inv", "mul", "mulntt", "rescale", "auto", "extend", "moddown", "bfvconv", "inner", "keyswitch", "hoist", "dhoist", "ring", "quotient", "plain", "sample", "ckks", "batch"], default="inv")
 ap.add_argument("--n", type=int, default=4096)
 ap.add_argument("--primes", type=int, default=4)
 ap.add_argument("--batch", type=int, default=4096)
@@ -89,6 +91,8 @@ if args.op == "plain":
     args.primes = args.qcount + 1      # Q = [0, L), gamma = L
 if args.op == "ckks":
     args.primes = args.qcount      # the handle's primes [0, L), every one in use
+if args.op == "batch":
+    args.primes = args.qcount + 1      # Q = [0, L), gamma = L, for the plaintext handle; the batching handle has a plan of its own
 args.only = args.only or ("all" if args.op in ("moddown", "bfvconv", "quotient") else "both")
 plan = agx.Plan(args.n, agx.find_primes(args.bits, args.n, args.primes))
 if args.variant is not None:
@@ -510,6 +514,75 @@ def run_ckks():
 
         json.dump({"us": times, "launches": args.launches, "kernel_launches": {"encode_ntt": info[3], "decode_ntt": info[4]}, "model_bytes": 16.0 * half}, open(args.report, "w"))
     ck.close()
+    plan.close()
+
+
+def run_batch():
+    """agx_ntt_batch_encode and agx_ntt_batch_decode (the scratch the operand) at t = 65537, alternating in one process with the inner plan's inverse and
+    forward alone on the same frames (agx_ntt_inverse / agx_ntt_forward on the plan agx_ntt_batch_plan lends, in place) and with a device copy of the
+    permutation's bytes, 16 n per frame; then agx_ntt_plain_reduce beside agx_ntt_plain_scale_down on the same L = --qcount slabs (the scratch the operand:
+    any words serve as the next call's input) and a copy of their kernel's 8 (L + 1) bytes per coefficient.  The permutation kernel has no call of its own:
+    its time is encode less the inverse, or decode less the forward, a difference of two medians.  The other gather side (scattered writes) is a library of
+    its own, built with EXTRA=-DAGX_BATCH_SCATTER and loaded through AGX_NTT_LIB: run this op once per library, alternating.  Prints us per call: median
+    (min ... max)."""
+    import statistics
+
+    L, n, batch, t = args.qcount, args.n, args.batch, 65537
+    words = batch * n
+    bt = agx.Batch(n, t)
+    inner = bt.plan()
+    z = torch.randint(0, 1 << 62, (words,), dtype=torch.int64, device="cuda")
+    m, back = torch.empty_like(z), torch.empty_like(z)
+    c_src, c_dst = torch.empty_like(z), torch.empty_like(z)      # a copy reads and writes 8 bytes per word: the permutation's 16 n per frame
+    pt = plan.plain(0, L, L, t)
+    x = torch.empty(L * words, dtype=torch.int64, device="cuda")
+    plan.sample_uniform(bytes(range(32)), 0, x.data_ptr(), batch, 0, 0, L, stream)
+    half = (L + 1) * words // 2
+    r_src, r_dst = (torch.empty(half, dtype=torch.int64, device="cuda") for _ in range(2))
+    bt.encode(z.data_ptr(), m.data_ptr(), batch, stream)
+
+    def encode():
+        bt.encode(z.data_ptr(), m.data_ptr(), batch, stream)
+
+    def decode():
+        bt.decode(m.data_ptr(), back.data_ptr(), m.data_ptr(), batch, stream)
+
+    def inner_inverse():
+        agx._check(agx.lib().agx_ntt_inverse(inner, m.data_ptr(), m.data_ptr(), batch, stream), "inverse")
+
+    def inner_forward():
+        agx._check(agx.lib().agx_ntt_forward(inner, m.data_ptr(), m.data_ptr(), batch, stream), "forward")
+
+    def copy():
+        c_dst.copy_(c_src)
+
+    def reduce():
+        pt.reduce(x.data_ptr(), back.data_ptr(), x.data_ptr(), batch, 3, stream)
+
+    def scale_down():
+        pt.scale_down(x.data_ptr(), back.data_ptr(), x.data_ptr(), batch, stream)
+
+    def inverse():
+        plan.inverse_range(x.data_ptr(), x.data_ptr(), batch, 0, L, stream)
+
+    def copy_rows():
+        r_dst.copy_(r_src)
+
+    times = _alternate([encode, decode, inner_inverse, inner_forward, copy, reduce, scale_down, inverse, copy_rows])
+    info = bt.info()
+    print(f"batch n={n} t={t} batch={batch} launches encode {info[3]} decode {info[4]}; plain_reduce l={L} bits={args.bits}:")
+    for name, v in times.items():
+        print(f"  {name} {_fmt(v)} us")
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(f"  (encode - inner_inverse)/copy {(med['encode'] - med['inner_inverse']) / med['copy']:.3f}  (decode - inner_forward)/copy {(med['decode'] - med['inner_forward']) / med['copy']:.3f};  "
+          f"encode/(inner_inverse + copy) {med['encode'] / (med['inner_inverse'] + med['copy']):.3f}  decode/(inner_forward + copy) {med['decode'] / (med['inner_forward'] + med['copy']):.3f};  "
+          f"reduce/scale_down {med['reduce'] / med['scale_down']:.3f}  (reduce - inverse)/copy_rows {(med['reduce'] - med['inverse']) / med['copy_rows']:.3f}")
+    if args.report:
+        import json
+
+        json.dump({"us": times, "launches": args.launches, "kernel_launches": {"encode": info[3], "decode": info[4]}}, open(args.report, "w"))
+    pt.close()
+    bt.close()
     plan.close()
 
 
@@ -1138,6 +1211,9 @@ if args.op == "sample":
     sys.exit(0)
 if args.op == "ckks":
     run_ckks()
+    sys.exit(0)
+if args.op == "batch":
+    run_batch()
     sys.exit(0)
 slabs = [torch.empty(per, dtype=torch.int64, device="cuda") for _ in range(args.slabs)]
 for i, s in enumerate(slabs):
