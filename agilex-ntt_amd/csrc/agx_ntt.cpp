@@ -1,6 +1,6 @@
 // agx_ntt.cpp -- the extern "C" boundary declared in include/agx_ntt.h: plans and the transform and product calls.
 // Owns plan objects (device tables, the routes from a call to its kernel), their argument validation and the mapping of HIP errors to
-// status codes.  The RNS calls composed of these live in agx_rns.cpp, the steps and rules both share in plan_internal.hpp; kernels in
+// status codes.  The RNS calls composed of these live in agx_basis.cpp, agx_ring.cpp, agx_keyswitch.cpp and agx_boundary.cpp, the steps and rules all share in plan_internal.hpp; kernels in
 // ntt_kernels.hip and the registry groups; number theory in host_math.cpp; host-resident frames in agx_host.cpp.
 #include "../../include/agx_ntt.h"
 
@@ -508,8 +508,8 @@ int agx_ntt_inverse(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_
 // rule right behind the NULL rule; then the plan's route for this batch viewed on the range, as the RNS calls run it
 static int range_call(bool inverse, const agx_ntt_plan* plan, const uint64_t* d_in, uint64_t* d_out, uint64_t batch, uint32_t first, uint32_t count, void* stream) {
     if (!plan || !d_in || !d_out) return AGX_ERR_NULL_POINTER;
-    const uint32_t P = plan->num_primes, n = plan->n;
-    if (count == 0 || count > P || first > P - count) return AGX_ERR_BAD_ARGUMENT;
+    const uint32_t n = plan->n;
+    if (!primes_in_plan(plan, first, count)) return AGX_ERR_BAD_ARGUMENT;
     if (int rc = check_plan(plan)) return rc;
     const frame_layout fl = dense(plan, batch);
     if (!aligned8(d_in) || !batch_fits_grid(plan, batch) || !layout_fits(n, count, batch, fl.prime_stride, fl.poly_stride)) return AGX_ERR_BAD_ARGUMENT;
@@ -517,8 +517,8 @@ static int range_call(bool inverse, const agx_ntt_plan* plan, const uint64_t* d_
     if (inverse && !plan->has_inverse) return AGX_ERR_NO_INVERSE;
     if (batch == 0) return AGX_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (inverse) AGX_HIP(run_inverse(prime_range(plan->routes.inverse, first, first + count), d_in, nullptr, d_out, fl, s));
-    else AGX_HIP(run_forward(prime_range(forward_route(plan, batch), first, first + count), d_in, d_out, fl, s));
+    if (inverse) AGX_HIP(run_inverse_on(plan, first, count, nullptr, d_in, d_out, batch, s));
+    else AGX_HIP(run_forward_on(plan, first, count, d_in, d_out, batch, s));
     return AGX_OK;
 }
 
@@ -604,7 +604,7 @@ int agx_ntt_automorphism(const agx_ntt_plan* plan, const uint64_t* d_in, uint64_
     int rc = check_plan(plan);
     if (rc || (rc = check_frames(plan, d_in, dense(plan, batch)))) return rc;
     if (!aligned8(d_out)) return AGX_ERR_BAD_ARGUMENT;
-    if (!galois_ok(galois_elt, plan->n) || (form != AGX_FORM_COEFF && form != AGX_FORM_NTT)) return AGX_ERR_BAD_ARGUMENT;
+    if (!galois_ok(galois_elt, plan->n) || !form_ok(form)) return AGX_ERR_BAD_ARGUMENT;
     // out of place only, equal pointers included: a frame is permuted across its whole length and workgroups run in any order
     if (d_out == d_in || ranges_touch(addr(d_in), dense_words(plan, batch), addr(d_out), dense_words(plan, batch))) return AGX_ERR_BAD_ARGUMENT;
     if (batch == 0) return AGX_OK;

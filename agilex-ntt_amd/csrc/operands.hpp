@@ -91,4 +91,14 @@ inline bool down_buffers_ok(uintptr_t xq, uint64_t qwords, uintptr_t xp, uint64_
     return scratch == xp || !ranges_touch(scratch, pwords, xp, pwords);
 }
 
+// The buffer rule of the calls that transform x (x_words words) into a scratch of as many words and stream out (out_words words) from it:
+// agx_ntt_basis_quotient, agx_ntt_plain_scale_down / _reduce, agx_ntt_ckks_decode from NTT form and agx_ntt_batch_decode.  Dense sets, one range each.
+//   the scratch IS x (the plan's inverse -- batch_decode's forward -- then runs in place, as agx_ntt_inverse may) or touches none of it: every
+//   workgroup of the transform reads its frame of x before it writes the scratch's, but no other frame's;
+//   out touches neither: the streaming kernel reads the scratch while other workgroups already write out, and the first launch reads x.
+inline bool scratch_buffers_ok(uintptr_t x, uint64_t x_words, uintptr_t scratch, uintptr_t out, uint64_t out_words) {
+    if (scratch != x && ranges_touch(scratch, x_words, x, x_words)) return false;
+    return !ranges_touch(out, out_words, x, x_words) && !ranges_touch(out, out_words, scratch, x_words);
+}
+
 }  // namespace agx

@@ -1,5 +1,5 @@
-// plan_internal.hpp -- what agx_ntt.cpp (plans, transform and product calls), agx_rns.cpp (the RNS calls composed of them) and agx_group.cpp
-// (multi-device groups) share.  Host only: no device unit includes it.  Not installed; the public surface is include/agx_ntt.h.
+// plan_internal.hpp -- what agx_ntt.cpp (plans, transform and product calls), the units of the RNS calls composed of them (agx_basis.cpp, agx_ring.cpp,
+// agx_keyswitch.cpp, agx_boundary.cpp) and agx_group.cpp (multi-device groups) share.  Host only: no device unit includes it.  Not installed; the public surface is include/agx_ntt.h.
 #pragma once
 #include "../../include/agx_ntt.h"
 
@@ -116,7 +116,7 @@ struct agx_ntt_plan {
 
 // agx_ntt_basis_extend: the constants of one (plan, source range, target range) on the plan's device, and nothing of the plan but a pointer --
 // the kernels come from the plan's routes at every call, so agx_ntt_plan_set_variant between calls stays legal.  The plan outlives the basis.
-// Made from a basis_image (host_math.hpp, whose fields say what each buffer holds) by one function of agx_rns.cpp, which also fills the two views, once:
+// Made from a basis_image (host_math.hpp, whose fields say what each buffer holds) by one function of agx_basis.cpp, which also fills the two views, once:
 // a call hands them to its kernel as they are.  The ranges live in `view`; m and the two k of the auxiliary forms in `aux` only.
 struct agx_ntt_basis {
     const agx_ntt_plan* plan = nullptr;
@@ -152,7 +152,7 @@ struct agx_ntt_basis {
 
 // agx_ntt_plain_*: the constants of one plaintext boundary (plan, Q, gamma, t) on the plan's device, and nothing of the plan but a pointer, as a basis: the
 // plan outlives the handle, agx_ntt_plan_set_variant between calls stays legal.  Made from a plain_image (host_math.hpp, whose fields say what each buffer
-// holds) by one function of agx_rns.cpp, which also fills the view, once.  d_src_consts: the plan's prime_consts of the Q primes with the last-stage factors
+// holds) by one function of agx_boundary.cpp, which also fills the view, once.  d_src_consts: the plan's prime_consts of the Q primes with the last-stage factors
 // replaced by the image's sn, sw, as a basis' d_src_consts: the plan's inverse on the view of Q with `consts` pointing here writes the y_i of scale_down.
 struct agx_ntt_plain {
     const agx_ntt_plan* plan = nullptr;
@@ -174,12 +174,12 @@ struct agx_ntt_batch {
     agx_ntt_batch() = default;
     agx_ntt_batch(const agx_ntt_batch&) = delete;
     agx_ntt_batch& operator=(const agx_ntt_batch&) = delete;
-    ~agx_ntt_batch();      // agx_rns.cpp: the plan goes with its owner
+    ~agx_ntt_batch();      // agx_boundary.cpp: the plan goes with its owner
 };
 
 // agx_ntt_ckks_*: the tables of one CKKS boundary (plan, the primes [q_first, q_first + q_count)) on the plan's device, and nothing of the plan but a pointer,
 // as a basis: the plan outlives the handle, agx_ntt_plan_set_variant between calls stays legal.  Made from a ckks_image (host_math.hpp, whose fields say what
-// each buffer holds) by one function of agx_rns.cpp, which also fills the view, once.
+// each buffer holds) by one function of agx_boundary.cpp, which also fills the view, once.
 struct agx_ntt_ckks {
     const agx_ntt_plan* plan = nullptr;
     agx::device_buf<double2> d_tw;
@@ -273,7 +273,8 @@ int check_create_args(uint32_t n, uint32_t num_primes, const uint64_t* moduli, c
 int build_plan(agx_ntt_plan** out, uint32_t n, uint32_t num_primes, const uint64_t* moduli, const uint64_t* psi,
                const uint64_t* tw, const uint64_t* pre, const uint64_t* itw, const uint64_t* ipre);
 
-// ---- what the entry points of agx_ntt.cpp and agx_rns.cpp share: each launch step and each frame rule once ----
+// ---- what the entry points of agx_ntt.cpp and of the RNS units (agx_basis.cpp, agx_ring.cpp, agx_keyswitch.cpp, agx_boundary.cpp) share: each launch
+// step, each frame rule and each argument rule once ----
 
 // The plan's forward / inverse on the frames a route views: the route's registry entry, or the radix-2 kernels.  in2 != null (the product in * in2
 // is transformed) only with an entry.
@@ -298,11 +299,53 @@ inline uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); } 
 inline bool aligned8(const void* p) { return (addr(p) & 7u) == 0; }      // uint64_t data
 inline bool galois_ok(uint32_t g, uint32_t n) { return (g & 1u) && g < 2u * n; }      // a Galois element: odd, in [1, 2n)
 inline bool batch_fits_grid(const agx_ntt_plan* plan, uint64_t batch) { return batch <= (0x7fffffffull >> (plan->log_n > 14 ? plan->log_n - 14 : 0)); }      // grid.x limit (the radix-2 kernels split n = 32768 in two blocks)
+inline bool dense_fits(uint32_t n, uint32_t slabs, uint64_t frames) { return layout_fits(n, slabs, frames, (int64_t)(frames * n), (int64_t)n); }      // one dense range of slabs x frames x n words (formed in 128 bits)
+// The argument rules every family states, each as the calls wrote it, negated: a range of at least one of the plan's primes (first + count is never formed),
+// a form and a rounding mode of include/agx_ntt.h
+inline bool primes_in_plan(const agx_ntt_plan* plan, uint32_t first, uint32_t count) { const uint32_t P = plan->num_primes; return !(count == 0 || count > P || first > P - count); }
+inline bool form_ok(int form) { return !(form != AGX_FORM_COEFF && form != AGX_FORM_NTT); }
+inline bool mode_ok(int mode) { return !(mode != AGX_RESCALE_FLOOR && mode != AGX_RESCALE_ROUND); }
 
 // The dense [prime][batch][n] layout of a plan, for the checks and the launches alike.  Nothing is multiplied for a batch past the grid
 // limit, which check_frames refuses before it looks at a stride: batch * n stays below 2^46.
 inline frame_layout dense(const agx_ntt_plan* plan, uint64_t batch) { return frame_layout{batch, batch_fits_grid(plan, batch) ? (int64_t)(batch * plan->n) : 0, (int64_t)plan->n}; }
 inline uint64_t dense_words(const agx_ntt_plan* plan, uint64_t batch) { return plan->num_primes * batch * plan->n; }      // of a bounded batch: < 2^62
+
+// The plan's forward / inverse on the view of primes [first, first + count), dense frames: what every RNS call and agx_ntt_{forward,inverse}_range run.
+// The forward takes the route forward_route chooses for this batch on the WHOLE plan (batch x the plan's primes against min_frames, not the range's).
+// consts null: the plan's own constants; else a handle's scaled constants (scaled_consts below), already at the range's first prime as prime_range
+// leaves the plan's: every inverse family reads its last-stage factors there.
+inline hipError_t run_forward_on(const agx_ntt_plan* plan, uint32_t first, uint32_t count, const uint64_t* in, uint64_t* out, uint64_t batch, hipStream_t s) {
+    return run_forward(prime_range(forward_route(plan, batch), first, first + count), in, out, dense(plan, batch), s);
+}
+inline hipError_t run_inverse_on(const agx_ntt_plan* plan, uint32_t first, uint32_t count, const prime_consts* consts, const uint64_t* in, uint64_t* out, uint64_t batch,
+                                 hipStream_t s) {
+    route r = prime_range(plan->routes.inverse, first, first + count);
+    if (consts) r.consts = consts;
+    return run_inverse(r, in, nullptr, out, dense(plan, batch), s);
+}
+
+// ---- what the handles made from a host image (bases, agx_boundary.cpp's) share ----
+
+// The plan's prime_consts of primes [first, first + count) with the inverse's last-stage factors (n_inv, w1n and their quotients) replaced by sn, sw
+// ([count] each): what run_inverse_on takes as `consts`
+inline std::vector<prime_consts> scaled_consts(const agx_ntt_plan* plan, uint32_t first, uint32_t count, const shoup_pair* sn, const shoup_pair* sw) {
+    std::vector<prime_consts> c(plan->consts.begin() + first, plan->consts.begin() + first + count);
+    for (uint32_t i = 0; i < count; ++i) c[i].n_inv = sn[i].w, c[i].n_inv_p = sn[i].p, c[i].w1n = sw[i].w, c[i].w1n_p = sw[i].p;
+    return c;
+}
+
+// the unscaled factors of the same range, as the image requests of host_math.hpp take them
+inline void inverse_factors(const agx_ntt_plan* plan, uint32_t first, uint32_t count, std::vector<uint64_t>& n_inv, std::vector<uint64_t>& w1n) {
+    n_inv.resize(count), w1n.resize(count);
+    for (uint32_t i = 0; i < count; ++i) n_inv[i] = plan->consts[first + i].n_inv, w1n[i] = plan->consts[first + i].w1n;
+}
+
+// One upload of a handle's list: skipped once an earlier one has failed, so rc keeps the first failure and the list ends in one `if (rc) return rc;`.
+// The order of the list is the allocation order on the device.
+template <class T>
+inline void upload_next(int& rc, device_buf<T>& to, const std::vector<T>& from) { if (rc == AGX_OK) rc = to.upload(from); }
+inline void upload_next(int& rc, device_buf<ulonglong2>& to, const std::vector<shoup_pair>& pairs) { if (rc == AGX_OK) rc = upload_pairs(to, pairs); }
 
 // Frame-set rule: the plan's frames in layout fl at `base`.  Batch first, then layout_fits: nothing after them can overflow (operands.hpp).
 inline int check_frames(const agx_ntt_plan* plan, const void* base, const frame_layout& fl) {

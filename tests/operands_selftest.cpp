@@ -148,10 +148,44 @@ static uint64_t down_buffers_grid() {
     return cases;
 }
 
+// The scratch rule of agx_ntt_basis_quotient, agx_ntt_plain_scale_down / _reduce, agx_ntt_ckks_decode and agx_ntt_batch_decode as those calls spelled it out
+// before scratch_buffers_ok stated it once.  true = the call goes on, false = AGX_ERR_BAD_ARGUMENT.
+static bool scratch_rule_as_written(uintptr_t x, uintptr_t scratch, uintptr_t out, uint64_t x_words, uint64_t out_words) {
+    if (scratch != x && ranges_touch(scratch, x_words, x, x_words)) return false;
+    if (ranges_touch(out, out_words, x, x_words) || ranges_touch(out, out_words, scratch, x_words)) return false;
+    return true;
+}
+
+// scratch_buffers_ok against it, every placement: x and the scratch of 0 .. 6 words, out of 0 .. 3, every base on a grid of 14 words (equal bases,
+// adjacency and every partial overlap occur); then by hand: the scratch that IS x, empty ranges, ranges ending at the top of the address space.
+static uint64_t scratch_buffers_grid() {
+    const uintptr_t base = (uintptr_t)1 << 40;
+    const int grid = 14;
+    uint64_t cases = 0;
+    auto at = [&](int w) { return base + 8 * (uintptr_t)w; };
+    for (uint64_t x_words : {0, 1, 2, 3, 4, 6})
+        for (uint64_t out_words = 0; out_words <= 3; ++out_words)
+            for (int x = 0; x < grid; ++x)
+                for (int scratch = 0; scratch < grid; ++scratch)
+                    for (int out = 0; out < grid; ++out, ++cases)
+                        CHECK(scratch_buffers_ok(at(x), x_words, at(scratch), at(out), out_words) == scratch_rule_as_written(at(x), at(scratch), at(out), x_words, out_words));
+    const uintptr_t a = 0x1000;
+    CHECK(scratch_buffers_ok(a, 4, a, a + 32, 2) && scratch_buffers_ok(a, 4, a, a - 16, 2));      // in place, out adjacent on either side
+    CHECK(!scratch_buffers_ok(a, 4, a, a + 24, 2) && !scratch_buffers_ok(a, 4, a, a, 2) && !scratch_buffers_ok(a, 4, a, a - 8, 2));      // out on the shared words
+    CHECK(!scratch_buffers_ok(a, 4, a + 8, a + 64, 2) && !scratch_buffers_ok(a, 4, a - 24, a + 64, 2));      // a scratch that straddles x
+    CHECK(scratch_buffers_ok(a, 4, a + 32, a + 64, 2) && !scratch_buffers_ok(a, 4, a + 32, a + 56, 2) && !scratch_buffers_ok(a, 4, a + 32, a + 16, 2));      // apart; out on the scratch, on x
+    CHECK(scratch_buffers_ok(a, 0, a + 8, a, 2) && scratch_buffers_ok(a, 4, a + 32, a + 8, 0) && scratch_buffers_ok(a, 0, a, a, 0));      // empty ranges touch nothing
+    const uintptr_t last = ~(uintptr_t)0 - 7;      // the last aligned word of the address space: a range ending there does not wrap
+    CHECK(scratch_buffers_ok(last - 24, 4, last - 56, 0, 2) && scratch_buffers_ok(0, 2, 16, last - 24, 4));
+    CHECK(!scratch_buffers_ok(last - 24, 4, last - 56, last, 1) && !scratch_buffers_ok(last - 24, 4, last - 48, 0, 2) && scratch_buffers_ok(last - 24, 4, last - 24, 0, 2));
+    return cases;
+}
+
 int main() {
     const uint64_t cases = brute_force_grid();
     std::printf("brute force: %" PRIu64 " cases\n", cases);
     std::printf("down_buffers_ok: %" PRIu64 " placements\n", down_buffers_grid());
+    std::printf("scratch_buffers_ok: %" PRIu64 " placements\n", scratch_buffers_grid());
     layout_fits_limits();
     largest_shapes();
     ranges();

@@ -292,6 +292,7 @@ def test_statuses_in_their_order_and_nothing_written(agx, orc, dev):
     assert status_of(agx, dec, W, NTT, 3, scale, Z, s, None, batch) == 1      # NTT form needs its scratch
     assert status_of(agx, enc, Z, s, scale, W, 0, 3, NTT) == 0 and status_of(agx, dec, W, NTT, 3, scale, Z, s, W2, 0) == 0      # batch 0: nothing launched
     assert status_of(agx, dec, W, COEFF, 3, scale, Z, s, W + 8, batch) == 0      # coefficient form never looks at the scratch ...
+    assert status_of(agx, dec, W, COEFF, 3, scale, Z, s, W2 + 4, batch) == 0 and status_of(agx, dec, W, COEFF, 3, scale, Z, s, None, batch) == 0      # ... misaligned or NULL
     dev.sync()
     assert np.array_equal(dev.to_host(d_w), canary(0, words + 16)) and np.array_equal(dev.to_host(d_w2), canary(1, words + 16))
     assert np.all(dd.get(d_z)[2 * batch * s:] == -7.25), "the guard band behind d_z was written"      # ... and wrote the slots of its one legal call only

@@ -28,4 +28,8 @@ def test_operand_predicates_against_brute_force_and_at_the_limits(tmp_path):
     # bases (1..3 source slabs) resp. rescale's three on a grid of 14 words: 4 * 3 * (3 * 14**4 + 14**3) placements
     m = re.search(r"down_buffers_ok: (\d+) placements", run.stdout)
     assert m and int(m.group(1)) == 4 * 3 * (3 * 14**4 + 14**3) == 1415904
+    # scratch_buffers_ok against the rule agx_ntt_basis_quotient, agx_ntt_plain_scale_down / _reduce, agx_ntt_ckks_decode and agx_ntt_batch_decode used to spell
+    # out: x and the scratch of 0, 1, 2, 3, 4 or 6 words, out of 0..3, three bases on a grid of 14 words
+    m = re.search(r"scratch_buffers_ok: (\d+) placements", run.stdout)
+    assert m and int(m.group(1)) == 6 * 4 * 14**3 == 65856
     assert "ok: 0 failures" in run.stdout
